@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Msamples/s of velvet-noise decorrelation on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 Headline workload (BASELINE.json configs[1], "cfg2"): synthetic 48 kHz stereo float32, 10 s per
 signal, 30 taps over 30 ms (seed 1, the reference generator's defaults).  One cfg2 signal is only
@@ -40,6 +40,9 @@ What is printed where.  stdout carries ONE short JSON line (a few KB): the contr
 descriptions, notes, per-leg records - goes to `bench_detail.json` beside this file (and to `gpurun_out/` when
 that directory exists) and, as one JSON document, to stderr BEFORE the line.
 
+`--dump-outputs DIR` writes the output of the last timed step - a fixed, seeded sample of 16 of rank 0's streams - to
+DIR/convolved.npy; the pool's input is seeded, so two builds run with the same arguments can be compared output for output.
+
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts its own N ranks: the parent -
 which never imports torch or touches a GPU - runs `python -m torch.distributed.run --nproc-per-node N bench.py ...`
 as a CHILD process, relays rank 0's line and exits with the child's code.
@@ -67,6 +70,8 @@ HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec (MI355X_MICROARCH.md)
 FP32_VECTOR_PEAK_TFLOPS = 157.3   # MI355X FP32 vector peak (same guide): what bounds a table of more than ~80 taps per stereo frame
 ALGO_BYTES_PER_SAMPLE = 8      # 4 B read + 4 B written per output channel-sample
 MIN_TIMED_MS = 50.0            # the timed region of the headline must be at least this long
+DUMP_STREAMS = 16              # --dump-outputs: 16 of the pool's 3.84 MB output streams = 61.4 MB, under the 64 MB cap
+DUMP_SEED = 0                  # --dump-outputs: which streams
 
 
 def parse():
@@ -88,6 +93,9 @@ def parse():
     ap.add_argument('--detail', default=None, help='where the detail document goes (default: bench_detail.json beside bench.py)')
     ap.add_argument('--variant', type=int, default=-1, help='kernel variant override (tuning)')
     ap.add_argument('--backend', default='nccl', help='torch.distributed backend (nccl = RCCL; gloo for rehearsals)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed to DIR/convolved.npy (float32): a fixed '
+                         f'sample of up to {DUMP_STREAMS} of rank 0\'s output streams, the same ones in every run')
     return ap.parse_args()
 
 
@@ -390,7 +398,7 @@ def end_to_end(torch, vnd, mode) -> dict:
 def audio_leg(torch, vnd, _native, ctx, pool, power=None) -> dict:
     """The path on AUDIO instead of uniform random floats (SURVEY 8d's synthetic input is the worst case for the board's power cap,
     DESIGN.md 3.4): BASELINE configs[0]'s material - the 1 s stereo excerpt of the reference's viola recording kept in
-    tests/golden/golden.npz (`viola_excerpt_in`, 44.1 kHz; /root/reference/tests/test_example.py:19-49 runs the whole file) - tiled to
+    tests/golden/golden.npz (`viola_excerpt_in`, 44.1 kHz; the reference's tests/test_example.py:19-49 runs the whole file) - tiled to
     the headline pool's shape (as many streams, as many frames), every stream starting at another frame of the excerpt; the table
     is that test's (20 ms, 30 impulses, seed 1).  Fast and exact kernels, three streams of each against the C oracle."""
     from vndecorrelate_amd.taps import function_path_arrays
@@ -952,6 +960,18 @@ def compact(d: dict) -> dict:
     return line
 
 
+def dump_outputs(out_dir, torch, y) -> None:
+    """--dump-outputs: the timed path's output of its last step, on a seeded sample of the pool's streams (in pool order), so that
+    two builds run with the same arguments can be compared array for array.  The pool's input is seeded too (1234 + rank)."""
+    pool = y.shape[0]
+    streams = np.sort(np.random.default_rng(DUMP_SEED).choice(pool, size=min(pool, DUMP_STREAMS), replace=False))
+    sample = y[torch.from_numpy(streams).to(y.device)].cpu().numpy()
+    out = pathlib.Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    np.save(out / 'convolved.npy', sample)
+    print(f'bench.py: wrote {out / "convolved.npy"}: {sample.shape} {sample.dtype}, streams {streams.tolist()} of {pool}', file=sys.stderr)
+
+
 def main():
     args = parse()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ and 'RANK' not in os.environ:
@@ -1052,6 +1072,8 @@ def main():
     timed_ms = elapsed * 1e3
     checked = sorted({0, args.pool // 2, args.pool - 1})      # first, middle, last stream (the last: past 4 GiB of offsets)
     y_timed = {b: y[b].cpu().numpy() for b in checked} if rank == 0 else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, y)
 
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device if args.backend == 'nccl' else 'cpu')

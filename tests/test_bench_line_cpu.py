@@ -99,3 +99,21 @@ def test_plain_gpus_n_starts_its_own_ranks(monkeypatch, capsys):
     assert seen['kw']['env']['HSA_ENABLE_IPC_MODE_LEGACY'] == '0'
     out = capsys.readouterr()
     assert out.out == '{"metric": "m", "value": 1}\n' and 'chatter' in out.err
+
+
+def test_dump_outputs_is_a_fixed_sample_under_the_cap(tmp_path):
+    """--dump-outputs: the same streams in every run, float32, at most 64 MB for the bench's 10 s stereo streams."""
+    import numpy as np
+    import torch
+    import bench
+    y = torch.arange(100 * 3 * 2, dtype=torch.float32).reshape(100, 3, 2)
+    bench.dump_outputs(tmp_path / 'a', torch, y)
+    bench.dump_outputs(tmp_path / 'b', torch, y)
+    a, b = np.load(tmp_path / 'a' / 'convolved.npy'), np.load(tmp_path / 'b' / 'convolved.npy')
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_STREAMS, 3, 2) and np.array_equal(a, b)
+    streams = a[:, 0, 0] / 6
+    assert np.all(np.diff(streams) > 0)                                # distinct streams, in pool order, copied whole
+    assert np.array_equal(a, y.numpy()[streams.astype(int)])
+    assert bench.DUMP_STREAMS * bench.SAMPLE_RATE * bench.SECONDS * bench.CHANNELS * 4 <= 64e6
+    bench.dump_outputs(tmp_path / 'c', torch, y[:5])                   # a pool smaller than the sample: all of it
+    assert np.array_equal(np.load(tmp_path / 'c' / 'convolved.npy'), y[:5].numpy())

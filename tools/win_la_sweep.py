@@ -1,5 +1,5 @@
 import os, sys, time
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ['VND_TUNING'] = '1'
 import numpy as np, torch
 import vndecorrelate_amd.decorrelation as vnd

@@ -1,5 +1,5 @@
 import os, sys
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ['VND_SPEC_VERBOSE'] = '1'
 import numpy as np
 os.environ.setdefault('VND_TUNING', '1')      # geometry variables are read live
