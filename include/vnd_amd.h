@@ -247,6 +247,27 @@ vnd_status vnd_haas_f64_host(vnd_ctx *ctx, const float *x, double *y, int64_t ba
                              int32_t in_channels, int32_t delay_frames, int32_t delayed_channel,
                              int32_t ms_mode, int32_t use_width, double width);
 
+/* ---- WhiteNoise on the device: the dense float64 FIR and its stage ---------------
+ * Replaces WhiteNoise.decorrelate after its float32 cast / mono->stereo (decorrelation.py:684-706):
+ *   y[b,n,c] = np.convolve(x[b,:,c'], h[:,c], mode='same')[n]     c' = c, or 0 when in_channels = 1
+ *            = sum over k (0 <= n+o-k < n_frames) of h[k,c] * x[b, n+o-k, c'],   o = (fir_length - 1) / 2
+ * then in place on y: use_width -> apply_stereo_width(y, width) (utils/dsp.py:21-37, 2 channels), normalize ->
+ * rms_normalize(x, y) DUAL_MONO (utils/dsp.py:87-109; VND_NORMALIZE_RMS and _REFERENCE_ORDER both take NumPy's own order
+ * of the sums of squares, as the exact velvet-noise stage does).  x is float32 [batch][n_frames][in_channels]
+ * (in_channels = n_channels, or 1 with n_channels = 2: mono_to_stereo without the copy), h FLOAT64 [fir_length][n_channels]
+ * as upstream, y float32 [batch][n_frames][n_channels]; device pointers, no overlap; n_frames >= fir_length >= 1;
+ * `workspace` as for vnd_decorrelate_f32_dev (vnd_decorrelate_workspace_bytes; unused when normalize = OFF).
+ * Numerics: NumPy forms each output as a float64 dot product of the exactly promoted signal and rounds it once to float32;
+ * here each output is one float64 FMA chain over k = 0 .. fir_length-1 ascending, rounded once.  NumPy's float64 summation
+ * order follows the host's BLAS kernel, so the contract is per output: |y - y_numpy| <= ulp_f32(|y_numpy|) + 2^-40 * sum_k
+ * |h[k] x[n+o-k]|; where the float32 convolution outputs agree, the whole stage is bit-identical.  The order here is fixed per
+ * output: results are bit-identical across batch sizes, stream positions and runs.  A non-finite h is not covered (0 * h
+ * padding); non-finite x propagates as in NumPy.  normalize = OFF with use_width = 0 is the bare convolution. */
+vnd_status vnd_white_noise_f32_dev(vnd_ctx *ctx, const float *x_dev, const double *h_dev, float *y_dev,
+                                   int64_t batch, int64_t n_frames, int32_t in_channels, int32_t n_channels,
+                                   int32_t fir_length, int32_t use_width, double width, int32_t normalize,
+                                   float eps, void *workspace_dev, int64_t workspace_bytes, void *hip_stream);
+
 /* ---- host staging memory ---------------------------------------------------------
  * The reference returns a freshly allocated array from every call (out = np.zeros(...),
  * decorrelation.py:647).  A fresh pageable buffer costs a page fault per 4 KiB and a staged,

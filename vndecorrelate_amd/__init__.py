@@ -22,4 +22,5 @@ from .decorrelation import (  # noqa: F401
     generate_velvet_noise,
     set_default_mode,
     set_device_epilogue,
+    set_white_noise_device,
 )

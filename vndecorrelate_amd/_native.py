@@ -102,6 +102,10 @@ SIGNATURES = {
     'vnd_convolve_promote_host': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_i32p, _c_i32p,
                                                  ctypes.POINTER(ctypes.c_double), ctypes.c_void_p, ctypes.c_int32,
                                                  _c_f32p, ctypes.c_int64, ctypes.c_int64]),
+    'vnd_white_noise_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                               ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
+                                               ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     'vnd_host_alloc': (ctypes.c_int, [ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p)]),
     'vnd_host_buffers_mapped': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
                                                ctypes.POINTER(ctypes.c_int32)]),
@@ -590,6 +594,17 @@ def haas_device(ctx: 'Context', x_ptr: int, y_ptr: int, batch: int, n: int, chan
     _check(ctx._lib.vnd_haas_f64_dev(ctx.handle, ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr), batch, n, channels,
                                      int(delay), int(delayed_channel), int(bool(ms_mode)), int(width is not None),
                                      float(width or 0.0), ctypes.c_void_p(stream)), 'vnd_haas_f64_dev')
+
+
+def white_noise_device(ctx: 'Context', x_ptr: int, h_ptr: int, y_ptr: int, batch: int, n: int, in_channels: int,
+                       channels: int, fir_length: int, *, width, normalize: int, workspace_ptr: int = 0,
+                       workspace_bytes: int = 0, eps: float = 1e-10, stream: int = 0):
+    """``vnd_white_noise_f32_dev``: WhiteNoise's dense float64 FIR (+ width, + normaliser) on device buffers, enqueued on
+    ``stream``.  x float32 ``(batch, n, in_channels)``, h float64 ``(fir_length, channels)``, y float32 ``(batch, n, channels)``."""
+    _check(ctx._lib.vnd_white_noise_f32_dev(ctx.handle, ctypes.c_void_p(x_ptr), ctypes.c_void_p(h_ptr), ctypes.c_void_p(y_ptr),
+                                            batch, n, in_channels, channels, fir_length, int(width is not None),
+                                            float(width or 0.0), int(normalize), float(eps), ctypes.c_void_p(workspace_ptr),
+                                            workspace_bytes, ctypes.c_void_p(stream)), 'vnd_white_noise_f32_dev')
 
 
 def polar_moments_workspace_bytes(n: int, pairs: int) -> int:

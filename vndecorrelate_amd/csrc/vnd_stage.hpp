@@ -25,6 +25,154 @@ vnd_status vnd_decorrelate_workspace_bytes(int64_t batch, int64_t n, int32_t C, 
     return VND_OK;
 }
 
+// The epilogue's arguments and the form of its normaliser sums, as the convolution leaves them to it: shared by the
+// velvet-noise stage (decorrelate_dev) and the dense-FIR stage (vnd_dense.hpp, whose float64 FIR counts as the exact mode).
+struct StageSetup {
+    EArgs e;
+    RArgs r;
+    dim3 grid;
+    int seq_frames;
+    bool want_seq, par_ok, par_forced, want_blk;
+};
+
+static StageSetup stage_setup(vnd_ctx *ctx, const float *x, float *y, int64_t batch, int64_t n, int32_t Cx, int32_t C,
+                              int32_t mode, int32_t ms_encode, int32_t use_width, double width, int32_t normalize, float eps,
+                              void *workspace)
+{
+    StageSetup s{};
+    EArgs &e = s.e;
+    RArgs &r = s.r;
+    e.x = x; e.y = y; e.partials = (double *)workspace; e.n = n; e.C = C; e.Cx = Cx;
+    e.scales = (float *)((double *)workspace + batch * epi_rows_max(n) * 2 * C);
+    e.ms_encode = ms_encode ? 1 : 0; e.use_width = use_width ? 1 : 0;
+    e.w_mid = (float)(1.0 - width); e.w_side = (float)width;   // float32(python float), as NumPy's in-place multiply
+    e.normalize = normalize ? 1 : 0; e.eps = eps;
+    e.wide = (((uintptr_t)y & 15) == 0 && ((uintptr_t)x & (Cx == 1 ? 7 : 15)) == 0 && (batch == 1 || n % 2 == 0) && spec_env("VND_EPI_WIDE", 1) != 0) ? 1 : 0;
+    // (wide == 2, the block-parallel sums' staging: a wave's 16-byte accesses on consecutive bytes instead of 32 consecutive bytes per
+    //  lane as two accesses - interleaved A/B at 128 / 64 / 32 streams: stereo +1 ... 3 %, mono +3 ... 10 %, the quads of a wider signal
+    //  441 -> 348 us (tools/stage_coalesced_ab.py).  The per-stream kernel of pools of 256 streams and more keeps its own mapping:
+    //  it measured slower with this one - see epilogue_rms_seq_kernel)
+    const int wide_par = e.wide ? (spec_env("VND_EPI_PAR_COALESCED", 1) != 0 ? 2 : 1) : 0;
+    s.grid = dim3((unsigned)epi_chunks(n), (unsigned)batch);
+
+    // normalize == VND_NORMALIZE_RMS_REFERENCE_ORDER: the sums of squares in NumPy's own (sequential
+    // float32) order in every mode, so that the scale differs from the reference's only through y
+    // frames per staged block of the sums kernel: as many as the 2C rows of squares leave room for
+    const int seq_frames = C == 2 ? kSeqFramesStereo
+                         : ((size_t)2 * C * kSeqFrames * sizeof(float) <= (size_t)ctx->lds_limit ? kSeqFrames : kSeqFramesWide);
+    const bool seq_ok = normalize && C >= 2 && 2 * C <= 64 &&
+                        (size_t)2 * C * seq_frames * sizeof(float) <= (size_t)ctx->lds_limit;
+    // a single-channel table: NumPy sums that array pairwise (rms_pairwise_kernel); the flow is the same
+    const bool pair_ok = normalize && C == 1 && Cx == 1;
+    const bool want_seq = (seq_ok || pair_ok) && (mode == VND_MODE_EXACT || normalize == VND_NORMALIZE_RMS_REFERENCE_ORDER);
+    // stereo: the reference-order sums parallel over the stream's 2048-frame blocks (vnd_epilogue.hpp, rms_par_*).  They start from
+    // per-block sums of squares (predictions of the running sum's binade) - which the window kernel's store phase leaves on its way
+    // (x still in the ring, the finished y in registers: EpiFuse::blk_sum) where that kernel runs; rms_par_sum_kernel reads both
+    // arrays for them otherwise.  Which form, by batch (tools/rms_batch_rate.py, 10 s signals, ms per stage: per-stream / block-parallel):
+    //   up to 64 streams the one-workgroup-per-stream kernel leaves most CUs dark (16: 0.49 / 0.17);
+    //   65 .. 255: it still fills less than every CU once (128: 0.80 / 0.82, and 0.66 once the block sums come from the convolution);
+    //   more than 320: it fills the chip by itself and reads the data once instead of twice (1024: 4.43 / 5.0; the switch was at 256 until round 6).
+    // variant bit 19 keeps the per-stream kernel, bit 17 forces the block-parallel form (A/B runs).
+    // Wider signals (round 5): the same kernels channel pair by channel pair - a "stream" of theirs is one pair of a stream (RArgs::pairs),
+    // 8 bytes of every frame.  The per-stream kernel takes 16 workgroups for cfg5's pool of 16 signals (8.7 ms for the stage); the
+    // block-parallel form 16 x 4 pairs x 469 blocks.
+    const int pairs = C / 2;
+    const bool par_ok = want_seq && C % 2 == 0 && (C == 2 || Cx == C) && par_blocks(n) <= kParMaxBlocks && !(ctx->variant >= 0 && ((ctx->variant >> 19) & 1));
+    const bool par_forced = ctx->variant >= 0 && ((ctx->variant >> 17) & 1);
+    if (par_ok) {
+        r.x = x; r.y = y; r.n = n; r.Cx = Cx; r.nblocks = (int32_t)par_blocks(n); r.C = C; r.pairs = pairs;
+        char *extra = (char *)((float *)((double *)workspace + batch * epi_rows_max(n) * 2 * C) + batch * C);
+        extra += (16 - ((uintptr_t)extra & 15)) & 15;
+        r.blk_sum = (double *)extra;
+        r.rec = (ParRec *)(r.blk_sum + batch * pairs * 4 * (int64_t)r.nblocks);
+        r.grp = (ParGrp *)(r.rec + batch * pairs * 4 * (int64_t)r.nblocks);
+        r.first = (float *)(r.grp + batch * pairs * 4 * (int64_t)r.nblocks);
+        r.partials = (double *)workspace;
+        r.prefixed = r.nblocks > kParPrefixBlocks ? 1 : 0;
+        r.wide = wide_par;
+    }
+    // (round 6, with the tally's staging on consecutive bytes: 256 streams 1.27-1.37 -> 1.22-1.25 ms block-parallel; from 384 on the per-stream
+    //  kernel leads, 1.70 against 1.80-1.84 - tools/f1_threshold_try.py, profiles/r06_f1_threshold.txt)
+    const bool want_blk = par_ok && C == 2 && (batch <= 320 || par_forced) && spec_env("VND_EPI_BLOCK_SUMS", 1) != 0;
+    s.seq_frames = seq_frames; s.want_seq = want_seq; s.par_ok = par_ok; s.par_forced = par_forced; s.want_blk = want_blk;
+    return s;
+}
+
+// The normaliser's sums (in NumPy's order where want_seq), then its reduce and scale passes - everything after the
+// convolution and the pointwise steps have been enqueued.
+static vnd_status stage_sums(vnd_ctx *ctx, StageSetup &s, const float *x, const float *y, int64_t batch, int64_t n, int32_t Cx,
+                             int32_t C, int32_t normalize, bool sums_pending, bool blk_done, hipStream_t stream)
+{
+    EArgs &e = s.e;
+    RArgs &r = s.r;
+    const dim3 grid = s.grid;
+    const int seq_frames = s.seq_frames;
+    const bool par_ok = s.par_ok, par_forced = s.par_forced;
+    const int pairs = C / 2;
+    // (wider signals: the per-stream kernel fills the chip from 256 streams on, as for stereo; below that the pairs' blocks do)
+    const bool par_sums = sums_pending && par_ok && (batch <= 64 || par_forced || blk_done || (C > 2 && batch < 256));
+    if (par_sums) {
+        e.rows = 1;
+        e.exact_rms = 1;
+        e.normalize = 1;
+        // (wider signals: the pairs of a block side by side in one XCD's queue - par_unit)
+        // 4k channels with 16-byte-aligned streams: a channel QUAD per workgroup (512 threads, whole 16-byte accesses)
+        const int pw = (pairs > 1 && pairs % 2 == 0 && r.wide) ? 2 : 1;
+        const unsigned gx = pairs == 1 ? (unsigned)r.nblocks : (unsigned)(((r.nblocks + 7) / 8) * 8 * (pairs / pw));
+        const dim3 pgrid(gx, (unsigned)batch), tgrid(gx, (unsigned)batch);     // tally: blocks 1.., plus block 0's chain
+        const dim3 sgrid((unsigned)(batch * pairs * 4));
+        if (Cx == 1) {
+            if (!blk_done) hipLaunchKernelGGL(rms_par_sum_kernel<true>, pgrid, dim3(kParThreads), 0, stream, r);
+            if (r.prefixed) hipLaunchKernelGGL(rms_par_prefix_kernel, dim3((unsigned)(batch * 4)), dim3(kParThreads), 0, stream, r);
+            hipLaunchKernelGGL(rms_par_tally_kernel<true>, tgrid, dim3(kParThreads), 0, stream, r);
+            hipLaunchKernelGGL(rms_par_stitch_kernel<true>, sgrid, dim3(64), 0, stream, r);
+        } else if (pw == 2) {
+            if (!blk_done) hipLaunchKernelGGL((rms_par_sum_kernel<false, 2>), pgrid, dim3(2 * kParThreads), 0, stream, r);
+            if (r.prefixed) hipLaunchKernelGGL(rms_par_prefix_kernel, dim3((unsigned)(batch * pairs * 4)), dim3(kParThreads), 0, stream, r);
+            hipLaunchKernelGGL((rms_par_tally_kernel<false, 2>), tgrid, dim3(2 * kParThreads), 0, stream, r);
+            hipLaunchKernelGGL(rms_par_stitch_kernel<false>, sgrid, dim3(64), 0, stream, r);
+        } else {
+            if (!blk_done) hipLaunchKernelGGL(rms_par_sum_kernel<false>, pgrid, dim3(kParThreads), 0, stream, r);
+            if (r.prefixed) hipLaunchKernelGGL(rms_par_prefix_kernel, dim3((unsigned)(batch * pairs * 4)), dim3(kParThreads), 0, stream, r);
+            hipLaunchKernelGGL(rms_par_tally_kernel<false>, tgrid, dim3(kParThreads), 0, stream, r);
+            hipLaunchKernelGGL(rms_par_stitch_kernel<false>, sgrid, dim3(64), 0, stream, r);
+        }
+    } else if (sums_pending && C == 1) {
+        e.rows = 1;
+        e.exact_rms = 1;
+        e.normalize = 1;
+        PwArgs q{};
+        q.x = x; q.y = y; q.n = n; q.nchunks = (int32_t)pw_chunks(n);
+        char *extra = (char *)(e.scales + batch * C);
+        extra += (16 - ((uintptr_t)extra & 15)) & 15;
+        q.chunk_sums = (float *)extra;
+        q.partials = e.partials;
+        hipLaunchKernelGGL(rms_pairwise_kernel, dim3((unsigned)q.nchunks, (unsigned)batch), dim3(2 * kPwThreads), 0, stream, q);
+        hipLaunchKernelGGL(rms_pairwise_fold_kernel, dim3((unsigned)batch), dim3(64), 0, stream, q);
+    } else if (sums_pending) {
+        e.rows = 1;
+        e.exact_rms = 1;
+        e.normalize = 1;
+        const size_t lds = (size_t)2 * C * seq_frames * sizeof(float);
+        const int waves = C == 2 ? 4 : std::min(2 * C, kSeqMaxWaves);
+        auto k = C == 2 ? (Cx == 1 ? epilogue_rms_seq_kernel<true, true> : epilogue_rms_seq_kernel<true, false>)
+                        : (seq_frames == kSeqFrames ? epilogue_rms_seq_kernel<false, false, kSeqFrames>
+                                                    : epilogue_rms_seq_kernel<false, false, kSeqFramesWide>);
+        if (lds > 65536) HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                      ctx->lds_limit));
+        // stereo, fewer streams than two per CU: a workgroup per ARRAY of a stream (x's chains, y's chains) - twice the loads in flight
+        const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+        e.seq_split = (C == 2 && batch < 2 * (int64_t)cus && spec_env("VND_EPI_SEQ_SPLIT", 1) != 0) ? 1 : 0;
+        hipLaunchKernelGGL(k, dim3((unsigned)(e.seq_split ? 2 * batch : batch)), dim3(64 * waves), lds, stream, e);
+    }
+    if (normalize) {
+        hipLaunchKernelGGL(epilogue_reduce_kernel, dim3((unsigned)batch), dim3(kEpiThreads), 0, stream, e);
+        hipLaunchKernelGGL(epilogue_scale_kernel, grid, dim3(kEpiThreads), 0, stream, e);
+    }
+    HIP_TRY(hipGetLastError());
+    return VND_OK;
+}
+
 static vnd_status decorrelate_dev(vnd_ctx *ctx, const vnd_taps *t, const float *x, float *y, int64_t batch,
                                   int64_t n, int32_t Cx, int32_t C, int32_t mode, int32_t ms_encode,
                                   int32_t use_width, double width, int32_t normalize, float eps, void *workspace,
@@ -46,65 +194,16 @@ static vnd_status decorrelate_dev(vnd_ctx *ctx, const vnd_taps *t, const float *
     hipStream_t stream = (hipStream_t)stream_;
     const bool any = ms_encode || use_width || normalize;
 
-    EArgs e{};
-    e.x = x; e.y = y; e.partials = (double *)workspace; e.n = n; e.C = C; e.Cx = Cx;
-    e.scales = (float *)((double *)workspace + batch * epi_rows_max(n) * 2 * C);
-    e.ms_encode = ms_encode ? 1 : 0; e.use_width = use_width ? 1 : 0;
-    e.w_mid = (float)(1.0 - width); e.w_side = (float)width;   // float32(python float), as NumPy's in-place multiply
-    e.normalize = normalize ? 1 : 0; e.eps = eps;
-    e.wide = (((uintptr_t)y & 15) == 0 && ((uintptr_t)x & (Cx == 1 ? 7 : 15)) == 0 && (batch == 1 || n % 2 == 0) && spec_env("VND_EPI_WIDE", 1) != 0) ? 1 : 0;
-    // (wide == 2, the block-parallel sums' staging: a wave's 16-byte accesses on consecutive bytes instead of 32 consecutive bytes per
-    //  lane as two accesses - interleaved A/B at 128 / 64 / 32 streams: stereo +1 ... 3 %, mono +3 ... 10 %, the quads of a wider signal
-    //  441 -> 348 us (tools/stage_coalesced_ab.py).  The per-stream kernel of pools of 256 streams and more keeps its own mapping:
-    //  it measured slower with this one - see epilogue_rms_seq_kernel)
-    const int wide_par = e.wide ? (spec_env("VND_EPI_PAR_COALESCED", 1) != 0 ? 2 : 1) : 0;
-    const dim3 grid((unsigned)epi_chunks(n), (unsigned)batch);
-
+    StageSetup s = stage_setup(ctx, x, y, batch, n, Cx, C, mode, ms_encode, use_width, width, normalize, eps, workspace);
+    EArgs &e = s.e;
+    RArgs &r = s.r;
+    const dim3 grid = s.grid;
+    const bool want_seq = s.want_seq, par_ok = s.par_ok, want_blk = s.want_blk;
     // Fused form: the fast kernel applies the pointwise steps and writes one row of sums per tile.
     const Plan p = make_plan(ctx, t, batch, n, C, mode, Cx);
-    // normalize == VND_NORMALIZE_RMS_REFERENCE_ORDER: the sums of squares in NumPy's own (sequential
-    // float32) order in every mode, so that the scale differs from the reference's only through y
-    // frames per staged block of the sums kernel: as many as the 2C rows of squares leave room for
-    const int seq_frames = C == 2 ? kSeqFramesStereo
-                         : ((size_t)2 * C * kSeqFrames * sizeof(float) <= (size_t)ctx->lds_limit ? kSeqFrames : kSeqFramesWide);
-    const bool seq_ok = normalize && C >= 2 && 2 * C <= 64 &&
-                        (size_t)2 * C * seq_frames * sizeof(float) <= (size_t)ctx->lds_limit;
-    // a single-channel table: NumPy sums that array pairwise (rms_pairwise_kernel); the flow is the same
-    const bool pair_ok = normalize && C == 1 && Cx == 1;
-    const bool want_seq = (seq_ok || pair_ok) && (mode == VND_MODE_EXACT || normalize == VND_NORMALIZE_RMS_REFERENCE_ORDER);
     const bool fused = any && mode == VND_MODE_FAST && ctx->variant_nofuse == 0 && fast_epi_kernel(p) != nullptr &&
                        (!(ms_encode || use_width) || p.cg == 2) && !(want_seq && !(ms_encode || use_width));
-    // stereo: the reference-order sums parallel over the stream's 2048-frame blocks (vnd_epilogue.hpp, rms_par_*).  They start from
-    // per-block sums of squares (predictions of the running sum's binade) - which the window kernel's store phase leaves on its way
-    // (x still in the ring, the finished y in registers: EpiFuse::blk_sum) where that kernel runs; rms_par_sum_kernel reads both
-    // arrays for them otherwise.  Which form, by batch (tools/rms_batch_rate.py, 10 s signals, ms per stage: per-stream / block-parallel):
-    //   up to 64 streams the one-workgroup-per-stream kernel leaves most CUs dark (16: 0.49 / 0.17);
-    //   65 .. 255: it still fills less than every CU once (128: 0.80 / 0.82, and 0.66 once the block sums come from the convolution);
-    //   more than 320: it fills the chip by itself and reads the data once instead of twice (1024: 4.43 / 5.0; the switch was at 256 until round 6).
-    // variant bit 19 keeps the per-stream kernel, bit 17 forces the block-parallel form (A/B runs).
-    // Wider signals (round 5): the same kernels channel pair by channel pair - a "stream" of theirs is one pair of a stream (RArgs::pairs),
-    // 8 bytes of every frame.  The per-stream kernel takes 16 workgroups for cfg5's pool of 16 signals (8.7 ms for the stage); the
-    // block-parallel form 16 x 4 pairs x 469 blocks.
-    const int pairs = C / 2;
-    const bool par_ok = want_seq && C % 2 == 0 && (C == 2 || Cx == C) && par_blocks(n) <= kParMaxBlocks && !(ctx->variant >= 0 && ((ctx->variant >> 19) & 1));
-    const bool par_forced = ctx->variant >= 0 && ((ctx->variant >> 17) & 1);
-    RArgs r{};
     int conv_path = 0;                                     // EpiFuse::path of the convolution launch
-    if (par_ok) {
-        r.x = x; r.y = y; r.n = n; r.Cx = Cx; r.nblocks = (int32_t)par_blocks(n); r.C = C; r.pairs = pairs;
-        char *extra = (char *)((float *)((double *)workspace + batch * epi_rows_max(n) * 2 * C) + batch * C);
-        extra += (16 - ((uintptr_t)extra & 15)) & 15;
-        r.blk_sum = (double *)extra;
-        r.rec = (ParRec *)(r.blk_sum + batch * pairs * 4 * (int64_t)r.nblocks);
-        r.grp = (ParGrp *)(r.rec + batch * pairs * 4 * (int64_t)r.nblocks);
-        r.first = (float *)(r.grp + batch * pairs * 4 * (int64_t)r.nblocks);
-        r.partials = (double *)workspace;
-        r.prefixed = r.nblocks > kParPrefixBlocks ? 1 : 0;
-        r.wide = wide_par;
-    }
-    // (round 6, with the tally's staging on consecutive bytes: 256 streams 1.27-1.37 -> 1.22-1.25 ms block-parallel; from 384 on the per-stream
-    //  kernel leads, 1.70 against 1.80-1.84 - tools/f1_threshold_try.py, profiles/r06_f1_threshold.txt)
-    const bool want_blk = par_ok && C == 2 && (batch <= 320 || par_forced) && spec_env("VND_EPI_BLOCK_SUMS", 1) != 0;
     bool sums_pending = false;                             // the sequential sums still have to run
     // 4k channels, fast mode, the normaliser alone (LR mode - cfg5 through the class API, decorrelation.py:433-440): the quad / octet
     // kernel's store phase leaves the sums of squares on its way (x still in the ring, y in registers), one streaming pass scales:
@@ -183,68 +282,7 @@ static vnd_status decorrelate_dev(vnd_ctx *ctx, const vnd_taps *t, const float *
         sums_pending = seq;
     }
     const bool blk_done = (conv_path == 1 && want_blk) || q_blk_done;
-    // (wider signals: the per-stream kernel fills the chip from 256 streams on, as for stereo; below that the pairs' blocks do)
-    const bool par_sums = sums_pending && par_ok && (batch <= 64 || par_forced || blk_done || (C > 2 && batch < 256));
-    if (par_sums) {
-        e.rows = 1;
-        e.exact_rms = 1;
-        e.normalize = 1;
-        // (wider signals: the pairs of a block side by side in one XCD's queue - par_unit)
-        // 4k channels with 16-byte-aligned streams: a channel QUAD per workgroup (512 threads, whole 16-byte accesses)
-        const int pw = (pairs > 1 && pairs % 2 == 0 && r.wide) ? 2 : 1;
-        const unsigned gx = pairs == 1 ? (unsigned)r.nblocks : (unsigned)(((r.nblocks + 7) / 8) * 8 * (pairs / pw));
-        const dim3 pgrid(gx, (unsigned)batch), tgrid(gx, (unsigned)batch);     // tally: blocks 1.., plus block 0's chain
-        const dim3 sgrid((unsigned)(batch * pairs * 4));
-        if (Cx == 1) {
-            if (!blk_done) hipLaunchKernelGGL(rms_par_sum_kernel<true>, pgrid, dim3(kParThreads), 0, stream, r);
-            if (r.prefixed) hipLaunchKernelGGL(rms_par_prefix_kernel, dim3((unsigned)(batch * 4)), dim3(kParThreads), 0, stream, r);
-            hipLaunchKernelGGL(rms_par_tally_kernel<true>, tgrid, dim3(kParThreads), 0, stream, r);
-            hipLaunchKernelGGL(rms_par_stitch_kernel<true>, sgrid, dim3(64), 0, stream, r);
-        } else if (pw == 2) {
-            if (!blk_done) hipLaunchKernelGGL((rms_par_sum_kernel<false, 2>), pgrid, dim3(2 * kParThreads), 0, stream, r);
-            if (r.prefixed) hipLaunchKernelGGL(rms_par_prefix_kernel, dim3((unsigned)(batch * pairs * 4)), dim3(kParThreads), 0, stream, r);
-            hipLaunchKernelGGL((rms_par_tally_kernel<false, 2>), tgrid, dim3(2 * kParThreads), 0, stream, r);
-            hipLaunchKernelGGL(rms_par_stitch_kernel<false>, sgrid, dim3(64), 0, stream, r);
-        } else {
-            if (!blk_done) hipLaunchKernelGGL(rms_par_sum_kernel<false>, pgrid, dim3(kParThreads), 0, stream, r);
-            if (r.prefixed) hipLaunchKernelGGL(rms_par_prefix_kernel, dim3((unsigned)(batch * pairs * 4)), dim3(kParThreads), 0, stream, r);
-            hipLaunchKernelGGL(rms_par_tally_kernel<false>, tgrid, dim3(kParThreads), 0, stream, r);
-            hipLaunchKernelGGL(rms_par_stitch_kernel<false>, sgrid, dim3(64), 0, stream, r);
-        }
-    } else if (sums_pending && C == 1) {
-        e.rows = 1;
-        e.exact_rms = 1;
-        e.normalize = 1;
-        PwArgs q{};
-        q.x = x; q.y = y; q.n = n; q.nchunks = (int32_t)pw_chunks(n);
-        char *extra = (char *)(e.scales + batch * C);
-        extra += (16 - ((uintptr_t)extra & 15)) & 15;
-        q.chunk_sums = (float *)extra;
-        q.partials = e.partials;
-        hipLaunchKernelGGL(rms_pairwise_kernel, dim3((unsigned)q.nchunks, (unsigned)batch), dim3(2 * kPwThreads), 0, stream, q);
-        hipLaunchKernelGGL(rms_pairwise_fold_kernel, dim3((unsigned)batch), dim3(64), 0, stream, q);
-    } else if (sums_pending) {
-        e.rows = 1;
-        e.exact_rms = 1;
-        e.normalize = 1;
-        const size_t lds = (size_t)2 * C * seq_frames * sizeof(float);
-        const int waves = C == 2 ? 4 : std::min(2 * C, kSeqMaxWaves);
-        auto k = C == 2 ? (Cx == 1 ? epilogue_rms_seq_kernel<true, true> : epilogue_rms_seq_kernel<true, false>)
-                        : (seq_frames == kSeqFrames ? epilogue_rms_seq_kernel<false, false, kSeqFrames>
-                                                    : epilogue_rms_seq_kernel<false, false, kSeqFramesWide>);
-        if (lds > 65536) HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                      ctx->lds_limit));
-        // stereo, fewer streams than two per CU: a workgroup per ARRAY of a stream (x's chains, y's chains) - twice the loads in flight
-        const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
-        e.seq_split = (C == 2 && batch < 2 * (int64_t)cus && spec_env("VND_EPI_SEQ_SPLIT", 1) != 0) ? 1 : 0;
-        hipLaunchKernelGGL(k, dim3((unsigned)(e.seq_split ? 2 * batch : batch)), dim3(64 * waves), lds, stream, e);
-    }
-    if (normalize) {
-        hipLaunchKernelGGL(epilogue_reduce_kernel, dim3((unsigned)batch), dim3(kEpiThreads), 0, stream, e);
-        hipLaunchKernelGGL(epilogue_scale_kernel, grid, dim3(kEpiThreads), 0, stream, e);
-    }
-    HIP_TRY(hipGetLastError());
-    return VND_OK;
+    return stage_sums(ctx, s, x, y, batch, n, Cx, C, normalize, sums_pending, blk_done, stream);
 }
 
 static vnd_status decorrelate_host(vnd_ctx *ctx, const vnd_taps *t, const float *x, float *y, int64_t batch,

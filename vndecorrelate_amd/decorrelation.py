@@ -14,8 +14,9 @@ reference                    here
 ``SignalChain``              :class:`SignalChain`
 ``HaasEffect``               :class:`HaasEffect` (device kernel ``vnd_haas_f64_*`` in a
                              device-resident chain, NumPy otherwise)
-``WhiteNoise``               NumPy-only chain stage (out of the GPU scope, SURVEY.md §2
-                             row 7; kept so chains stay drop-in)
+``WhiteNoise``               :class:`WhiteNoise` (dense float64 FIR + width + normaliser on the
+                             GPU through ``vnd_white_noise_f32_dev`` where covered, see
+                             ``set_white_noise_device``; NumPy otherwise)
 ===========================  ==================================================
 
 There is no CPU implementation of the tap sum in this package: without the
@@ -108,6 +109,56 @@ def _normalize_flag(has_normalizer: bool) -> int:
     if not has_normalizer:
         return _native.NORMALIZE_OFF
     return _native.NORMALIZE_RMS if _device_epilogue else _native.NORMALIZE_RMS_REFERENCE_ORDER
+
+
+_white_noise_device: Optional[bool] = None
+
+
+def set_white_noise_device(enabled: Optional[bool]) -> None:
+    """Where ``WhiteNoise.decorrelate`` (and ``decorrelate_batched``) runs.
+
+    ``None`` (default): on the GPU (``vnd_white_noise_f32_dev``: one float64 FMA chain per output, rounded once, then the
+    width and NumPy-order normaliser of the velvet-noise stage) when a gfx950 device is present and the call is covered
+    (``white_noise_covers``); otherwise the NumPy code.  Per output the device result is within one float32 ulp plus
+    2^-40 * sum |h x| of NumPy's (whose float64 summation order is the host BLAS's); where the convolution's float32
+    outputs agree, the stage is bit-identical.
+    ``True``: the device for every covered call; ``RuntimeError`` when there is no device.
+    ``False``: always NumPy, bit-identical to the reference."""
+    global _white_noise_device
+    if enabled is not None and not isinstance(enabled, (bool, np.bool_)):
+        raise TypeError(f'set_white_noise_device takes True, False or None, not {enabled!r}')
+    _white_noise_device = None if enabled is None else bool(enabled)
+
+
+def white_noise_covers(shape: Sequence[int], num_outs: int, width, fir, c_contiguous: bool = True) -> bool:
+    """Whether ``WhiteNoise.decorrelate`` of a float32 signal of ``shape`` has a device form: a finite float64 2-D
+    filter with at least ``num_outs`` columns and 1 <= M <= n taps; a ``(n, num_outs)`` C-contiguous signal (NumPy's
+    sums of squares follow the memory layout), or a ``(n,)`` one with ``num_outs == 2``; width only on two channels;
+    at most 32 channels (the device repeats NumPy's sum order up to there).  Everything else keeps the NumPy code and
+    its exceptions."""
+    if not isinstance(fir, np.ndarray) or fir.dtype != np.float64 or fir.ndim != 2:
+        return False
+    if not 1 <= num_outs <= 32 or fir.shape[1] < num_outs:
+        return False
+    if len(shape) == 1:
+        if num_outs != 2:
+            return False
+    elif len(shape) != 2 or shape[1] != num_outs or not c_contiguous:
+        return False
+    if width is not None and num_outs != 2:
+        return False
+    m = fir.shape[0]
+    if not 1 <= m <= shape[0] or m > 2 ** 31 - 1:
+        return False
+    return bool(np.isfinite(fir[:, :num_outs]).all())
+
+
+def _gpu_present() -> bool:
+    try:
+        _native.default_context()
+        return True
+    except RuntimeError:                                  # no built extension, no device, not a gfx950
+        return False
 
 
 def set_default_mode(mode: int) -> None:
@@ -737,7 +788,7 @@ def decorrelate_bank(input_signal: NDArray, decorrelators: Sequence[VelvetNoise]
 
 
 # ----------------------------------------------------------------------------
-# NumPy-only chain stages (outside the GPU scope)
+# The chain stages either side of the path: HaasEffect, WhiteNoise
 # ----------------------------------------------------------------------------
 @dataclass(kw_only=True)
 class HaasEffect(Decorrelator):
@@ -775,8 +826,9 @@ class HaasEffect(Decorrelator):
 
 @dataclass(kw_only=True)
 class WhiteNoise(Decorrelator):
-    """Dense Gaussian FIR per channel via ``np.convolve(mode='same')``
-    (decorrelation.py:670-716) - the comparison baseline of the reference's plots."""
+    """Dense Gaussian FIR per channel via ``np.convolve(mode='same')``, then width and
+    ``rms_normalize`` (decorrelation.py:670-716) - the comparison baseline of the reference's plots.
+    On the GPU where covered (``set_white_noise_device``), in NumPy otherwise."""
 
     duration_seconds: float = 0.03
     seed: Optional[int] = None
@@ -786,6 +838,7 @@ class WhiteNoise(Decorrelator):
         rng = np.random.default_rng(self.seed)
         self.white_noise_filter = rng.normal(loc=0, scale=1,
                                              size=(self.fir_length_samples, self.num_outs))
+        self._device_fir = None           # (key, device tensor) of the filter's used columns
 
     @property
     def fir_length_samples(self) -> int:
@@ -797,6 +850,9 @@ class WhiteNoise(Decorrelator):
 
     def decorrelate(self, input_signal: NDArray) -> NDArray:
         input_signal = to_float32(input_signal)
+        if self._on_device(input_signal.shape, input_signal.ndim != 2 or input_signal.flags.c_contiguous):
+            x = np.ascontiguousarray(input_signal)
+            return self._decorrelate_on_device(x.reshape((1,) + x.shape[:1] + (x.shape[1] if x.ndim == 2 else 1,)))[0]
         if input_signal.ndim == 1:
             input_signal = mono_to_stereo(input_signal)
         out = np.zeros((len(input_signal), self.num_outs), dtype=np.float32)
@@ -805,6 +861,60 @@ class WhiteNoise(Decorrelator):
         if self.width is not None:
             apply_stereo_width(out, self.width)
         rms_normalize(input_signal, out)
+        return out
+
+    def decorrelate_batched(self, input_signals: NDArray) -> NDArray:
+        """``(B, n, C)`` or mono ``(B, n)`` independent signals through the whole stage; float32 ``(B, n, num_outs)``,
+        equal bit for bit to stacking ``decorrelate`` over the streams.  Covered shapes take one device pass per
+        VND_MAX_STREAMS streams; others the per-stream loop."""
+        x = to_float32(np.asarray(input_signals))
+        if x.ndim not in (2, 3):
+            raise ValueError(f'expected (batch, n) or (batch, n, channels), got shape {x.shape}')
+        if len(x) and self._on_device(x.shape[1:], x.flags.c_contiguous):
+            x = np.ascontiguousarray(x)
+            return self._decorrelate_on_device(x if x.ndim == 3 else x[:, :, None])
+        if not len(x):
+            return np.zeros((0, x.shape[1], self.num_outs), np.float32)
+        return np.stack([self.decorrelate(sig) for sig in x])
+
+    def _on_device(self, shape, c_contiguous: bool) -> bool:
+        if _white_noise_device is False:
+            return False
+        if _white_noise_device and not _gpu_present():
+            raise RuntimeError('set_white_noise_device(True): no gfx950 device (or no built extension) to run WhiteNoise on')
+        return white_noise_covers(shape, self.num_outs, self.width, self.white_noise_filter, c_contiguous) and \
+            (_white_noise_device is True or _gpu_present())
+
+    def _device_filter(self, torch, device):
+        """The filter's ``num_outs`` columns as a float64 device tensor, uploaded again only when their bytes change."""
+        view = np.ascontiguousarray(self.white_noise_filter[:, :self.num_outs], dtype=np.float64)
+        key = (view.shape, _digest16(view), str(device))
+        cached = getattr(self, '_device_fir', None)
+        if cached is None or cached[0] != key:
+            cached = self._device_fir = (key, torch.from_numpy(view.copy()).to(device))
+        return cached[1]
+
+    def _decorrelate_on_device(self, x: NDArray) -> NDArray:
+        """x: C-contiguous float32 ``(B, n, Cx)``, Cx = num_outs or 1 (fanned out to 2)."""
+        from .resident import _torch
+        torch = _torch()
+        ctx = _native.default_context()
+        device = torch.device('cuda', ctx.device)
+        batch, n, cx = x.shape
+        h = self._device_filter(torch, device)
+        out = _native.pinned_pool.empty((batch, n, self.num_outs), np.float32)
+        step = _native.MAX_STREAMS_PER_CALL
+        for first in range(0, batch, step):
+            part = x[first:first + step]
+            xd = torch.from_numpy(part if part.flags.writeable else part.copy()).to(device)
+            yd = torch.empty((len(part), n, self.num_outs), dtype=torch.float32, device=device)
+            ws_bytes = _native.decorrelate_workspace_bytes(len(part), n, self.num_outs)
+            work = torch.empty((ws_bytes,), dtype=torch.uint8, device=device)
+            _native.white_noise_device(ctx, xd.data_ptr(), h.data_ptr(), yd.data_ptr(), len(part), n, cx, self.num_outs,
+                                       h.shape[0], width=self.width, normalize=_native.NORMALIZE_RMS_REFERENCE_ORDER,
+                                       workspace_ptr=work.data_ptr(), workspace_bytes=ws_bytes,
+                                       stream=torch.cuda.current_stream(device).cuda_stream)
+            torch.from_numpy(out[first:first + len(part)]).copy_(yd)
         return out
 
 

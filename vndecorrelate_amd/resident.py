@@ -7,10 +7,13 @@ through the ``*_dev`` entry points of the C ABI, and the result comes back once:
 
 * ``VelvetNoise``  -> ``vnd_decorrelate[_fanout]_f32_dev`` (convolution + epilogue; float32)
 * ``HaasEffect``   -> ``vnd_haas_f64_dev`` (float64 ``(n + delay, 2)``, bit-identical)
+* ``WhiteNoise``   -> ``vnd_white_noise_f32_dev`` (dense float64 FIR + width + normaliser; float32) on the shapes
+  ``decorrelation.white_noise_covers`` accepts, unless ``set_white_noise_device(False)``; a float64 input (Haas
+  output) is cast to float32 on the device
 * ``stateless(convolve_velvet_noise, velvet_noise_filters=fir)`` (the README's stateless stage,
   decorrelation.py:104-110, :630-660; also ``convolve_velvet_noise_batched``) -> ``vnd_convolve_f32_dev``
   on a float32 signal with a float32 filter (the operand types NumPy multiplies in float32)
-* anything else (``WhiteNoise``, other ``stateless`` callables - the positional quirk form
+* anything else (other ``stateless`` callables - the positional quirk form
   ``stateless(convolve_velvet_noise, fir)`` included, which makes the SIGNAL the filter, SURVEY
   Appendix B #7 -, custom normalisers, float64 operands) runs on the host exactly as in the plain
   chain, with one download/upload around it.
@@ -117,6 +120,27 @@ def _velvet_on_device(stage, buf, torch, dec, pool=None, key=None):
     return y
 
 
+def _white_noise_on_device(stage, buf, torch, dec, pool=None, key=None):
+    """``WhiteNoise.decorrelate`` (decorrelation.py:684-706) on a device tensor, or None when the call is not covered
+    (``dec.white_noise_covers``): the host code then keeps NumPy's behaviour and exceptions."""
+    if dec._white_noise_device is False or buf.dim() not in (1, 2):
+        return None
+    if not dec.white_noise_covers(tuple(buf.shape), stage.num_outs, stage.width, stage.white_noise_filter):
+        return None
+    x = (buf.unsqueeze(1) if buf.dim() == 1 else buf).to(torch.float32).contiguous()     # to_float32 (utils/dsp.py:66-68)
+    n, channels = x.shape
+    pool = pool or BufferPool()
+    h = stage._device_filter(torch, x.device)
+    y = pool.get(torch, (key, 'y'), (n, stage.num_outs), torch.float32, x.device)
+    ws_bytes = _native.decorrelate_workspace_bytes(1, n, stage.num_outs)
+    work = pool.get(torch, (key, 'work'), (ws_bytes,), torch.uint8, x.device)
+    _native.white_noise_device(_native.default_context(), x.data_ptr(), h.data_ptr(), y.data_ptr(), 1, n, channels,
+                               stage.num_outs, h.shape[0], width=stage.width,
+                               normalize=_native.NORMALIZE_RMS_REFERENCE_ORDER, workspace_ptr=work.data_ptr(),
+                               workspace_bytes=ws_bytes, stream=torch.cuda.current_stream(x.device).cuda_stream)
+    return y
+
+
 def _haas_on_device(stage, buf, torch, pool=None, key=None):
     """``HaasEffect.decorrelate`` (decorrelation.py:192-230) on a device tensor, or None."""
     delay = round(stage.delay_time_seconds * stage.sample_rate_hz)
@@ -178,6 +202,12 @@ def run(stages: Sequence, input_signal: np.ndarray, pool: Optional[BufferPool] =
                 out = _velvet_on_device(stage, to_device(), torch, dec, pool, index)
         elif isinstance(stage, dec.HaasEffect):
             out = _haas_on_device(stage, to_device(), torch, pool, index)
+        elif isinstance(stage, dec.WhiteNoise):
+            # (the normaliser's sums follow the memory layout: an odd-layout host signal stays with NumPy, as for VelvetNoise)
+            current = buf if buf is not None else host
+            if not odd_layout and dec._white_noise_device is not False and \
+                    dec.white_noise_covers(tuple(current.shape), stage.num_outs, stage.width, stage.white_noise_filter):
+                out = _white_noise_on_device(stage, to_device(), torch, dec, pool, index)
         elif isinstance(stage, partial) and stage.func in (dec.convolve_velvet_noise, dec.convolve_velvet_noise_batched):
             # (decided on what the signal IS: a float64 signal - Haas output - or one still on the host as int16 keeps
             #  the host function and its promoting kernel)
