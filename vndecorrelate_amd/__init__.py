@@ -24,3 +24,4 @@ from .decorrelation import (  # noqa: F401
     set_device_epilogue,
     set_white_noise_device,
 )
+from .analysis import cross_correlogram_batched, set_correlogram_device  # noqa: F401

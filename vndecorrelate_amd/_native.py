@@ -140,6 +140,15 @@ INTERNAL_SIGNATURES = {
                                              ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
 }
 
+# include/vnd_analysis.h: the analysis entry points, bound apart so that SIGNATURES keeps matching vnd_amd.h
+ANALYSIS_SIGNATURES = {
+    'vnd_correlogram_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                               ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
+                                               ctypes.c_void_p]),
+}
+CORRELOGRAM_MAX_WINDOW = 16384   # VND_CORRELOGRAM_MAX_WINDOW
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -185,7 +194,8 @@ def load_library():
                 f'g.build()"` (hipcc --offload-arch=gfx950).  vndecorrelate_amd has no CPU fallback.')
         _preload_hip_runtime()
         lib = ctypes.CDLL(str(LIB_PATH))
-        for name, (res, args) in list(SIGNATURES.items()) + list(INTERNAL_SIGNATURES.items()):
+        for name, (res, args) in (list(SIGNATURES.items()) + list(INTERNAL_SIGNATURES.items())
+                                  + list(ANALYSIS_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -605,6 +615,15 @@ def white_noise_device(ctx: 'Context', x_ptr: int, h_ptr: int, y_ptr: int, batch
                                             batch, n, in_channels, channels, fir_length, int(width is not None),
                                             float(width or 0.0), int(normalize), float(eps), ctypes.c_void_p(workspace_ptr),
                                             workspace_bytes, ctypes.c_void_p(stream)), 'vnd_white_noise_f32_dev')
+
+
+def correlogram_device(ctx: 'Context', x_ptr: int, y_ptr: int, out_ptr: int, batch: int, n: int, stream_stride: int,
+                       frame_stride: int, *, window: int, hop: int, num_lags: int, eps: float, stream: int = 0):
+    """``vnd_correlogram_f32_dev``: the windowed, normalised cross-correlogram of float32 device signals (sample t of stream
+    b at ``b * stream_stride + t * frame_stride``) into float32 ``(batch, windows, num_lags)``, enqueued on ``stream``."""
+    _check(ctx._lib.vnd_correlogram_f32_dev(ctx.handle, ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr),
+                                            ctypes.c_void_p(out_ptr), batch, n, stream_stride, frame_stride, window, hop,
+                                            num_lags, float(eps), ctypes.c_void_p(stream)), 'vnd_correlogram_f32_dev')
 
 
 def polar_moments_workspace_bytes(n: int, pairs: int) -> int:

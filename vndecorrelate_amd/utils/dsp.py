@@ -6,9 +6,12 @@ citations are ``file:line`` in ckonst/VNDecorrelate v1.1.0.  These are O(N)
 pointwise NumPy steps or O(K) tap-placement maths; the O(N*K) tap sum itself
 never runs here - it lives in the HIP extension.
 
-``polar_coordinates`` is here for the optimiser's objective; the
-other analysis/plot helpers of the reference (correlograms, sweeps) are out of scope
-(SURVEY.md §2 rows 9-10).
+``polar_coordinates`` is here for the optimiser's objective.  The
+analysis helpers of SURVEY.md §2 row 9 are here too: ``cross_correlogram`` (on the
+GPU where covered, see ``vndecorrelate_amd.analysis``; NumPy otherwise), and the pure
+host helpers ``sine_sweep``, ``polar_to_cartesian``, ``exponential_decay``,
+``generate_decay_envelope`` and ``radians_to_degrees``, bit-identical to the
+reference.  Plots (row 10) stay out of scope.
 """
 from __future__ import annotations
 
@@ -167,3 +170,76 @@ def polar_coordinates(left: NDArray, right: NDArray, mode: LayoutMode = LayoutMo
     if not compute_weights:
         return radii, thetas
     return radii, thetas, radii / (radii.sum() + EPSILON)
+
+
+# ---- analysis (utils/dsp.py:313-467) --------------------------------------------------
+def _correlogram_numpy(x: NDArray[np.float32], y: NDArray[np.float32], window: int, hop: int, max_lag: int,
+                       epsilon: float) -> NDArray[np.float32]:
+    """The reference's per-window loop: ``np.correlate(..., 'full')`` over the window's energy norm, first
+    ``2 max_lag + 1`` columns kept (zeros past ``2 window - 1``).  Its exceptions: hop 0 -> ZeroDivisionError,
+    window 0 -> ValueError, a negative column count -> ValueError."""
+    starts = np.arange(0, len(x) - window + 1, hop)
+    result = np.zeros((len(starts), 2 * max_lag + 1), dtype=np.float32)
+    for row, first in enumerate(starts):
+        xw = x[first:first + window]
+        yw = y[first:first + window]
+        full = np.correlate(xw, yw, mode='full') / (np.sqrt(np.dot(xw, xw) * np.dot(yw, yw)) + epsilon)
+        kept = full[:result.shape[1]]
+        result[row, :len(kept)] = kept
+    return result
+
+
+def correlogram_sizes(sample_rate_hz, max_lag_seconds, window_size_seconds, stride_seconds):
+    """``(window, hop, max_lag)`` in samples, by the reference's own ``int(seconds * rate)``."""
+    return (int(window_size_seconds * sample_rate_hz), int(stride_seconds * sample_rate_hz),
+            int(max_lag_seconds * sample_rate_hz))
+
+
+def cross_correlogram(x: NDArray, y: NDArray, sample_rate_hz: int = 44100, max_lag_seconds: float = 0.02,
+                      window_size_seconds: float = 0.02, stride_seconds: float = 0.01,
+                      epsilon: float = EPSILON) -> NDArray[np.float32]:
+    """Cross-correlogram of mono ``x`` and ``y``: float32 ``(windows, 2 max_lag + 1)``, row i the full correlation of
+    the i-th window (hop ``stride``) over ``sqrt(Exx * Eyy) + epsilon``; column j is lag j - (window - 1).
+
+    On the GPU where ``vndecorrelate_amd.analysis.correlogram_covers`` says the call is covered and
+    ``set_correlogram_device`` allows it (float64 sums); the reference's NumPy loop otherwise."""
+    check_mono(x)
+    check_mono(y)
+    check_equal_length(x, y)
+    x = to_float32(x)
+    y = to_float32(y)
+    window, hop, max_lag = correlogram_sizes(sample_rate_hz, max_lag_seconds, window_size_seconds, stride_seconds)
+    from .. import analysis                       # lazily: this module stays free of the native binding
+    if analysis.use_device(len(x), window, hop, 2 * max_lag + 1, epsilon):
+        return analysis.correlogram_numpy_batch(x[None], y[None], window, hop, 2 * max_lag + 1, epsilon)[0]
+    return _correlogram_numpy(x, y, window, hop, max_lag, epsilon)
+
+
+def sine_sweep(start_freq_hz: float, end_freq_hz: float, duration_seconds: float,
+               sample_rate_hz: int = 44100) -> NDArray[np.float32]:
+    """Exponential sweep from ``start_freq_hz`` to ``end_freq_hz``, float32."""
+    t = np.linspace(0, duration_seconds, int(sample_rate_hz * duration_seconds), endpoint=False)
+    rate = np.log(end_freq_hz / start_freq_hz) / duration_seconds
+    return np.sin(2 * np.pi * start_freq_hz * (np.exp(rate * t) - 1) / rate).astype(np.float32)
+
+
+def polar_to_cartesian(angles_degrees: NDArray, radii: NDArray):
+    """``(x, y) = (r sin theta, r cos theta)``: angle 0 points up."""
+    thetas = np.radians(angles_degrees)
+    return radii * np.sin(thetas), radii * np.cos(thetas)
+
+
+def exponential_decay(t: float, k: float = 2) -> float:
+    """``e ** (-k t)``."""
+    return np.e ** (-k * t)
+
+
+def generate_decay_envelope(num_segments: int, segment_position: float) -> tuple:
+    """``num_segments`` samples of ``exponential_decay`` at ``(t + segment_position) / num_segments``."""
+    return tuple(exponential_decay((t / num_segments) + (segment_position * 1 / num_segments))
+                 for t in range(num_segments))
+
+
+def radians_to_degrees(radians: NDArray) -> NDArray:
+    """Degrees, clipped to [-90, 90]."""
+    return np.clip(np.degrees(radians), -90.0, 90.0)
