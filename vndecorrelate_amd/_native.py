@@ -149,6 +149,19 @@ ANALYSIS_SIGNATURES = {
 }
 CORRELOGRAM_MAX_WINDOW = 16384   # VND_CORRELOGRAM_MAX_WINDOW
 
+# include/vnd_scan.h: the optimiser's scan entry points, bound apart like the analysis ones
+SCAN_SIGNATURES = {
+    'vnd_haas_scan_workspace_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                     ctypes.POINTER(ctypes.c_int64)]),
+    'vnd_haas_scan_f64_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                             ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                             ctypes.c_int32, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_int64, ctypes.c_void_p]),
+    'vnd_haas_scan_f64_host': (ctypes.c_int, [ctypes.c_void_p, _c_f32p, ctypes.c_int64, ctypes.c_int32, _c_i32p,
+                                              ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                              ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
+}
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -195,7 +208,7 @@ def load_library():
         _preload_hip_runtime()
         lib = ctypes.CDLL(str(LIB_PATH))
         for name, (res, args) in (list(SIGNATURES.items()) + list(INTERNAL_SIGNATURES.items())
-                                  + list(ANALYSIS_SIGNATURES.items())):
+                                  + list(ANALYSIS_SIGNATURES.items()) + list(SCAN_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -625,6 +638,42 @@ def correlogram_device(ctx: 'Context', x_ptr: int, y_ptr: int, out_ptr: int, bat
                                             ctypes.c_void_p(out_ptr), batch, n, stream_stride, frame_stride, window, hop,
                                             num_lags, float(eps), ctypes.c_void_p(stream)), 'vnd_correlogram_f32_dev')
 
+
+
+def haas_scan_workspace_bytes(n: int, n_delays: int, max_delay: int) -> int:
+    need = ctypes.c_int64()
+    _check(load_library().vnd_haas_scan_workspace_bytes(n, n_delays, max_delay, ctypes.byref(need)),
+           'vnd_haas_scan_workspace_bytes')
+    return need.value
+
+
+def haas_scan_host(ctx: 'Context', x: np.ndarray, delays, *, delayed_channel: int, ms_mode: bool, width) -> np.ndarray:
+    """``vnd_haas_scan_f64_host``: float64 ``(F, 8)`` polar moments of ``HaasEffect(delay d).decorrelate(x)`` for
+    each integer delay d, from a C-contiguous float32 ``(n, 1|2)`` signal in host memory."""
+    if x.dtype != np.float32 or not x.flags.c_contiguous or x.ndim != 2:
+        raise ValueError('haas_scan_host wants a C-contiguous float32 (n, C) array')
+    d = np.ascontiguousarray(delays, np.int64)
+    if d.ndim != 1 or (d.size and (d.min() < np.iinfo(np.int32).min or d.max() > np.iinfo(np.int32).max)):
+        raise ValueError('haas_scan_host wants a 1-D list of int32 delays')
+    d = d.astype(np.int32)
+    out = np.zeros((d.size, MOMENTS), np.float64)
+    _check(ctx._lib.vnd_haas_scan_f64_host(ctx.handle, _ptr(x, ctypes.c_float), x.shape[0], x.shape[1],
+                                           _ptr(d, ctypes.c_int32), d.size, int(delayed_channel), int(bool(ms_mode)),
+                                           int(width is not None), float(width or 0.0), _ptr(out, ctypes.c_double)),
+           'vnd_haas_scan_f64_host')
+    return out
+
+
+def haas_scan_device(ctx: 'Context', x_ptr: int, n: int, channels: int, delays_ptr: int, n_delays: int,
+                     moments_ptr: int, *, delayed_channel: int, ms_mode: bool, width, workspace_ptr: int,
+                     workspace_bytes: int, stream: int = 0):
+    """``vnd_haas_scan_f64_dev``: float64 ``(n_delays, 8)`` moments from float32 ``(n, channels)`` and int32 delays,
+    all device buffers, enqueued on ``stream``."""
+    _check(ctx._lib.vnd_haas_scan_f64_dev(ctx.handle, ctypes.c_void_p(x_ptr), n, channels, ctypes.c_void_p(delays_ptr),
+                                          n_delays, int(delayed_channel), int(bool(ms_mode)), int(width is not None),
+                                          float(width or 0.0), ctypes.c_void_p(moments_ptr),
+                                          ctypes.c_void_p(workspace_ptr), workspace_bytes, ctypes.c_void_p(stream)),
+           'vnd_haas_scan_f64_dev')
 
 def polar_moments_workspace_bytes(n: int, pairs: int) -> int:
     need = ctypes.c_int64()

@@ -1,12 +1,13 @@
 // vnd_amd.hip - C ABI (include/vnd_amd.h) over the gfx950 kernels: the one translation unit of libvnd_amd.so.
 // Host code only decides launch geometry and orchestrates; all arithmetic lives in the kernels (vnd_kernels.hpp, vnd_win_kernel.inc,
 // vnd_spec_kernel.inc, vnd_epilogue.hpp, vnd_moments.hpp, vnd_haas.hpp, vnd_dense.hpp,
-// vnd_correlogram.hpp).  Parts:
+// vnd_correlogram.hpp, vnd_haas_scan.hpp).  Parts:
 //   vnd_objects.hpp  context, tap table, error channel            vnd_plan.hpp   which kernel, how the work is cut, launch
 //   vnd_host.hpp     *_host entry points (pipelined staging)       vnd_stage.hpp  decorrelate stage, promoted operands, scan, Haas
 //   vnd_rccl.hpp     shard ranges, the tap table over RCCL         vnd_hooks.hpp  measurement / tuning / diagnosis hooks
 //   vnd_dense.hpp    WhiteNoise: the dense float64 FIR and its stage
 //   vnd_correlogram.hpp  cross_correlogram (include/vnd_analysis.h)
+//   vnd_haas_scan.hpp    the Haas-delay optimiser's scan (include/vnd_scan.h)
 #include "vnd_objects.hpp"
 #include "vnd_plan.hpp"
 
@@ -413,4 +414,5 @@ vnd_status vnd_prepare_launch(vnd_ctx *ctx, const vnd_taps *t, int64_t batch, in
 #include "vnd_stage.hpp"
 #include "vnd_dense.hpp"
 #include "vnd_correlogram.hpp"
+#include "vnd_haas_scan.hpp"
 #include "vnd_hooks.hpp"

@@ -36,17 +36,10 @@ __device__ __forceinline__ double haas_column(const HArgs &a, const float *__res
     return c == 0 ? (l + r) * 0.5 : (l - r) * 0.5;           // LR_to_MS
 }
 
-__global__ __launch_bounds__(kHaasThreads) void haas_kernel(const HArgs a)
+// frame k of the output: both columns after the roll, MS decode and stereo width (shared with vnd_haas_scan.hpp)
+__device__ __forceinline__ void haas_frame(const HArgs &a, const double c0, const double c1, double v[2])
 {
-    const int64_t total = a.n + a.delay;
-    const int64_t k = (int64_t)blockIdx.x * kHaasThreads + threadIdx.x;
-    if (k >= total) return;
-    const float *__restrict__ xs = a.x + (int64_t)blockIdx.y * a.n * a.Cx;
-    double *__restrict__ ys = a.y + (int64_t)blockIdx.y * total * 2;
-    double v[2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-        v[c] = haas_column(a, xs, c, c == a.delayed_channel ? k - a.delay : k);   // np.roll: zeros wrap in
+    v[0] = c0; v[1] = c1;
     if (a.ms) {                                               // MS_to_LR, then the mono compensation (:226-229)
         const double l = v[0] + v[1], r = v[0] - v[1];
         v[0] = l; v[1] = r;
@@ -58,6 +51,20 @@ __global__ __launch_bounds__(kHaasThreads) void haas_kernel(const HArgs a)
         s = s * a.w_side;
         v[0] = m + s; v[1] = m - s;
     }
+}
+
+__global__ __launch_bounds__(kHaasThreads) void haas_kernel(const HArgs a)
+{
+    const int64_t total = a.n + a.delay;
+    const int64_t k = (int64_t)blockIdx.x * kHaasThreads + threadIdx.x;
+    if (k >= total) return;
+    const float *__restrict__ xs = a.x + (int64_t)blockIdx.y * a.n * a.Cx;
+    double *__restrict__ ys = a.y + (int64_t)blockIdx.y * total * 2;
+    double c[2], v[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+        c[j] = haas_column(a, xs, j, j == a.delayed_channel ? k - a.delay : k);   // np.roll: zeros wrap in
+    haas_frame(a, c[0], c[1], v);
     *(double2 *)(ys + 2 * k) = make_double2(v[0], v[1]);
 }
 

@@ -1,0 +1,259 @@
+// vnd_haas_scan.hpp - the Haas-delay optimiser's scan on the device (include/vnd_scan.h): the eight polar
+// moments (vnd_moments.hpp's quantities and order) of HaasEffect(delay d_f).decorrelate(x) for F delays of ONE
+// signal, without writing any delayed signal.
+//
+// Frame k of candidate f (k in [0, n + d_f)) is haas_column / haas_frame of vnd_haas.hpp at (k, k - d_f), so it is
+// bit-identical to the reference's float64 frame, and polar_add64 (vnd_polar.hpp) takes it in float64 as the
+// reference's polar_coordinates does.  The roll's zero prefix and the tail past the signal are ordinary frames.
+//
+// Shape: the hot loop is one float64 atan2 and one sqrt per (frame, candidate) - FP64 VALU, not memory.  A workgroup
+// owns a tile of kHsTile frames and a block of kHsBlock candidates.  The undelayed column of the tile is the same for
+// every candidate: each lane keeps its kHsPer frames of it in registers.  The delayed column is staged once in LDS
+// over the block's history window [t0 - dmax, t0 + kHsTile - dmin) (delays sorted ascending keep dmax - dmin small),
+// and the block's candidates sweep the tile from there.  A block whose window does not fit kHsWin reads the delayed
+// column through haas_column from global memory instead: the same values, so the same bits.
+//
+// Sums are float64 in a fixed order: per lane over its frames, a fixed shuffle tree and wave order per (tile,
+// candidate) partial, then a fixed-order reduction of candidate f's ceil((n + d_f) / kHsTile) partials.  Neither the
+// other candidates of a launch nor the launch's extent enter candidate f's order, so results are bit-identical
+// across runs and across how the candidates are split into launches.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "vnd_haas.hpp"
+#include "vnd_polar.hpp"
+#include "../../include/vnd_scan.h"
+
+namespace vnd {
+
+constexpr int kHsThreads = 256;
+constexpr int kHsPer = 8;                               // frames per lane and tile
+constexpr int kHsTile = kHsThreads * kHsPer;            // 2048 frames per workgroup
+constexpr int kHsBlock = 16;                            // candidates per workgroup
+constexpr int kHsWin = 4096;                            // staged delayed-column doubles (32 KB of LDS)
+
+struct HsArgs {
+    HArgs h;                                            // signal and the shared configuration (h.delay unused)
+    const int32_t *__restrict__ delays;                 // [F]
+    double *__restrict__ partials;                      // [F][cap][8]
+    double *__restrict__ moments;                       // [F][8]
+    int32_t F;
+    int64_t cap;                                        // partials per candidate the workspace holds
+};
+
+__device__ __forceinline__ int64_t hs_chunks(int64_t frames) { return (frames + kHsTile - 1) / kHsTile; }
+
+__device__ __forceinline__ bool hs_valid(const HsArgs &a, int32_t d)
+{
+    return d >= 0 && hs_chunks(a.h.n + d) <= a.cap;
+}
+
+// fixed-order sum (max for slot 4) of v over the workgroup; the result is valid in thread 0
+__device__ __forceinline__ void hs_block_reduce(double v[kMoments], double (*red)[kMoments])
+{
+#pragma unroll
+    for (int k = 0; k < kMoments; ++k) {
+#pragma unroll
+        for (int sh = 32; sh > 0; sh >>= 1) {
+            const double o = __shfl_xor(v[k], sh);
+            v[k] = k == 4 ? fmax(v[k], o) : v[k] + o;
+        }
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < kMoments; ++k) red[threadIdx.x >> 6][k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < kMoments; ++k) {
+            double t = red[0][k];
+            for (int w = 1; w < kHsThreads / 64; ++w) t = k == 4 ? fmax(t, red[w][k]) : t + red[w][k];
+            v[k] = t;
+        }
+    }
+    __syncthreads();                                    // red[] is free for the next candidate
+}
+
+// grid = (tiles, ceil(F / kHsBlock))
+__global__ __launch_bounds__(kHsThreads) void haas_scan_kernel(const HsArgs a)
+{
+    __shared__ double hist[kHsWin];
+    __shared__ double red[kHsThreads / 64][kMoments];
+    __shared__ int32_t dl[kHsBlock];
+    const int f0 = blockIdx.y * kHsBlock;
+    const int nb = min(kHsBlock, a.F - f0);
+    if ((int)threadIdx.x < nb) dl[threadIdx.x] = a.delays[f0 + threadIdx.x];
+    __syncthreads();
+    int32_t dmin = INT32_MAX, dmax = -1;                // over the block's valid candidates (wave-uniform)
+    for (int c = 0; c < nb; ++c) {
+        const int32_t d = dl[c];
+        if (hs_valid(a, d)) { dmin = min(dmin, d); dmax = max(dmax, d); }
+    }
+    const int64_t t0 = (int64_t)blockIdx.x * kHsTile;
+    if (dmax < 0 || t0 >= a.h.n + dmax) return;         // no candidate of the block reaches this tile
+    const HArgs &h = a.h;
+    const int cu = 1 - h.delayed_channel, cd = h.delayed_channel;
+    // the delayed column over [t0 - dmax, t0 + kHsTile - dmin)
+    const int64_t span = (int64_t)kHsTile + dmax - dmin;
+    const bool staged = span <= kHsWin;
+    if (staged) {
+        const int64_t k0 = t0 - dmax;
+        for (int i = threadIdx.x; i < span; i += kHsThreads) hist[i] = haas_column(h, h.x, cd, k0 + i);
+        __syncthreads();
+    }
+    double und[kHsPer];                                 // the undelayed column at this lane's frames
+#pragma unroll
+    for (int j = 0; j < kHsPer; ++j) und[j] = haas_column(h, h.x, cu, t0 + threadIdx.x + j * kHsThreads);
+
+    for (int c = 0; c < nb; ++c) {
+        const int32_t d = dl[c];
+        if (!hs_valid(a, d)) continue;
+        const int64_t len = h.n + d;
+        if (t0 >= len) continue;                        // (uniform) candidate f has no frame here
+        PolarAcc64 acc;
+#pragma unroll
+        for (int j = 0; j < kHsPer; ++j) {
+            const int64_t k = t0 + threadIdx.x + j * kHsThreads;
+            if (k < len) {
+                const double del = staged ? hist[(k - t0) + (dmax - d)] : haas_column(h, h.x, cd, k - d);
+                double v[2];
+                haas_frame(h, cu == 0 ? und[j] : del, cu == 0 ? del : und[j], v);
+                polar_add64(acc, v[0], v[1]);
+            }
+        }
+        double v[kMoments];
+        polar_values64(v, acc);
+        hs_block_reduce(v, red);
+        if (threadIdx.x == 0) {
+            double *p = a.partials + ((int64_t)(f0 + c) * a.cap + blockIdx.x) * kMoments;
+#pragma unroll
+            for (int k = 0; k < kMoments; ++k) p[k] = v[k];
+        }
+    }
+}
+
+// One workgroup per candidate: lanes stride over its ceil((n + d) / kHsTile) partials, then the fixed tree.
+// A candidate outside the contract (negative delay, or more partials than the workspace holds) gets NaN moments.
+__global__ __launch_bounds__(kHsThreads) void haas_scan_reduce_kernel(const HsArgs a)
+{
+    __shared__ double red[kHsThreads / 64][kMoments];
+    const int f = blockIdx.x;
+    const int32_t d = a.delays[f];
+    const bool ok = hs_valid(a, d);
+    const int64_t chunks = ok ? hs_chunks(a.h.n + d) : 0;
+    double v[kMoments];
+#pragma unroll
+    for (int k = 0; k < kMoments; ++k) v[k] = 0.0;
+    for (int64_t c = threadIdx.x; c < chunks; c += kHsThreads) {
+        const double *p = a.partials + ((int64_t)f * a.cap + c) * kMoments;
+#pragma unroll
+        for (int k = 0; k < kMoments; ++k) v[k] = k == 4 ? fmax(v[k], p[k]) : v[k] + p[k];
+    }
+    hs_block_reduce(v, red);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < kMoments; ++k) a.moments[(int64_t)f * kMoments + k] = ok ? v[k] : __builtin_nan("");
+    }
+}
+
+}  // namespace vnd
+
+static_assert(VND_HAAS_SCAN_MAX_DELAYS == 65535 * vnd::kHsBlock, "the grid's y extent bounds the delays per call");
+
+extern "C" {
+
+static vnd_status haas_scan_check(int64_t n_frames, int32_t n_delays, int32_t in_channels, int32_t delayed_channel)
+{
+    if (n_frames < 0 || n_delays < 0) return fail(VND_ERR_INVALID, "negative frame or delay count");
+    if (in_channels != 1 && in_channels != 2)
+        return fail(VND_ERR_INVALID, "a Haas scan takes a mono or stereo signal, got %d channels", in_channels);
+    if (delayed_channel != 0 && delayed_channel != 1)
+        return fail(VND_ERR_INVALID, "delayed_channel must be 0 or 1, got %d", delayed_channel);
+    if (n_delays > VND_HAAS_SCAN_MAX_DELAYS)
+        return fail(VND_ERR_UNSUPPORTED, "more than %d delays per call: split them", VND_HAAS_SCAN_MAX_DELAYS);
+    return VND_OK;
+}
+
+vnd_status vnd_haas_scan_workspace_bytes(int64_t n_frames, int32_t n_delays, int32_t max_delay, int64_t *bytes)
+{
+    if (!bytes) return fail(VND_ERR_INVALID, "null bytes");
+    *bytes = 0;
+    if (n_frames < 0 || n_delays < 0 || max_delay < 0)
+        return fail(VND_ERR_INVALID, "negative frame count, delay count or delay");
+    const int64_t chunks = (n_frames + max_delay + kHsTile - 1) / kHsTile;
+    if (chunks > (1 << 23)) return fail(VND_ERR_UNSUPPORTED, "signal plus delay above %lld frames", (long long)kHsTile << 23);
+    *bytes = chunks * n_delays * kMoments * (int64_t)sizeof(double);
+    return VND_OK;
+}
+
+vnd_status vnd_haas_scan_f64_dev(vnd_ctx *ctx, const float *x, int64_t n_frames, int32_t in_channels,
+                                 const int32_t *delays, int32_t n_delays, int32_t delayed_channel, int32_t ms_mode,
+                                 int32_t use_width, double width, double *moments, void *workspace,
+                                 int64_t workspace_bytes, void *stream_)
+{
+    if (!ctx) return fail(VND_ERR_INVALID, "null context");
+    vnd_status st = haas_scan_check(n_frames, n_delays, in_channels, delayed_channel);
+    if (st != VND_OK) return st;
+    if (workspace_bytes < 0) return fail(VND_ERR_INVALID, "negative workspace size");
+    if (n_delays == 0) return VND_OK;
+    if (!delays || !moments || (n_frames > 0 && !x)) return fail(VND_ERR_INVALID, "null signal, delay or moments pointer");
+    const int64_t per = (int64_t)n_delays * kMoments * (int64_t)sizeof(double);
+    const int64_t cap = std::min<int64_t>(workspace_bytes / per, 1 << 23);
+    if (cap > 0 && !workspace) return fail(VND_ERR_INVALID, "null workspace");
+    DeviceScope on(ctx->device);
+    hipStream_t stream = (hipStream_t)stream_;
+    HsArgs a{};
+    a.h.x = x; a.h.n = n_frames; a.h.Cx = in_channels; a.h.delayed_channel = delayed_channel;
+    a.h.ms = ms_mode ? 1 : 0; a.h.use_width = use_width ? 1 : 0; a.h.w_mid = 1.0 - width; a.h.w_side = width;
+    a.delays = delays; a.partials = (double *)workspace; a.moments = moments; a.F = n_delays; a.cap = cap;
+    if (cap > 0)
+        hipLaunchKernelGGL(haas_scan_kernel, dim3((unsigned)cap, (unsigned)((n_delays + kHsBlock - 1) / kHsBlock)),
+                           dim3(kHsThreads), 0, stream, a);
+    hipLaunchKernelGGL(haas_scan_reduce_kernel, dim3((unsigned)n_delays), dim3(kHsThreads), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return VND_OK;
+}
+
+vnd_status vnd_haas_scan_f64_host(vnd_ctx *ctx, const float *x, int64_t n_frames, int32_t in_channels,
+                                  const int32_t *delays, int32_t n_delays, int32_t delayed_channel, int32_t ms_mode,
+                                  int32_t use_width, double width, double *moments)
+{
+    if (!ctx) return fail(VND_ERR_INVALID, "null context");
+    vnd_status st = haas_scan_check(n_frames, n_delays, in_channels, delayed_channel);
+    if (st != VND_OK) return st;
+    if (n_delays == 0) return VND_OK;
+    if (!delays || !moments || (n_frames > 0 && !x)) return fail(VND_ERR_INVALID, "null signal, delay or moments pointer");
+    int32_t dmax = 0;
+    for (int32_t f = 0; f < n_delays; ++f) {
+        if (delays[f] < 0) return fail(VND_ERR_INVALID, "delay %d of candidate %d is negative", delays[f], f);
+        dmax = std::max(dmax, delays[f]);
+    }
+    int64_t ws = 0;
+    st = vnd_haas_scan_workspace_bytes(n_frames, n_delays, dmax, &ws);
+    if (st != VND_OK) return st;
+    HostLock lock(ctx->host_mutex);
+    DeviceScope on(ctx->device);
+    if (!on.ok) return fail(VND_ERR_HIP, "cannot select device %d", ctx->device);
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t x_bytes = (size_t)n_frames * in_channels * sizeof(float);
+    const size_t d_bytes = (size_t)n_delays * sizeof(int32_t);
+    const size_t m_bytes = (size_t)n_delays * kMoments * sizeof(double);
+    st = ensure_work(ctx, (size_t)ws + up(m_bytes) + up(d_bytes) + up(x_bytes));
+    if (st != VND_OK) return st;
+    char *work = ctx->work;
+    double *m_dev = (double *)(work + ws);
+    int32_t *d_dev = (int32_t *)(work + ws + up(m_bytes));
+    float *x_dev = (float *)(work + ws + up(m_bytes) + up(d_bytes));
+    if (x_bytes) HIP_TRY(hipMemcpyAsync(x_dev, x, x_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_dev, delays, d_bytes, hipMemcpyHostToDevice, ctx->stream));
+    st = vnd_haas_scan_f64_dev(ctx, x_dev, n_frames, in_channels, d_dev, n_delays, delayed_channel, ms_mode, use_width,
+                               width, m_dev, work, ws, ctx->stream);
+    if (st != VND_OK) return st;
+    HIP_TRY(hipMemcpyAsync(moments, m_dev, m_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return VND_OK;
+}
+
+}  // extern "C"

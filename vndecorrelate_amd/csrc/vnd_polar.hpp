@@ -39,4 +39,36 @@ __device__ __forceinline__ void polar_store(double *out, const PolarAcc &a)
 }
 
 
+// The float64 sibling, for float64 signals (HaasEffect's output, vnd_haas_scan.hpp): theta, r and every product in
+// float64 as NumPy does them on float64 arrays - np.arctan2, the fold with float64 pi, np.sqrt(l**2 + r**2) (two
+// roundings, then a correctly rounded sqrt; the build keeps mul and add apart).  atan2 follows C99 on signed zeros,
+// as NumPy's does: a silent frame folds to theta = +0 (from +-pi) or keeps its sign (+-0), so |theta| = 0.
+struct PolarAcc64 {
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, tmax = 0.0, lr = 0.0, ll = 0.0, rr = 0.0;
+};
+
+__device__ __forceinline__ void polar_add64(PolarAcc64 &a, double l, double r)
+{
+    const double kHalfPi = 1.5707963267948966, kPi = 3.141592653589793;          // np.pi / 2, np.pi
+    double th = atan2(l - r, l + r);
+    if (th < -kHalfPi) th = th + kPi;
+    else if (th > kHalfPi) th = th - kPi;
+    const double rad = sqrt(l * l + r * r);
+    const double t2 = th * th;
+    a.s0 += rad;
+    a.s1 += rad * th;
+    a.s2 += rad * t2;
+    a.s3 += rad * (t2 * th);
+    a.tmax = fmax(a.tmax, fabs(th));
+    a.lr += l * r;
+    a.ll += l * l;
+    a.rr += r * r;
+}
+
+__device__ __forceinline__ void polar_values64(double v[kMoments], const PolarAcc64 &a)
+{
+    v[0] = a.s0; v[1] = a.s1; v[2] = a.s2; v[3] = a.s3; v[4] = a.tmax; v[5] = a.lr; v[6] = a.ll; v[7] = a.rr;
+}
+
+
 }  // namespace vnd
