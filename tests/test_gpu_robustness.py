@@ -172,9 +172,9 @@ def test_first_paced_launch_of_a_fresh_context_inside_a_graph_capture(vnd):
 
 
 def test_an_unregistered_tuning_name_is_an_error_code_not_an_abort(vnd):
-    """Under VND_TUNING=1 (the test tier sets it) every tuning variable the library reads must be in its registry; a name
-    that is not used to abort() the host process in debug builds - it is VND_ERR_INVALID now, and after this module's
-    launches through every kernel family no such name has been recorded."""
+    """Under VND_TUNING=1 (the test tier sets it) the library reads its tuning variables through one registry (a snapshot
+    struct, csrc/vnd_spec.hpp); a name that was not in it used to abort() the host process in debug builds - a launch plan
+    now cannot read one, and it plans as ever."""
     from vndecorrelate_amd import _native
     from vndecorrelate_amd.taps import function_path_arrays
     arr = function_path_arrays(vnd.generate_velvet_noise(duration_seconds=0.03, num_impulses=30, num_outs=2, sample_rate_hz=48000, seed=1))

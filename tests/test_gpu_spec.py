@@ -698,3 +698,41 @@ def test_exact_stage_in_the_window_form_equals_the_generic_kernels(env, golden, 
             xs = x[pool - 1].cpu().numpy().copy()
             want = O.decorrelate(xs[:, 0] if cx == 1 else xs, sample_rate_hz=48000, seed=77, width=width, mode='MS')
             assert np.array_equal(outs['window'][pool - 1].cpu().numpy(), want, equal_nan=True)
+
+
+def test_a_changed_tuning_variable_builds_a_new_kernel(env, golden, tmp_path, monkeypatch):
+    """A table's modules are keyed by SpecConfig, and every tuning variable that shapes the generated source is a field of it: in a
+    tuning session (the tests run in one) changing VND_WIN_STAMPS or VND_WIN_SPLIT_LATE between two launches of one table builds a
+    new kernel with the new #define, never hands back the one already built - and every build still equals the C oracle."""
+    import torch
+    d, native, ctx = env
+    offs, idx, w = O.fir_to_taps(golden.fir('g48k_k30'))
+    table = _table(native, ctx, golden.fir('g48k_k30'))
+    monkeypatch.setenv('VND_SPEC_CACHE_DIR', str(tmp_path / 'cache'))
+    monkeypatch.setenv('VND_SPEC_DUMP', str(tmp_path / 'kernel.hip'))
+    monkeypatch.delenv('VND_WIN_STAMPS', raising=False)
+    monkeypatch.delenv('VND_WIN_SPLIT_LATE', raising=False)
+    pool, n = 4, 3 * 8192 + 100
+    x = torch.empty((pool, n, 2), dtype=torch.float32, device='cuda').uniform_(-1, 1)
+    want = c_oracle.convolve(x[pool - 1].cpu().numpy(), offs, idx, w)
+    s = torch.cuda.current_stream().cuda_stream
+    ctx.set_variant(FORCE | EXACT_TOO | span_bits(1, 2))
+    # (the exact mode on a function-path stereo table: the split 64-frame window form, whose late refill VND_WIN_SPLIT_LATE sets)
+    text = table.describe(pool, n, 2, d.MODE_EXACT)
+    assert 'frames_per_lane=64 ' in text and 'waves=split-by-channel' in text, text
+    sources = []
+    for key, value in ((None, None), ('VND_WIN_STAMPS', '2'), ('VND_WIN_SPLIT_LATE', '3')):
+        monkeypatch.delenv('VND_WIN_STAMPS', raising=False)
+        if key:
+            monkeypatch.setenv(key, value)
+        y = torch.empty((pool, n, 2), dtype=torch.float32, device='cuda')
+        table.convolve_device(x.data_ptr(), y.data_ptr(), pool, n, 2, mode=d.MODE_EXACT, stream=s)
+        torch.cuda.synchronize()
+        sources.append((tmp_path / 'kernel.hip').read_text())
+        assert np.array_equal(y[pool - 1].cpu().numpy(), want), key
+    ctx.set_variant(-1)
+    assert '#define VW_STAMPS 0' in sources[0] and '#define VW_LATE 8' in sources[0]
+    assert '#define VW_STAMPS 2' in sources[1] and '#define VW_LATE 8' in sources[1]
+    assert '#define VW_STAMPS 0' in sources[2] and '#define VW_LATE 3' in sources[2]
+    assert len(list((tmp_path / 'cache').glob('*.co'))) == 3
+    table.close()

@@ -332,7 +332,6 @@ static vnd_status describe(vnd_ctx *ctx, const vnd_taps *t, int64_t batch, int64
     // the pointers only decide alignment: describe the launch of 256-byte-aligned buffers (hipMalloc's)
     for (int attempt = 0; attempt < 8; ++attempt) {
         const SpecPlan sp = make_spec_plan(ctx, t, nullptr, nullptr, batch, n, C, Cx, mode, nullptr);
-        if (vnd_status ts = tuning_status(); ts != VND_OK) return ts;
         if (!sp.use) break;
         DeviceScope on(ctx->device);
         SpecModule *m = spec_module(ctx, t, sp.cfg, !sp.eager);
@@ -400,7 +399,6 @@ vnd_status vnd_prepare_launch(vnd_ctx *ctx, const vnd_taps *t, int64_t batch, in
     DeviceScope on(ctx->device);
     for (int attempt = 0; attempt < 8; ++attempt) {               // (a window geometry that does not build is skipped: plan again)
         const SpecPlan sp = make_spec_plan(ctx, t, nullptr, nullptr, batch, n, t->C, in_channels, mode, nullptr);
-        if (vnd_status ts = tuning_status(); ts != VND_OK) return ts;
         if (!sp.use) return VND_OK;
         SpecModule *m = spec_module(ctx, t, sp.cfg, false);
         if (m && !m->failed) return VND_OK;

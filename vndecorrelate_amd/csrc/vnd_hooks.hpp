@@ -75,36 +75,68 @@ vnd_status vnd_time_copy_f32_dev(vnd_ctx *ctx, const float *x, float *y, int64_t
     return VND_OK;
 }
 
+// the SpecTable of a CSR tap table as the source hooks take it (seg_offsets NULL: the function path): whole channel pairs, offsets
+// under 2^24, finite weights, segments that cover their channel's taps without an empty one
+static vnd_status spec_table_from_csr(int32_t C, const int32_t *tap_offsets, const int32_t *tap_index, const float *tap_weight,
+                                      const int32_t *seg_offsets, const int32_t *seg_end, const float *seg_gain, int32_t apply_gain,
+                                      SpecTable *t)
+{
+    if (C < 2 || (C & 1) || C > 64 || !tap_offsets || tap_offsets[0] != 0)
+        return fail(VND_ERR_INVALID, "the per-table kernels take a CSR tap table of whole channel pairs (2..64 channels)");
+    t->C = C;
+    t->tap_off.assign(tap_offsets, tap_offsets + C + 1);
+    const int32_t total = tap_offsets[C];
+    if (total <= 0 || !tap_index || !tap_weight) return fail(VND_ERR_INVALID, "empty tap table");
+    for (int32_t k = 0; k < total; ++k) {
+        if (tap_index[k] < 0 || tap_index[k] >= (1 << 24) || !std::isfinite(tap_weight[k]))
+            return fail(VND_ERR_UNSUPPORTED, "tap %d is outside the specialised kernel's scope", k);
+        t->max_index = std::max(t->max_index, tap_index[k]);
+    }
+    t->idx.assign(tap_index, tap_index + total);
+    t->w.assign(tap_weight, tap_weight + total);
+    t->w_raw = t->w;
+    if (!seg_offsets) return VND_OK;
+    if (!seg_end || !seg_gain || seg_offsets[0] != 0) return fail(VND_ERR_INVALID, "segment arrays incomplete");
+    t->has_seg = true;
+    t->apply_gain = apply_gain != 0;
+    t->seg_off.assign(seg_offsets, seg_offsets + C + 1);
+    t->seg_end.assign(seg_end, seg_end + seg_offsets[C]);
+    t->seg_gain.assign(seg_gain, seg_gain + seg_offsets[C]);
+    for (int c = 0; c < C; ++c) {
+        int32_t prev = tap_offsets[c];
+        for (int32_t sg = seg_offsets[c]; sg < seg_offsets[c + 1]; ++sg) {
+            if (seg_end[sg] <= prev || seg_end[sg] > tap_offsets[c + 1]) return fail(VND_ERR_UNSUPPORTED, "empty or misplaced segment");
+            prev = seg_end[sg];
+            if (apply_gain)
+                for (int32_t k = (sg == seg_offsets[c] ? tap_offsets[c] : seg_end[sg - 1]); k < seg_end[sg]; ++k) t->w[k] = tap_weight[k] * seg_gain[sg];
+        }
+        if (prev != tap_offsets[c + 1]) return fail(VND_ERR_UNSUPPORTED, "segments do not cover the channel's taps");
+    }
+    return VND_OK;
+}
+
+static vnd_status source_out(const std::string &src, char *text, int64_t capacity, int64_t *bytes)
+{
+    *bytes = (int64_t)src.size() + 1;
+    if (!text) return VND_OK;                    // size query
+    if (capacity < *bytes) return fail(VND_ERR_INVALID, "buffer too small: need %lld bytes", (long long)*bytes);
+    memcpy(text, src.c_str(), src.size() + 1);
+    return VND_OK;
+}
+
 vnd_status vnd_spec_kernel_source(int32_t C, const int32_t *tap_offsets, const int32_t *tap_index,
                                   const float *tap_weight, int32_t mode, char *text, int64_t capacity, int64_t *bytes)
 {
     if (mode != VND_MODE_FAST && mode != VND_MODE_EXACT)
         return fail(VND_ERR_INVALID, "the specialised kernel exists for VND_MODE_FAST and VND_MODE_EXACT");
     if (!bytes) return fail(VND_ERR_INVALID, "null bytes pointer");
-    if (C <= 0 || C % 2 != 0 || C > 64 || !tap_offsets || tap_offsets[0] != 0)
-        return fail(VND_ERR_INVALID, "the specialised kernel takes an even channel count (2..64) and a CSR tap table");
+    const Tuning tun = tuning_snapshot();
     SpecTable t;
-    t.C = C;
-    t.tap_off.assign(tap_offsets, tap_offsets + C + 1);
-    const int32_t total = tap_offsets[C];
-    if (total <= 0 || !tap_index || !tap_weight) return fail(VND_ERR_INVALID, "empty tap table");
-    for (int32_t k = 0; k < total; ++k) {
-        if (tap_index[k] < 0 || tap_index[k] >= (1 << 24) || !std::isfinite(tap_weight[k]))
-            return fail(VND_ERR_UNSUPPORTED, "tap %d is outside the specialised kernel's scope", k);
-        t.max_index = std::max(t.max_index, tap_index[k]);
-    }
-    t.idx.assign(tap_index, tap_index + total);
-    t.w.assign(tap_weight, tap_weight + total);
-    t.w_raw = t.w;
+    if (vnd_status st = spec_table_from_csr(C, tap_offsets, tap_index, tap_weight, nullptr, nullptr, nullptr, 0, &t); st != VND_OK) return st;
     SpecConfig cfg;
-    if (!spec_pick_config(t, 160 * 1024, 0, 0, &cfg, false, false, mode == VND_MODE_EXACT)) return fail(VND_ERR_UNSUPPORTED, "halo does not fit the LDS ring");
+    if (!spec_pick_config(t, tun, 160 * 1024, 0, 0, &cfg, false, false, mode == VND_MODE_EXACT)) return fail(VND_ERR_UNSUPPORTED, "halo does not fit the LDS ring");
     cfg.exact = mode == VND_MODE_EXACT ? 1 : 0;
-    const std::string src = spec_prologue(t, cfg) + kSpecKernelSource;
-    *bytes = (int64_t)src.size() + 1;
-    if (!text) return VND_OK;                    // size query
-    if (capacity < *bytes) return fail(VND_ERR_INVALID, "buffer too small: need %lld bytes", (long long)*bytes);
-    memcpy(text, src.c_str(), src.size() + 1);
-    return VND_OK;
+    return source_out(spec_prologue(t, cfg) + kSpecKernelSource, text, capacity, bytes);
 }
 
 vnd_status vnd_window_kernel_source(int32_t C, const int32_t *tap_offsets, const int32_t *tap_index,
@@ -116,76 +148,35 @@ vnd_status vnd_window_kernel_source(int32_t C, const int32_t *tap_offsets, const
     if (mode != VND_MODE_FAST && mode != VND_MODE_EXACT)
         return fail(VND_ERR_INVALID, "the specialised kernel exists for VND_MODE_FAST and VND_MODE_EXACT");
     if (!bytes) return fail(VND_ERR_INVALID, "null bytes pointer");
-    if (C < 2 || (C & 1) || C > 64 || !tap_offsets || tap_offsets[0] != 0)
-        return fail(VND_ERR_INVALID, "the window kernel takes a CSR tap table of whole channel pairs");
+    const Tuning tun = tuning_snapshot();
     SpecTable t;
-    t.C = C;
-    t.tap_off.assign(tap_offsets, tap_offsets + C + 1);
-    const int32_t total = tap_offsets[C];
-    if (total <= 0 || !tap_index || !tap_weight) return fail(VND_ERR_INVALID, "empty tap table");
-    for (int32_t k = 0; k < total; ++k) {
-        if (tap_index[k] < 0 || tap_index[k] >= (1 << 24) || !std::isfinite(tap_weight[k]))
-            return fail(VND_ERR_UNSUPPORTED, "tap %d is outside the specialised kernel's scope", k);
-        t.max_index = std::max(t.max_index, tap_index[k]);
-    }
-    t.idx.assign(tap_index, tap_index + total);
-    t.w.assign(tap_weight, tap_weight + total);
-    t.w_raw = t.w;
-    if (seg_offsets) {
-        if (!seg_end || !seg_gain || seg_offsets[0] != 0) return fail(VND_ERR_INVALID, "segment arrays incomplete");
-        t.has_seg = true;
-        t.apply_gain = apply_gain != 0;
-        t.seg_off.assign(seg_offsets, seg_offsets + C + 1);
-        t.seg_end.assign(seg_end, seg_end + seg_offsets[C]);
-        t.seg_gain.assign(seg_gain, seg_gain + seg_offsets[C]);
-        for (int c = 0; c < C; ++c) {
-            int32_t prev = tap_offsets[c];
-            for (int32_t sg = seg_offsets[c]; sg < seg_offsets[c + 1]; ++sg) {
-                if (seg_end[sg] <= prev || seg_end[sg] > tap_offsets[c + 1]) return fail(VND_ERR_UNSUPPORTED, "empty or misplaced segment");
-                prev = seg_end[sg];
-                if (apply_gain)
-                    for (int32_t k = (sg == seg_offsets[c] ? tap_offsets[c] : seg_end[sg - 1]); k < seg_end[sg]; ++k) t.w[k] = tap_weight[k] * seg_gain[sg];
-            }
-            if (prev != tap_offsets[c + 1]) return fail(VND_ERR_UNSUPPORTED, "segments do not cover the channel's taps");
-        }
-    }
+    if (vnd_status st = spec_table_from_csr(C, tap_offsets, tap_index, tap_weight, seg_offsets, seg_end, seg_gain, apply_gain, &t); st != VND_OK)
+        return st;
+    const int M = frames_per_lane, G = tun.win_g > 0 ? tun.win_g : 8;
     WinGeom g;
     // (tables of 4k channels: the quad / octet form, as the launches take it - VND_WIN_QUAD=0: channel pairs)
-    bool quad = C % 8 == 0 && spec_env("VND_WIN_QUAD", 1) != 0 && spec_env("VND_WIN_OCTET", 1) != 0 &&
-                win_geometry(t, frames_per_lane, threads, spec_env("VND_WIN_G", 8), false, 160 * 1024, &g, 2);
-    quad = quad || ((C % 4 == 0 || (C % 4 == 2 && C >= 6)) && spec_env("VND_WIN_QUAD", 1) != 0 &&
-                    win_geometry(t, frames_per_lane, threads, spec_env("VND_WIN_G", 8), false, 160 * 1024, &g, 1));
-    const bool split = !quad && C == 2 && spec_env("VND_WIN_SPLIT", 0) != 0 &&
-                       win_geometry(t, frames_per_lane, threads, spec_env("VND_WIN_G", 8), false, 160 * 1024, &g, 0, true);
+    bool quad = C % 8 == 0 && tun.win_quad != 0 && tun.win_octet != 0 && win_geometry(t, M, threads, G, false, 160 * 1024, &g, 2);
+    quad = quad || ((C % 4 == 0 || (C % 4 == 2 && C >= 6)) && tun.win_quad != 0 && win_geometry(t, M, threads, G, false, 160 * 1024, &g, 1));
+    // (VND_WIN_SPLIT=1: the split form of a stereo table)
+    const bool split = !quad && C == 2 && tun.win_split > 0 && win_geometry(t, M, threads, G, false, 160 * 1024, &g, 0, true);
     // (VND_WIN_SOURCE_FANOUT=1: the source of a mono input's fan-out launch through a stereo table - VW_BC)
-    const bool bc = C == 2 && spec_env("VND_WIN_SOURCE_FANOUT", 0) != 0;
-    if (bc && !win_geometry(t, frames_per_lane, threads, spec_env("VND_WIN_G", 8), true, 160 * 1024, &g, 0, split))
+    const bool bc = C == 2 && tun.win_source_fanout != 0;
+    if (bc && !win_geometry(t, M, threads, G, true, 160 * 1024, &g, 0, split))
         return fail(VND_ERR_UNSUPPORTED, "this window geometry does not fit the LDS");
-    if (!bc && !quad && !split && !win_geometry(t, frames_per_lane, threads, spec_env("VND_WIN_G", 8), false, 160 * 1024, &g))
+    if (!bc && !quad && !split && !win_geometry(t, M, threads, G, false, 160 * 1024, &g))
         return fail(VND_ERR_UNSUPPORTED, "this window geometry does not fit the LDS");
-    SpecConfig cfg;
-    cfg.nt = threads; cfg.win = frames_per_lane; cfg.win_g = g.G; cfg.win_lds = (int)g.lds_bytes(); cfg.win_q = g.quad; cfg.win_s = g.split;
-    cfg.la = spec_env("VND_SPEC_LA", (split && frames_per_lane >= 64) ? (mode == VND_MODE_EXACT ? 3 : 2) : (frames_per_lane >= 32 ? 4 : 6));      // (as win_pick_config)
-    cfg.win_xpose = spec_env("VND_WIN_XPOSE_PAIRS", 1) != 0 ? 1 : 0;
-    cfg.exact = mode == VND_MODE_EXACT ? 1 : 0;
-    cfg.bc = bc ? 1 : 0;
-    cfg.adds = (!cfg.exact && spec_env("VND_WIN_ADDS", 1) != 0 && win_adds_ok(t)) ? 1 : 0;      // (as make_spec_plan)
+    SpecConfig cfg = win_config(t, g, tun, mode == VND_MODE_EXACT, bc);
     // (VND_WIN_SOURCE_EPI=1: with the decorrelate stage's steps in the store phase - stereo: pointwise steps and block sums; quads /
     //  octets, fast mode: the normaliser's sums)
-    cfg.epi = (spec_env("VND_WIN_SOURCE_EPI", 0) != 0 && !bc && !split && (C == 2 || quad)) ? 1 : 0;
+    cfg.epi = (tun.win_source_epi != 0 && !bc && !split && (C == 2 || quad)) ? 1 : 0;
     if (lds_bytes_per_tile || fmas_per_tile) {
         size_t lb = 0, fm = 0;
-        if (cfg.exact) win_traffic_exact(t, frames_per_lane, &lb, &fm);
-        else win_traffic(t, frames_per_lane, &lb, &fm);
+        if (cfg.exact) win_traffic_exact(t, M, &lb, &fm);
+        else win_traffic(t, M, &lb, &fm);
         if (lds_bytes_per_tile) *lds_bytes_per_tile = (int64_t)lb;
         if (fmas_per_tile) *fmas_per_tile = (int64_t)fm;
     }
-    const std::string src = win_source(t, g, cfg);
-    *bytes = (int64_t)src.size() + 1;
-    if (!text) return VND_OK;                    // size query
-    if (capacity < *bytes) return fail(VND_ERR_INVALID, "buffer too small: need %lld bytes", (long long)*bytes);
-    memcpy(text, src.c_str(), src.size() + 1);
-    return VND_OK;
+    return source_out(win_source(t, g, cfg), text, capacity, bytes);
 }
 
 vnd_status vnd_code_object_private_bytes(const void *code, int64_t bytes, const char *kernel, int64_t *private_bytes)
@@ -199,20 +190,16 @@ vnd_status vnd_code_object_private_bytes(const void *code, int64_t bytes, const 
 vnd_status vnd_tuning_read(const char *name, int32_t fallback, int32_t *value)
 {
     if (!name || !value) return fail(VND_ERR_INVALID, "null name or value pointer");
-    // (the caller's pointer never reaches the process-wide record of spec_env: that one holds pointers into the library's own
-    //  literals only, and another thread's launch may be reading it - or have just written its own finding - right now)
-    const char *known = nullptr;
-    for (const char *k : kTuningNames) if (strcmp(k, name) == 0) known = k;
-    if (!known) { *value = fallback; return fail(VND_ERR_INVALID, "'%.64s' is not a registered tuning variable (kTuningNames, csrc/vnd_spec.hpp)", name); }
-    *value = spec_env(known, fallback);
-    return VND_OK;
+    for (const TuningName &v : kTuningNames)
+        if (strcmp(v.name, name) == 0) { *value = tuning_value(v, fallback); return VND_OK; }
+    *value = fallback;
+    return fail(VND_ERR_INVALID, "'%.64s' is not a registered tuning variable (kTuningNames, csrc/vnd_spec.hpp)", name);
 }
 
 vnd_status vnd_set_variant(vnd_ctx *ctx, int32_t variant)
 {
     if (!ctx) return fail(VND_ERR_INVALID, "null context");
-    ctx->variant = variant;
-    ctx->variant_nofuse = (variant >= 0 && ((variant >> 24) & 1)) ? 1 : 0;   // bit 24: unfused epilogue
+    ctx->variant = decode_variant(variant);
     return VND_OK;
 }
 

@@ -70,6 +70,35 @@ static vnd_status fail(vnd_status st, const char *fmt, ...)
 // ------------------------------------------------------------------------------
 // objects
 // ------------------------------------------------------------------------------
+// The variant word of vnd_set_variant (tuning runs and tests: -1, any negative word, leaves every choice automatic), decoded once.
+// 0 in a field: automatic.  Bit 17 has two readers: the generic fast kernel's thread count and the RMS sums' form.
+struct Variant {
+    int rr = 0;                  // bits 0-4: frame pairs per lane
+    int win = 0;                 // bits 5-7: the window form off (1), or 16 (2), 32 (3), 64 (4) frames per lane
+    int cg = 0;                  // bits 8-11: channels per workgroup of the generic kernels
+    bool direct = false;         // bit 12: the direct kernel
+    bool spec_exact = false;     // bit 15: the exact mode specialises whatever VND_SPEC_EXACT says
+    int fast_nt = 0;             // bits 16-17: threads of the generic fast kernel (0: 256, 1: 128, 2: 512, 3: 1024)
+    bool par_sums = false, no_par_sums = false;      // bit 17 / bit 19: the exact RMS sums block-parallel / per stream whatever the batch
+    int min_span = 0;            // bits 20-22: shortest span of the per-table kernels, in tiles
+    bool force = false;          // bit 23: specialise however little work there is
+    bool nofuse = false;         // bit 24: the decorrelate epilogue and the scan's moments as passes of their own
+    bool spec_off = false;       // bit 25: the generic kernels only
+    int dd = 0;                  // bits 26-27: tiles prefetched ahead (pair-read form)
+    int rounds = 0;              // bits 28-30: spans per resident slot
+};
+
+static Variant decode_variant(int32_t v)
+{
+    Variant d;
+    if (v < 0) return d;
+    auto bits = [v](int lo, int width) { return (int)((v >> lo) & ((1 << width) - 1)); };
+    d.rr = bits(0, 5); d.win = bits(5, 3); d.cg = bits(8, 4); d.direct = bits(12, 1); d.spec_exact = bits(15, 1);
+    d.fast_nt = bits(16, 2); d.par_sums = bits(17, 1); d.no_par_sums = bits(19, 1); d.min_span = bits(20, 3); d.force = bits(23, 1);
+    d.nofuse = bits(24, 1); d.spec_off = bits(25, 1); d.dd = bits(26, 2); d.rounds = bits(28, 3);
+    return d;
+}
+
 struct vnd_ctx {
     int device = 0;
     hipDeviceProp_t prop{};
@@ -81,8 +110,7 @@ struct vnd_ctx {
     size_t scratch_elems = 0;
     char *work = nullptr;         // grow-only workspace of the *_host entry points
     size_t work_bytes = 0;
-    int variant = -1;
-    int variant_nofuse = 0;       // tuning: 1 = keep the decorrelate epilogue as separate passes
+    Variant variant;              // vnd_set_variant
     // One *_host call at a time per context: they share the stream, the staging buffers and the
     // workspace.  The reference's functions are re-entrant (decorrelation.py:630-660), and ctypes /
     // cgo / JNI callers run without a global lock, so the library serialises them itself.

@@ -13,6 +13,7 @@ struct Plan {
     size_t lds_bytes = 0;
     uint32_t nblocks = 0;
     int tiles = 0, groups = 1;
+    bool stream_out = false;                    // the output streamed past the caches (KArgs::stream_out)
 };
 
 typedef void (*kern_t)(const KArgs);
@@ -177,33 +178,35 @@ static size_t lds_need(int nt, int cg, int r, int max_index, bool bc = false)
 static const int kFastR[] = {8, 6, 4, 3, 2, 1};
 static const int kOrderedR[] = {8, 4, 2, 1};
 
-// variant word (vnd_set_variant): bits 0-4 frame pairs per lane (0 = auto),
-// bits 8-11 channels per workgroup (0 = auto), bit 12 direct,
-// bits 16-17 threads per workgroup of the fast kernel (0: 256, 1: 128, 2: 512, 3: 1024).
+// the variant's frame pairs per lane, channels per workgroup, direct kernel and fast kernel's threads (Variant) apply.
 // Cx = interleaved input channels (== C for the plain call; a divisor of C for a fan-out).
 static Plan make_plan(const vnd_ctx *ctx, const vnd_taps *t, int64_t batch, int64_t n, int C, int mode, int Cx)
 {
     Plan p;
-    const int v = ctx->variant;
+    const Variant &v = ctx->variant;
+    const Tuning tun = tuning_snapshot();
+    // an output beyond what the L2 + Infinity Cache could hand to a consumer is streamed past them
+    // (only where a workgroup writes whole frames: pieces of a frame written past the caches by different
+    // workgroups reach HBM as separate partial writes: cg != C, below)
+    p.stream_out = batch * n * C * (int64_t)sizeof(float) >= ((int64_t)64 << 20) && !tun.no_nt;
     const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
     const bool fast = mode == VND_MODE_FAST;
     // A term whose tap reaches past the end of the stream DROPS in the reference (decorrelation.py:656-658).
     // The LDS kernels read such a sample as 0.0f, which is the same thing for a finite weight only
     // (0 * inf = NaN), so a table with a non-finite weight takes the direct kernel, which tests the index.
-    const bool force_direct = (v >= 0 && ((v >> 12) & 1)) || t->nonfinite || !t->lds_images;
-    int cg = (v >= 0 && ((v >> 8) & 15)) ? ((v >> 8) & 15) : 0;
+    const bool force_direct = v.direct || t->nonfinite || !t->lds_images;
+    int cg = v.cg;
     if (cg == 0) cg = (C % 2 == 0) ? 2 : 1;
     if (C % cg != 0 || (cg != 1 && cg != 2 && cg != 4)) cg = 1;
     int nt = kOrderedThreads;
     if (fast) {
-        const int sel = v >= 0 ? ((v >> 16) & 3) : 0;
-        nt = sel == 1 ? 128 : sel == 2 ? 512 : sel == 3 ? 1024 : 256;
+        nt = v.fast_nt == 1 ? 128 : v.fast_nt == 2 ? 512 : v.fast_nt == 3 ? 1024 : 256;
     }
     // a workgroup's cg output channels must come from cg consecutive input channels, or all from
     // the one channel of a mono input (bc: staged once)
     bool bc = false;
     if (Cx != C) {
-        if (Cx == 1 && C % 2 == 0 && !(v >= 0 && ((v >> 8) & 15) == 1)) { bc = true; cg = 2; nt = 256; }
+        if (Cx == 1 && C % 2 == 0 && v.cg != 1) { bc = true; cg = 2; nt = 256; }
         else if (Cx % cg != 0) cg = (Cx % 2 == 0 && cg >= 2) ? 2 : 1;
     }
     const int *sizes = fast ? kFastR : kOrderedR;
@@ -211,7 +214,7 @@ static Plan make_plan(const vnd_ctx *ctx, const vnd_taps *t, int64_t batch, int6
     const size_t limit = (size_t)ctx->lds_limit - 1024;       // the kernels' static LDS (reduction scratch) shares the 160 KiB
     auto fits = [&](int r_) { return lds_need(nt, cg, r_, t->max_index, bc) <= limit; };
 
-    int r = (v >= 0) ? (v & 31) : 0;
+    int r = v.rr;
     if (r != 0) {
         bool known = false;
         for (int i = 0; i < nsizes; ++i) known |= sizes[i] == r;
@@ -246,6 +249,7 @@ static Plan make_plan(const vnd_ctx *ctx, const vnd_taps *t, int64_t batch, int6
         p.nblocks = (uint32_t)std::min<int64_t>(std::max<int64_t>(blocks, 1), (int64_t)cus * 32);
         return p;
     }
+    if (cg != C && !tun.force_nt) p.stream_out = false;
     const int64_t T = (int64_t)2 * nt * r;
     p.nt = nt; p.cg = cg; p.r = r; p.bc = bc;
     p.W = (int)T + halo_of(t->max_index);
@@ -254,15 +258,6 @@ static Plan make_plan(const vnd_ctx *ctx, const vnd_taps *t, int64_t batch, int6
     p.groups = C / cg;
     p.nblocks = (uint32_t)(batch * p.tiles * p.groups);
     return p;
-}
-
-// VND_TUNING=1 sessions: a tuning variable the library read that is not in kTuningNames (vnd_spec.hpp) is a bug in the library;
-// the entry point that planned the launch reports it as VND_ERR_INVALID - it never ends the host process
-static vnd_status tuning_status()
-{
-    const char *name = spec_unregistered_name().load();
-    if (name == nullptr) return VND_OK;
-    return fail(VND_ERR_INVALID, "tuning variable %s is read by the library but not registered in kTuningNames", name);
 }
 
 static vnd_status check_shape(const vnd_ctx *ctx, const vnd_taps *t, int64_t batch, int64_t n,
@@ -297,6 +292,7 @@ struct SpecPlan {
     // chunk_len0 of them, the second the rest (0: uniform spans)
     int chunk_tiles = 0, chunk_len0 = 0, chunks_per_stream = 0, cus_per_xcd = 0, stagger_ticks = 0;
     int bal_total = 0;              // > 0: the BALANCED cut - every workgroup a contiguous range of the pool's streams x tiles_total tiles
+    bool pace = false;              // pacing of co-resident workgroups (VWArgs::pace)
     const char *why = "";           // when !use: the reason, for vnd_describe_launch
 };
 
@@ -326,15 +322,14 @@ struct EpiFuse {                 // non-null => launch the fused-epilogue instan
     bool spec_only = false;
 };
 
-// variant word, specialised kernel: bit 25 forces the generic kernel; bits 26-27 prefetch depth
-// (0 = auto), bits 28-30 spans per resident slot ("rounds", 0 = auto); bits 0-4 = pairs per lane as ever;
-// bits 20-22 shortest span in tiles (0 = auto, 8) and bit 23 "specialise however little work there
-// is" - the two that let the tests drive span seams and tiny signals through this kernel.
+// the variant (Variant) applies here with its pairs per lane, window frames per lane, prefetch depth, rounds, shortest span (the
+// tests drive span seams through it), force (tiny signals) and spec_off / spec_exact
 static SpecPlan make_spec_plan(const vnd_ctx *ctx, const vnd_taps *t, const float *x, const float *y, int64_t batch,
                                int64_t n, int C, int Cx, int mode, const EpiFuse *epi)
 {
     SpecPlan p;
-    const int v = ctx->variant;
+    const Variant &v = ctx->variant;
+    const Tuning tun = tuning_snapshot();
     if (mode != VND_MODE_FAST && mode != VND_MODE_EXACT) { p.why = "neither the fast nor the exact mode"; return p; }
     // a fused epilogue is within scope when it is the pointwise steps alone (no sums, no moments sink) on a stereo output:
     // they ride in the per-table kernels' store phase (VS_EPI)
@@ -353,30 +348,24 @@ static SpecPlan make_spec_plan(const vnd_ctx *ctx, const vnd_taps *t, const floa
     // VND_MODE_EXACT specialises by default as well: with the shifted plane copies (odd offsets as aligned pairs) the per-table
     // kernel is ahead of the generic ordered one by 24 % on a function-path table, 37 % on a class-path one and 23-50 % on a mono
     // input fanned out (cfg2 pool; tools/closed/exact_geometry_try.py, tools/closed/fanout_spec_try.py).  VND_SPEC_EXACT=0 keeps the generic kernel.
-    if (mode == VND_MODE_EXACT && !(v >= 0 && ((v >> 15) & 1))) {
+    if (mode == VND_MODE_EXACT && !v.spec_exact) {
         static const bool off = [] { const char *e = getenv("VND_SPEC_EXACT"); return e && e[0] == '0'; }();
         if (off) { p.why = "exact mode specialisation switched off"; return p; }
     }
-    const bool force = v >= 0 && ((v >> 23) & 1);
-    // the fast mode's window forms in the reference's class-path association (adds inside a segment, the gain ratio once per segment:
-    // vnd_win.hpp, win_adds_ok) wherever the table has few distinct |w| - every generated table has; VND_WIN_ADDS=0: one FMA per tap
-    const int adds_now = (mode == VND_MODE_FAST && spec_env("VND_WIN_ADDS", 1) != 0 && win_adds_ok(t->spec_table)) ? 1 : 0;
-    if (spec_disabled_by_env() || (v >= 0 && ((v >> 25) & 1))) { p.why = "disabled"; return p; }
+    if (spec_disabled_by_env() || v.spec_off) { p.why = "disabled"; return p; }
     // access shape: 16 bytes per frame pair (stereo) or 8 per frame, from every stream's first sample
     const uintptr_t align = C == 2 ? 16 : 8, align_x = bc ? 8 : align;
     if (((uintptr_t)y & (align - 1)) || ((uintptr_t)x & (align_x - 1))) { p.why = "unaligned base"; return p; }
     if (batch > 1 && (((uint64_t)n * C * 4) % align != 0 || ((uint64_t)n * Cx * 4) % align_x != 0)) { p.why = "unaligned streams"; return p; }
     // (before any geometry is searched: below about two million frames per channel pair the generic kernels - many small workgroups -
     //  stay ahead, and a tiny launch should not pay for a plan it will discard)
-    if (!force && batch * (C / 2) * n < 2000000) { p.why = "too little work for persistent workgroups"; return p; }
-    const int rr_hint = (v >= 0 && (v & 31) != 0 && (v & 31) <= 8) ? (v & 31) : 0;
-    const int dd_hint = v >= 0 ? ((v >> 26) & 3) : 0;
-    // variant bits 5-7: window form off (1), or 16 (2), 32 (3), 64 (4) frames per lane; VND_WIN_M: the default (32; 0 = pair-read kernel)
-    const int win_env = spec_env("VND_WIN_M", 32);
-    const int vw = v >= 0 ? ((v >> 5) & 7) : 0;
-    const int win_m = vw == 1 ? 0 : (vw == 2 ? 16 : (vw == 3 ? 32 : (vw == 4 ? 64 : win_env)));
+    if (!v.force && batch * (C / 2) * n < 2000000) { p.why = "too little work for persistent workgroups"; return p; }
+    const int rr_hint = v.rr <= 8 ? v.rr : 0;
+    // variant: window form off (1), or 16 (2), 32 (3), 64 (4) frames per lane; VND_WIN_M: the default (32; 0 = pair-read kernel)
+    const int vw = v.win;
+    const int win_m = vw == 1 ? 0 : (vw == 2 ? 16 : (vw == 3 ? 32 : (vw == 4 ? 64 : tun.win_m)));
     // VND_MODE_EXACT in the window form: tables whose weights let the sign ride in the add (finite) - all in spec scope
-    const int win_exact_env = spec_env("VND_WIN_EXACT", 1);       // 0: never, 1: where it pays (the table knows), 2: always
+    const int win_exact_env = tun.win_exact;       // 0: never, 1: where it pays (the table knows), 2: always
     const bool win_exact = vw >= 2 || win_exact_env == 2 || (win_exact_env == 1 && t->win_exact_pays);
     // 1536-frame tiles (cfg4's 32-tile streams included: 0.167 vs 0.179 ms) unless a span would be shorter than 12 of them
     for (int attempt = 0; attempt < 2; ++attempt) {
@@ -391,24 +380,22 @@ static SpecPlan make_spec_plan(const vnd_ctx *ctx, const vnd_taps *t, const floa
     //  ask for the window form: there a workgroup moves 8 bytes of every frame, the memory pipeline's time per useful byte
     //  is 2-4x a stereo signal's and the window form's few waves per CU do not hide it - cfg5 0.54 ms against 0.45, while
     //  the same tables on planar channel pairs run 0.33 against 0.39: tools/closed/c8_win_try.py, profiles/r03_cfg5_request_floor.txt)
-    const int win_wide_env = spec_env("VND_WIN_WIDE", 0);
-    const bool win_c = C == 2 || (C % 2 == 0 && (win_wide_env != 0 || vw >= 2));
+    const bool win_c = C == 2 || (C % 2 == 0 && (tun.win_wide != 0 || vw >= 2));
     // signals of 4k channels: the window form on channel QUADS / OCTETS (VW_Q, vw_span_qc: a workgroup moves 16 / 32 bytes of every
     // frame, a wave per channel) - VND_WIN_QUAD=0 keeps the pair-read kernel (or, with VND_WIN_WIDE=1 / variant bits 5-7, the
     // window form on channel pairs)
     // (4k + 2 channels - 6, 10, ... - ride the quad form too: k quads and one more from channel C - 4, overlapping in one pair)
-    const bool win_quad = (C % 4 == 0 || (C % 4 == 2 && C >= 6 && epi == nullptr)) && Cx == C && (!pointwise || sums_q) && spec_env("VND_WIN_QUAD", 1) != 0;
+    const bool win_quad = (C % 4 == 0 || (C % 4 == 2 && C >= 6 && epi == nullptr)) && Cx == C && (!pointwise || sums_q) && tun.win_quad != 0;
     // (a geometry whose build failed or spilled is remembered in the table's module map: skipped, the next best taken)
-    const bool nt_big = batch * n * C * (int64_t)sizeof(float) >= ((int64_t)spec_env("VND_NT_MIN_MB", 64) << 20);
+    const bool nt_big = batch * n * C * (int64_t)sizeof(float) >= ((int64_t)tun.nt_min_mb << 20);
     auto nt_stores_of = [&](const SpecConfig &c) {
         // a channel pair (or quad) is a piece of a frame: let L2 merge the pieces - unless the quad IS the frame
-        if (C != 2 && !(c.win_q && C == 4 * c.win_q) && !spec_env("VND_FORCE_NT", 0)) return 0;
+        if (C != 2 && !(c.win_q && C == 4 * c.win_q) && !tun.force_nt) return 0;
         return nt_big ? 1 : 0;
     };
     auto rejected = [&](const SpecConfig &c0) {
         SpecConfig c = c0;
-        c.nt_stores = nt_stores_of(c0); c.exact = mode == VND_MODE_EXACT ? 1 : 0; c.epi = pointwise ? 1 : 0; c.bc = bc ? 1 : 0;
-        c.adds = c0.win ? adds_now : 0;
+        c.nt_stores = nt_stores_of(c0); c.epi = pointwise ? 1 : 0;      // (the rest as win_config completed it)
         std::lock_guard<std::mutex> g(const_cast<vnd_taps *>(t)->spec_mutex);
         auto it = t->spec_modules.find(c);
         return it != t->spec_modules.end() && !it->second->building && it->second->failed;
@@ -416,11 +403,11 @@ static SpecPlan make_spec_plan(const vnd_ctx *ctx, const vnd_taps *t, const floa
     const bool win_mode_ok = win_m > 0 && rr_hint == 0 && (mode == VND_MODE_FAST || win_exact || (win_quad && win_exact_env != 0));
     // (8k channels: two neighbouring quads - with 8 channels whole frames, whole cache lines - per workgroup of 512 lanes when that ring
     //  fits, else and for 4k channels a quad per workgroup of 256; a wave per CHANNEL, 32-frame runs: vw_span_qc)
-    const int quad_m = vw >= 2 ? win_m : spec_env("VND_WIN_QUAD_M", 32);
-    if (win_mode_ok && win_quad && C % 8 == 0 && spec_env("VND_WIN_OCTET", 1) != 0)
-        picked = win_pick_config(t->spec_table, (size_t)ctx->lds_limit, quad_m, attempt == 1, false, &p.cfg, rejected, 2, false, mode == VND_MODE_EXACT);
+    const int quad_m = vw >= 2 ? win_m : tun.win_quad_m;
+    if (win_mode_ok && win_quad && C % 8 == 0 && tun.win_octet != 0)
+        picked = win_pick_config(t->spec_table, tun, (size_t)ctx->lds_limit, quad_m, attempt == 1, false, &p.cfg, rejected, 2, false, mode == VND_MODE_EXACT);
     if (!picked && win_mode_ok && win_quad)
-        picked = win_pick_config(t->spec_table, (size_t)ctx->lds_limit, quad_m, attempt == 1, false, &p.cfg, rejected, 1, false, mode == VND_MODE_EXACT);
+        picked = win_pick_config(t->spec_table, tun, (size_t)ctx->lds_limit, quad_m, attempt == 1, false, &p.cfg, rejected, 1, false, mode == VND_MODE_EXACT);
     // plain stereo: the waves SPLIT over the two channels (VW_S, vw_span_s: a lane carries ONE channel's accumulators).
     // VND_WIN_SPLIT: 0 never; 1 (default) where it pays; 2 always, with the frames per lane of the plain form.
     //  * 32-frame runs, three waves per SIMD (three workgroups of 256 lanes per CU): cfg3 fast +2.0 / +2.4 % on two boxes, but
@@ -434,13 +421,13 @@ static SpecPlan make_spec_plan(const vnd_ctx *ctx, const vnd_taps *t, const floa
     // ... and in the exact mode for function-path tables (one ascending pass per channel: win_taps_function_exact_merged - the reads and
     // the products f32(x * |w|) shared by both channels, every sum the same operation as in a pass per channel); VND_WIN_EXACT_MERGED=0
     // keeps the split form with the input staged into both plane sets
-    const bool merged_exact = bc && mode == VND_MODE_EXACT && win_exact && spec_env("VND_WIN_EXACT_MERGED", 1) != 0 && win_exact_merged_ok(t->spec_table);
+    const bool merged_exact = bc && mode == VND_MODE_EXACT && win_exact && tun.win_exact_merged != 0 && win_exact_merged_ok(t->spec_table);
     if (!picked && win_mode_ok && bc && (mode == VND_MODE_FAST || merged_exact) && vw == 0)
-        picked = win_pick_config(t->spec_table, (size_t)ctx->lds_limit, win_m, attempt == 1, true, &p.cfg, rejected);
-    const int split_env = spec_env("VND_WIN_SPLIT", 1);
+        picked = win_pick_config(t->spec_table, tun, (size_t)ctx->lds_limit, win_m, attempt == 1, true, &p.cfg, rejected, 0, false, mode == VND_MODE_EXACT);
+    const int split_env = tun.win_split < 0 ? 1 : tun.win_split;
     // (a mono input fanned out rides the same form: its one channel staged into both plane sets, VW_BC - cfg1's shape 0.177 -> 0.15 ms
     //  for 128 x 10 s against the pair-read form, tools/closed/fanout_win_try.py; VND_WIN_SPLIT_FANOUT=0 keeps that)
-    const bool split_scope = C == 2 && (Cx == 2 || (bc && spec_env("VND_WIN_SPLIT_FANOUT", 1) != 0)) && !pointwise;
+    const bool split_scope = C == 2 && (Cx == 2 || (bc && tun.win_split_fanout != 0)) && !pointwise;
     //    In the FAST mode (E and P: 128 accumulator registers) the 64-frame split form needs its refill loaded late (VW_LATE: 15
     //    of a wave's 16 accesses per tile at the start of the store phase that consumes them, not a tile ahead) and the per-access
     //    constants kept out of the tile loop's registers: cfg3 +3-4.5 % (0.457 -> 0.437 ms), cfg2 +3.8 % (0.195 -> 0.188 ms,
@@ -449,19 +436,19 @@ static SpecPlan make_spec_plan(const vnd_ctx *ctx, const vnd_taps *t, const floa
     //    Class-path tables in the exact mode (a segment sum and an output sum per pair: the fast mode's register count) take it with
     //    the fast mode's late refill since round 6 (VND_WIN_SPLIT_CLASS=0: the plain 32-frame form)
     if (!picked && win_mode_ok && split_scope && split_env == 1 && vw == 0 &&
-        ((exact_now && (!t->spec_table.has_seg || spec_env("VND_WIN_SPLIT_CLASS", 1) != 0)) || mode == VND_MODE_FAST))
-        picked = win_pick_config(t->spec_table, (size_t)ctx->lds_limit, 64, attempt == 1, bc, &p.cfg, rejected, 0, true, exact_now);
+        ((exact_now && (!t->spec_table.has_seg || tun.win_split_class != 0)) || mode == VND_MODE_FAST))
+        picked = win_pick_config(t->spec_table, tun, (size_t)ctx->lds_limit, 64, attempt == 1, bc, &p.cfg, rejected, 0, true, exact_now);
     if (!picked && win_mode_ok && split_scope && split_env == 2)
-        picked = win_pick_config(t->spec_table, (size_t)ctx->lds_limit, win_m, attempt == 1, bc, &p.cfg, rejected, 0, true, exact_now);
+        picked = win_pick_config(t->spec_table, tun, (size_t)ctx->lds_limit, win_m, attempt == 1, bc, &p.cfg, rejected, 0, true, exact_now);
     // (a mono input under the decorrelate stage's pointwise steps, exact mode - VelvetNoise.decorrelate of mono signals,
     //  decorrelation.py:428-440 - rides the plain form too since round 6: both channels' passes read the one plane set, the store
     //  phase has the mono frame for the side-channel encode and leaves the block sums of the exact RMS; until then the pair-read form
     //  plus a pass of its own for those sums: 128 x 10 s 0.916 -> 0.655 ms, bit-identical; pools of more than 320 streams, whose sums
     //  run per stream and take no block sums, stay 2 % ahead in the pair-read form and keep it: profiles/r06_f1_mono.txt)
-    if (!picked && win_mode_ok && win_c && (!bc || vw >= 2 || (pointwise2 && epi->blk_sum != nullptr && mode == VND_MODE_EXACT && spec_env("VND_WIN_FANOUT_EPI", 1) != 0)))
-        picked = win_pick_config(t->spec_table, (size_t)ctx->lds_limit, win_m, attempt == 1, bc, &p.cfg, rejected);
+    if (!picked && win_mode_ok && win_c && (!bc || vw >= 2 || (pointwise2 && epi->blk_sum != nullptr && mode == VND_MODE_EXACT && tun.win_fanout_epi != 0)))
+        picked = win_pick_config(t->spec_table, tun, (size_t)ctx->lds_limit, win_m, attempt == 1, bc, &p.cfg, rejected, 0, false, mode == VND_MODE_EXACT);
     if (sums_q && !(picked && p.cfg.win_q)) { p.why = "the sums of a 4k-channel table ride in the quad / octet form only"; return p; }
-    if (!picked && !spec_pick_config(t->spec_table, (size_t)ctx->lds_limit, rr_hint, dd_hint, &p.cfg, attempt == 1 || C != 2, bc, mode == VND_MODE_EXACT)) { p.why = "halo does not fit the ring"; return p; }
+    if (!picked && !spec_pick_config(t->spec_table, tun, (size_t)ctx->lds_limit, rr_hint, v.dd, &p.cfg, attempt == 1 || C != 2, bc, mode == VND_MODE_EXACT)) { p.why = "halo does not fit the ring"; return p; }
     const int64_t T = p.cfg.tile();
     const int64_t tiles_total = (n + T - 1) / T;
     const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
@@ -474,20 +461,19 @@ static SpecPlan make_spec_plan(const vnd_ctx *ctx, const vnd_taps *t, const floa
     // slot; with less, shorter spans (down to 2 tiles) so that the chip still fills - a lone 60 s stream then runs 1.1x
     // (fast) to 1.75x (exact, 128 taps) faster than through the generic kernels, tools/closed/single_stream_try.py - and below
     // about two million frames per channel pair the generic kernels (many small workgroups) stay ahead
-    int64_t min_span = (v >= 0 && ((v >> 20) & 7)) ? ((v >> 20) & 7) : 8;
-    if (!(v >= 0 && ((v >> 20) & 7)))
+    int64_t min_span = v.min_span;
+    if (min_span == 0)
         min_span = std::min<int64_t>(8, std::max<int64_t>(2, units * tiles_total / (2 * resident)));
     const int64_t pair_frames = batch * (C / 2) * n;           // the work, in frames per channel pair (whatever a workgroup's unit is)
-    if (!force && pair_frames < 2000000) { p.why = "too little work for persistent workgroups"; return p; }
-    p.eager = force || pair_frames >= 12000000;                // enough work to be worth building the kernel for
+    if (!v.force && pair_frames < 2000000) { p.why = "too little work for persistent workgroups"; return p; }
+    p.eager = v.force || pair_frames >= 12000000;                // enough work to be worth building the kernel for
     // Spans per stream: the workgroups are equally long, so the grid should fill the resident slots
     // a whole number of times ("rounds") - 1.5 rounds cost as much as 2.  Fewest spans (longest
     // rings) whose last round is at least 95 % full, else the fullest.
-    const int rounds = (v >= 0 && ((v >> 28) & 7)) ? ((v >> 28) & 7) : 0;
     const int64_t max_spans = std::max<int64_t>(1, tiles_total / min_span);
     int64_t spans = 1;
-    if (rounds > 0) {
-        spans = std::min(std::max<int64_t>(1, resident * rounds / units), max_spans);
+    if (v.rounds > 0) {
+        spans = std::min(std::max<int64_t>(1, resident * v.rounds / units), max_spans);
     } else {
         double best = -1.0;
         const int64_t limit = std::min<int64_t>(max_spans, std::max<int64_t>(1, 4 * resident / units + 1));
@@ -519,9 +505,8 @@ static SpecPlan make_spec_plan(const vnd_ctx *ctx, const vnd_taps *t, const floa
     p.cfg.exact = mode == VND_MODE_EXACT ? 1 : 0;
     p.cfg.epi = pointwise ? 1 : 0;
     p.cfg.bc = bc ? 1 : 0;
-    p.cfg.adds = p.cfg.win ? adds_now : 0;
     // exact mode counts VS_LA in steps of RR to 2*RR reads: the LDS queue holds 15, three steps fill it
-    if (p.cfg.exact && !p.cfg.win && spec_env("VND_SPEC_LA", -1) < 0) p.cfg.la = 3;
+    if (p.cfg.exact && !p.cfg.win && tun.spec_la < 0) p.cfg.la = 3;
     p.tiles_total = (int)tiles_total; p.tiles_per_span = (int)per_span; p.spans = (int)spans;
     // one round of workgroups: at most the resident slots, each walking units w, w + nblocks, ...
     p.units = (uint32_t)(units * spans);
@@ -535,7 +520,7 @@ static SpecPlan make_spec_plan(const vnd_ctx *ctx, const vnd_taps *t, const floa
     // (prologue 0.55 / 0.8 of a tile period, period 1 / 1.2); taken only when the model puts it ahead of the uniform plan.
     p.chunk_tiles = 0;
     if (p.cfg.win && C == 2 && per_cu >= 2 && cus % 8 == 0 && units <= cus && cus % units == 0 && units * spans <= resident &&
-        !(v >= 0 && ((v >> 28) & 7)) && spec_env("VND_WIN_CHUNKS", 1) != 0) {
+        v.rounds == 0 && tun.win_chunks != 0) {
         const int64_t cps = cus / units;                              // chunks per stream: one per CU
         const int64_t w = (tiles_total + cps - 1) / cps;              // tiles per chunk
         auto cost2 = [](int64_t a, int64_t b) { return std::max(0.55 + (double)a, b > 0 ? 0.8 + 1.2 * (double)b : 0.0); };
@@ -548,11 +533,11 @@ static SpecPlan make_spec_plan(const vnd_ctx *ctx, const vnd_taps *t, const floa
             const double c = cost2(a0, w - a0);
             if (c < best - 1e-9) { best = c; best_len0 = a0; }
         }
-        const int len0_env = spec_env("VND_WIN_CHUNK_LEN0", 0);      // (tuning: force the split)
+        const int len0_env = tun.win_chunk_len0;      // (tuning: force the split)
         if (len0_env > 0 && len0_env < w) { best_len0 = len0_env; best = -1.0; }
         if (w >= 2 && best < uniform - 1e-9 && best_len0 < w && w * (cps - 1) < tiles_total) {
             p.chunk_tiles = (int)w; p.chunk_len0 = (int)best_len0; p.chunks_per_stream = (int)cps; p.cus_per_xcd = cus / 8;
-            p.stagger_ticks = std::max(0, spec_env("VND_WIN_STAGGER_TICKS", 300));      // 3 us: about the first workgroup's ring fill - the later one loads while that one computes (tools/ablate/RUNS.md: run_r4b, run_r4c.sh)
+            p.stagger_ticks = std::max(0, tun.win_stagger_ticks);      // 3 us: about the first workgroup's ring fill - the later one loads while that one computes (tools/ablate/RUNS.md: run_r4b, run_r4c.sh)
             p.units = (uint32_t)(2 * cus);
             p.nblocks = p.units;
         }
@@ -563,7 +548,7 @@ static SpecPlan make_spec_plan(const vnd_ctx *ctx, const vnd_taps *t, const floa
     // every workgroup takes a contiguous range of the pool's tiles, the same number (+- 1); a range that crosses into the next stream
     // starts a new ring there.  Taken when a two-line cost model (a ring fill = 0.55 tile periods) puts it 3 % ahead of the spans.
     p.bal_total = 0;
-    if (p.cfg.win && C == 2 && p.chunk_tiles == 0 && !(v >= 0 && ((v >> 28) & 7)) && !(v >= 0 && ((v >> 20) & 7)) && spec_env("VND_WIN_BALANCE", 1) != 0) {
+    if (p.cfg.win && C == 2 && p.chunk_tiles == 0 && v.rounds == 0 && v.min_span == 0 && tun.win_balance != 0) {
         const int64_t total = batch * tiles_total;
         const int64_t wgs = std::min<int64_t>(resident, total / 4);                      // (at least 4 tiles per workgroup)
         if (wgs >= 1 && total < 0x7fffffffLL) {
@@ -571,13 +556,20 @@ static SpecPlan make_spec_plan(const vnd_ctx *ctx, const vnd_taps *t, const floa
             const int64_t uni_units = (units * spans + p.nblocks - 1) / p.nblocks;         // units the busiest workgroup walks
             const double cost_spans = (double)uni_units * ((double)per_span + 0.55);
             const double cost_bal = (double)per_wg + 0.55 * (1.0 + (double)per_wg / (double)tiles_total);
-            if (per_wg <= max_tiles && (spec_env("VND_WIN_BALANCE", 1) == 2 || cost_bal < 0.97 * cost_spans)) {      // (a range stays under 2 GiB of descriptor offsets)
+            if (per_wg <= max_tiles && (tun.win_balance == 2 || cost_bal < 0.97 * cost_spans)) {      // (a range stays under 2 GiB of descriptor offsets)
                 p.bal_total = (int)total;
                 p.nblocks = (uint32_t)wgs; p.units = (uint32_t)wgs;
                 p.tiles_per_span = (int)per_wg; p.spans = 0;                           // (what the description and the pacing rule read)
             }
         }
     }
+    // pacing: one full round of workgroups, two per CU (their co-residency lasts the whole launch), plain stereo forms
+    // (long launches only: with a few tiles per workgroup the bias it corrects has no time to build up, and handing the later
+    //  workgroup the priority costs - cfg4's N = 4 shard, 3 tiles each: 42.8 -> 48.8 us; cfg3's 17 tiles: +4.7 %)
+    const uint32_t cus_per_xcd = (uint32_t)std::max(1, cus / 8);
+    p.pace = p.cfg.win && !p.cfg.win_q && p.chunk_tiles == 0 && p.cfg.win_per_cu == 2 && tun.win_pace != 0 &&
+             p.nblocks > 8 * cus_per_xcd && p.nblocks <= 2 * 8 * cus_per_xcd && p.units >= p.nblocks &&
+             (int64_t)p.units * p.tiles_per_span >= (int64_t)p.nblocks * tun.win_pace_min_tiles;
     p.use = true;
     // (window form: 8192-frame tiles down to 3 per span - 256 one-second streams 42.6 us with them, 45.7 with 4096-frame
     //  tiles; at 2 per span - 128 such streams - the smaller tiles win, 26.3 against 28.1 us: tools/closed/shard_try.py)
@@ -657,14 +649,7 @@ static vnd_status launch_spec(vnd_ctx *ctx, const vnd_taps *t, const SpecPlan &p
     a.units = p.units;
     a.chunk_tiles = p.chunk_tiles; a.chunk_len0 = p.chunk_len0; a.chunks_per_stream = p.chunks_per_stream;
     a.cus_per_xcd = std::max(1, (ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256) / 8);      // (pacing needs it without a chunk plan too)
-    // pacing: one full round of workgroups, two per CU (their co-residency lasts the whole launch), plain stereo forms
-    if (p.cfg.win && !p.cfg.win_q && p.chunk_tiles == 0 && p.cfg.win_per_cu == 2 && spec_env("VND_WIN_PACE", 1) != 0 &&
-        p.nblocks > (uint32_t)(8 * a.cus_per_xcd) && p.nblocks <= (uint32_t)(2 * 8 * a.cus_per_xcd) && p.units >= p.nblocks &&
-        // (long launches only: with a few tiles per workgroup the bias it corrects has no time to build up, and handing the later
-        //  workgroup the priority costs - cfg4's N = 4 shard, 3 tiles each: 42.8 -> 48.8 us; cfg3's 17 tiles: +4.7 %)
-        (int64_t)p.units * p.tiles_per_span >= (int64_t)p.nblocks * spec_env("VND_WIN_PACE_MIN_TILES", 16)) {
-        a.pace = ctx->pace;                                  // made and zeroed by vnd_ctx_create: a *_dev launch only enqueues (null: no pacing)
-    }
+    if (p.pace) a.pace = ctx->pace;                          // made and zeroed by vnd_ctx_create: a *_dev launch only enqueues (null: no pacing)
     a.stagger_ticks = p.stagger_ticks; a.chunk_prio = 1; a.bal_total = p.bal_total;
     if (epi != nullptr && p.cfg.epi) {
         a.epi_ms_encode = epi->ms_encode; a.epi_use_width = epi->use_width; a.epi_w_mid = epi->w_mid; a.epi_w_side = epi->w_side;
@@ -709,7 +694,6 @@ static vnd_status launch(vnd_ctx *ctx, const vnd_taps *t, const float *x, float 
     if (Cx == 0) Cx = C;
     for (int attempt = 0; attempt < 8; ++attempt) {
         const SpecPlan sp = make_spec_plan(ctx, t, x, y, batch, n, C, Cx, mode, epi);
-        if (vnd_status ts = tuning_status(); ts != VND_OK) return ts;
         if (!sp.use) break;
         bool launched = false, built = true;
         vnd_status st = launch_spec(ctx, t, sp, x, y, n, stream, &launched, epi, &built);
@@ -724,11 +708,7 @@ static vnd_status launch(vnd_ctx *ctx, const vnd_taps *t, const float *x, float 
     a.seg_end = t->d_seg_end; a.seg_gain = t->d_seg_gain;
     a.chan_flags = t->has_flags ? t->d_flags : nullptr;
     a.n = n; a.C = C; a.Cx = Cx; a.apply_gain = t->apply_gain;
-    // an output beyond what the L2 + Infinity Cache could hand to a consumer is streamed past them
-    // (only where a workgroup writes whole frames: pieces of a frame written past the caches by different
-    // workgroups reach HBM as separate partial writes)
-    a.stream_out = (batch * n * C * (int64_t)sizeof(float) >= ((int64_t)64 << 20) && !spec_env("VND_NO_NT", 0)) ? 1 : 0;
-    if (!p.direct && p.cg != C && !spec_env("VND_FORCE_NT", 0)) a.stream_out = 0;
+    a.stream_out = p.stream_out ? 1 : 0;
     a.nblocks = p.nblocks;
     if (p.direct) {
         a.tiles = (int32_t)batch; a.groups = 1; a.W = 0;

@@ -17,7 +17,6 @@
 #include <unistd.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cstdarg>
 #include <cstring>
 #include <cstdio>
@@ -52,6 +51,9 @@ struct SpecConfig {
     int win_q = 0;     // window form on channel QUADS (1: signals of 4k channels, a quarter of the workgroup's lanes per channel) or OCTETS (2: 8k channels, an eighth)
     int win_s = 0;     // window form with the waves SPLIT over the two channels of a stereo signal
     int adds = 0;      // window form, fast mode: adds inside a run of equal |w|, the gain ratio once where |w| changes (vnd_win.hpp: win_adds_ok)
+    int win_merged = 0; // window form, exact mode, a mono input fanned out: one read stream for both channels (win_exact_merged_ok)
+    int win_late = 0;  // split form: refill accesses per tile loaded at the start of the store phase instead of a tile ahead (VW_LATE)
+    int win_stamps = 0, win_stamp_phases = 0, win_stamp_wave = 0;      // diagnosis builds: phase stamps (VW_STAMPS, vnd_debug_read_stamps)
     int tile() const { return win ? (win_s ? nt / 2 : (win_q ? nt / (4 * win_q) : nt)) * win : 2 * nt * rr; }
     size_t lds_bytes() const
     {
@@ -61,8 +63,11 @@ struct SpecConfig {
     }
     bool operator<(const SpecConfig &o) const
     {
-        return std::tie(nt, rr, pp, dd, la, nt_stores, exact, epi, bc, shift, win, win_g, win_xpose, win_q, win_s, adds) <
-               std::tie(o.nt, o.rr, o.pp, o.dd, o.la, o.nt_stores, o.exact, o.epi, o.bc, o.shift, o.win, o.win_g, o.win_xpose, o.win_q, o.win_s, o.adds);
+        // (every field that shapes the generated source is part of the key: the table's module map returns what this key built)
+        return std::tie(nt, rr, pp, dd, la, nt_stores, exact, epi, bc, shift, win, win_g, win_xpose, win_q, win_s, adds, win_merged, win_late,
+                        win_stamps, win_stamp_phases, win_stamp_wave) <
+               std::tie(o.nt, o.rr, o.pp, o.dd, o.la, o.nt_stores, o.exact, o.epi, o.bc, o.shift, o.win, o.win_g, o.win_xpose, o.win_q, o.win_s,
+                        o.adds, o.win_merged, o.win_late, o.win_stamps, o.win_stamp_phases, o.win_stamp_wave);
     }
 };
 
@@ -84,19 +89,40 @@ struct SpecTable {
 // Two kinds.  HOST switches (VND_SPEC, VND_SPEC_EXACT, VND_SPEC_CACHE_DIR, VND_SPEC_DUMP, VND_SPEC_VERBOSE,
 // VND_HOST_DIRECT, VND_HOST_TIME_PIECES / _CHUNKS) are read where they act, always.  TUNING variables - geometry overrides, A/B
 // switches of the sweep tools and the tests, diagnosis builds - exist only in a TUNING SESSION: a process started with VND_TUNING=1
-// reads them live at every launch plan; any other process never looks at them (spec_env returns the default).  The one list of them:
-static const char *const kTuningNames[] = {
-    // geometry of the per-table kernels
-    "VND_SPEC_NT", "VND_SPEC_RR", "VND_SPEC_DD", "VND_SPEC_LA", "VND_SPEC_SHIFT", "VND_SPEC_QUAD_STORES", "VND_WIN_M", "VND_WIN_G", "VND_WIN_QUAD_M",
-    "VND_WIN_SPLIT_LATE", "VND_WIN_SPLIT_SMALL_NT", "VND_WIN_TAIL",
-    // which form runs
-    "VND_WIN_EXACT", "VND_WIN_SPLIT_CLASS", "VND_WIN_QUAD", "VND_WIN_OCTET", "VND_WIN_WIDE", "VND_WIN_SPLIT", "VND_WIN_SPLIT_FANOUT", "VND_WIN_FANOUT_EPI", "VND_WIN_XPOSE_PAIRS", "VND_WIN_FAR_FIRST", "VND_WIN_ADDS", "VND_WIN_EXACT_MERGED",
-    "VND_WIN_SOURCE_FANOUT", "VND_WIN_SOURCE_EPI", "VND_EPI_BLOCK_SUMS", "VND_EPI_SUMS_ONLY", "VND_EPI_WIDE", "VND_EPI_SEQ_SPLIT", "VND_EPI_PAR_COALESCED",
-    // one-round launches, pacing, priorities, cache policies
-    "VND_WIN_CHUNKS", "VND_WIN_BALANCE", "VND_WIN_CHUNK_LEN0", "VND_WIN_STAGGER_TICKS", "VND_WIN_PACE", "VND_WIN_PACE_MIN_TILES", "VND_WIN_PRIO", "VND_SPEC_LOAD_AUX",
-    "VND_SPEC_STORE_AUX", "VND_NT_MIN_MB", "VND_NO_NT", "VND_FORCE_NT",
-    // diagnosis builds
-    "VND_WIN_STAMPS", "VND_WIN_STAMP_PHASES", "VND_WIN_STAMP_WAVE",
+// takes a fresh snapshot of them at every launch plan (tuning_snapshot); any other process gets the defaults below and reads none.
+// The one list of them - name, field of Tuning, default; a negative value of a field whose default is -1 leaves the choice to the
+// library (VND_WIN_SPLIT: launches take 1, where it pays; the window source hook 0, the plain or quad form):
+#define VND_TUNING_VARIABLES(X) \
+    /* geometry of the per-table kernels */ \
+    X("VND_SPEC_NT", spec_nt, 0) X("VND_SPEC_RR", spec_rr, -1) X("VND_SPEC_DD", spec_dd, -1) X("VND_SPEC_LA", spec_la, -1) \
+    X("VND_SPEC_SHIFT", spec_shift, 1) X("VND_WIN_M", win_m, 32) X("VND_WIN_G", win_g, 0) X("VND_WIN_QUAD_M", win_quad_m, 32) \
+    X("VND_WIN_SPLIT_LATE", win_split_late, -1) X("VND_WIN_SPLIT_SMALL_NT", win_split_small_nt, 256) \
+    /* which form runs (VND_WIN_SOURCE_*: the window source hook's fan-out and fused-epilogue sources) */ \
+    X("VND_WIN_EXACT", win_exact, 1) X("VND_WIN_SPLIT_CLASS", win_split_class, 1) X("VND_WIN_QUAD", win_quad, 1) \
+    X("VND_WIN_OCTET", win_octet, 1) X("VND_WIN_WIDE", win_wide, 0) X("VND_WIN_SPLIT", win_split, -1) \
+    X("VND_WIN_SPLIT_FANOUT", win_split_fanout, 1) X("VND_WIN_FANOUT_EPI", win_fanout_epi, 1) X("VND_WIN_XPOSE_PAIRS", win_xpose_pairs, 1) \
+    X("VND_WIN_ADDS", win_adds, 1) X("VND_WIN_EXACT_MERGED", win_exact_merged, 1) \
+    X("VND_WIN_SOURCE_FANOUT", win_source_fanout, 0) X("VND_WIN_SOURCE_EPI", win_source_epi, 0) \
+    X("VND_EPI_BLOCK_SUMS", epi_block_sums, 1) X("VND_EPI_SUMS_ONLY", epi_sums_only, 1) X("VND_EPI_WIDE", epi_wide, 1) \
+    X("VND_EPI_SEQ_SPLIT", epi_seq_split, 1) X("VND_EPI_PAR_COALESCED", epi_par_coalesced, 1) \
+    /* one-round launches, pacing, cache policies */ \
+    X("VND_WIN_CHUNKS", win_chunks, 1) X("VND_WIN_BALANCE", win_balance, 1) X("VND_WIN_CHUNK_LEN0", win_chunk_len0, 0) \
+    X("VND_WIN_STAGGER_TICKS", win_stagger_ticks, 300) X("VND_WIN_PACE", win_pace, 1) X("VND_WIN_PACE_MIN_TILES", win_pace_min_tiles, 16) \
+    X("VND_NT_MIN_MB", nt_min_mb, 64) X("VND_NO_NT", no_nt, 0) X("VND_FORCE_NT", force_nt, 0) \
+    /* diagnosis builds */ \
+    X("VND_WIN_STAMPS", win_stamps, 0) X("VND_WIN_STAMP_PHASES", win_stamp_phases, 1) X("VND_WIN_STAMP_WAVE", win_stamp_wave, 0)
+
+struct Tuning {
+#define VND_TUNING_FIELD(name, field, fallback) int field = fallback;
+    VND_TUNING_VARIABLES(VND_TUNING_FIELD)
+#undef VND_TUNING_FIELD
+};
+
+struct TuningName { const char *name; int Tuning::*field; };
+static const TuningName kTuningNames[] = {
+#define VND_TUNING_NAME(name, field, fallback) {name, &Tuning::field},
+    VND_TUNING_VARIABLES(VND_TUNING_NAME)
+#undef VND_TUNING_NAME
 };
 
 inline bool spec_tuning()
@@ -105,22 +131,20 @@ inline bool spec_tuning()
     return on;
 }
 
-// a name the library asked for that is not in the list: a library bug, reported - never by ending the host process - as
-// VND_ERR_INVALID by the entry point that planned the launch (tuning_status() in vnd_plan.hpp), with the name in vnd_last_error
-inline std::atomic<const char *> &spec_unregistered_name()
-{
-    static std::atomic<const char *> name{nullptr};
-    return name;
-}
-
-inline int spec_env(const char *name, int fallback)
+// a registered tuning variable's value in a tuning session, else the fallback
+inline int tuning_value(const TuningName &v, int fallback)
 {
     if (!spec_tuning()) return fallback;
-    bool known = false;
-    for (const char *k : kTuningNames) known |= strcmp(k, name) == 0;
-    if (!known) { spec_unregistered_name().store(name); return fallback; }
-    const char *e = getenv(name);
+    const char *e = getenv(v.name);
     return (e && *e) ? atoi(e) : fallback;
+}
+
+inline Tuning tuning_snapshot()
+{
+    Tuning t;
+    if (spec_tuning())
+        for (const TuningName &v : kTuningNames) t.*v.field = tuning_value(v, t.*v.field);
+    return t;
 }
 
 // a HOST switch: read once per process (getenv is not safe against a concurrent setenv, and a host sets these before it starts)
@@ -132,7 +156,7 @@ inline int host_env_once(const char *name, int fallback, int *slot)
 
 // Smallest ring that holds one tile's window (tile + halo) plus the slot being refilled.
 // Returns false when no supported geometry fits (the caller then uses the generic kernel).
-inline bool spec_pick_config(const SpecTable &t, size_t lds_limit, int rr_hint, int dd_hint, SpecConfig *out,
+inline bool spec_pick_config(const SpecTable &t, const Tuning &tun, size_t lds_limit, int rr_hint, int dd_hint, SpecConfig *out,
                              bool small_tiles = false, bool bc = false, bool shift_wanted = false)
 {
     const int reach = (t.max_index | 1) + 1;          // frames past a pair's first frame that an (aligned) read touches
@@ -147,15 +171,15 @@ inline bool spec_pick_config(const SpecTable &t, size_t lds_limit, int rr_hint, 
     // 4 ring slots, 74 KB: two workgroups = 8 waves per CU) ahead of 192 x 4 by 5-11 %, everything else behind
     static const int kExact[][2] = {{256, 2}, {192, 4}, {320, 2}, {128, 4}, {128, 2}, {256, 1}};
     const int (&kShapes)[6][2] = shift_wanted ? kExact : (small_tiles ? kShort : kLong);
-    const int nt_env = spec_env("VND_SPEC_NT", 0);
-    rr_hint = spec_env("VND_SPEC_RR", rr_hint);
-    dd_hint = spec_env("VND_SPEC_DD", dd_hint);
+    const int nt_env = tun.spec_nt;
+    if (tun.spec_rr >= 0) rr_hint = tun.spec_rr;
+    if (tun.spec_dd >= 0) dd_hint = tun.spec_dd;
     for (const auto &shape : kShapes) {
         SpecConfig c;
         c.bc = bc ? 1 : 0;
         c.nt = nt_env > 0 ? nt_env : shape[0];
         c.rr = rr_hint > 0 ? rr_hint : shape[1];
-        c.la = spec_env("VND_SPEC_LA", c.la);
+        if (tun.spec_la >= 0) c.la = tun.spec_la;
         if (c.nt % 64 != 0 || c.nt > 1024 || c.rr > 16) return false;
         const int T = c.tile();
         c.pp = (T + reach + T - 1) / T + 1;            // slots covering tile + halo, plus the one being refilled
@@ -163,7 +187,7 @@ inline bool spec_pick_config(const SpecTable &t, size_t lds_limit, int rr_hint, 
         c.dd = std::min(dd_hint > 0 ? dd_hint : (c.pp >= 4 ? 2 : 1), 3);      // measured: 2 ahead only pays with 4+ slots
         // exact mode: shifted copies of the planes (odd offsets become aligned pairs: +22 % on class-path tables, +7 % on
         // function-path ones at cfg2) when two workgroups still fit a CU
-        c.shift = (shift_wanted && c.rr >= 2 && spec_env("VND_SPEC_SHIFT", 1)) ? 1 : 0;
+        c.shift = (shift_wanted && c.rr >= 2 && tun.spec_shift) ? 1 : 0;
         if (c.shift && c.lds_bytes() > 81 * 1024) c.shift = 0;
         // ... and those two still hold six waves (128-thread workgroups measured 23 % slower with the copies than without)
         if (c.shift && ((size_t)(160 * 1024) / c.lds_bytes()) * (size_t)(c.nt / 64) < 6) c.shift = 0;
@@ -206,11 +230,12 @@ inline std::string spec_prologue(const SpecTable &t, const SpecConfig &c)
                 c.pp, c.dd, c.la);
     spec_append(s, "#define VS_C %d\n#define VS_GROUPS %d\n#define VS_NT_STORES %d\n#define VS_EXACT %d\n#define VS_EPI %d\n#define VS_BC %d\n#define VS_SHIFT %d\n", t.C, groups,
                 c.nt_stores, c.exact, c.epi, c.bc, c.shift);
-    spec_append(s, "#define VS_NT_STORE_AUX %d\n", spec_env("VND_SPEC_STORE_AUX", 2));   // cache policy bits of the non-temporal stores (tuning)
-    spec_append(s, "#define VS_LOAD_AUX %d\n", spec_env("VND_SPEC_LOAD_AUX", 2));     // input is read once: non-temporal loads (+1-2 % on cfg2)
+    s += "#define VS_NT_STORE_AUX 2\n";      // cache policy bits of the non-temporal stores
+    s += "#define VS_LOAD_AUX 2\n";          // input is read once: non-temporal loads (+1-2 % on cfg2)
     // wider signals: the four lanes of a quad exchange their frames so that one store instruction writes four CONSECUTIVE
-    // frames' pieces (one 128-byte line) instead of every other frame's (tools/micro/piece_stores.hip: 2.8 against 1.7 TB/s)
-    spec_append(s, "#define VS_QUAD_STORES %d\n", spec_env("VND_SPEC_QUAD_STORES", 1));
+    // frames' pieces (one 128-byte line) instead of every other frame's (tools/micro/piece_stores.hip: 2.8 against 1.7 TB/s) - the
+    // only store form of vs_store_pair for them, stated in the source as the kernel checks it
+    s += "#define VS_QUAD_STORES 1\n";
     {   // resident workgroups per CU (LDS-bound, at most 32 waves) -> waves per SIMD the register budget must allow
         const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(16, 2048 / c.nt), (160 * 1024) / c.lds_bytes()));
         const int waves = (per_cu * (c.nt / 64) + 3) / 4;

@@ -116,6 +116,7 @@ __device__ __forceinline__ v4f vs_load_pair(v4i rsrc, int voff)
 
 // aux bit 1 = nt: a large output is not read again before it has left the caches
 constexpr int VS_STORE_AUX = VS_NT_STORES ? VS_NT_STORE_AUX : 0;
+static_assert(VS_QUAD_STORES == 1, "a wider signal's frame pairs are stored through the lane-quad exchange (vs_store_pair): the only form");
 
 // a value of another lane of the quad (DPP quad_perm; every lane of the quad must be executing)
 template <int CTRL>
@@ -136,7 +137,7 @@ __device__ __forceinline__ void vs_store_pair(v4f v, v4i rsrc, int voff, bool se
     if constexpr (VS_C == 2) {
         if (second) vs_store4(v, rsrc, voff, 0, VS_STORE_AUX);
         else vs_store2(v2f{v.x, v.y}, rsrc, voff, 0, VS_STORE_AUX);
-    } else if constexpr (VS_QUAD_STORES) {
+    } else {
         const int i = (int)threadIdx.x & 3;
         const bool odd = (i & 1) != 0;
         // quad_perm [0,0,1,1] = 0x50: lane i reads lane i/2;  [2,2,3,3] = 0xfa: lane 2 + i/2
@@ -148,9 +149,6 @@ __device__ __forceinline__ void vs_store_pair(v4f v, v4i rsrc, int voff, bool se
         vs_store2(A, rsrc, va, 0, VS_STORE_AUX);
         if (second) vs_store2(B, rsrc, va + 4 * VS_C * 4, 0, VS_STORE_AUX);      // (frame 8k+7 is lane 3's own second frame)
         __builtin_amdgcn_sched_barrier(0);         // (one pair's exchange at a time: hoisted together they cost 8 registers per pair)
-    } else {
-        vs_store2(v2f{v.x, v.y}, rsrc, voff, 0, VS_STORE_AUX);
-        if (second) vs_store2(v2f{v.z, v.w}, rsrc, voff + VS_C * 4, 0, VS_STORE_AUX);
     }
 }
 

@@ -33,6 +33,7 @@ struct StageSetup {
     dim3 grid;
     int seq_frames;
     bool want_seq, par_ok, par_forced, want_blk;
+    Tuning tun;                  // the stage's snapshot of the tuning variables
 };
 
 static StageSetup stage_setup(vnd_ctx *ctx, const float *x, float *y, int64_t batch, int64_t n, int32_t Cx, int32_t C,
@@ -40,6 +41,8 @@ static StageSetup stage_setup(vnd_ctx *ctx, const float *x, float *y, int64_t ba
                               void *workspace)
 {
     StageSetup s{};
+    s.tun = tuning_snapshot();
+    const Tuning &tun = s.tun;
     EArgs &e = s.e;
     RArgs &r = s.r;
     e.x = x; e.y = y; e.partials = (double *)workspace; e.n = n; e.C = C; e.Cx = Cx;
@@ -47,12 +50,12 @@ static StageSetup stage_setup(vnd_ctx *ctx, const float *x, float *y, int64_t ba
     e.ms_encode = ms_encode ? 1 : 0; e.use_width = use_width ? 1 : 0;
     e.w_mid = (float)(1.0 - width); e.w_side = (float)width;   // float32(python float), as NumPy's in-place multiply
     e.normalize = normalize ? 1 : 0; e.eps = eps;
-    e.wide = (((uintptr_t)y & 15) == 0 && ((uintptr_t)x & (Cx == 1 ? 7 : 15)) == 0 && (batch == 1 || n % 2 == 0) && spec_env("VND_EPI_WIDE", 1) != 0) ? 1 : 0;
+    e.wide = (((uintptr_t)y & 15) == 0 && ((uintptr_t)x & (Cx == 1 ? 7 : 15)) == 0 && (batch == 1 || n % 2 == 0) && tun.epi_wide != 0) ? 1 : 0;
     // (wide == 2, the block-parallel sums' staging: a wave's 16-byte accesses on consecutive bytes instead of 32 consecutive bytes per
     //  lane as two accesses - interleaved A/B at 128 / 64 / 32 streams: stereo +1 ... 3 %, mono +3 ... 10 %, the quads of a wider signal
     //  441 -> 348 us (tools/stage_coalesced_ab.py).  The per-stream kernel of pools of 256 streams and more keeps its own mapping:
     //  it measured slower with this one - see epilogue_rms_seq_kernel)
-    const int wide_par = e.wide ? (spec_env("VND_EPI_PAR_COALESCED", 1) != 0 ? 2 : 1) : 0;
+    const int wide_par = e.wide ? (tun.epi_par_coalesced != 0 ? 2 : 1) : 0;
     s.grid = dim3((unsigned)epi_chunks(n), (unsigned)batch);
 
     // normalize == VND_NORMALIZE_RMS_REFERENCE_ORDER: the sums of squares in NumPy's own (sequential
@@ -72,13 +75,13 @@ static StageSetup stage_setup(vnd_ctx *ctx, const float *x, float *y, int64_t ba
     //   up to 64 streams the one-workgroup-per-stream kernel leaves most CUs dark (16: 0.49 / 0.17);
     //   65 .. 255: it still fills less than every CU once (128: 0.80 / 0.82, and 0.66 once the block sums come from the convolution);
     //   more than 320: it fills the chip by itself and reads the data once instead of twice (1024: 4.43 / 5.0; the switch was at 256 until round 6).
-    // variant bit 19 keeps the per-stream kernel, bit 17 forces the block-parallel form (A/B runs).
+    // The variant's no_par_sums keeps the per-stream kernel, par_sums forces the block-parallel form (A/B runs).
     // Wider signals (round 5): the same kernels channel pair by channel pair - a "stream" of theirs is one pair of a stream (RArgs::pairs),
     // 8 bytes of every frame.  The per-stream kernel takes 16 workgroups for cfg5's pool of 16 signals (8.7 ms for the stage); the
     // block-parallel form 16 x 4 pairs x 469 blocks.
     const int pairs = C / 2;
-    const bool par_ok = want_seq && C % 2 == 0 && (C == 2 || Cx == C) && par_blocks(n) <= kParMaxBlocks && !(ctx->variant >= 0 && ((ctx->variant >> 19) & 1));
-    const bool par_forced = ctx->variant >= 0 && ((ctx->variant >> 17) & 1);
+    const bool par_ok = want_seq && C % 2 == 0 && (C == 2 || Cx == C) && par_blocks(n) <= kParMaxBlocks && !ctx->variant.no_par_sums;
+    const bool par_forced = ctx->variant.par_sums;
     if (par_ok) {
         r.x = x; r.y = y; r.n = n; r.Cx = Cx; r.nblocks = (int32_t)par_blocks(n); r.C = C; r.pairs = pairs;
         char *extra = (char *)((float *)((double *)workspace + batch * epi_rows_max(n) * 2 * C) + batch * C);
@@ -93,7 +96,7 @@ static StageSetup stage_setup(vnd_ctx *ctx, const float *x, float *y, int64_t ba
     }
     // (round 6, with the tally's staging on consecutive bytes: 256 streams 1.27-1.37 -> 1.22-1.25 ms block-parallel; from 384 on the per-stream
     //  kernel leads, 1.70 against 1.80-1.84 - tools/f1_threshold_try.py, profiles/r06_f1_threshold.txt)
-    const bool want_blk = par_ok && C == 2 && (batch <= 320 || par_forced) && spec_env("VND_EPI_BLOCK_SUMS", 1) != 0;
+    const bool want_blk = par_ok && C == 2 && (batch <= 320 || par_forced) && tun.epi_block_sums != 0;
     s.seq_frames = seq_frames; s.want_seq = want_seq; s.par_ok = par_ok; s.par_forced = par_forced; s.want_blk = want_blk;
     return s;
 }
@@ -162,7 +165,7 @@ static vnd_status stage_sums(vnd_ctx *ctx, StageSetup &s, const float *x, const 
                                                       ctx->lds_limit));
         // stereo, fewer streams than two per CU: a workgroup per ARRAY of a stream (x's chains, y's chains) - twice the loads in flight
         const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
-        e.seq_split = (C == 2 && batch < 2 * (int64_t)cus && spec_env("VND_EPI_SEQ_SPLIT", 1) != 0) ? 1 : 0;
+        e.seq_split = (C == 2 && batch < 2 * (int64_t)cus && s.tun.epi_seq_split != 0) ? 1 : 0;
         hipLaunchKernelGGL(k, dim3((unsigned)(e.seq_split ? 2 * batch : batch)), dim3(64 * waves), lds, stream, e);
     }
     if (normalize) {
@@ -199,9 +202,10 @@ static vnd_status decorrelate_dev(vnd_ctx *ctx, const vnd_taps *t, const float *
     RArgs &r = s.r;
     const dim3 grid = s.grid;
     const bool want_seq = s.want_seq, par_ok = s.par_ok, want_blk = s.want_blk;
+    const bool nofuse = ctx->variant.nofuse, blk_sums_ok = s.tun.epi_block_sums != 0;
     // Fused form: the fast kernel applies the pointwise steps and writes one row of sums per tile.
     const Plan p = make_plan(ctx, t, batch, n, C, mode, Cx);
-    const bool fused = any && mode == VND_MODE_FAST && ctx->variant_nofuse == 0 && fast_epi_kernel(p) != nullptr &&
+    const bool fused = any && mode == VND_MODE_FAST && !nofuse && fast_epi_kernel(p) != nullptr &&
                        (!(ms_encode || use_width) || p.cg == 2) && !(want_seq && !(ms_encode || use_width));
     int conv_path = 0;                                     // EpiFuse::path of the convolution launch
     bool sums_pending = false;                             // the sequential sums still have to run
@@ -210,7 +214,7 @@ static vnd_status decorrelate_dev(vnd_ctx *ctx, const vnd_taps *t, const float *
     // 16 bytes per sample instead of 24.  Where that kernel does not take the launch nothing has run and the passes below do.
     bool q_done = false, q_blk_done = false;
     if (mode == VND_MODE_FAST && normalize && !want_seq && !ms_encode && !use_width && C % 4 == 0 && Cx == C &&
-        ctx->variant_nofuse == 0 && spec_env("VND_EPI_BLOCK_SUMS", 1) != 0) {
+        !nofuse && blk_sums_ok) {
         int rows_q = 0;
         EpiFuse f{(double *)workspace, 0, 0, e.normalize, e.w_mid, e.w_side};
         f.path = &conv_path; f.blk_sum = (double *)workspace; f.rows_major = 1; f.rows = &rows_q; f.rows_max = (int)std::min<int64_t>(epi_rows_max(n), INT32_MAX); f.spec_only = true;
@@ -228,7 +232,7 @@ static vnd_status decorrelate_dev(vnd_ctx *ctx, const vnd_taps *t, const float *
         if (want_blk && want_seq) { f.blk_sum = r.blk_sum; f.nblocks = r.nblocks; }
         // the fully fused stage: the window kernel writes one row of sums per 2048-frame block where it runs (the generic fast
         // kernel one per tile), and one streaming pass scales
-        else if (!want_seq && e.normalize && C == 2 && spec_env("VND_EPI_BLOCK_SUMS", 1) != 0) { f.blk_sum = (double *)workspace; f.nblocks = (int)par_blocks(n); f.rows_major = 1; }
+        else if (!want_seq && e.normalize && C == 2 && blk_sums_ok) { f.blk_sum = (double *)workspace; f.nblocks = (int)par_blocks(n); f.rows_major = 1; }
         st = launch(ctx, t, x, y, batch, n, C, mode, stream, &f, Cx);
         if (st != VND_OK) return st;
         e.rows = p.tiles;
@@ -246,8 +250,8 @@ static vnd_status decorrelate_dev(vnd_ctx *ctx, const vnd_taps *t, const float *
         const bool pointwise = ms_encode || use_width;
         // (LR mode with the normaliser alone - no pointwise step - takes the same launch for the block sums its store phase leaves: the
         //  sums' own pass over x and y is a fifth of the stage at 128 streams)
-        const bool sums_only = !pointwise && want_blk && normalize && spec_env("VND_EPI_SUMS_ONLY", 1) != 0;
-        const bool in_kernel = (pointwise || sums_only) && mode != VND_MODE_FAST && ctx->variant_nofuse == 0 &&
+        const bool sums_only = !pointwise && want_blk && normalize && s.tun.epi_sums_only != 0;
+        const bool in_kernel = (pointwise || sums_only) && mode != VND_MODE_FAST && !nofuse &&
                                ordered_epi_kernel(p, arithmetic_of(t, mode)) != nullptr;
         if (in_kernel) {
             EpiFuse f{nullptr, e.ms_encode, e.use_width, 0, e.w_mid, e.w_side};
@@ -260,7 +264,7 @@ static vnd_status decorrelate_dev(vnd_ctx *ctx, const vnd_taps *t, const float *
             // NumPy-order sums start from (as the stereo window form does) - when that kernel takes the launch
             bool launched_q = false;
             if (par_ok && C > 2 && C % 4 == 0 && Cx == C && normalize && mode == VND_MODE_EXACT && batch < 256 &&
-                ctx->variant_nofuse == 0 && spec_env("VND_EPI_BLOCK_SUMS", 1) != 0) {
+                !nofuse && blk_sums_ok) {
                 int rows_q = 0;
                 EpiFuse f{nullptr, 0, 0, 0, e.w_mid, e.w_side};
                 f.path = &conv_path; f.blk_sum = r.blk_sum; f.nblocks = r.nblocks; f.rows = &rows_q; f.spec_only = true;
@@ -478,7 +482,7 @@ vnd_status vnd_scan_bank_f32_host(vnd_ctx *ctx, const vnd_taps *t, const float *
     // Fused form: the convolution kernel's store phase reduces each tile to the eight moments per
     // candidate (KArgs.sink_partials) - the [n][2F] output, 1.6 GB there and back for 400 candidates
     // of a 5.7 s signal, is never written.  Needs the two-channels-per-workgroup epilogue instantiation.
-    if (n > 0 && !(ctx->variant >= 0 && ((ctx->variant >> 16) & 0x100))) {
+    if (n > 0 && !ctx->variant.nofuse) {
         const Plan p = make_plan(ctx, t, 1, n, t->C, mode, in_channels);
         kern_t k = p.direct ? nullptr
                             : (mode == VND_MODE_FAST ? fast_epi_kernel(p) : ordered_epi_kernel(p, arithmetic_of(t, mode)));

@@ -102,7 +102,7 @@ inline bool win_geometry(const SpecTable &t, int M, int nt, int G, bool bc, size
             // offsets go through per-lane bases of their own (ring or tail).  Same LDS, no wave straddles a ring end out of step
             // with the banks any more: SQ_LDS_BANK_CONFLICT 0.13 -> 0.0x of the LDS cycles on cfg5.
             const int cut = (nh + de) % 16;
-            if (quad && spec_env("VND_WIN_TAIL", 1) != 0 && cut > 0 && nh + de - cut >= nh + G && cut <= (nt / 64) * (64 / (M * quad))) {
+            if (quad && cut > 0 && nh + de - cut >= nh + G && cut <= (nt / 64) * (64 / (M * quad))) {
                 if (!(lay_out(de, cut) && win_workgroups_per_cu(*g) >= before)) *g = plain;
             }
         }
@@ -301,14 +301,13 @@ inline std::string win_taps_function(const SpecTable &t, const WinGeom &g, int l
     // The chunks are consumed from the FAR end of the window to the near one: a velvet table's gains decay with the offset, so every
     // chain adds its small terms first - the partial sums stay small for most of the chain, and so does what each rounding costs
     // (128-tap tables: the worst sample's distance from the reference 8.5e-7 -> 7.9e-7 / 7.1e-7 -> 5.1e-7 of peak, 30 taps 3.6e-7 -> 3.0e-7;
-    // most of what remains is the reference's own rounding).  Taps inside a chunk keep ascending order.
-    const bool far_first = spec_env("VND_WIN_FAR_FIRST", 1) != 0;
+    // most of what remains is the reference's own rounding).  Taps inside a chunk keep ascending order (adds: descending).
     for (int ch = 0; ch < 2; ++ch) {
         first_of_ch[ch] = reads.size();
         if (only_ch >= 0 && ch != only_ch) continue;
         std::vector<WinRead> one = win_schedule(t, 2 * pg + ch, M);
-        if (far_first) std::reverse(one.begin(), one.end());
-        if (adds && far_first)
+        std::reverse(one.begin(), one.end());
+        if (adds)
             for (WinRead &r : one) std::stable_sort(r.ops.begin(), r.ops.end(), [](const WinOp &a, const WinOp &b) { return a.tap > b.tap; });
         for (WinRead &r : one) { r.ch = ch; reads.push_back(std::move(r)); }      // ch: the LDS plane set
     }
@@ -480,8 +479,8 @@ inline void win_traffic_exact(const SpecTable &t, int M, size_t *lds_bytes, size
 // A mono input fanned out (VW_BC, plain form): both output channels read the SAME plane, and the two channels of a velvet table
 // place their taps almost alike (the same segment grid, jittered) - so ONE read stream over the union of both channels' windows feeds
 // both channels' FMAs: cfg2's table 178 reads per tile and lane instead of 157 + 160, 1.48 B of LDS per FMA instead of 2.64.  Each
-// channel keeps its own E / P chains in the read order of win_taps_function - FAR end of the window first by default (small terms first,
-// VND_WIN_FAR_FIRST), ascending offsets when that is switched off: the results are those of a pass per channel, bit for bit.
+// channel keeps its own E / P chains in the read order of win_taps_function - FAR end of the window first (small terms first): the
+// results are those of a pass per channel, bit for bit.
 inline std::string win_taps_function_merged(const SpecTable &t, const WinGeom &g, int la, int pg = 0, bool adds = false)
 {
     const int M = g.M;
@@ -499,11 +498,9 @@ inline std::string win_taps_function_merged(const SpecTable &t, const WinGeom &g
         }
     std::vector<Rd> reads;
     for (auto &kv : by_o) reads.push_back(std::move(kv.second));
-    if (spec_env("VND_WIN_FAR_FIRST", 1) != 0) {      // (small terms first: win_taps_function)
-        std::reverse(reads.begin(), reads.end());
-        if (adds)
-            for (Rd &r : reads) std::stable_sort(r.ops.begin(), r.ops.end(), [](const std::pair<int, WinOp> &a, const std::pair<int, WinOp> &b) { return a.second.tap > b.second.tap; });
-    }
+    std::reverse(reads.begin(), reads.end());      // (small terms first: win_taps_function)
+    if (adds)
+        for (Rd &r : reads) std::stable_sort(r.ops.begin(), r.ops.end(), [](const std::pair<int, WinOp> &a, const std::pair<int, WinOp> &b) { return a.second.tap > b.second.tap; });
     auto emit_read = [&](size_t k) {
         spec_append(s, "    q[%zu] = %s;\n", k % (size_t)(la + 1), win_rd(g, 0, reads[k].o).c_str());
     };
@@ -779,31 +776,24 @@ inline std::string win_taps_function_exact_merged(const SpecTable &t, const WinG
     return s;
 }
 
-inline std::string win_prologue(const WinGeom &g, const SpecConfig &c, bool two_sums = false)
+inline std::string win_prologue(const WinGeom &g, const SpecConfig &c)
 {
     std::string s;
     spec_append(s, "#define VW_NT %d\n#define VW_M %d\n#define VW_R %d\n#define VW_G %d\n#define VW_NB %d\n#define VW_DE %d\n#define VW_PLANE %d\n#define VW_LA %d\n",
                 g.nt, g.M, g.R, g.G, g.NB, g.DE, g.plane, c.la);
     spec_append(s, "#define VW_NT_STORES %d\n#define VW_EPI %d\n#define VW_BC %d\n#define VW_EXACT %d\n#define VW_C %d\n", c.nt_stores, c.epi, c.bc, c.exact, g.C);
     spec_append(s, "#define VW_Q %d\n#define VW_S %d\n#define VW_QUADPAD %d\n#define VW_TAIL %d\n", g.quad, g.split, g.quad_pad(), g.tail);
-    // split form: how many of a wave's M/4 refill accesses per tile are loaded late (at the start of the store phase that consumes
-    // them) instead of a tile ahead: 64-frame runs keep half of them out of the tap phase's registers
-    // (the fast mode's E / P accumulators are twice the exact mode's sums: all but one late there - hipRTC's build of cfg2's table
-    //  spills 20-64 bytes with 12-14 of the 16 late and none with 15; 4 to 15 late run the same)
-    // (two_sums: a class-path table in the exact mode carries a segment sum AND an output sum per pair - as many registers as the fast mode)
-    spec_append(s, "#define VW_LATE %d\n", g.split ? std::min(std::max(spec_env("VND_WIN_SPLIT_LATE", g.M >= 64 ? ((c.exact && !two_sums) ? g.M / 8 : g.M / 4 - 1) : 0), 0), g.M / 4 - 1) : 0);
-    spec_append(s, "#define VW_NT_STORE_AUX %d\n", spec_env("VND_SPEC_STORE_AUX", 2));
+    spec_append(s, "#define VW_LATE %d\n", c.win_late);
+    s += "#define VW_NT_STORE_AUX 2\n";
     // the transposition as interleaved frame pairs (one 16-byte read-back per store, planes an odd number of slots apart) or as
     // planar chunks read back in 8-byte halves (VND_WIN_XPOSE_PAIRS=0: then 32-frame runs swizzle their lanes' pair indices)
     const int xpose = c.win_xpose ? 1 : 0;
     spec_append(s, "#define VW_XPOSE_PAIRS %d\n", xpose);
     spec_append(s, "#define VW_LANE_SWIZZLE %d\n", g.M == 32 ? 1 : 0);
-    spec_append(s, "#define VW_STAMP_PHASES %d\n", spec_env("VND_WIN_STAMP_PHASES", 1) != 0 ? 1 : 0);
-    spec_append(s, "#define VW_STAMP_WAVE %d\n", std::max(0, spec_env("VND_WIN_STAMP_WAVE", 0)));      // (whose clock readings the phase stamps are)
-    spec_append(s, "#define VW_STAMPS %d\n", std::min(std::max(spec_env("VND_WIN_STAMPS", 0), 0), 4096));
-    // s_setprio of the store / refill phase (0: none): cfg2 +1.0 % fast, +0.5 % exact at 1, 2 or 3; cfg3 unchanged (tools/closed/win_phase_try.py)
-    spec_append(s, "#define VW_PRIO %d\n", spec_env("VND_WIN_PRIO", 1));
-    spec_append(s, "#define VW_LOAD_AUX %d\n", spec_env("VND_SPEC_LOAD_AUX", 2));
+    spec_append(s, "#define VW_STAMP_PHASES %d\n", c.win_stamp_phases);
+    spec_append(s, "#define VW_STAMP_WAVE %d\n", c.win_stamp_wave);      // (whose clock readings the phase stamps are)
+    spec_append(s, "#define VW_STAMPS %d\n", c.win_stamps);
+    s += "#define VW_LOAD_AUX 2\n";
     const int waves = (win_workgroups_per_cu(g) * (g.nt / 64) + 3) / 4;
     spec_append(s, "#define VW_WAVES_PER_EU %d\n", std::max(1, std::min(waves, win_waves_per_simd_max(g.M, g.split != 0))));
     return s;
@@ -812,7 +802,7 @@ inline std::string win_prologue(const WinGeom &g, const SpecConfig &c, bool two_
 // the whole translation unit of the window kernel for (table, geometry)
 inline std::string win_source(const SpecTable &t, const WinGeom &g, const SpecConfig &c)
 {
-    std::string src = win_prologue(g, c, c.exact && t.has_seg);
+    std::string src = win_prologue(g, c);
     const std::string fixed = kWinKernelSource;
     const std::string marker = "//@@VW_TAPS@@";
     const size_t at = fixed.find(marker);
@@ -842,53 +832,80 @@ inline std::string win_source(const SpecTable &t, const WinGeom &g, const SpecCo
         src += "#define VW_DISPATCH(pg) vw_span_s(a, lds, stream, t_first, ntiles, flags, pace);\n";
     } else {
         const bool merged = c.bc && !c.exact;      // (one read stream for both channels of a mono input)
-        const bool merged_exact = c.bc && c.exact && win_exact_merged_ok(t) && spec_env("VND_WIN_EXACT_MERGED", 1) != 0;
-        for (int pg = 0; pg < t.C / 2; ++pg) src += c.exact ? (merged_exact ? win_taps_function_exact_merged(t, g, c.la, pg) : win_taps_function_exact(t, g, c.la, pg)) : (merged ? win_taps_function_merged(t, g, c.la, pg, c.adds != 0) : win_taps_function(t, g, c.la, pg, -1, c.adds != 0));
+        for (int pg = 0; pg < t.C / 2; ++pg) src += c.exact ? (c.win_merged ? win_taps_function_exact_merged(t, g, c.la, pg) : win_taps_function_exact(t, g, c.la, pg)) : (merged ? win_taps_function_merged(t, g, c.la, pg, c.adds != 0) : win_taps_function(t, g, c.la, pg, -1, c.adds != 0));
         src += win_taps_dispatch(t);
     }
     src += fixed.substr(at + marker.size());
     return src;
 }
 
+// A window config of geometry g, completed as a launch builds it: everything the generated source depends on besides the
+// geometry (the plan adds nt_stores and epi).  vnd_window_kernel_source completes its configs here too.
+inline SpecConfig win_config(const SpecTable &t, const WinGeom &g, const Tuning &tun, bool exact, bool bc)
+{
+    SpecConfig c;
+    const int M = g.M;
+    const bool split = g.split != 0, quad = g.quad != 0;
+    c.nt = g.nt; c.win = M; c.win_g = g.G; c.win_lds = (int)g.lds_bytes(); c.win_q = g.quad; c.win_s = g.split;
+    c.win_per_cu = win_workgroups_per_cu(g);
+    c.rr = 0; c.pp = 0; c.dd = 0;
+    c.exact = exact ? 1 : 0; c.bc = bc ? 1 : 0;
+    // reads kept in flight: each holds 4 registers, and 32-frame runs already live at ~240 of the 256 a lane
+    // has at two waves per SIMD (measured: 3 to 10 reads ahead run the same, tools/closed/win_try.py)
+    c.la = tun.spec_la >= 0 ? tun.spec_la : ((split && M >= 64) ? (exact ? 3 : 2) : (M >= 32 ? 4 : 6));      // (64-frame runs: 64 / 128 accumulator registers)
+    // the store phase: interleaved frame pairs (one 16-byte read-back per store) - planar chunks in 8-byte halves where a build of
+    // the pairs spilled (win_pick_config) and in the split and quad forms, whose outputs cross waves as planar runs
+    c.win_xpose = (split || quad) ? 0 : (tun.win_xpose_pairs != 0 ? 1 : 0);
+    // the fast mode in the reference's class-path association (adds inside a segment, the gain ratio once per segment) wherever the
+    // table has few distinct |w| - every generated table has; VND_WIN_ADDS=0: one FMA per tap
+    c.adds = (!exact && tun.win_adds != 0 && win_adds_ok(t)) ? 1 : 0;
+    // a mono input fanned out, exact mode, plain form: one read stream for both channels where the table allows (VND_WIN_EXACT_MERGED=0:
+    // a pass per channel)
+    c.win_merged = (bc && exact && !split && !quad && tun.win_exact_merged != 0 && win_exact_merged_ok(t)) ? 1 : 0;
+    // split form: how many of a wave's M/4 refill accesses per tile are loaded late (at the start of the store phase that consumes
+    // them) instead of a tile ahead: 64-frame runs keep half of them out of the tap phase's registers
+    // (the fast mode's E / P accumulators are twice the exact mode's sums: all but one late there - hipRTC's build of cfg2's table
+    //  spills 20-64 bytes with 12-14 of the 16 late and none with 15; 4 to 15 late run the same; a class-path table in the exact mode
+    //  carries a segment sum AND an output sum per pair - as many registers as the fast mode)
+    if (split) {
+        const int late = M >= 64 ? ((exact && !t.has_seg) ? M / 8 : M / 4 - 1) : 0;
+        c.win_late = std::min(std::max(tun.win_split_late >= 0 ? tun.win_split_late : late, 0), M / 4 - 1);
+    }
+    c.win_stamps = std::min(std::max(tun.win_stamps, 0), 4096);
+    c.win_stamp_phases = tun.win_stamp_phases != 0 ? 1 : 0;
+    c.win_stamp_wave = std::max(0, tun.win_stamp_wave);
+    return c;
+}
+
 // geometry choice: the largest workgroup whose ring (tile + halo, mirror) still fits; small_tiles starts lower
 // (short streams: a ring is filled once per span)
-inline bool win_pick_config(const SpecTable &t, size_t lds_limit, int M, bool small_tiles, bool bc, SpecConfig *out,
-                            const std::function<bool(const SpecConfig &)> &rejected = nullptr, int quad = 0, bool split = false,
-                            bool exact = false)
+inline bool win_pick_config(const SpecTable &t, const Tuning &tun, size_t lds_limit, int M, bool small_tiles, bool bc, SpecConfig *out,
+                            const std::function<bool(const SpecConfig &)> &rejected, int quad, bool split, bool exact)
 {
     // the geometry that keeps the most waves on a CU (the ring is LDS-bound: tile + halo per workgroup), the larger
     // workgroup on a tie (the halo is shared by more lanes); short streams (small_tiles: a ring is filled once per
     // span) take at most 128 threads = 4096-frame tiles
     static const int kShapes[] = {512, 384, 256, 192, 128, 64};
-    const int nt_env = spec_env("VND_SPEC_NT", 0), g_env = spec_env("VND_WIN_G", 0);
+    const int nt_env = tun.spec_nt, g_env = tun.win_g;
     int best_waves = 0;
     for (int k = 0; k < 6; ++k) {
         const int nt = nt_env > 0 ? nt_env : kShapes[k];
         if (nt_env <= 0 && nt > 256 && quad < 2 && !split) continue;  // 512 lanes: octets (an eighth of them per channel) and the split form only
         if (nt_env <= 0 && nt == 384) continue;                       // (six waves land unevenly on four SIMDs: the split form 17 % slower than with 256 lanes)
-        if (small_tiles && nt_env <= 0 && nt > (quad ? 256 * quad : (split ? spec_env("VND_WIN_SPLIT_SMALL_NT", 256) : 128))) continue;
+        if (small_tiles && nt_env <= 0 && nt > (quad ? 256 * quad : (split ? tun.win_split_small_nt : 128))) continue;
         for (int G : {8, 4}) {
             if (g_env > 0) G = g_env;
             WinGeom g;
             if (win_geometry(t, M, nt, G, bc, lds_limit, &g, quad, split)) {
                 const int waves = win_workgroups_per_cu(g) * (nt / 64);
                 if (waves > best_waves) {
-                    SpecConfig c;
-                    c.nt = nt; c.win = M; c.win_g = G; c.win_lds = (int)g.lds_bytes(); c.bc = bc ? 1 : 0; c.win_q = g.quad; c.win_s = g.split;
-                    c.win_per_cu = win_workgroups_per_cu(g);
-                    // reads kept in flight: each holds 4 registers, and 32-frame runs already live at ~240 of the 256 a lane
-                    // has at two waves per SIMD (measured: 3 to 10 reads ahead run the same, tools/closed/win_try.py)
-                    c.la = spec_env("VND_SPEC_LA", (split && M >= 64) ? (exact ? 3 : 2) : (M >= 32 ? 4 : 6));      // (64-frame runs: 64 / 128 accumulator registers)
-                    c.rr = 0; c.pp = 0; c.dd = 0;
-                    // the store phase: interleaved frame pairs (one 16-byte read-back per store) unless that build spilled
-                    // before - it holds both channels' outputs interleaved - then planar chunks in 8-byte halves
-                    c.win_xpose = (split || quad) ? 0 : (spec_env("VND_WIN_XPOSE_PAIRS", 1) != 0 ? 1 : 0);      // (the split form's outputs cross waves as planar runs)
+                    SpecConfig c = win_config(t, g, tun, exact, bc);
                     if (rejected && rejected(c)) {                  // a build of this geometry failed or spilled before
                         if (!c.win_xpose) {
                             // (the split form with 64-frame runs lives within a few registers of its budget: one read less in flight
                             //  frees four - a mono input's build spills 12-20 bytes with two reads ahead and none with one)
                             bool found = false;
-                            if (split && M >= 64 && spec_env("VND_SPEC_LA", -1) < 0)
+                            if (split && M >= 64 && tun.spec_la < 0)
                                 while (!found && c.la > 1) { c.la -= 1; found = !rejected(c); }
                             if (!found) continue;
                             best_waves = waves;
@@ -897,7 +914,7 @@ inline bool win_pick_config(const SpecTable &t, size_t lds_limit, int M, bool sm
                         }
                         // (cfg2's fast kernel: 44 bytes of spill with 4 reads ahead, none with 3 - and 3 to 10 run the same)
                         bool found = false;
-                        if (c.la > 3 && spec_env("VND_SPEC_LA", -1) < 0) {
+                        if (c.la > 3 && tun.spec_la < 0) {
                             c.la -= 1;
                             found = !rejected(c);
                             if (!found) c.la += 1;

@@ -420,10 +420,9 @@ __device__ __forceinline__ void vw_span(const VWArgs &a, vw_lchar *lds, long lon
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         // the store / refill phase is a chain of round trips with a handful of instructions between them: ahead of the other
         // workgroup's tap phase in the SIMD's arbitration, it ends sooner and costs that tap phase next to nothing
+        // (priority 1 against none: cfg2 +1.0 % fast, +0.5 % exact; cfg3 unchanged - tools/closed/win_phase_try.py)
         if (hi) __builtin_amdgcn_s_setprio(3);
-#if VW_PRIO
-        else __builtin_amdgcn_s_setprio(VW_PRIO);
-#endif
+        else __builtin_amdgcn_s_setprio(1);
         unsigned seen = 0;                                               // (pacing: the partner's count, in flight through the store phase)
         if (pace.other != nullptr) seen = __hip_atomic_load(pace.other, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 
@@ -484,9 +483,7 @@ __device__ __forceinline__ void vw_span(const VWArgs &a, vw_lchar *lds, long lon
             hi = (unsigned)__builtin_amdgcn_readfirstlane((int)seen) > pace.done;       // the partner is ahead: this workgroup's next tile goes first
         }
         if (hi) __builtin_amdgcn_s_setprio(2);
-#if VW_PRIO
         else __builtin_amdgcn_s_setprio(0);
-#endif
         // Y. the refill is in place for every wave's window (and, after the last tile, the ring is free for the next unit)
         if (!fin) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     }
@@ -681,9 +678,7 @@ __device__ __forceinline__ void vw_span_qc(const VWArgs &a, vw_lchar *lds, long 
         // With ONE wave per channel (NWH == 1: octets of 512 lanes, quads of 256) nobody else reads the channel's planes: the wave that
         // read the window is the one that overwrites it, in LDS program order - no barrier here, two per tile instead of three.
         if constexpr (NWH > 1) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#if VW_PRIO
-        __builtin_amdgcn_s_setprio(VW_PRIO);
-#endif
+        __builtin_amdgcn_s_setprio(1);
         vw_lchar *const mine = lp + (pc & 1) * VW_CH + pl * 16u;
 #pragma unroll
         for (int r = 0; r < VW_QC; ++r)
@@ -725,9 +720,7 @@ __device__ __forceinline__ void vw_span_qc(const VWArgs &a, vw_lchar *lds, long 
 #endif
         }
         p0 = p0 + VW_NH >= VW_R ? p0 + VW_NH - VW_R : p0 + VW_NH;
-#if VW_PRIO
         __builtin_amdgcn_s_setprio(0);
-#endif
         if (!fin) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         VW_STAMP_TILE(t, 3);
     }
@@ -871,9 +864,7 @@ __device__ __forceinline__ void vw_span_s(const VWArgs &a, vw_lchar *lds, long l
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         VW_STAMP_TILE(t, 1);
         if (hi) __builtin_amdgcn_s_setprio(3);
-#if VW_PRIO
-        else __builtin_amdgcn_s_setprio(VW_PRIO);
-#endif
+        else __builtin_amdgcn_s_setprio(1);
         // (pacing: the partner's count, in flight through the store phase)
         unsigned seen = 0;
         if (pace.other != nullptr) seen = __hip_atomic_load(pace.other, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -925,9 +916,7 @@ __device__ __forceinline__ void vw_span_s(const VWArgs &a, vw_lchar *lds, long l
             hi = (unsigned)__builtin_amdgcn_readfirstlane((int)seen) > pace.done;       // the partner is ahead: this workgroup's next tile goes first
         }
         if (hi) __builtin_amdgcn_s_setprio(2);
-#if VW_PRIO
         else __builtin_amdgcn_s_setprio(0);
-#endif
         // Y. the refill is in place for every wave's window
         if (!fin) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         VW_STAMP_TILE(t, 3);
