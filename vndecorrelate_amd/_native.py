@@ -162,6 +162,17 @@ SCAN_SIGNATURES = {
                                               ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
 }
 
+# include/vnd_stream.h: chunked streaming of the tap sum, bound apart like the scan and analysis entry points
+_STREAM_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.POINTER(ctypes.c_int64)]
+STREAM_SIGNATURES = {
+    'vnd_stream_state_bytes': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
+                                              ctypes.POINTER(ctypes.c_int64)]),
+    'vnd_stream_f32_dev': (ctypes.c_int, _STREAM_ARGS + [ctypes.c_void_p]),
+    'vnd_stream_f32_host': (ctypes.c_int, _STREAM_ARGS),
+}
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -208,7 +219,8 @@ def load_library():
         _preload_hip_runtime()
         lib = ctypes.CDLL(str(LIB_PATH))
         for name, (res, args) in (list(SIGNATURES.items()) + list(INTERNAL_SIGNATURES.items())
-                                  + list(ANALYSIS_SIGNATURES.items()) + list(SCAN_SIGNATURES.items())):
+                                  + list(ANALYSIS_SIGNATURES.items()) + list(SCAN_SIGNATURES.items())
+                                  + list(STREAM_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

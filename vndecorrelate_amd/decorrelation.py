@@ -698,6 +698,32 @@ class VelvetNoise(Decorrelator):
         output_signal = self.convolve(input_signal)
         return self._host_epilogue(input_signal, output_signal)
 
+    def stream(self, *, num_streams: int = 1, in_channels: Optional[int] = None, mode: int = MODE_EXACT,
+               max_frames_per_call: int = 4800):
+        """A chunked stream of ``decorrelate`` (``streaming.Stream``): a pool of ``num_streams`` signals fed block by block,
+        each block's final outputs returned at once, ``H = latency_frames`` frames behind the input.  The concatenation
+        equals ``decorrelate`` of the whole signal - bit for bit in ``MODE_EXACT`` - with the mid/side encode (MS mode) and
+        the width on the device.  ``in_channels``: ``num_outs`` (default), or 1 for a mono signal of a stereo stage
+        (``mono_to_stereo``, read by both output channels).  Chunks of any real dtype are cast to float32 first, as
+        ``decorrelate`` casts its input.  The impulse table and envelope are taken as they are now.
+
+        The RMS normaliser scales by the RMS of the whole input and output, which a stream has not seen: a stage with a
+        normaliser raises ``ValueError`` - build it with ``normalizer=None`` (and, if wanted, normalise afterwards)."""
+        from . import streaming
+        if self.normalizer is not None:
+            raise ValueError('VelvetNoise.stream needs normalizer=None: the RMS normaliser scales by the RMS of the whole '
+                             'input and output signals, which a stream only has once it has ended')
+        channels = self.num_outs if in_channels is None else in_channels
+        if channels != self.num_outs and not (channels == 1 and self.num_outs == 2):
+            raise ValueError(f'in_channels={channels}: a stage of {self.num_outs} outputs streams {self.num_outs} '
+                             'input channels' + (', or 1 (mono to stereo)' if self.num_outs == 2 else ''))
+        if (self.mode == LayoutMode.MS or self.width is not None) and self.num_outs != 2:
+            raise ValueError('Input shape invalid: Expected shape (num samples, 2), '
+                             f'but got shape (num samples, {self.num_outs}).')
+        return streaming.Stream(self._tap_arrays(), num_streams=num_streams, in_channels=channels, mode=mode,
+                                max_frames_per_call=max_frames_per_call, ms_encode=self.mode == LayoutMode.MS,
+                                width=self.width, any_dtype=True, one_shot='VelvetNoise.decorrelate')
+
     def _host_epilogue(self, input_signal: NDArray, output_signal: NDArray) -> NDArray:
         """decorrelation.py:433-440, in place on ``output_signal`` (NumPy: bit-identical)."""
         if self.mode == LayoutMode.MS:
