@@ -25,4 +25,4 @@ from .decorrelation import (  # noqa: F401
     set_white_noise_device,
 )
 from .analysis import cross_correlogram_batched, set_correlogram_device  # noqa: F401
-from .streaming import Stream, convolve_velvet_noise_stream  # noqa: F401
+from .streaming import ChainStream, HaasStream, Stream, convolve_velvet_noise_stream  # noqa: F401

@@ -173,6 +173,17 @@ STREAM_SIGNATURES = {
     'vnd_stream_f32_host': (ctypes.c_int, _STREAM_ARGS),
 }
 
+# include/vnd_haas_stream.h: chunked streaming of the HaasEffect delay, bound apart like the tap-sum stream
+_HAAS_STREAM_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                     ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                     ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.POINTER(ctypes.c_int64)]
+HAAS_STREAM_SIGNATURES = {
+    'vnd_haas_stream_state_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                                   ctypes.POINTER(ctypes.c_int64)]),
+    'vnd_haas_stream_f64_dev': (ctypes.c_int, _HAAS_STREAM_ARGS + [ctypes.c_void_p]),
+    'vnd_haas_stream_f64_host': (ctypes.c_int, _HAAS_STREAM_ARGS),
+}
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -220,7 +231,7 @@ def load_library():
         lib = ctypes.CDLL(str(LIB_PATH))
         for name, (res, args) in (list(SIGNATURES.items()) + list(INTERNAL_SIGNATURES.items())
                                   + list(ANALYSIS_SIGNATURES.items()) + list(SCAN_SIGNATURES.items())
-                                  + list(STREAM_SIGNATURES.items())):
+                                  + list(STREAM_SIGNATURES.items()) + list(HAAS_STREAM_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

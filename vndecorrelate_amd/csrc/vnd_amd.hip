@@ -9,6 +9,7 @@
 //   vnd_correlogram.hpp  cross_correlogram (include/vnd_analysis.h)
 //   vnd_haas_scan.hpp    the Haas-delay optimiser's scan (include/vnd_scan.h)
 //   vnd_stream.hpp       chunked streaming of the tap sum (include/vnd_stream.h)
+//   vnd_haas_stream.hpp  chunked streaming of the HaasEffect delay (include/vnd_haas_stream.h)
 #include "vnd_objects.hpp"
 #include "vnd_plan.hpp"
 
@@ -415,4 +416,5 @@ vnd_status vnd_prepare_launch(vnd_ctx *ctx, const vnd_taps *t, int64_t batch, in
 #include "vnd_correlogram.hpp"
 #include "vnd_haas_scan.hpp"
 #include "vnd_stream.hpp"
+#include "vnd_haas_stream.hpp"
 #include "vnd_hooks.hpp"

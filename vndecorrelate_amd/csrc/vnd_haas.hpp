@@ -26,14 +26,21 @@ struct HArgs {
     double w_mid, w_side;            // 1.0 - width, width
 };
 
+// column c of the padded buffer before the roll, from one input frame (l, r); a mono frame is l alone
+// (shared with vnd_haas_stream.hpp, which loads its frames from a ring or the caller's chunk)
+__device__ __forceinline__ double haas_column_of(const HArgs &a, int c, double l, double r)
+{
+    if (a.Cx == 1) return l;                                  // mono_to_stereo: both columns (never re-encoded, :214)
+    if (!a.ms) return c == 0 ? l : r;
+    return c == 0 ? (l + r) * 0.5 : (l - r) * 0.5;           // LR_to_MS
+}
+
 // column c of the padded buffer before the roll, at frame k
 __device__ __forceinline__ double haas_column(const HArgs &a, const float *__restrict__ xs, int c, int64_t k)
 {
     if (k < 0 || k >= a.n) return 0.0;
-    if (a.Cx == 1) return (double)xs[k];                      // mono_to_stereo: both columns (never re-encoded, :214)
-    const double l = (double)xs[2 * k], r = (double)xs[2 * k + 1];
-    if (!a.ms) return c == 0 ? l : r;
-    return c == 0 ? (l + r) * 0.5 : (l - r) * 0.5;           // LR_to_MS
+    if (a.Cx == 1) return haas_column_of(a, c, (double)xs[k], 0.0);
+    return haas_column_of(a, c, (double)xs[2 * k], (double)xs[2 * k + 1]);
 }
 
 // frame k of the output: both columns after the roll, MS decode and stereo width (shared with vnd_haas_scan.hpp)

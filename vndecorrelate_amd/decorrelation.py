@@ -831,6 +831,25 @@ class HaasEffect(Decorrelator):
             apply_stereo_width(output_signal, self.width)
         return output_signal
 
+    def stream(self, *, num_streams: int = 1, in_channels: int = 2, max_frames_per_call: int = 4800):
+        """A chunked stream of ``decorrelate`` (``streaming.HaasStream``): a pool of ``num_streams`` signals fed block by
+        block.  The delay is causal, so each call returns the frames it was given, at no latency; ``flush()`` returns the
+        ``d = tail_frames`` tail frames, and the concatenation equals ``decorrelate`` of the whole signal bit for bit,
+        float64 ``(n + d, 2)``.  ``in_channels``: 2, or 1 for a mono ``(n,)`` signal.  Chunks of any real dtype are cast to
+        float32 first, as ``decorrelate`` casts its input.  The stage's settings are taken as they are now.
+
+        Covered: what ``optimization.haas_scan_covers`` accepts - a plain ``HaasEffect`` in LR or MS layout, delayed
+        channel 0 or 1, a delay in [0, 2**31) frames and a finite Python / float64 width or None; anything else raises
+        ``ValueError`` before any device call."""
+        from . import optimization, streaming
+        if not optimization.haas_scan_covers(np.zeros(1), self):
+            raise ValueError('HaasEffect.stream covers a plain HaasEffect in LR or MS layout with delayed channel 0 or 1, '
+                             'an integer delay in [0, 2**31) and a finite Python / float64 width or None')
+        delayed_channel, ms_mode, width = optimization._haas_key(self)
+        return streaming.HaasStream(num_streams=num_streams, in_channels=in_channels,
+                                    max_frames_per_call=max_frames_per_call, delay=optimization._haas_delay(self),
+                                    delayed_channel=delayed_channel, ms_mode=ms_mode, width=width)
+
     def haas_delay(self, input_signal: NDArray) -> NDArray:
         delay = round(self.delay_time_seconds * self.sample_rate_hz)
         n = len(input_signal)
@@ -1008,6 +1027,18 @@ class SignalChain:
             return
         self._decorrelators = [factory() for factory in self._decorrelators]
         self._hot = True
+
+    def stream(self, *, num_streams: int = 1, in_channels: int = 2, mode: int = MODE_EXACT,
+               max_frames_per_call: int = 4800):
+        """A chunked stream of the whole chain (``streaming.ChainStream``): a pool of ``num_streams`` signals of
+        ``in_channels`` channels (1: a mono ``(n,)`` signal) fed block by block, every stage on the device.  The
+        concatenation of every call's outputs equals ``chain(x)`` of the whole signal.  The stages are instantiated now and
+        taken as they are; a stage without a stream form (a normaliser, ``WhiteNoise``, other callables) raises
+        ``ValueError`` / ``TypeError`` naming it."""
+        from . import streaming
+        self._init_decorrelators()
+        return streaming.ChainStream(list(self._decorrelators), num_streams=num_streams, in_channels=in_channels,
+                                     mode=mode, max_frames_per_call=max_frames_per_call)
 
     def __call__(self, input_signal: NDArray) -> NDArray:
         self._init_decorrelators()

@@ -17,11 +17,15 @@ NumPy chunks in give NumPy arrays out, synchronously (``vnd_stream_f32_host``). 
 tensors out, enqueued on the current stream (``vnd_stream_f32_dev``), with no host copy.  The per-stream state is a
 ring of the last input frames in device memory (torch).  Every argument and shape check runs here, before any device
 call.  The calls are not graph-capturable: the stream position is a kernel argument.
+
+Two more stream forms build on it: :class:`HaasStream` (``HaasEffect(...).stream(...)``, ``include/vnd_haas_stream.h``),
+the causal Haas delay with no latency and a tail of ``d`` frames, and :class:`ChainStream` (``SignalChain(...).stream(...)``),
+every stage of a chain on the device, block by block.
 """
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -81,14 +85,17 @@ class Stream:
         self.position = 0
         self.flushed = False
 
+    _out_dtype = np.float32
+
     # ---- public ------------------------------------------------------------------------
-    def process(self, x):
-        """Push the next block of every stream; returns the outputs that became final."""
+    def process(self, x, *, final: bool = False):
+        """Push the next block of every stream; returns the outputs that became final.  ``final=True``: ``x`` is the last
+        block, and the outputs ``flush()`` would return come with it, in one device call; the signal ends."""
         if self.flushed:
             raise RuntimeError('process() after flush(): call reset() to start a new signal')
         x3, squeeze, is_torch = self._chunk(x)
         self._torch_out = is_torch
-        return self._call(x3, is_torch, squeeze, final=False)
+        return self._call(x3, is_torch, squeeze, final=bool(final))
 
     def flush(self):
         """The outputs still held back (the last ``latency_frames`` of every stream, or fewer); ends the signal."""
@@ -162,7 +169,7 @@ class Stream:
 
     def _call(self, x3, is_torch: bool, squeeze: bool, final: bool):
         n_in = 0 if x3 is None else int(x3.shape[1])
-        first, end = output_span(self.position, n_in, self.latency_frames, final)
+        first, end = self._span(n_in, final)
         n_out = end - first
         S, C = self.num_streams, self.num_channels
         if n_in == 0 and n_out == 0:                      # nothing to compute or to keep: no device call
@@ -176,13 +183,16 @@ class Stream:
             self.flushed = True
         return out[0] if squeeze else out
 
+    def _span(self, n_in: int, final: bool) -> Tuple[int, int]:
+        return output_span(self.position, n_in, self.latency_frames, final)
+
     def _empty(self, is_torch: bool, x3):
         shape = (self.num_streams, 0, self.num_channels)
         if is_torch:
             import torch
             device = x3.device if x3 is not None else torch.device('cuda', _native.default_context().device)
-            return torch.empty(shape, dtype=torch.float32, device=device)
-        return np.zeros(shape, np.float32)
+            return torch.empty(shape, dtype=getattr(torch, np.dtype(self._out_dtype).name), device=device)
+        return np.zeros(shape, self._out_dtype)
 
     def _tail(self, n_in: int, final: bool):
         return (self.num_streams, self.position, n_in, self.in_channels, int(final), self.mode, int(self.ms_encode),
@@ -259,3 +269,238 @@ def convolve_velvet_noise_stream(velvet_noise_filters, *, num_streams: int = 1, 
                          f'{channels} and {fir.shape[1]} for dimension 1.')
     return Stream(function_path_arrays(fir, channels), num_streams=num_streams, in_channels=channels, mode=mode,
                   max_frames_per_call=max_frames_per_call)
+
+
+def haas_output_span(position: int, n_in: int, delay: int, final: bool) -> Tuple[int, int]:
+    """``(E, E')`` of a call of a Haas stream (``include/vnd_haas_stream.h``): the delay is causal, so a call returns the
+    frames it pushed, and the final call the ``delay`` tail frames as well."""
+    return position, position + n_in + (delay if final else 0)
+
+
+class HaasStream(Stream):
+    """A pool of ``num_streams`` streams through one ``HaasEffect``, advancing in lockstep (``HaasEffect.stream``).
+
+    The same interface as :class:`Stream`; ``latency_frames`` is 0 (the delay is causal) and ``tail_frames`` is the delay
+    ``d``: the final call returns ``d`` frames more than it was given, so the concatenation is ``n + d`` frames, float64
+    ``(..., 2)``, bit-identical to ``HaasEffect.decorrelate`` of the whole signal.  ``in_channels``: 2, or 1 for a mono
+    ``(n,)`` signal.  Chunks of any real dtype are cast to float32 first, as ``decorrelate`` casts its input."""
+
+    _out_dtype = np.float64
+
+    def __init__(self, *, num_streams: int, in_channels: int, max_frames_per_call: int, delay: int,
+                 delayed_channel: int, ms_mode: bool, width: Optional[float]):
+        for name, v in (('num_streams', num_streams), ('in_channels', in_channels),
+                        ('max_frames_per_call', max_frames_per_call)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f'{name} must be a positive integer, got {v!r}')
+        if num_streams > _native.MAX_STREAMS_PER_CALL:
+            raise ValueError(f'num_streams {num_streams} above {_native.MAX_STREAMS_PER_CALL}: split the pool')
+        if in_channels not in (1, 2):
+            raise ValueError(f'HaasEffect streams a mono (1) or stereo (2) signal, got in_channels={in_channels}')
+        self.num_streams, self.in_channels, self.num_channels = int(num_streams), int(in_channels), 2
+        self.max_frames_per_call = int(max_frames_per_call)
+        self.delay, self.delayed_channel, self.ms_mode, self.width = int(delay), int(delayed_channel), bool(ms_mode), width
+        self.latency_frames, self.tail_frames = 0, self.delay
+        self._any_dtype, self._one_shot = True, 'HaasEffect.decorrelate'
+        self._state = None
+        self._pending = None
+        self._torch_out = False
+        self.position = 0
+        self.flushed = False
+
+    def _span(self, n_in: int, final: bool) -> Tuple[int, int]:
+        return haas_output_span(self.position, n_in, self.delay, final)
+
+    def _ensure(self, torch, device_index: int):
+        if self._state is None:
+            need = ctypes.c_int64()
+            _native._check(_native.load_library().vnd_haas_stream_state_bytes(
+                self.num_streams, self.in_channels, self.delay, self.max_frames_per_call, ctypes.byref(need)),
+                'vnd_haas_stream_state_bytes')
+            buf = torch.empty((max(need.value, 1),), dtype=torch.uint8, device=torch.device('cuda', device_index))
+            self._state = (buf, need.value)
+        return self._state
+
+    def _args(self, n_in: int, final: bool):
+        return (self.num_streams, self.position, n_in, self.in_channels, int(final), self.delay, self.delayed_channel,
+                int(self.ms_mode), int(self.width is not None), float(self.width or 0.0))
+
+    def _call_host(self, x3, n_in: int, n_out: int, final: bool):
+        from .resident import _torch
+        torch = _torch()
+        ctx = _native.default_context()
+        state, state_bytes = self._ensure(torch, ctx.device)
+        if self._pending is not None:                     # a device call of this stream may still run on its stream
+            self._pending.synchronize()
+            self._pending = None
+        x = np.ascontiguousarray(x3, np.float32) if x3 is not None else np.zeros((self.num_streams, 0, self.in_channels),
+                                                                                 np.float32)
+        y = np.empty((self.num_streams, n_out, 2), np.float64)
+        got = ctypes.c_int64()
+        _native._check(ctx._lib.vnd_haas_stream_f64_host(
+            ctx.handle, ctypes.c_void_p(state.data_ptr()), state_bytes, self.max_frames_per_call,
+            ctypes.c_void_p(x.ctypes.data), ctypes.c_void_p(y.ctypes.data), *self._args(n_in, final), ctypes.byref(got)),
+            'vnd_haas_stream_f64_host')
+        assert got.value == n_out, (got.value, n_out)
+        return y
+
+    def _call_device(self, x3, n_in: int, n_out: int, final: bool):
+        from .resident import _torch
+        torch = _torch()
+        ctx = _native.default_context()
+        device = torch.device('cuda', ctx.device)
+        if x3 is not None and x3.device != device:
+            raise ValueError(f'chunk on {x3.device}, the stream runs on {device}')
+        state, state_bytes = self._ensure(torch, ctx.device)
+        stream = torch.cuda.current_stream(device)
+        x = x3.contiguous() if x3 is not None else torch.empty((self.num_streams, 0, self.in_channels),
+                                                               dtype=torch.float32, device=device)
+        y = torch.empty((self.num_streams, n_out, 2), dtype=torch.float64, device=device)
+        got = ctypes.c_int64()
+        _native._check(ctx._lib.vnd_haas_stream_f64_dev(
+            ctx.handle, ctypes.c_void_p(state.data_ptr()), state_bytes, self.max_frames_per_call,
+            ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(y.data_ptr()), *self._args(n_in, final), ctypes.byref(got),
+            ctypes.c_void_p(stream.cuda_stream)), 'vnd_haas_stream_f64_dev')
+        assert got.value == n_out, (got.value, n_out)
+        if x.numel():
+            x.record_stream(stream)
+        state.record_stream(stream)
+        self._pending = stream
+        return y
+
+
+class StagePlan(NamedTuple):
+    """How :class:`ChainStream` runs one stage: ``kind`` ('velvet', 'haas' or 'convolve'), the channels it is fed, the dtype
+    it is handed (None: the caller's chunk, cast as that stage casts it; 'float64': a Haas output, cast to float32 on the
+    device), the most frames one of its calls takes, and its latency and tail in frames."""
+    kind: str
+    in_channels: int
+    in_dtype: Optional[str]
+    max_frames_per_call: int
+    latency_frames: int
+    tail_frames: int
+
+
+class ChainStream:
+    """A pool of ``num_streams`` streams through every stage of a ``SignalChain`` (``SignalChain.stream``).
+
+    ``process(x)`` takes the next block, as :meth:`Stream.process` does, and runs every stage on the device, in order, on
+    the current stream; ``flush()`` hands each stage's remaining frames to the next one as that stage's final block.  The
+    concatenation of everything returned equals ``chain(x)`` on the whole signal (bit for bit in ``MODE_EXACT`` and
+    ``MODE_FMA``): ``n + tail_frames`` frames, ``latency_frames`` behind the input.  A NumPy block makes one upload and one
+    download (``transfers`` counts those of the last call); a torch device block makes none and does not synchronise.
+
+    Stages: ``VelvetNoise`` with ``normalizer=None``, a covered ``HaasEffect`` (``optimization.haas_scan_covers``),
+    ``stateless(convolve_velvet_noise, velvet_noise_filters=<float32 FIR>)`` fed float32 or int16.  Anything else -
+    normalisers, ``WhiteNoise``, other callables, channel counts or dtypes the one-shot chain treats otherwise - raises
+    ``ValueError`` / ``TypeError`` naming the stage, here, before any device call."""
+
+    def __init__(self, stages, *, num_streams: int = 1, in_channels: int = 2, mode: int = _native.MODE_EXACT,
+                 max_frames_per_call: int = 4800):
+        for name, v in (('num_streams', num_streams), ('in_channels', in_channels),
+                        ('max_frames_per_call', max_frames_per_call)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f'{name} must be a positive integer, got {v!r}')
+        if mode not in MODES:
+            raise ValueError(f'unknown mode {mode!r}')
+        if not stages:
+            raise ValueError('a chain stream needs at least one stage')
+        self.num_streams, self.in_channels, self.mode = int(num_streams), int(in_channels), int(mode)
+        self.max_frames_per_call = int(max_frames_per_call)
+        self.streams, self.plan = [], []
+        channels, one_d, dtype, final_frames = self.in_channels, self.in_channels == 1, None, 0
+        for index, stage in enumerate(stages):
+            frames = max(self.max_frames_per_call, final_frames)    # a final call takes the previous stage's tail
+            try:
+                kind, stream = self._stage_stream(stage, channels, one_d, dtype, frames)
+            except (ValueError, TypeError) as exc:
+                raise type(exc)(f'stage {index} ({type(stage).__name__}): {exc}') from exc
+            tail = stream.tail_frames if kind == 'haas' else 0
+            self.plan.append(StagePlan(kind, channels, dtype, frames, stream.latency_frames, tail))
+            self.streams.append(stream)
+            final_frames += stream.latency_frames + tail        # a final call returns n_in + H (or n_in + d) frames
+            channels, one_d, dtype = stream.num_channels, False, ('float64' if kind == 'haas' else 'float32')
+        self.num_channels = channels
+        self.latency_frames = sum(p.latency_frames for p in self.plan)
+        self.tail_frames = sum(p.tail_frames for p in self.plan)
+        self.transfers = {'to_device': 0, 'to_host': 0}
+        self._torch_out = False
+        self._squeeze = self.num_streams == 1
+        self.position = 0
+        self.flushed = False
+
+    def _stage_stream(self, stage, channels: int, one_d: bool, dtype: Optional[str], frames: int):
+        from functools import partial
+        from . import decorrelation as dec
+        from . import optimization
+        S = self.num_streams
+        if isinstance(stage, dec.VelvetNoise):
+            if not one_d and channels != stage.num_outs:
+                raise ValueError(f'a stage of {stage.num_outs} outputs is fed {channels} channels: the one-shot chain '
+                                 f'convolves its first {stage.num_outs} columns, which a stream does not')
+            return 'velvet', stage.stream(num_streams=S, in_channels=channels, mode=self.mode, max_frames_per_call=frames)
+        if isinstance(stage, dec.HaasEffect):
+            if not optimization.haas_scan_covers(np.zeros(1), stage):
+                raise ValueError('only a plain HaasEffect in LR or MS layout, delayed channel 0 or 1, an integer delay '
+                                 'in [0, 2**31) and a finite Python / float64 width or None streams')
+            if not one_d and channels != 2:
+                raise ValueError(f'HaasEffect streams a mono (n,) or a stereo (n, 2) signal, it is fed {channels} channels')
+            return 'haas', stage.stream(num_streams=S, in_channels=channels, max_frames_per_call=frames)
+        if isinstance(stage, dec.WhiteNoise):
+            raise ValueError('WhiteNoise does not stream: its RMS normaliser scales by the RMS of the whole signal')
+        if isinstance(stage, partial) and stage.func is dec.convolve_velvet_noise and not stage.args \
+                and set(stage.keywords) == {'velvet_noise_filters'}:
+            if dtype == 'float64':
+                raise TypeError('a stateless convolve fed a float64 Haas output is multiplied in float64 by the one-shot '
+                                'convolve_velvet_noise (it promotes); a stream runs float32 only')
+            if one_d:
+                raise ValueError('a stateless convolve takes a (n, C) signal: the one-shot convolve_velvet_noise raises '
+                                 'IndexError for a mono (n,) one')
+            return 'convolve', convolve_velvet_noise_stream(stage.keywords['velvet_noise_filters'], num_streams=S,
+                                                            in_channels=channels, mode=self.mode,
+                                                            max_frames_per_call=frames)
+        raise TypeError(f'{stage!r} has no stream form: stateless stages stream as '
+                        'stateless(convolve_velvet_noise, velvet_noise_filters=<float32 FIR>) only')
+
+    # ---- public ------------------------------------------------------------------------
+    def process(self, x):
+        """Push the next block of every stream through every stage; returns the outputs that became final."""
+        if self.flushed:
+            raise RuntimeError('process() after flush(): call reset() to start a new signal')
+        first = self.streams[0]
+        x3, squeeze, is_torch = first._chunk(x)          # the first stage's shape and dtype rules, on the host or device
+        self.transfers = {'to_device': 0, 'to_host': 0}
+        self._torch_out, self._squeeze = is_torch, squeeze
+        if not is_torch:
+            from .resident import _torch
+            torch = _torch()
+            x3 = torch.from_numpy(np.ascontiguousarray(x3)).to(torch.device('cuda', _native.default_context().device))
+            self.transfers['to_device'] += 1
+        self.position += int(x3.shape[1])
+        return self._run(x3, final=False)
+
+    def flush(self):
+        """Every stage's remaining outputs, each handed to the next stage as its final block; ends the signal."""
+        if self.flushed:
+            raise RuntimeError('flush() after flush(): call reset() to start a new signal')
+        self.transfers = {'to_device': 0, 'to_host': 0}
+        out = self._run(None, final=True)
+        self.flushed = True
+        return out
+
+    def reset(self):
+        """Start a new signal at position 0 in every stage."""
+        for stream in self.streams:
+            stream.reset()
+        self.position = 0
+        self.flushed = False
+
+    def _run(self, buf, final: bool):
+        for stream in self.streams:                      # device tensors from stage to stage, on the current stream
+            if buf is not None:
+                buf, _, _ = stream._chunk(buf)           # a float64 Haas output is cast to float32 here, on the device
+            buf = stream._call(buf, True, False, final)
+        if not self._torch_out:
+            buf = buf.cpu().numpy()
+            self.transfers['to_host'] += 1
+        return buf[0] if self._squeeze else buf
