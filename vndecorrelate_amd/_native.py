@@ -184,6 +184,17 @@ HAAS_STREAM_SIGNATURES = {
     'vnd_haas_stream_f64_host': (ctypes.c_int, _HAAS_STREAM_ARGS),
 }
 
+# include/vnd_correlogram_stream.h: the cross-correlogram streamed block by block, bound apart like the other streams
+CORRELOGRAM_STREAM_SIGNATURES = {
+    'vnd_correlogram_stream_state_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
+                                                          ctypes.POINTER(ctypes.c_int64)]),
+    'vnd_correlogram_stream_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                                      ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                      ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
+                                                      ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]),
+}
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -231,7 +242,8 @@ def load_library():
         lib = ctypes.CDLL(str(LIB_PATH))
         for name, (res, args) in (list(SIGNATURES.items()) + list(INTERNAL_SIGNATURES.items())
                                   + list(ANALYSIS_SIGNATURES.items()) + list(SCAN_SIGNATURES.items())
-                                  + list(STREAM_SIGNATURES.items()) + list(HAAS_STREAM_SIGNATURES.items())):
+                                  + list(STREAM_SIGNATURES.items()) + list(HAAS_STREAM_SIGNATURES.items())
+                                  + list(CORRELOGRAM_STREAM_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -661,6 +673,27 @@ def correlogram_device(ctx: 'Context', x_ptr: int, y_ptr: int, out_ptr: int, bat
                                             ctypes.c_void_p(out_ptr), batch, n, stream_stride, frame_stride, window, hop,
                                             num_lags, float(eps), ctypes.c_void_p(stream)), 'vnd_correlogram_f32_dev')
 
+
+def correlogram_stream_state_bytes(batch: int, window: int, max_frames_per_call: int) -> int:
+    """``vnd_correlogram_stream_state_bytes``: the ring of a pool of ``batch`` streams."""
+    need = ctypes.c_int64()
+    _check(load_library().vnd_correlogram_stream_state_bytes(batch, window, max_frames_per_call, ctypes.byref(need)),
+           'vnd_correlogram_stream_state_bytes')
+    return need.value
+
+
+def correlogram_stream_device(ctx: 'Context', state_ptr: int, state_bytes: int, max_frames_per_call: int, x_ptr: int,
+                              y_ptr: int, stream_stride: int, frame_stride: int, out_ptr: int, batch: int, position: int,
+                              n_in: int, *, window: int, hop: int, num_lags: int, eps: float, stream: int = 0) -> int:
+    """``vnd_correlogram_stream_f32_dev``: push ``n_in`` frames per stream (frame t of stream b at ``b * stream_stride +
+    t * frame_stride``) at ``position``; the rows that became final go to float32 ``(batch, rows, num_lags)`` at
+    ``out_ptr``, enqueued on ``stream``.  Returns the row count."""
+    rows = ctypes.c_int64()
+    _check(ctx._lib.vnd_correlogram_stream_f32_dev(
+        ctx.handle, ctypes.c_void_p(state_ptr), state_bytes, max_frames_per_call, ctypes.c_void_p(x_ptr),
+        ctypes.c_void_p(y_ptr), stream_stride, frame_stride, ctypes.c_void_p(out_ptr), batch, position, n_in, window, hop,
+        num_lags, float(eps), ctypes.byref(rows), ctypes.c_void_p(stream)), 'vnd_correlogram_stream_f32_dev')
+    return rows.value
 
 
 def haas_scan_workspace_bytes(n: int, n_delays: int, max_delay: int) -> int:

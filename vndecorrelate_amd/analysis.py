@@ -6,7 +6,9 @@ The reference measures decorrelation with ``utils/dsp.py:313`` ``cross_correlogr
 * ``utils.dsp.cross_correlogram`` - the reference's signature; on the device where covered, NumPy otherwise;
 * :func:`cross_correlogram_batched` - ``(B, n)`` pairs, or channel 0 against channel 1 of a ``(B, n, 2)`` signal in
   place; NumPy in, NumPy out (pinned); a float32 torch tensor on the device in, a device tensor out;
-* :func:`set_correlogram_device` and the pure routing rule :func:`correlogram_covers`.
+* :func:`set_correlogram_device` and the pure routing rule :func:`correlogram_covers`;
+* :func:`cross_correlogram_stream` - the same rows, block by block, for a pool of live streams
+  (``include/vnd_correlogram_stream.h``): a :class:`CorrelogramStream`.
 
 Numerics: each correlation output is one float64 FMA chain over exact products, rounded once; the
 energies are float64 sums rounded once; the normaliser is NumPy 2's float32 arithmetic.  The result is within one
@@ -183,4 +185,209 @@ def cross_correlogram_batched(x, y=None, *, sample_rate_hz: int = 44100, max_lag
     return np.stack([cross_correlogram(a, b, **kw) for a, b in pairs])
 
 
-__all__ = ['cross_correlogram_batched', 'correlogram_covers', 'set_correlogram_device', 'MAX_WINDOW']
+def stream_rows(position: int, n_in: int, window: int, hop: int):
+    """``(first, end)``: the rows ``[first, end)`` - windows, counted from 0 - that a call pushing ``n_in`` frames at
+    ``position`` (frames pushed before it) completes (``include/vnd_correlogram_stream.h``)."""
+    return _windows(position, window, hop), _windows(position + n_in, window, hop)
+
+
+def _is_torch(x) -> bool:
+    return type(x).__module__.split('.')[0] == 'torch'
+
+
+class CorrelogramStream:
+    """``cross_correlogram`` of a pool of ``num_streams`` stream pairs, block by block (``cross_correlogram_stream``).
+
+    ``process(x, y=None)`` pushes the next block of every stream: ``x`` ``(S, B, 2)`` (channel 0 against channel 1, read in
+    place) or ``(B, 2)`` when ``S == 1``; or ``x``, ``y`` ``(S, B)``, or ``(B,)`` when ``S == 1``.  ``0 <= B <=
+    max_frames_per_call``, free to change from call to call.  It returns the rows of the windows that became final, float32
+    ``(S, rows, num_lags)`` (``(rows, num_lags)`` for the unbatched forms); their concatenation equals
+    :func:`cross_correlogram_batched` of the whole signal bit for bit.  NumPy in, NumPy out (the block goes through the
+    device and back, synchronously).  A float32 device tensor in, a device tensor out, enqueued on the current stream with
+    no host copy or synchronisation.  Float64 NumPy blocks are cast to float32 as ``cross_correlogram`` casts them, float64
+    device tensors by torch on the device (round to nearest even, as ``astype``).
+
+    ``flush()`` returns the zero rows left - windows that never complete are dropped, as in the reference - and ends the
+    signal: ``process`` raises ``RuntimeError`` after it until ``reset()``.  ``window``, ``hop``, ``num_lags``: the sizes
+    in samples; ``position``: the frames pushed per stream.  Every argument and shape check runs before any device call;
+    the state (a ring of the last ``window - 1`` frames per stream) is allocated on first use.  The stream always runs
+    on the device: ``set_correlogram_device`` is not consulted, and without a device the first call that needs one
+    raises ``RuntimeError``."""
+
+    def __init__(self, num_streams: int, *, window: int, hop: int, num_lags: int, epsilon, max_frames_per_call: int):
+        for name, v in (('num_streams', num_streams), ('max_frames_per_call', max_frames_per_call)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f'{name} must be a positive integer, got {v!r}')
+        if num_streams > _native.MAX_STREAMS_PER_CALL:
+            raise ValueError(f'num_streams {num_streams} above {_native.MAX_STREAMS_PER_CALL}: split the pool')
+        if not correlogram_covers(0, window, hop, num_lags, epsilon):
+            raise ValueError(f'window {window}, hop {hop}, {num_lags} lags and epsilon {epsilon!r} have no device form '
+                             f'(correlogram_covers is False) and the stream has no NumPy one: use cross_correlogram')
+        self.num_streams, self.max_frames_per_call = int(num_streams), int(max_frames_per_call)
+        self.window, self.hop, self.num_lags, self.epsilon = int(window), int(hop), int(num_lags), epsilon
+        self._state = None            # (torch uint8 tensor, bytes)
+        self._last_stream = None      # torch stream of the last launch: the next one is ordered after it
+        self._torch_out = None        # device of the last process() that took a tensor: flush() answers in kind
+        self._squeeze_last = True
+        self.position = 0
+        self.flushed = False
+
+    # ---- public ------------------------------------------------------------------------
+    def process(self, x, y=None):
+        """Push the next block of every stream; returns the rows that became final."""
+        if self.flushed:
+            raise RuntimeError('process() after flush(): call reset() to start a new signal')
+        xs, ys, squeeze, is_torch = self._chunk(x, y)
+        self._squeeze_last = squeeze
+        self._torch_out = xs.device if is_torch else None
+        n_in = int(xs.shape[1])
+        first, end = stream_rows(self.position, n_in, self.window, self.hop)
+        if n_in == 0:                                     # nothing to compute or to keep: no device call
+            out = self._empty(0)
+        elif is_torch:
+            out = self._call_device(xs, ys, n_in, end - first)
+        else:
+            out = self._call_host(xs, ys, n_in, end - first)
+        self.position += n_in
+        return out[0] if squeeze else out
+
+    def flush(self):
+        """The rows still held back: none (incomplete windows are dropped); ends the signal."""
+        if self.flushed:
+            raise RuntimeError('flush() after flush(): call reset() to start a new signal')
+        self.flushed = True
+        out = self._empty(0)
+        return out[0] if self.num_streams == 1 and self._squeeze_last else out
+
+    def reset(self):
+        """Start a new signal at position 0 (the ring needs no clearing: it is never read before it is written)."""
+        self.position = 0
+        self.flushed = False
+
+    # ---- checks --------------------------------------------------------------------------
+    def _cast(self, v, is_torch: bool):
+        if is_torch:
+            torch = _torch()
+            if not v.is_cuda:
+                raise ValueError('a torch block must be a device tensor (NumPy arrays take the host path)')
+            if v.dtype == torch.float64:
+                return v.to(torch.float32)
+            if v.dtype != torch.float32:
+                raise TypeError(f'device blocks must be float32 or float64, got {v.dtype}')
+            return v
+        v = np.asarray(v)
+        if v.dtype.kind not in 'biuf':
+            raise TypeError(f'blocks must be real numbers, got {v.dtype}')
+        return to_float32(v)
+
+    def _chunk(self, x, y):
+        is_torch = _is_torch(x)
+        if y is not None and _is_torch(y) != is_torch:
+            raise ValueError('x and y must both be NumPy arrays or both device tensors')
+        xs = self._cast(x, is_torch)
+        ys = None if y is None else self._cast(y, is_torch)
+        S = self.num_streams
+        shape = tuple(xs.shape)
+        if ys is None:
+            if len(shape) == 2 and S == 1:
+                xs, squeeze = xs.reshape(1, *shape), True
+            elif len(shape) == 3:
+                squeeze = False
+            else:
+                raise ValueError(f'with y=None, x must be (num_streams={S}, frames, 2)'
+                                 + (' or (frames, 2)' if S == 1 else '') + f': got shape {shape}')
+            if xs.shape[0] != S or xs.shape[2] != 2:
+                raise ValueError(f'block of shape {shape} does not match the pool: {S} streams, 2 channels')
+        else:
+            if tuple(ys.shape) != shape:
+                raise ValueError(f'x and y must have one shape: got {shape} and {tuple(ys.shape)}')
+            if is_torch and ys.device != xs.device:
+                raise ValueError('x and y must be tensors on the same device')
+            if len(shape) == 1 and S == 1:
+                xs, ys, squeeze = xs.reshape(1, -1), ys.reshape(1, -1), True
+            elif len(shape) == 2:
+                squeeze = False
+            else:
+                raise ValueError(f'x and y must be (num_streams={S}, frames)' + (' or (frames,)' if S == 1 else '')
+                                 + f': got shape {shape}')
+            if xs.shape[0] != S:
+                raise ValueError(f'block of shape {shape} does not match the pool of {S} streams')
+        if xs.shape[1] > self.max_frames_per_call:
+            raise ValueError(f'{xs.shape[1]} frames in one call, above max_frames_per_call={self.max_frames_per_call}')
+        return xs, ys, squeeze, is_torch
+
+    # ---- the device -------------------------------------------------------------------------
+    def _empty(self, rows: int):
+        shape = (self.num_streams, rows, self.num_lags)
+        if self._torch_out is not None:
+            return _torch().empty(shape, dtype=_torch().float32, device=self._torch_out)
+        return np.zeros(shape, np.float32)
+
+    def _launch(self, torch, ctx, device, xp: int, yp: int, stream_stride: int, frame_stride: int, n_in: int, rows: int):
+        if self._state is None:
+            need = _native.correlogram_stream_state_bytes(self.num_streams, self.window, self.max_frames_per_call)
+            self._state = (torch.empty((need,), dtype=torch.uint8, device=device), need)
+        state, state_bytes = self._state
+        stream = torch.cuda.current_stream(device)
+        if self._last_stream is not None and self._last_stream != stream:
+            stream.wait_stream(self._last_stream)         # the ring is read and written in call order
+        out = torch.empty((self.num_streams, rows, self.num_lags), dtype=torch.float32, device=device)
+        got = _native.correlogram_stream_device(
+            ctx, state.data_ptr(), state_bytes, self.max_frames_per_call, xp, yp, max(1, stream_stride), frame_stride,
+            out.data_ptr(), self.num_streams, self.position, n_in, window=self.window, hop=self.hop,
+            num_lags=self.num_lags, eps=float(self.epsilon), stream=stream.cuda_stream)
+        assert got == rows, (got, rows)
+        state.record_stream(stream)
+        self._last_stream = stream
+        return out, stream
+
+    def _call_device(self, xs, ys, n_in: int, rows: int):
+        torch = _torch()
+        ctx = _native.default_context()
+        device = torch.device('cuda', ctx.device)
+        if xs.device != device:
+            raise ValueError(f'block on {xs.device}, the stream runs on {device}')
+        if ys is None:
+            if xs.stride(2) != 1 or not 1 <= xs.stride(1) <= _INT32_MAX or (self.num_streams > 1 and xs.stride(0) < 1):
+                xs = xs.contiguous()
+            keep, xp, yp = (xs,), xs.data_ptr(), xs.data_ptr() + 4
+        else:
+            if (xs.stride() != ys.stride() or not 1 <= xs.stride(1) <= _INT32_MAX
+                    or (self.num_streams > 1 and xs.stride(0) < 1)):
+                xs, ys = xs.contiguous(), ys.contiguous()
+            keep, xp, yp = (xs, ys), xs.data_ptr(), ys.data_ptr()
+        out, stream = self._launch(torch, ctx, device, xp, yp, xs.stride(0), xs.stride(1), n_in, rows)
+        for t in keep:
+            t.record_stream(stream)
+        return out
+
+    def _call_host(self, xs, ys, n_in: int, rows: int):
+        torch = _torch()
+        ctx = _native.default_context()
+        device = torch.device('cuda', ctx.device)
+        xd = torch.from_numpy(np.ascontiguousarray(xs)).to(device)
+        if ys is None:
+            out_d, _ = self._launch(torch, ctx, device, xd.data_ptr(), xd.data_ptr() + 4, n_in * 2, 2, n_in, rows)
+        else:
+            yd = torch.from_numpy(np.ascontiguousarray(ys)).to(device)
+            out_d, _ = self._launch(torch, ctx, device, xd.data_ptr(), yd.data_ptr(), n_in, 1, n_in, rows)
+        out = _native.pinned_pool.empty(tuple(out_d.shape), np.float32)
+        if out.size:
+            torch.from_numpy(out).copy_(out_d)
+        return out
+
+
+def cross_correlogram_stream(num_streams: int = 1, *, sample_rate_hz: int = 44100, max_lag_seconds: float = 0.02,
+                             window_size_seconds: float = 0.02, stride_seconds: float = 0.01, epsilon: float = EPSILON,
+                             max_frames_per_call: int = 4800) -> CorrelogramStream:
+    """A :class:`CorrelogramStream`: ``cross_correlogram`` with these arguments, computed block by block for a pool of
+    ``num_streams`` stream pairs as their frames arrive.  The sizes come from ``correlogram_sizes`` as for the one-shot
+    call.  Sizes the device does not cover (:func:`correlogram_covers`) and pools above ``MAX_STREAMS_PER_CALL`` raise
+    ``ValueError`` here: there is no NumPy stream.  ``set_correlogram_device`` is not consulted."""
+    window, hop, max_lag = correlogram_sizes(sample_rate_hz, max_lag_seconds, window_size_seconds, stride_seconds)
+    return CorrelogramStream(num_streams, window=window, hop=hop, num_lags=2 * max_lag + 1, epsilon=epsilon,
+                             max_frames_per_call=max_frames_per_call)
+
+
+__all__ = ['cross_correlogram_batched', 'cross_correlogram_stream', 'CorrelogramStream', 'correlogram_covers',
+           'set_correlogram_device', 'MAX_WINDOW']

@@ -7,6 +7,7 @@
 //   vnd_rccl.hpp     shard ranges, the tap table over RCCL         vnd_hooks.hpp  measurement / tuning / diagnosis hooks
 //   vnd_dense.hpp    WhiteNoise: the dense float64 FIR and its stage
 //   vnd_correlogram.hpp  cross_correlogram (include/vnd_analysis.h)
+//   vnd_correlogram_stream.hpp  cross_correlogram streamed block by block (include/vnd_correlogram_stream.h)
 //   vnd_haas_scan.hpp    the Haas-delay optimiser's scan (include/vnd_scan.h)
 //   vnd_stream.hpp       chunked streaming of the tap sum (include/vnd_stream.h)
 //   vnd_haas_stream.hpp  chunked streaming of the HaasEffect delay (include/vnd_haas_stream.h)
@@ -414,6 +415,7 @@ vnd_status vnd_prepare_launch(vnd_ctx *ctx, const vnd_taps *t, int64_t batch, in
 #include "vnd_stage.hpp"
 #include "vnd_dense.hpp"
 #include "vnd_correlogram.hpp"
+#include "vnd_correlogram_stream.hpp"
 #include "vnd_haas_scan.hpp"
 #include "vnd_stream.hpp"
 #include "vnd_haas_stream.hpp"

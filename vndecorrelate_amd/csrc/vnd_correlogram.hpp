@@ -41,6 +41,30 @@ struct CgArgs {
     float eps;
 };
 
+// The sample sources of correlogram_kernel: the one place it reads x and y.  A source names the kernel's argument
+// type (Args; cg(a) is its CgArgs) and, per window ww of stream b, gives a Run of the window's W consecutive frames:
+// run.x(i) and run.y(i), i in [0, W).  slot0 is the ring slot of the window's first frame
+// (slot0_of(a, ww): one 64-bit modulo per window, not per sample); a source without a ring ignores it.  prologue(a, b)
+// runs first in every workgroup; false ends the workgroup.
+struct CgSignal {                               // the one-shot call: x[b * stream_stride + f * frame_stride]
+    using Args = CgArgs;
+    static constexpr bool kRing = false;
+    struct Run {
+        const float *px, *py;
+        int64_t bs, f0;               // b * stream_stride, the window's first frame
+        int32_t fs;
+        __device__ __forceinline__ float x(int i) const { return px[bs + (f0 + i) * (int64_t)fs]; }
+        __device__ __forceinline__ float y(int i) const { return py[bs + (f0 + i) * (int64_t)fs]; }
+    };
+    __device__ static __forceinline__ const CgArgs &cg(const Args &a) { return a; }
+    __device__ static __forceinline__ bool prologue(const Args &, int64_t) { return true; }
+    __device__ static __forceinline__ int64_t slot0_of(const Args &, int64_t) { return 0; }
+    __device__ static __forceinline__ Run run(const Args &a, int64_t b, int64_t ww, int64_t)
+    {
+        return Run{a.x, a.y, b * a.stream_stride, ww * a.hop, a.frame_stride};
+    }
+};
+
 __device__ __forceinline__ void cg_load(double (&v)[kCgR], const float *p)
 {
 #pragma unroll
@@ -66,8 +90,10 @@ __device__ __forceinline__ void cg_block(double (&acc)[kCgR], const double (&lo)
     }
 }
 
-__global__ __launch_bounds__(kCgThreads) void correlogram_kernel(CgArgs a)
+template <class Src>
+__global__ __launch_bounds__(kCgThreads) void correlogram_kernel(const typename Src::Args sa)
 {
+    const CgArgs &a = Src::cg(sa);
     __shared__ __align__(16) float xs[kCgG][kCgTile + kCgTaps];
     __shared__ __align__(16) double hs[kCgG][kCgTaps];
     __shared__ float en[kCgG][2];
@@ -80,6 +106,8 @@ __global__ __launch_bounds__(kCgThreads) void correlogram_kernel(CgArgs a)
     const int t0 = wave * kCgSpan + (lane & 15) * kCgR;         // the lane's first column, relative to T0
     const int W = a.W;
     float *__restrict__ orow = a.out + (b * a.windows + w) * (int64_t)a.num_lags;
+    __shared__ int64_t slot0[kCgG];                             // (a ring source: the ring slot of each window's frame 0)
+    if (!Src::prologue(sa, b)) return;
 
     if (T0 >= a.jmax) {                                         // a tile of trailing zero columns only
         if (w < a.windows)
@@ -97,10 +125,11 @@ __global__ __launch_bounds__(kCgThreads) void correlogram_kernel(CgArgs a)
         const int64_t ww = group * kCgG + wave;
         double ex = 0.0, ey = 0.0;
         if (ww < a.windows) {
-            const int64_t base = b * a.stream_stride + ww * a.hop * (int64_t)a.frame_stride;
+            const int64_t s0 = Src::slot0_of(sa, ww);
+            if (Src::kRing && lane == 0) slot0[wave] = s0;     // read by the staging loops after the next barrier
+            const typename Src::Run r = Src::run(sa, b, ww, s0);
             for (int i = lane; i < W; i += 64) {
-                const int64_t at = base + (int64_t)i * a.frame_stride;
-                const double xv = (double)a.x[at], yv = (double)a.y[at];
+                const double xv = (double)r.x(i), yv = (double)r.y(i);
                 ex = fma(xv, xv, ex);
                 ey = fma(yv, yv, ey);
             }
@@ -139,7 +168,7 @@ __global__ __launch_bounds__(kCgThreads) void correlogram_kernel(CgArgs a)
             const int i = gbase + s;
             float v = 0.0f;
             if (ww < a.windows && i >= 0 && i < W)
-                v = a.x[b * a.stream_stride + (ww * a.hop + i) * (int64_t)a.frame_stride];
+                v = Src::run(sa, b, ww, Src::kRing ? slot0[gg] : 0).x(i);
             xs[gg][s] = v;
         }
         for (int e = threadIdx.x; e < kCgG * Lr; e += kCgThreads) {
@@ -148,7 +177,7 @@ __global__ __launch_bounds__(kCgThreads) void correlogram_kernel(CgArgs a)
             const int k = kc_end - Lr + p;
             double v = 0.0;
             if (ww < a.windows && k >= kc0)
-                v = (double)a.y[b * a.stream_stride + (ww * a.hop + (W - 1 - k)) * (int64_t)a.frame_stride];
+                v = (double)Src::run(sa, b, ww, Src::kRing ? slot0[gg] : 0).y(W - 1 - k);
             hs[gg][p] = v;
         }
         __syncthreads();
@@ -239,7 +268,7 @@ vnd_status vnd_correlogram_f32_dev(vnd_ctx *ctx, const float *x, const float *y,
         for (int64_t g0 = 0; g0 < groups; g0 += per_launch) {
             s.group0 = g0;
             const int64_t ng = std::min(per_launch, groups - g0);
-            hipLaunchKernelGGL(correlogram_kernel, dim3((unsigned)(ng * c.tiles), (unsigned)nb), dim3(kCgThreads), 0, stream, s);
+            hipLaunchKernelGGL(correlogram_kernel<CgSignal>, dim3((unsigned)(ng * c.tiles), (unsigned)nb), dim3(kCgThreads), 0, stream, s);
         }
     }
     HIP_TRY(hipGetLastError());
