@@ -162,6 +162,21 @@ SCAN_SIGNATURES = {
                                               ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
 }
 
+# include/vnd_haas_search.h: (signal, delay) pairs of a pool, the batched Haas-delay optimiser's unit of work
+HAAS_SEARCH_SIGNATURES = {
+    'vnd_haas_pairs_workspace_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                      ctypes.POINTER(ctypes.c_int64)]),
+    'vnd_haas_pairs_f64_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
+                                              ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                              ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    'vnd_haas_pairs_f64_host': (ctypes.c_int, [ctypes.c_void_p, _c_f32p, ctypes.c_int32, ctypes.c_int64,
+                                               ctypes.c_int32, _c_i32p, _c_i32p, ctypes.c_int32, ctypes.c_int32,
+                                               ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
+                                               ctypes.POINTER(ctypes.c_double)]),
+}
+HAAS_PAIRS_MAX = 1048560   # VND_HAAS_PAIRS_MAX: pairs per call
+
 # include/vnd_stream.h: chunked streaming of the tap sum, bound apart like the scan and analysis entry points
 _STREAM_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
                 ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
@@ -243,7 +258,8 @@ def load_library():
         for name, (res, args) in (list(SIGNATURES.items()) + list(INTERNAL_SIGNATURES.items())
                                   + list(ANALYSIS_SIGNATURES.items()) + list(SCAN_SIGNATURES.items())
                                   + list(STREAM_SIGNATURES.items()) + list(HAAS_STREAM_SIGNATURES.items())
-                                  + list(CORRELOGRAM_STREAM_SIGNATURES.items())):
+                                  + list(CORRELOGRAM_STREAM_SIGNATURES.items())
+                                  + list(HAAS_SEARCH_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -730,6 +746,51 @@ def haas_scan_device(ctx: 'Context', x_ptr: int, n: int, channels: int, delays_p
                                           float(width or 0.0), ctypes.c_void_p(moments_ptr),
                                           ctypes.c_void_p(workspace_ptr), workspace_bytes, ctypes.c_void_p(stream)),
            'vnd_haas_scan_f64_dev')
+
+
+def haas_pairs_workspace_bytes(n: int, n_pairs: int, max_delay: int) -> int:
+    need = ctypes.c_int64()
+    _check(load_library().vnd_haas_pairs_workspace_bytes(n, n_pairs, max_delay, ctypes.byref(need)),
+           'vnd_haas_pairs_workspace_bytes')
+    return need.value
+
+
+def haas_pairs_host(ctx: 'Context', x: np.ndarray, signals, delays, *, delayed_channel: int, ms_mode: bool,
+                    width) -> np.ndarray:
+    """``vnd_haas_pairs_f64_host``: float64 ``(P, 8)`` polar moments of ``HaasEffect(delay d_p).decorrelate(x[s_p])``
+    for each pair ``(s_p, d_p)``, from a C-contiguous float32 ``(batch, n, 1|2)`` pool in host memory."""
+    if x.dtype != np.float32 or not x.flags.c_contiguous or x.ndim != 3:
+        raise ValueError('haas_pairs_host wants a C-contiguous float32 (batch, n, C) array')
+    s = np.ascontiguousarray(signals, np.int64)
+    d = np.ascontiguousarray(delays, np.int64)
+    i32 = np.iinfo(np.int32)
+    for v in (s, d):
+        if v.ndim != 1 or (v.size and (v.min() < i32.min or v.max() > i32.max)):
+            raise ValueError('haas_pairs_host wants 1-D lists of int32 signal indices and delays')
+    if s.size != d.size:
+        raise ValueError(f'{s.size} signal indices for {d.size} delays')
+    s, d = s.astype(np.int32), d.astype(np.int32)
+    out = np.zeros((d.size, MOMENTS), np.float64)
+    _check(ctx._lib.vnd_haas_pairs_f64_host(ctx.handle, _ptr(x, ctypes.c_float), x.shape[0], x.shape[1], x.shape[2],
+                                            _ptr(s, ctypes.c_int32), _ptr(d, ctypes.c_int32), d.size,
+                                            int(delayed_channel), int(bool(ms_mode)), int(width is not None),
+                                            float(width or 0.0), _ptr(out, ctypes.c_double)),
+           'vnd_haas_pairs_f64_host')
+    return out
+
+
+def haas_pairs_device(ctx: 'Context', x_ptr: int, batch: int, n: int, channels: int, signals_ptr: int,
+                      delays_ptr: int, n_pairs: int, moments_ptr: int, *, delayed_channel: int, ms_mode: bool, width,
+                      workspace_ptr: int, workspace_bytes: int, stream: int = 0):
+    """``vnd_haas_pairs_f64_dev``: float64 ``(n_pairs, 8)`` moments from a float32 ``(batch, n, channels)`` pool and
+    int32 signal indices and delays, all device buffers, enqueued on ``stream``."""
+    _check(ctx._lib.vnd_haas_pairs_f64_dev(ctx.handle, ctypes.c_void_p(x_ptr), batch, n, channels,
+                                           ctypes.c_void_p(signals_ptr), ctypes.c_void_p(delays_ptr), n_pairs,
+                                           int(delayed_channel), int(bool(ms_mode)), int(width is not None),
+                                           float(width or 0.0), ctypes.c_void_p(moments_ptr),
+                                           ctypes.c_void_p(workspace_ptr), workspace_bytes, ctypes.c_void_p(stream)),
+           'vnd_haas_pairs_f64_dev')
+
 
 def polar_moments_workspace_bytes(n: int, pairs: int) -> int:
     need = ctypes.c_int64()

@@ -8,7 +8,7 @@
 //   vnd_dense.hpp    WhiteNoise: the dense float64 FIR and its stage
 //   vnd_correlogram.hpp  cross_correlogram (include/vnd_analysis.h)
 //   vnd_correlogram_stream.hpp  cross_correlogram streamed block by block (include/vnd_correlogram_stream.h)
-//   vnd_haas_scan.hpp    the Haas-delay optimiser's scan (include/vnd_scan.h)
+//   vnd_haas_scan.hpp    the Haas-delay optimiser's scan (include/vnd_scan.h) and its pool pairs (include/vnd_haas_search.h)
 //   vnd_stream.hpp       chunked streaming of the tap sum (include/vnd_stream.h)
 //   vnd_haas_stream.hpp  chunked streaming of the HaasEffect delay (include/vnd_haas_stream.h)
 #include "vnd_objects.hpp"

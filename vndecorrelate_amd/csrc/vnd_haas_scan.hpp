@@ -1,22 +1,24 @@
-// vnd_haas_scan.hpp - the Haas-delay optimiser's scan on the device (include/vnd_scan.h): the eight polar
-// moments (vnd_moments.hpp's quantities and order) of HaasEffect(delay d_f).decorrelate(x) for F delays of ONE
-// signal, without writing any delayed signal.
+// vnd_haas_scan.hpp - the Haas-delay optimiser's scan on the device (include/vnd_scan.h, include/vnd_haas_search.h):
+// the eight polar moments (vnd_moments.hpp's quantities and order) of HaasEffect(delay d_p).decorrelate(x[s_p]) for
+// P pairs (signal s_p, delay d_p) of a pool x[batch][n][Cx], without writing any delayed signal.  The single-signal
+// scan (vnd_haas_scan_f64_*) is the case "every pair is signal 0" (signals == nullptr).
 //
-// Frame k of candidate f (k in [0, n + d_f)) is haas_column / haas_frame of vnd_haas.hpp at (k, k - d_f), so it is
+// Frame k of pair p (k in [0, n + d_p)) is haas_column / haas_frame of vnd_haas.hpp at (k, k - d_p), so it is
 // bit-identical to the reference's float64 frame, and polar_add64 (vnd_polar.hpp) takes it in float64 as the
 // reference's polar_coordinates does.  The roll's zero prefix and the tail past the signal are ordinary frames.
 //
-// Shape: the hot loop is one float64 atan2 and one sqrt per (frame, candidate) - FP64 VALU, not memory.  A workgroup
-// owns a tile of kHsTile frames and a block of kHsBlock candidates.  The undelayed column of the tile is the same for
-// every candidate: each lane keeps its kHsPer frames of it in registers.  The delayed column is staged once in LDS
-// over the block's history window [t0 - dmax, t0 + kHsTile - dmin) (delays sorted ascending keep dmax - dmin small),
-// and the block's candidates sweep the tile from there.  A block whose window does not fit kHsWin reads the delayed
-// column through haas_column from global memory instead: the same values, so the same bits.
+// Shape: the hot loop is one float64 atan2 and one sqrt per (frame, pair) - FP64 VALU, not memory.  A workgroup
+// owns a tile of kHsTile frames and a block of kHsBlock consecutive pairs, which it walks as runs of one signal.
+// The undelayed column of the tile is the same for every pair of a run: each lane keeps its kHsPer frames of it in
+// registers.  The delayed column is staged once per run in LDS over the run's history window
+// [t0 - dmax, t0 + kHsTile - dmin) (pairs sorted by (signal, delay) keep runs long and dmax - dmin small), and the
+// run's pairs sweep the tile from there.  A run whose window does not fit kHsWin reads the delayed column through
+// haas_column from global memory instead: the same values, so the same bits.
 //
-// Sums are float64 in a fixed order: per lane over its frames, a fixed shuffle tree and wave order per (tile,
-// candidate) partial, then a fixed-order reduction of candidate f's ceil((n + d_f) / kHsTile) partials.  Neither the
-// other candidates of a launch nor the launch's extent enter candidate f's order, so results are bit-identical
-// across runs and across how the candidates are split into launches.
+// Sums are float64 in a fixed order: per lane over its frames, a fixed shuffle tree and wave order per (tile, pair)
+// partial, then a fixed-order reduction of pair p's ceil((n + d_p) / kHsTile) partials.  Neither the other pairs of a
+// launch, nor their order, nor the launch's extent enter pair p's order, so results are bit-identical across runs
+// and across how the pairs are ordered and split into launches.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -24,30 +26,35 @@
 #include "vnd_haas.hpp"
 #include "vnd_polar.hpp"
 #include "../../include/vnd_scan.h"
+#include "../../include/vnd_haas_search.h"
 
 namespace vnd {
 
 constexpr int kHsThreads = 256;
 constexpr int kHsPer = 8;                               // frames per lane and tile
 constexpr int kHsTile = kHsThreads * kHsPer;            // 2048 frames per workgroup
-constexpr int kHsBlock = 16;                            // candidates per workgroup
+constexpr int kHsBlock = 16;                            // pairs per workgroup
 constexpr int kHsWin = 4096;                            // staged delayed-column doubles (32 KB of LDS)
 
 struct HsArgs {
-    HArgs h;                                            // signal and the shared configuration (h.delay unused)
+    HArgs h;                                            // pool (h.x, h.n, h.Cx) and the shared configuration
+    const int32_t *__restrict__ signals;                // [F] signal of each pair; nullptr: every pair is signal 0
     const int32_t *__restrict__ delays;                 // [F]
     double *__restrict__ partials;                      // [F][cap][8]
     double *__restrict__ moments;                       // [F][8]
-    int32_t F;
-    int64_t cap;                                        // partials per candidate the workspace holds
+    int32_t F;                                          // pairs
+    int32_t batch;                                      // signals in the pool
+    int64_t cap;                                        // partials per pair the workspace holds
 };
 
 __device__ __forceinline__ int64_t hs_chunks(int64_t frames) { return (frames + kHsTile - 1) / kHsTile; }
 
-__device__ __forceinline__ bool hs_valid(const HsArgs &a, int32_t d)
+__device__ __forceinline__ bool hs_valid(const HsArgs &a, int32_t s, int32_t d)
 {
-    return d >= 0 && hs_chunks(a.h.n + d) <= a.cap;
+    return s >= 0 && s < a.batch && d >= 0 && hs_chunks(a.h.n + d) <= a.cap;
 }
+
+__device__ __forceinline__ int32_t hs_signal(const HsArgs &a, int f) { return a.signals ? a.signals[f] : 0; }
 
 // fixed-order sum (max for slot 4) of v over the workgroup; the result is valid in thread 0
 __device__ __forceinline__ void hs_block_reduce(double v[kMoments], double (*red)[kMoments])
@@ -81,67 +88,85 @@ __global__ __launch_bounds__(kHsThreads) void haas_scan_kernel(const HsArgs a)
 {
     __shared__ double hist[kHsWin];
     __shared__ double red[kHsThreads / 64][kMoments];
-    __shared__ int32_t dl[kHsBlock];
+    __shared__ int32_t dl[kHsBlock], sl[kHsBlock];      // delay (-1: outside the contract) and signal of each pair
+    __shared__ int32_t run[kHsBlock][3];                // at a run's first pair: its end, dmin and dmax
     const int f0 = blockIdx.y * kHsBlock;
     const int nb = min(kHsBlock, a.F - f0);
-    if ((int)threadIdx.x < nb) dl[threadIdx.x] = a.delays[f0 + threadIdx.x];
-    __syncthreads();
-    int32_t dmin = INT32_MAX, dmax = -1;                // over the block's valid candidates (wave-uniform)
-    for (int c = 0; c < nb; ++c) {
-        const int32_t d = dl[c];
-        if (hs_valid(a, d)) { dmin = min(dmin, d); dmax = max(dmax, d); }
+    if ((int)threadIdx.x < nb) {
+        const int32_t s = hs_signal(a, f0 + threadIdx.x), d = a.delays[f0 + threadIdx.x];
+        sl[threadIdx.x] = s;
+        dl[threadIdx.x] = hs_valid(a, s, d) ? d : -1;
     }
-    const int64_t t0 = (int64_t)blockIdx.x * kHsTile;
-    if (dmax < 0 || t0 >= a.h.n + dmax) return;         // no candidate of the block reaches this tile
+    __syncthreads();
+    if ((int)threadIdx.x < nb && (threadIdx.x == 0 || sl[threadIdx.x - 1] != sl[threadIdx.x])) {
+        int c = threadIdx.x;
+        int32_t dmin = INT32_MAX, dmax = -1;            // over the run's valid pairs
+        for (; c < nb && sl[c] == sl[threadIdx.x]; ++c) {
+            if (dl[c] >= 0) { dmin = min(dmin, dl[c]); dmax = max(dmax, dl[c]); }
+        }
+        run[threadIdx.x][0] = c; run[threadIdx.x][1] = dmin; run[threadIdx.x][2] = dmax;
+    }
+    __syncthreads();
     const HArgs &h = a.h;
     const int cu = 1 - h.delayed_channel, cd = h.delayed_channel;
-    // the delayed column over [t0 - dmax, t0 + kHsTile - dmin)
-    const int64_t span = (int64_t)kHsTile + dmax - dmin;
-    const bool staged = span <= kHsWin;
-    if (staged) {
-        const int64_t k0 = t0 - dmax;
-        for (int i = threadIdx.x; i < span; i += kHsThreads) hist[i] = haas_column(h, h.x, cd, k0 + i);
-        __syncthreads();
-    }
-    double und[kHsPer];                                 // the undelayed column at this lane's frames
-#pragma unroll
-    for (int j = 0; j < kHsPer; ++j) und[j] = haas_column(h, h.x, cu, t0 + threadIdx.x + j * kHsThreads);
-
-    for (int c = 0; c < nb; ++c) {
-        const int32_t d = dl[c];
-        if (!hs_valid(a, d)) continue;
-        const int64_t len = h.n + d;
-        if (t0 >= len) continue;                        // (uniform) candidate f has no frame here
-        PolarAcc64 acc;
-#pragma unroll
-        for (int j = 0; j < kHsPer; ++j) {
-            const int64_t k = t0 + threadIdx.x + j * kHsThreads;
-            if (k < len) {
-                const double del = staged ? hist[(k - t0) + (dmax - d)] : haas_column(h, h.x, cd, k - d);
-                double v[2];
-                haas_frame(h, cu == 0 ? und[j] : del, cu == 0 ? del : und[j], v);
-                polar_add64(acc, v[0], v[1]);
-            }
+    const int64_t t0 = (int64_t)blockIdx.x * kHsTile;
+    // runs of consecutive pairs of one signal (wave-uniform: every bound comes from LDS)
+    for (int r0 = 0, r1; r0 < nb; r0 = r1) {
+        r1 = run[r0][0];
+        const int32_t s = __builtin_amdgcn_readfirstlane(sl[r0]);
+        const int32_t dmin = run[r0][1], dmax = run[r0][2];
+        if (dmax < 0 || t0 >= h.n + dmax) continue;     // no pair of the run reaches this tile
+        const float *__restrict__ xs = h.x + (int64_t)s * h.n * h.Cx;
+        // the delayed column over [t0 - dmax, t0 + kHsTile - dmin)
+        const int64_t span = (int64_t)kHsTile + dmax - dmin;
+        const bool staged = span <= kHsWin;
+        if (staged) {
+            __syncthreads();                            // the previous run's readers are done with hist
+            const int64_t k0 = t0 - dmax;
+            for (int i = threadIdx.x; i < span; i += kHsThreads) hist[i] = haas_column(h, xs, cd, k0 + i);
+            __syncthreads();
         }
-        double v[kMoments];
-        polar_values64(v, acc);
-        hs_block_reduce(v, red);
-        if (threadIdx.x == 0) {
-            double *p = a.partials + ((int64_t)(f0 + c) * a.cap + blockIdx.x) * kMoments;
+        double und[kHsPer];                             // the undelayed column at this lane's frames
 #pragma unroll
-            for (int k = 0; k < kMoments; ++k) p[k] = v[k];
+        for (int j = 0; j < kHsPer; ++j) und[j] = haas_column(h, xs, cu, t0 + threadIdx.x + j * kHsThreads);
+
+        for (int c = r0; c < r1; ++c) {
+            const int32_t d = __builtin_amdgcn_readfirstlane(dl[c]);
+            if (d < 0) continue;
+            const int64_t len = h.n + d;
+            if (t0 >= len) continue;                    // (uniform) pair c has no frame here
+            PolarAcc64 acc;
+#pragma unroll
+            for (int j = 0; j < kHsPer; ++j) {
+                const int64_t k = t0 + threadIdx.x + j * kHsThreads;
+                if (k < len) {
+                    const double del = staged ? hist[(k - t0) + (dmax - d)] : haas_column(h, xs, cd, k - d);
+                    double v[2];
+                    haas_frame(h, cu == 0 ? und[j] : del, cu == 0 ? del : und[j], v);
+                    polar_add64(acc, v[0], v[1]);
+                }
+            }
+            double v[kMoments];
+            polar_values64(v, acc);
+            hs_block_reduce(v, red);
+            if (threadIdx.x == 0) {
+                double *p = a.partials + ((int64_t)(f0 + c) * a.cap + blockIdx.x) * kMoments;
+#pragma unroll
+                for (int k = 0; k < kMoments; ++k) p[k] = v[k];
+            }
         }
     }
 }
 
-// One workgroup per candidate: lanes stride over its ceil((n + d) / kHsTile) partials, then the fixed tree.
-// A candidate outside the contract (negative delay, or more partials than the workspace holds) gets NaN moments.
+// One workgroup per pair: lanes stride over its ceil((n + d) / kHsTile) partials, then the fixed tree.  A pair
+// outside the contract (signal outside [0, batch), negative delay, or more partials than the workspace holds) gets
+// NaN moments.
 __global__ __launch_bounds__(kHsThreads) void haas_scan_reduce_kernel(const HsArgs a)
 {
     __shared__ double red[kHsThreads / 64][kMoments];
     const int f = blockIdx.x;
     const int32_t d = a.delays[f];
-    const bool ok = hs_valid(a, d);
+    const bool ok = hs_valid(a, hs_signal(a, f), d);
     const int64_t chunks = ok ? hs_chunks(a.h.n + d) : 0;
     double v[kMoments];
 #pragma unroll
@@ -161,6 +186,7 @@ __global__ __launch_bounds__(kHsThreads) void haas_scan_reduce_kernel(const HsAr
 }  // namespace vnd
 
 static_assert(VND_HAAS_SCAN_MAX_DELAYS == 65535 * vnd::kHsBlock, "the grid's y extent bounds the delays per call");
+static_assert(VND_HAAS_PAIRS_MAX == 65535 * vnd::kHsBlock, "the grid's y extent bounds the pairs per call");
 
 extern "C" {
 
@@ -188,6 +214,34 @@ vnd_status vnd_haas_scan_workspace_bytes(int64_t n_frames, int32_t n_delays, int
     return VND_OK;
 }
 
+// Both _dev entries: validated scalars in, the two kernels enqueued on the caller's stream.
+static vnd_status haas_pairs_launch(vnd_ctx *ctx, const float *x, int32_t batch, int64_t n_frames, int32_t in_channels,
+                                    const int32_t *signals, const int32_t *delays, int32_t n_pairs,
+                                    int32_t delayed_channel, int32_t ms_mode, int32_t use_width, double width,
+                                    double *moments, void *workspace, int64_t workspace_bytes, void *stream_)
+{
+    if (workspace_bytes < 0) return fail(VND_ERR_INVALID, "negative workspace size");
+    if (n_pairs == 0) return VND_OK;
+    if (!delays || !moments || (n_frames > 0 && batch > 0 && !x))
+        return fail(VND_ERR_INVALID, "null signal, delay or moments pointer");
+    const int64_t per = (int64_t)n_pairs * kMoments * (int64_t)sizeof(double);
+    const int64_t cap = std::min<int64_t>(workspace_bytes / per, 1 << 23);
+    if (cap > 0 && !workspace) return fail(VND_ERR_INVALID, "null workspace");
+    DeviceScope on(ctx->device);
+    hipStream_t stream = (hipStream_t)stream_;
+    HsArgs a{};
+    a.h.x = x; a.h.n = n_frames; a.h.Cx = in_channels; a.h.delayed_channel = delayed_channel;
+    a.h.ms = ms_mode ? 1 : 0; a.h.use_width = use_width ? 1 : 0; a.h.w_mid = 1.0 - width; a.h.w_side = width;
+    a.signals = signals; a.delays = delays; a.partials = (double *)workspace; a.moments = moments; a.F = n_pairs;
+    a.batch = batch; a.cap = cap;
+    if (cap > 0)
+        hipLaunchKernelGGL(haas_scan_kernel, dim3((unsigned)cap, (unsigned)((n_pairs + kHsBlock - 1) / kHsBlock)),
+                           dim3(kHsThreads), 0, stream, a);
+    hipLaunchKernelGGL(haas_scan_reduce_kernel, dim3((unsigned)n_pairs), dim3(kHsThreads), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return VND_OK;
+}
+
 vnd_status vnd_haas_scan_f64_dev(vnd_ctx *ctx, const float *x, int64_t n_frames, int32_t in_channels,
                                  const int32_t *delays, int32_t n_delays, int32_t delayed_channel, int32_t ms_mode,
                                  int32_t use_width, double width, double *moments, void *workspace,
@@ -196,24 +250,8 @@ vnd_status vnd_haas_scan_f64_dev(vnd_ctx *ctx, const float *x, int64_t n_frames,
     if (!ctx) return fail(VND_ERR_INVALID, "null context");
     vnd_status st = haas_scan_check(n_frames, n_delays, in_channels, delayed_channel);
     if (st != VND_OK) return st;
-    if (workspace_bytes < 0) return fail(VND_ERR_INVALID, "negative workspace size");
-    if (n_delays == 0) return VND_OK;
-    if (!delays || !moments || (n_frames > 0 && !x)) return fail(VND_ERR_INVALID, "null signal, delay or moments pointer");
-    const int64_t per = (int64_t)n_delays * kMoments * (int64_t)sizeof(double);
-    const int64_t cap = std::min<int64_t>(workspace_bytes / per, 1 << 23);
-    if (cap > 0 && !workspace) return fail(VND_ERR_INVALID, "null workspace");
-    DeviceScope on(ctx->device);
-    hipStream_t stream = (hipStream_t)stream_;
-    HsArgs a{};
-    a.h.x = x; a.h.n = n_frames; a.h.Cx = in_channels; a.h.delayed_channel = delayed_channel;
-    a.h.ms = ms_mode ? 1 : 0; a.h.use_width = use_width ? 1 : 0; a.h.w_mid = 1.0 - width; a.h.w_side = width;
-    a.delays = delays; a.partials = (double *)workspace; a.moments = moments; a.F = n_delays; a.cap = cap;
-    if (cap > 0)
-        hipLaunchKernelGGL(haas_scan_kernel, dim3((unsigned)cap, (unsigned)((n_delays + kHsBlock - 1) / kHsBlock)),
-                           dim3(kHsThreads), 0, stream, a);
-    hipLaunchKernelGGL(haas_scan_reduce_kernel, dim3((unsigned)n_delays), dim3(kHsThreads), 0, stream, a);
-    HIP_TRY(hipGetLastError());
-    return VND_OK;
+    return haas_pairs_launch(ctx, x, 1, n_frames, in_channels, nullptr, delays, n_delays, delayed_channel, ms_mode,
+                             use_width, width, moments, workspace, workspace_bytes, stream_);
 }
 
 vnd_status vnd_haas_scan_f64_host(vnd_ctx *ctx, const float *x, int64_t n_frames, int32_t in_channels,
@@ -250,6 +288,86 @@ vnd_status vnd_haas_scan_f64_host(vnd_ctx *ctx, const float *x, int64_t n_frames
     HIP_TRY(hipMemcpyAsync(d_dev, delays, d_bytes, hipMemcpyHostToDevice, ctx->stream));
     st = vnd_haas_scan_f64_dev(ctx, x_dev, n_frames, in_channels, d_dev, n_delays, delayed_channel, ms_mode, use_width,
                                width, m_dev, work, ws, ctx->stream);
+    if (st != VND_OK) return st;
+    HIP_TRY(hipMemcpyAsync(moments, m_dev, m_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return VND_OK;
+}
+
+// ---- include/vnd_haas_search.h: (signal, delay) pairs of a pool ----------------------------------------------------
+static vnd_status haas_pairs_check(int32_t batch, int64_t n_frames, int32_t n_pairs, int32_t in_channels,
+                                   int32_t delayed_channel)
+{
+    if (batch < 0 || n_frames < 0 || n_pairs < 0) return fail(VND_ERR_INVALID, "negative batch, frame or pair count");
+    if (in_channels != 1 && in_channels != 2)
+        return fail(VND_ERR_INVALID, "a Haas scan takes mono or stereo signals, got %d channels", in_channels);
+    if (delayed_channel != 0 && delayed_channel != 1)
+        return fail(VND_ERR_INVALID, "delayed_channel must be 0 or 1, got %d", delayed_channel);
+    if (n_pairs > VND_HAAS_PAIRS_MAX)
+        return fail(VND_ERR_UNSUPPORTED, "more than %d pairs per call: split them", VND_HAAS_PAIRS_MAX);
+    if (n_frames > 0 && (int64_t)batch > INT64_MAX / 2 / n_frames)
+        return fail(VND_ERR_UNSUPPORTED, "pool of %d x %lld frames too large", batch, (long long)n_frames);
+    return VND_OK;
+}
+
+vnd_status vnd_haas_pairs_workspace_bytes(int64_t n_frames, int32_t n_pairs, int32_t max_delay, int64_t *bytes)
+{
+    return vnd_haas_scan_workspace_bytes(n_frames, n_pairs, max_delay, bytes);
+}
+
+vnd_status vnd_haas_pairs_f64_dev(vnd_ctx *ctx, const float *x, int32_t batch, int64_t n_frames, int32_t in_channels,
+                                  const int32_t *signals, const int32_t *delays, int32_t n_pairs,
+                                  int32_t delayed_channel, int32_t ms_mode, int32_t use_width, double width,
+                                  double *moments, void *workspace, int64_t workspace_bytes, void *stream_)
+{
+    if (!ctx) return fail(VND_ERR_INVALID, "null context");
+    vnd_status st = haas_pairs_check(batch, n_frames, n_pairs, in_channels, delayed_channel);
+    if (st != VND_OK) return st;
+    if (n_pairs > 0 && !signals) return fail(VND_ERR_INVALID, "null signal index pointer");
+    return haas_pairs_launch(ctx, x, batch, n_frames, in_channels, signals, delays, n_pairs, delayed_channel, ms_mode,
+                             use_width, width, moments, workspace, workspace_bytes, stream_);
+}
+
+vnd_status vnd_haas_pairs_f64_host(vnd_ctx *ctx, const float *x, int32_t batch, int64_t n_frames, int32_t in_channels,
+                                   const int32_t *signals, const int32_t *delays, int32_t n_pairs,
+                                   int32_t delayed_channel, int32_t ms_mode, int32_t use_width, double width,
+                                   double *moments)
+{
+    if (!ctx) return fail(VND_ERR_INVALID, "null context");
+    vnd_status st = haas_pairs_check(batch, n_frames, n_pairs, in_channels, delayed_channel);
+    if (st != VND_OK) return st;
+    if (n_pairs == 0) return VND_OK;
+    if (!signals || !delays || !moments || (n_frames > 0 && batch > 0 && !x))
+        return fail(VND_ERR_INVALID, "null signal, signal index, delay or moments pointer");
+    int32_t dmax = 0;
+    for (int32_t p = 0; p < n_pairs; ++p) {
+        if (signals[p] < 0 || signals[p] >= batch)
+            return fail(VND_ERR_INVALID, "signal %d of pair %d is outside [0, %d)", signals[p], p, batch);
+        if (delays[p] < 0) return fail(VND_ERR_INVALID, "delay %d of pair %d is negative", delays[p], p);
+        dmax = std::max(dmax, delays[p]);
+    }
+    int64_t ws = 0;
+    st = vnd_haas_pairs_workspace_bytes(n_frames, n_pairs, dmax, &ws);
+    if (st != VND_OK) return st;
+    HostLock lock(ctx->host_mutex);
+    DeviceScope on(ctx->device);
+    if (!on.ok) return fail(VND_ERR_HIP, "cannot select device %d", ctx->device);
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t x_bytes = (size_t)batch * n_frames * in_channels * sizeof(float);
+    const size_t i_bytes = (size_t)n_pairs * sizeof(int32_t);
+    const size_t m_bytes = (size_t)n_pairs * kMoments * sizeof(double);
+    st = ensure_work(ctx, (size_t)ws + up(m_bytes) + 2 * up(i_bytes) + up(x_bytes));
+    if (st != VND_OK) return st;
+    char *work = ctx->work;
+    double *m_dev = (double *)(work + ws);
+    int32_t *s_dev = (int32_t *)(work + ws + up(m_bytes));
+    int32_t *d_dev = (int32_t *)(work + ws + up(m_bytes) + up(i_bytes));
+    float *x_dev = (float *)(work + ws + up(m_bytes) + 2 * up(i_bytes));
+    if (x_bytes) HIP_TRY(hipMemcpyAsync(x_dev, x, x_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(s_dev, signals, i_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_dev, delays, i_bytes, hipMemcpyHostToDevice, ctx->stream));
+    st = vnd_haas_pairs_f64_dev(ctx, x_dev, batch, n_frames, in_channels, s_dev, d_dev, n_pairs, delayed_channel,
+                                ms_mode, use_width, width, m_dev, work, ws, ctx->stream);
     if (st != VND_OK) return st;
     HIP_TRY(hipMemcpyAsync(moments, m_dev, m_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));

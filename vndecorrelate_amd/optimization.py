@@ -24,10 +24,13 @@ bit-identical to the reference's given the bit-identical exact-mode convolution;
 scanned velvet-noise scores agree to ~1e-7 relative (float64 sums where NumPy adds
 float32), scanned Haas scores to ~1e-12 (both float64; sum order and atan2 ulps differ).
 ``optimize_haas_delay``'s refinement memoises its host objective by the integer delay,
-on which alone it depends.
+on which alone it depends.  ``optimize_haas_delay_batched`` runs the whole search, refinement
+included, for a pool of signals on the device: one launch over (signal, delay) pairs for the
+grid and one per round of a lockstep bounded minimiser (``bounded.py``) for the refinements.
 """
 from __future__ import annotations
 
+from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -35,6 +38,7 @@ from numpy.typing import NDArray
 
 from . import _native
 from . import decorrelation as _dec
+from .bounded import minimize_bounded_lockstep, round_half_even
 from .decorrelation import Decorrelator, HaasEffect, VelvetNoise
 from .taps import class_path_bank_arrays
 from .utils.dsp import EPSILON, LayoutMode, polar_coordinates, to_float32
@@ -44,6 +48,8 @@ _SCAN_BYTES = 2 << 30
 # the Haas scan's workspace is ceil((n + max d) / 2048) * F * 64 bytes: keep it under this many bytes per launch
 _HAAS_SCAN_BYTES = 1 << 30
 _HAAS_SCAN_MAX_DELAYS = 1048560                      # VND_HAAS_SCAN_MAX_DELAYS: delays per launch
+# optimize_haas_delay_batched keeps at most this many bytes of its float32 pool on the device (else chunks of signals)
+_HAAS_POOL_BYTES = 4 << 30
 _INT32_MAX = 2 ** 31 - 1
 
 _haas_scan_device: Optional[bool] = None
@@ -367,6 +373,237 @@ def optimize_haas_delay(*, input_signal: NDArray, sample_rate_hz: int, max_delay
     memo = DelayMemo(lambda tau: symmetry_aware_objective(input_signal, make(tau), **weights), sample_rate_hz)
     last_haas_memo = memo
     return _search(input_signal, np.linspace(0.0, max_delay_seconds, grid_size), make, grid_size, weights, memo)
+
+
+# ---- the batched Haas-delay optimiser -------------------------------------------------------------------------------
+@dataclass
+class HaasSearchStats:
+    """The work of one :func:`optimize_haas_delay_batched` call (tools, tests).  ``rounds`` counts the lockstep
+    refinement's rounds, the first points of every minimum included; ``pairs_per_round`` the distinct (signal, delay)
+    pairs each round scored in one launch; ``grid_pairs`` those of the grid; ``evaluations[b]`` the objective
+    evaluations of signal b's refinements (SciPy's ``nfev`` summed over its local minima); ``minimum_signal`` and
+    ``minimum_nfev`` the signal and ``nfev`` of each refined minimum in order (device route); ``pool_uploads`` how many
+    chunks of the pool went to the device (0 for a device tensor and on the host route)."""
+    route: str
+    signals: int
+    rounds: int = 0
+    pairs_per_round: List[int] = field(default_factory=list)
+    grid_pairs: int = 0
+    evaluations: NDArray = field(default_factory=lambda: np.zeros(0, np.int64))
+    minimum_signal: NDArray = field(default_factory=lambda: np.zeros(0, np.int64))
+    minimum_nfev: NDArray = field(default_factory=lambda: np.zeros(0, np.int64))
+    pool_uploads: int = 0
+
+
+last_haas_search: Optional[HaasSearchStats] = None   # the last optimize_haas_delay_batched call's work
+
+
+def haas_delays(taus, sample_rate_hz) -> NDArray[np.int64]:
+    """``round(tau * sample_rate_hz)`` of each tau, as ``HaasEffect.haas_delay`` rounds it (ties to even)."""
+    return round_half_even(np.asarray(taus, np.float64) * sample_rate_hz)
+
+
+def haas_search(score_pairs: Callable[[NDArray, NDArray], NDArray], num_signals: int, taus: NDArray,
+                sample_rate_hz, grid_size: int, stats: Optional[HaasSearchStats] = None) -> NDArray[np.float64]:
+    """``optimize_haas_delay``'s search for ``num_signals`` signals at once, given a scorer.
+
+    ``score_pairs(signals, delays)`` returns the objective of ``HaasEffect(delay).decorrelate(signal)`` for distinct
+    (signal, integer delay) pairs sorted by (signal, delay).  The grid is one call over every signal and distinct grid
+    delay; each refinement round is one call over the distinct pairs its lanes ask for.  Per signal: the grid's local
+    minima (:func:`get_local_minima`), each refined over its neighbours by :func:`minimize_bounded_lockstep` (SciPy's
+    bounded method, ``xatol=1e-4``) on ``f(tau) = score of round(tau * fs)``, and :func:`optimize_local_minima`'s
+    choice among them."""
+    taus = np.asarray(taus, np.float64)
+    stats = HaasSearchStats(route='custom', signals=num_signals) if stats is None else stats
+
+    def delays_of(values):
+        delays = haas_delays(values, sample_rate_hz)
+        if delays.size and (delays.min() < 0 or delays.max() > _INT32_MAX):
+            raise ValueError(f'Haas delays must lie in [0, 2^31): got {int(delays.min())}..{int(delays.max())}')
+        return delays
+
+    def score(signals, delays):
+        return np.asarray(score_pairs(signals, delays), np.float64)
+
+    unique, inverse = np.unique(delays_of(taus), return_inverse=True)
+    grid = score(np.repeat(np.arange(num_signals, dtype=np.int64), unique.size), np.tile(unique, num_signals))
+    scores = grid.reshape(num_signals, unique.size)[:, inverse.reshape(-1)]
+    stats.grid_pairs += num_signals * unique.size
+    lane_signal, lower, upper = [], [], []
+    for b in range(num_signals):
+        for i in get_local_minima(scores[b], grid_size):
+            lane_signal.append(b)
+            lower.append(taus[max(0, i - 1)])
+            upper.append(taus[min(grid_size - 1, i + 1)])
+    lane_signal = np.asarray(lane_signal, np.int64)
+
+    def objective(lanes, x):
+        key = (lane_signal[lanes] << 32) | delays_of(x)
+        pairs, back = np.unique(key, return_inverse=True)
+        stats.pairs_per_round.append(int(pairs.size))
+        return score(pairs >> 32, pairs & 0xFFFFFFFF)[back.reshape(-1)]
+
+    result = minimize_bounded_lockstep(objective, lower, upper, xatol=1e-4)
+    stats.rounds += result.rounds
+    best_tau, best_score = np.zeros(num_signals), np.full(num_signals, np.inf)
+    evaluations = np.zeros(num_signals, np.int64)
+    for lane, b in enumerate(lane_signal):               # minima in order, strict <, from (0.0, inf)
+        evaluations[b] += result.nfev[lane]
+        if result.fun[lane] < best_score[b]:
+            best_score[b], best_tau[b] = result.fun[lane], result.x[lane]
+    stats.minimum_signal = np.concatenate([stats.minimum_signal, lane_signal + stats.evaluations.size])
+    stats.minimum_nfev = np.concatenate([stats.minimum_nfev, result.nfev])
+    stats.evaluations = np.concatenate([stats.evaluations, evaluations])
+    return best_tau
+
+
+def host_pair_scorer(pool, sample_rate_hz, weights: dict) -> Callable[[NDArray, NDArray], NDArray]:
+    """A :func:`haas_search` scorer on the host: ``symmetry_aware_objective`` of an LR ``HaasEffect`` per pair."""
+    def score(signals, delays):
+        return np.array([symmetry_aware_objective(pool[s], HaasEffect(sample_rate_hz=1, delay_time_seconds=float(d),
+                                                                      mode='LR'), **weights)
+                         for s, d in zip(signals.tolist(), delays.tolist())], np.float64)
+    return score
+
+
+class _DevicePairScorer:
+    """A :func:`haas_search` scorer over a float32 ``(B, n, C)`` pool resident on the device: one
+    ``vnd_haas_pairs_f64_dev`` launch per call (more only past the workspace budget); pairs go up, moments come
+    down, and ``scores_from_moments`` turns them into scores."""
+
+    def __init__(self, ctx, pool, weights: dict):
+        self.ctx, self.pool, self.weights = ctx, pool, weights
+        import torch
+        self.torch = torch
+        self.batch, self.n, self.channels = (int(v) for v in pool.shape)
+        self.workspace = None
+
+    def _launch(self, signals, delays):
+        torch = self.torch
+        dev = self.pool.device
+        count = int(delays.size)
+        ws = _native.haas_pairs_workspace_bytes(self.n, count, int(delays.max()))
+        if self.workspace is None or self.workspace.numel() < ws:
+            self.workspace = torch.empty(max(ws, 1), dtype=torch.uint8, device=dev)
+        pairs = torch.from_numpy(np.stack([signals, delays]).astype(np.int32)).to(dev)
+        moments = torch.empty((count, _native.MOMENTS), dtype=torch.float64, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        _native.haas_pairs_device(self.ctx, self.pool.data_ptr(), self.batch, self.n, self.channels,
+                                  pairs[0].data_ptr(), pairs[1].data_ptr(), count, moments.data_ptr(),
+                                  delayed_channel=0, ms_mode=False, width=None,
+                                  workspace_ptr=self.workspace.data_ptr(), workspace_bytes=ws,
+                                  stream=stream.cuda_stream)
+        return moments.cpu().numpy()
+
+    def __call__(self, signals, delays):
+        rows: List[NDArray] = []
+        first = 0
+        chunks = (self.n + delays + 2047) // 2048           # the workspace's partials per pair (vnd_haas_scan.hpp)
+        while first < delays.size:                          # launches bounded by their workspace
+            need = np.maximum.accumulate(chunks[first:]) * np.arange(1, delays.size - first + 1) * 64
+            last = first + min(max(1, int(np.count_nonzero(need <= _HAAS_SCAN_BYTES))), _native.HAAS_PAIRS_MAX)
+            rows.append(self._launch(signals[first:last], delays[first:last]))
+            first = last
+        moments = np.concatenate(rows) if rows else np.zeros((0, _native.MOMENTS))
+        return scores_from_moments(moments, **self.weights)
+
+
+def _haas_pool(input_signals):
+    """``(pool, is_torch)``: the pool as ``(B, n, C)`` with C = 1 (mono) or 2, after the shape checks."""
+    from .analysis import _is_torch
+    is_torch = _is_torch(input_signals)
+    x = input_signals if is_torch else np.asarray(input_signals)
+    shape = tuple(x.shape)
+    if not (len(shape) == 2 or (len(shape) == 3 and shape[2] == 2)):
+        raise ValueError(f'expected a stereo pool (B, n, 2) or a mono pool (B, n), got shape {shape}')
+    if shape[0] > 0 and shape[1] == 0:
+        raise ValueError(f'the signals of a pool need n > 0 frames, got shape {shape}')
+    if is_torch:
+        import torch
+        if x.is_complex() or x.dtype == torch.bool:
+            raise TypeError(f'signals must be real numbers, got {x.dtype}')
+    elif x.dtype.kind not in 'biuf':
+        raise TypeError(f'signals must be real numbers, got {x.dtype}')
+    return x, is_torch
+
+
+def _haas_batched_route() -> bool:
+    if _haas_scan_device is False:
+        return False
+    from .analysis import _gpu_present
+    if _haas_scan_device is True:
+        if not _gpu_present():
+            raise RuntimeError('set_haas_scan_device(True): no gfx950 device (or no built extension) to run on')
+        return True
+    return _gpu_present()
+
+
+def optimize_haas_delay_batched(*, input_signals, sample_rate_hz: int, max_delay_seconds, grid_size: int = 400,
+                                angle_limit: float = np.pi / 4, lambda_mean: float = 5.0, lambda_skew: float = 2.0,
+                                lambda_correlation: float = 15.0, lambda_penalty: float = 1e3) -> NDArray[np.float64]:
+    """:func:`optimize_haas_delay` for every signal of a pool: ``(B,)`` float64 delays in seconds.
+
+    ``input_signals`` is a stereo pool ``(B, n, 2)`` or a mono pool ``(B, n)`` with n > 0: a NumPy array of any real
+    dtype (cast as ``to_float32`` casts it) or a CUDA torch tensor, read in place.  B = 0 gives an empty array.
+
+    Device route (:func:`set_haas_scan_device`: ``None`` with a gfx950 device, or ``True``): the pool goes up once
+    (in chunks of whole signals past ``_HAAS_POOL_BYTES``) and stays there.  The grid is one launch over every
+    (signal, distinct grid delay) pair; the local minima of every signal are then refined together by
+    :func:`minimize_bounded_lockstep`, one launch per round over the distinct (signal, delay) pairs the round needs.
+    Only pairs go up and moments come down (:func:`haas_search`, ``vnd_haas_pairs_f64_dev``).
+    Parity: the grid scores equal ``grid_scan(x_b, candidates)`` on the device route bit for bit, so the local minima
+    are the same; the refinement takes the same iterates, ``nfev`` and tau as ``optimize_local_minima`` through SciPy
+    with ``f(tau)`` = the device score of ``round(tau * fs)`` for that signal.  Against the host-refined
+    :func:`optimize_haas_delay`, tau is equal unless two distinct delays' scores lie within the device / host score
+    difference (<= 7.4e-16 relative on the fixtures): the refinement then may pick the other delay.
+    Host route (``False``, or ``None`` without a device): :func:`optimize_haas_delay` signal by signal.
+    ``last_haas_search`` records the call's work (:class:`HaasSearchStats`)."""
+    global last_haas_search
+    weights = dict(angle_limit=angle_limit, lambda_mean=lambda_mean, lambda_skew=lambda_skew,
+                   lambda_correlation=lambda_correlation, lambda_penalty=lambda_penalty)
+    x, is_torch = _haas_pool(input_signals)
+    batch = int(x.shape[0])
+    if batch == 0:
+        last_haas_search = HaasSearchStats(route='none', signals=0)
+        return np.zeros(0, np.float64)
+    if not _haas_batched_route():
+        if is_torch:
+            x = x.detach().cpu().numpy()
+        stats = HaasSearchStats(route='host', signals=batch)
+        last_haas_search = stats
+        out = np.empty(batch, np.float64)
+        evaluations = np.empty(batch, np.int64)
+        for b in range(batch):
+            out[b] = optimize_haas_delay(input_signal=x[b], sample_rate_hz=sample_rate_hz,
+                                         max_delay_seconds=max_delay_seconds, grid_size=grid_size, **weights)
+            evaluations[b] = last_haas_memo.calls
+        stats.evaluations = evaluations
+        return out
+    taus = np.linspace(0.0, max_delay_seconds, grid_size)
+    stats = HaasSearchStats(route='device', signals=batch)
+    last_haas_search = stats
+    print('Starting Grid Scan')
+    print('Starting Local Minima optimization')
+    import torch
+    if is_torch:
+        if not x.is_cuda:
+            raise ValueError('a torch pool must be a device tensor (NumPy arrays are uploaded)')
+        ctx = _native.context_for(x.device.index if x.device.index is not None else torch.cuda.current_device())
+        pool = x.reshape(batch, x.shape[1], -1)
+        pool = (pool if pool.dtype == torch.float32 else pool.to(torch.float32)).contiguous()
+        return haas_search(_DevicePairScorer(ctx, pool, weights), batch, taus, sample_rate_hz, grid_size, stats)
+    ctx = _native.default_context()
+    dev = torch.device('cuda', ctx.device)
+    x = x.reshape(batch, x.shape[1], -1)
+    per_chunk = max(1, _HAAS_POOL_BYTES // (x.shape[1] * x.shape[2] * 4))
+    out = []
+    for first in range(0, batch, per_chunk):
+        part = np.ascontiguousarray(to_float32(x[first:first + per_chunk]))
+        pool = torch.from_numpy(part).to(dev)
+        stats.pool_uploads += 1
+        out.append(haas_search(_DevicePairScorer(ctx, pool, weights), part.shape[0], taus, sample_rate_hz, grid_size,
+                               stats))
+    return np.concatenate(out)
 
 
 def optimize_velvet_noise(*, input_signal: NDArray, sample_rate_hz: int, duration_seconds: float,
