@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Msamples/s of velvet-noise decorrelation on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Headline workload (BASELINE.json configs[1], "cfg2"): synthetic 48 kHz stereo float32, 10 s per
 signal, 30 taps over 30 ms (seed 1, the reference generator's defaults).  One cfg2 signal is only
@@ -16,10 +16,20 @@ independent streams: each rank owns its own pool, the only communication is one 
 the serialized tap table before the timed region, and no collective sits on the data path
 ("scaling": "weak").
 
-The JSON line also carries
-  roofline      algorithmic HBM bytes (8 B per output sample) / kernel time measured with HIP
-                events on the launch stream, vs 8 TB/s; `traffic` = HBM bytes per launch from the
-                committed PMC passes of the same launch geometry (`traffic_source` says which file);
+A plain run does what the headline needs and nothing more: it sets up the table and the pool, warms up,
+times the K steps, writes `--dump-outputs` if asked, and prints the line.  Its `roofline` comes from the
+HIP events of the timed steps themselves: algorithmic HBM bytes (8 B per output sample) / kernel time on
+the launch stream, vs 8 TB/s, with `traffic` = HBM bytes per launch from the committed PMC passes of the
+same launch geometry (`traffic_source` says which file).
+
+`--full` adds everything else the benchmark measures and checks, all after the timed steps (the `--no-*`
+options drop single parts of it):
+  parity        three streams of the timed output (first, middle, last) against the C oracle;
+  roofline      beside the kernel, the same pool through a plain device copy and the library's streaming
+                copy, and the board's power and shader clock sampled from hwmon during the timed steps
+                and under each kernel;
+  exact_mode    the bit-exact mode on the same pool, function-path and class-path tables;
+  single_launch one cfg2 signal per launch: latency and back-to-back kernel time;
   cpu_baseline  the NumPy restatement of the reference's convolve_velvet_noise
                 (oracle/vnd_oracle.py, single thread - NumPy slicing does not multithread) timed on
                 this host on a bounded number of cfg2 signals; rank 0, N=1 only;
@@ -32,10 +42,13 @@ The JSON line also carries
                 at N = 1 `projection` times what ONE rank does at N = 1/2/4/8 (1024/512/256/128 streams
                 per pass, rotating buffers) beside a plain device copy of the same shard;
   end_to_end    the synchronous host API (H2D + kernel + D2H) on pageable and pinned NumPy buffers,
-                N=1 only - PCIe-inclusive, never part of `value`.
+                N=1 only - PCIe-inclusive, never part of `value`;
+  audio         the headline pool's shape filled with the reference's viola recording, N=1 only;
+  next_rows     SURVEY 8(f) rows on one GPU (the decorrelate stage, mono to stereo, the grid scan, a
+                resident chain), N=1 only.
 
-What is printed where.  stdout carries ONE short JSON line (a few KB): the contract's keys, `roofline`,
-`cpu_baseline`, and in `config` one short numeric key per claim of README's table (`exact_frac`, `cfg3_frac`,
+What is printed where.  stdout carries ONE short JSON line (a few KB): the contract's keys, `roofline`, and
+with --full `cpu_baseline` and in `config` one short numeric key per claim of README's table (`exact_frac`, `cfg3_frac`,
 `cfg5_frac`, `proj_speedup`, ... - `COMPACT_KEYS` below says what each one is).  Everything else - launch
 descriptions, notes, per-leg records - goes to `bench_detail.json` beside this file (and to `gpurun_out/` when
 that directory exists) and, as one JSON document, to stderr BEFORE the line.
@@ -84,6 +97,10 @@ def parse():
                          'ramps its clocks over the first ~40 ms of load (tools/sustain.py)')
     ap.add_argument('--pool', type=int, default=2048, help='distinct cfg2 signals per rank and step')
     ap.add_argument('--mode', choices=['exact', 'fma', 'fast'], default=os.environ.get('VND_BENCH_MODE', 'fast'))
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also run every other leg: oracle parity, exact mode, copy ceilings, board power, '
+                         'single-signal latency, cfg4 strong scaling, the secondary configs, end_to_end, audio, the next rows '
+                         'and the CPU baseline (the --no-* options below skip parts of it)')
     ap.add_argument('--cpu-seconds', type=float, default=10.0, help='budget of the CPU baseline leg')
     ap.add_argument('--no-cpu', action='store_true')
     ap.add_argument('--no-exact', action='store_true', help='skip the extra exact-mode timing')
@@ -831,7 +848,7 @@ def dig(record, *path, default=None):
 
 # what the short keys of `config` are (the detail document carries the full records they come from)
 COMPACT_KEYS = {
-    'parity': 'headline: worst of the checked streams of the timed output vs the C oracle, fraction of the output peak',
+    'parity': 'headline: worst of the checked streams of the timed output vs the C oracle, fraction of the output peak (--full; null without)',
     'cfg4_strong': 'this run\'s ranks on the 1024 x 1 s batch: max-over-ranks ms per pass, whole-job Msamples/s - the strong-scaling figure',
     'proj_N1_us / proj_N8_us / proj_copy_N8_us / proj_speedup': 'one-GPU projection of the cfg4 strong cut: a rank\'s pass at N = 1 and N = 8, a copy of the N = 8 shard, N1 / N8',
     'exact_ms / exact_frac': 'VND_MODE_EXACT (bit-identical, the API default) on the headline pool: kernel ms, fraction of 8 TB/s',
@@ -862,9 +879,10 @@ def compact(d: dict) -> dict:
     """The stdout line: the contract's keys plus one short numeric key per claim, all under `config`, `roofline` and
     `cpu_baseline` (which the driver's record keeps whole), no string above 120 characters."""
     cfg, roof, sec, nxt = d['config'], d['roofline'], d.get('secondary') or {}, d.get('next_rows') or {}
+    parity = cfg['parity_vs_oracle_of_peak']                  # None: a plain run checks nothing against the oracle
     c = {'workload': f"cfg2: 48 kHz stereo f32, 10 s, 30 taps / 30 ms, seed 1; pool of {cfg['pool_signals_per_gpu']} signals per GPU, one launch per step",
          'pool': cfg['pool_signals_per_gpu'], 'frames': cfg['frames'], 'channels': cfg['channels'], 'mode': cfg['arithmetic'],
-         'parity': float(f"{cfg['parity_vs_oracle_of_peak']:.3g}"), 'timed_ms': d.get('timed_ms'), 'world_size': cfg['world_size'], 'backend': cfg['backend'],
+         'parity': None if parity is None else float(f'{parity:.3g}'), 'timed_ms': d.get('timed_ms'), 'world_size': cfg['world_size'], 'backend': cfg['backend'],
          'ranks_seen': cfg['ranks_seen_by_all_reduce'],
          'exact_ms': dig(d, 'exact_mode', 'kernel_ms'), 'exact_frac': dig(d, 'exact_mode', 'frac_of_8TBs'),
          'class_exact_frac': dig(d, 'exact_mode', 'class_path_table', 'frac_of_8TBs')}
@@ -1002,7 +1020,7 @@ def main():
         dist.all_reduce(ones)
         ranks_seen = int(ones.item())
         assert ranks_seen == dist.get_world_size() == world, (ranks_seen, dist.get_world_size(), world)
-    power = PowerSampler(torch, local_rank) if (rank == 0 and not args.no_power) else None
+    power = PowerSampler(torch, local_rank) if (rank == 0 and args.full and not args.no_power) else None
 
     import vndecorrelate_amd.decorrelation as vnd
     from vndecorrelate_amd import _native
@@ -1071,7 +1089,7 @@ def main():
     elapsed, kernel_ms = timed(mode, args.steps, args.warmup)
     timed_ms = elapsed * 1e3
     checked = sorted({0, args.pool // 2, args.pool - 1})      # first, middle, last stream (the last: past 4 GiB of offsets)
-    y_timed = {b: y[b].cpu().numpy() for b in checked} if rank == 0 else None
+    y_timed = {b: y[b].cpu().numpy() for b in checked} if (rank == 0 and args.full) else None
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, torch, y)
 
@@ -1081,7 +1099,8 @@ def main():
         elapsed = float(t.item())
 
     # spot-check the timed output against the oracle on three streams (rank 0)
-    if rank == 0:
+    parity = None
+    if rank == 0 and args.full:
         from oracle import c_oracle
         parity = 0.0
         for b in checked:
@@ -1096,7 +1115,7 @@ def main():
 
     # the bit-exact mode on the same pool, reported beside the headline (not part of `value`)
     exact_info = None
-    if mode != vnd.MODE_EXACT and not args.no_exact:
+    if args.full and mode != vnd.MODE_EXACT and not args.no_exact:
         e_elapsed, e_kernel_ms = timed(vnd.MODE_EXACT, max(args.steps // 2, 1), 2)
         if rank == 0:
             assert np.array_equal(y[args.pool - 1].cpu().numpy(), want), 'exact mode differs from the oracle'
@@ -1144,7 +1163,7 @@ def main():
     # written per sample, the kernel's algorithmic traffic), the honest companion of the 8 TB/s figure
     copy_gbs = stream_copy_gbs = None
     power_info = None
-    if rank == 0:
+    if rank == 0 and args.full:
         for _ in range(3):
             y.copy_(x)
         c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -1187,7 +1206,7 @@ def main():
     # what a one-file caller sees (the reference's own use, tests/test_example.py:19-49): ONE device-resident cfg2 signal per launch -
     # never builds a per-table kernel by itself (small launches do not stall for hipRTC), so this is a generic kernel's latency
     single_launch = None
-    if rank == 0:
+    if rank == 0 and args.full:
         single_launch = {}
         for label, m in (('fast', vnd.MODE_FAST), ('exact', vnd.MODE_EXACT)):
             lat = []
@@ -1210,7 +1229,7 @@ def main():
     torch.cuda.empty_cache()
 
     strong = None
-    if not (args.no_strong or args.no_secondary):           # (--no-secondary: the headline alone)
+    if args.full and not (args.no_strong or args.no_secondary):     # (--no-secondary: the headline alone)
         strong = cfg4_strong(torch, dist, vnd, _native, ctx, image, mode, world, rank, device, args.backend,
                              taps=(arrays.tap_offsets, arrays.tap_index, arrays.tap_weight) if rank == 0 else None)
 
@@ -1247,8 +1266,8 @@ def main():
                                    f'{args.pool} distinct signals resident per GPU, one batched launch per step',
                        'pool_signals_per_gpu': args.pool, 'frames': n, 'channels': CHANNELS,
                        'Mframes_per_s': round(value / CHANNELS, 1),
-                       'arithmetic': args.mode, 'parity_vs_oracle_of_peak': (0.0 if mode == vnd.MODE_EXACT else parity),
-                       'parity_streams_checked': checked,
+                       'arithmetic': args.mode, 'parity_vs_oracle_of_peak': parity,
+                       'parity_streams_checked': checked if parity is not None else None,
                        'launch': launch_text, 'exact_mode': 'top-level key `exact_mode`', 'single_launch_us': single_launch,
                        'world_size': world, 'backend': (args.backend if world > 1 else None), 'ranks_seen_by_all_reduce': ranks_seen,
                        'sharding': 'independent streams per rank; RCCL broadcast of the tap table only'},
@@ -1259,9 +1278,10 @@ def main():
                          'unit': 'GB/s', 'frac': round(achieved / HBM_PEAK_GBS, 4), 'traffic': traffic,
                          'traffic_source': traffic_source,
                          'read_only_frac': round(achieved / 2 / HBM_PEAK_GBS, 4),
-                         'kernel_ms': round(kernel_ms, 4), 'device_copy_GBs': round(copy_gbs, 1),
-                         'streaming_copy_GBs': round(stream_copy_gbs, 1),
-                         'frac_of_streaming_copy': round(achieved / stream_copy_gbs, 4),
+                         'kernel_ms': round(kernel_ms, 4),
+                         'device_copy_GBs': round(copy_gbs, 1) if copy_gbs else None,
+                         'streaming_copy_GBs': round(stream_copy_gbs, 1) if stream_copy_gbs else None,
+                         'frac_of_streaming_copy': round(achieved / stream_copy_gbs, 4) if stream_copy_gbs else None,
                          'streaming_copy_what': 'a plain copy of the same pool in this run (vnd_time_copy_f32_dev: 16-byte '
                                                 'non-temporal loads and stores; device_copy_GBs is torch\'s Tensor.copy_): what a '
                                                 'kernel that reads 4 B and writes 4 B per sample can reach on this box',
@@ -1273,7 +1293,7 @@ def main():
         }
         if strong is not None:
             detail['cfg4_strong'] = strong
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             detail['secondary'] = secondary_configs(torch, vnd, _native, ctx, mode, power)
             try:
                 detail['end_to_end'] = end_to_end(torch, vnd, mode)
@@ -1286,7 +1306,7 @@ def main():
             detail['next_rows'] = next_rows(torch, vnd, _native, power)
         if power is not None:
             power.close()
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             detail['cpu_baseline'] = cpu_baseline(args.cpu_seconds)
         # the long record: a side file (and gpurun_out/, which travels back from a GPU box) and stderr; the short line: stdout, last
         text = json.dumps(detail, indent=1)

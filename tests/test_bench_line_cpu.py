@@ -66,6 +66,35 @@ def test_a_failed_leg_costs_its_keys_only():
     assert 'cfg5_frac' not in config and 'cfg5_error' in config and config['exact_frac'] is None and config['cfg3_frac'] > 0
 
 
+def test_a_plain_run_line_has_the_contract_and_nothing_it_did_not_measure():
+    """Without --full the run times the headline alone: no oracle parity, no copy kernels or board readings, no other leg.  The line
+    keeps the contract's keys and the roofline of the timed steps, and carries null or nothing for the rest."""
+    import bench
+    d = _detail()
+    for leg in ('secondary', 'next_rows', 'audio', 'end_to_end', 'cfg4_strong', 'cpu_baseline'):
+        d.pop(leg, None)
+    d['exact_mode'] = None
+    d['config'].update(parity_vs_oracle_of_peak=None, single_launch_us=None)
+    d['roofline'].update(device_copy_GBs=None, streaming_copy_GBs=None, frac_of_streaming_copy=None, power=None)
+    line = bench.compact(d)
+    assert len(json.dumps(line, separators=(',', ':'))) < 4096 and all(len(s) <= 120 for s in _strings(line))
+    for key in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'dtype'):
+        assert line[key] == d[key], key
+    assert 'config' in line and 'roofline' in line and 'cpu_baseline' not in line
+    config, roof = line['config'], line['roofline']
+    assert config['parity'] is None and config['exact_frac'] is None and 'cfg3_frac' not in config and 'cfg4_strong' not in config
+    assert roof['frac'] == d['roofline']['frac'] and roof['kernel_ms'] == d['roofline']['kernel_ms']
+    assert roof['copy_GBs'] is None and roof['frac_of_copy'] is None and roof['power_W'] is None
+
+
+def test_full_is_off_by_default(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '20', '--warmup', '5'])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full'])
+    assert bench.parse().full is True
+
+
 def test_plain_gpus_n_starts_its_own_ranks(monkeypatch, capsys):
     """`python bench.py --gpus 4` without WORLD_SIZE: a CHILD `python -m torch.distributed.run` with the same arguments; rank 0's line
     is relayed to stdout, other output to stderr, the child's code is the exit code; the parent does not import torch."""

@@ -234,7 +234,7 @@ def test_bench_runs_with_two_ranks(tmp_path, how):
         env['VND_BENCH_FORCE_DEVICE'] = '0'
     detail = tmp_path / 'detail.json'
     args = ['--gpus', '2', '--steps', '3', '--warmup', '1', '--pool', '16', '--min-warmup-ms', '10', '--backend', 'nccl' if two else 'gloo',
-            '--detail', str(detail)]
+            '--detail', str(detail), '--full']
     if how == 'plain':
         cmd = [sys.executable, str(repo / 'bench.py'), *args]
     else:
@@ -282,7 +282,7 @@ def test_bench_rehearsal_with_four_ranks(tmp_path):
         env['VND_BENCH_FORCE_DEVICE'] = '0'
     detail = tmp_path / 'detail.json'
     cmd = [sys.executable, str(repo / 'bench.py'), '--gpus', str(ranks), '--steps', '3', '--warmup', '1', '--pool', '64', '--min-warmup-ms', '10',
-           '--backend', 'nccl' if real else 'gloo', '--detail', str(detail)]
+           '--backend', 'nccl' if real else 'gloo', '--detail', str(detail), '--full']
     t0 = time.perf_counter()
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=str(repo))
     wall = time.perf_counter() - t0

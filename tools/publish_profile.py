@@ -10,7 +10,7 @@ kernel = next(k for k in digest['kernels'] if needle in k)
 trace = digest['kernels'][kernel]
 counters = {c: round(v['mean'], 1) for c, v in digest['counters'].get(kernel, {}).items()}
 out = {
-    'command': 'rocprofv3 {--kernel-trace --stats | --pmc <one group per pass>} -- python3 bench.py --steps 20 '
+    'command': 'rocprofv3 {--kernel-trace --stats | --pmc <one group per pass>} -- python3 bench.py --full --steps 20 '
                '--warmup 5 --no-cpu --no-exact --no-secondary [--mode exact]  (tools/profile.sh)',
     'kernel': kernel,
     'kernel_trace_us': trace,
