@@ -382,3 +382,74 @@ def haas_effect(x, *, sample_rate_hz, delay_time_seconds=0.02, delayed_channel=0
     if width is not None:
         apply_stereo_width(y, width)
     return y
+
+
+# ---- VND_MODE_FMA: the tap sum with one rounding per tap (include/vnd_amd.h) ---------------
+# The library's own third arithmetic, no reference counterpart: tests/test_fma_oracle_cpu.py holds
+# it to exact rational arithmetic instead of to fixtures.
+def fma_f32(x, w, acc) -> np.ndarray:
+    """Correctly rounded float32 ``fma(x, w, acc)`` (round to nearest, ties to even), vectorised.
+
+    The float64 product of two float32 values is exact (48 significand bits, exponents in
+    range).  TwoSum gives the float64 sum ``s`` and its exact error ``e``; stepping ``s`` one ulp
+    toward ``e`` when ``e != 0`` and the last significand bit of ``s`` is even rounds the sum to
+    odd, and a round-to-odd float64 (53 >= 24 + 2 bits) casts to the correctly rounded float32,
+    subnormal results included.  Non-finite sums pass through unchanged.
+    """
+    x, w, acc = np.broadcast_arrays(np.asarray(x, np.float32), np.asarray(w, np.float32),
+                                    np.asarray(acc, np.float32))
+    p = x.astype(np.float64) * w.astype(np.float64)
+    a = acc.astype(np.float64)
+    with np.errstate(invalid='ignore', over='ignore'):
+        s = p + a
+        bp = s - a                                   # TwoSum (Knuth): s + e == p + a exactly
+        e = (a - (s - bp)) + (p - bp)
+        finite = np.isfinite(s)
+        even = (s.view(np.int64) & 1) == 0
+        step = finite & (e != 0) & even
+        s = np.where(step, np.nextafter(s, np.where(e > 0, np.inf, -np.inf)), s)
+        return s.astype(np.float32)
+
+
+def convolve_taps_fma(x, offsets, idx, w, seg_offsets=None, seg_end=None, seg_gain=None,
+                      chan_flags=None, apply_gain=False) -> np.ndarray:
+    """VND_MODE_FMA restated: the C oracle's tables and association, one rounding per tap.
+
+    Per segment ``sb`` starts at +0 and takes ``sb = fma(x[n+i], w, sb)`` for each tap in table
+    order; then ``sb *= gain`` (``apply_gain``) and ``out += sb`` - or ``out = sb`` on the function
+    path (no segment table).  Pass-through channels (``chan_flags & 1``) copy their input.  A term
+    whose tap reaches past the end of the signal is dropped, not added as zero.  ``x`` is
+    ``(n, C)`` or ``(batch, n, C)`` float32.
+    """
+    x = np.ascontiguousarray(x, np.float32)
+    xb = x[None] if x.ndim == 2 else x
+    batch, n, channels = xb.shape
+    offsets = np.asarray(offsets, np.int64)
+    idx = np.asarray(idx, np.int64)
+    w = np.asarray(w, np.float32)
+    y = np.zeros_like(xb)
+    for c in range(channels):
+        if chan_flags is not None and int(chan_flags[c]) & 1:
+            y[:, :, c] = xb[:, :, c]
+            continue
+        if seg_offsets is None:
+            ends = [int(offsets[c + 1])]
+        else:
+            ends = [int(seg_end[s]) for s in range(int(seg_offsets[c]), int(seg_offsets[c + 1]))]
+        out = np.zeros((batch, n), np.float32)
+        k = int(offsets[c])
+        for s, kend in enumerate(ends):
+            sb = np.zeros((batch, n), np.float32)
+            for t in range(k, kend):
+                i = int(idx[t])
+                if i < n:
+                    sb[:, :n - i] = fma_f32(xb[:, i:, c], w[t], sb[:, :n - i])
+            k = kend
+            if seg_offsets is None:
+                out = sb
+            else:
+                if apply_gain:
+                    sb = sb * np.float32(seg_gain[int(seg_offsets[c]) + s])
+                out = out + sb
+        y[:, :, c] = out
+    return y.reshape(x.shape)

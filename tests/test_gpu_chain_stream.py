@@ -155,7 +155,12 @@ def test_chain_pool_of_one_shapes(vnd):
 
 
 def test_chain_fma_and_fast_modes(vnd):
+    from oracle import c_oracle
+    from oracle import vnd_oracle as O
     x = _input('stereo', 5, 5000, 21)
+    offs, idx, w = O.fir_to_taps(_fir())
+    conv_fma = c_oracle.convolve_fma(x, offs, idx, w, threads=4)
+    assert not np.array_equal(conv_fma, c_oracle.convolve(x, offs, idx, w, threads=4))
     for name in ('vn>haas', 'conv>haas'):
         make = _chains(vnd)[name]
         cs = make().stream(num_streams=5, mode=vnd.MODE_FMA, max_frames_per_call=480)
@@ -165,6 +170,9 @@ def test_chain_fma_and_fast_modes(vnd):
             chain = make()
             for b in range(5):
                 assert np.array_equal(got[b], chain(x[b])), (name, b)
+                if name == 'conv>haas':      # the fma definition, then the reference's Haas stage
+                    want = O.haas_effect(conv_fma[b], sample_rate_hz=FS, delay_time_seconds=0.005, delayed_channel=1, mode='MS')
+                    assert np.array_equal(got[b], want), (name, b)
         finally:
             vnd.set_default_mode(vnd.MODE_EXACT)
         cs = make().stream(num_streams=5, mode=vnd.MODE_FAST, max_frames_per_call=480)

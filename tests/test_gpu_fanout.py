@@ -4,7 +4,8 @@ channels than the tap table, output channel c reading input channel c % in_chann
 The oracle is the plain convolution on the REPLICATED input (that is what the
 reference does: `mono_to_stereo` then convolve, decorrelation.py:431-432; or the
 optimiser's loop over candidate filters, optimization.py:107-117), so every case
-is checked bit for bit in the exact mode and to 1e-6 of peak in the others.
+is checked bit for bit in the exact mode, bit for bit against its own definition
+(oracle.c_oracle.convolve_fma) in the fma mode, and to 1e-6 of peak in the fast mode.
 """
 import numpy as np
 import pytest
@@ -55,12 +56,15 @@ def test_mono_to_stereo_function_path(vnd, golden, n):
     table = _table(fir)
     x = make_input(dict(seed=40 + n % 7, shape=[n, 1]))
     want = c_oracle.convolve(_replicate(x, 2), offs, idx, w, threads=4)
+    want_fma = c_oracle.convolve_fma(_replicate(x, 2), offs, idx, w, threads=4)
+    assert np.array_equal(want_fma, want) == (n == 1)      # (one frame: no tap reaches it, the output is zero)
     assert 'fanout' in table.describe(1, n, 1, vnd.MODE_EXACT)
+    assert table.describe(1, n, 1, vnd.MODE_FMA).startswith('conv_ordered_fanout')
     y = table.convolve_host(x, vnd.MODE_EXACT)
     assert y.shape == (n, 2) and y.dtype == np.float32
     assert np.array_equal(y, want)
-    for mode in (vnd.MODE_FMA, vnd.MODE_FAST):
-        assert _close(table.convolve_host(x, mode), want) <= TOL_PEAK, mode
+    assert np.array_equal(table.convolve_host(x, vnd.MODE_FMA), want_fma)
+    assert _close(table.convolve_host(x, vnd.MODE_FAST), want) <= TOL_PEAK
 
 
 def test_mono_batch_and_every_tile_size(vnd, golden):
@@ -71,15 +75,20 @@ def test_mono_batch_and_every_tile_size(vnd, golden):
     table = _table(fir)
     x = make_input(dict(seed=41, shape=[5, 20011, 1]))
     want = c_oracle.convolve(_replicate(x, 2), offs, idx, w, threads=4)
+    want_fma = c_oracle.convolve_fma(_replicate(x, 2), offs, idx, w, threads=4)
+    assert not np.array_equal(want_fma, want)
     try:
         for pairs in (0, 1, 2, 3, 4, 6, 8):
             ctx.set_variant(pairs if pairs else -1)
-            for mode in (vnd.MODE_EXACT, vnd.MODE_FAST):
-                if mode == vnd.MODE_EXACT and pairs in (3, 6):
+            for mode in (vnd.MODE_EXACT, vnd.MODE_FMA, vnd.MODE_FAST):
+                if mode != vnd.MODE_FAST and pairs in (3, 6):
                     continue                                   # the ordered kernel has no such tile
                 y = table.convolve_host(x, mode)
                 if mode == vnd.MODE_EXACT:
                     assert np.array_equal(y, want), pairs
+                elif mode == vnd.MODE_FMA:
+                    assert table.describe(5, 20011, 1, mode).startswith('conv_ordered_fanout'), pairs
+                    assert np.array_equal(y, want_fma), pairs
                 else:
                     assert _close(y, want) <= TOL_PEAK, pairs
         ctx.set_variant(1 << 8)                                # one channel per workgroup: plain staging, stride 1
@@ -176,17 +185,22 @@ def test_fanout_device_pointers_misaligned(vnd, golden):
     n, batch = 9001, 3
     x = make_input(dict(seed=46, shape=[batch, n, 1]))
     want = c_oracle.convolve(_replicate(x, 2), offs, idx, w, threads=4)
+    want_fma = c_oracle.convolve_fma(_replicate(x, 2), offs, idx, w, threads=4)
+    assert not np.array_equal(want_fma, want)
     stream = torch.cuda.current_stream().cuda_stream
     for shift in (0, 1, 2, 3):
         xin = torch.zeros(x.size + 8, dtype=torch.float32, device='cuda:0')
         yout = torch.full((want.size + 8,), 7.0, dtype=torch.float32, device='cuda:0')
         xin[shift:shift + x.size] = torch.from_numpy(x.ravel()).cuda()
-        for mode in (vnd.MODE_EXACT, vnd.MODE_FAST):
+        for mode in (vnd.MODE_EXACT, vnd.MODE_FMA, vnd.MODE_FAST):
             table.convolve_device(xin.data_ptr() + 4 * shift, yout.data_ptr() + 4 * shift, batch, n, 1, mode, stream)
             torch.cuda.synchronize()
             got = yout.cpu().numpy()
             body = got[shift:shift + want.size].reshape(want.shape)
-            assert (np.array_equal(body, want) if mode == vnd.MODE_EXACT else _close(body, want) <= TOL_PEAK), shift
+            if mode == vnd.MODE_FAST:
+                assert _close(body, want) <= TOL_PEAK, shift
+            else:
+                assert np.array_equal(body, want if mode == vnd.MODE_EXACT else want_fma), (mode, shift)
             assert np.all(got[:shift] == 7.0) and np.all(got[shift + want.size:] == 7.0), shift
 
 

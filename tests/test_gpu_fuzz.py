@@ -1,11 +1,14 @@
 """GPU tier: RANDOM tap tables - channel counts, spans, tap counts, weights (among them +-1, tiny ones, repeated magnitudes),
 signal lengths and batches drawn per seed - through every kernel family the library can pick or be told to pick (automatic
 choice, per-table pair-read form, per-table window form with 32- and 16-frame runs, generic kernels), against the NumPy
-oracle: VND_MODE_EXACT bit for bit, VND_MODE_FAST within 1e-6 of the output peak.  The golden tables of the other tests
-are the reference's; these are not velvet noise at all - any FIR table the API accepts must come out right."""
+oracle: VND_MODE_EXACT bit for bit, VND_MODE_FMA bit for bit against its definition (oracle.c_oracle.convolve_fma; it has
+no per-table form, so a generic kernel runs whatever is asked), VND_MODE_FAST within 1e-6 of the output peak.  The golden
+tables of the other tests are the reference's; these are not velvet noise at all - any FIR table the API accepts must come
+out right."""
 import numpy as np
 import pytest
 
+from oracle import c_oracle
 from oracle import vnd_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -55,6 +58,7 @@ def test_random_tables_through_every_kernel_family(seed, monkeypatch):
     if C == 2:
         variants.append(('window 64 split', FORCE | WIN[64] | span_bits(1, 3)))
         env_of['window 64 split'] = {'VND_WIN_SPLIT': '2', 'VND_SPEC_NT': '256'}
+    fma_told_apart = False
     try:
         # (the largest length is a multiple of 4 frames: streams of a batch then start 16-byte aligned, which the per-table
         #  kernels ask for - the odd lengths before it go through the generic kernels whatever is asked)
@@ -65,6 +69,8 @@ def test_random_tables_through_every_kernel_family(seed, monkeypatch):
                 if seed % 2:
                     x[0, :min(n, 50)] *= np.float32(1e-30)      # products that underflow to denormals and to zero
                 want = np.stack([O.convolve_velvet_noise(x[b], fir) for b in range(batch)])
+                want_fma = c_oracle.convolve_fma(x, a.tap_offsets, a.tap_index, a.tap_weight, threads=4)
+                fma_told_apart |= not np.array_equal(want_fma, want)
                 peak = float(np.max(np.abs(want))) or 1.0
                 for name, variant in variants:
                     ctx.set_variant(variant)
@@ -72,17 +78,22 @@ def test_random_tables_through_every_kernel_family(seed, monkeypatch):
                         monkeypatch.delenv(key, raising=False)
                     for key, value in env_of.get(name, {}).items():
                         monkeypatch.setenv(key, value)
-                    for mode in (d.MODE_EXACT, d.MODE_FAST):
+                    for mode in (d.MODE_EXACT, d.MODE_FMA, d.MODE_FAST):
                         got = table.convolve_host(x, mode)
                         where = f'seed {seed} C={C} span={span} taps={len(a.tap_index)} n={n} batch={batch} {name}: {table.describe(batch, n, C, mode)[:60]}'
                         assert got.shape == want.shape, where
-                        if C % 2 == 0 and n >= 10000 and name != 'automatic':       # the family asked for is the family that ran
+                        if mode == d.MODE_FMA:                                      # no per-table fma form: a generic kernel ran
+                            text = table.describe(batch, n, C, mode)
+                            assert text.startswith(('conv_ordered', 'conv_direct')), where
+                        elif C % 2 == 0 and n >= 10000 and name != 'automatic':     # the family asked for is the family that ran
                             text = table.describe(batch, n, C, mode)
                             family = {'pair-read': 'conv_spec', 'generic': 'conv_'}.get(name, 'conv_spec')
                             assert text.startswith(family) and ('_window' in text) == name.startswith('window') and \
                                 ('conv_spec' in text) == (name != 'generic'), where
                         if mode == d.MODE_EXACT:
                             assert np.array_equal(got, want), where
+                        elif mode == d.MODE_FMA:
+                            assert np.array_equal(got, want_fma), where
                         else:
                             err = float(np.max(np.abs(got.astype(np.float64) - want))) / peak
                             assert err <= 1e-6, f'{where}: {err:.2e}'
@@ -91,6 +102,7 @@ def test_random_tables_through_every_kernel_family(seed, monkeypatch):
         for key in ('VND_WIN_SPLIT', 'VND_SPEC_NT'):
             monkeypatch.delenv(key, raising=False)
         table.close()
+    assert fma_told_apart, seed               # the fma reference is not the exact oracle on this seed's inputs
 
 
 # (sample rate, seconds of filter, impulses, segment envelope, log strength, width, mode, normalise, input: frames / channels)

@@ -32,9 +32,8 @@ def ctx():
 
 def _term_scale(arr, x) -> float:
     """max over channels of sum_k |w_k * gain| times max|x|: the size of what is being added up.
-    The fma modes round each product differently from mul-then-add and the fast mode adds in
-    another order, so when the taps cancel (output peak << terms; hypothesis finds -x[0] + x[0])
-    the honest floor is the rounding bound of a K-term sum, K * 2^-24 * sum|terms|, not a
+    The fast mode adds in another order, so when the taps cancel (output peak << terms; hypothesis
+    finds -x[0] + x[0]) the honest floor is the rounding bound of a K-term sum, K * 2^-24 * sum|terms|, not a
     fraction of the vanishing peak.  (A wrong tap or weight is off by the size of a term.)"""
     w = np.abs(arr.tap_weight.astype(np.float64))
     if arr.seg_offsets is not None and arr.apply_gain and len(w):
@@ -50,7 +49,11 @@ def _term_scale(arr, x) -> float:
 
 
 def _check(ctx, arr, x, want, pairs):
+    """mode 0 (exact) and mode 1 (fma, against its definition) bit for bit, mode 2 (fast) within tolerance."""
     from vndecorrelate_amd import _native
+    want_fma = c_oracle.convolve_fma(x, arr.tap_offsets, arr.tap_index, arr.tap_weight, seg_off=arr.seg_offsets,
+                                     seg_end=arr.seg_end, seg_gain=arr.seg_gain, chan_flags=arr.chan_flags,
+                                     apply_gain=arr.apply_gain)
     table = _native.TapTable.create(ctx, arr.tap_offsets, arr.tap_index, arr.tap_weight, **arr.kwargs())
     peak = max(float(np.max(np.abs(want))) if want.size else 0.0, 1e-30)
     floor = 2.0 ** -24 * _term_scale(arr, x)
@@ -60,6 +63,8 @@ def _check(ctx, arr, x, want, pairs):
             y = table.convolve_host(x, mode)
             if mode == 0:
                 assert np.array_equal(y, want), f'exact mode, pairs={pairs}'
+            elif mode == 1:
+                assert np.array_equal(y, want_fma), f'fma mode, pairs={pairs}'
             else:
                 assert np.max(np.abs(y.astype(np.float64) - want)) <= 1e-6 * peak + floor + 1e-30, (mode, pairs)
     finally:

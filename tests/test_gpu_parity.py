@@ -2,8 +2,10 @@
 and against the fixtures captured from the reference.
 
 Bars: VND_MODE_EXACT is BIT-EXACT for float32 input (sha256 of the whole output
-equals the reference's); VND_MODE_FMA and non-float32 inputs (rounded to float32
-at the boundary) stay within 1e-6 of the output peak - the north-star tolerance.
+equals the reference's); VND_MODE_FMA is BIT-EXACT against its own definition
+(``acc = fma(x, w, acc)`` in table order: oracle.c_oracle.convolve_fma) and within
+1e-6 of the reference's peak; non-float32 inputs (rounded to float32 at the
+boundary) stay within 1e-6 of the output peak - the north-star tolerance.
 """
 import json
 import pathlib
@@ -101,8 +103,12 @@ def test_function_path_tolerance_modes(vnd, golden, name, mode):
     meta = golden.manifest['fn'][name]
     x = make_input(meta['input'])
     m = vnd.MODE_FMA if mode == 'fma' else vnd.MODE_FAST
-    y = vnd.convolve_velvet_noise(x, _fir_for(golden, name, meta), mode=m)
+    fir = _fir_for(golden, name, meta)
+    y = vnd.convolve_velvet_noise(x, fir, mode=m)
     golden.expect(name, y, exact=False, rtol_peak=TOL_PEAK)
+    if m == vnd.MODE_FMA:       # outside exact mode the operands are cast to float32 first; then the fma definition, bit for bit
+        offs, idx, w = O.fir_to_taps(fir.astype(np.float32))
+        assert np.array_equal(y, c_oracle.convolve_fma(x.astype(np.float32), offs, idx, w, threads=4)), name
 
 
 def test_function_path_errors(vnd, golden):
@@ -213,6 +219,11 @@ def test_variants_agree(vnd, golden, channels, gname):
     x = make_input(dict(seed=11, shape=[20011, channels]))
     offs, idx, w = O.fir_to_taps(fir)
     want = c_oracle.convolve(x, offs, idx, w)
+    want_fma = c_oracle.convolve_fma(x, offs, idx, w)
+    assert not np.array_equal(want_fma, want)             # the two arithmetics are told apart on this input
+    from vndecorrelate_amd.taps import function_path_arrays
+    arr = function_path_arrays(fir)
+    table = _native.TapTable.create(ctx, arr.tap_offsets, arr.tap_index, arr.tap_weight)
     cgs = [c for c in (1, 2, 4) if channels % c == 0]
     try:
         for mode in (vnd.MODE_EXACT, vnd.MODE_FMA, vnd.MODE_FAST):
@@ -224,11 +235,17 @@ def test_variants_agree(vnd, golden, channels, gname):
                         tag = f'mode={mode} direct={direct} cg={cg} pairs={r}'
                         if mode == vnd.MODE_EXACT:
                             assert np.array_equal(y, want), tag
+                        elif mode == vnd.MODE_FMA:
+                            text = table.describe(1, 20011, channels, mode)      # the generic kernel asked for ran
+                            assert text.startswith('conv_direct') if direct else \
+                                (text.startswith('conv_ordered') and f'cg={cg} pairs_per_lane={r} ' in text), (tag, text)
+                            assert np.array_equal(y, want_fma), tag
                         else:
                             err = np.max(np.abs(y.astype(np.float64) - want)) / np.max(np.abs(want))
                             assert err <= TOL_PEAK, (tag, err)
     finally:
         ctx.set_variant(-1)
+        table.close()
 
 
 def test_class_variants_agree(vnd, golden):
@@ -266,20 +283,22 @@ def test_mid_length_firs_stay_in_lds(vnd, seconds):
     table = _native.TapTable.create(_native.default_context(), arr.tap_offsets, arr.tap_index, arr.tap_weight)
     assert 'direct' not in table.describe(2, 90001, 2, vnd.MODE_FAST)
     want = c_oracle.convolve(x, arr.tap_offsets, arr.tap_index, arr.tap_weight, threads=4)
+    want_fma = c_oracle.convolve_fma(x, arr.tap_offsets, arr.tap_index, arr.tap_weight, threads=4)
+    assert not np.array_equal(want_fma, want)
     assert np.array_equal(table.convolve_host(x, vnd.MODE_EXACT), want)
+    assert np.array_equal(table.convolve_host(x, vnd.MODE_FMA), want_fma)
     peak = np.max(np.abs(want))
-    for mode in (vnd.MODE_FMA, vnd.MODE_FAST):
-        assert np.max(np.abs(table.convolve_host(x, mode).astype(np.float64) - want)) <= 1e-6 * peak, mode
+    assert np.max(np.abs(table.convolve_host(x, vnd.MODE_FAST).astype(np.float64) - want)) <= 1e-6 * peak
     from vndecorrelate_amd.utils import dsp
-    for mode in (vnd.MODE_EXACT, vnd.MODE_FAST):
+    for mode in (vnd.MODE_EXACT, vnd.MODE_FMA, vnd.MODE_FAST):
         got = table.decorrelate_host(x, mode, ms_encode=True, width=0.4, normalize=_native.NORMALIZE_RMS_REFERENCE_ORDER)
         for b in range(2):
-            ref = want[b].copy()
+            ref = (want_fma if mode == vnd.MODE_FMA else want)[b].copy()
             dsp.encode_signal_to_side_channel(x[b], ref)
             dsp.apply_stereo_width(ref, 0.4)
             dsp.rms_normalize(x[b], ref)
-            if mode == vnd.MODE_EXACT:
-                assert np.array_equal(got[b], ref), (seconds, b)
+            if mode != vnd.MODE_FAST:
+                assert np.array_equal(got[b], ref), (seconds, mode, b)
             else:
                 assert np.max(np.abs(got[b] - ref)) <= 3e-6 * np.max(np.abs(ref)), (seconds, b)
 
@@ -468,15 +487,17 @@ def test_fused_and_unfused_epilogue_agree(vnd, golden):
 @pytest.mark.parametrize('name', sorted(MANIFEST['cls_decorrelate']))
 def test_default_epilogue_in_tolerance_modes(vnd, golden, name, mode):
     """Default policy outside exact mode: device epilogue with the sums in NumPy's order, so the stage
-    differs from the reference only through the convolution's 1e-6 of peak."""
+    differs from the reference only through the convolution's 1e-6 of peak.  The class-path tables are
+    +-1, where the fma arithmetic is the exact one: in fma mode a float32 stage is the reference's bits."""
     meta = golden.manifest['cls_decorrelate'][name]
     kw = _kw(golden.manifest['class_taps'][meta['class']]['kwargs'])
+    x = make_input(meta['input'])
     vnd.set_default_mode(vnd.MODE_FMA if mode == 'fma' else vnd.MODE_FAST)
     try:
-        y = vnd.VelvetNoise(**kw).decorrelate(make_input(meta['input']))
+        y = vnd.VelvetNoise(**kw).decorrelate(x)
     finally:
         vnd.set_default_mode(vnd.MODE_EXACT)
-    golden.expect(name, y, exact=False, rtol_peak=3e-6)
+    golden.expect(name, y, exact=mode == 'fma' and x.dtype == np.float32, rtol_peak=3e-6)
 
 
 def test_device_epilogue_batched(vnd, golden):

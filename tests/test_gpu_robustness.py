@@ -104,11 +104,14 @@ def test_non_finite_weight_drops_tail_terms_like_the_reference(vnd):
     x = np.random.default_rng(9).uniform(0.1, 1, (300, 2)).astype(np.float32)
     with np.errstate(all='ignore'):
         want = O.convolve_velvet_noise(x, fir)
+        want_fma = O.convolve_taps_fma(x, *O.fir_to_taps(fir))
     for mode in (vnd.MODE_EXACT, vnd.MODE_FMA, vnd.MODE_FAST):
         got = vnd.convolve_velvet_noise(x, fir, mode=mode)
         assert np.array_equal(np.isnan(got), np.isnan(want)), mode
         assert np.array_equal(np.isinf(got), np.isinf(want)), mode
         fin = np.isfinite(want)
+        if mode == vnd.MODE_FMA:        # the fma definition, bit for bit where finite (tests/test_gpu_fma.py: a table where the modes differ)
+            assert np.array_equal(got[fin], want_fma[fin])
         assert np.allclose(got[fin], want[fin], rtol=1e-6, atol=1e-6), mode
     assert np.isfinite(want[-4:, 0]).all() and np.isfinite(want[-10:, 1]).all()   # the dropped terms
 

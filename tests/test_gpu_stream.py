@@ -135,12 +135,17 @@ def test_pool_of_64_exact_and_fma(vnd):
     from vndecorrelate_amd.streaming import convolve_velvet_noise_stream
     fir = vnd.generate_velvet_noise(duration_seconds=0.03, num_impulses=30, sample_rate_hz=48000, seed=1)
     x = _pool()
+    offs, idx, w = O.fir_to_taps(fir)
+    ref = {vnd.MODE_EXACT: c_oracle.convolve(x, offs, idx, w, threads=8),
+           vnd.MODE_FMA: c_oracle.convolve_fma(x, offs, idx, w, threads=8)}
+    assert not np.array_equal(ref[vnd.MODE_FMA], ref[vnd.MODE_EXACT])
     for mode in (vnd.MODE_EXACT, vnd.MODE_FMA):
         s = convolve_velvet_noise_stream(fir, num_streams=64, mode=mode, max_frames_per_call=8192)
         y = _run(s, x, _schedule('random', x.shape[1], s.latency_frames, seed=mode))
         want = vnd.convolve_velvet_noise_batched(x, fir, mode=mode)
         for b in range(64):
             assert np.array_equal(y[b], want[b]), (mode, b)
+            assert np.array_equal(y[b], ref[mode][b]), (mode, b)
     vn = vnd.VelvetNoise(sample_rate_hz=48000, seed=1, normalizer=None, width=0.3)
     s = vn.stream(num_streams=64, max_frames_per_call=8192)
     y = _run(s, x, _schedule('random', x.shape[1], s.latency_frames, seed=5))
