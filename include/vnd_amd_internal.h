@@ -72,6 +72,12 @@ vnd_status vnd_tuning_read(const char *name, int32_t fallback, int32_t *value);
 vnd_status vnd_debug_read_stamps(vnd_ctx *ctx, const vnd_taps *taps, int64_t batch, int64_t n_frames,
                                  int32_t in_channels, int32_t mode, uint64_t *stamps, int64_t capacity,
                                  int64_t *count);
+/* Diagnosis: the launch plan a vnd_stream_f32_dev call (include/vnd_stream.h) of `batch` streams with `n_out` output frames per
+ * stream would take - the same planner, no device work - as one line of key=value fields: direct, r (frame pairs per lane),
+ * cg (channels per workgroup), bc (one staged plane for a mono input fanned out), W (window frames), lds_bytes, tiles,
+ * groups, nblocks.  epilogue = the call's ms_encode || use_width.                                                      */
+vnd_status vnd_describe_stream_launch(vnd_ctx *ctx, const vnd_taps *taps, int64_t batch, int64_t n_out,
+                                      int32_t in_channels, int32_t mode, int32_t epilogue, char *text, int32_t len);
 
 #ifdef __cplusplus
 }

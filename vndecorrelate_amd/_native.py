@@ -138,6 +138,9 @@ INTERNAL_SIGNATURES = {
     'vnd_tuning_read': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
     'vnd_debug_read_stamps': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
                                              ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+    'vnd_describe_stream_launch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                  ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p,
+                                                  ctypes.c_int32]),
 }
 
 # include/vnd_analysis.h: the analysis entry points, bound apart so that SIGNATURES keeps matching vnd_amd.h
@@ -607,6 +610,15 @@ class TapTable:
                     if channels == self.num_channels else
                     (self._lib.vnd_describe_fanout_launch, 'vnd_describe_fanout_launch'))
         _check(fn(self.ctx.handle, self.handle, batch, n, channels, int(mode), buf, 512), name)
+        return buf.value.decode()
+
+    def describe_stream(self, batch: int, n_out: int, in_channels: int, mode: int = MODE_EXACT,
+                        epilogue: bool = False) -> str:
+        """The plan of a ``vnd_stream_f32_dev`` call with ``n_out`` output frames per stream
+        (``vnd_describe_stream_launch``)."""
+        buf = ctypes.create_string_buffer(512)
+        _check(self._lib.vnd_describe_stream_launch(self.ctx.handle, self.handle, batch, n_out, in_channels, int(mode),
+                                                    int(bool(epilogue)), buf, 512), 'vnd_describe_stream_launch')
         return buf.value.decode()
 
     def read_stamps(self, batch: int, n: int, channels: int, mode: int = MODE_EXACT) -> np.ndarray:

@@ -225,4 +225,25 @@ vnd_status vnd_debug_read_stamps(vnd_ctx *ctx, const vnd_taps *t, int64_t batch,
     return VND_OK;
 }
 
+// The StreamPlan a vnd_stream_f32_dev call of this shape takes: the same make_stream_plan, on the call's output frames.
+vnd_status vnd_describe_stream_launch(vnd_ctx *ctx, const vnd_taps *t, int64_t batch, int64_t n_out, int32_t in_channels,
+                                      int32_t mode, int32_t epilogue, char *text, int32_t len)
+{
+    if (!ctx || !t) return fail(VND_ERR_INVALID, "null context or tap table");
+    if (!text || len <= 0) return fail(VND_ERR_INVALID, "null text buffer");
+    if (batch < 0 || batch > VND_MAX_STREAMS) return fail(VND_ERR_INVALID, "batch %lld outside 0..%d", (long long)batch, VND_MAX_STREAMS);
+    if (n_out < 0) return fail(VND_ERR_INVALID, "negative frame count");
+    if (in_channels <= 0 || t->C % in_channels != 0)
+        return fail(VND_ERR_INVALID, "%d input channels do not divide the tap table's %d channels", in_channels, t->C);
+    if (mode != VND_MODE_EXACT && mode != VND_MODE_FMA && mode != VND_MODE_FAST) return fail(VND_ERR_INVALID, "unknown mode %d", mode);
+    if (epilogue && t->C != 2)
+        return fail(VND_ERR_INVALID, "the side-channel encode and the width need 2 output channels, the table has %d", t->C);
+    const StreamPlan p = make_stream_plan(ctx, t, batch, n_out, t->C, in_channels, mode, epilogue != 0);
+    snprintf(text, (size_t)len,
+             "%s direct=%d r=%d cg=%d bc=%d W=%d lds_bytes=%zu tiles=%d groups=%d nblocks=%u mode=%d epilogue=%d threads=%d",
+             p.direct ? "conv_stream_direct" : "conv_stream", p.direct ? 1 : 0, p.r, p.cg, p.bc ? 1 : 0, p.W, p.lds_bytes,
+             p.tiles, p.groups, p.nblocks, mode, epilogue ? 1 : 0, p.direct ? kDirectThreads : kStreamThreads);
+    return VND_OK;
+}
+
 }  // extern "C"
