@@ -161,8 +161,12 @@ vnd_status vnd_convolve_promote_host(vnd_ctx *ctx, int32_t num_channels, const i
  *     NumPy's own float32 summation order, reproduced bit for bit - the sequential row-by-row
  *     recurrence of an (n, C >= 2) array, the pairwise sums (8192-element chunks) of an (n, 1)
  *     one; in exact mode the whole stage is bit-identical to the reference;
- *   otherwise (normalize = VND_NORMALIZE_RMS): exactly rounded float64 sums, fused into the
- *     fast kernel - the fastest form, ~1e-4 relative from NumPy's RMS on long signals.
+ *   otherwise (normalize = VND_NORMALIZE_RMS): float32 partial sums of at most 64 squares (16 to 64
+ *     by kernel form), added in float64 - the fastest form, fused into the fast kernel, ~1e-4
+ *     relative from NumPy's RMS on long signals.  Not correctly rounded: each sum is within
+ *     gamma_k = k 2^-24 / (1 - k 2^-24) of the exact one for partials of k squares, and the
+ *     scale is float32(sqrt(f32 mean_x) / sqrt(f32 mean_y + eps)) of those sums; the output is
+ *     float32(y * scale) exactly.
  * `workspace` is device memory of >= vnd_decorrelate_workspace_bytes().          */
 #define VND_MAX_STREAMS 65535   /* streams (batch) per decorrelate / Haas call: split larger batches */
 #define VND_NORMALIZE_OFF 0

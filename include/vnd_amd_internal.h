@@ -78,6 +78,16 @@ vnd_status vnd_debug_read_stamps(vnd_ctx *ctx, const vnd_taps *taps, int64_t bat
  * groups, nblocks.  epilogue = the call's ms_encode || use_width.                                                      */
 vnd_status vnd_describe_stream_launch(vnd_ctx *ctx, const vnd_taps *taps, int64_t batch, int64_t n_out,
                                       int32_t in_channels, int32_t mode, int32_t epilogue, char *text, int32_t len);
+/* Diagnosis (tests): vnd_decorrelate_fanout_f32_dev (in_channels == the table's channels: vnd_decorrelate_f32_dev), and which of the
+ * stage's forms ran, in taken[4]: [0] 0 the table-order launch with the pointwise steps and the sums as passes of their own, 1 the
+ * fast kernel with the pointwise steps (and, with VND_NORMALIZE_RMS, the sums) fused into its store phase, 2 the quad / octet kernel
+ * leaving the normaliser's sums, -1 nothing ran (no frames); [1] what the convolution launch reports: 0 a generic kernel, 1 the per-table
+ * kernel and it left the sums of squares, 2 the per-table kernel without them; [2] 1 if the sums are taken in NumPy's own order;
+ * [3] 1 if the convolution's store phase left the block sums those start from.  The planning is decorrelate's own.              */
+vnd_status vnd_debug_decorrelate_f32_dev(vnd_ctx *ctx, const vnd_taps *taps, const float *x, float *y, int64_t batch, int64_t n,
+                                         int32_t in_channels, int32_t mode, int32_t ms_encode, int32_t use_width, double width,
+                                         int32_t normalize, float eps, void *workspace, int64_t workspace_bytes, void *stream,
+                                         int32_t *taken);
 
 #ifdef __cplusplus
 }

@@ -453,3 +453,66 @@ def convolve_taps_fma(x, offsets, idx, w, seg_offsets=None, seg_end=None, seg_ga
                 out = out + sb
         y[:, :, c] = out
     return y.reshape(x.shape)
+
+
+# ---- the decorrelate stage's epilogue on a given convolution (VND_MODE_FAST, include/vnd_amd.h) ------------------
+# The fast mode's convolution has no reference counterpart, but everything the stage does after it does: for one
+# convolution ``y`` the pointwise steps and the NumPy-order normaliser are the reference's own operations, and the
+# float64-sum normaliser (VND_NORMALIZE_RMS) is the device's formula on sums of squares whose error the tests bound.
+def pointwise(x, y, ms_encode, width):
+    """The stage's pointwise steps on a ``(n, 2)`` convolution ``y`` of ``x`` - side-channel encode, then stereo width,
+    in the reference's float32 operations (utils/dsp.py:40-63, :21-37) - on a copy."""
+    y = np.array(y, np.float32, copy=True)
+    if ms_encode:
+        encode_side(x, y)
+    if width is not None:
+        apply_stereo_width(y, width)
+    return y
+
+
+def exact_sum_squares(a) -> np.ndarray:
+    """Per channel of a ``(n, C)`` float32 array, sum a^2 correctly rounded to float64: a float32 square is exact in
+    float64 (48 significand bits, exponents in range) and ``math.fsum`` rounds the exact sum of those once."""
+    import math
+    a = np.asarray(a, np.float32)
+    sq = np.square(a.astype(np.float64))
+    return np.array([math.fsum(sq[:, c]) for c in range(sq.shape[1])], np.float64)
+
+
+def rms_scale_of_sums(sx, sy, n, eps=RMS_EPS) -> np.ndarray:
+    """The float64-sum normaliser's scale (VND_NORMALIZE_RMS: epilogue_reduce_kernel) from float64 sums of squares of
+    the input ``sx`` and of the output ``sy`` over ``n`` frames: float32 means of a float64 division, float32 square
+    roots of the float64 root of each, ``mean_y + eps`` added in float32, and the float64 ratio rounded to float32.
+    Every step is monotone, so sums in an interval give a scale in the interval of its ends' scales."""
+    sx, sy = np.asarray(sx, np.float64), np.asarray(sy, np.float64)
+    with np.errstate(all='ignore'):
+        mean_x = (sx / np.float64(n)).astype(np.float32)
+        mean_y = (sy / np.float64(n)).astype(np.float32)
+        rms_x = np.sqrt(mean_x.astype(np.float64)).astype(np.float32)
+        rms_y = np.sqrt((mean_y + np.float32(eps)).astype(np.float64)).astype(np.float32)
+        return (rms_x.astype(np.float64) / rms_y.astype(np.float64)).astype(np.float32)
+
+
+def rms_sum_error(k, n) -> tuple:
+    """(relative, absolute) bound on a sum of ``n`` squares of float32 values formed as float32 partial sums of at most
+    ``k`` rounded squares each, added in float64: gamma_k = k u / (1 - k u), u = 2^-24, for every order of the partial's
+    additions and with or without fused multiply-adds (Higham, Accuracy and Stability, (3.5)), plus n float64 additions;
+    the absolute term covers squares that underflow in float32 (at most 2^-150 each)."""
+    u, u64 = 2.0 ** -24, 2.0 ** -53
+    rel = k * u / (1 - k * u)
+    rel = rel + (n + 1) * u64 * (1 + rel) / (1 - (n + 1) * u64)
+    return rel, n * 2.0 ** -149
+
+
+def rms_scale_bounds(x, p, k, eps=RMS_EPS):
+    """(lo, exact, hi) float32 scales per channel of VND_NORMALIZE_RMS on input ``x`` and pointwise output ``p`` (both
+    ``(n, C)``, float32): ``exact`` is ``rms_scale_of_sums`` of the correctly rounded sums, ``lo`` / ``hi`` those of the
+    ends of the intervals ``rms_sum_error(k, n)`` puts around them - a device whose float32 partials hold at most ``k``
+    squares applies a scale in [lo, hi]."""
+    n = len(x)
+    sx, sy = exact_sum_squares(x), exact_sum_squares(p)
+    rel, ab = rms_sum_error(k, n)
+    down = lambda s: np.maximum(np.nextafter(s * (1 - rel) - ab, -np.inf), 0.0)
+    up = lambda s: np.nextafter(s * (1 + rel) + ab, np.inf)
+    return (rms_scale_of_sums(down(sx), up(sy), n, eps), rms_scale_of_sums(sx, sy, n, eps),
+            rms_scale_of_sums(up(sx), down(sy), n, eps))

@@ -141,6 +141,11 @@ INTERNAL_SIGNATURES = {
     'vnd_describe_stream_launch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p,
                                                   ctypes.c_int32]),
+    'vnd_debug_decorrelate_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                     ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
+                                                     ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                     _c_i32p]),
 }
 
 # include/vnd_analysis.h: the analysis entry points, bound apart so that SIGNATURES keeps matching vnd_amd.h
@@ -567,6 +572,21 @@ class TapTable:
         _check(fn(self.ctx.handle, self.handle, ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr), batch, n, channels,
                   int(mode), int(bool(ms_encode)), int(width is not None), float(width or 0.0), int(normalize),
                   float(eps), ctypes.c_void_p(workspace_ptr), workspace_bytes, ctypes.c_void_p(stream)), name)
+
+    def decorrelate_device_taken(self, x_ptr: int, y_ptr: int, batch: int, n: int, channels: int, *, mode: int,
+                                 ms_encode: bool, width, normalize: int, workspace_ptr: int, workspace_bytes: int,
+                                 eps: float = 1e-10, stream: int = 0) -> dict:
+        """``decorrelate_device``, and which form of the stage ran (``vnd_debug_decorrelate_f32_dev``; tests only):
+        ``branch`` ('table-order', 'fused', 'q_done' or None when nothing ran), ``conv_path`` (0 a generic kernel, 1 the
+        per-table kernel leaving the sums, 2 the per-table kernel without them), ``numpy_order`` and ``blk_done``."""
+        taken = np.zeros(4, np.int32)
+        _check(self._lib.vnd_debug_decorrelate_f32_dev(
+            self.ctx.handle, self.handle, ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr), batch, n, channels, int(mode),
+            int(bool(ms_encode)), int(width is not None), float(width or 0.0), int(normalize), float(eps),
+            ctypes.c_void_p(workspace_ptr), workspace_bytes, ctypes.c_void_p(stream), _ptr(taken, ctypes.c_int32)),
+            'vnd_debug_decorrelate_f32_dev')
+        branch = {-1: None, 0: 'table-order', 1: 'fused', 2: 'q_done'}[int(taken[0])]
+        return dict(branch=branch, conv_path=int(taken[1]), numpy_order=bool(taken[2]), blk_done=bool(taken[3]))
 
     def convolve_device(self, x_ptr: int, y_ptr: int, batch: int, n: int, channels: int,
                         mode: int = MODE_EXACT, stream: int = 0):

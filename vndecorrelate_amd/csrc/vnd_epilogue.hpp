@@ -9,9 +9,12 @@
 //           precision, deterministic) and forms the per-channel scales;
 //   pass 2  multiplies y by the scales.
 // The reference sums the squares with NumPy's float32 axis-0 reduction, which is a
-// plain sequential sum (relative error ~1e-4 on 10 s of audio); the scale computed
-// here is the correctly rounded one, so the normalised output agrees with the
-// reference to ~2e-4 of peak and with exact arithmetic to float32 rounding.
+// plain sequential sum (relative error ~1e-4 on 10 s of audio).  Here (VND_NORMALIZE_RMS)
+// a lane first adds k squares in float32 (16 per thread in pass 1; 32 / 64 or 2 x pairs
+// per lane in the fused kernels' store phases), then everything is float64: each sum is
+// within gamma_k = k 2^-24 / (1 - k 2^-24) of the exact one - not correctly rounded - so
+// the normalised output agrees with the reference to ~2e-4 of peak and with exact
+// arithmetic to a few float32 ulps of the scale (tests/test_gpu_fast_stage.py).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

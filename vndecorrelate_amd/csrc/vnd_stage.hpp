@@ -179,8 +179,12 @@ static vnd_status stage_sums(vnd_ctx *ctx, StageSetup &s, const float *x, const 
 static vnd_status decorrelate_dev(vnd_ctx *ctx, const vnd_taps *t, const float *x, float *y, int64_t batch,
                                   int64_t n, int32_t Cx, int32_t C, int32_t mode, int32_t ms_encode,
                                   int32_t use_width, double width, int32_t normalize, float eps, void *workspace,
-                                  int64_t workspace_bytes, void *stream_)
+                                  int64_t workspace_bytes, void *stream_, int32_t *taken = nullptr)
 {
+    // taken (tests only, vnd_debug_decorrelate_f32_dev): [0] the branch - 0 table order / separate passes, 1 fused, 2 the quad / octet
+    // kernel's sums (q_done), -1 nothing ran; [1] the convolution launch's EpiFuse::path; [2] the sums in NumPy's order (want_seq);
+    // [3] the store phase left the block sums the NumPy-order sums start from (blk_done)
+    if (taken) taken[0] = -1, taken[1] = taken[2] = taken[3] = 0;
     vnd_status st = check_shape(ctx, t, batch, n, C, mode, Cx);
     if (st != VND_OK) return st;
     if (batch == 0 || n == 0) return VND_OK;
@@ -275,6 +279,7 @@ static vnd_status decorrelate_dev(vnd_ctx *ctx, const vnd_taps *t, const float *
             }
             if (!launched_q) st = launch(ctx, t, x, y, batch, n, C, mode, stream, nullptr, Cx);
         }
+        if (taken) taken[0] = 0, taken[1] = conv_path;
         if (st != VND_OK || !any) return st;
         // reference-order sums (always in VND_MODE_EXACT, C >= 2: the bit-identical stage); C == 1 is
         // summed pairwise by NumPy and keeps the float64 sums.
@@ -286,6 +291,7 @@ static vnd_status decorrelate_dev(vnd_ctx *ctx, const vnd_taps *t, const float *
         sums_pending = seq;
     }
     const bool blk_done = (conv_path == 1 && want_blk) || q_blk_done;
+    if (taken) taken[0] = q_done ? 2 : (fused ? 1 : 0), taken[1] = conv_path, taken[2] = want_seq ? 1 : 0, taken[3] = blk_done ? 1 : 0;
     return stage_sums(ctx, s, x, y, batch, n, Cx, C, normalize, sums_pending, blk_done, stream);
 }
 
@@ -362,6 +368,19 @@ vnd_status vnd_decorrelate_fanout_f32_dev(vnd_ctx *ctx, const vnd_taps *t, const
     if (in_channels <= 0) return fail(VND_ERR_INVALID, "in_channels must be positive");
     return decorrelate_dev(ctx, t, x, y, batch, n, in_channels, t->C, mode, ms_encode, use_width, width, normalize,
                            eps, workspace, workspace_bytes, stream);
+}
+
+// vnd_amd_internal.h: the stage of vnd_decorrelate_fanout_f32_dev, and which of decorrelate_dev's branches it took
+vnd_status vnd_debug_decorrelate_f32_dev(vnd_ctx *ctx, const vnd_taps *t, const float *x, float *y, int64_t batch, int64_t n,
+                                         int32_t in_channels, int32_t mode, int32_t ms_encode, int32_t use_width, double width,
+                                         int32_t normalize, float eps, void *workspace, int64_t workspace_bytes, void *stream,
+                                         int32_t *taken)
+{
+    if (!t) return fail(VND_ERR_INVALID, "null context or tap table");
+    if (in_channels <= 0) return fail(VND_ERR_INVALID, "in_channels must be positive");
+    if (!taken) return fail(VND_ERR_INVALID, "null taken pointer");
+    return decorrelate_dev(ctx, t, x, y, batch, n, in_channels, t->C, mode, ms_encode, use_width, width, normalize,
+                           eps, workspace, workspace_bytes, stream, taken);
 }
 
 vnd_status vnd_decorrelate_fanout_f32_host(vnd_ctx *ctx, const vnd_taps *t, const float *x, float *y,

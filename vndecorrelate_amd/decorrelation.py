@@ -87,7 +87,7 @@ def set_device_epilogue(enabled: Optional[bool]) -> None:
     (~1e-6 of peak).  A single-channel table's sums are NumPy's pairwise ones (8192-sample
     chunks, 128-sample leaves), reproduced the same way; custom normalisers keep the host epilogue.
     ``True``: on the GPU in its fastest form - in MODE_FAST everything fused into the fast
-    kernel with exactly rounded float64 sums, which puts the normalised output ~1e-4
+    kernel with float64 sums of float32 partials (include/vnd_amd.h), which puts the normalised output ~1e-4
     relative from the reference's on long signals (NumPy's sequential sum is that far off).
     ``False``: in NumPy on the host, behind the device convolution."""
     global _device_epilogue
