@@ -234,3 +234,52 @@ def test_invalid_calls_write_nothing(vnd):
     torch.cuda.synchronize(dev)
     assert not bool((y[:, :480] == 5.0).all())
     table.close()
+
+
+# ---- 7. calls ordered across torch streams ----------------------------------------------------
+SPIN_CYCLES = 1_000_000
+
+
+@pytest.mark.parametrize('kind', ['velvet', 'haas', 'correlogram'])
+def test_calls_on_alternating_torch_streams_stay_in_order(vnd, kind):
+    """Every call runs on the other of two side streams, and each call on the first waits behind a spin there, so its
+    state write lands late: the next call, on the second, must still read it.  Exact mode, bit for bit."""
+    import torch
+    from vndecorrelate_amd import _native, analysis
+    from vndecorrelate_amd.streaming import convolve_velvet_noise_stream
+    dev = torch.device('cuda', _native.default_context().device)
+    S, n, top = 4, 6007, 480
+    x = _pool(seed=31, streams=S, n=n)
+    if kind == 'velvet':
+        fir = vnd.generate_velvet_noise(duration_seconds=0.03, num_impulses=30, sample_rate_hz=48000, seed=1)
+        s = convolve_velvet_noise_stream(fir, num_streams=S, max_frames_per_call=top)
+        want = vnd.convolve_velvet_noise_batched(x, fir, mode=vnd.MODE_EXACT)
+    elif kind == 'haas':
+        stage = vnd.HaasEffect(sample_rate_hz=48000, delay_time_seconds=0.0125, delayed_channel=1, mode='MS', width=0.7)
+        s = stage.stream(num_streams=S, max_frames_per_call=top)
+        want = np.stack([stage.decorrelate(x[b]) for b in range(S)])
+    else:
+        s = analysis.cross_correlogram_stream(S, sample_rate_hz=48000, max_frames_per_call=top)
+        want = analysis.correlogram_numpy_batch(x, None, s.window, s.hop, s.num_lags, s.epsilon)
+    rng, sched, left = np.random.default_rng(8), [], n
+    while left > 0:
+        b = int(min(left, rng.choice([0, 1, 97, top, int(rng.integers(1, top + 1))])))
+        sched.append(b)
+        left -= b
+    xt = torch.from_numpy(x).to(dev)
+    sides = (torch.cuda.Stream(dev), torch.cuda.Stream(dev))
+    for side in sides:
+        side.wait_stream(torch.cuda.current_stream(dev))
+    outs, pos = [], 0
+    for k, b in enumerate(sched):
+        with torch.cuda.stream(sides[k % 2]):
+            if k % 2 == 0:
+                torch.cuda._sleep(SPIN_CYCLES)
+            outs.append(s.process(xt[:, pos:pos + b]))
+        pos += b
+    with torch.cuda.stream(sides[len(sched) % 2]):
+        outs.append(s.flush())
+    torch.cuda.synchronize(dev)
+    got = torch.cat(outs, dim=1).cpu().numpy()
+    assert got.dtype == want.dtype and got.shape == want.shape
+    assert got.tobytes() == want.tobytes(), kind

@@ -116,6 +116,20 @@ def test_policy_without_a_gpu(vnd):
     assert np.array_equal(wn.decorrelate(x), _numpy_white_noise(wn, x))
 
 
+def test_forced_device_without_one_runs_uncovered_calls_in_numpy(vnd, monkeypatch):
+    """set_white_noise_device(True) raises only for a call the device covers; the others run the NumPy code."""
+    from vndecorrelate_amd import analysis
+    monkeypatch.setattr(analysis, '_gpu_present', lambda: False)
+    wn = vnd.WhiteNoise(sample_rate_hz=8000, duration_seconds=0.01, seed=3, width=0.5)
+    x = np.random.default_rng(1).standard_normal((1000, 2)).astype(np.float32)
+    xf = np.asfortranarray(x)
+    assert not vnd.white_noise_covers(xf.shape, wn.num_outs, wn.width, wn.white_noise_filter, xf.flags.c_contiguous)
+    vnd.set_white_noise_device(True)
+    assert np.array_equal(wn.decorrelate(xf), _numpy_white_noise(wn, xf))
+    with pytest.raises(RuntimeError, match='no gfx950 device'):
+        wn.decorrelate(x)
+
+
 def test_routing_table(vnd):
     covers = vnd.white_noise_covers
     rng = np.random.default_rng(0)

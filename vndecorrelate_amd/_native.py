@@ -927,3 +927,19 @@ def default_context() -> Context:
     if n > 0:
         dev %= n
     return context_for(dev)
+
+
+def is_torch(x) -> bool:
+    """Whether ``x`` is a torch tensor (without importing torch)."""
+    return type(x).__module__.split('.')[0] == 'torch'
+
+
+def torch_module():
+    """torch, for device buffers and the current stream; ``RuntimeError`` without it or without a GPU."""
+    try:
+        import torch
+    except ImportError as exc:            # pragma: no cover - the image ships torch
+        raise RuntimeError('device-resident chains need torch for device buffers') from exc
+    if not torch.cuda.is_available():
+        raise RuntimeError('device-resident chains need a GPU (torch.cuda.is_available() is False)')
+    return torch

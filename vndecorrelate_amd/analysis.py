@@ -6,7 +6,8 @@ The reference measures decorrelation with ``utils/dsp.py:313`` ``cross_correlogr
 * ``utils.dsp.cross_correlogram`` - the reference's signature; on the device where covered, NumPy otherwise;
 * :func:`cross_correlogram_batched` - ``(B, n)`` pairs, or channel 0 against channel 1 of a ``(B, n, 2)`` signal in
   place; NumPy in, NumPy out (pinned); a float32 torch tensor on the device in, a device tensor out;
-* :func:`set_correlogram_device` and the pure routing rule :func:`correlogram_covers`;
+* :func:`set_correlogram_device` and the pure routing rule :func:`correlogram_covers`; :func:`device_route`, the
+  rule of every ``set_*_device`` switch of the package;
 * :func:`cross_correlogram_stream` - the same rows, block by block, for a pool of live streams
   (``include/vnd_correlogram_stream.h``): a :class:`CorrelogramStream`.
 
@@ -22,10 +23,12 @@ from typing import Optional
 import numpy as np
 
 from . import _native
+from .streaming import BlockStream
 from .utils.dsp import EPSILON, correlogram_sizes, to_float32
 
 MAX_WINDOW = _native.CORRELOGRAM_MAX_WINDOW
 _INT32_MAX = 2 ** 31 - 1
+_torch = _native.torch_module          # the name this module's device paths look torch up by
 
 _correlogram_device: Optional[bool] = None
 
@@ -61,6 +64,7 @@ def correlogram_covers(n_frames: int, window: int, hop: int, num_lags: int, epsi
 
 
 def _gpu_present() -> bool:
+    """The package's one probe for a device: every ``set_*_device`` route (:func:`device_route`) reads it here."""
     try:
         _native.default_context()
         return True
@@ -68,24 +72,26 @@ def _gpu_present() -> bool:
         return False
 
 
+def device_route(setting: Optional[bool], covered: bool, refusal: str) -> bool:
+    """The rule of every ``set_*_device`` switch (this module's, ``set_haas_scan_device``, ``set_white_noise_device``)
+    for one call: ``False``, or a call without a device form (``covered`` False), runs on the host; ``True`` on the
+    device, raising ``RuntimeError(refusal)`` when there is none; ``None`` on the device when one is present."""
+    if setting is False or not covered:
+        return False
+    present = _gpu_present()
+    if setting is True and not present:
+        raise RuntimeError(refusal)
+    return present
+
+
 def use_device(n_frames: int, window: int, hop: int, num_lags: int, epsilon) -> bool:
     """The routing decision of one call: :func:`correlogram_covers` and :func:`set_correlogram_device`."""
-    if _correlogram_device is False or not correlogram_covers(n_frames, window, hop, num_lags, epsilon):
-        return False
-    if _correlogram_device is True:
-        if not _gpu_present():
-            raise RuntimeError('set_correlogram_device(True): no gfx950 device (or no built extension) to run on')
-        return True
-    return _gpu_present()
+    return device_route(_correlogram_device, correlogram_covers(n_frames, window, hop, num_lags, epsilon),
+                        'set_correlogram_device(True): no gfx950 device (or no built extension) to run on')
 
 
 def _windows(n_frames: int, window: int, hop: int) -> int:
     return (n_frames - window) // hop + 1 if n_frames >= window else 0
-
-
-def _torch():
-    from .resident import _torch as get
-    return get()
 
 
 def _launch(torch, ctx, x_ptr: int, y_ptr: int, batch: int, n: int, stream_stride: int, frame_stride: int, window: int,
@@ -149,11 +155,11 @@ def cross_correlogram_batched(x, y=None, *, sample_rate_hz: int = 44100, max_lag
     num_lags = 2 * max_lag + 1
     kw = dict(sample_rate_hz=sample_rate_hz, max_lag_seconds=max_lag_seconds, window_size_seconds=window_size_seconds,
               stride_seconds=stride_seconds, epsilon=epsilon)
-    is_tensor = type(x).__module__.startswith('torch')
+    is_tensor = _native.is_torch(x)
     if is_tensor:
         torch = _torch()
         _check_batch(x, y)
-        if y is not None and (not type(y).__module__.startswith('torch') or y.device != x.device):
+        if y is not None and (not _native.is_torch(y) or y.device != x.device):
             raise ValueError('x and y must be tensors on the same device')
         ctx_device = None
         try:
@@ -191,11 +197,7 @@ def stream_rows(position: int, n_in: int, window: int, hop: int):
     return _windows(position, window, hop), _windows(position + n_in, window, hop)
 
 
-def _is_torch(x) -> bool:
-    return type(x).__module__.split('.')[0] == 'torch'
-
-
-class CorrelogramStream:
+class CorrelogramStream(BlockStream):
     """``cross_correlogram`` of a pool of ``num_streams`` stream pairs, block by block (``cross_correlogram_stream``).
 
     ``process(x, y=None)`` pushes the next block of every stream: ``x`` ``(S, B, 2)`` (channel 0 against channel 1, read in
@@ -214,55 +216,22 @@ class CorrelogramStream:
     on the device: ``set_correlogram_device`` is not consulted, and without a device the first call that needs one
     raises ``RuntimeError``."""
 
+    _noun = 'block'
+
     def __init__(self, num_streams: int, *, window: int, hop: int, num_lags: int, epsilon, max_frames_per_call: int):
-        for name, v in (('num_streams', num_streams), ('max_frames_per_call', max_frames_per_call)):
-            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 1:
-                raise ValueError(f'{name} must be a positive integer, got {v!r}')
-        if num_streams > _native.MAX_STREAMS_PER_CALL:
-            raise ValueError(f'num_streams {num_streams} above {_native.MAX_STREAMS_PER_CALL}: split the pool')
+        super().__init__(num_streams=num_streams, max_frames_per_call=max_frames_per_call)
         if not correlogram_covers(0, window, hop, num_lags, epsilon):
             raise ValueError(f'window {window}, hop {hop}, {num_lags} lags and epsilon {epsilon!r} have no device form '
                              f'(correlogram_covers is False) and the stream has no NumPy one: use cross_correlogram')
-        self.num_streams, self.max_frames_per_call = int(num_streams), int(max_frames_per_call)
         self.window, self.hop, self.num_lags, self.epsilon = int(window), int(hop), int(num_lags), epsilon
-        self._state = None            # (torch uint8 tensor, bytes)
-        self._last_stream = None      # torch stream of the last launch: the next one is ordered after it
-        self._torch_out = None        # device of the last process() that took a tensor: flush() answers in kind
-        self._squeeze_last = True
-        self.position = 0
-        self.flushed = False
 
-    # ---- public ------------------------------------------------------------------------
+    @property
+    def _out_width(self) -> int:
+        return self.num_lags
+
     def process(self, x, y=None):
         """Push the next block of every stream; returns the rows that became final."""
-        if self.flushed:
-            raise RuntimeError('process() after flush(): call reset() to start a new signal')
-        xs, ys, squeeze, is_torch = self._chunk(x, y)
-        self._squeeze_last = squeeze
-        self._torch_out = xs.device if is_torch else None
-        n_in = int(xs.shape[1])
-        first, end = stream_rows(self.position, n_in, self.window, self.hop)
-        if n_in == 0:                                     # nothing to compute or to keep: no device call
-            out = self._empty(0)
-        elif is_torch:
-            out = self._call_device(xs, ys, n_in, end - first)
-        else:
-            out = self._call_host(xs, ys, n_in, end - first)
-        self.position += n_in
-        return out[0] if squeeze else out
-
-    def flush(self):
-        """The rows still held back: none (incomplete windows are dropped); ends the signal."""
-        if self.flushed:
-            raise RuntimeError('flush() after flush(): call reset() to start a new signal')
-        self.flushed = True
-        out = self._empty(0)
-        return out[0] if self.num_streams == 1 and self._squeeze_last else out
-
-    def reset(self):
-        """Start a new signal at position 0 (the ring needs no clearing: it is never read before it is written)."""
-        self.position = 0
-        self.flushed = False
+        return self._process((x, y), False)
 
     # ---- checks --------------------------------------------------------------------------
     def _cast(self, v, is_torch: bool):
@@ -281,8 +250,9 @@ class CorrelogramStream:
         return to_float32(v)
 
     def _chunk(self, x, y):
-        is_torch = _is_torch(x)
-        if y is not None and _is_torch(y) != is_torch:
+        """``((xs, ys), squeeze, is_torch)``: the block as ``(S, B, 2)`` and None, or two ``(S, B)``."""
+        is_torch = _native.is_torch(x)
+        if y is not None and _native.is_torch(y) != is_torch:
             raise ValueError('x and y must both be NumPy arrays or both device tensors')
         xs = self._cast(x, is_torch)
         ys = None if y is None else self._cast(y, is_torch)
@@ -314,63 +284,41 @@ class CorrelogramStream:
                 raise ValueError(f'block of shape {shape} does not match the pool of {S} streams')
         if xs.shape[1] > self.max_frames_per_call:
             raise ValueError(f'{xs.shape[1]} frames in one call, above max_frames_per_call={self.max_frames_per_call}')
-        return xs, ys, squeeze, is_torch
+        return (xs, ys), squeeze, is_torch
+
+    def _lead(self, block):
+        return block[0]
 
     # ---- the device -------------------------------------------------------------------------
-    def _empty(self, rows: int):
-        shape = (self.num_streams, rows, self.num_lags)
-        if self._torch_out is not None:
-            return _torch().empty(shape, dtype=_torch().float32, device=self._torch_out)
-        return np.zeros(shape, np.float32)
+    def _span(self, n_in: int, final: bool):
+        return stream_rows(self.position, n_in, self.window, self.hop)
 
-    def _launch(self, torch, ctx, device, xp: int, yp: int, stream_stride: int, frame_stride: int, n_in: int, rows: int):
-        if self._state is None:
-            need = _native.correlogram_stream_state_bytes(self.num_streams, self.window, self.max_frames_per_call)
-            self._state = (torch.empty((need,), dtype=torch.uint8, device=device), need)
-        state, state_bytes = self._state
-        stream = torch.cuda.current_stream(device)
-        if self._last_stream is not None and self._last_stream != stream:
-            stream.wait_stream(self._last_stream)         # the ring is read and written in call order
-        out = torch.empty((self.num_streams, rows, self.num_lags), dtype=torch.float32, device=device)
-        got = _native.correlogram_stream_device(
-            ctx, state.data_ptr(), state_bytes, self.max_frames_per_call, xp, yp, max(1, stream_stride), frame_stride,
-            out.data_ptr(), self.num_streams, self.position, n_in, window=self.window, hop=self.hop,
-            num_lags=self.num_lags, eps=float(self.epsilon), stream=stream.cuda_stream)
-        assert got == rows, (got, rows)
-        state.record_stream(stream)
-        self._last_stream = stream
-        return out, stream
+    def _state_bytes(self, ctx) -> int:
+        return _native.correlogram_stream_state_bytes(self.num_streams, self.window, self.max_frames_per_call)
 
-    def _call_device(self, xs, ys, n_in: int, rows: int):
-        torch = _torch()
-        ctx = _native.default_context()
-        device = torch.device('cuda', ctx.device)
-        if xs.device != device:
-            raise ValueError(f'block on {xs.device}, the stream runs on {device}')
+    def _launch(self, torch, ctx, state, state_bytes: int, block, out, n_in: int, final: bool, stream):
+        xs, ys = block
         if ys is None:
             if xs.stride(2) != 1 or not 1 <= xs.stride(1) <= _INT32_MAX or (self.num_streams > 1 and xs.stride(0) < 1):
                 xs = xs.contiguous()
-            keep, xp, yp = (xs,), xs.data_ptr(), xs.data_ptr() + 4
+            read, xp, yp = (xs,), xs.data_ptr(), xs.data_ptr() + 4
         else:
             if (xs.stride() != ys.stride() or not 1 <= xs.stride(1) <= _INT32_MAX
                     or (self.num_streams > 1 and xs.stride(0) < 1)):
                 xs, ys = xs.contiguous(), ys.contiguous()
-            keep, xp, yp = (xs, ys), xs.data_ptr(), ys.data_ptr()
-        out, stream = self._launch(torch, ctx, device, xp, yp, xs.stride(0), xs.stride(1), n_in, rows)
-        for t in keep:
-            t.record_stream(stream)
-        return out
+            read, xp, yp = (xs, ys), xs.data_ptr(), ys.data_ptr()
+        got = _native.correlogram_stream_device(
+            ctx, state.data_ptr(), state_bytes, self.max_frames_per_call, xp, yp, max(1, xs.stride(0)), xs.stride(1),
+            out.data_ptr(), self.num_streams, self.position, n_in, window=self.window, hop=self.hop,
+            num_lags=self.num_lags, eps=float(self.epsilon), stream=stream.cuda_stream)
+        return got, read
 
-    def _call_host(self, xs, ys, n_in: int, rows: int):
+    def _call_host(self, block, n_in: int, rows: int, final: bool):
+        """The block goes up, through :meth:`_call_device`, and its rows come back."""
         torch = _torch()
-        ctx = _native.default_context()
-        device = torch.device('cuda', ctx.device)
-        xd = torch.from_numpy(np.ascontiguousarray(xs)).to(device)
-        if ys is None:
-            out_d, _ = self._launch(torch, ctx, device, xd.data_ptr(), xd.data_ptr() + 4, n_in * 2, 2, n_in, rows)
-        else:
-            yd = torch.from_numpy(np.ascontiguousarray(ys)).to(device)
-            out_d, _ = self._launch(torch, ctx, device, xd.data_ptr(), yd.data_ptr(), n_in, 1, n_in, rows)
+        device = torch.device('cuda', _native.default_context().device)
+        up = tuple(None if v is None else torch.from_numpy(np.ascontiguousarray(v)).to(device) for v in block)
+        out_d = self._call_device(up, n_in, rows, final)
         out = _native.pinned_pool.empty(tuple(out_d.shape), np.float32)
         if out.size:
             torch.from_numpy(out).copy_(out_d)

@@ -46,7 +46,7 @@ from typing import Any, Callable, Iterator, List, Optional, Protocol, Sequence
 import numpy as np
 from numpy.typing import NDArray
 
-from . import _native
+from . import _native, analysis
 from .taps import TapArrays, class_path_arrays, concat_tap_arrays, function_path_arrays
 from .utils.dsp import (
     IDENTITY_ENVELOPE,
@@ -151,14 +151,6 @@ def white_noise_covers(shape: Sequence[int], num_outs: int, width, fir, c_contig
     if not 1 <= m <= shape[0] or m > 2 ** 31 - 1:
         return False
     return bool(np.isfinite(fir[:, :num_outs]).all())
-
-
-def _gpu_present() -> bool:
-    try:
-        _native.default_context()
-        return True
-    except RuntimeError:                                  # no built extension, no device, not a gfx950
-        return False
 
 
 def set_default_mode(mode: int) -> None:
@@ -923,12 +915,9 @@ class WhiteNoise(Decorrelator):
         return np.stack([self.decorrelate(sig) for sig in x])
 
     def _on_device(self, shape, c_contiguous: bool) -> bool:
-        if _white_noise_device is False:
-            return False
-        if _white_noise_device and not _gpu_present():
-            raise RuntimeError('set_white_noise_device(True): no gfx950 device (or no built extension) to run WhiteNoise on')
-        return white_noise_covers(shape, self.num_outs, self.width, self.white_noise_filter, c_contiguous) and \
-            (_white_noise_device is True or _gpu_present())
+        return analysis.device_route(
+            _white_noise_device, white_noise_covers(shape, self.num_outs, self.width, self.white_noise_filter, c_contiguous),
+            'set_white_noise_device(True): no gfx950 device (or no built extension) to run WhiteNoise on')
 
     def _device_filter(self, torch, device):
         """The filter's ``num_outs`` columns as a float64 device tensor, uploaded again only when their bytes change."""
@@ -941,8 +930,7 @@ class WhiteNoise(Decorrelator):
 
     def _decorrelate_on_device(self, x: NDArray) -> NDArray:
         """x: C-contiguous float32 ``(B, n, Cx)``, Cx = num_outs or 1 (fanned out to 2)."""
-        from .resident import _torch
-        torch = _torch()
+        torch = _native.torch_module()
         ctx = _native.default_context()
         device = torch.device('cuda', ctx.device)
         batch, n, cx = x.shape

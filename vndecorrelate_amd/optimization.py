@@ -36,7 +36,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 from numpy.typing import NDArray
 
-from . import _native
+from . import _native, analysis
 from . import decorrelation as _dec
 from .bounded import minimize_bounded_lockstep, round_half_even
 from .decorrelation import Decorrelator, HaasEffect, VelvetNoise
@@ -218,16 +218,11 @@ def _haas_delay(d) -> Optional[int]:
     return int(delay)
 
 
-def _haas_route(input_signal) -> bool:
-    """The routing decision of one :func:`grid_scan` call's HaasEffect candidates."""
-    if _haas_scan_device is False or not haas_scan_covers(input_signal):
-        return False
-    from .analysis import _gpu_present
-    if _haas_scan_device is True:
-        if not _gpu_present():
-            raise RuntimeError('set_haas_scan_device(True): no gfx950 device (or no built extension) to run on')
-        return True
-    return _gpu_present()
+def _haas_route(covered: bool = True) -> bool:
+    """The routing decision of one :func:`grid_scan` call's HaasEffect candidates (``covered``:
+    :func:`haas_scan_covers` of its input), or of one :func:`optimize_haas_delay_batched` call."""
+    return analysis.device_route(_haas_scan_device, covered,
+                                 'set_haas_scan_device(True): no gfx950 device (or no built extension) to run on')
 
 
 def _haas_groups(decorrelators: Sequence) -> Dict[Tuple, Tuple[List[int], NDArray, NDArray]]:
@@ -292,7 +287,7 @@ def grid_scan(input_signal: NDArray, decorrelators: Sequence[Decorrelator], **kw
     else:
         on_device = []
     haas = [i for i, d in enumerate(decorrelators) if haas_scan_covers(input_signal, d)]
-    if haas and _haas_route(input_signal):
+    if haas and _haas_route(haas_scan_covers(input_signal)):
         moments = scan_haas_moments(input_signal, [decorrelators[i] for i in haas])
         scores[haas] = scores_from_moments(moments, **kwargs)
         on_device += haas
@@ -510,8 +505,7 @@ class _DevicePairScorer:
 
 def _haas_pool(input_signals):
     """``(pool, is_torch)``: the pool as ``(B, n, C)`` with C = 1 (mono) or 2, after the shape checks."""
-    from .analysis import _is_torch
-    is_torch = _is_torch(input_signals)
+    is_torch = _native.is_torch(input_signals)
     x = input_signals if is_torch else np.asarray(input_signals)
     shape = tuple(x.shape)
     if not (len(shape) == 2 or (len(shape) == 3 and shape[2] == 2)):
@@ -525,17 +519,6 @@ def _haas_pool(input_signals):
     elif x.dtype.kind not in 'biuf':
         raise TypeError(f'signals must be real numbers, got {x.dtype}')
     return x, is_torch
-
-
-def _haas_batched_route() -> bool:
-    if _haas_scan_device is False:
-        return False
-    from .analysis import _gpu_present
-    if _haas_scan_device is True:
-        if not _gpu_present():
-            raise RuntimeError('set_haas_scan_device(True): no gfx950 device (or no built extension) to run on')
-        return True
-    return _gpu_present()
 
 
 def optimize_haas_delay_batched(*, input_signals, sample_rate_hz: int, max_delay_seconds, grid_size: int = 400,
@@ -566,7 +549,7 @@ def optimize_haas_delay_batched(*, input_signals, sample_rate_hz: int, max_delay
     if batch == 0:
         last_haas_search = HaasSearchStats(route='none', signals=0)
         return np.zeros(0, np.float64)
-    if not _haas_batched_route():
+    if not _haas_route():
         if is_torch:
             x = x.detach().cpu().numpy()
         stats = HaasSearchStats(route='host', signals=batch)

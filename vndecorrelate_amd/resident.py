@@ -35,16 +35,6 @@ from . import _native
 from .utils.dsp import LayoutMode, rms_normalize, to_float32
 
 
-def _torch():
-    try:
-        import torch
-    except ImportError as exc:            # pragma: no cover - the image ships torch
-        raise RuntimeError('device-resident chains need torch for device buffers') from exc
-    if not torch.cuda.is_available():
-        raise RuntimeError('device-resident chains need a GPU (torch.cuda.is_available() is False)')
-    return torch
-
-
 transfers = {'to_host': 0, 'to_device': 0}      # of the last run(): downloads / uploads of the signal
 
 
@@ -167,7 +157,7 @@ def run(stages: Sequence, input_signal: np.ndarray, pool: Optional[BufferPool] =
     ``pool``: the calling chain's buffers (a stage's output stays valid until that stage runs again:
     the result handed back to the caller is a host copy)."""
     from . import decorrelation as dec
-    torch = _torch()
+    torch = _native.torch_module()
     pool = pool or BufferPool()
     transfers['to_host'] = transfers['to_device'] = 0
     device = torch.device('cuda', _native.default_context().device)

@@ -43,27 +43,143 @@ def output_span(position: int, n_in: int, latency: int, final: bool) -> Tuple[in
     return first, end
 
 
-def _is_torch(x) -> bool:
-    return type(x).__module__.split('.')[0] == 'torch'
+def _check_counts(**counts):
+    """Each of ``counts`` (in order) a positive integer, else ``ValueError`` naming it."""
+    for name, v in counts.items():
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(f'{name} must be a positive integer, got {v!r}')
 
 
-class Stream:
+class BlockStream:
+    """What every block stream shares: a pool of ``num_streams`` streams advancing in lockstep, ``0 <= B <=
+    max_frames_per_call`` frames per call; ``process`` returns the outputs that became final, ``flush()`` the rest and
+    ends the signal (``process`` raises ``RuntimeError`` after it until ``reset()``), answering in kind - a device tensor
+    after a device block, unbatched after an unbatched one.  The state lives in device memory (torch), allocated on first
+    use.  Every device call of a stream is ordered after its previous one, whatever torch stream each runs on; a host
+    call waits for a pending device call.
+
+    A subclass gives its block rules (``_chunk``: ``(block, squeeze, is_torch)``), its
+    output span (``_span``), dtype (``_out_dtype``) and width (``_out_width``), its state size (``_state_bytes``), its
+    native device call (``_launch``) and its host path (``_call_host``)."""
+
+    _out_dtype = np.float32
+    _noun = 'chunk'                   # what the error messages call one call's input
+    _squeeze_last = True
+
+    def __init__(self, **counts):
+        """``counts``: ``num_streams``, ``max_frames_per_call`` and the stream's other sizes, each a positive integer."""
+        _check_counts(**counts)
+        for name, v in counts.items():
+            setattr(self, name, int(v))
+        if self.num_streams > _native.MAX_STREAMS_PER_CALL:
+            raise ValueError(f'num_streams {self.num_streams} above {_native.MAX_STREAMS_PER_CALL}: split the pool')
+        self._state = None            # (torch uint8 tensor, bytes)
+        self._last_stream = None      # torch stream of the last device call: the next call is ordered after it
+        self._torch_out = False       # the last process() took a device tensor: flush() answers in kind
+        self.position = 0
+        self.flushed = False
+
+    # ---- public ------------------------------------------------------------------------
+    def flush(self):
+        """The outputs still held back; ends the signal."""
+        if self.flushed:
+            raise RuntimeError('flush() after flush(): call reset() to start a new signal')
+        return self._push(None, self._torch_out, self.num_streams == 1 and self._squeeze_last, final=True)
+
+    def reset(self):
+        """Start a new signal at position 0 (the state needs no clearing: it is never read before it is written)."""
+        self.position = 0
+        self.flushed = False
+
+    # ---- the lifecycle -----------------------------------------------------------------------
+    def _process(self, args, final: bool):
+        if self.flushed:
+            raise RuntimeError('process() after flush(): call reset() to start a new signal')
+        block, squeeze, is_torch = self._chunk(*args)
+        self._squeeze_last, self._torch_out = squeeze, is_torch
+        return self._push(block, is_torch, squeeze, final)
+
+    def _push(self, block, on_device: bool, squeeze: bool, final: bool):
+        """One checked block (None: no frames) through the stream, on the device or the host."""
+        lead = None if block is None else self._lead(block)
+        n_in = 0 if lead is None else int(lead.shape[1])
+        first, end = self._span(n_in, final)
+        if n_in == 0 and end == first:                    # nothing to compute or to keep: no device call
+            out = self._empty(on_device, lead)
+        elif on_device:
+            out = self._call_device(block, n_in, end - first, final)
+        else:
+            out = self._call_host(block, n_in, end - first, final)
+        self.position += n_in
+        if final:
+            self.flushed = True
+        return out[0] if squeeze else out
+
+    def _lead(self, block):
+        """The array of a block that carries its frame count and device."""
+        return block
+
+    def _empty(self, on_device: bool, lead):
+        shape = (self.num_streams, 0, self._out_width)
+        if on_device:
+            torch = _native.torch_module()
+            device = lead.device if lead is not None else torch.device('cuda', _native.default_context().device)
+            return torch.empty(shape, dtype=getattr(torch, self._out_dtype.__name__), device=device)
+        return np.zeros(shape, self._out_dtype)
+
+    # ---- the device -------------------------------------------------------------------------
+    def _ensure_state(self, torch, ctx):
+        if self._state is None:
+            need = self._state_bytes(ctx)
+            buf = torch.empty((max(need, 1),), dtype=torch.uint8, device=torch.device('cuda', ctx.device))
+            self._state = (buf, need)
+        return self._state
+
+    def _wait_for_last(self):
+        """A host call: wait for this stream's pending device call."""
+        if self._last_stream is not None:
+            self._last_stream.synchronize()
+            self._last_stream = None
+
+    def _call_device(self, block, n_in: int, n_out: int, final: bool):
+        torch = _native.torch_module()
+        ctx = _native.default_context()
+        device = torch.device('cuda', ctx.device)
+        lead = None if block is None else self._lead(block)
+        if lead is not None and lead.device != device:
+            raise ValueError(f'{self._noun} on {lead.device}, the stream runs on {device}')
+        state, state_bytes = self._ensure_state(torch, ctx)
+        stream = torch.cuda.current_stream(device)
+        last = self._last_stream
+        if last is not None and last.cuda_stream != stream.cuda_stream:
+            stream.wait_stream(last)                      # the state is read and written in call order
+        out = torch.empty((self.num_streams, n_out, self._out_width), dtype=getattr(torch, self._out_dtype.__name__),
+                          device=device)
+        got, read = self._launch(torch, ctx, state, state_bytes, block, out, n_in, final, stream)
+        assert got == n_out, (got, n_out)
+        for t in read:
+            if t.numel():
+                t.record_stream(stream)
+        state.record_stream(stream)
+        self._last_stream = stream
+        return out
+
+
+class Stream(BlockStream):
     """A pool of ``num_streams`` streams through one tap table, advancing in lockstep.
 
     ``process(x)``: ``x`` is ``(B, in_channels)`` (a pool of one stream; ``(B,)`` as well when ``in_channels == 1``) or
     ``(num_streams, B, in_channels)``, with ``0 <= B <= max_frames_per_call`` free to change from call to call; returns
     ``(n_out, C)`` or ``(num_streams, n_out, C)``.  ``flush()``: the remaining frames; ``process`` raises ``RuntimeError``
-    after it until ``reset()``.  ``latency_frames``: ``H``.  Nothing touches the device until frames need computing."""
+    after it until ``reset()``.  ``latency_frames``: ``H``.  Nothing touches the device until frames need computing.
+    Every device call is ordered after the stream's previous call, whatever torch stream each one runs on."""
+
+    _host_entry, _dev_entry = 'vnd_stream_f32_host', 'vnd_stream_f32_dev'
 
     def __init__(self, arrays: TapArrays, *, num_streams: int, in_channels: int, mode: int, max_frames_per_call: int,
                  ms_encode: bool = False, width: Optional[float] = None, any_dtype: bool = False,
                  one_shot: str = 'convolve_velvet_noise'):
-        for name, v in (('num_streams', num_streams), ('in_channels', in_channels),
-                        ('max_frames_per_call', max_frames_per_call)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
-                raise ValueError(f'{name} must be a positive integer, got {v!r}')
-        if num_streams > _native.MAX_STREAMS_PER_CALL:
-            raise ValueError(f'num_streams {num_streams} above {_native.MAX_STREAMS_PER_CALL}: split the pool')
+        super().__init__(num_streams=num_streams, in_channels=in_channels, max_frames_per_call=max_frames_per_call)
         if mode not in MODES:
             raise ValueError(f'unknown mode {mode!r}')
         channels = arrays.num_channels
@@ -72,47 +188,24 @@ class Stream:
         if (ms_encode or width is not None) and channels != 2:
             raise ValueError('the side-channel encode and the width need 2 output channels, '
                              f'the table has {channels}')
-        self.arrays = arrays
-        self.num_streams, self.in_channels, self.num_channels = int(num_streams), int(in_channels), channels
-        self.mode, self.max_frames_per_call = int(mode), int(max_frames_per_call)
+        self.arrays, self.num_channels, self.mode = arrays, channels, int(mode)
         self.ms_encode, self.width = bool(ms_encode), width
         self.latency_frames = int(arrays.tap_index.max()) if len(arrays.tap_index) else 0
         self._any_dtype, self._one_shot = any_dtype, one_shot
         self._table = None
-        self._state = None            # (torch uint8 tensor, bytes)
-        self._pending = None          # torch stream of the last device call (a host call waits for it)
-        self._torch_out = False       # the last process() took a torch tensor: flush() answers in kind
-        self.position = 0
-        self.flushed = False
 
-    _out_dtype = np.float32
+    @property
+    def _out_width(self) -> int:
+        return self.num_channels
 
-    # ---- public ------------------------------------------------------------------------
     def process(self, x, *, final: bool = False):
         """Push the next block of every stream; returns the outputs that became final.  ``final=True``: ``x`` is the last
         block, and the outputs ``flush()`` would return come with it, in one device call; the signal ends."""
-        if self.flushed:
-            raise RuntimeError('process() after flush(): call reset() to start a new signal')
-        x3, squeeze, is_torch = self._chunk(x)
-        self._torch_out = is_torch
-        return self._call(x3, is_torch, squeeze, final=bool(final))
-
-    def flush(self):
-        """The outputs still held back (the last ``latency_frames`` of every stream, or fewer); ends the signal."""
-        if self.flushed:
-            raise RuntimeError('flush() after flush(): call reset() to start a new signal')
-        return self._call(None, self._torch_out, self.num_streams == 1 and self._squeeze_last, final=True)
-
-    def reset(self):
-        """Start a new signal at position 0 (the state needs no clearing: it is never read before it is written)."""
-        self.position = 0
-        self.flushed = False
-
-    _squeeze_last = True
+        return self._process((x,), bool(final))
 
     # ---- checks --------------------------------------------------------------------------
     def _chunk(self, x):
-        is_torch = _is_torch(x)
+        is_torch = _native.is_torch(x)
         if is_torch:
             import torch
             if not x.is_cuda:
@@ -149,97 +242,54 @@ class Stream:
             raise ValueError(f'chunk of shape {shape} does not match the pool: {S} streams of {cx} channels')
         if x3.shape[1] > self.max_frames_per_call:
             raise ValueError(f'{x3.shape[1]} frames in one call, above max_frames_per_call={self.max_frames_per_call}')
-        self._squeeze_last = squeeze
         return x3, squeeze, is_torch
 
-    # ---- the device -------------------------------------------------------------------------
-    def _ensure(self, torch, device_index: int):
-        if self._table is None:
-            a = self.arrays
-            self._table = _native.TapTable.create(_native.default_context(), a.tap_offsets, a.tap_index, a.tap_weight,
-                                                  **a.kwargs())
-        if self._state is None:
-            need = ctypes.c_int64()
-            _native._check(self._table._lib.vnd_stream_state_bytes(self._table.handle, self.num_streams, self.in_channels,
-                                                                   self.max_frames_per_call, ctypes.byref(need)),
-                           'vnd_stream_state_bytes')
-            buf = torch.empty((max(need.value, 1),), dtype=torch.uint8, device=torch.device('cuda', device_index))
-            self._state = (buf, need.value)
-        return self._table, self._state
-
-    def _call(self, x3, is_torch: bool, squeeze: bool, final: bool):
-        n_in = 0 if x3 is None else int(x3.shape[1])
-        first, end = self._span(n_in, final)
-        n_out = end - first
-        S, C = self.num_streams, self.num_channels
-        if n_in == 0 and n_out == 0:                      # nothing to compute or to keep: no device call
-            out = self._empty(is_torch, x3)
-        elif is_torch:
-            out = self._call_device(x3, n_in, n_out, final)
-        else:
-            out = self._call_host(x3, n_in, n_out, final)
-        self.position += n_in
-        if final:
-            self.flushed = True
-        return out[0] if squeeze else out
-
+    # ---- the native entries ------------------------------------------------------------------
     def _span(self, n_in: int, final: bool) -> Tuple[int, int]:
         return output_span(self.position, n_in, self.latency_frames, final)
 
-    def _empty(self, is_torch: bool, x3):
-        shape = (self.num_streams, 0, self.num_channels)
-        if is_torch:
-            import torch
-            device = x3.device if x3 is not None else torch.device('cuda', _native.default_context().device)
-            return torch.empty(shape, dtype=getattr(torch, np.dtype(self._out_dtype).name), device=device)
-        return np.zeros(shape, self._out_dtype)
+    def _head(self, ctx):
+        """The native entries' arguments before the state (the table is made with the state)."""
+        return ctx.handle, self._table.handle
 
     def _tail(self, n_in: int, final: bool):
+        """The native entries' arguments after the output pointer."""
         return (self.num_streams, self.position, n_in, self.in_channels, int(final), self.mode, int(self.ms_encode),
                 int(self.width is not None), float(self.width or 0.0))
 
+    def _state_bytes(self, ctx) -> int:
+        a = self.arrays
+        self._table = _native.TapTable.create(ctx, a.tap_offsets, a.tap_index, a.tap_weight, **a.kwargs())
+        need = ctypes.c_int64()
+        _native._check(ctx._lib.vnd_stream_state_bytes(self._table.handle, self.num_streams, self.in_channels,
+                                                       self.max_frames_per_call, ctypes.byref(need)),
+                       'vnd_stream_state_bytes')
+        return need.value
+
+    def _entry(self, ctx, name: str, state, state_bytes: int, x_ptr: int, y_ptr: int, n_in: int, final: bool, *stream):
+        got = ctypes.c_int64()
+        _native._check(getattr(ctx._lib, name)(
+            *self._head(ctx), ctypes.c_void_p(state.data_ptr()), state_bytes, self.max_frames_per_call,
+            ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr), *self._tail(n_in, final), ctypes.byref(got), *stream), name)
+        return got.value
+
     def _call_host(self, x3, n_in: int, n_out: int, final: bool):
-        from .resident import _torch
-        torch = _torch()
         ctx = _native.default_context()
-        table, (state, state_bytes) = self._ensure(torch, ctx.device)
-        if self._pending is not None:                     # a device call of this stream may still run on its stream
-            self._pending.synchronize()
-            self._pending = None
+        state, state_bytes = self._ensure_state(_native.torch_module(), ctx)
+        self._wait_for_last()
         x = np.ascontiguousarray(x3, np.float32) if x3 is not None else np.zeros((self.num_streams, 0, self.in_channels),
                                                                                  np.float32)
-        y = np.empty((self.num_streams, n_out, self.num_channels), np.float32)
-        got = ctypes.c_int64()
-        _native._check(table._lib.vnd_stream_f32_host(
-            ctx.handle, table.handle, ctypes.c_void_p(state.data_ptr()), state_bytes, self.max_frames_per_call,
-            ctypes.c_void_p(x.ctypes.data), ctypes.c_void_p(y.ctypes.data), *self._tail(n_in, final), ctypes.byref(got)),
-            'vnd_stream_f32_host')
-        assert got.value == n_out, (got.value, n_out)
+        y = np.empty((self.num_streams, n_out, self.num_channels), self._out_dtype)
+        got = self._entry(ctx, self._host_entry, state, state_bytes, x.ctypes.data, y.ctypes.data, n_in, final)
+        assert got == n_out, (got, n_out)
         return y
 
-    def _call_device(self, x3, n_in: int, n_out: int, final: bool):
-        from .resident import _torch
-        torch = _torch()
-        ctx = _native.default_context()
-        device = torch.device('cuda', ctx.device)
-        if x3 is not None and x3.device != device:
-            raise ValueError(f'chunk on {x3.device}, the stream runs on {device}')
-        table, (state, state_bytes) = self._ensure(torch, ctx.device)
-        stream = torch.cuda.current_stream(device)
+    def _launch(self, torch, ctx, state, state_bytes: int, x3, y, n_in: int, final: bool, stream):
         x = x3.contiguous() if x3 is not None else torch.empty((self.num_streams, 0, self.in_channels),
-                                                               dtype=torch.float32, device=device)
-        y = torch.empty((self.num_streams, n_out, self.num_channels), dtype=torch.float32, device=device)
-        got = ctypes.c_int64()
-        _native._check(table._lib.vnd_stream_f32_dev(
-            ctx.handle, table.handle, ctypes.c_void_p(state.data_ptr()), state_bytes, self.max_frames_per_call,
-            ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(y.data_ptr()), *self._tail(n_in, final), ctypes.byref(got),
-            ctypes.c_void_p(stream.cuda_stream)), 'vnd_stream_f32_dev')
-        assert got.value == n_out, (got.value, n_out)
-        if x.numel():
-            x.record_stream(stream)
-        state.record_stream(stream)
-        self._pending = stream
-        return y
+                                                               dtype=torch.float32, device=y.device)
+        got = self._entry(ctx, self._dev_entry, state, state_bytes, x.data_ptr(), y.data_ptr(), n_in, final,
+                          ctypes.c_void_p(stream.cuda_stream))
+        return got, (x,)
 
 
 def convolve_velvet_noise_stream(velvet_noise_filters, *, num_streams: int = 1, in_channels: Optional[int] = None,
@@ -251,7 +301,7 @@ def convolve_velvet_noise_stream(velvet_noise_filters, *, num_streams: int = 1, 
 
     A float64 filter raises ``TypeError``, and so do float64 and int32 / int64 chunks: NumPy multiplies those in float64,
     which the one-shot call repeats through its promoting kernel and the stream does not."""
-    if _is_torch(velvet_noise_filters):
+    if _native.is_torch(velvet_noise_filters):
         raise TypeError('the filter is a host array (NumPy), as for convolve_velvet_noise')
     fir = np.asarray(velvet_noise_filters)
     if fir.dtype != np.float32:
@@ -286,87 +336,35 @@ class HaasStream(Stream):
     ``(n,)`` signal.  Chunks of any real dtype are cast to float32 first, as ``decorrelate`` casts its input."""
 
     _out_dtype = np.float64
+    _host_entry, _dev_entry = 'vnd_haas_stream_f64_host', 'vnd_haas_stream_f64_dev'
+    _any_dtype, _one_shot = True, 'HaasEffect.decorrelate'
+    num_channels = 2
 
     def __init__(self, *, num_streams: int, in_channels: int, max_frames_per_call: int, delay: int,
                  delayed_channel: int, ms_mode: bool, width: Optional[float]):
-        for name, v in (('num_streams', num_streams), ('in_channels', in_channels),
-                        ('max_frames_per_call', max_frames_per_call)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
-                raise ValueError(f'{name} must be a positive integer, got {v!r}')
-        if num_streams > _native.MAX_STREAMS_PER_CALL:
-            raise ValueError(f'num_streams {num_streams} above {_native.MAX_STREAMS_PER_CALL}: split the pool')
+        BlockStream.__init__(self, num_streams=num_streams, in_channels=in_channels,
+                             max_frames_per_call=max_frames_per_call)
         if in_channels not in (1, 2):
             raise ValueError(f'HaasEffect streams a mono (1) or stereo (2) signal, got in_channels={in_channels}')
-        self.num_streams, self.in_channels, self.num_channels = int(num_streams), int(in_channels), 2
-        self.max_frames_per_call = int(max_frames_per_call)
         self.delay, self.delayed_channel, self.ms_mode, self.width = int(delay), int(delayed_channel), bool(ms_mode), width
         self.latency_frames, self.tail_frames = 0, self.delay
-        self._any_dtype, self._one_shot = True, 'HaasEffect.decorrelate'
-        self._state = None
-        self._pending = None
-        self._torch_out = False
-        self.position = 0
-        self.flushed = False
 
     def _span(self, n_in: int, final: bool) -> Tuple[int, int]:
         return haas_output_span(self.position, n_in, self.delay, final)
 
-    def _ensure(self, torch, device_index: int):
-        if self._state is None:
-            need = ctypes.c_int64()
-            _native._check(_native.load_library().vnd_haas_stream_state_bytes(
-                self.num_streams, self.in_channels, self.delay, self.max_frames_per_call, ctypes.byref(need)),
-                'vnd_haas_stream_state_bytes')
-            buf = torch.empty((max(need.value, 1),), dtype=torch.uint8, device=torch.device('cuda', device_index))
-            self._state = (buf, need.value)
-        return self._state
+    def _head(self, ctx):
+        return (ctx.handle,)
 
-    def _args(self, n_in: int, final: bool):
+    def _tail(self, n_in: int, final: bool):
         return (self.num_streams, self.position, n_in, self.in_channels, int(final), self.delay, self.delayed_channel,
                 int(self.ms_mode), int(self.width is not None), float(self.width or 0.0))
 
-    def _call_host(self, x3, n_in: int, n_out: int, final: bool):
-        from .resident import _torch
-        torch = _torch()
-        ctx = _native.default_context()
-        state, state_bytes = self._ensure(torch, ctx.device)
-        if self._pending is not None:                     # a device call of this stream may still run on its stream
-            self._pending.synchronize()
-            self._pending = None
-        x = np.ascontiguousarray(x3, np.float32) if x3 is not None else np.zeros((self.num_streams, 0, self.in_channels),
-                                                                                 np.float32)
-        y = np.empty((self.num_streams, n_out, 2), np.float64)
-        got = ctypes.c_int64()
-        _native._check(ctx._lib.vnd_haas_stream_f64_host(
-            ctx.handle, ctypes.c_void_p(state.data_ptr()), state_bytes, self.max_frames_per_call,
-            ctypes.c_void_p(x.ctypes.data), ctypes.c_void_p(y.ctypes.data), *self._args(n_in, final), ctypes.byref(got)),
-            'vnd_haas_stream_f64_host')
-        assert got.value == n_out, (got.value, n_out)
-        return y
-
-    def _call_device(self, x3, n_in: int, n_out: int, final: bool):
-        from .resident import _torch
-        torch = _torch()
-        ctx = _native.default_context()
-        device = torch.device('cuda', ctx.device)
-        if x3 is not None and x3.device != device:
-            raise ValueError(f'chunk on {x3.device}, the stream runs on {device}')
-        state, state_bytes = self._ensure(torch, ctx.device)
-        stream = torch.cuda.current_stream(device)
-        x = x3.contiguous() if x3 is not None else torch.empty((self.num_streams, 0, self.in_channels),
-                                                               dtype=torch.float32, device=device)
-        y = torch.empty((self.num_streams, n_out, 2), dtype=torch.float64, device=device)
-        got = ctypes.c_int64()
-        _native._check(ctx._lib.vnd_haas_stream_f64_dev(
-            ctx.handle, ctypes.c_void_p(state.data_ptr()), state_bytes, self.max_frames_per_call,
-            ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(y.data_ptr()), *self._args(n_in, final), ctypes.byref(got),
-            ctypes.c_void_p(stream.cuda_stream)), 'vnd_haas_stream_f64_dev')
-        assert got.value == n_out, (got.value, n_out)
-        if x.numel():
-            x.record_stream(stream)
-        state.record_stream(stream)
-        self._pending = stream
-        return y
+    def _state_bytes(self, ctx) -> int:
+        need = ctypes.c_int64()
+        _native._check(ctx._lib.vnd_haas_stream_state_bytes(self.num_streams, self.in_channels, self.delay,
+                                                            self.max_frames_per_call, ctypes.byref(need)),
+                       'vnd_haas_stream_state_bytes')
+        return need.value
 
 
 class StagePlan(NamedTuple):
@@ -397,10 +395,7 @@ class ChainStream:
 
     def __init__(self, stages, *, num_streams: int = 1, in_channels: int = 2, mode: int = _native.MODE_EXACT,
                  max_frames_per_call: int = 4800):
-        for name, v in (('num_streams', num_streams), ('in_channels', in_channels),
-                        ('max_frames_per_call', max_frames_per_call)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
-                raise ValueError(f'{name} must be a positive integer, got {v!r}')
+        _check_counts(num_streams=num_streams, in_channels=in_channels, max_frames_per_call=max_frames_per_call)
         if mode not in MODES:
             raise ValueError(f'unknown mode {mode!r}')
         if not stages:
@@ -472,8 +467,7 @@ class ChainStream:
         self.transfers = {'to_device': 0, 'to_host': 0}
         self._torch_out, self._squeeze = is_torch, squeeze
         if not is_torch:
-            from .resident import _torch
-            torch = _torch()
+            torch = _native.torch_module()
             x3 = torch.from_numpy(np.ascontiguousarray(x3)).to(torch.device('cuda', _native.default_context().device))
             self.transfers['to_device'] += 1
         self.position += int(x3.shape[1])
@@ -499,7 +493,7 @@ class ChainStream:
         for stream in self.streams:                      # device tensors from stage to stage, on the current stream
             if buf is not None:
                 buf, _, _ = stream._chunk(buf)           # a float64 Haas output is cast to float32 here, on the device
-            buf = stream._call(buf, True, False, final)
+            buf = stream._push(buf, True, False, final)
         if not self._torch_out:
             buf = buf.cpu().numpy()
             self.transfers['to_host'] += 1
