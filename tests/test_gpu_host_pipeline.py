@@ -1,5 +1,5 @@
 """GPU tier: the synchronous host API's pipelines.  A few long streams are cut in TIME (upload || kernel || download
-over pieces of one stream, csrc/vnd_amd.hip: host_time_pipeline): the seams must not show - bit-identical to the
+over pieces of one stream, csrc/vnd_host.hpp: host_time_pipeline): the seams must not show - bit-identical to the
 oracle in exact mode, whatever the length, channel count or batch."""
 import numpy as np
 import pytest

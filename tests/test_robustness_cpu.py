@@ -100,18 +100,38 @@ def test_table_cache_is_thread_safe(monkeypatch):
 
 def test_host_entry_points_take_the_context_lock():
     """Every *_host entry point of the C ABI serialises on the context (source-level check; the
-    behaviour is exercised on the GPU by tests/test_gpu_robustness.py)."""
+    behaviour is exercised on the GPU by tests/test_gpu_robustness.py).  The lock is taken in one place, the
+    HostCall helper every host call runs on, which also waits for the call's streams on every way out."""
     import re
     # (the library's one translation unit: vnd_amd.hip and the parts it includes)
-    text = '\n'.join((REPO / 'vndecorrelate_amd' / 'csrc' / f).read_text() for f in ('vnd_amd.hip', 'vnd_host.hpp', 'vnd_stage.hpp', 'vnd_rccl.hpp', 'vnd_hooks.hpp'))
-    header = re.sub(r'/\*.*?\*/', '', (REPO / 'include' / 'vnd_amd.h').read_text(), flags=re.S)
-    host_fns = sorted(set(re.findall(r'\b(vnd_[a-z0-9_]+_host)\s*\(', header)))
-    assert len(host_fns) >= 7
+    csrc = REPO / 'vndecorrelate_amd' / 'csrc'
+    text = '\n'.join(f.read_text() for f in sorted(csrc.glob('*.hip')) + sorted(csrc.glob('*.hpp')))
+    headers = '\n'.join(f.read_text() for f in sorted((REPO / 'include').glob('*.h')))
+    headers = re.sub(r'/\*.*?\*/', '', headers, flags=re.S)
+    host_fns = sorted(set(re.findall(r'\b(vnd_[a-z0-9_]+_host)\s*\(', headers)))
+    assert len(host_fns) >= 11
+    helper = re.search(r'\nclass HostCall \{\n(.*?)\n\};\n', text, re.S).group(1)
+    assert 'HostLock lock_;' in helper and 'lock_(c->host_mutex)' in helper
+    assert '~HostCall() { drain(); }' in helper and 'hipStreamSynchronize' in helper
+    assert text.count('host_mutex)') == 1                   # nobody else takes it, or takes it twice
+    takes_lock = 'HostCall call(ctx);'
     # each one either locks itself or forwards to a static helper that does
-    locked_helpers = set()
-    for m in re.finditer(r'static vnd_status (\w+_host)\(.*?\n\{(.*?)\n\}\n', text, re.S):
-        if 'HostLock lock(ctx->host_mutex)' in m.group(2):
-            locked_helpers.add(m.group(1))
+    bodies = {m.group(1): m.group(2) for m in re.finditer(r'static vnd_status (\w+_host)\(.*?\n\{(.*?)\n\}\n', text, re.S)}
+    locked_helpers = {name for name, body in bodies.items() if takes_lock in body}
     for fn in host_fns:
-        body = re.search(r'vnd_status ' + fn + r'\(.*?\n\{(.*?)\n\}\n', text, re.S).group(1)
-        assert 'HostLock lock(ctx->host_mutex)' in body or any(h + '(' in body for h in locked_helpers), fn
+        bodies[fn] = re.search(r'vnd_status ' + fn + r'\(.*?\n\{(.*?)\n\}\n', text, re.S).group(1)
+        assert takes_lock in bodies[fn] or any(h + '(' in bodies[fn] for h in locked_helpers), fn
+    # once the helper exists, every way out is its exit: no return of another kind, no synchronise of the call's own
+    # (the callables handed to the helper return to the helper: cut out before the search)
+    checked = 0
+    for fn, body in bodies.items():
+        if takes_lock not in body:
+            continue
+        after = re.sub(r'\[&\] \{ return [^;]*; \}\);', '', body[body.index(takes_lock):])            # one statement
+        after = re.sub(r'\[&\][^\n]*\{\n.*?\n {4,}\}\);', '', after, flags=re.S)                        # a block
+        assert '[&]' not in after, fn
+        assert 'hipStreamSynchronize' not in after and 'HIP_TRY' not in after, fn
+        returns = re.findall(r'\n\s+return ([^;]*);', after)
+        assert returns and all(r.startswith('call.finish(') for r in returns), (fn, returns)
+        checked += 1
+    assert checked >= 8

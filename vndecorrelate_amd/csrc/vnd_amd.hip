@@ -3,7 +3,7 @@
 // vnd_spec_kernel.inc, vnd_epilogue.hpp, vnd_moments.hpp, vnd_haas.hpp, vnd_dense.hpp,
 // vnd_correlogram.hpp, vnd_haas_scan.hpp).  Parts:
 //   vnd_objects.hpp  context, tap table, error channel            vnd_plan.hpp   which kernel, how the work is cut, launch
-//   vnd_host.hpp     *_host entry points (pipelined staging)       vnd_stage.hpp  decorrelate stage, promoted operands, scan, Haas
+//   vnd_host.hpp     HostCall: what every *_host call runs on       vnd_stage.hpp  decorrelate stage, promoted operands, scan, Haas
 //   vnd_rccl.hpp     shard ranges, the tap table over RCCL         vnd_hooks.hpp  measurement / tuning / diagnosis hooks
 //   vnd_dense.hpp    WhiteNoise: the dense float64 FIR and its stage
 //   vnd_correlogram.hpp  cross_correlogram (include/vnd_analysis.h)
@@ -87,9 +87,9 @@ vnd_status vnd_ctx_destroy(vnd_ctx *c)
 {
     if (!c) return VND_OK;
     DeviceScope on(c->device);
-    if (c->scratch_x) (void)hipFree(c->scratch_x);
-    if (c->scratch_y) (void)hipFree(c->scratch_y);
-    if (c->work) (void)hipFree(c->work);
+    c->scratch_x.release();
+    c->scratch_y.release();
+    c->work.release();
     if (c->pace) (void)hipFree(c->pace);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
@@ -333,39 +333,30 @@ static vnd_status describe(vnd_ctx *ctx, const vnd_taps *t, int64_t batch, int64
     if (st != VND_OK) return st;
     if (!text || len <= 0) return fail(VND_ERR_INVALID, "null text buffer");
     // the pointers only decide alignment: describe the launch of 256-byte-aligned buffers (hipMalloc's)
-    for (int attempt = 0; attempt < 8; ++attempt) {
-        const SpecPlan sp = make_spec_plan(ctx, t, nullptr, nullptr, batch, n, C, Cx, mode, nullptr);
-        if (!sp.use) break;
-        DeviceScope on(ctx->device);
-        SpecModule *m = spec_module(ctx, t, sp.cfg, !sp.eager);
-        if (m && m->failed && sp.cfg.win && attempt < 7) {         // as launch(): plan again without that geometry
-            if (getenv("VND_SPEC_VERBOSE")) fprintf(stderr, "vnd: window form (frames_per_lane=%d threads=%d) unavailable: %s\n", sp.cfg.win, sp.cfg.nt, m->log.c_str());
-            continue;
-        }
-        if (m && !m->failed) {
-            if (sp.cfg.win) {
-                char split[96];
-                if (sp.chunk_tiles > 0) snprintf(split, sizeof split, "a chunk of %d tiles per CU as %d + %d, %d chunks", sp.chunk_tiles, sp.chunk_len0, sp.chunk_tiles - sp.chunk_len0, sp.chunks_per_stream);
-                else if (sp.bal_total > 0) snprintf(split, sizeof split, "balanced ranges of %d tiles, %d in the pool", sp.tiles_per_span, sp.bal_total);
-                else snprintf(split, sizeof split, "%d spans x %d tiles", sp.spans, sp.tiles_per_span);
-                snprintf(text, (size_t)len,
-                         "conv_spec%s_window (hipRTC, per table) frames_per_lane=%d tile=%d reads_ahead=%d "
-                         "nt_stores=%d mode=%d lds=%zuB workgroups=%u (%u units: %s per stream) threads=%d store_phase=%s%s",
-                         sp.cfg.exact ? "_exact" : "", sp.cfg.win, sp.cfg.tile(), sp.cfg.la, sp.cfg.nt_stores, mode,
-                         sp.cfg.lds_bytes(), sp.nblocks, sp.units, split, sp.cfg.nt,
-                         sp.cfg.win_s ? "planar waves=split-by-channel" : sp.cfg.win_q == 2 ? "planar pieces=channel-octets waves=split-by-channel" : (sp.cfg.win_q ? "planar pieces=channel-quads waves=split-by-channel" : (sp.cfg.win_xpose ? "frame-pairs" : "planar")),
-                         sp.cfg.adds ? " taps=adds-per-segment" : "");
-                return VND_OK;
-            }
+    DeviceScope on(ctx->device);                                   // (a build works on the context's device)
+    const SpecChoice sc = choose_spec(ctx, t, nullptr, nullptr, batch, n, C, Cx, mode, nullptr, false, getenv("VND_SPEC_VERBOSE") != nullptr);
+    if (sc.module) {
+        const SpecPlan &sp = sc.plan;
+        if (sp.cfg.win) {
+            char split[96];
+            if (sp.chunk_tiles > 0) snprintf(split, sizeof split, "a chunk of %d tiles per CU as %d + %d, %d chunks", sp.chunk_tiles, sp.chunk_len0, sp.chunk_tiles - sp.chunk_len0, sp.chunks_per_stream);
+            else if (sp.bal_total > 0) snprintf(split, sizeof split, "balanced ranges of %d tiles, %d in the pool", sp.tiles_per_span, sp.bal_total);
+            else snprintf(split, sizeof split, "%d spans x %d tiles", sp.spans, sp.tiles_per_span);
             snprintf(text, (size_t)len,
-                     "conv_spec%s (hipRTC, per table) pairs_per_lane=%d tile=%d ring_slots=%d prefetch=%d reads_ahead=%d "
-                     "nt_stores=%d mode=%d lds=%zuB workgroups=%u (%u units: %d spans x %d tiles per stream) threads=%d",
-                     sp.cfg.exact ? "_exact" : "", sp.cfg.rr, sp.cfg.tile(), sp.cfg.pp, sp.cfg.dd, sp.cfg.la, sp.cfg.nt_stores, mode,
-                     sp.cfg.lds_bytes(), sp.nblocks, sp.units, sp.spans, sp.tiles_per_span, sp.cfg.nt);
+                     "conv_spec%s_window (hipRTC, per table) frames_per_lane=%d tile=%d reads_ahead=%d "
+                     "nt_stores=%d mode=%d lds=%zuB workgroups=%u (%u units: %s per stream) threads=%d store_phase=%s%s",
+                     sp.cfg.exact ? "_exact" : "", sp.cfg.win, sp.cfg.tile(), sp.cfg.la, sp.cfg.nt_stores, mode,
+                     sp.cfg.lds_bytes(), sp.nblocks, sp.units, split, sp.cfg.nt,
+                     sp.cfg.win_s ? "planar waves=split-by-channel" : sp.cfg.win_q == 2 ? "planar pieces=channel-octets waves=split-by-channel" : (sp.cfg.win_q ? "planar pieces=channel-quads waves=split-by-channel" : (sp.cfg.win_xpose ? "frame-pairs" : "planar")),
+                     sp.cfg.adds ? " taps=adds-per-segment" : "");
             return VND_OK;
         }
-        if (m && getenv("VND_SPEC_VERBOSE")) fprintf(stderr, "vnd: specialised kernel unavailable: %s\n", m->log.c_str());
-        break;
+        snprintf(text, (size_t)len,
+                 "conv_spec%s (hipRTC, per table) pairs_per_lane=%d tile=%d ring_slots=%d prefetch=%d reads_ahead=%d "
+                 "nt_stores=%d mode=%d lds=%zuB workgroups=%u (%u units: %d spans x %d tiles per stream) threads=%d",
+                 sp.cfg.exact ? "_exact" : "", sp.cfg.rr, sp.cfg.tile(), sp.cfg.pp, sp.cfg.dd, sp.cfg.la, sp.cfg.nt_stores, mode,
+                 sp.cfg.lds_bytes(), sp.nblocks, sp.units, sp.spans, sp.tiles_per_span, sp.cfg.nt);
+        return VND_OK;
     }
     const Plan p = make_plan(ctx, t, batch, n, C, mode, Cx);
     if (p.direct)
@@ -387,27 +378,20 @@ vnd_status vnd_describe_launch(vnd_ctx *ctx, const vnd_taps *t, int64_t batch, i
 vnd_status vnd_describe_fanout_launch(vnd_ctx *ctx, const vnd_taps *t, int64_t batch, int64_t n,
                                       int32_t in_channels, int32_t mode, char *text, int32_t len)
 {
-    if (!t) return fail(VND_ERR_INVALID, "null context or tap table");
-    if (in_channels <= 0) return fail(VND_ERR_INVALID, "in_channels must be positive");
+    if (vnd_status st = check_fanout(t, in_channels); st != VND_OK) return st;
     return describe(ctx, t, batch, n, in_channels, t->C, mode, text, len);
 }
 
 vnd_status vnd_prepare_launch(vnd_ctx *ctx, const vnd_taps *t, int64_t batch, int64_t n, int32_t in_channels, int32_t mode)
 {
-    if (!ctx || !t) return fail(VND_ERR_INVALID, "null context or tap table");
-    if (in_channels <= 0) return fail(VND_ERR_INVALID, "in_channels must be positive");
-    vnd_status st = check_shape(ctx, t, batch, n, t->C, mode, in_channels);
+    vnd_status st = check_fanout(t, in_channels);
+    if (st == VND_OK) st = check_shape(ctx, t, batch, n, t->C, mode, in_channels);
     if (st != VND_OK) return st;
     if (batch == 0 || n == 0) return VND_OK;
     DeviceScope on(ctx->device);
-    for (int attempt = 0; attempt < 8; ++attempt) {               // (a window geometry that does not build is skipped: plan again)
-        const SpecPlan sp = make_spec_plan(ctx, t, nullptr, nullptr, batch, n, t->C, in_channels, mode, nullptr);
-        if (!sp.use) return VND_OK;
-        SpecModule *m = spec_module(ctx, t, sp.cfg, false);
-        if (m && !m->failed) return VND_OK;
-        if (!sp.cfg.win) break;
-    }
-    return VND_OK;                                                 // the generic kernels take such launches
+    // build now, whatever the launch's size (where nothing builds the generic kernels take such launches)
+    (void)choose_spec(ctx, t, nullptr, nullptr, batch, n, t->C, in_channels, mode, nullptr, true);
+    return VND_OK;
 }
 
 }  // extern "C"

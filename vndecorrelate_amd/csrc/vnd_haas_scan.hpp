@@ -242,6 +242,30 @@ static vnd_status haas_pairs_launch(vnd_ctx *ctx, const float *x, int32_t batch,
     return VND_OK;
 }
 
+// Both _host entries after their checks, host pointers in: the arrays staged in `ws` bytes of partial sums and four more pieces
+// (signals == null: the scan of one signal, no index array).
+static vnd_status haas_pairs_host(vnd_ctx *ctx, const char *name, const float *x, int32_t batch, int64_t n_frames,
+                                  int32_t in_channels, const int32_t *signals, const int32_t *delays, int32_t n_pairs,
+                                  int32_t delayed_channel, int32_t ms_mode, int32_t use_width, double width, double *moments,
+                                  int64_t ws)
+{
+    HostCall call(ctx);
+    const size_t x_bytes = (size_t)batch * n_frames * in_channels * sizeof(float);
+    const size_t i_bytes = (size_t)n_pairs * sizeof(int32_t), s_bytes = signals ? i_bytes : 0;
+    const size_t m_bytes = (size_t)n_pairs * kMoments * sizeof(double);
+    call.carve({(size_t)ws, m_bytes, s_bytes, i_bytes, x_bytes});
+    double *m_dev = call.piece<double>(1);
+    int32_t *s_dev = signals ? call.piece<int32_t>(2) : nullptr, *d_dev = call.piece<int32_t>(3);
+    float *x_dev = call.piece<float>(4);
+    call.up(x_dev, x, x_bytes, "x");
+    call.up(s_dev, signals, s_bytes, "signals");
+    call.up(d_dev, delays, i_bytes, "delays");
+    call.run([&] { return haas_pairs_launch(ctx, x_dev, batch, n_frames, in_channels, s_dev, d_dev, n_pairs, delayed_channel,
+                                            ms_mode, use_width, width, m_dev, call.piece<char>(0), ws, call.stream()); });
+    call.down(moments, m_dev, m_bytes, "moments");
+    return call.finish(name);
+}
+
 vnd_status vnd_haas_scan_f64_dev(vnd_ctx *ctx, const float *x, int64_t n_frames, int32_t in_channels,
                                  const int32_t *delays, int32_t n_delays, int32_t delayed_channel, int32_t ms_mode,
                                  int32_t use_width, double width, double *moments, void *workspace,
@@ -271,27 +295,8 @@ vnd_status vnd_haas_scan_f64_host(vnd_ctx *ctx, const float *x, int64_t n_frames
     int64_t ws = 0;
     st = vnd_haas_scan_workspace_bytes(n_frames, n_delays, dmax, &ws);
     if (st != VND_OK) return st;
-    HostLock lock(ctx->host_mutex);
-    DeviceScope on(ctx->device);
-    if (!on.ok) return fail(VND_ERR_HIP, "cannot select device %d", ctx->device);
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t x_bytes = (size_t)n_frames * in_channels * sizeof(float);
-    const size_t d_bytes = (size_t)n_delays * sizeof(int32_t);
-    const size_t m_bytes = (size_t)n_delays * kMoments * sizeof(double);
-    st = ensure_work(ctx, (size_t)ws + up(m_bytes) + up(d_bytes) + up(x_bytes));
-    if (st != VND_OK) return st;
-    char *work = ctx->work;
-    double *m_dev = (double *)(work + ws);
-    int32_t *d_dev = (int32_t *)(work + ws + up(m_bytes));
-    float *x_dev = (float *)(work + ws + up(m_bytes) + up(d_bytes));
-    if (x_bytes) HIP_TRY(hipMemcpyAsync(x_dev, x, x_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_dev, delays, d_bytes, hipMemcpyHostToDevice, ctx->stream));
-    st = vnd_haas_scan_f64_dev(ctx, x_dev, n_frames, in_channels, d_dev, n_delays, delayed_channel, ms_mode, use_width,
-                               width, m_dev, work, ws, ctx->stream);
-    if (st != VND_OK) return st;
-    HIP_TRY(hipMemcpyAsync(moments, m_dev, m_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return VND_OK;
+    return haas_pairs_host(ctx, "vnd_haas_scan_f64_host", x, 1, n_frames, in_channels, nullptr, delays, n_delays, delayed_channel,
+                           ms_mode, use_width, width, moments, ws);
 }
 
 // ---- include/vnd_haas_search.h: (signal, delay) pairs of a pool ----------------------------------------------------
@@ -349,29 +354,8 @@ vnd_status vnd_haas_pairs_f64_host(vnd_ctx *ctx, const float *x, int32_t batch, 
     int64_t ws = 0;
     st = vnd_haas_pairs_workspace_bytes(n_frames, n_pairs, dmax, &ws);
     if (st != VND_OK) return st;
-    HostLock lock(ctx->host_mutex);
-    DeviceScope on(ctx->device);
-    if (!on.ok) return fail(VND_ERR_HIP, "cannot select device %d", ctx->device);
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t x_bytes = (size_t)batch * n_frames * in_channels * sizeof(float);
-    const size_t i_bytes = (size_t)n_pairs * sizeof(int32_t);
-    const size_t m_bytes = (size_t)n_pairs * kMoments * sizeof(double);
-    st = ensure_work(ctx, (size_t)ws + up(m_bytes) + 2 * up(i_bytes) + up(x_bytes));
-    if (st != VND_OK) return st;
-    char *work = ctx->work;
-    double *m_dev = (double *)(work + ws);
-    int32_t *s_dev = (int32_t *)(work + ws + up(m_bytes));
-    int32_t *d_dev = (int32_t *)(work + ws + up(m_bytes) + up(i_bytes));
-    float *x_dev = (float *)(work + ws + up(m_bytes) + 2 * up(i_bytes));
-    if (x_bytes) HIP_TRY(hipMemcpyAsync(x_dev, x, x_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(s_dev, signals, i_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_dev, delays, i_bytes, hipMemcpyHostToDevice, ctx->stream));
-    st = vnd_haas_pairs_f64_dev(ctx, x_dev, batch, n_frames, in_channels, s_dev, d_dev, n_pairs, delayed_channel,
-                                ms_mode, use_width, width, m_dev, work, ws, ctx->stream);
-    if (st != VND_OK) return st;
-    HIP_TRY(hipMemcpyAsync(moments, m_dev, m_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return VND_OK;
+    return haas_pairs_host(ctx, "vnd_haas_pairs_f64_host", x, batch, n_frames, in_channels, signals, delays, n_pairs,
+                           delayed_channel, ms_mode, use_width, width, moments, ws);
 }
 
 }  // extern "C"

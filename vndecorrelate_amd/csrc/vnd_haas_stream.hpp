@@ -180,24 +180,18 @@ vnd_status vnd_haas_stream_f64_host(vnd_ctx *ctx, void *state, int64_t state_byt
     if (st != VND_OK) return st;
     const int64_t nout = *n_out;
     if (batch == 0 || (n_in == 0 && nout == 0)) return VND_OK;
-    HostLock lock(ctx->host_mutex);
-    DeviceScope on(ctx->device);
-    if (!on.ok) return fail(VND_ERR_HIP, "cannot select device %d", ctx->device);
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    HostCall call(ctx);
     const size_t x_bytes = (size_t)(batch * n_in * Cx) * sizeof(float);
     const size_t y_bytes = (size_t)(batch * nout * 2) * sizeof(double);
-    st = ensure_work(ctx, up(x_bytes) + up(y_bytes));
-    if (st != VND_OK) return st;
-    float *x_dev = (float *)ctx->work;
-    double *y_dev = (double *)(ctx->work + up(x_bytes));
-    if (x_bytes) HIP_TRY(hipMemcpyAsync(x_dev, x, x_bytes, hipMemcpyHostToDevice, ctx->stream));
+    call.carve({x_bytes, y_bytes});
+    float *x_dev = call.piece<float>(0);
+    double *y_dev = call.piece<double>(1);
+    call.up(x_dev, x, x_bytes, "the chunk");
     int64_t got = 0;
-    st = vnd_haas_stream_f64_dev(ctx, state, state_bytes, max_frames_per_call, x_dev, y_dev, batch, pos, n_in, Cx, final_,
-                                 delay, delayed_channel, ms_mode, use_width, width, &got, ctx->stream);
-    if (st != VND_OK) return st;
-    if (y_bytes) HIP_TRY(hipMemcpyAsync(y, y_dev, y_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return VND_OK;
+    call.run([&] { return vnd_haas_stream_f64_dev(ctx, state, state_bytes, max_frames_per_call, x_dev, y_dev, batch, pos, n_in, Cx,
+                                                  final_, delay, delayed_channel, ms_mode, use_width, width, &got, call.stream()); });
+    call.down(y, y_dev, y_bytes, "y");
+    return call.finish("vnd_haas_stream_f64_host");
 }
 
 }  // extern "C"

@@ -67,6 +67,22 @@ static vnd_status fail(vnd_status st, const char *fmt, ...)
                         __FILE__, __LINE__);                                           \
     } while (0)
 
+// A grow-only device buffer (the staging buffers and the workspace of the *_host entry points): reallocated only when a call
+// outgrows it, to exactly the size that call asks for.
+struct DevBuffer {
+    char *p = nullptr;
+    size_t bytes = 0;
+    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+    vnd_status reserve(size_t want)
+    {
+        if (want <= bytes) return VND_OK;
+        release();
+        HIP_TRY(hipMalloc((void **)&p, want));
+        bytes = want;
+        return VND_OK;
+    }
+};
+
 // ------------------------------------------------------------------------------
 // objects
 // ------------------------------------------------------------------------------
@@ -106,14 +122,13 @@ struct vnd_ctx {
     hipStream_t stream = nullptr; // used by the *_host entry points
     hipStream_t stream2 = nullptr;    // second lane of the chunked host pipeline
     std::vector<hipEvent_t> up_events;    // "piece k is on the device" marks of the time-chunked pipeline (made on first use)
-    float *scratch_x = nullptr, *scratch_y = nullptr;
-    size_t scratch_elems = 0;
-    char *work = nullptr;         // grow-only workspace of the *_host entry points
-    size_t work_bytes = 0;
+    DevBuffer scratch_x, scratch_y;   // staged input and output of the *_host entry points (HostCall::stage)
+    DevBuffer work;               // their workspace (HostCall::carve)
     Variant variant;              // vnd_set_variant
     // One *_host call at a time per context: they share the stream, the staging buffers and the
     // workspace.  The reference's functions are re-entrant (decorrelation.py:630-660), and ctypes /
     // cgo / JNI callers run without a global lock, so the library serialises them itself.
+    // (HostCall, vnd_host.hpp, is the one place that takes it)
     std::mutex host_mutex;
     // kernels already opted in to > 64 KiB of dynamic LDS on THIS context's device
     // (hipFuncSetAttribute applies to the current device's copy of the function)

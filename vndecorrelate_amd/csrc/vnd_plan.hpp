@@ -279,6 +279,39 @@ static vnd_status check_shape(const vnd_ctx *ctx, const vnd_taps *t, int64_t bat
     return VND_OK;
 }
 
+// the *_fanout_* entry points take the output's channel count from the table: before check_shape, which needs it
+static vnd_status check_fanout(const vnd_taps *t, int32_t in_channels)
+{
+    if (!t) return fail(VND_ERR_INVALID, "null context or tap table");
+    if (in_channels <= 0) return fail(VND_ERR_INVALID, "in_channels must be positive");
+    return VND_OK;
+}
+
+// the tap table's fields of a generic kernel's arguments
+static void table_args(KArgs &a, const vnd_taps *t)
+{
+    a.taps = t->d_taps; a.taps_fast = t->d_taps_fast; a.taps_ord = t->d_taps_ord; a.fast_off = t->d_fast_off; a.fast_even = t->d_fast_even; a.tap_off = t->d_tap_off;
+    a.seg_off = t->has_seg ? t->d_seg_off : nullptr;
+    a.seg_end = t->d_seg_end; a.seg_gain = t->d_seg_gain;
+    a.chan_flags = t->has_flags ? t->d_flags : nullptr;
+    a.apply_gain = t->apply_gain;
+}
+
+// opt a kernel in to > 64 KiB of dynamic LDS, once per (device, kernel)
+static vnd_status allow_lds(vnd_ctx *ctx, const void *kernel, size_t bytes)
+{
+    if (bytes <= 65536) return VND_OK;
+    // ask for what the launch needs, not for the whole LDS: a kernel's static LDS (reduction
+    // scratch of the epilogue instantiations) counts against the same 160 KiB
+    std::lock_guard<std::mutex> g(ctx->raised_mutex);
+    size_t &have = ctx->raised[kernel];
+    if (have < bytes) {
+        HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        have = bytes;
+    }
+    return VND_OK;
+}
+
 // ------------------------------------------------------------------------------
 // the specialised fast kernel (vnd_spec.hpp, vnd_spec_kernel.inc)
 // ------------------------------------------------------------------------------
@@ -636,13 +669,39 @@ static SpecModule *spec_module(vnd_ctx *ctx, const vnd_taps *t_, const SpecConfi
     }
 }
 
-static vnd_status launch_spec(vnd_ctx *ctx, const vnd_taps *t, const SpecPlan &p, const float *x, float *y, int64_t n,
-                              hipStream_t stream, bool *launched, const EpiFuse *epi = nullptr, bool *built = nullptr)
+// The per-table kernel of a launch: plan, get (or build) the plan's module, and plan again when a window geometry does not build -
+// it is remembered as failed in the table's module map, so the next plan skips it.  module == null: the generic kernels take the
+// launch (plan.why says why when nothing was planned).  build_now: build even for a launch too small to be worth it on its own
+// (vnd_prepare_launch); verbose: say on stderr what did not build (vnd_describe_launch under VND_SPEC_VERBOSE).
+struct SpecChoice {
+    SpecPlan plan;
+    SpecModule *module = nullptr;
+};
+
+static SpecChoice choose_spec(vnd_ctx *ctx, const vnd_taps *t, const float *x, const float *y, int64_t batch, int64_t n, int C,
+                              int Cx, int mode, const EpiFuse *epi, bool build_now = false, bool verbose = false)
+{
+    SpecChoice c;
+    for (int attempt = 0; attempt < 8; ++attempt) {
+        c.plan = make_spec_plan(ctx, t, x, y, batch, n, C, Cx, mode, epi);
+        if (!c.plan.use) break;
+        SpecModule *m = spec_module(ctx, t, c.plan.cfg, !build_now && !c.plan.eager);
+        if (m && !m->failed) { c.module = m; break; }
+        const bool again = m && c.plan.cfg.win && attempt != 7;      // (the last attempt ends the search)
+        if (m && verbose) {
+            if (again) fprintf(stderr, "vnd: window form (frames_per_lane=%d threads=%d) unavailable: %s\n", c.plan.cfg.win, c.plan.cfg.nt, m->log.c_str());
+            else fprintf(stderr, "vnd: specialised kernel unavailable: %s\n", m->log.c_str());
+        }
+        if (!again) break;
+    }
+    return c;
+}
+
+// (a launch that fails marks the module failed: the generic kernel takes this launch and every later one of that geometry)
+static vnd_status launch_spec(vnd_ctx *ctx, const vnd_taps *t, const SpecPlan &p, SpecModule *m, const float *x, float *y, int64_t n,
+                              hipStream_t stream, bool *launched, const EpiFuse *epi = nullptr)
 {
     *launched = false;
-    SpecModule *m = spec_module(ctx, t, p.cfg, !p.eager);
-    if (built) *built = !(m && m->failed);                   // false: a build was tried and failed (not: none was tried)
-    if (!m || m->failed) return VND_OK;                      // generic kernel instead
     SpecArgs a{};
     a.x = x; a.y = y; a.n = n;
     a.tiles_total = p.tiles_total; a.tiles_per_span = p.tiles_per_span; a.spans = p.spans; a.nblocks = p.nblocks;
@@ -692,22 +751,17 @@ static vnd_status launch(vnd_ctx *ctx, const vnd_taps *t, const float *x, float 
 {
     if (batch == 0 || n == 0) return VND_OK;
     if (Cx == 0) Cx = C;
-    for (int attempt = 0; attempt < 8; ++attempt) {
-        const SpecPlan sp = make_spec_plan(ctx, t, x, y, batch, n, C, Cx, mode, epi);
-        if (!sp.use) break;
-        bool launched = false, built = true;
-        vnd_status st = launch_spec(ctx, t, sp, x, y, n, stream, &launched, epi, &built);
+    const SpecChoice sc = choose_spec(ctx, t, x, y, batch, n, C, Cx, mode, epi);
+    if (sc.module) {
+        bool launched = false;
+        vnd_status st = launch_spec(ctx, t, sc.plan, sc.module, x, y, n, stream, &launched, epi);
         if (st != VND_OK || launched) return st;
-        if (!sp.cfg.win || built) break;                          // (a failed window build: plan again, that geometry is skipped now)
     }
     if (epi != nullptr && epi->spec_only) return VND_OK;          // (*epi->path is 0: nothing was launched)
     const Plan p = make_plan(ctx, t, batch, n, C, mode, Cx);
     KArgs a{};
-    a.x = x; a.y = y; a.taps = t->d_taps; a.taps_fast = t->d_taps_fast; a.taps_ord = t->d_taps_ord; a.fast_off = t->d_fast_off; a.fast_even = t->d_fast_even; a.tap_off = t->d_tap_off;
-    a.seg_off = t->has_seg ? t->d_seg_off : nullptr;
-    a.seg_end = t->d_seg_end; a.seg_gain = t->d_seg_gain;
-    a.chan_flags = t->has_flags ? t->d_flags : nullptr;
-    a.n = n; a.C = C; a.Cx = Cx; a.apply_gain = t->apply_gain;
+    a.x = x; a.y = y; a.n = n; a.C = C; a.Cx = Cx;
+    table_args(a, t);
     a.stream_out = p.stream_out ? 1 : 0;
     a.nblocks = p.nblocks;
     if (p.direct) {
@@ -727,16 +781,7 @@ static vnd_status launch(vnd_ctx *ctx, const vnd_taps *t, const float *x, float 
             a.epi_normalize = epi->normalize; a.epi_w_mid = epi->w_mid; a.epi_w_side = epi->w_side;
             a.sink_partials = epi->sink;
         }
-        if (p.lds_bytes > 65536) {           // opt in to > 64 KiB of dynamic LDS, once per (device, kernel)
-            // ask for what the launch needs, not for the whole LDS: a kernel's static LDS (reduction
-            // scratch of the epilogue instantiations) counts against the same 160 KiB
-            std::lock_guard<std::mutex> g(ctx->raised_mutex);
-            size_t &have = ctx->raised[(const void *)k];
-            if (have < p.lds_bytes) {
-                HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
-                have = p.lds_bytes;
-            }
-        }
+        if (vnd_status st = allow_lds(ctx, (const void *)k, p.lds_bytes); st != VND_OK) return st;
         hipLaunchKernelGGL(k, dim3(p.nblocks), dim3(p.nt), p.lds_bytes, stream, a);
     }
     HIP_TRY(hipGetLastError());

@@ -161,8 +161,8 @@ static vnd_status stage_sums(vnd_ctx *ctx, StageSetup &s, const float *x, const 
         auto k = C == 2 ? (Cx == 1 ? epilogue_rms_seq_kernel<true, true> : epilogue_rms_seq_kernel<true, false>)
                         : (seq_frames == kSeqFrames ? epilogue_rms_seq_kernel<false, false, kSeqFrames>
                                                     : epilogue_rms_seq_kernel<false, false, kSeqFramesWide>);
-        if (lds > 65536) HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                      ctx->lds_limit));
+        // (this kernel has no static LDS: the whole of it)
+        if (vnd_status st = lds > 65536 ? allow_lds(ctx, (const void *)k, (size_t)ctx->lds_limit) : VND_OK; st != VND_OK) return st;
         // stereo, fewer streams than two per CU: a workgroup per ARRAY of a stream (x's chains, y's chains) - twice the loads in flight
         const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
         e.seq_split = (C == 2 && batch < 2 * (int64_t)cus && s.tun.epi_seq_split != 0) ? 1 : 0;
@@ -303,44 +303,20 @@ static vnd_status decorrelate_host(vnd_ctx *ctx, const vnd_taps *t, const float 
     if (st != VND_OK) return st;
     if (batch == 0 || n == 0) return VND_OK;
     if (!x || !y) return fail(VND_ERR_INVALID, "null signal pointer");
-    HostLock lock(ctx->host_mutex);
-    DeviceScope on(ctx->device);
-    if (!on.ok) return fail(VND_ERR_HIP, "cannot select device %d", ctx->device);
+    HostCall call(ctx);
     const size_t in_elems = (size_t)batch * n * Cx, out_elems = (size_t)batch * n * C;
-    st = ensure_scratch(ctx, out_elems);
-    if (st != VND_OK) return st;
-    int64_t ws = 0;
-    vnd_decorrelate_workspace_bytes(batch, n, C, &ws);
-    st = ensure_work(ctx, (size_t)ws);
-    if (st != VND_OK) return st;
+    call.stage(out_elems);
+    // one workspace per pipeline lane: the two lanes' epilogues run side by side
     const int chunks = host_chunks(batch, (in_elems + out_elems) * sizeof(float));
-    if (chunks > 1) {
-        // one workspace per pipeline lane: the two lanes' epilogues run side by side
-        const int64_t per = (batch + chunks - 1) / chunks;
-        vnd_decorrelate_workspace_bytes(per, n, C, &ws);
-        ws = (ws + 255) & ~(int64_t)255;
-        st = ensure_work(ctx, (size_t)ws * 2);
-        if (st != VND_OK) return st;
-    }
-    hipError_t e = hipSuccess;
-    for (int c = 0; c < chunks && st == VND_OK && e == hipSuccess; ++c) {
-        const int64_t b0 = batch * c / chunks, b1 = batch * (c + 1) / chunks;
-        if (b1 == b0) continue;
-        hipStream_t s = (c & 1) ? ctx->stream2 : ctx->stream;
-        const size_t xo = (size_t)b0 * n * Cx, yo = (size_t)b0 * n * C;
-        e = hipMemcpyAsync(ctx->scratch_x + xo, x + xo, (size_t)(b1 - b0) * n * Cx * sizeof(float), hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) break;
-        st = decorrelate_dev(ctx, t, ctx->scratch_x + xo, ctx->scratch_y + yo, b1 - b0, n, Cx, C, mode, ms_encode, use_width,
-                             width, normalize, eps, ctx->work + (size_t)(c & 1) * (size_t)ws, ws, s);
-        if (st != VND_OK) break;
-        e = hipMemcpyAsync(y + yo, ctx->scratch_y + yo, (size_t)(b1 - b0) * n * C * sizeof(float), hipMemcpyDeviceToHost, s);
-    }
-    // on any failure too: nothing of this call stays in flight behind its return (see convolve_host)
-    const hipError_t s1 = hipStreamSynchronize(ctx->stream), s2 = hipStreamSynchronize(ctx->stream2);
-    if (st != VND_OK) return st;
-    if (e == hipSuccess) e = s1 != hipSuccess ? s1 : s2;
-    if (e != hipSuccess) return fail(VND_ERR_HIP, "host pipeline failed: %s", hipGetErrorString(e));
-    return VND_OK;
+    int64_t ws = 0;
+    vnd_decorrelate_workspace_bytes(chunks > 1 ? (batch + chunks - 1) / chunks : batch, n, C, &ws);
+    call.carve({(size_t)ws, chunks > 1 ? (size_t)ws : 0});
+    host_group_pipeline(call, x, y, nullptr, batch, n, Cx, C, chunks,
+                        [&](const float *xg, float *yg, int64_t streams, int lane, hipStream_t s) {
+                            return decorrelate_dev(ctx, t, xg, yg, streams, n, Cx, C, mode, ms_encode, use_width, width, normalize,
+                                                   eps, call.piece<char>(chunks > 1 ? lane : 0), ws, s);
+                        });
+    return call.finish("host pipeline");
 }
 
 vnd_status vnd_decorrelate_f32_dev(vnd_ctx *ctx, const vnd_taps *t, const float *x, float *y, int64_t batch,
@@ -364,8 +340,7 @@ vnd_status vnd_decorrelate_fanout_f32_dev(vnd_ctx *ctx, const vnd_taps *t, const
                                           int32_t ms_encode, int32_t use_width, double width, int32_t normalize,
                                           float eps, void *workspace, int64_t workspace_bytes, void *stream)
 {
-    if (!t) return fail(VND_ERR_INVALID, "null context or tap table");
-    if (in_channels <= 0) return fail(VND_ERR_INVALID, "in_channels must be positive");
+    if (vnd_status st = check_fanout(t, in_channels); st != VND_OK) return st;
     return decorrelate_dev(ctx, t, x, y, batch, n, in_channels, t->C, mode, ms_encode, use_width, width, normalize,
                            eps, workspace, workspace_bytes, stream);
 }
@@ -376,8 +351,7 @@ vnd_status vnd_debug_decorrelate_f32_dev(vnd_ctx *ctx, const vnd_taps *t, const 
                                          int32_t normalize, float eps, void *workspace, int64_t workspace_bytes, void *stream,
                                          int32_t *taken)
 {
-    if (!t) return fail(VND_ERR_INVALID, "null context or tap table");
-    if (in_channels <= 0) return fail(VND_ERR_INVALID, "in_channels must be positive");
+    if (vnd_status st = check_fanout(t, in_channels); st != VND_OK) return st;
     if (!taken) return fail(VND_ERR_INVALID, "null taken pointer");
     return decorrelate_dev(ctx, t, x, y, batch, n, in_channels, t->C, mode, ms_encode, use_width, width, normalize,
                            eps, workspace, workspace_bytes, stream, taken);
@@ -388,8 +362,7 @@ vnd_status vnd_decorrelate_fanout_f32_host(vnd_ctx *ctx, const vnd_taps *t, cons
                                            int32_t ms_encode, int32_t use_width, double width, int32_t normalize,
                                            float eps)
 {
-    if (!t) return fail(VND_ERR_INVALID, "null context or tap table");
-    if (in_channels <= 0) return fail(VND_ERR_INVALID, "in_channels must be positive");
+    if (vnd_status st = check_fanout(t, in_channels); st != VND_OK) return st;
     return decorrelate_host(ctx, t, x, y, batch, n, in_channels, t->C, mode, ms_encode, use_width, width,
                             normalize, eps);
 }
@@ -412,35 +385,27 @@ vnd_status vnd_convolve_promote_host(vnd_ctx *ctx, int32_t C, const int32_t *tap
     const int64_t total = batch * n * C;
     if (total == 0) return VND_OK;
     if (!x || !y) return fail(VND_ERR_INVALID, "null signal pointer");
-    HostLock lock(ctx->host_mutex);
-    DeviceScope on(ctx->device);
-    if (!on.ok) return fail(VND_ERR_HIP, "cannot select device %d", ctx->device);
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    HostCall call(ctx);
     const size_t xb = (size_t)total * (x_is_f64 ? 8 : 4), yb = (size_t)total * 4;
     const size_t wb = (size_t)taps * 8, ob = (size_t)(C + 1) * 4, ib = (size_t)taps * 4;
-    vnd_status st = ensure_work(ctx, up16(xb) + up16(yb) + up16(wb) + up16(ob) + up16(ib) + 16);
-    if (st != VND_OK) return st;
-    char *p = ctx->work;                                   // hipMalloc'ed: 256-byte aligned
+    call.carve({xb, yb, wb, ob, ib});
     PArgs a{};
-    a.x = p;
-    a.y = (float *)(p + up16(xb));
-    a.w = (const double *)((const char *)a.y + up16(yb));
-    a.tap_off = (const int32_t *)((const char *)a.w + up16(wb));
-    a.idx = (const int32_t *)((const char *)a.tap_off + up16(ob));
+    a.x = call.piece<char>(0); a.y = call.piece<float>(1); a.w = call.piece<double>(2);
+    a.tap_off = call.piece<int32_t>(3); a.idx = call.piece<int32_t>(4);
     a.n = n; a.total = total; a.C = C; a.x_is_f64 = x_is_f64 ? 1 : 0;
-    HIP_TRY(hipMemcpyAsync(p, x, xb, hipMemcpyHostToDevice, ctx->stream));
-    if (taps) {
-        HIP_TRY(hipMemcpyAsync((void *)a.w, tap_weight, (size_t)taps * 8, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipMemcpyAsync((void *)a.idx, tap_index, (size_t)taps * 4, hipMemcpyHostToDevice, ctx->stream));
-    }
-    HIP_TRY(hipMemcpyAsync((void *)a.tap_off, tap_offsets, (size_t)(C + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
-    const int64_t blocks = std::min<int64_t>((total + kDirectThreads - 1) / kDirectThreads, (int64_t)cus * 32);
-    hipLaunchKernelGGL(conv_promote_kernel, dim3((unsigned)blocks), dim3(kDirectThreads), 0, ctx->stream, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(y, a.y, yb, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return VND_OK;
+    call.up((void *)a.x, x, xb, "x");
+    call.up((void *)a.w, tap_weight, wb, "tap_weight");
+    call.up((void *)a.idx, tap_index, ib, "tap_index");
+    call.up((void *)a.tap_off, tap_offsets, ob, "tap_offsets");
+    call.run([&] {
+        const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+        const int64_t blocks = std::min<int64_t>((total + kDirectThreads - 1) / kDirectThreads, (int64_t)cus * 32);
+        hipLaunchKernelGGL(conv_promote_kernel, dim3((unsigned)blocks), dim3(kDirectThreads), 0, call.stream(), a);
+        HIP_TRY(hipGetLastError());
+        return VND_OK;
+    });
+    call.down(y, a.y, yb, "y");
+    return call.finish("vnd_convolve_promote_host");
 }
 
 // ------------------------------------------------------------------------------
@@ -495,54 +460,38 @@ vnd_status vnd_scan_bank_f32_host(vnd_ctx *ctx, const vnd_taps *t, const float *
     if (st != VND_OK) return st;
     if (!moments || (n > 0 && !x)) return fail(VND_ERR_INVALID, "null pointer");
     const int32_t pairs = t->C / 2;
-    HostLock lock(ctx->host_mutex);
-    DeviceScope on(ctx->device);
-    if (!on.ok) return fail(VND_ERR_HIP, "cannot select device %d", ctx->device);
+    HostCall call(ctx);
     // Fused form: the convolution kernel's store phase reduces each tile to the eight moments per
     // candidate (KArgs.sink_partials) - the [n][2F] output, 1.6 GB there and back for 400 candidates
     // of a 5.7 s signal, is never written.  Needs the two-channels-per-workgroup epilogue instantiation.
+    Plan p{};
+    bool fused = false;
     if (n > 0 && !ctx->variant.nofuse) {
-        const Plan p = make_plan(ctx, t, 1, n, t->C, mode, in_channels);
+        p = make_plan(ctx, t, 1, n, t->C, mode, in_channels);
         kern_t k = p.direct ? nullptr
                             : (mode == VND_MODE_FAST ? fast_epi_kernel(p) : ordered_epi_kernel(p, arithmetic_of(t, mode)));
-        if (k != nullptr && p.cg == 2) {
-            const size_t part_bytes = (size_t)p.tiles * pairs * kMoments * sizeof(double);
-            const size_t out_bytes = (size_t)pairs * kMoments * sizeof(double);
-            st = ensure_scratch(ctx, (size_t)n * in_channels);
-            if (st != VND_OK) return st;
-            st = ensure_work(ctx, part_bytes + out_bytes);
-            if (st != VND_OK) return st;
-            HIP_TRY(hipMemcpyAsync(ctx->scratch_x, x, (size_t)n * in_channels * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-            EpiFuse f{nullptr, 0, 0, 0, 0.0f, 0.0f, (double *)ctx->work};
-            st = launch(ctx, t, ctx->scratch_x, ctx->scratch_y, 1, n, t->C, mode, ctx->stream, &f, in_channels);
-            if (st != VND_OK) return st;
-            MArgs m{};
-            m.partials = (double *)ctx->work; m.moments = (double *)(ctx->work + part_bytes); m.n = n; m.F = pairs; m.chunks = p.tiles;
-            hipLaunchKernelGGL(moments_reduce_kernel, dim3((unsigned)pairs), dim3(kMomThreads), 0, ctx->stream, m);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(moments, ctx->work + part_bytes, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
-            return VND_OK;
-        }
+        fused = k != nullptr && p.cg == 2;
     }
-    st = ensure_scratch(ctx, (size_t)std::max<int64_t>(n, 1) * t->C);
-    if (st != VND_OK) return st;
-    int64_t ws = 0;
+    int64_t ws = 0;                                        // unfused: the moments pass's own partial sums
     vnd_polar_moments_workspace_bytes(n, pairs, &ws);
     const size_t out_bytes = (size_t)pairs * kMoments * sizeof(double);
-    st = ensure_work(ctx, (size_t)ws + out_bytes);
-    if (st != VND_OK) return st;
-    char *work = ctx->work;
-    if (n > 0)
-        HIP_TRY(hipMemcpyAsync(ctx->scratch_x, x, (size_t)n * in_channels * sizeof(float), hipMemcpyHostToDevice,
-                               ctx->stream));
-    st = launch(ctx, t, ctx->scratch_x, ctx->scratch_y, 1, n, t->C, mode, ctx->stream, nullptr, in_channels);
-    if (st != VND_OK) return st;
-    st = vnd_polar_moments_f32_dev(ctx, ctx->scratch_y, n, pairs, (double *)(work + ws), work, ws, ctx->stream);
-    if (st != VND_OK) return st;
-    HIP_TRY(hipMemcpyAsync(moments, work + ws, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return VND_OK;
+    call.stage(fused ? (size_t)n * in_channels : (size_t)std::max<int64_t>(n, 1) * t->C);
+    call.carve({fused ? (size_t)p.tiles * pairs * kMoments * sizeof(double) : (size_t)ws, out_bytes});
+    double *partials = call.piece<double>(0), *m_dev = call.piece<double>(1);
+    call.up(call.staged_x(), x, (size_t)n * in_channels * sizeof(float), "x");
+    call.run([&] {
+        EpiFuse f{nullptr, 0, 0, 0, 0.0f, 0.0f, partials};
+        const vnd_status conv = launch(ctx, t, call.staged_x(), call.staged_y(), 1, n, t->C, mode, call.stream(), fused ? &f : nullptr, in_channels);
+        if (conv != VND_OK) return conv;
+        if (!fused) return vnd_polar_moments_f32_dev(ctx, call.staged_y(), n, pairs, m_dev, partials, ws, call.stream());
+        MArgs m{};
+        m.partials = partials; m.moments = m_dev; m.n = n; m.F = pairs; m.chunks = p.tiles;
+        hipLaunchKernelGGL(moments_reduce_kernel, dim3((unsigned)pairs), dim3(kMomThreads), 0, call.stream(), m);
+        HIP_TRY(hipGetLastError());
+        return VND_OK;
+    });
+    call.down(moments, m_dev, out_bytes, "moments");
+    return call.finish("vnd_scan_bank_f32_host");
 }
 
 // ------------------------------------------------------------------------------
@@ -589,21 +538,17 @@ vnd_status vnd_haas_f64_host(vnd_ctx *ctx, const float *x, double *y, int64_t ba
     const int64_t total = n + delay;
     if (batch == 0 || total == 0) return VND_OK;
     if (!y || (n > 0 && !x)) return fail(VND_ERR_INVALID, "null signal pointer");
-    HostLock lock(ctx->host_mutex);
-    DeviceScope on(ctx->device);
-    if (!on.ok) return fail(VND_ERR_HIP, "cannot select device %d", ctx->device);
+    HostCall call(ctx);
     const size_t in_bytes = (size_t)batch * n * in_channels * sizeof(float);
     const size_t out_bytes = (size_t)batch * total * 2 * sizeof(double);
-    st = ensure_work(ctx, out_bytes + std::max<size_t>(in_bytes, 16));
-    if (st != VND_OK) return st;
-    char *buf = ctx->work;
-    if (in_bytes) HIP_TRY(hipMemcpyAsync(buf + out_bytes, x, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    st = vnd_haas_f64_dev(ctx, (const float *)(buf + out_bytes), (double *)buf, batch, n, in_channels, delay,
-                          delayed_channel, ms_mode, use_width, width, ctx->stream);
-    if (st != VND_OK) return st;
-    HIP_TRY(hipMemcpyAsync(y, buf, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return VND_OK;
+    call.carve({out_bytes, in_bytes});                     // (n == 0: the kernel reads no input, only the delay's zeros go out)
+    double *y_dev = call.piece<double>(0);
+    float *x_dev = call.piece<float>(1);
+    call.up(x_dev, x, in_bytes, "x");
+    call.run([&] { return vnd_haas_f64_dev(ctx, x_dev, y_dev, batch, n, in_channels, delay, delayed_channel, ms_mode, use_width,
+                                           width, call.stream()); });
+    call.down(y, y_dev, out_bytes, "y");
+    return call.finish("vnd_haas_f64_host");
 }
 
 }  // extern "C"

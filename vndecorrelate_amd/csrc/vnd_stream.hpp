@@ -486,12 +486,8 @@ vnd_status vnd_stream_f32_dev(vnd_ctx *ctx, const vnd_taps *t, void *state, int6
     const bool epi = ms_encode || use_width;
     const StreamPlan p = make_stream_plan(ctx, t, batch, nout, (int)C, Cx, mode, epi);
     KArgs &a = sa.k;
-    a.y = y; a.taps = t->d_taps; a.taps_fast = t->d_taps_fast; a.taps_ord = t->d_taps_ord; a.fast_off = t->d_fast_off;
-    a.fast_even = t->d_fast_even; a.tap_off = t->d_tap_off;
-    a.seg_off = t->has_seg ? t->d_seg_off : nullptr;
-    a.seg_end = t->d_seg_end; a.seg_gain = t->d_seg_gain;
-    a.chan_flags = t->has_flags ? t->d_flags : nullptr;
-    a.n = nout; a.C = (int32_t)C; a.Cx = Cx; a.apply_gain = t->apply_gain;
+    a.y = y; a.n = nout; a.C = (int32_t)C; a.Cx = Cx;
+    table_args(a, t);
     a.epi_ms_encode = ms_encode ? 1 : 0; a.epi_use_width = use_width ? 1 : 0;
     a.epi_w_mid = (float)(1.0 - width); a.epi_w_side = (float)width;       // as the decorrelate stage passes the width
     a.nblocks = p.nblocks;
@@ -509,14 +505,7 @@ vnd_status vnd_stream_f32_dev(vnd_ctx *ctx, const vnd_taps *t, void *state, int6
         a.tiles = p.tiles; a.groups = p.groups; a.W = p.W;
         stream_kern_t k = stream_kernel(p, arithmetic_of(t, mode));
         if (!k) return fail(VND_ERR_UNSUPPORTED, "no stream kernel for this tile shape");
-        if (p.lds_bytes > 65536) {
-            std::lock_guard<std::mutex> g(ctx->raised_mutex);
-            size_t &have = ctx->raised[(const void *)k];
-            if (have < p.lds_bytes) {
-                HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
-                have = p.lds_bytes;
-            }
-        }
+        if (st = allow_lds(ctx, (const void *)k, p.lds_bytes); st != VND_OK) return st;
         hipLaunchKernelGGL(k, dim3(p.nblocks), dim3(kStreamThreads), p.lds_bytes, stream, sa);
     }
     HIP_TRY(hipGetLastError());
@@ -532,24 +521,17 @@ vnd_status vnd_stream_f32_host(vnd_ctx *ctx, const vnd_taps *t, void *state, int
     if (st != VND_OK) return st;
     const int64_t nout = *n_out;
     if (batch == 0 || (n_in == 0 && nout == 0)) return VND_OK;
-    HostLock lock(ctx->host_mutex);
-    DeviceScope on(ctx->device);
-    if (!on.ok) return fail(VND_ERR_HIP, "cannot select device %d", ctx->device);
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    HostCall call(ctx);
     const size_t x_bytes = (size_t)(batch * n_in * Cx) * sizeof(float);
     const size_t y_bytes = (size_t)(batch * nout * t->C) * sizeof(float);
-    st = ensure_work(ctx, up(x_bytes) + up(y_bytes));
-    if (st != VND_OK) return st;
-    float *x_dev = (float *)ctx->work;
-    float *y_dev = (float *)(ctx->work + up(x_bytes));
-    if (x_bytes) HIP_TRY(hipMemcpyAsync(x_dev, x, x_bytes, hipMemcpyHostToDevice, ctx->stream));
+    call.carve({x_bytes, y_bytes});
+    float *x_dev = call.piece<float>(0), *y_dev = call.piece<float>(1);
+    call.up(x_dev, x, x_bytes, "the chunk");
     int64_t got = 0;
-    st = vnd_stream_f32_dev(ctx, t, state, state_bytes, max_frames_per_call, x_dev, y_dev, batch, pos, n_in, Cx, final_, mode,
-                            ms_encode, use_width, width, &got, ctx->stream);
-    if (st != VND_OK) return st;
-    if (y_bytes) HIP_TRY(hipMemcpyAsync(y, y_dev, y_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return VND_OK;
+    call.run([&] { return vnd_stream_f32_dev(ctx, t, state, state_bytes, max_frames_per_call, x_dev, y_dev, batch, pos, n_in, Cx,
+                                             final_, mode, ms_encode, use_width, width, &got, call.stream()); });
+    call.down(y, y_dev, y_bytes, "y");
+    return call.finish("vnd_stream_f32_host");
 }
 
 }  // extern "C"
