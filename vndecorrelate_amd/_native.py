@@ -185,6 +185,22 @@ HAAS_SEARCH_SIGNATURES = {
 }
 HAAS_PAIRS_MAX = 1048560   # VND_HAAS_PAIRS_MAX: pairs per call
 
+# include/vnd_velvet_search.h: (signal, candidate) pairs of a pool, the batched velvet-noise optimiser's unit of work
+VELVET_SEARCH_SIGNATURES = {
+    'vnd_velvet_pairs_workspace_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]),
+    'vnd_velvet_pairs_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                                ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_int64, ctypes.c_void_p]),
+    'vnd_velvet_pairs_f32_host': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_f32p, ctypes.c_int32,
+                                                 ctypes.c_int64, ctypes.c_int32, _c_i32p, _c_i32p, ctypes.c_int32,
+                                                 ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]),
+}
+VELVET_PAIRS_MAX = 1048560           # VND_VELVET_PAIRS_MAX: pairs per call
+VELVET_PAIRS_MAX_TAP_INDEX = 4094    # VND_VELVET_PAIRS_MAX_TAP_INDEX: the largest tap index of a bank the kernel takes
+VELVET_PAIRS_TILE = 2048             # frames per workspace partial (vnd_velvet_pairs.hpp)
+VELVET_BANK_MAX_CANDIDATES = 32767   # vnd_taps_create takes at most 65535 channels: two per candidate
+
 # include/vnd_stream.h: chunked streaming of the tap sum, bound apart like the scan and analysis entry points
 _STREAM_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
                 ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
@@ -267,7 +283,8 @@ def load_library():
                                   + list(ANALYSIS_SIGNATURES.items()) + list(SCAN_SIGNATURES.items())
                                   + list(STREAM_SIGNATURES.items()) + list(HAAS_STREAM_SIGNATURES.items())
                                   + list(CORRELOGRAM_STREAM_SIGNATURES.items())
-                                  + list(HAAS_SEARCH_SIGNATURES.items())):
+                                  + list(HAAS_SEARCH_SIGNATURES.items())
+                                  + list(VELVET_SEARCH_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -822,6 +839,53 @@ def haas_pairs_device(ctx: 'Context', x_ptr: int, batch: int, n: int, channels: 
                                            float(width or 0.0), ctypes.c_void_p(moments_ptr),
                                            ctypes.c_void_p(workspace_ptr), workspace_bytes, ctypes.c_void_p(stream)),
            'vnd_haas_pairs_f64_dev')
+
+
+def velvet_pairs_workspace_bytes(n: int, n_pairs: int) -> int:
+    need = ctypes.c_int64()
+    _check(load_library().vnd_velvet_pairs_workspace_bytes(n, n_pairs, ctypes.byref(need)),
+           'vnd_velvet_pairs_workspace_bytes')
+    return need.value
+
+
+def _pair_indices(signals, candidates, what: str):
+    s = np.ascontiguousarray(signals, np.int64)
+    c = np.ascontiguousarray(candidates, np.int64)
+    i32 = np.iinfo(np.int32)
+    for v in (s, c):
+        if v.ndim != 1 or (v.size and (v.min() < i32.min or v.max() > i32.max)):
+            raise ValueError(f'{what} wants 1-D lists of int32 signal and candidate indices')
+    if s.size != c.size:
+        raise ValueError(f'{s.size} signal indices for {c.size} candidates')
+    return s.astype(np.int32), c.astype(np.int32)
+
+
+def velvet_pairs_host(ctx: 'Context', bank: 'TapTable', x: np.ndarray, signals, candidates, *,
+                      mode: int = MODE_EXACT) -> np.ndarray:
+    """``vnd_velvet_pairs_f32_host``: float64 ``(P, 8)`` polar moments of candidate ``c_p`` of ``bank`` (channels
+    ``2c``, ``2c + 1``) convolved with ``x[s_p]`` for each pair ``(s_p, c_p)``, from a C-contiguous float32
+    ``(batch, n, 1|2)`` pool in host memory."""
+    if x.dtype != np.float32 or not x.flags.c_contiguous or x.ndim != 3:
+        raise ValueError('velvet_pairs_host wants a C-contiguous float32 (batch, n, C) array')
+    s, c = _pair_indices(signals, candidates, 'velvet_pairs_host')
+    out = np.zeros((c.size, MOMENTS), np.float64)
+    _check(ctx._lib.vnd_velvet_pairs_f32_host(ctx.handle, bank.handle, _ptr(x, ctypes.c_float), x.shape[0], x.shape[1],
+                                              x.shape[2], _ptr(s, ctypes.c_int32), _ptr(c, ctypes.c_int32), c.size,
+                                              int(mode), _ptr(out, ctypes.c_double)),
+           'vnd_velvet_pairs_f32_host')
+    return out
+
+
+def velvet_pairs_device(ctx: 'Context', bank: 'TapTable', x_ptr: int, batch: int, n: int, channels: int,
+                        signals_ptr: int, candidates_ptr: int, n_pairs: int, moments_ptr: int, *,
+                        workspace_ptr: int, workspace_bytes: int, mode: int = MODE_EXACT, stream: int = 0):
+    """``vnd_velvet_pairs_f32_dev``: float64 ``(n_pairs, 8)`` moments from a float32 ``(batch, n, channels)`` pool and
+    int32 signal and candidate indices, all device buffers, enqueued on ``stream``."""
+    _check(ctx._lib.vnd_velvet_pairs_f32_dev(ctx.handle, bank.handle, ctypes.c_void_p(x_ptr), batch, n, channels,
+                                             ctypes.c_void_p(signals_ptr), ctypes.c_void_p(candidates_ptr), n_pairs,
+                                             int(mode), ctypes.c_void_p(moments_ptr), ctypes.c_void_p(workspace_ptr),
+                                             workspace_bytes, ctypes.c_void_p(stream)),
+           'vnd_velvet_pairs_f32_dev')
 
 
 def polar_moments_workspace_bytes(n: int, pairs: int) -> int:

@@ -73,8 +73,8 @@ def _gpu_present() -> bool:
 
 
 def device_route(setting: Optional[bool], covered: bool, refusal: str) -> bool:
-    """The rule of every ``set_*_device`` switch (this module's, ``set_haas_scan_device``, ``set_white_noise_device``)
-    for one call: ``False``, or a call without a device form (``covered`` False), runs on the host; ``True`` on the
+    """The rule of every ``set_*_device`` switch (this module's, ``set_haas_scan_device``, ``set_velvet_search_device``,
+    ``set_white_noise_device``) for one call: ``False``, or a call without a device form (``covered`` False), runs on the host; ``True`` on the
     device, raising ``RuntimeError(refusal)`` when there is none; ``None`` on the device when one is present."""
     if setting is False or not covered:
         return False

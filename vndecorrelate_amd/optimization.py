@@ -27,6 +27,8 @@ float32), scanned Haas scores to ~1e-12 (both float64; sum order and atan2 ulps 
 on which alone it depends.  ``optimize_haas_delay_batched`` runs the whole search, refinement
 included, for a pool of signals on the device: one launch over (signal, delay) pairs for the
 grid and one per round of a lockstep bounded minimiser (``bounded.py``) for the refinements.
+``optimize_velvet_noise_batched`` does the same for ``optimize_velvet_noise``: one launch over (signal, distinct table)
+pairs for the kappa grid and one bank and one launch per refinement round (``vnd_velvet_pairs_f32_dev``).
 """
 from __future__ import annotations
 
@@ -40,7 +42,7 @@ from . import _native, analysis
 from . import decorrelation as _dec
 from .bounded import minimize_bounded_lockstep, round_half_even
 from .decorrelation import Decorrelator, HaasEffect, VelvetNoise
-from .taps import class_path_bank_arrays
+from .taps import TapArrays, class_path_bank_arrays
 from .utils.dsp import EPSILON, LayoutMode, polar_coordinates, to_float32
 
 # one bank's device output is n * 2F floats: keep it under this many bytes per launch
@@ -603,3 +605,370 @@ def optimize_velvet_noise(*, input_signal: NDArray, sample_rate_hz: int, duratio
                            filtered_channels=(0,), mode='LR', seed=seed)
 
     return _search(input_signal, np.linspace(0.0, 1.0, grid_size), make, grid_size, weights)
+
+
+# ---- the batched velvet-noise optimiser -----------------------------------------------------------------------------
+# the pairs kernel's workspace is ceil(n / 2048) * P * 64 bytes: keep it under this many bytes per launch
+_VELVET_SCAN_BYTES = 1 << 30
+# optimize_velvet_noise_batched keeps at most this many bytes of its float32 pool on the device (else chunks of signals)
+_VELVET_POOL_BYTES = 4 << 30
+
+_velvet_search_device: Optional[bool] = None
+
+
+def set_velvet_search_device(enabled: Optional[bool]) -> None:
+    """Where :func:`optimize_velvet_noise_batched` runs.
+
+    ``None`` (default): on the GPU when a gfx950 device is present, otherwise :func:`optimize_velvet_noise` signal by
+    signal on the host.  ``True``: the device; a call raises ``RuntimeError`` when there is none.  ``False``: always
+    the host loop, whose kappa is the reference's."""
+    global _velvet_search_device
+    if enabled is not None and not isinstance(enabled, (bool, np.bool_)):
+        raise TypeError(f'set_velvet_search_device takes True, False or None, not {enabled!r}')
+    _velvet_search_device = None if enabled is None else bool(enabled)
+
+
+def _velvet_route() -> bool:
+    return analysis.device_route(_velvet_search_device, True,
+                                 'set_velvet_search_device(True): no gfx950 device (or no built extension) to run on')
+
+
+class VelvetBank:
+    """The candidates of :func:`optimize_velvet_noise` at one ``(sample_rate_hz, duration_seconds, num_impulses, seed,
+    segment_envelope)``, built for many kappa at once: ``VelvetNoise(log_distribution_strength=kappa, normalizer=None,
+    filtered_channels=(0,), mode='LR', num_outs=2)``.
+
+    ``_draw_taps`` makes its two PCG64 draws (signs, then offsets) whatever kappa is, so they are made once here; only
+    ``generate_log_distribution``, the cumulative marks and ``apply_log_distribution`` depend on kappa, and those are
+    the same float64 operations broadcast over a kappa axis (``np.cumsum`` along the row adds in the same order).
+    ``positions`` therefore equals ``_draw_taps`` position for position, and ``arrays`` equals
+    ``class_path_bank_arrays([VelvetNoise(kappa)._tap_member() ...])`` array for array.  (``seed=None`` draws once for
+    the whole bank, where ``VelvetNoise`` draws afresh per candidate.)"""
+
+    def __init__(self, *, sample_rate_hz, duration_seconds: float, num_impulses: int, seed=1,
+                 segment_envelope: Sequence[float] = _dec.DEFAULT_SEGMENT_ENVELOPE):
+        self.sample_rate_hz, self.duration_seconds, self.num_impulses = sample_rate_hz, duration_seconds, int(num_impulses)
+        self.fir_length = int(round(sample_rate_hz * duration_seconds))
+        if self.num_impulses >= self.fir_length * 0.2:            # VelvetNoise.__post_init__'s refusal
+            raise ValueError(f'Velvet Noise Filter of length {self.fir_length} with {self.num_impulses} impulses is '
+                             'not sparse.\n\tnum_impulses must be less than 20% the FIR length in samples.')
+        self.envelope = segment_envelope if segment_envelope else _dec.IDENTITY_ENVELOPE
+        self.apply_gain = self.envelope != _dec.IDENTITY_ENVELOPE
+        rng = np.random.default_rng(seed)
+        sign_draw = rng.uniform(low=0, high=1, size=(self.num_impulses, 1))
+        self.offset_draw = rng.uniform(low=0, high=1, size=(self.num_impulses + 1, 1))[:, 0]
+        signs = ((2 * np.round(sign_draw)) - 1)[:, 0]
+        self.mean_gap = sample_rate_hz / (self.num_impulses / duration_seconds)
+        # table order: per segment the negative taps, then the positive ones, each in generation order
+        num_segments = len(self.envelope)
+        segment = np.array([_dec._segment_index(k, self.num_impulses, num_segments) for k in range(self.num_impulses)])
+        positive = ((signs + 1) / 2).astype(np.int64)
+        self.order = np.lexsort((np.arange(self.num_impulses), positive, segment))
+        self.weights = np.where(positive[self.order] == 1, 1.0, -1.0).astype(np.float32)
+        self.seg_end = np.cumsum(np.bincount(segment, minlength=num_segments)).astype(np.int64)
+        self.seg_gain = np.asarray([float(self.envelope[s]) if self.apply_gain else 1.0 for s in range(num_segments)],
+                                   np.float32)
+
+    def positions(self, kappas) -> NDArray[np.int32]:
+        """``(K, num_impulses + 1)`` int32: row j is ``_draw_taps(..., strength=kappas[j])[0][:, 0]``."""
+        kappa = np.asarray(kappas, np.float64).reshape(-1, 1)
+        size = self.num_impulses
+        ramp = np.arange(size + 1.0) / size
+        weights = (10.0 ** (2.0 * kappa * ramp)) / (100.0 * ((1.0 + (kappa * 99.0)) / 100.0))
+        marks = np.cumsum(weights, axis=1)
+        marks[kappa[:, 0] == 0.0] -= 1.0
+        marks *= self.fir_length / marks[:, -1:]
+        spread = np.fmax(0.0, weights * self.mean_gap - 1)
+        return np.round(self.offset_draw * spread + marks).astype(np.int32)
+
+    def keys(self, kappas) -> NDArray[np.int32]:
+        """``(K, num_impulses)``: what a candidate's table depends on kappa through - its taps' positions."""
+        return self.positions(kappas)[:, :self.num_impulses]
+
+    def arrays_of_keys(self, keys) -> TapArrays:
+        """The class-path bank of the candidates whose :meth:`keys` rows are ``keys``: candidate t owns channels
+        ``2t`` (filtered) and ``2t + 1`` (copied through)."""
+        keys = np.asarray(keys, np.int32).reshape(-1, self.num_impulses)
+        count, taps, segs = keys.shape[0], self.num_impulses, len(self.seg_end)
+        if count == 0:
+            return class_path_bank_arrays([])
+        first = np.arange(count, dtype=np.int64)
+        tap_offsets = np.concatenate([[0], np.repeat((first + 1) * taps, 2)])
+        seg_offsets = np.concatenate([[0], np.repeat((first + 1) * segs, 2)])
+        return TapArrays(tap_offsets.astype(np.int32), np.ascontiguousarray(keys[:, self.order]).reshape(-1),
+                         np.tile(self.weights, count), seg_offsets.astype(np.int32),
+                         (first[:, None] * taps + self.seg_end).reshape(-1).astype(np.int32),
+                         np.tile(self.seg_gain, count), np.tile(np.array([0, 1], np.uint8), count), self.apply_gain)
+
+    def arrays(self, kappas) -> TapArrays:
+        return self.arrays_of_keys(self.keys(kappas))
+
+
+def velvet_bank_arrays(kappas, *, sample_rate_hz, duration_seconds: float, num_impulses: int, seed=1,
+                       segment_envelope: Sequence[float] = _dec.DEFAULT_SEGMENT_ENVELOPE) -> TapArrays:
+    """The ``TapArrays`` of :func:`optimize_velvet_noise`'s candidates at the K values ``kappas``, vectorised over
+    kappa (:class:`VelvetBank`): equal to ``class_path_bank_arrays([VelvetNoise(kappa)._tap_member() ...])``."""
+    return VelvetBank(sample_rate_hz=sample_rate_hz, duration_seconds=duration_seconds, num_impulses=num_impulses,
+                      seed=seed, segment_envelope=segment_envelope).arrays(kappas)
+
+
+@dataclass
+class VelvetSearchStats:
+    """The work of one :func:`optimize_velvet_noise_batched` call (tools, tests), in the shape of
+    :class:`HaasSearchStats`.  ``rounds`` counts the lockstep refinement's rounds, the first points of every minimum
+    included; ``pairs_per_round`` / ``tables_per_round`` the distinct (signal, table) pairs and distinct tables each
+    round scored; ``grid_pairs`` / ``grid_tables`` those of the grid; ``evaluations[b]`` the objective evaluations of
+    signal b's refinements; ``minimum_signal``, ``minimum_nfev``, ``minimum_x`` and ``minimum_fun`` the signal, ``nfev``,
+    kappa and score of each refined minimum in order; ``evaluated`` per round the (signal, kappa) of every lane; ``pool_uploads`` how many chunks of the pool went
+    to the device.  Device route: ``grid_launches`` and ``launches`` count ``vnd_velvet_pairs_f32_dev`` calls,
+    ``launch_pairs`` / ``launch_ms`` / ``launch_pool`` their pairs, device-event milliseconds and pool pointer, and
+    ``bank_seconds`` the host time spent building banks (their arrays, ``TapTable.create``'s device images and uploads)."""
+    route: str
+    signals: int
+    rounds: int = 0
+    pairs_per_round: List[int] = field(default_factory=list)
+    tables_per_round: List[int] = field(default_factory=list)
+    grid_pairs: int = 0
+    grid_tables: int = 0
+    evaluations: NDArray = field(default_factory=lambda: np.zeros(0, np.int64))
+    minimum_signal: NDArray = field(default_factory=lambda: np.zeros(0, np.int64))
+    minimum_nfev: NDArray = field(default_factory=lambda: np.zeros(0, np.int64))
+    minimum_x: NDArray = field(default_factory=lambda: np.zeros(0, np.float64))
+    minimum_fun: NDArray = field(default_factory=lambda: np.zeros(0, np.float64))
+    evaluated: List[Tuple[NDArray, NDArray]] = field(default_factory=list)
+    pool_uploads: int = 0
+    grid_launches: int = 0
+    launches: int = 0
+    launch_pairs: List[int] = field(default_factory=list)
+    launch_ms: List[float] = field(default_factory=list)
+    launch_pool: List[int] = field(default_factory=list)
+    bank_seconds: float = 0.0
+
+
+last_velvet_search: Optional[VelvetSearchStats] = None   # the last optimize_velvet_noise_batched call's work
+
+
+def _distinct_rows(keys: NDArray) -> Tuple[NDArray, NDArray]:
+    """``(distinct rows in lexicographic order, index of each row among them)``: tables deduplicated by content."""
+    unique, inverse = np.unique(keys, axis=0, return_inverse=True)
+    return unique, np.asarray(inverse, np.int64).reshape(-1)
+
+
+def velvet_search(score_pairs: Callable[[NDArray, NDArray, NDArray], NDArray], num_signals: int, kappas: NDArray,
+                  table_keys: Callable[[NDArray], NDArray], grid_size: int,
+                  stats: Optional[VelvetSearchStats] = None) -> NDArray[np.float64]:
+    """``optimize_velvet_noise``'s search for ``num_signals`` signals at once, given a scorer.
+
+    ``table_keys(values)`` gives one integer row per value: everything the candidate's table depends on the value
+    through (:meth:`VelvetBank.keys`); equal rows are one table.  ``score_pairs(signals, tables, keys)`` returns the
+    objective of table ``keys[tables[p]]`` on signal ``signals[p]`` for distinct (signal, table) pairs sorted by
+    (signal, table); ``keys`` holds the call's distinct tables.  The grid is one call over every signal and distinct
+    grid table; each refinement round is one call over the distinct pairs its lanes ask for.  Per signal: the grid's
+    local minima (:func:`get_local_minima`), each refined over its neighbours by :func:`minimize_bounded_lockstep`
+    (SciPy's bounded method, ``xatol=1e-4``), and :func:`optimize_local_minima`'s choice among them."""
+    kappas = np.asarray(kappas, np.float64)
+    stats = VelvetSearchStats(route='custom', signals=num_signals) if stats is None else stats
+
+    def score(signals, tables, keys):
+        return np.asarray(score_pairs(signals, tables, keys), np.float64)
+
+    keys, inverse = _distinct_rows(np.asarray(table_keys(kappas)))
+    count = keys.shape[0]
+    launches_before = stats.launches
+    grid = score(np.repeat(np.arange(num_signals, dtype=np.int64), count),
+                 np.tile(np.arange(count, dtype=np.int64), num_signals), keys)
+    scores = grid.reshape(num_signals, count)[:, inverse]
+    stats.grid_pairs += num_signals * count
+    stats.grid_tables = count                            # (the same for every chunk of a pool)
+    stats.grid_launches += stats.launches - launches_before
+    lane_signal, lower, upper = [], [], []
+    for b in range(num_signals):
+        for i in get_local_minima(scores[b], grid_size):
+            lane_signal.append(b)
+            lower.append(kappas[max(0, i - 1)])
+            upper.append(kappas[min(grid_size - 1, i + 1)])
+    lane_signal = np.asarray(lane_signal, np.int64)
+
+    def objective(lanes, x):
+        tables, which = _distinct_rows(np.asarray(table_keys(x)))
+        pairs, back = np.unique(lane_signal[lanes] * tables.shape[0] + which, return_inverse=True)
+        stats.pairs_per_round.append(int(pairs.size))
+        stats.tables_per_round.append(int(tables.shape[0]))
+        stats.evaluated.append((lane_signal[lanes] + stats.evaluations.size, np.array(x, np.float64)))
+        return score(pairs // tables.shape[0], pairs % tables.shape[0], tables)[np.asarray(back).reshape(-1)]
+
+    result = minimize_bounded_lockstep(objective, lower, upper, xatol=1e-4)
+    stats.rounds += result.rounds
+    best_kappa, best_score = np.zeros(num_signals), np.full(num_signals, np.inf)
+    evaluations = np.zeros(num_signals, np.int64)
+    for lane, b in enumerate(lane_signal):               # minima in order, strict <, from (0.0, inf)
+        evaluations[b] += result.nfev[lane]
+        if result.fun[lane] < best_score[b]:
+            best_score[b], best_kappa[b] = result.fun[lane], result.x[lane]
+    stats.minimum_signal = np.concatenate([stats.minimum_signal, lane_signal + stats.evaluations.size])
+    stats.minimum_nfev = np.concatenate([stats.minimum_nfev, result.nfev])
+    stats.minimum_x = np.concatenate([stats.minimum_x, result.x])
+    stats.minimum_fun = np.concatenate([stats.minimum_fun, result.fun])
+    stats.evaluations = np.concatenate([stats.evaluations, evaluations])
+    return best_kappa
+
+
+class _VelvetUnsupported(Exception):
+    """A bank outside the pairs kernel's scope (largest tap index): the call takes the host route."""
+
+
+class _DeviceVelvetScorer:
+    """A :func:`velvet_search` scorer over a float32 ``(B, n, C)`` pool resident on the device: per call one bank of
+    the call's distinct tables (:meth:`VelvetBank.arrays_of_keys`) and one ``vnd_velvet_pairs_f32_dev`` launch (more
+    only past the workspace budget, the pair limit or the 32767 candidates a tap table holds); tables and pairs go up,
+    moments come down, and ``scores_from_moments`` turns them into scores.  Always ``VND_MODE_EXACT``."""
+
+    def __init__(self, ctx, pool, weights: dict, bank: VelvetBank, stats: VelvetSearchStats):
+        self.ctx, self.pool, self.weights, self.bank, self.stats = ctx, pool, weights, bank, stats
+        import torch
+        self.torch = torch
+        self.batch, self.n, self.channels = (int(v) for v in pool.shape)
+        self.workspace = None
+        tiles = (self.n + _native.VELVET_PAIRS_TILE - 1) // _native.VELVET_PAIRS_TILE
+        self.per_launch = min(_native.VELVET_PAIRS_MAX, max(1, _VELVET_SCAN_BYTES // (tiles * 64)))
+
+    def _launch(self, table, signals, candidates):
+        torch, stats = self.torch, self.stats
+        dev = self.pool.device
+        count = int(signals.size)
+        ws = _native.velvet_pairs_workspace_bytes(self.n, count)
+        if self.workspace is None or self.workspace.numel() < ws:
+            self.workspace = None                                  # the old one goes before the new one comes
+            self.workspace = torch.empty(max(ws, 1), dtype=torch.uint8, device=dev)
+        pairs = torch.from_numpy(np.stack([signals, candidates]).astype(np.int32)).to(dev)
+        moments = torch.empty((count, _native.MOMENTS), dtype=torch.float64, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        begin, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        begin.record(stream)
+        _native.velvet_pairs_device(self.ctx, table, self.pool.data_ptr(), self.batch, self.n, self.channels,
+                                    pairs[0].data_ptr(), pairs[1].data_ptr(), count, moments.data_ptr(),
+                                    workspace_ptr=self.workspace.data_ptr(), workspace_bytes=ws,
+                                    mode=_native.MODE_EXACT, stream=stream.cuda_stream)
+        end.record(stream)
+        out = moments.cpu().numpy()                                # (synchronises the stream)
+        stats.launches += 1
+        stats.launch_pairs.append(count)
+        stats.launch_ms.append(float(begin.elapsed_time(end)))
+        stats.launch_pool.append(int(self.pool.data_ptr()))
+        return out
+
+    def _bank_rows(self, keys, signals, candidates):
+        """Moments of the pairs (signals[p], candidates[p]) of one bank, built from its tables' ``keys``."""
+        import time
+        started = time.perf_counter()
+        arrays = self.bank.arrays_of_keys(keys)
+        table = _native.TapTable.create(self.ctx, arrays.tap_offsets, arrays.tap_index, arrays.tap_weight,
+                                        **arrays.kwargs())
+        self.stats.bank_seconds += time.perf_counter() - started       # arrays, device images and their uploads
+        try:
+            rows = [self._launch(table, signals[first:first + self.per_launch], candidates[first:first + self.per_launch])
+                    for first in range(0, signals.size, self.per_launch)]
+        finally:
+            table.close()
+        return np.concatenate(rows)
+
+    def __call__(self, signals, tables, keys):
+        if keys.size and int(keys.max()) > _native.VELVET_PAIRS_MAX_TAP_INDEX:
+            raise _VelvetUnsupported(f'tap index {int(keys.max())} is above {_native.VELVET_PAIRS_MAX_TAP_INDEX}')
+        moments = np.zeros((signals.size, _native.MOMENTS))
+        # A tap table holds at most VELVET_BANK_MAX_CANDIDATES candidates: more distinct tables go in several banks.  A row
+        # does not depend on its candidate's bank or place in it, so the split changes no bit.
+        limit = _native.VELVET_BANK_MAX_CANDIDATES
+        for first in range(0, keys.shape[0], limit):
+            mine = np.flatnonzero((tables >= first) & (tables < first + limit))      # (keeps the (signal, table) order)
+            if mine.size:
+                moments[mine] = self._bank_rows(keys[first:first + limit], signals[mine], tables[mine] - first)
+        return scores_from_moments(moments, **self.weights)
+
+
+def optimize_velvet_noise_batched(*, input_signals, sample_rate_hz: int, duration_seconds: float, num_impulses: int,
+                                  seed: int = 1, grid_size: int = 400, angle_limit: float = np.pi / 4,
+                                  lambda_mean: float = 5.0, lambda_skew: float = 2.0, lambda_correlation: float = 15.0,
+                                  lambda_penalty: float = 1e3) -> NDArray[np.float64]:
+    """:func:`optimize_velvet_noise` for every signal of a pool: ``(B,)`` float64 ``log_distribution_strength``.
+
+    ``input_signals`` is a stereo pool ``(B, n, 2)`` or a mono pool ``(B, n)`` with n > 0: a NumPy array of any real
+    dtype (cast as ``to_float32`` casts it) or a CUDA torch tensor, read in place.  B = 0 gives an empty array.
+
+    Device route (:func:`set_velvet_search_device`: ``None`` with a gfx950 device, or ``True``): the pool goes up once
+    (in chunks of whole signals past ``_VELVET_POOL_BYTES``) and stays there.  The kappa grid's tables are built at
+    once (:class:`VelvetBank`) and deduplicated by content; the grid is one launch over every (signal, distinct table)
+    pair (more only past the workspace budget or the pair limit).  The local minima of every signal
+    (:func:`get_local_minima`) are then refined together by :func:`minimize_bounded_lockstep` (``xatol=1e-4``): each
+    round builds one bank of the round's distinct tables and makes one launch over its distinct (signal, table) pairs
+    (:func:`velvet_search`, ``vnd_velvet_pairs_f32_dev``).  Only tables and pairs go up and moments come down;
+    ``scores_from_moments`` scores them; the choice among a signal's minima is :func:`optimize_local_minima`'s.  The
+    kernel runs in ``VND_MODE_EXACT`` whatever ``set_default_mode`` says: every frame is the exact-mode
+    ``VelvetNoise.convolve`` output bit for bit, polar maths in float32, sums in float64.  A filter whose taps reach
+    past ``VND_VELVET_PAIRS_MAX_TAP_INDEX`` (4094 frames) is outside the kernel: such a call takes the host route.
+
+    **kappa may differ from** :func:`optimize_velvet_noise`'s, whose refinement runs ``symmetry_aware_objective`` on the
+    host and reproduces the reference's kappa.  The objective is piecewise constant in kappa (tap positions are rounded
+    to integers) and Brent's parabolic steps use the score values themselves, so score differences far below any
+    tolerance steer the minimiser elsewhere.  Measured on the ``viola_excerpt`` fixture at grid 9, feeding the exact
+    frames through this route's arithmetic (float32 element maths, float64 sums): every score moved by at most 5.6e-5 on
+    scores of about 619 and the grid's local minima stayed [2, 4, 6], but ``nfev`` became [12, 16, 11] against the
+    host's [12, 15, 20] and kappa 0.75965 against the reference's 0.75804 - with a lower score, 618.306 against
+    618.404.  The returned kappa is, bit for bit, what ``optimize_local_minima`` returns through SciPy when its
+    objective is this route's device score.  A caller who needs the reference's kappa uses
+    :func:`optimize_velvet_noise`.
+
+    Host route (``False``, or ``None`` without a device): :func:`optimize_velvet_noise` signal by signal.
+    ``last_velvet_search`` records the call's work (:class:`VelvetSearchStats`)."""
+    global last_velvet_search
+    weights = dict(angle_limit=angle_limit, lambda_mean=lambda_mean, lambda_skew=lambda_skew,
+                   lambda_correlation=lambda_correlation, lambda_penalty=lambda_penalty)
+    x, is_torch = _haas_pool(input_signals)
+    batch = int(x.shape[0])
+    if batch == 0:
+        last_velvet_search = VelvetSearchStats(route='none', signals=0)
+        return np.zeros(0, np.float64)
+
+    def on_host():
+        global last_velvet_search
+        pool = x.detach().cpu().numpy() if is_torch else x
+        last_velvet_search = VelvetSearchStats(route='host', signals=batch)
+        return np.array([optimize_velvet_noise(input_signal=pool[b], sample_rate_hz=sample_rate_hz,
+                                               duration_seconds=duration_seconds, num_impulses=num_impulses, seed=seed,
+                                               grid_size=grid_size, **weights) for b in range(batch)], np.float64)
+
+    if not _velvet_route():
+        return on_host()
+    bank = VelvetBank(sample_rate_hz=sample_rate_hz, duration_seconds=duration_seconds, num_impulses=num_impulses,
+                      seed=seed)
+    kappas = np.linspace(0.0, 1.0, grid_size)
+    if int(bank.keys(kappas).max()) > _native.VELVET_PAIRS_MAX_TAP_INDEX:      # outside the kernel's window: nothing printed yet
+        return on_host()
+    stats = VelvetSearchStats(route='device', signals=batch)
+    last_velvet_search = stats
+    print('Starting Grid Scan')
+    print('Starting Local Minima optimization')
+    import torch
+    try:
+        if is_torch:
+            if not x.is_cuda:
+                raise ValueError('a torch pool must be a device tensor (NumPy arrays are uploaded)')
+            ctx = _native.context_for(x.device.index if x.device.index is not None else torch.cuda.current_device())
+            pool = x.reshape(batch, x.shape[1], -1)
+            pool = (pool if pool.dtype == torch.float32 else pool.to(torch.float32)).contiguous()
+            return velvet_search(_DeviceVelvetScorer(ctx, pool, weights, bank, stats), batch, kappas, bank.keys,
+                                 grid_size, stats)
+        ctx = _native.default_context()
+        dev = torch.device('cuda', ctx.device)
+        x3 = x.reshape(batch, x.shape[1], -1)
+        per_chunk = max(1, _VELVET_POOL_BYTES // (x3.shape[1] * x3.shape[2] * 4))
+        out = []
+        for first in range(0, batch, per_chunk):
+            part = np.ascontiguousarray(to_float32(x3[first:first + per_chunk]))
+            pool = torch.from_numpy(part).to(dev)
+            stats.pool_uploads += 1
+            out.append(velvet_search(_DeviceVelvetScorer(ctx, pool, weights, bank, stats), part.shape[0], kappas,
+                                     bank.keys, grid_size, stats))
+        return np.concatenate(out)
+    except _VelvetUnsupported:
+        return on_host()
