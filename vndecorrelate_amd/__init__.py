@@ -19,9 +19,12 @@ from .decorrelation import (  # noqa: F401
     convolve_velvet_noise_bank,
     convolve_velvet_noise_batched,
     decorrelate_bank,
+    decorrelate_each,
+    each_covers,
     generate_velvet_noise,
     set_default_mode,
     set_device_epilogue,
+    set_each_device,
     set_white_noise_device,
 )
 from .analysis import cross_correlogram_batched, set_correlogram_device  # noqa: F401

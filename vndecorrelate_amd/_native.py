@@ -201,6 +201,30 @@ VELVET_PAIRS_MAX_TAP_INDEX = 4094    # VND_VELVET_PAIRS_MAX_TAP_INDEX: the large
 VELVET_PAIRS_TILE = 2048             # frames per workspace partial (vnd_velvet_pairs.hpp)
 VELVET_BANK_MAX_CANDIDATES = 32767   # vnd_taps_create takes at most 65535 channels: two per candidate
 
+# include/vnd_each.h: a pool through one filter or one delay per signal
+_EACH_STAGE = [ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_float]
+EACH_SIGNATURES = {
+    'vnd_convolve_each_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+                                                 ctypes.c_int32, ctypes.c_void_p]),
+    'vnd_convolve_each_f32_host': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_f32p, _c_i32p, _c_f32p,
+                                                  ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
+    'vnd_decorrelate_each_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+                                                    ctypes.c_int32] + _EACH_STAGE
+                                     + [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    'vnd_decorrelate_each_f32_host': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_f32p, _c_i32p, _c_f32p,
+                                                     ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]
+                                      + _EACH_STAGE),
+    'vnd_haas_each_f64_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                             ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                             ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
+                                             ctypes.c_void_p]),
+    'vnd_haas_each_f64_host': (ctypes.c_int, [ctypes.c_void_p, _c_f32p, ctypes.POINTER(ctypes.c_double), ctypes.c_int64,
+                                              ctypes.c_int64, ctypes.c_int32, _c_i32p, ctypes.c_int32, ctypes.c_int32,
+                                              ctypes.c_int32, ctypes.c_int32, ctypes.c_double]),
+}
+
 # include/vnd_stream.h: chunked streaming of the tap sum, bound apart like the scan and analysis entry points
 _STREAM_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
                 ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
@@ -284,7 +308,8 @@ def load_library():
                                   + list(STREAM_SIGNATURES.items()) + list(HAAS_STREAM_SIGNATURES.items())
                                   + list(CORRELOGRAM_STREAM_SIGNATURES.items())
                                   + list(HAAS_SEARCH_SIGNATURES.items())
-                                  + list(VELVET_SEARCH_SIGNATURES.items())):
+                                  + list(VELVET_SEARCH_SIGNATURES.items())
+                                  + list(EACH_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -886,6 +911,88 @@ def velvet_pairs_device(ctx: 'Context', bank: 'TapTable', x_ptr: int, batch: int
                                              int(mode), ctypes.c_void_p(moments_ptr), ctypes.c_void_p(workspace_ptr),
                                              workspace_bytes, ctypes.c_void_p(stream)),
            'vnd_velvet_pairs_f32_dev')
+
+
+def _each_host_args(x: np.ndarray, per_signal, what: str, name: str):
+    if x.dtype != np.float32 or not x.flags.c_contiguous or x.ndim != 3:
+        raise ValueError(f'{what} wants a C-contiguous float32 (batch, n, C) array')
+    v = np.ascontiguousarray(per_signal, np.int64)
+    i32 = np.iinfo(np.int32)
+    if v.ndim != 1 or v.size != x.shape[0] or (v.size and (v.min() < i32.min or v.max() > i32.max)):
+        raise ValueError(f'{what} wants one int32 {name} per signal: {x.shape[0]} signals, {name} of shape {v.shape}')
+    return v.astype(np.int32)
+
+
+def _stage_tail(ms_encode: bool, width, normalize, eps: float):
+    return int(bool(ms_encode)), int(width is not None), float(width or 0.0), int(normalize), float(eps)
+
+
+def convolve_each_host(ctx: 'Context', bank: 'TapTable', x: np.ndarray, tables, *, mode: int = MODE_EXACT) -> np.ndarray:
+    """``vnd_convolve_each_f32_host``: float32 ``(batch, n, 2)``, row b the convolution of ``x[b]`` with candidate
+    ``tables[b]`` of ``bank`` (channels ``2t``, ``2t + 1``), from a C-contiguous float32 ``(batch, n, 1|2)`` pool in
+    host memory."""
+    t = _each_host_args(x, tables, 'convolve_each_host', 'table index')
+    y = np.empty(x.shape[:2] + (2,), np.float32)
+    _check(ctx._lib.vnd_convolve_each_f32_host(ctx.handle, bank.handle, _ptr(x, ctypes.c_float), _ptr(t, ctypes.c_int32),
+                                               _ptr(y, ctypes.c_float), x.shape[0], x.shape[1], x.shape[2], int(mode)),
+           'vnd_convolve_each_f32_host')
+    return y
+
+
+def convolve_each_device(ctx: 'Context', bank: 'TapTable', x_ptr: int, tables_ptr: int, y_ptr: int, batch: int, n: int,
+                         channels: int, *, mode: int = MODE_EXACT, stream: int = 0):
+    """``vnd_convolve_each_f32_dev``: float32 ``(batch, n, channels)`` pool, int32 ``(batch,)`` table indices and the
+    float32 ``(batch, n, 2)`` result, all device buffers, enqueued on ``stream``."""
+    _check(ctx._lib.vnd_convolve_each_f32_dev(ctx.handle, bank.handle, ctypes.c_void_p(x_ptr), ctypes.c_void_p(tables_ptr),
+                                              ctypes.c_void_p(y_ptr), batch, n, channels, int(mode),
+                                              ctypes.c_void_p(stream)), 'vnd_convolve_each_f32_dev')
+
+
+def decorrelate_each_host(ctx: 'Context', bank: 'TapTable', x: np.ndarray, tables, *, ms_encode: bool, width, normalize,
+                          eps: float = 1e-10, mode: int = MODE_EXACT) -> np.ndarray:
+    """``vnd_decorrelate_each_f32_host``: :func:`convolve_each_host` and the decorrelate stage behind it (``normalize``:
+    False/True or one of the ``NORMALIZE_*`` values); the stage settings are the call's, not per signal."""
+    t = _each_host_args(x, tables, 'decorrelate_each_host', 'table index')
+    y = np.empty(x.shape[:2] + (2,), np.float32)
+    _check(ctx._lib.vnd_decorrelate_each_f32_host(ctx.handle, bank.handle, _ptr(x, ctypes.c_float), _ptr(t, ctypes.c_int32),
+                                                  _ptr(y, ctypes.c_float), x.shape[0], x.shape[1], x.shape[2], int(mode),
+                                                  *_stage_tail(ms_encode, width, normalize, eps)),
+           'vnd_decorrelate_each_f32_host')
+    return y
+
+
+def decorrelate_each_device(ctx: 'Context', bank: 'TapTable', x_ptr: int, tables_ptr: int, y_ptr: int, batch: int, n: int,
+                            channels: int, *, ms_encode: bool, width, normalize, workspace_ptr: int, workspace_bytes: int,
+                            eps: float = 1e-10, mode: int = MODE_EXACT, stream: int = 0):
+    """``vnd_decorrelate_each_f32_dev``; the workspace is ``decorrelate_workspace_bytes(batch, n, 2)``'s."""
+    _check(ctx._lib.vnd_decorrelate_each_f32_dev(ctx.handle, bank.handle, ctypes.c_void_p(x_ptr),
+                                                 ctypes.c_void_p(tables_ptr), ctypes.c_void_p(y_ptr), batch, n, channels,
+                                                 int(mode), *_stage_tail(ms_encode, width, normalize, eps),
+                                                 ctypes.c_void_p(workspace_ptr), workspace_bytes, ctypes.c_void_p(stream)),
+           'vnd_decorrelate_each_f32_dev')
+
+
+def haas_each_host(ctx: 'Context', x: np.ndarray, delays, *, max_delay: int, delayed_channel: int, ms_mode: bool,
+                   width) -> np.ndarray:
+    """``vnd_haas_each_f64_host``: float64 ``(batch, n + max_delay, 2)``; rows ``[0, n + delays[b])`` of signal b are
+    ``HaasEffect`` with that delay, the rest zeros.  x: a C-contiguous float32 ``(batch, n, 1|2)`` pool."""
+    d = _each_host_args(x, delays, 'haas_each_host', 'delay')
+    y = np.empty((x.shape[0], x.shape[1] + int(max_delay), 2), np.float64)
+    _check(ctx._lib.vnd_haas_each_f64_host(ctx.handle, _ptr(x, ctypes.c_float), _ptr(y, ctypes.c_double), x.shape[0],
+                                           x.shape[1], x.shape[2], _ptr(d, ctypes.c_int32), int(max_delay),
+                                           int(delayed_channel), int(bool(ms_mode)), int(width is not None),
+                                           float(width or 0.0)), 'vnd_haas_each_f64_host')
+    return y
+
+
+def haas_each_device(ctx: 'Context', x_ptr: int, y_ptr: int, batch: int, n: int, channels: int, delays_ptr: int, *,
+                     max_delay: int, delayed_channel: int, ms_mode: bool, width, stream: int = 0):
+    """``vnd_haas_each_f64_dev``: float32 ``(batch, n, channels)`` pool, int32 ``(batch,)`` delays and the float64
+    ``(batch, n + max_delay, 2)`` result, all device buffers, enqueued on ``stream``."""
+    _check(ctx._lib.vnd_haas_each_f64_dev(ctx.handle, ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr), batch, n, channels,
+                                          ctypes.c_void_p(delays_ptr), int(max_delay), int(delayed_channel),
+                                          int(bool(ms_mode)), int(width is not None), float(width or 0.0),
+                                          ctypes.c_void_p(stream)), 'vnd_haas_each_f64_dev')
 
 
 def polar_moments_workspace_bytes(n: int, pairs: int) -> int:

@@ -10,6 +10,7 @@
 //   vnd_correlogram_stream.hpp  cross_correlogram streamed block by block (include/vnd_correlogram_stream.h)
 //   vnd_haas_scan.hpp    the Haas-delay optimiser's scan (include/vnd_scan.h) and its pool pairs (include/vnd_haas_search.h)
 //   vnd_velvet_pairs.hpp the velvet-noise optimiser's scan over (signal, candidate) pairs of a pool (include/vnd_velvet_search.h)
+//   vnd_each.hpp         a pool through one filter or one delay per signal (include/vnd_each.h)
 //   vnd_stream.hpp       chunked streaming of the tap sum (include/vnd_stream.h)
 //   vnd_haas_stream.hpp  chunked streaming of the HaasEffect delay (include/vnd_haas_stream.h)
 #include "vnd_objects.hpp"
@@ -403,6 +404,7 @@ vnd_status vnd_prepare_launch(vnd_ctx *ctx, const vnd_taps *t, int64_t batch, in
 #include "vnd_correlogram_stream.hpp"
 #include "vnd_haas_scan.hpp"
 #include "vnd_velvet_pairs.hpp"
+#include "vnd_each.hpp"
 #include "vnd_stream.hpp"
 #include "vnd_haas_stream.hpp"
 #include "vnd_hooks.hpp"

@@ -47,7 +47,7 @@ import numpy as np
 from numpy.typing import NDArray
 
 from . import _native, analysis
-from .taps import TapArrays, class_path_arrays, concat_tap_arrays, function_path_arrays
+from .taps import TapArrays, class_path_arrays, class_path_bank_arrays, concat_tap_arrays, function_path_arrays
 from .utils.dsp import (
     IDENTITY_ENVELOPE,
     LayoutMode,
@@ -949,6 +949,355 @@ class WhiteNoise(Decorrelator):
                                        stream=torch.cuda.current_stream(device).cuda_stream)
             torch.from_numpy(out[first:first + len(part)]).copy_(yd)
         return out
+
+
+# ----------------------------------------------------------------------------
+# decorrelate_each: a pool through one decorrelator PER SIGNAL (include/vnd_each.h) - the application side of
+# optimize_velvet_noise_batched / optimize_haas_delay_batched, which return one kappa or one delay per signal
+# ----------------------------------------------------------------------------
+# the padded float64 block of the Haas route, (B, n + max delay, 2): above this many bytes the call takes the host loop
+_EACH_HAAS_BYTES = 4 << 30
+
+_each_device: Optional[bool] = None
+
+
+def set_each_device(enabled: Optional[bool]) -> None:
+    """Where :func:`decorrelate_each` runs.
+
+    ``None`` (default): on the GPU when a gfx950 device is present and the call is covered (:func:`each_covers`),
+    otherwise the loop ``[d.decorrelate(x_b) ...]``.  ``True``: the device for every covered call; ``RuntimeError`` when
+    there is none.  ``False``: always the loop."""
+    global _each_device
+    if enabled is not None and not isinstance(enabled, (bool, np.bool_)):
+        raise TypeError(f'set_each_device takes True, False or None, not {enabled!r}')
+    _each_device = None if enabled is None else bool(enabled)
+
+
+@dataclass
+class EachStats:
+    """The work of one :func:`decorrelate_each` call (tools, tests), after ``optimization.VelvetSearchStats``."""
+    route: str                                            # 'device', 'host' (the loop) or 'none' (an empty pool)
+    kind: str = ''                                        # 'velvet' or 'haas' on the device route
+    signals: int = 0
+    tables: int = 0                                       # velvet: distinct tap tables among the signals'
+    launches: int = 0                                     # calls into the library
+    launch_signals: List[int] = field(default_factory=list)
+    launch_tables: List[int] = field(default_factory=list)   # velvet: candidates in each call's bank
+    launch_pool: List[int] = field(default_factory=list)  # a tensor pool: the device address each call read its signals at
+    pool_uploads: int = 0                                 # a NumPy pool: the calls that took it up from host memory
+    result_downloads: int = 0                             # ... and brought their result back
+
+
+last_each: Optional[EachStats] = None
+
+
+def _each_pool(input_signals):
+    """``(pool, is_torch)``: the pool as it came, after the shape and dtype checks."""
+    is_torch = _native.is_torch(input_signals)
+    x = input_signals if is_torch else np.asarray(input_signals)
+    shape = tuple(x.shape)
+    if not (len(shape) == 2 or (len(shape) == 3 and shape[2] in (1, 2))):
+        raise ValueError(f'expected a stereo pool (B, n, 2) or a mono pool (B, n, 1) or (B, n), got shape {shape}')
+    if is_torch:
+        import torch
+        if x.is_complex() or x.dtype == torch.bool:
+            raise TypeError(f'signals must be real numbers, got {x.dtype}')
+    elif x.dtype.kind not in 'biuf':
+        raise TypeError(f'signals must be real numbers, got {x.dtype}')
+    return x, is_torch
+
+
+def _each_signal(x, b: int):
+    """Signal b of a pool as ``decorrelate`` takes it: ``(n, 2)``, or ``(n,)`` of a mono pool."""
+    return x[b, :, 0] if x.ndim == 3 and x.shape[2] == 1 else x[b]
+
+
+def _each_velvet_key(d):
+    """``(MS?, width, normaliser?)`` of a VelvetNoise whose stage the device form covers, else None."""
+    if type(d) is not VelvetNoise or d.num_outs != 2 or d.mode not in (LayoutMode.LR, LayoutMode.MS):
+        return None
+    if d.normalizer is not None and d.normalizer is not rms_normalize:
+        return None
+    w = d.width
+    if w is not None and (type(w) not in (int, float, np.float64) or not np.isfinite(w)):
+        return None
+    return d.mode == LayoutMode.MS, None if w is None else float(w), d.normalizer is not None
+
+
+def _member_key(member):
+    channels, envelope, apply_gain = member
+    return (tuple(None if segs is None else tuple((tuple(neg), tuple(pos)) for neg, pos in segs) for segs in channels),
+            tuple(envelope), bool(apply_gain))
+
+
+def _member_in_window(member) -> bool:
+    """Whether a table's largest index is within the kernel's staged window and its weights (+-1 times the gains) are
+    finite as float32."""
+    channels, envelope, apply_gain = member
+    for segs in channels:
+        if segs is None:
+            continue
+        for s, (neg, pos) in enumerate(segs):
+            if (neg and not 0 <= min(neg) <= max(neg) <= _native.VELVET_PAIRS_MAX_TAP_INDEX) or \
+                    (pos and not 0 <= min(pos) <= max(pos) <= _native.VELVET_PAIRS_MAX_TAP_INDEX):
+                return False
+            with np.errstate(over='ignore'):
+                if apply_gain and not np.isfinite(np.float32(envelope[s])):
+                    return False
+    return True
+
+
+def each_velvet_members(decorrelators: Sequence[VelvetNoise]):
+    """``(members, tables)``: the distinct ``d._tap_member()`` triples of the list in order of first appearance -
+    deduplicated by content: equal tap arrays, envelope and gain flag share a member - and the int32 index of every
+    decorrelator's member.  ``class_path_bank_arrays(members)`` is the bank of a call over all of them."""
+    members, index, tables = [], {}, []
+    for d in decorrelators:
+        member = d._tap_member()
+        tables.append(index.setdefault(_member_key(member), len(members)))
+        if tables[-1] == len(members):
+            members.append(member)
+    return members, np.asarray(tables, np.int32)
+
+
+def _each_plan(shape: Sequence[int], decorrelators: Sequence):
+    """The device form of one call, or None: ``('velvet', (MS?, width, normaliser?), members, tables)`` or
+    ``('haas', (delayed channel, MS?, width), delays)``."""
+    shape = tuple(shape)
+    if not (len(shape) == 2 or (len(shape) == 3 and shape[2] in (1, 2))) or shape[0] != len(decorrelators) \
+            or shape[0] == 0 or shape[1] == 0:
+        return None
+    if all(type(d) is VelvetNoise for d in decorrelators):
+        if _default_mode != MODE_EXACT:
+            return None
+        keys = {_each_velvet_key(d) for d in decorrelators}
+        if len(keys) != 1 or None in keys:
+            return None
+        try:
+            members, tables = each_velvet_members(decorrelators)
+            if not all(_member_in_window(m) for m in members):
+                return None
+        except (IndexError, TypeError, ValueError):       # e.g. an envelope shorter than the segment list: the loop's error
+            return None
+        return 'velvet', keys.pop(), members, tables
+    if all(type(d) is HaasEffect for d in decorrelators):
+        from . import optimization
+        keys = {optimization._haas_key(d) for d in decorrelators}
+        delays = [optimization._haas_delay(d) for d in decorrelators]
+        if len(keys) != 1 or None in keys or None in delays:
+            return None
+        if shape[0] * (shape[1] + max(delays)) * 16 > _EACH_HAAS_BYTES:
+            return None
+        return 'haas', keys.pop(), np.asarray(delays, np.int32)
+    return None
+
+
+def each_covers(input_signals, decorrelators: Sequence) -> bool:
+    """Whether :func:`decorrelate_each` has a device form for this pool and list: a pool ``(B, n, 2)``, ``(B, n, 1)``
+    or ``(B, n)`` with B = ``len(decorrelators)`` > 0 and n > 0, and
+
+    * all plain ``VelvetNoise`` with ``num_outs == 2``; ``mode`` (LR or MS), ``width`` and ``normalizer`` equal across
+      the list, the normaliser None or ``rms_normalize``, the width None or a finite Python / float64 number; the
+      default mode ``MODE_EXACT``; every table's largest index at most ``VND_VELVET_PAIRS_MAX_TAP_INDEX`` (4094) and its
+      weights finite; or
+    * all plain ``HaasEffect`` that ``optimization.haas_scan_covers`` accepts (LR or MS layout, delayed channel 0 or 1,
+      a delay in [0, 2^31) frames, a finite Python / float64 width or None), with ``delayed_channel``, ``mode`` and
+      ``width`` equal across the list, and a padded result of at most ``_EACH_HAAS_BYTES``.
+
+    Everything else keeps the loop and its exceptions."""
+    return _each_plan(np.shape(input_signals) if not _native.is_torch(input_signals) else tuple(input_signals.shape),
+                      list(decorrelators)) is not None
+
+
+def _each_ranges(tables, max_signals: int, max_tables: int):
+    """Contiguous signal ranges ``[first, last)`` of at most ``max_signals`` signals and ``max_tables`` distinct tables
+    each, greedily: one library call per range (a row depends on no other signal, so the split changes no bit)."""
+    ranges, first, seen = [], 0, set()
+    for b, t in enumerate(np.asarray(tables).tolist()):
+        if b - first == max_signals or (t not in seen and len(seen) == max_tables):
+            ranges.append((first, b))
+            first, seen = b, set()
+        seen.add(t)
+    if len(tables) > first:
+        ranges.append((first, len(tables)))
+    return ranges
+
+
+class _EachBanks:
+    """The last few banks built, by content and device: a repeated call uploads nothing, and a bank a kernel may still
+    be reading is not freed behind an asynchronous call (a dropped table goes with its last reference)."""
+
+    def __init__(self, capacity: int = 4):
+        self.capacity, self._lock, self._items = capacity, threading.Lock(), OrderedDict()
+
+    def get(self, ctx, arrays: TapArrays) -> _native.TapTable:
+        key = (ctx.device, hashlib.blake2b(arrays.to_bytes(), digest_size=16).digest())
+        with self._lock:
+            table = self._items.get(key)
+            if table is not None:
+                self._items.move_to_end(key)
+                return table
+        table = _native.TapTable.create(ctx, arrays.tap_offsets, arrays.tap_index, arrays.tap_weight, **arrays.kwargs())
+        with self._lock:
+            table = self._items.setdefault(key, table)
+            self._items.move_to_end(key)
+            while len(self._items) > self.capacity:
+                self._items.popitem(last=False)
+        return table
+
+    def clear(self):
+        with self._lock:
+            self._items.clear()
+
+
+_each_banks = _EachBanks()
+
+
+class _EachVelvet:
+    """The velvet-noise driver of :func:`decorrelate_each` over a float32 ``(B, n, C)`` pool - a C-contiguous NumPy
+    array (through ``vnd_decorrelate_each_f32_host``) or a device tensor (read in place by
+    ``vnd_decorrelate_each_f32_dev`` on the current stream): per range of :func:`_each_ranges` one bank of the range's
+    distinct members and one call."""
+
+    def __init__(self, ctx, pool, is_torch: bool, stage, stats: EachStats):
+        self.ctx, self.pool, self.is_torch, self.stats = ctx, pool, is_torch, stats
+        ms_encode, width, has_normalizer = stage
+        self.stage = dict(ms_encode=ms_encode, width=width, normalize=_normalize_flag(has_normalizer))
+        self.batch, self.n, self.channels = (int(v) for v in pool.shape)
+
+    def run(self, members, tables):
+        out = self._result()
+        self.stats.tables = len(members)
+        for first, last in _each_ranges(tables, _native.MAX_STREAMS_PER_CALL, _native.VELVET_BANK_MAX_CANDIDATES):
+            distinct, local = np.unique(tables[first:last], return_inverse=True)
+            arrays = class_path_bank_arrays([members[t] for t in distinct.tolist()])
+            self._call(arrays, local.reshape(-1).astype(np.int32), first, last, out)
+            self.stats.launches += 1
+            self.stats.launch_signals.append(last - first)
+            self.stats.launch_tables.append(int(distinct.size))
+        return out
+
+    def _result(self):
+        if not self.is_torch:
+            return np.empty((self.batch, self.n, 2), np.float32)
+        import torch
+        return torch.empty((self.batch, self.n, 2), dtype=torch.float32, device=self.pool.device)
+
+    def _call(self, arrays: TapArrays, local, first: int, last: int, out) -> None:
+        bank = _each_banks.get(self.ctx, arrays)
+        if not self.is_torch:
+            out[first:last] = _native.decorrelate_each_host(self.ctx, bank, self.pool[first:last], local, **self.stage)
+            self.stats.pool_uploads += 1
+            self.stats.result_downloads += 1
+            return
+        import torch
+        dev = self.pool.device
+        part, y = self.pool[first:last], out[first:last]
+        ws = _native.decorrelate_workspace_bytes(last - first, self.n, 2) if self.stage['normalize'] else 0
+        work = torch.empty(max(ws, 1), dtype=torch.uint8, device=dev)
+        index = torch.from_numpy(local).to(dev)
+        _native.decorrelate_each_device(self.ctx, bank, part.data_ptr(), index.data_ptr(), y.data_ptr(), last - first,
+                                        self.n, self.channels, workspace_ptr=work.data_ptr(), workspace_bytes=ws,
+                                        stream=torch.cuda.current_stream(dev).cuda_stream, **self.stage)
+        self.stats.launch_pool.append(int(part.data_ptr()))
+
+
+def _each_haas(ctx, pool, is_torch: bool, key, delays, stats: EachStats):
+    """The Haas driver of :func:`decorrelate_each`: one padded float64 block ``(B, n + max delay, 2)`` and one call per
+    ``VND_MAX_STREAMS`` signals; the result is the list of views ``block[b, :n + d_b]``."""
+    delayed_channel, ms_mode, width = key
+    batch, n, channels = (int(v) for v in pool.shape)
+    max_delay = int(delays.max())
+    settings = dict(max_delay=max_delay, delayed_channel=delayed_channel, ms_mode=ms_mode, width=width)
+    step = _native.MAX_STREAMS_PER_CALL
+    if is_torch:
+        import torch
+        dev = pool.device
+        block = torch.empty((batch, n + max_delay, 2), dtype=torch.float64, device=dev)
+        frames = torch.from_numpy(delays).to(dev)
+        for first in range(0, batch, step):
+            part, count = pool[first:first + step], min(step, batch - first)
+            _native.haas_each_device(ctx, part.data_ptr(), block[first:first + step].data_ptr(), count, n, channels,
+                                     frames[first:first + step].data_ptr(),
+                                     stream=torch.cuda.current_stream(dev).cuda_stream, **settings)
+            stats.launches += 1
+            stats.launch_signals.append(count)
+            stats.launch_pool.append(int(part.data_ptr()))
+    else:
+        block = np.empty((batch, n + max_delay, 2), np.float64)
+        for first in range(0, batch, step):
+            block[first:first + step] = _native.haas_each_host(ctx, pool[first:first + step], delays[first:first + step],
+                                                               **settings)
+            stats.launches += 1
+            stats.launch_signals.append(min(step, batch - first))
+            stats.pool_uploads += 1
+            stats.result_downloads += 1
+    return [block[b, :n + int(d)] for b, d in enumerate(delays.tolist())]
+
+
+def decorrelate_each(input_signals, decorrelators: Sequence[Decorrelator]):
+    """Signal b of a pool through ``decorrelators[b]``: ``[d.decorrelate(x_b) for x_b, d in zip(pool, decorrelators)]``
+    as one launch chain for the whole pool - what applies the per-signal results of
+    ``optimization.optimize_velvet_noise_batched`` / ``optimize_haas_delay_batched``.
+
+    ``input_signals`` is a pool ``(B, n, 2)``, ``(B, n, 1)`` or ``(B, n)`` (mono signals, fanned out to both outputs):
+    a NumPy array of any real dtype (cast as ``to_float32`` casts it) or a CUDA torch tensor, which is read in place -
+    the result is then a device tensor (tensors), enqueued on the current stream without synchronising.
+    ``len(decorrelators)`` must be B (``ValueError``); the list is of one type (``TypeError`` for a mix).
+
+    All ``VelvetNoise``: ``(B, n, 2)`` float32, equal to ``np.stack`` of the loop bit for bit.  The signals' tap tables
+    (``d._tap_member()``) are deduplicated by content and go up as one class-path bank (several past 32767 distinct
+    tables or ``VND_MAX_STREAMS`` signals); signal b runs through its own candidate (``vnd_decorrelate_each_f32_*``,
+    always ``VND_MODE_EXACT``).
+    All ``HaasEffect``: a list of B float64 ``(n + d_b, 2)`` arrays (tensors), views of one padded block, each equal to
+    ``d.decorrelate(x_b)`` bit for bit (``vnd_haas_each_f64_*``).
+
+    Device route (:func:`set_each_device`: ``None`` with a gfx950 device, or ``True``) for the calls
+    :func:`each_covers` accepts; everything else - other decorrelator types, per-signal stage settings, a custom
+    normaliser, a tolerance mode, filters past 4094 frames - is the loop, with the loop's own exceptions.
+    ``last_each`` records the call's work (:class:`EachStats`)."""
+    global last_each
+    decorrelators = list(decorrelators)
+    x, is_torch = _each_pool(input_signals)
+    batch = int(x.shape[0])
+    if len(decorrelators) != batch:
+        raise ValueError(f'{len(decorrelators)} decorrelators for a pool of {batch} signals')
+    if len({type(d) for d in decorrelators}) > 1:
+        raise TypeError('decorrelate_each takes decorrelators of one type, got '
+                        + ', '.join(sorted({type(d).__name__ for d in decorrelators})))
+    if batch == 0:
+        last_each = EachStats(route='none')
+        if is_torch:
+            import torch
+            return torch.zeros((0, int(x.shape[1]), 2), dtype=torch.float32, device=x.device)
+        return np.zeros((0, x.shape[1], 2), np.float32)
+    plan = _each_plan(tuple(x.shape), decorrelators)
+    if not analysis.device_route(_each_device, plan is not None,
+                                 'set_each_device(True): no gfx950 device (or no built extension) to run on'):
+        last_each = EachStats(route='host', signals=batch)
+        pool = x.detach().cpu().numpy() if is_torch else x
+        rows = [d.decorrelate(_each_signal(pool, b)) for b, d in enumerate(decorrelators)]
+        if type(decorrelators[0]) is VelvetNoise:
+            rows = np.stack(rows)
+        if not is_torch:
+            return rows
+        import torch
+        return torch.from_numpy(rows).to(x.device) if isinstance(rows, np.ndarray) \
+            else [torch.from_numpy(np.ascontiguousarray(r)).to(x.device) for r in rows]
+    stats = last_each = EachStats(route='device', kind=plan[0], signals=batch)
+    if is_torch:
+        import torch
+        if not x.is_cuda:
+            raise ValueError('a torch pool must be a device tensor (NumPy arrays are uploaded)')
+        ctx = _native.context_for(x.device.index if x.device.index is not None else torch.cuda.current_device())
+        pool = x.reshape(batch, x.shape[1], -1)
+        pool = (pool if pool.dtype == torch.float32 else pool.to(torch.float32)).contiguous()
+    else:
+        ctx = _native.default_context()
+        pool = np.ascontiguousarray(to_float32(x.reshape(batch, x.shape[1], -1)))
+    if plan[0] == 'velvet':
+        return _EachVelvet(ctx, pool, is_torch, plan[1], stats).run(plan[2], plan[3])
+    return _each_haas(ctx, pool, is_torch, plan[1], plan[2], stats)
 
 
 # ----------------------------------------------------------------------------
