@@ -114,7 +114,7 @@ def _run(env, table, x, *, variant, ms=False, width=None, normalize=OFF, tuning=
             y = torch.full((batch, n, C), float('nan'), dtype=torch.float32, device='cuda')
             c = torch.full((batch, n, C), float('nan'), dtype=torch.float32, device='cuda')
             ws_bytes = native.decorrelate_workspace_bytes(batch, n, C)
-            ws = torch.zeros(ws_bytes // 8 + 1, dtype=torch.float64, device='cuda')
+            ws = torch.full((ws_bytes,), 0xA5, dtype=torch.uint8, device='cuda')        # exactly the declared size, and not zeroed
             taken = table.decorrelate_device_taken(xd.data_ptr(), y.data_ptr(), batch, n, cx, mode=d.MODE_FAST, ms_encode=ms,
                                                    width=width, normalize=normalize, workspace_ptr=ws.data_ptr(),
                                                    workspace_bytes=ws_bytes, stream=st)
@@ -123,7 +123,7 @@ def _run(env, table, x, *, variant, ms=False, width=None, normalize=OFF, tuning=
             torch.cuda.synchronize()
         finally:
             ctx.set_variant(-1)
-    return y.cpu().numpy(), c.cpu().numpy(), ws.cpu().numpy(), taken, text
+    return y.cpu().numpy(), c.cpu().numpy(), ws[:ws_bytes // 8 * 8].view(torch.float64).cpu().numpy(), taken, text
 
 
 def _seq_sums(a):

@@ -608,12 +608,12 @@ def test_exact_rms_sums_are_numpys(vnd, name, x):
     xd = torch.from_numpy(x).cuda()
     yd = torch.empty_like(xd)
     ws_bytes = _native.decorrelate_workspace_bytes(1, n, channels)
-    ws = torch.zeros(ws_bytes // 8 + 1, dtype=torch.float64, device='cuda')
+    ws = torch.full((ws_bytes,), 0xA5, dtype=torch.uint8, device='cuda')        # exactly the declared size, and not zeroed
     table.decorrelate_device(xd.data_ptr(), yd.data_ptr(), 1, n, channels, mode=vnd.MODE_EXACT, ms_encode=False,
                              width=None, normalize=True, workspace_ptr=ws.data_ptr(), workspace_bytes=ws_bytes,
                              stream=torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
-    got_sums = ws[:2 * channels].cpu().numpy()             # exact mode: one row of 2C float32 sums (as doubles)
+    got_sums = ws[:ws_bytes // 8 * 8].view(torch.float64)[:2 * channels].cpu().numpy()             # exact mode: one row of 2C float32 sums (as doubles)
     want = _seq_sums(x)
     assert np.array_equal(got_sums[:channels].astype(np.float32), want, equal_nan=True), (name, got_sums, want)
     assert np.array_equal(got_sums[channels:].astype(np.float32), want, equal_nan=True), name      # y == x here
@@ -653,12 +653,12 @@ def test_single_channel_sums_are_numpys_pairwise_ones(vnd, name, x):
     xd = torch.from_numpy(xs).cuda()
     yd = torch.empty_like(xd)
     ws_bytes = _native.decorrelate_workspace_bytes(batch, n, 1)
-    ws = torch.zeros(ws_bytes // 8 + 1, dtype=torch.float64, device='cuda')
+    ws = torch.full((ws_bytes,), 0xA5, dtype=torch.uint8, device='cuda')        # exactly the declared size, and not zeroed
     table.decorrelate_device(xd.data_ptr(), yd.data_ptr(), batch, n, 1, mode=vnd.MODE_EXACT, ms_encode=False,
                              width=None, normalize=True, workspace_ptr=ws.data_ptr(), workspace_bytes=ws_bytes,
                              stream=torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
-    got = ws[:2 * batch].cpu().numpy().astype(np.float32).reshape(batch, 2)       # per stream: sum x^2, sum y^2
+    got = ws[:ws_bytes // 8 * 8].view(torch.float64)[:2 * batch].cpu().numpy().astype(np.float32).reshape(batch, 2)       # per stream: sum x^2, sum y^2
     for b in range(batch):
         with np.errstate(all='ignore'):
             want = np.add.reduce(np.square(xs[b]), axis=0)[0]
@@ -721,11 +721,11 @@ def test_block_parallel_sums_equal_the_sequential_kernel(vnd):
         xd = torch.from_numpy(x[:batch]).cuda()
         yd = torch.empty_like(xd)
         ws_bytes = _native.decorrelate_workspace_bytes(batch, n, 2)
-        ws = torch.zeros(ws_bytes // 8 + 1, dtype=torch.float64, device='cuda')
+        ws = torch.full((ws_bytes,), 0xA5, dtype=torch.uint8, device='cuda')        # exactly the declared size, and not zeroed
         table.decorrelate_device(xd.data_ptr(), yd.data_ptr(), batch, n, 2, mode=vnd.MODE_EXACT, ms_encode=False, width=None,
                                  normalize=True, workspace_ptr=ws.data_ptr(), workspace_bytes=ws_bytes, stream=st)
         torch.cuda.synchronize()
-        results[label] = (ws[:4 * batch].cpu().numpy().astype(np.float32).reshape(batch, 4), yd.cpu().numpy())
+        results[label] = (ws[:ws_bytes // 8 * 8].view(torch.float64)[:4 * batch].cpu().numpy().astype(np.float32).reshape(batch, 4), yd.cpu().numpy())
     ctx.set_variant(-1)
     want = np.stack([_seq_sums(s) for s in streams])
     for label, (sums, y) in results.items():
@@ -855,7 +855,7 @@ def test_block_sums_from_the_convolutions_store_phase(vnd):
             os.environ['VND_EPI_SEQ_SPLIT'] = '0'
         try:
             yd = torch.empty_like(xd)
-            ws = torch.zeros(ws_bytes // 8 + 1, dtype=torch.float64, device='cuda')
+            ws = torch.full((ws_bytes,), 0xA5, dtype=torch.uint8, device='cuda')        # exactly the declared size, and not zeroed
             table.decorrelate_device(xd.data_ptr(), yd.data_ptr(), batch, n, 2, mode=vnd.MODE_EXACT, ms_encode=True, width=None,
                                      normalize=True, workspace_ptr=ws.data_ptr(), workspace_bytes=ws_bytes, stream=st)
             torch.cuda.synchronize()
@@ -863,7 +863,7 @@ def test_block_sums_from_the_convolutions_store_phase(vnd):
             os.environ.pop('VND_EPI_BLOCK_SUMS', None)
             os.environ.pop('VND_EPI_SEQ_SPLIT', None)
             ctx.set_variant(-1)
-        out[label] = (ws[:4 * batch].cpu().numpy().copy(), yd.cpu().numpy())
+        out[label] = (ws[:ws_bytes // 8 * 8].view(torch.float64)[:4 * batch].cpu().numpy().copy(), yd.cpu().numpy())
         table.close()
     for label, (sums, y) in out.items():
         assert np.array_equal(sums, out['per-stream'][0]), label

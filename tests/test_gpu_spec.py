@@ -362,7 +362,7 @@ def test_decorrelate_stage_through_the_specialised_kernel(env, golden, ms_encode
     for label, variant in (('spec', FORCE | span_bits(1, 2)), ('generic', GENERIC)):
         ctx.set_variant(variant)
         y = torch.empty_like(x)
-        ws = torch.zeros(ws_bytes // 8 + 1, dtype=torch.float64, device='cuda')
+        ws = torch.full((ws_bytes,), 0xA5, dtype=torch.uint8, device='cuda')        # exactly the declared size, and not zeroed
         table.decorrelate_device(x.data_ptr(), y.data_ptr(), pool, n, 2, mode=d.MODE_EXACT, ms_encode=ms_encode, width=width,
                                  normalize=True, workspace_ptr=ws.data_ptr(), workspace_bytes=ws_bytes, stream=s)
         torch.cuda.synchronize()
@@ -444,7 +444,7 @@ def test_mono_decorrelate_stage_through_the_specialised_kernel(env, golden, tmp_
         ctx.set_variant(variant)
         monkeypatch.setenv('VND_WIN_FANOUT_EPI', fan)
         y = torch.empty((pool, n, 2), dtype=torch.float32, device='cuda')
-        ws = torch.zeros(ws_bytes // 8 + 1, dtype=torch.float64, device='cuda')
+        ws = torch.full((ws_bytes,), 0xA5, dtype=torch.uint8, device='cuda')        # exactly the declared size, and not zeroed
         table.decorrelate_device(x.data_ptr(), y.data_ptr(), pool, n, 1, mode=d.MODE_EXACT, ms_encode=True, width=0.4,
                                  normalize=True, workspace_ptr=ws.data_ptr(), workspace_bytes=ws_bytes, stream=s)
         torch.cuda.synchronize()
@@ -479,7 +479,7 @@ def test_fast_decorrelate_stage_through_the_specialised_kernel(env, golden, tmp_
     ws_bytes = native.decorrelate_workspace_bytes(pool, n, 2)
     ctx.set_variant(FORCE | span_bits(1, 3))
     y = torch.empty((pool, n, 2), dtype=torch.float32, device='cuda')
-    ws = torch.zeros(ws_bytes // 8 + 1, dtype=torch.float64, device='cuda')
+    ws = torch.full((ws_bytes,), 0xA5, dtype=torch.uint8, device='cuda')        # exactly the declared size, and not zeroed
     table.decorrelate_device(x.data_ptr(), y.data_ptr(), pool, n, cx, mode=d.MODE_FAST, ms_encode=True, width=0.6,
                              normalize=2, workspace_ptr=ws.data_ptr(), workspace_bytes=ws_bytes, stream=s)
     torch.cuda.synchronize()
@@ -684,7 +684,7 @@ def test_exact_stage_in_the_window_form_equals_the_generic_kernels(env, golden, 
         for label, variant in (('window', FORCE | EXACT_TOO | span_bits(1, 2)), ('generic', GENERIC)):
             ctx.set_variant(variant)
             y = torch.empty((pool, n, 2), dtype=torch.float32, device='cuda')
-            ws = torch.zeros(ws_bytes // 8 + 1, dtype=torch.float64, device='cuda')
+            ws = torch.full((ws_bytes,), 0xA5, dtype=torch.uint8, device='cuda')        # exactly the declared size, and not zeroed
             table.decorrelate_device(x.data_ptr(), y.data_ptr(), pool, n, cx, mode=d.MODE_EXACT, ms_encode=ms_encode, width=width,
                                      normalize=normalize, workspace_ptr=ws.data_ptr(), workspace_bytes=ws_bytes, stream=s)
             torch.cuda.synchronize()
