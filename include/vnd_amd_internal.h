@@ -78,6 +78,13 @@ vnd_status vnd_debug_read_stamps(vnd_ctx *ctx, const vnd_taps *taps, int64_t bat
  * groups, nblocks.  epilogue = the call's ms_encode || use_width.                                                      */
 vnd_status vnd_describe_stream_launch(vnd_ctx *ctx, const vnd_taps *taps, int64_t batch, int64_t n_out,
                                       int32_t in_channels, int32_t mode, int32_t epilogue, char *text, int32_t len);
+/* Diagnosis: the launch a vnd_each_stream_f32_dev call (include/vnd_each_stream.h) with these arguments would take - the
+ * call's own scalar checks and planner, no device work - as one line of key=value fields: r (frame pairs per lane: the
+ * tile is 2 * 256 * r frames), W (window frames), lds_bytes, tiles (per stream), nblocks, n_out, fma (a bank of +-1
+ * weights takes the fma instantiation: the same bits).  epilogue = the call's ms_encode || use_width.                    */
+vnd_status vnd_describe_each_stream_launch(vnd_ctx *ctx, const vnd_taps *bank, int64_t max_frames_per_call, int64_t batch,
+                                           int64_t position, int64_t n_in, int32_t in_channels, int32_t final,
+                                           int32_t mode, int32_t epilogue, char *text, int32_t len);
 /* Diagnosis (tests): vnd_decorrelate_fanout_f32_dev (in_channels == the table's channels: vnd_decorrelate_f32_dev), and which of the
  * stage's forms ran, in taken[4]: [0] 0 the table-order launch with the pointwise steps and the sums as passes of their own, 1 the
  * fast kernel with the pointwise steps (and, with VND_NORMALIZE_RMS, the sums) fused into its store phase, 2 the quad / octet kernel

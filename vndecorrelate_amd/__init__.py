@@ -20,6 +20,7 @@ from .decorrelation import (  # noqa: F401
     convolve_velvet_noise_batched,
     decorrelate_bank,
     decorrelate_each,
+    decorrelate_each_stream,
     each_covers,
     generate_velvet_noise,
     set_default_mode,
@@ -28,4 +29,11 @@ from .decorrelation import (  # noqa: F401
     set_white_noise_device,
 )
 from .analysis import cross_correlogram_batched, set_correlogram_device  # noqa: F401
-from .streaming import ChainStream, HaasStream, Stream, convolve_velvet_noise_stream  # noqa: F401
+from .streaming import (  # noqa: F401
+    ChainStream,
+    EachStream,
+    HaasEachStream,
+    HaasStream,
+    Stream,
+    convolve_velvet_noise_stream,
+)

@@ -141,6 +141,9 @@ INTERNAL_SIGNATURES = {
     'vnd_describe_stream_launch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p,
                                                   ctypes.c_int32]),
+    'vnd_describe_each_stream_launch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                       ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                       ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32]),
     'vnd_debug_decorrelate_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                      ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                                      ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
@@ -258,6 +261,26 @@ CORRELOGRAM_STREAM_SIGNATURES = {
                                                       ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]),
 }
 
+# include/vnd_each_stream.h: a pool streamed with its own filter or delay per stream
+_EACH_STREAM_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                     ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
+                     ctypes.POINTER(ctypes.c_int64)]
+_HAAS_EACH_STREAM_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                          ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                          ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
+                          ctypes.POINTER(ctypes.c_int64)]
+EACH_STREAM_SIGNATURES = {
+    'vnd_each_stream_state_bytes': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
+                                                   ctypes.POINTER(ctypes.c_int64)]),
+    'vnd_each_stream_f32_dev': (ctypes.c_int, _EACH_STREAM_ARGS + [ctypes.c_void_p]),
+    'vnd_each_stream_f32_host': (ctypes.c_int, _EACH_STREAM_ARGS),
+    'vnd_haas_each_stream_state_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                                        ctypes.POINTER(ctypes.c_int64)]),
+    'vnd_haas_each_stream_f64_dev': (ctypes.c_int, _HAAS_EACH_STREAM_ARGS + [ctypes.c_void_p]),
+    'vnd_haas_each_stream_f64_host': (ctypes.c_int, _HAAS_EACH_STREAM_ARGS),
+}
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -309,7 +332,7 @@ def load_library():
                                   + list(CORRELOGRAM_STREAM_SIGNATURES.items())
                                   + list(HAAS_SEARCH_SIGNATURES.items())
                                   + list(VELVET_SEARCH_SIGNATURES.items())
-                                  + list(EACH_SIGNATURES.items())):
+                                  + list(EACH_SIGNATURES.items()) + list(EACH_STREAM_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -683,6 +706,16 @@ class TapTable:
                                                     int(bool(epilogue)), buf, 512), 'vnd_describe_stream_launch')
         return buf.value.decode()
 
+    def describe_each_stream(self, max_frames_per_call: int, batch: int, position: int, n_in: int, in_channels: int,
+                             final: bool = False, mode: int = MODE_EXACT, epilogue: bool = False) -> str:
+        """The launch of a ``vnd_each_stream_f32_dev`` call with these arguments on this bank
+        (``vnd_describe_each_stream_launch``): ``r=``, ``tiles=``, ``nblocks=`` among its fields."""
+        buf = ctypes.create_string_buffer(512)
+        _check(self._lib.vnd_describe_each_stream_launch(self.ctx.handle, self.handle, max_frames_per_call, batch, position,
+                                                         n_in, in_channels, int(bool(final)), int(mode),
+                                                         int(bool(epilogue)), buf, 512), 'vnd_describe_each_stream_launch')
+        return buf.value.decode()
+
     def read_stamps(self, batch: int, n: int, channels: int, mode: int = MODE_EXACT) -> np.ndarray:
         """Phase stamps of the window-form kernel of this launch shape (``vnd_debug_read_stamps``; diagnosis builds
         under ``VND_TUNING=1 VND_WIN_STAMPS=<workgroups>``): ``(workgroups, 16)`` uint64, empty without such a build."""
@@ -993,6 +1026,95 @@ def haas_each_device(ctx: 'Context', x_ptr: int, y_ptr: int, batch: int, n: int,
                                           ctypes.c_void_p(delays_ptr), int(max_delay), int(delayed_channel),
                                           int(bool(ms_mode)), int(width is not None), float(width or 0.0),
                                           ctypes.c_void_p(stream)), 'vnd_haas_each_f64_dev')
+
+
+def each_stream_state_bytes(bank: 'TapTable', batch: int, channels: int, max_frames_per_call: int) -> int:
+    """``vnd_each_stream_state_bytes``: the ring of a pool of ``batch`` streams at the bank's latency."""
+    need = ctypes.c_int64()
+    _check(load_library().vnd_each_stream_state_bytes(bank.handle, batch, channels, max_frames_per_call, ctypes.byref(need)),
+           'vnd_each_stream_state_bytes')
+    return need.value
+
+
+def _each_stream_call(fn, name: str, ctx, bank, tables_ptr, state_ptr, state_bytes, max_frames_per_call, x_ptr, y_ptr, batch,
+                      position, n_in, channels, final, ms_encode, width, mode, *stream) -> int:
+    got = ctypes.c_int64()
+    _check(fn(ctx.handle, bank.handle, ctypes.c_void_p(tables_ptr), ctypes.c_void_p(state_ptr), state_bytes,
+              max_frames_per_call, ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr), batch, position, n_in, channels,
+              int(bool(final)), int(mode), int(bool(ms_encode)), int(width is not None), float(width or 0.0),
+              ctypes.byref(got), *stream), name)
+    return got.value
+
+
+def each_stream_device(ctx: 'Context', bank: 'TapTable', tables_ptr: int, state_ptr: int, state_bytes: int,
+                       max_frames_per_call: int, x_ptr: int, y_ptr: int, batch: int, position: int, n_in: int, channels: int,
+                       *, final: bool, ms_encode: bool, width, mode: int = MODE_EXACT, stream: int = 0) -> int:
+    """``vnd_each_stream_f32_dev``: the next float32 ``(batch, n_in, channels)`` block of a pool, stream b through
+    candidate ``tables[b]`` of ``bank``; int32 ``(batch,)`` table indices, the state, the block and the float32
+    ``(batch, n_out, 2)`` result are device buffers; enqueued on ``stream``.  Returns ``n_out``."""
+    return _each_stream_call(ctx._lib.vnd_each_stream_f32_dev, 'vnd_each_stream_f32_dev', ctx, bank, tables_ptr, state_ptr,
+                             state_bytes, max_frames_per_call, x_ptr, y_ptr, batch, position, n_in, channels, final,
+                             ms_encode, width, mode, ctypes.c_void_p(stream))
+
+
+def each_stream_host(ctx: 'Context', bank: 'TapTable', tables, state_ptr: int, state_bytes: int, max_frames_per_call: int,
+                     x: np.ndarray, n_out: int, position: int, *, final: bool, ms_encode: bool, width,
+                     mode: int = MODE_EXACT) -> np.ndarray:
+    """``vnd_each_stream_f32_host``: the same from a C-contiguous float32 ``(batch, n_in, 1|2)`` block and table indices
+    in host memory (the state stays on the device), synchronous; float32 ``(batch, n_out, 2)``."""
+    t = _each_host_args(x, tables, 'each_stream_host', 'table index')
+    y = np.empty((x.shape[0], int(n_out), 2), np.float32)
+    got = _each_stream_call(ctx._lib.vnd_each_stream_f32_host, 'vnd_each_stream_f32_host', ctx, bank, t.ctypes.data, state_ptr,
+                            state_bytes, max_frames_per_call, x.ctypes.data, y.ctypes.data, x.shape[0], position, x.shape[1],
+                            x.shape[2], final, ms_encode, width, mode)
+    if got != n_out:
+        raise NativeError(f'vnd_each_stream_f32_host returned {got} frames, the span is {n_out}')
+    return y
+
+
+def haas_each_stream_state_bytes(batch: int, channels: int, max_delay: int, max_frames_per_call: int) -> int:
+    """``vnd_haas_each_stream_state_bytes``: the ring of a pool of ``batch`` streams delayed by up to ``max_delay``."""
+    need = ctypes.c_int64()
+    _check(load_library().vnd_haas_each_stream_state_bytes(batch, channels, int(max_delay), max_frames_per_call,
+                                                           ctypes.byref(need)), 'vnd_haas_each_stream_state_bytes')
+    return need.value
+
+
+def _haas_each_stream_call(fn, name: str, ctx, state_ptr, state_bytes, max_frames_per_call, x_ptr, y_ptr, batch, position,
+                           n_in, channels, final, delays_ptr, max_delay, delayed_channel, ms_mode, width, *stream) -> int:
+    got = ctypes.c_int64()
+    _check(fn(ctx.handle, ctypes.c_void_p(state_ptr), state_bytes, max_frames_per_call, ctypes.c_void_p(x_ptr),
+              ctypes.c_void_p(y_ptr), batch, position, n_in, channels, int(bool(final)), ctypes.c_void_p(delays_ptr),
+              int(max_delay), int(delayed_channel), int(bool(ms_mode)), int(width is not None), float(width or 0.0),
+              ctypes.byref(got), *stream), name)
+    return got.value
+
+
+def haas_each_stream_device(ctx: 'Context', state_ptr: int, state_bytes: int, max_frames_per_call: int, x_ptr: int, y_ptr: int,
+                            batch: int, position: int, n_in: int, channels: int, delays_ptr: int, *, final: bool,
+                            max_delay: int, delayed_channel: int, ms_mode: bool, width, stream: int = 0) -> int:
+    """``vnd_haas_each_stream_f64_dev``: the next float32 ``(batch, n_in, channels)`` block of a pool, stream b delayed by
+    ``delays[b]`` frames; int32 ``(batch,)`` delays, the state, the block and the float64 ``(batch, n_out, 2)`` result are
+    device buffers; enqueued on ``stream``.  Returns ``n_out = n_in + (max_delay if final else 0)``."""
+    return _haas_each_stream_call(ctx._lib.vnd_haas_each_stream_f64_dev, 'vnd_haas_each_stream_f64_dev', ctx, state_ptr,
+                                  state_bytes, max_frames_per_call, x_ptr, y_ptr, batch, position, n_in, channels, final,
+                                  delays_ptr, max_delay, delayed_channel, ms_mode, width, ctypes.c_void_p(stream))
+
+
+def haas_each_stream_host(ctx: 'Context', state_ptr: int, state_bytes: int, max_frames_per_call: int, x: np.ndarray, delays,
+                          position: int, *, final: bool, max_delay: int, delayed_channel: int, ms_mode: bool,
+                          width) -> np.ndarray:
+    """``vnd_haas_each_stream_f64_host``: the same from a C-contiguous float32 ``(batch, n_in, 1|2)`` block and delays in
+    host memory (the state stays on the device), synchronous; float64 ``(batch, n_out, 2)``."""
+    d = _each_host_args(x, delays, 'haas_each_stream_host', 'delay')
+    n_out = x.shape[1] + (int(max_delay) if final else 0)
+    y = np.empty((x.shape[0], n_out, 2), np.float64)
+    got = _haas_each_stream_call(ctx._lib.vnd_haas_each_stream_f64_host, 'vnd_haas_each_stream_f64_host', ctx, state_ptr,
+                                 state_bytes, max_frames_per_call, x.ctypes.data, y.ctypes.data, x.shape[0], position,
+                                 x.shape[1], x.shape[2], final, d.ctypes.data, max_delay, delayed_channel, ms_mode, width)
+    if got != n_out:
+        raise NativeError(f'vnd_haas_each_stream_f64_host returned {got} frames, the span is {n_out}')
+    return y
 
 
 def polar_moments_workspace_bytes(n: int, pairs: int) -> int:

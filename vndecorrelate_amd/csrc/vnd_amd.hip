@@ -13,6 +13,7 @@
 //   vnd_each.hpp         a pool through one filter or one delay per signal (include/vnd_each.h)
 //   vnd_stream.hpp       chunked streaming of the tap sum (include/vnd_stream.h)
 //   vnd_haas_stream.hpp  chunked streaming of the HaasEffect delay (include/vnd_haas_stream.h)
+//   vnd_each_stream.hpp  a pool streamed through one filter or one delay per stream (include/vnd_each_stream.h)
 #include "vnd_objects.hpp"
 #include "vnd_plan.hpp"
 
@@ -407,4 +408,5 @@ vnd_status vnd_prepare_launch(vnd_ctx *ctx, const vnd_taps *t, int64_t batch, in
 #include "vnd_each.hpp"
 #include "vnd_stream.hpp"
 #include "vnd_haas_stream.hpp"
+#include "vnd_each_stream.hpp"
 #include "vnd_hooks.hpp"

@@ -246,4 +246,19 @@ vnd_status vnd_describe_stream_launch(vnd_ctx *ctx, const vnd_taps *t, int64_t b
     return VND_OK;
 }
 
+// The EachStreamPlan a vnd_each_stream_f32_dev call with these arguments takes: the same checks and planner, no pointers.
+vnd_status vnd_describe_each_stream_launch(vnd_ctx *ctx, const vnd_taps *t, int64_t max_frames_per_call, int64_t batch,
+                                           int64_t pos, int64_t n_in, int32_t in_channels, int32_t final_, int32_t mode,
+                                           int32_t epilogue, char *text, int32_t len)
+{
+    if (!text || len <= 0) return fail(VND_ERR_INVALID, "null text buffer");
+    int64_t nout = 0;
+    vnd_status st = each_stream_scalars(ctx, t, max_frames_per_call, batch, pos, n_in, in_channels, final_, mode, &nout);
+    if (st != VND_OK) return st;
+    const EachStreamPlan p = make_each_stream_plan(ctx, t, batch, nout, in_channels, epilogue != 0);
+    snprintf(text, (size_t)len, "each_stream r=%d W=%d lds_bytes=%zu tiles=%d nblocks=%u n_out=%lld fma=%d epilogue=%d threads=%d",
+             p.r, p.W, p.lds_bytes, p.tiles, p.nblocks, (long long)nout, p.fma ? 1 : 0, p.epi ? 1 : 0, kVpThreads);
+    return VND_OK;
+}
+
 }  // extern "C"

@@ -50,11 +50,11 @@ __device__ __forceinline__ bool vp_valid(const VpArgs &a, int32_t s, int32_t c)
 }
 
 // Channel `ch` of the bank over this lane's frames, from the staged plane `pa` (the lane's first pair): the tap loop of
-// conv_ordered_kernel.
-template <int MODE>
-__device__ __forceinline__ void vp_channel(const KArgs &a, int ch, const float *pa, v2f (&out)[kVpR])
+// conv_ordered_kernel.  R: the lane's frame pairs (the block stream of vnd_each_stream.hpp picks its tile per call).
+template <int MODE, int R = kVpR>
+__device__ __forceinline__ void vp_channel(const KArgs &a, int ch, const float *pa, v2f (&out)[R])
 {
-    constexpr int NT = kVpThreads, R = kVpR;
+    constexpr int NT = kVpThreads;
     if (a.chan_flags != nullptr && (a.chan_flags[ch] & 1)) {          // unfiltered: copy through
 #pragma unroll
         for (int j = 0; j < R; ++j) out[j] = *(const v2f *)(pa + 2 * NT * j);

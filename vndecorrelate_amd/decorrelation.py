@@ -1300,6 +1300,91 @@ def decorrelate_each(input_signals, decorrelators: Sequence[Decorrelator]):
     return _each_haas(ctx, pool, is_torch, plan[1], plan[2], stats)
 
 
+def _same_across(decorrelators, fields: Sequence[str]) -> None:
+    """``ValueError`` naming the first of ``fields`` that differs across the list: the stage settings are scalars of a
+    call, the same for every stream."""
+    for name in fields:
+        first = getattr(decorrelators[0], name)
+        for b, d in enumerate(decorrelators):
+            v = getattr(d, name)
+            if not (v is first or (type(v) is type(first) and v == first)):
+                raise ValueError(f'decorrelate_each_stream: {name} differs across the list ({first!r}, and {v!r} for stream '
+                                 f'{b}): the stage settings are the same for every stream of a pool')
+
+
+def decorrelate_each_stream(decorrelators: Sequence[Decorrelator], *, in_channels: int = 2, max_frames_per_call: int = 4800):
+    """A block stream in which stream b of a pool runs through ``decorrelators[b]`` - the streaming form of
+    :func:`decorrelate_each`, and what runs the per-signal results of ``optimization.optimize_velvet_noise_batched`` /
+    ``optimize_haas_delay_batched`` live: one kernel launch per call for the whole pool, the state in a per-stream ring on
+    the device.  ``num_streams = len(decorrelators)``; ``in_channels``: 2, or 1 for mono signals (fanned out to both
+    outputs); blocks are ``(num_streams, B, in_channels)`` with ``0 <= B <= max_frames_per_call``, NumPy arrays of any real
+    dtype (cast to float32 first, as ``decorrelate`` casts its input) or CUDA tensors, answered in kind.
+
+    All ``VelvetNoise`` (``normalizer=None``): a ``streaming.EachStream``.  The tap tables (``d._tap_member()``) are
+    deduplicated by content and go up as one class-path bank; the pool advances at one latency, ``latency_frames`` = the
+    bank's largest tap index.  For every stream the concatenation of everything returned equals
+    ``decorrelators[b].decorrelate(x_b)`` bit for bit.
+    All ``HaasEffect``: a ``streaming.HaasEachStream``, ``latency_frames`` 0 and ``tail_frames`` the largest delay; stream
+    b's own signal is the first ``n + tail_frames_each[b]`` frames of its concatenation, the rest is zeros.
+
+    A stream has no host loop to fall back to: everything not covered raises here, before any device call - ``TypeError``
+    for a mixed or unsupported decorrelator type; ``ValueError`` for an empty list, a normaliser, stage settings that
+    differ across the list, ``num_outs != 2``, a table past 4094 frames or a non-finite gain (stream those with the
+    decorrelator's own ``.stream()``), more than ``VND_MAX_STREAMS`` streams or 32767 distinct tables, or ``in_channels``
+    not in {1, 2}."""
+    from . import optimization, streaming
+    decorrelators = list(decorrelators)
+    if not decorrelators:
+        raise ValueError('decorrelate_each_stream needs at least one decorrelator: the pool has one stream per decorrelator')
+    kinds = {type(d) for d in decorrelators}
+    if len(kinds) > 1:
+        raise TypeError('decorrelate_each_stream takes decorrelators of one type, got '
+                        + ', '.join(sorted(k.__name__ for k in kinds)))
+    kind = kinds.pop()
+    if kind is not VelvetNoise and kind is not HaasEffect:
+        raise TypeError(f'decorrelate_each_stream streams plain VelvetNoise or HaasEffect decorrelators, not {kind.__name__}')
+    if isinstance(in_channels, (bool, np.bool_)) or in_channels not in (1, 2):
+        raise ValueError(f'in_channels must be 1 (mono, fanned out) or 2 (stereo), got {in_channels!r}')
+    if len(decorrelators) > _native.MAX_STREAMS_PER_CALL:
+        raise ValueError(f'{len(decorrelators)} streams, above {_native.MAX_STREAMS_PER_CALL} per pool: split the pool')
+    if kind is VelvetNoise:
+        _same_across(decorrelators, ('mode', 'width', 'normalizer'))
+        if decorrelators[0].normalizer is not None:
+            raise ValueError('VelvetNoise.stream needs normalizer=None: the RMS normaliser scales by the RMS of the whole '
+                             'input and output signals, which a stream only has once it has ended')
+        for b, d in enumerate(decorrelators):
+            if d.num_outs != 2:
+                raise ValueError(f'stream {b}: num_outs={d.num_outs}; a bank holds stereo pairs (num_outs == 2)')
+        key = _each_velvet_key(decorrelators[0])
+        if key is None:
+            raise ValueError('decorrelate_each_stream covers the LR and MS layouts and a finite Python / float64 width or '
+                             f'None, got mode={decorrelators[0].mode!r}, width={decorrelators[0].width!r}')
+        try:
+            members, tables = each_velvet_members(decorrelators)
+            inside = [_member_in_window(m) for m in members]
+        except (IndexError, TypeError) as exc:
+            raise ValueError(f'decorrelate_each_stream: a tap table cannot be built ({exc})') from exc
+        if not all(inside):
+            b = int(np.flatnonzero(tables == inside.index(False))[0])
+            raise ValueError(f'stream {b}: its table reaches past {_native.VELVET_PAIRS_MAX_TAP_INDEX} frames or has a gain '
+                             'that is not finite as float32; stream that decorrelator with its own .stream()')
+        if len(members) > _native.VELVET_BANK_MAX_CANDIDATES:
+            raise ValueError(f'{len(members)} distinct tap tables, above {_native.VELVET_BANK_MAX_CANDIDATES} per bank: '
+                             'split the pool')
+        ms_encode, width, _ = key
+        return streaming.EachStream(class_path_bank_arrays(members), tables, in_channels=in_channels,
+                                    max_frames_per_call=max_frames_per_call, ms_encode=ms_encode, width=width)
+    _same_across(decorrelators, ('delayed_channel', 'mode', 'width'))
+    key = optimization._haas_key(decorrelators[0])
+    delays = [optimization._haas_delay(d) for d in decorrelators]
+    if key is None or None in delays:
+        raise ValueError('decorrelate_each_stream covers a plain HaasEffect in LR or MS layout with delayed channel 0 or 1, '
+                         'an integer delay in [0, 2**31) and a finite Python / float64 width or None')
+    delayed_channel, ms_mode, width = key
+    return streaming.HaasEachStream(delays, in_channels=in_channels, max_frames_per_call=max_frames_per_call,
+                                    delayed_channel=delayed_channel, ms_mode=ms_mode, width=width)
+
+
 # ----------------------------------------------------------------------------
 # SignalChain   (decorrelation.py:71-153)
 # ----------------------------------------------------------------------------

@@ -20,7 +20,9 @@ call.  The calls are not graph-capturable: the stream position is a kernel argum
 
 Two more stream forms build on it: :class:`HaasStream` (``HaasEffect(...).stream(...)``, ``include/vnd_haas_stream.h``),
 the causal Haas delay with no latency and a tail of ``d`` frames, and :class:`ChainStream` (``SignalChain(...).stream(...)``),
-every stage of a chain on the device, block by block.
+every stage of a chain on the device, block by block.  :class:`EachStream` and :class:`HaasEachStream`
+(``decorrelate_each_stream``, ``include/vnd_each_stream.h``) run every stream of a pool through its own filter of a bank
+or its own delay, one launch per call for the whole pool.
 """
 from __future__ import annotations
 
@@ -365,6 +367,94 @@ class HaasStream(Stream):
                                                             self.max_frames_per_call, ctypes.byref(need)),
                        'vnd_haas_stream_state_bytes')
         return need.value
+
+
+class _PerStream:
+    """What the two per-stream forms share: one int32 value per stream (a table index, a delay) that the device entry
+    reads from device memory and the host entry from host memory.  The device copy goes up once, with the state, and
+    lives as long as the stream."""
+
+    def _set_each(self, values):
+        self._each_host = np.ascontiguousarray(values, np.int32)
+        self._each_dev = None
+        self._each_ptr = None
+
+    def _upload_each(self, ctx):
+        torch = _native.torch_module()
+        self._each_dev = torch.from_numpy(self._each_host).to(torch.device('cuda', ctx.device))
+
+    def _entry(self, ctx, name: str, *args):
+        self._each_ptr = self._each_host.ctypes.data if name == self._host_entry else self._each_dev.data_ptr()
+        return super()._entry(ctx, name, *args)
+
+
+class EachStream(_PerStream, Stream):
+    """A pool whose stream ``b`` runs through its own velvet-noise filter of a bank (``decorrelate_each_stream``).
+
+    The same interface as :class:`Stream`.  The pool advances in lockstep at one latency, ``latency_frames`` = the bank's
+    largest tap index: a stream whose own filter is shorter waits with the others.  For every stream the concatenation of
+    everything returned equals ``decorrelators[b].decorrelate(x_b)`` on the whole signal bit for bit, float32
+    ``(num_streams, n, 2)``.  ``tables`` is the int32 index of every stream's candidate in ``arrays``, a
+    ``class_path_bank_arrays`` bank.  Always ``MODE_EXACT``.  One kernel launch per call (``vnd_each_stream_f32_*``)."""
+
+    _host_entry, _dev_entry = 'vnd_each_stream_f32_host', 'vnd_each_stream_f32_dev'
+    num_channels = 2
+
+    def __init__(self, arrays: TapArrays, tables, *, in_channels: int, max_frames_per_call: int, ms_encode: bool = False,
+                 width: Optional[float] = None):
+        BlockStream.__init__(self, num_streams=len(tables), in_channels=in_channels,
+                             max_frames_per_call=max_frames_per_call)
+        if in_channels not in (1, 2):
+            raise ValueError(f'a pool of mono (1) or stereo (2) streams is taken, got in_channels={in_channels}')
+        if arrays.num_channels < 2 or arrays.num_channels % 2:
+            raise ValueError(f'a bank holds stereo pairs: this one has {arrays.num_channels} channels')
+        self._set_each(tables)
+        if self._each_host.min() < 0 or self._each_host.max() >= arrays.num_channels // 2:
+            raise ValueError(f'table indices outside [0, {arrays.num_channels // 2})')
+        self.arrays, self.tables, self.mode = arrays, self._each_host, _native.MODE_EXACT
+        self.ms_encode, self.width = bool(ms_encode), width
+        self.latency_frames = int(arrays.tap_index.max()) if len(arrays.tap_index) else 0
+        self._any_dtype, self._one_shot = True, 'VelvetNoise.decorrelate'
+        self._table = None
+
+    def _head(self, ctx):
+        return ctx.handle, self._table.handle, ctypes.c_void_p(self._each_ptr)
+
+    def _state_bytes(self, ctx) -> int:
+        from . import decorrelation
+        self._table = decorrelation._each_banks.get(ctx, self.arrays)
+        self._upload_each(ctx)
+        return _native.each_stream_state_bytes(self._table, self.num_streams, self.in_channels, self.max_frames_per_call)
+
+
+class HaasEachStream(_PerStream, HaasStream):
+    """A pool whose stream ``b`` is delayed by its own ``delays[b]`` frames (``decorrelate_each_stream``).
+
+    The same interface as :class:`HaasStream`; ``latency_frames`` is 0 and ``tail_frames`` the largest delay: the final
+    call returns that many frames more than it was given.  ``tail_frames_each`` is the int array of the streams' own
+    delays: stream ``b``'s signal is the first ``n + tail_frames_each[b]`` frames of its concatenation - bit-identical to
+    ``decorrelators[b].decorrelate(x_b)`` - and the rest is zeros.  One kernel launch per call
+    (``vnd_haas_each_stream_f64_*``)."""
+
+    _host_entry, _dev_entry = 'vnd_haas_each_stream_f64_host', 'vnd_haas_each_stream_f64_dev'
+
+    def __init__(self, delays, *, in_channels: int, max_frames_per_call: int, delayed_channel: int, ms_mode: bool,
+                 width: Optional[float]):
+        self._set_each(delays)
+        if self._each_host.ndim != 1 or not self._each_host.size or self._each_host.min() < 0:
+            raise ValueError('delays: one delay >= 0 per stream')
+        HaasStream.__init__(self, num_streams=len(self._each_host), in_channels=in_channels,
+                            max_frames_per_call=max_frames_per_call, delay=int(self._each_host.max()),
+                            delayed_channel=delayed_channel, ms_mode=ms_mode, width=width)
+        self.tail_frames_each = self._each_host.astype(np.int64)
+
+    def _tail(self, n_in: int, final: bool):
+        return (self.num_streams, self.position, n_in, self.in_channels, int(final), ctypes.c_void_p(self._each_ptr),
+                self.delay, self.delayed_channel, int(self.ms_mode), int(self.width is not None), float(self.width or 0.0))
+
+    def _state_bytes(self, ctx) -> int:
+        self._upload_each(ctx)
+        return _native.haas_each_stream_state_bytes(self.num_streams, self.in_channels, self.delay, self.max_frames_per_call)
 
 
 class StagePlan(NamedTuple):
