@@ -10,6 +10,7 @@ encode_side and apply_stereo_width (O.decorrelate's order).  Each case names the
 import contextlib
 import ctypes
 import io
+import itertools
 
 import numpy as np
 import pytest
@@ -619,6 +620,45 @@ def test_haas_python_route(dec):
         want = d.decorrelate(pool[b])
         assert got[b, :n + s.tail_frames_each[b]].tobytes() == want.tobytes(), b
         assert not got[b, n + s.tail_frames_each[b]:].view(np.int64).any(), b
+
+
+def test_one_delay_and_a_delay_per_stream_agree_on_every_call(dec, ctx):
+    """HaasStream with delay d and HaasEachStream with every delay d run one kernel (haas_stream_kernel<EACH>): call by
+    call they return the same float64 bits, on the host and on the device entries, and their concatenation is
+    HaasEffect.decorrelate of the whole signal.  The schedule 0, 1, 5, 7, 2, flush puts the first d output frames -
+    whose delayed column reads frames below 0 - into the second and third calls, and holds a block of exactly d = 7
+    frames and one shorter than d."""
+    import torch
+    from vndecorrelate_amd.streaming import HaasEachStream, HaasStream
+    schedule, S = (0, 1, 5, 7, 2), 3
+    n, M = sum(schedule), max(schedule)
+    device = torch.device('cuda', ctx.device)
+    for d, cx, delayed_channel, ms_mode, width in itertools.product((0, 1, 7), (1, 2), (0, 1), (False, True), (None, 0.3)):
+        x = _noise((S, n, cx), 70 + 10 * d + cx)
+        stage = dec.HaasEffect(sample_rate_hz=1, delay_time_seconds=float(d), delayed_channel=delayed_channel,
+                               mode='MS' if ms_mode else 'LR', width=width)
+        want = np.stack([stage.decorrelate(x[b, :, 0] if cx == 1 else x[b]) for b in range(S)])
+        assert want.shape == (S, n + d, 2) and want.dtype == np.float64
+        kw = dict(in_channels=cx, max_frames_per_call=M, delayed_channel=delayed_channel, ms_mode=ms_mode, width=width)
+        for on_device in (False, True):
+            where = (d, cx, delayed_channel, ms_mode, width, 'device' if on_device else 'host')
+            one, each = HaasStream(num_streams=S, delay=d, **kw), HaasEachStream([d] * S, **kw)
+            outs, first = [], 0
+            for call, B in enumerate(schedule + (None,)):
+                if B is None:
+                    a, b, frames = one.flush(), each.flush(), d
+                else:
+                    block = np.ascontiguousarray(x[:, first:first + B])
+                    if on_device:
+                        block = torch.from_numpy(block).to(device)
+                    a, b, frames = one.process(block), each.process(block), B
+                    first += B
+                if on_device:
+                    a, b = a.cpu().numpy(), b.cpu().numpy()
+                assert a.shape == b.shape == (S, frames, 2) and a.dtype == b.dtype == np.float64, (where, call)
+                assert a.tobytes() == b.tobytes(), (where, call)
+                outs.append(a)
+            assert np.concatenate(outs, axis=1).tobytes() == want.tobytes(), where
 
 
 # ---- 7. the optimisers' results, streamed ----------------------------------------------------------------------------

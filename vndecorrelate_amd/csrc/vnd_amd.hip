@@ -11,9 +11,9 @@
 //   vnd_haas_scan.hpp    the Haas-delay optimiser's scan (include/vnd_scan.h) and its pool pairs (include/vnd_haas_search.h)
 //   vnd_velvet_pairs.hpp the velvet-noise optimiser's scan over (signal, candidate) pairs of a pool (include/vnd_velvet_search.h)
 //   vnd_each.hpp         a pool through one filter or one delay per signal (include/vnd_each.h)
-//   vnd_stream.hpp       chunked streaming of the tap sum (include/vnd_stream.h)
-//   vnd_haas_stream.hpp  chunked streaming of the HaasEffect delay (include/vnd_haas_stream.h)
-//   vnd_each_stream.hpp  a pool streamed through one filter or one delay per stream (include/vnd_each_stream.h)
+//   vnd_stream.hpp       chunked streaming of the tap sum (include/vnd_stream.h); the ring of every float32 block stream
+//   vnd_haas_stream.hpp  chunked streaming of the HaasEffect delay, one for the pool or one per stream (include/vnd_haas_stream.h, vnd_each_stream.h)
+//   vnd_each_stream.hpp  a pool streamed through one filter per stream (include/vnd_each_stream.h)
 #include "vnd_objects.hpp"
 #include "vnd_plan.hpp"
 

@@ -6,7 +6,8 @@
 // The block ranges, the staging, cg_load / cg_block, the energy chains and butterfly and the float32 normaliser are the
 // one-shot kernel's, so every row is the same operation sequence on the same values: bit for bit the one-shot call's row.
 //
-// Ring.  Per stream, cap = W - 1 + max_frames_per_call frames of interleaved float32 (x, y) pairs.  A call's launch copies
+// Ring (its own, planar float2 from strided sources; the contract is RingArgs' of vnd_stream.hpp with reach = W - 1).
+// Per stream, cap = W - 1 + max_frames_per_call frames of interleaved float32 (x, y) pairs.  A call's launch copies
 // the chunk's last min(n_in, W - 1) frames into the ring.  Why no slot is both read and written in one call:
 //   * the windows completing in a call are w >= wc(pos), and window wc(pos) was not complete at pos: wc(pos) H + W - 1 >=
 //     pos, so every frame read from the ring lies in [pos - W + 1, pos);

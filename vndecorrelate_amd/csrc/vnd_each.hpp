@@ -33,45 +33,56 @@ struct EachArgs {
     int32_t T;                                          // candidates in the bank
 };
 
+// One tile of a stream or signal through candidate `cand` of the bank - what each_kernel and each_stream_kernel
+// (vnd_each_stream.hpp) share.  stage() fills the CX planes of W floats at `lds` with the tile's window; store(q, v) takes
+// frame pair q = tid + kVpThreads * j, j < R, as (L_f, R_f, L_f+1, R_f+1), f = 2q.  cand is workgroup-uniform; outside
+// [0, T) - outside the contract - the tile's row is NaN and nothing is staged.
+template <int CX, int MODE, int R, bool EPI, typename Stage, typename Store>
+__device__ __forceinline__ void each_tile(const KArgs &k, const float *lds, int32_t cand, int32_t T, Stage stage, Store store)
+{
+    const int tid = threadIdx.x;
+    if (cand < 0 || cand >= T) {
+        const float nan = __builtin_nanf("");
+        const float v[4] = {nan, nan, nan, nan};
+#pragma unroll
+        for (int j = 0; j < R; ++j) store(tid + kVpThreads * j, v);
+        return;
+    }
+    stage();
+    __syncthreads();
+    const float *right = lds + (CX == 2 ? k.W : 0);
+    v2f out[2][R];
+    vp_channel<MODE, R>(k, 2 * cand, lds + 2 * tid, out[0]);
+    vp_channel<MODE, R>(k, 2 * cand + 1, right + 2 * tid, out[1]);
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        const int q = tid + kVpThreads * j;
+        float v[4] = {out[0][j].x, out[1][j].x, out[0][j].y, out[1][j].y};
+        if constexpr (EPI) {
+            const float2 x0 = *(const float2 *)(lds + 2 * q), x1 = *(const float2 *)(right + 2 * q);
+            const float xin[4] = {x0.x, x1.x, x0.y, x1.y};
+            epi_pointwise(k, v, xin);
+        }
+        store(q, v);
+    }
+}
+
 // grid = (ceil(n / kVpTile), batch); dynamic LDS = CX planes of k.W floats
 template <int CX, int MODE, bool EPI>
 __global__ __launch_bounds__(kVpThreads) void each_kernel(const EachArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float each_lds[];
-    const int tid = threadIdx.x;
     const KArgs &k = a.k;
-    const int W = k.W;
     const int64_t b = blockIdx.y;
     const int64_t t0 = (int64_t)blockIdx.x * kVpTile;
     const float *__restrict__ xs = k.x + b * k.n * CX;
     float *dst = k.y + (b * k.n + t0) * 2;
     const v4i rdst = make_rsrc(dst, (k.n - t0) * 2 * 4);           // the rest of this signal's row: nothing past it is written
     const int shape = access_shape<2>(dst, 2);                     // workgroup-uniform
-    const int32_t cand = __builtin_amdgcn_readfirstlane(a.tables[b]);
-    if (cand < 0 || cand >= a.T) {                                 // outside the contract: the signal's row is NaN
-        const float nan = __builtin_nanf("");
-        const float v[4] = {nan, nan, nan, nan};
-#pragma unroll
-        for (int j = 0; j < kVpR; ++j) store_result_aux<2, kStoreAux>(rdst, shape, tid + kVpThreads * j, 1, 2, v);
-        return;
-    }
-    stage_window<kVpThreads, CX>(each_lds, xs + t0 * CX, (k.n - t0) * CX * 4, CX, W, tid);
-    __syncthreads();
-    const float *right = each_lds + (CX == 2 ? W : 0);
-    v2f out[2][kVpR];
-    vp_channel<MODE>(k, 2 * cand, each_lds + 2 * tid, out[0]);
-    vp_channel<MODE>(k, 2 * cand + 1, right + 2 * tid, out[1]);
-#pragma unroll
-    for (int j = 0; j < kVpR; ++j) {
-        const int q = tid + kVpThreads * j;
-        float v[4] = {out[0][j].x, out[1][j].x, out[0][j].y, out[1][j].y};
-        if constexpr (EPI) {
-            const float2 x0 = *(const float2 *)(each_lds + 2 * q), x1 = *(const float2 *)(right + 2 * q);
-            const float xin[4] = {x0.x, x1.x, x0.y, x1.y};
-            epi_pointwise(k, v, xin);
-        }
-        store_result_aux<2, kStoreAux>(rdst, shape, q, 1, 2, v);
-    }
+    each_tile<CX, MODE, kVpR, EPI>(
+        k, each_lds, __builtin_amdgcn_readfirstlane(a.tables[b]), a.T,
+        [&] { stage_window<kVpThreads, CX>(each_lds, xs + t0 * CX, (k.n - t0) * CX * 4, CX, k.W, (int)threadIdx.x); },
+        [&](int q, const float (&v)[4]) { store_result_aux<2, kStoreAux>(rdst, shape, q, 1, 2, v); });
 }
 
 struct HeArgs {
@@ -108,6 +119,28 @@ __global__ __launch_bounds__(kHaasThreads) void haas_each_kernel(const HeArgs a)
 
 extern "C" {
 
+// The bank of a filter per signal or per stream, in two halves: a stream entry reports its position and frame count between
+// them.  `one` / `many`: "signal" / "signals" or "stream" / "streams"; `instead`: what to do with a bank that is refused.
+static vnd_status each_bank_pairs(const vnd_ctx *ctx, const vnd_taps *t)
+{
+    if (t->C % 2 != 0) return fail(VND_ERR_INVALID, "a bank holds stereo pairs: this one has %d channels", t->C);
+    if (t->ctx != ctx && t->ctx->device != ctx->device)
+        return fail(VND_ERR_INVALID, "the tap table lives on device %d, the context on device %d", t->ctx->device, ctx->device);
+    return VND_OK;
+}
+
+static vnd_status each_bank_limits(const vnd_taps *t, int64_t batch, int32_t mode, const char *one, const char *many,
+                                   const char *instead)
+{
+    if (mode != VND_MODE_EXACT) return fail(VND_ERR_UNSUPPORTED, "a filter per %s runs in VND_MODE_EXACT only, got mode %d", one, mode);
+    if (batch > VND_MAX_STREAMS) return fail(VND_ERR_UNSUPPORTED, "more than %d %s per call: split the pool", VND_MAX_STREAMS, many);
+    if (t->max_index > VND_VELVET_PAIRS_MAX_TAP_INDEX || !t->lds_images)
+        return fail(VND_ERR_UNSUPPORTED, "the bank's largest tap index %d is above %d: %s", t->max_index,
+                    VND_VELVET_PAIRS_MAX_TAP_INDEX, instead);
+    if (t->nonfinite) return fail(VND_ERR_UNSUPPORTED, "the bank has a weight that is not finite: %s", instead);
+    return VND_OK;
+}
+
 // What every velvet entry checks before anything else: scalars and the bank, no index array (after velvet_pairs_check).
 static vnd_status each_check(const vnd_ctx *ctx, const vnd_taps *t, int32_t batch, int64_t n_frames, int32_t in_channels,
                              int32_t mode)
@@ -116,15 +149,9 @@ static vnd_status each_check(const vnd_ctx *ctx, const vnd_taps *t, int32_t batc
     if (batch < 0 || n_frames < 0) return fail(VND_ERR_INVALID, "negative batch or frame count");
     if (in_channels != 1 && in_channels != 2)
         return fail(VND_ERR_INVALID, "a pool of mono or stereo signals is taken, got %d channels", in_channels);
-    if (t->C % 2 != 0) return fail(VND_ERR_INVALID, "a bank holds stereo pairs: this one has %d channels", t->C);
-    if (t->ctx != ctx && t->ctx->device != ctx->device)
-        return fail(VND_ERR_INVALID, "the tap table lives on device %d, the context on device %d", t->ctx->device, ctx->device);
-    if (mode != VND_MODE_EXACT) return fail(VND_ERR_UNSUPPORTED, "a filter per signal runs in VND_MODE_EXACT only, got mode %d", mode);
-    if (batch > VND_MAX_STREAMS) return fail(VND_ERR_UNSUPPORTED, "more than %d signals per call: split the pool", VND_MAX_STREAMS);
-    if (t->max_index > VND_VELVET_PAIRS_MAX_TAP_INDEX || !t->lds_images)
-        return fail(VND_ERR_UNSUPPORTED, "the bank's largest tap index %d is above %d: convolve it signal by signal", t->max_index,
-                    VND_VELVET_PAIRS_MAX_TAP_INDEX);
-    if (t->nonfinite) return fail(VND_ERR_UNSUPPORTED, "the bank has a weight that is not finite: convolve it signal by signal");
+    vnd_status st = each_bank_pairs(ctx, t);
+    if (st == VND_OK) st = each_bank_limits(t, batch, mode, "signal", "signals", "convolve it signal by signal");
+    if (st != VND_OK) return st;
     if (n_frames > 0 && (int64_t)batch > INT64_MAX / 8 / n_frames)
         return fail(VND_ERR_UNSUPPORTED, "pool of %d x %lld frames too large", batch, (long long)n_frames);
     if (velvet_tiles(n_frames) > INT32_MAX) return fail(VND_ERR_UNSUPPORTED, "signal above %lld frames", (long long)kVpTile * INT32_MAX);
@@ -201,15 +228,6 @@ vnd_status vnd_decorrelate_each_f32_dev(vnd_ctx *ctx, const vnd_taps *t, const f
     return stage_sums(ctx, s, x, y, batch, n, in_channels, 2, normalize, seq, false, stream);
 }
 
-// the host entries' index check: every entry of tables, before anything is launched
-static vnd_status each_tables(const int32_t *tables, int32_t batch, int32_t T)
-{
-    for (int32_t b = 0; b < batch; ++b)
-        if (tables[b] < 0 || tables[b] >= T)
-            return fail(VND_ERR_INVALID, "table %d of signal %d is outside [0, %d)", tables[b], b, T);
-    return VND_OK;
-}
-
 static vnd_status each_host(vnd_ctx *ctx, const vnd_taps *t, const float *x, const int32_t *tables, float *y, int32_t batch,
                             int64_t n, int32_t Cx, int32_t mode, bool stage, int32_t ms_encode, int32_t use_width, double width,
                             int32_t normalize, float eps, const char *name)
@@ -218,23 +236,16 @@ static vnd_status each_host(vnd_ctx *ctx, const vnd_taps *t, const float *x, con
     if (st != VND_OK) return st;
     if (batch == 0 || n == 0) return VND_OK;
     if ((st = each_pointers(x, tables, y, batch, n, Cx)) != VND_OK) return st;
-    if ((st = each_tables(tables, batch, t->C / 2)) != VND_OK) return st;
     int64_t ws = 0;
     if (stage && normalize) vnd_decorrelate_workspace_bytes(batch, n, 2, &ws);
+    const HostIndex ix{tables, t->C / 2, false, "table", "tables", "signal"};
     HostCall call(ctx);
-    const size_t x_bytes = (size_t)batch * n * Cx * sizeof(float), y_bytes = (size_t)batch * n * 2 * sizeof(float);
-    const size_t i_bytes = (size_t)batch * sizeof(int32_t);
-    call.carve({(size_t)ws, y_bytes, x_bytes, i_bytes});
-    float *y_dev = call.piece<float>(1), *x_dev = call.piece<float>(2);
-    int32_t *t_dev = call.piece<int32_t>(3);
-    call.up(x_dev, x, x_bytes, "x");
-    call.up(t_dev, tables, i_bytes, "tables");
-    call.run([&] {
-        if (!stage) return vnd_convolve_each_f32_dev(ctx, t, x_dev, t_dev, y_dev, batch, n, Cx, mode, call.stream());
-        return vnd_decorrelate_each_f32_dev(ctx, t, x_dev, t_dev, y_dev, batch, n, Cx, mode, ms_encode, use_width, width, normalize,
-                                            eps, call.piece<char>(0), ws, call.stream());
+    call.staged(x, (size_t)batch * n * Cx * sizeof(float), "x", y, (size_t)batch * n * 2 * sizeof(float), &ix, batch, (size_t)ws,
+                nullptr, [&](void *x_dev, void *y_dev, int32_t *t_dev, void *ws_dev, hipStream_t s) {
+        if (!stage) return vnd_convolve_each_f32_dev(ctx, t, (const float *)x_dev, t_dev, (float *)y_dev, batch, n, Cx, mode, s);
+        return vnd_decorrelate_each_f32_dev(ctx, t, (const float *)x_dev, t_dev, (float *)y_dev, batch, n, Cx, mode, ms_encode,
+                                            use_width, width, normalize, eps, ws_dev, ws, s);
     });
-    call.down(y, y_dev, y_bytes, "y");
     return call.finish(name);
 }
 
@@ -295,22 +306,13 @@ vnd_status vnd_haas_each_f64_host(vnd_ctx *ctx, const float *x, double *y, int64
     const int64_t rows = n + max_delay;
     if (batch == 0 || rows == 0) return VND_OK;
     if (!y || !delays || (n > 0 && !x)) return fail(VND_ERR_INVALID, "null signal or delay pointer");
-    for (int64_t b = 0; b < batch; ++b)
-        if (delays[b] < 0 || delays[b] > max_delay)
-            return fail(VND_ERR_INVALID, "delay %d of signal %lld is outside [0, %d]", delays[b], (long long)b, max_delay);
+    const HostIndex ix{delays, max_delay, true, "delay", "delays", "signal"};
     HostCall call(ctx);
-    const size_t in_bytes = (size_t)batch * n * in_channels * sizeof(float);
-    const size_t out_bytes = (size_t)batch * rows * 2 * sizeof(double);
-    const size_t d_bytes = (size_t)batch * sizeof(int32_t);
-    call.carve({out_bytes, in_bytes, d_bytes});
-    double *y_dev = call.piece<double>(0);
-    float *x_dev = call.piece<float>(1);
-    int32_t *d_dev = call.piece<int32_t>(2);
-    call.up(x_dev, x, in_bytes, "x");
-    call.up(d_dev, delays, d_bytes, "delays");
-    call.run([&] { return vnd_haas_each_f64_dev(ctx, x_dev, y_dev, batch, n, in_channels, d_dev, max_delay, delayed_channel, ms_mode,
-                                                use_width, width, call.stream()); });
-    call.down(y, y_dev, out_bytes, "y");
+    call.staged(x, (size_t)batch * n * in_channels * sizeof(float), "x", y, (size_t)batch * rows * 2 * sizeof(double), &ix, batch, 0,
+                nullptr, [&](void *x_dev, void *y_dev, int32_t *d_dev, void *, hipStream_t s) {
+        return vnd_haas_each_f64_dev(ctx, (const float *)x_dev, (double *)y_dev, batch, n, in_channels, d_dev, max_delay,
+                                     delayed_channel, ms_mode, use_width, width, s);
+    });
     return call.finish("vnd_haas_each_f64_host");
 }
 

@@ -11,6 +11,14 @@ static int host_chunks(int64_t batch, size_t bytes)
     return (int)std::min<int64_t>(std::min<int64_t>(batch, 16), (int64_t)std::max<size_t>(want, 2));
 }
 
+// A per-row int32 array of a host call (a table index or a delay per stream): every entry in [0, bound) - closed: [0, bound].
+struct HostIndex {
+    const int32_t *v;
+    int32_t bound;
+    bool closed;
+    const char *one, *many, *row;       // "table", "tables", "stream": the words of the error message and of the upload
+};
+
 // One synchronous *_host call.  It holds the context's host lock and device for its lifetime, hands out the staging buffers and
 // the workspace, and queues copies and launches on the context's two streams.  After the first failure every further step is
 // skipped, and there is ONE way out: finish() - or, for a path that forgets it, the destructor - waits for every stream this call
@@ -67,6 +75,29 @@ public:
     template <typename Dev>
     void run(Dev &&dev) { if (ok()) st_ = dev(); }          // dev: a callable around a _dev entry or launch(), on stream(lane)
     void hip(hipError_t e, const char *step, const char *what = "") { if (ok() && e != hipSuccess) { err_ = e; step_ = step; what_ = what; } }
+
+    // The whole of a staged call around a _dev entry: x up, y down, optionally `rows` entries of a HostIndex up and `extra`
+    // bytes of workspace; dev(x_dev, y_dev, index_dev, extra_dev, stream) is the callable around the entry.  The index
+    // array is checked first: on a bad entry nothing is queued, *n_out (if any) is 0 and finish() returns the failure.
+    template <typename Dev>
+    void staged(const void *x, size_t x_bytes, const char *x_name, void *y, size_t y_bytes, const HostIndex *ix, int64_t rows,
+                size_t extra_bytes, int64_t *n_out, Dev &&dev)
+    {
+        for (int64_t b = 0; ix && b < rows && ok(); ++b)
+            if (ix->v[b] < 0 || ix->v[b] > ix->bound - (ix->closed ? 0 : 1)) {
+                if (n_out) *n_out = 0;
+                st_ = fail(VND_ERR_INVALID, "%s %d of %s %lld is outside [0, %d%c", ix->one, ix->v[b], ix->row, (long long)b,
+                           ix->bound, ix->closed ? ']' : ')');
+            }
+        const size_t i_bytes = ix ? (size_t)rows * sizeof(int32_t) : 0;
+        carve({extra_bytes, y_bytes, x_bytes, i_bytes});
+        char *y_dev = piece<char>(1), *x_dev = piece<char>(2);
+        int32_t *i_dev = ix ? piece<int32_t>(3) : nullptr;
+        up(x_dev, x, x_bytes, x_name);
+        if (ix) up(i_dev, ix->v, i_bytes, ix->many);
+        run([&] { return dev(x_dev, y_dev, i_dev, piece<char>(0), stream()); });
+        down(y, y_dev, y_bytes, "y");
+    }
 
     // The one exit: the first vnd_status failure (its message stands), else the first HIP error, named after `call`.
     vnd_status finish(const char *call)

@@ -1,15 +1,15 @@
-// vnd_stream.hpp - chunked streaming of the velvet-noise tap sum (include/vnd_stream.h).
+// vnd_stream.hpp - chunked streaming of the velvet-noise tap sum (include/vnd_stream.h), and the ring every block stream
+// of float32 frames keeps its history in (RingArgs, ring_plan, ring_write: the velvet streams here and in
+// vnd_each_stream.hpp, the Haas streams in vnd_haas_stream.hpp).
 //
 // The tap sum is anti-causal, y[n] = sum_k w[c,k] * x[n + i[c,k]], so output frame n is final once input frame n + H has
 // arrived (H = the table's largest tap index).  A pool of streams advances in lockstep; a call pushes n_in frames per stream
 // at absolute position pos and writes outputs [E, E') of every stream:
 //     E  = max(0, pos - H)
 //     E' = final ? pos + n_in : max(0, pos + n_in - H)
-// It reads the virtual input x[E .. E' + H) clipped to [0, pos + n_in): frames below pos from a per-stream RING in device
-// memory (capacity >= H + max_frames_per_call, slot = absolute frame mod capacity), frames from pos on from the caller's
-// chunk, frames past the end as 0 - what the one-shot kernels' range-checked loads read there.  The kernel also copies the
-// chunk's last min(n_in, H) frames into the ring: with that capacity no slot read in a call is written in the same call
-// (a read frame f and a written frame g have 0 < g - f <= H + n_in - 1 < capacity), and every frame is written once.
+// It reads the virtual input x[E .. E' + H) clipped to [0, pos + n_in): frames below pos from the stream's ring, frames
+// from pos on from the caller's chunk, frames past the end as 0 - what the one-shot kernels' range-checked loads read
+// there.  The same launch copies the chunk's last min(n_in, H) frames into the ring (the ring contract: RingArgs below).
 //
 // Compute and store are the one-shot kernels' (vnd_kernels.hpp), called unchanged: ordered_tap / ordered_consume for the exact
 // and fma modes, run_tap_array (even / odd chains) for the fast mode, epi_pointwise for the side-channel encode and the width,
@@ -21,39 +21,55 @@
 
 namespace vnd {
 
-struct StreamArgs {
-    KArgs k;                       // k.n = output frames per stream of this call, k.Cx = channels of the chunk and the ring
+// THE RING.  A stream's history lives in a per-stream ring in device memory, owned by the caller: `cap` frames of Cx
+// float32 samples, slot = absolute frame mod cap.  `reach` is how far below pos a call may read: the table's largest tap
+// index H (velvet), the delay d (Haas) or the pool's max_delay (a delay per stream).  The contract, for every user:
+//   - capacity: cap >= reach + max_frames_per_call (and n_in <= max_frames_per_call is checked before every launch);
+//   - a call reads ring frames in [pos - reach, pos) only, never a frame below 0 (so the ring needs no clearing);
+//   - the same launch writes the chunk's last min(n_in, reach) frames [wr_first, pos + n_in) - none after the final
+//     call, none with reach = 0 - each stream's workgroups sharing them in grid-stride order (ring_write);
+//   - so a frame f read and a frame g written in one call have 0 < g - f <= reach + n_in - 1 < cap: they never share a
+//     slot, NO SLOT IS BOTH READ AND WRITTEN IN ONE CALL, no ordering between a call's workgroups is needed, and every
+//     frame is written exactly once.
+// The host computes the slots (ring_plan): no lane divides.
+struct RingArgs {
     const float *__restrict__ chunk;   // [batch][n_in][Cx]
     float *__restrict__ ring;          // [batch][cap][Cx]
-    int64_t pos, n_in, first_out;      // first_out = E
+    int64_t pos, n_in;
     int64_t cap;                       // ring capacity, frames
-    int64_t wr_first, wr_count;        // chunk frames [wr_first, wr_first + wr_count) (absolute) go to the ring
-    int32_t direct_epi;                // direct variant: one lane per frame, both channels, pointwise epilogue
+    int64_t wr_first, wr_count, wr_slot0;   // chunk frames [wr_first, wr_first + wr_count) (absolute) go to the ring, from slot wr_slot0
+    int32_t Cx;
 };
 
-// The chunk frames later calls need, into the ring: a stream's workgroups share them in grid-stride order.
-// (Slots of this call's reads are never among them: see above.)
+// The chunk frames later calls need, into the ring; `worker` of a stream's `workers` workgroups of NT lanes.
 template <int NT>
-__device__ __forceinline__ void stream_ring_write(const StreamArgs &a, int64_t stream, int64_t w, int64_t nw, int tid)
+__device__ __forceinline__ void ring_write(const RingArgs &r, int64_t stream, int64_t worker, int64_t workers, int tid)
 {
-    const int Cx = a.k.Cx;
-    const int64_t total = a.wr_count * Cx;
+    const int Cx = r.Cx;
+    const int64_t total = r.wr_count * Cx;
     if (total <= 0) return;
-    const int64_t capf = a.cap * Cx;
-    const float *__restrict__ src = a.chunk + stream * a.n_in * Cx + (a.wr_first - a.pos) * Cx;
-    float *__restrict__ dst = a.ring + stream * capf;
-    const int64_t s0 = (a.wr_first % a.cap) * Cx;
-    for (int64_t e = w * NT + tid; e < total; e += nw * NT) {
+    const int64_t capf = r.cap * Cx;
+    const float *__restrict__ src = r.chunk + (stream * r.n_in + (r.wr_first - r.pos)) * Cx;
+    float *__restrict__ dst = r.ring + stream * capf;
+    const int64_t s0 = r.wr_slot0 * Cx;
+    for (int64_t e = worker * NT + tid; e < total; e += workers * NT) {
         int64_t s = s0 + e;
         if (s >= capf) s -= capf;
         dst[s] = src[e];
     }
 }
 
+struct StreamArgs {
+    KArgs k;                       // k.n = output frames per stream of this call, k.Cx = r.Cx
+    RingArgs r;
+    int64_t first_out;             // E
+    int32_t direct_epi;            // direct variant: one lane per frame, both channels, pointwise epilogue
+};
+
 // One source frame of the virtual input: the ring below pos, the chunk up to pos + n_in, 0 past it.
-__device__ __forceinline__ float stream_sample(const StreamArgs &a, int64_t stream, int64_t f, int64_t ring_slot, int ch)
+__device__ __forceinline__ float stream_sample(const RingArgs &a, int64_t stream, int64_t f, int64_t ring_slot, int ch)
 {
-    const int Cx = a.k.Cx;
+    const int Cx = a.Cx;
     if (f < a.pos) return a.ring[(stream * a.cap + ring_slot) * Cx + ch];
     if (f < a.pos + a.n_in) return a.chunk[(stream * a.n_in + (f - a.pos)) * Cx + ch];
     return 0.0f;
@@ -62,7 +78,7 @@ __device__ __forceinline__ float stream_sample(const StreamArgs &a, int64_t stre
 // The window [base, base + W) of PG input channels from cx0 on, into per-channel LDS planes.  Consecutive lanes take
 // consecutive (frame, channel) samples, so both sources are read on consecutive addresses; kStageDepth loads in flight.
 template <int NT, int PG>
-__device__ __forceinline__ void stream_stage(const StreamArgs &a, float *plane, int64_t stream, int64_t base, int cx0,
+__device__ __forceinline__ void stream_stage(const RingArgs &a, float *plane, int64_t stream, int64_t base, int cx0,
                                              int W, int tid)
 {
     const int64_t slot0 = base % a.cap;            // only frames below pos are read from the ring: they lie within H of base
@@ -105,7 +121,7 @@ __global__ __launch_bounds__(NT) void conv_stream_kernel(const StreamArgs sa)
     const int W = a.W;
     const BlockCoord bc = decode_block(a);
     const int C = a.C, Cx = a.Cx;
-    stream_ring_write<NT>(sa, bc.stream, (int64_t)bc.tile * a.groups + bc.group, (int64_t)a.tiles * a.groups, tid);
+    ring_write<NT>(sa.r, bc.stream, (int64_t)bc.tile * a.groups + bc.group, (int64_t)a.tiles * a.groups, tid);
     if (a.n == 0) return;                          // (a call that only fills the ring: one workgroup per stream)
 
     const int c0 = bc.group * CG;
@@ -113,7 +129,7 @@ __global__ __launch_bounds__(NT) void conv_stream_kernel(const StreamArgs sa)
     const int64_t t0 = (int64_t)bc.tile * T;
     float *__restrict__ ys = a.y + bc.stream * a.n * C;
     const int64_t bytes_left = ((a.n - t0) * C - c0) * 4;
-    stream_stage<NT, PG>(sa, lds, bc.stream, sa.first_out + t0, cx0, W, tid);
+    stream_stage<NT, PG>(sa.r, lds, bc.stream, sa.first_out + t0, cx0, W, tid);
     __syncthreads();
 
     float v_out[R][2 * CG];                        // per j: frames 2q, 2q+1 of the CG channels
@@ -250,9 +266,9 @@ __device__ __forceinline__ float stream_direct_channel(const StreamArgs &sa, int
 {
     const KArgs &a = sa.k;
     const int cx = ch % a.Cx;
-    const int64_t end = sa.pos + sa.n_in;
-    auto slot_of = [&](int64_t f) { return f % sa.cap; };
-    if (a.chan_flags != nullptr && (a.chan_flags[ch] & 1)) return stream_sample(sa, b, fo, slot_of(fo), cx);
+    const int64_t end = sa.r.pos + sa.r.n_in;
+    auto slot_of = [&](int64_t f) { return f % sa.r.cap; };
+    if (a.chan_flags != nullptr && (a.chan_flags[ch] & 1)) return stream_sample(sa.r, b, fo, slot_of(fo), cx);
     const bool has_seg = a.seg_off != nullptr;
     int k = a.tap_off[ch];
     const int k_last = a.tap_off[ch + 1];
@@ -266,7 +282,7 @@ __device__ __forceinline__ float stream_direct_channel(const StreamArgs &sa, int
             const Tap tp = a.taps[k];
             const int64_t m = fo + tp.idx;
             if (m >= end) continue;                 // the term DROPS, as in the one-shot direct kernel
-            sb = tap_op<MODE>(sb, stream_sample(sa, b, m, slot_of(m), cx), tp.w);
+            sb = tap_op<MODE>(sb, stream_sample(sa.r, b, m, slot_of(m), cx), tp.w);
         }
         if (has_seg) {
             if (a.apply_gain) sb = sb * a.seg_gain[s_begin + s];
@@ -285,7 +301,7 @@ __global__ __launch_bounds__(kDirectThreads) void conv_stream_direct_kernel(cons
     const int64_t batch = a.tiles;                 // tiles carries the batch here, as in conv_direct_kernel
     const int64_t per_block = (int64_t)gridDim.x / batch;     // the grid is a whole number of blocks per stream
     const int64_t b_ring = blockIdx.x / per_block;
-    stream_ring_write<kDirectThreads>(sa, b_ring, blockIdx.x - b_ring * per_block, per_block, threadIdx.x);
+    ring_write<kDirectThreads>(sa.r, b_ring, blockIdx.x - b_ring * per_block, per_block, threadIdx.x);
     const int lanes_per_frame = sa.direct_epi ? 1 : a.C;
     const int64_t per_stream = a.n * lanes_per_frame;
     const int64_t total = per_stream * batch;
@@ -300,8 +316,8 @@ __global__ __launch_bounds__(kDirectThreads) void conv_stream_direct_kernel(cons
             float v[4], xin[4];
             v[0] = v[2] = stream_direct_channel<MODE>(sa, b, fo, 0);
             v[1] = v[3] = stream_direct_channel<MODE>(sa, b, fo, 1);
-            xin[0] = xin[2] = stream_sample(sa, b, fo, fo % sa.cap, 0);
-            xin[1] = xin[3] = stream_sample(sa, b, fo, fo % sa.cap, a.Cx == 1 ? 0 : 1);
+            xin[0] = xin[2] = stream_sample(sa.r, b, fo, fo % sa.r.cap, 0);
+            xin[1] = xin[3] = stream_sample(sa.r, b, fo, fo % sa.r.cap, a.Cx == 1 ? 0 : 1);
             epi_pointwise(a, v, xin);
             yf[0] = v[0]; yf[1] = v[1];
         } else {
@@ -411,6 +427,34 @@ static StreamPlan make_stream_plan(const vnd_ctx *ctx, const vnd_taps *t, int64_
     return p;
 }
 
+// The ring side of a call (RingArgs above): which chunk frames go to the ring, and from which slot.  reach = 0 keeps nothing.
+static RingArgs ring_plan(int64_t pos, int64_t n_in, int64_t reach, bool final_, int64_t cap)
+{
+    RingArgs r{};
+    r.pos = pos; r.n_in = n_in; r.cap = cap;
+    // the last `reach` frames of the chunk are what later calls read (none after the final call)
+    r.wr_first = (final_ || reach == 0) ? pos + n_in : std::max<int64_t>(pos, pos + n_in - reach);
+    r.wr_count = pos + n_in - r.wr_first;
+    r.wr_slot0 = cap > 0 ? r.wr_first % cap : 0;
+    return r;
+}
+
+// nothing to compute and nothing to keep: the call launches nothing
+static bool ring_idle(const RingArgs &r, int64_t batch, int64_t n_out) { return batch == 0 || (n_out == 0 && r.wr_count == 0); }
+
+// What every block stream checks of its position, frame count and state, in this order.
+static vnd_status block_stream_check(int64_t pos, int64_t n_in, int64_t max_frames_per_call, int64_t state_bytes, int64_t need)
+{
+    if (pos < 0 || pos > ((int64_t)1 << 60)) return fail(VND_ERR_INVALID, "position %lld out of range", (long long)pos);
+    if (n_in < 0) return fail(VND_ERR_INVALID, "negative frame count");
+    if (n_in > max_frames_per_call)
+        return fail(VND_ERR_INVALID, "%lld frames in one call, above max_frames_per_call %lld", (long long)n_in,
+                    (long long)max_frames_per_call);
+    if (state_bytes < need)
+        return fail(VND_ERR_INVALID, "state of %lld bytes, the stream needs %lld", (long long)state_bytes, (long long)need);
+    return VND_OK;
+}
+
 static int64_t stream_capacity(const vnd_taps *t, int64_t max_frames_per_call)
 {
     return std::max<int64_t>(1, (int64_t)t->max_index + max_frames_per_call);
@@ -447,13 +491,7 @@ static vnd_status stream_check(vnd_ctx *ctx, const vnd_taps *t, const void *stat
     vnd_status st = vnd_stream_state_bytes(t, batch, Cx, max_frames_per_call, &need);
     if (st != VND_OK) return st;
     if (mode != VND_MODE_EXACT && mode != VND_MODE_FMA && mode != VND_MODE_FAST) return fail(VND_ERR_INVALID, "unknown mode %d", mode);
-    if (pos < 0 || pos > ((int64_t)1 << 60)) return fail(VND_ERR_INVALID, "position %lld out of range", (long long)pos);
-    if (n_in < 0) return fail(VND_ERR_INVALID, "negative frame count");
-    if (n_in > max_frames_per_call)
-        return fail(VND_ERR_INVALID, "%lld frames in one call, above max_frames_per_call %lld", (long long)n_in,
-                    (long long)max_frames_per_call);
-    if (state_bytes < need)
-        return fail(VND_ERR_INVALID, "state of %lld bytes, the stream needs %lld", (long long)state_bytes, (long long)need);
+    if ((st = block_stream_check(pos, n_in, max_frames_per_call, state_bytes, need)) != VND_OK) return st;
     if ((ms_encode || use_width) && t->C != 2)
         return fail(VND_ERR_INVALID, "the side-channel encode and the width need 2 output channels, the table has %d", t->C);
     const int64_t H = t->max_index;
@@ -476,13 +514,10 @@ vnd_status vnd_stream_f32_dev(vnd_ctx *ctx, const vnd_taps *t, void *state, int6
     if (st != VND_OK) return st;
     const int64_t H = t->max_index, C = t->C, nout = *n_out;
     StreamArgs sa{};
-    sa.chunk = x; sa.ring = (float *)state;
-    sa.pos = pos; sa.n_in = n_in; sa.first_out = std::max<int64_t>(0, pos - H);
-    sa.cap = stream_capacity(t, max_frames_per_call);
-    // the last H frames of the chunk are what later calls read (none after the final call)
-    sa.wr_first = final_ ? pos + n_in : std::max<int64_t>(pos, pos + n_in - H);
-    sa.wr_count = pos + n_in - sa.wr_first;
-    if (batch == 0 || (nout == 0 && sa.wr_count == 0)) return VND_OK;
+    sa.r = ring_plan(pos, n_in, H, final_, stream_capacity(t, max_frames_per_call));
+    sa.r.chunk = x; sa.r.ring = (float *)state; sa.r.Cx = Cx;
+    sa.first_out = std::max<int64_t>(0, pos - H);
+    if (ring_idle(sa.r, batch, nout)) return VND_OK;
     const bool epi = ms_encode || use_width;
     const StreamPlan p = make_stream_plan(ctx, t, batch, nout, (int)C, Cx, mode, epi);
     KArgs &a = sa.k;
@@ -522,15 +557,12 @@ vnd_status vnd_stream_f32_host(vnd_ctx *ctx, const vnd_taps *t, void *state, int
     const int64_t nout = *n_out;
     if (batch == 0 || (n_in == 0 && nout == 0)) return VND_OK;
     HostCall call(ctx);
-    const size_t x_bytes = (size_t)(batch * n_in * Cx) * sizeof(float);
-    const size_t y_bytes = (size_t)(batch * nout * t->C) * sizeof(float);
-    call.carve({x_bytes, y_bytes});
-    float *x_dev = call.piece<float>(0), *y_dev = call.piece<float>(1);
-    call.up(x_dev, x, x_bytes, "the chunk");
-    int64_t got = 0;
-    call.run([&] { return vnd_stream_f32_dev(ctx, t, state, state_bytes, max_frames_per_call, x_dev, y_dev, batch, pos, n_in, Cx,
-                                             final_, mode, ms_encode, use_width, width, &got, call.stream()); });
-    call.down(y, y_dev, y_bytes, "y");
+    call.staged(x, (size_t)(batch * n_in * Cx) * sizeof(float), "the chunk", y, (size_t)(batch * nout * t->C) * sizeof(float),
+                nullptr, 0, 0, n_out, [&](void *x_dev, void *y_dev, int32_t *, void *, hipStream_t s) {
+        int64_t got = 0;
+        return vnd_stream_f32_dev(ctx, t, state, state_bytes, max_frames_per_call, (const float *)x_dev, (float *)y_dev, batch, pos,
+                                  n_in, Cx, final_, mode, ms_encode, use_width, width, &got, s);
+    });
     return call.finish("vnd_stream_f32_host");
 }
 
