@@ -21,6 +21,7 @@ from .decorrelation import (  # noqa: F401
     decorrelate_bank,
     decorrelate_each,
     decorrelate_each_stream,
+    decorrelate_voice_pool,
     each_covers,
     generate_velvet_noise,
     set_default_mode,
@@ -35,5 +36,7 @@ from .streaming import (  # noqa: F401
     HaasEachStream,
     HaasStream,
     Stream,
+    VoicePool,
     convolve_velvet_noise_stream,
+    voice_spans,
 )

@@ -281,6 +281,20 @@ EACH_STREAM_SIGNATURES = {
     'vnd_haas_each_stream_f64_host': (ctypes.c_int, _HAAS_EACH_STREAM_ARGS),
 }
 
+# include/vnd_voice_stream.h: a voice pool - the position per slot in the device state, counts and flags per slot and call
+VOICE_START, VOICE_END = 1, 2
+_VOICE_STREAM_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                      ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double]
+VOICE_STREAM_SIGNATURES = {
+    'vnd_voice_stream_state_bytes': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
+                                                    ctypes.POINTER(ctypes.c_int64)]),
+    'vnd_voice_stream_reset_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                  ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    'vnd_voice_stream_f32_dev': (ctypes.c_int, _VOICE_STREAM_ARGS + [ctypes.c_void_p]),
+    'vnd_voice_stream_f32_host': (ctypes.c_int, _VOICE_STREAM_ARGS),
+}
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -332,7 +346,8 @@ def load_library():
                                   + list(CORRELOGRAM_STREAM_SIGNATURES.items())
                                   + list(HAAS_SEARCH_SIGNATURES.items())
                                   + list(VELVET_SEARCH_SIGNATURES.items())
-                                  + list(EACH_SIGNATURES.items()) + list(EACH_STREAM_SIGNATURES.items())):
+                                  + list(EACH_SIGNATURES.items()) + list(EACH_STREAM_SIGNATURES.items())
+                                  + list(VOICE_STREAM_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -1070,6 +1085,68 @@ def each_stream_host(ctx: 'Context', bank: 'TapTable', tables, state_ptr: int, s
     if got != n_out:
         raise NativeError(f'vnd_each_stream_f32_host returned {got} frames, the span is {n_out}')
     return y
+
+
+def voice_stream_state_bytes(bank: 'TapTable', slots: int, channels: int, max_frames_per_call: int) -> int:
+    """``vnd_voice_stream_state_bytes``: one int64 position per slot (padded to 16 bytes), then the ring of a pool of
+    ``slots`` voices at the bank's latency."""
+    need = ctypes.c_int64()
+    _check(load_library().vnd_voice_stream_state_bytes(bank.handle, slots, channels, max_frames_per_call, ctypes.byref(need)),
+           'vnd_voice_stream_state_bytes')
+    return need.value
+
+
+def voice_stream_reset_device(ctx: 'Context', bank: 'TapTable', state_ptr: int, state_bytes: int, slots: int, channels: int,
+                              max_frames_per_call: int, *, stream: int = 0):
+    """``vnd_voice_stream_reset_dev``: every position of the pool to 0, enqueued on ``stream``; the ring is left alone."""
+    _check(ctx._lib.vnd_voice_stream_reset_dev(ctx.handle, ctypes.c_void_p(state_ptr), state_bytes, slots, channels,
+                                               bank.handle, max_frames_per_call, ctypes.c_void_p(stream)),
+           'vnd_voice_stream_reset_dev')
+
+
+def _voice_stream_call(fn, name: str, ctx, bank, state_ptr, state_bytes, max_frames_per_call, x_ptr, counts_ptr, flags_ptr,
+                       tables_ptr, y_ptr, out_counts_ptr, slots, channels, ms_encode, width, mode, *stream):
+    _check(fn(ctx.handle, bank.handle, ctypes.c_void_p(state_ptr), state_bytes, max_frames_per_call, ctypes.c_void_p(x_ptr),
+              ctypes.c_void_p(counts_ptr), ctypes.c_void_p(flags_ptr), ctypes.c_void_p(tables_ptr), ctypes.c_void_p(y_ptr),
+              ctypes.c_void_p(out_counts_ptr), slots, channels, int(mode), int(bool(ms_encode)), int(width is not None),
+              float(width or 0.0), *stream), name)
+
+
+def voice_stream_device(ctx: 'Context', bank: 'TapTable', state_ptr: int, state_bytes: int, max_frames_per_call: int,
+                        x_ptr: int, counts_ptr: int, flags_ptr: int, tables_ptr: int, y_ptr: int, out_counts_ptr: int,
+                        slots: int, channels: int, *, ms_encode: bool, width, mode: int = MODE_EXACT, stream: int = 0):
+    """``vnd_voice_stream_f32_dev``: one call of a voice pool.  float32 ``(slots, M, channels)`` blocks, int32 ``(slots,)``
+    counts, flags (``VOICE_START``, ``VOICE_END``) and table indices, the float32 ``(slots, M + H, 2)`` result and the
+    int32 ``(slots,)`` output counts are device buffers of fixed shape; two kernels enqueued on ``stream``, nothing else."""
+    _voice_stream_call(ctx._lib.vnd_voice_stream_f32_dev, 'vnd_voice_stream_f32_dev', ctx, bank, state_ptr, state_bytes,
+                       max_frames_per_call, x_ptr, counts_ptr, flags_ptr, tables_ptr, y_ptr, out_counts_ptr, slots, channels,
+                       ms_encode, width, mode, ctypes.c_void_p(stream))
+
+
+def voice_stream_host(ctx: 'Context', bank: 'TapTable', state_ptr: int, state_bytes: int, max_frames_per_call: int,
+                      x: np.ndarray, counts, flags, tables, y: np.ndarray, *, ms_encode: bool, width,
+                      mode: int = MODE_EXACT) -> np.ndarray:
+    """``vnd_voice_stream_f32_host``: the same from host arrays (the state stays on the device), synchronous.  ``x`` is a
+    C-contiguous float32 ``(slots, M, 1|2)`` block, ``y`` a C-contiguous float32 ``(slots, M + H, 2)`` array written in
+    place: the first ``out_counts[b]`` frames of row b.  Returns the int32 ``out_counts``."""
+    if x.dtype != np.float32 or not x.flags.c_contiguous or x.ndim != 3 or x.shape[1] != max_frames_per_call:
+        raise ValueError('voice_stream_host wants a C-contiguous float32 (slots, max_frames_per_call, C) block')
+    slots = x.shape[0]
+    if y.dtype != np.float32 or not y.flags.c_contiguous or y.ndim != 3 or y.shape[0] != slots or y.shape[2] != 2:
+        raise ValueError('voice_stream_host wants a C-contiguous float32 (slots, max_frames_per_call + H, 2) result')
+    per_slot = []
+    for name, v in (('count', counts), ('flags value', flags), ('table index', tables)):
+        v = np.ascontiguousarray(v, np.int64)
+        i32 = np.iinfo(np.int32)
+        if v.ndim != 1 or v.size != slots or (v.size and (v.min() < i32.min or v.max() > i32.max)):
+            raise ValueError(f'voice_stream_host wants one int32 {name} per slot: {slots} slots, shape {v.shape}')
+        per_slot.append(v.astype(np.int32))
+    c, f, t = per_slot
+    out_counts = np.zeros(slots, np.int32)
+    _voice_stream_call(ctx._lib.vnd_voice_stream_f32_host, 'vnd_voice_stream_f32_host', ctx, bank, state_ptr, state_bytes,
+                       max_frames_per_call, x.ctypes.data, c.ctypes.data, f.ctypes.data, t.ctypes.data, y.ctypes.data,
+                       out_counts.ctypes.data, slots, x.shape[2], ms_encode, width, mode)
+    return out_counts
 
 
 def haas_each_stream_state_bytes(batch: int, channels: int, max_delay: int, max_frames_per_call: int) -> int:

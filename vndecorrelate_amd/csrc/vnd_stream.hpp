@@ -428,12 +428,15 @@ static StreamPlan make_stream_plan(const vnd_ctx *ctx, const vnd_taps *t, int64_
 }
 
 // The ring side of a call (RingArgs above): which chunk frames go to the ring, and from which slot.  reach = 0 keeps nothing.
-static RingArgs ring_plan(int64_t pos, int64_t n_in, int64_t reach, bool final_, int64_t cap)
+// On the host for the streams whose position the caller holds, on the device for the voice pool (vnd_voice_stream.hpp),
+// whose positions live in the state: one 64-bit modulo per workgroup there.
+static __host__ __device__ inline RingArgs ring_plan(int64_t pos, int64_t n_in, int64_t reach, bool final_, int64_t cap)
 {
     RingArgs r{};
     r.pos = pos; r.n_in = n_in; r.cap = cap;
     // the last `reach` frames of the chunk are what later calls read (none after the final call)
-    r.wr_first = (final_ || reach == 0) ? pos + n_in : std::max<int64_t>(pos, pos + n_in - reach);
+    const int64_t kept = pos + n_in - reach;
+    r.wr_first = (final_ || reach == 0) ? pos + n_in : (kept > pos ? kept : pos);
     r.wr_count = pos + n_in - r.wr_first;
     r.wr_slot0 = cap > 0 ? r.wr_first % cap : 0;
     return r;

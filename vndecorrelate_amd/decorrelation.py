@@ -1300,16 +1300,47 @@ def decorrelate_each(input_signals, decorrelators: Sequence[Decorrelator]):
     return _each_haas(ctx, pool, is_torch, plan[1], plan[2], stats)
 
 
-def _same_across(decorrelators, fields: Sequence[str]) -> None:
+def _same_across(decorrelators, fields: Sequence[str], entry: str = 'decorrelate_each_stream', one: str = 'stream') -> None:
     """``ValueError`` naming the first of ``fields`` that differs across the list: the stage settings are scalars of a
-    call, the same for every stream."""
+    call, the same for every stream (``entry``, ``one``: the words of the message)."""
     for name in fields:
         first = getattr(decorrelators[0], name)
         for b, d in enumerate(decorrelators):
             v = getattr(d, name)
             if not (v is first or (type(v) is type(first) and v == first)):
-                raise ValueError(f'decorrelate_each_stream: {name} differs across the list ({first!r}, and {v!r} for stream '
-                                 f'{b}): the stage settings are the same for every stream of a pool')
+                raise ValueError(f'{entry}: {name} differs across the list ({first!r}, and {v!r} for {one} '
+                                 f'{b}): the stage settings are the same for every {one} of a pool')
+
+
+def _velvet_stream_bank(decorrelators, entry: str, one: str):
+    """What a streamed pool of plain ``VelvetNoise`` checks of its list, and the bank it runs on:
+    ``(bank arrays, tables, ms_encode, width)``, ``tables[b]`` the candidate of ``decorrelators[b]`` in the deduplicated
+    bank.  Every refusal is a ``ValueError`` that starts with ``entry`` or names the ``one`` (stream, bank entry) at fault."""
+    _same_across(decorrelators, ('mode', 'width', 'normalizer'), entry, one)
+    if decorrelators[0].normalizer is not None:
+        raise ValueError('VelvetNoise.stream needs normalizer=None: the RMS normaliser scales by the RMS of the whole '
+                         'input and output signals, which a stream only has once it has ended')
+    for b, d in enumerate(decorrelators):
+        if d.num_outs != 2:
+            raise ValueError(f'{one} {b}: num_outs={d.num_outs}; a bank holds stereo pairs (num_outs == 2)')
+    key = _each_velvet_key(decorrelators[0])
+    if key is None:
+        raise ValueError(f'{entry} covers the LR and MS layouts and a finite Python / float64 width or '
+                         f'None, got mode={decorrelators[0].mode!r}, width={decorrelators[0].width!r}')
+    try:
+        members, tables = each_velvet_members(decorrelators)
+        inside = [_member_in_window(m) for m in members]
+    except (IndexError, TypeError) as exc:
+        raise ValueError(f'{entry}: a tap table cannot be built ({exc})') from exc
+    if not all(inside):
+        b = int(np.flatnonzero(tables == inside.index(False))[0])
+        raise ValueError(f'{one} {b}: its table reaches past {_native.VELVET_PAIRS_MAX_TAP_INDEX} frames or has a gain '
+                         'that is not finite as float32; stream that decorrelator with its own .stream()')
+    if len(members) > _native.VELVET_BANK_MAX_CANDIDATES:
+        raise ValueError(f'{len(members)} distinct tap tables, above {_native.VELVET_BANK_MAX_CANDIDATES} per bank: '
+                         'split the pool')
+    ms_encode, width, _ = key
+    return class_path_bank_arrays(members), tables, ms_encode, width
 
 
 def decorrelate_each_stream(decorrelators: Sequence[Decorrelator], *, in_channels: int = 2, max_frames_per_call: int = 4800):
@@ -1348,31 +1379,8 @@ def decorrelate_each_stream(decorrelators: Sequence[Decorrelator], *, in_channel
     if len(decorrelators) > _native.MAX_STREAMS_PER_CALL:
         raise ValueError(f'{len(decorrelators)} streams, above {_native.MAX_STREAMS_PER_CALL} per pool: split the pool')
     if kind is VelvetNoise:
-        _same_across(decorrelators, ('mode', 'width', 'normalizer'))
-        if decorrelators[0].normalizer is not None:
-            raise ValueError('VelvetNoise.stream needs normalizer=None: the RMS normaliser scales by the RMS of the whole '
-                             'input and output signals, which a stream only has once it has ended')
-        for b, d in enumerate(decorrelators):
-            if d.num_outs != 2:
-                raise ValueError(f'stream {b}: num_outs={d.num_outs}; a bank holds stereo pairs (num_outs == 2)')
-        key = _each_velvet_key(decorrelators[0])
-        if key is None:
-            raise ValueError('decorrelate_each_stream covers the LR and MS layouts and a finite Python / float64 width or '
-                             f'None, got mode={decorrelators[0].mode!r}, width={decorrelators[0].width!r}')
-        try:
-            members, tables = each_velvet_members(decorrelators)
-            inside = [_member_in_window(m) for m in members]
-        except (IndexError, TypeError) as exc:
-            raise ValueError(f'decorrelate_each_stream: a tap table cannot be built ({exc})') from exc
-        if not all(inside):
-            b = int(np.flatnonzero(tables == inside.index(False))[0])
-            raise ValueError(f'stream {b}: its table reaches past {_native.VELVET_PAIRS_MAX_TAP_INDEX} frames or has a gain '
-                             'that is not finite as float32; stream that decorrelator with its own .stream()')
-        if len(members) > _native.VELVET_BANK_MAX_CANDIDATES:
-            raise ValueError(f'{len(members)} distinct tap tables, above {_native.VELVET_BANK_MAX_CANDIDATES} per bank: '
-                             'split the pool')
-        ms_encode, width, _ = key
-        return streaming.EachStream(class_path_bank_arrays(members), tables, in_channels=in_channels,
+        arrays, tables, ms_encode, width = _velvet_stream_bank(decorrelators, 'decorrelate_each_stream', 'stream')
+        return streaming.EachStream(arrays, tables, in_channels=in_channels,
                                     max_frames_per_call=max_frames_per_call, ms_encode=ms_encode, width=width)
     _same_across(decorrelators, ('delayed_channel', 'mode', 'width'))
     key = optimization._haas_key(decorrelators[0])
@@ -1383,6 +1391,36 @@ def decorrelate_each_stream(decorrelators: Sequence[Decorrelator], *, in_channel
     delayed_channel, ms_mode, width = key
     return streaming.HaasEachStream(delays, in_channels=in_channels, max_frames_per_call=max_frames_per_call,
                                     delayed_channel=delayed_channel, ms_mode=ms_mode, width=width)
+
+
+def decorrelate_voice_pool(bank: Sequence[Decorrelator], *, slots: int, in_channels: int = 2, max_frames_per_call: int = 4800):
+    """A ``streaming.VoicePool``: ``slots`` slots over a ``bank`` of plain ``VelvetNoise`` (``normalizer=None``), each
+    slot a voice with a life of its own - it starts on any call with any filter of the bank, brings blocks of any size up
+    to ``max_frames_per_call`` or none, ends on any call, and the slot goes to the next voice.  Where
+    :func:`decorrelate_each_stream` advances a pool in lockstep from a position the host holds, the voice pool keeps one
+    position per slot in the device state (``vnd_voice_stream_f32_*``), so a call is a pure function of device memory and
+    ``process_dev`` can be replayed from a captured graph.
+
+    ``pool.process({slot: block}, start={slot: bank_index}, end=[slot])`` takes float32 NumPy blocks and returns
+    ``{slot: (n_out, 2)}``; ``pool.process_dev(x, counts, flags, tables)`` takes device tensors of fixed shape and only
+    enqueues.  For every voice the concatenation of its outputs equals ``bank[t].decorrelate(x_voice)`` bit for bit.
+    ``latency_frames`` is the bank's largest tap index.  The bank is deduplicated by content
+    (``pool.bank_tables[bank_index]`` is the candidate ``process_dev`` names) and checked as
+    :func:`decorrelate_each_stream` checks its list, with the same exceptions before any device call.  There is no host
+    fallback: a stream has no host loop to fall back to."""
+    from . import streaming
+    bank = list(bank)
+    if not bank:
+        raise ValueError('decorrelate_voice_pool needs at least one decorrelator: a voice starts with a filter of the bank')
+    kinds = {type(d) for d in bank}
+    if kinds != {VelvetNoise}:
+        raise TypeError('decorrelate_voice_pool takes a bank of plain VelvetNoise decorrelators, got '
+                        + ', '.join(sorted(k.__name__ for k in kinds)))
+    if isinstance(in_channels, (bool, np.bool_)) or in_channels not in (1, 2):
+        raise ValueError(f'in_channels must be 1 (mono, fanned out) or 2 (stereo), got {in_channels!r}')
+    arrays, tables, ms_encode, width = _velvet_stream_bank(bank, 'decorrelate_voice_pool', 'bank entry')
+    return streaming.VoicePool(arrays, tables, slots=slots, in_channels=in_channels,
+                               max_frames_per_call=max_frames_per_call, ms_encode=ms_encode, width=width)
 
 
 # ----------------------------------------------------------------------------

@@ -22,7 +22,9 @@ Two more stream forms build on it: :class:`HaasStream` (``HaasEffect(...).stream
 the causal Haas delay with no latency and a tail of ``d`` frames, and :class:`ChainStream` (``SignalChain(...).stream(...)``),
 every stage of a chain on the device, block by block.  :class:`EachStream` and :class:`HaasEachStream`
 (``decorrelate_each_stream``, ``include/vnd_each_stream.h``) run every stream of a pool through its own filter of a bank
-or its own delay, one launch per call for the whole pool.
+or its own delay, one launch per call for the whole pool.  :class:`VoicePool` (``decorrelate_voice_pool``,
+``include/vnd_voice_stream.h``) is that pool with the position of every slot in the device state: voices start, end and
+bring their own block sizes call by call, and ``process_dev`` can be captured in a graph.
 """
 from __future__ import annotations
 
@@ -588,3 +590,249 @@ class ChainStream:
             buf = buf.cpu().numpy()
             self.transfers['to_host'] += 1
         return buf[0] if self._squeeze else buf
+
+
+# ----------------------------------------------------------------------------
+# A voice pool   (include/vnd_voice_stream.h)
+# ----------------------------------------------------------------------------
+VOICE_START, VOICE_END = _native.VOICE_START, _native.VOICE_END
+
+
+def voice_spans(positions, counts, flags, latency: int, max_frames_per_call: Optional[int] = None):
+    """``(out_counts, new_positions)`` of one call of a voice pool (``include/vnd_voice_stream.h``), per slot, from the
+    positions before the call, the frames pushed and the ``VOICE_START`` / ``VOICE_END`` flags alone - what the device
+    computes from its own state::
+
+        p  = START ? 0 : position            E  = max(0, p - H)
+        E' = END ? p + n : max(0, p + n - H)  out_count = E' - E        new position = END ? 0 : p + n
+
+    A count below 0 (or above ``max_frames_per_call``, when given) answers -1 and leaves the position as it was."""
+    pos = np.asarray(positions, np.int64)
+    n = np.asarray(counts, np.int64)
+    f = np.asarray(flags, np.int64)
+    if not (pos.shape == n.shape == f.shape):
+        raise ValueError(f'positions, counts and flags of one shape, got {pos.shape}, {n.shape}, {f.shape}')
+    H = int(latency)
+    start, end = (f & VOICE_START) != 0, (f & VOICE_END) != 0
+    p = np.where(start, 0, pos)
+    first = np.maximum(0, p - H)
+    last = np.where(end, p + n, np.maximum(0, p + n - H))
+    bad = n < 0
+    if max_frames_per_call is not None:
+        bad |= n > int(max_frames_per_call)
+    out = np.where(bad, -1, last - first).astype(np.int64)
+    new = np.where(bad, pos, np.where(end, 0, p + n)).astype(np.int64)
+    return out, new
+
+
+class VoicePool:
+    """``slots`` slots over a bank of velvet-noise filters, each slot a voice with a life of its own
+    (``decorrelation.decorrelate_voice_pool``, ``vnd_voice_stream_f32_*``): voices start and end on any call, bring blocks
+    of any size up to ``max_frames_per_call`` or none, and a slot is handed to a new voice with another filter of the bank
+    without ending the pool.  The stream position lives in the device state, one per slot, so a call is a pure function
+    of device memory.  ``latency_frames`` is the bank's largest tap index, the one latency of the pool.  For every voice
+    the concatenation of what its calls return, from its start up to and including its end, equals
+    ``bank[t].decorrelate(x_voice)`` on the whole signal bit for bit.
+
+    Two forms; a pool is used through one of them (mixing them raises ``RuntimeError`` until ``reset()``: the host mirror
+    of the positions would be stale):
+
+    * ``process({slot: block}, start={slot: bank_index}, end=[slot, ...])`` - float32 NumPy blocks ``(n, in_channels)``
+      in, ``{slot: (n_out, 2) array}`` out for every slot that got a block or ended, synchronously.  Everything is checked
+      before any device call.
+    * ``process_dev(x, counts, flags, tables)`` - the caller's device tensors of fixed shape on the current stream; only
+      enqueues, and can be captured with ``torch.cuda.graph`` (call ``reset()`` before the capture: it allocates the
+      state).  ``tables`` holds candidates of the deduplicated bank: ``bank_tables[bank_index]``."""
+
+    def __init__(self, arrays: TapArrays, bank_tables, *, slots: int, in_channels: int, max_frames_per_call: int,
+                 ms_encode: bool = False, width: Optional[float] = None):
+        _check_counts(slots=slots, in_channels=in_channels, max_frames_per_call=max_frames_per_call)
+        if in_channels not in (1, 2):
+            raise ValueError(f'a pool of mono (1) or stereo (2) voices is taken, got in_channels={in_channels}')
+        if slots > _native.MAX_STREAMS_PER_CALL:
+            raise ValueError(f'slots {slots} above {_native.MAX_STREAMS_PER_CALL}: split the pool')
+        if max_frames_per_call > 1 << 24:
+            raise ValueError(f'max_frames_per_call {max_frames_per_call} above 2**24')
+        if arrays.num_channels < 2 or arrays.num_channels % 2:
+            raise ValueError(f'a bank holds stereo pairs: this one has {arrays.num_channels} channels')
+        self.slots, self.in_channels, self.max_frames_per_call = int(slots), int(in_channels), int(max_frames_per_call)
+        self.arrays, self.num_tables = arrays, arrays.num_channels // 2
+        self.bank_tables = np.ascontiguousarray(bank_tables, np.int32)
+        if self.bank_tables.ndim != 1 or not self.bank_tables.size or self.bank_tables.min() < 0 \
+                or self.bank_tables.max() >= self.num_tables:
+            raise ValueError(f'table indices outside [0, {self.num_tables})')
+        self.ms_encode, self.width, self.mode = bool(ms_encode), width, _native.MODE_EXACT
+        self.latency_frames = int(arrays.tap_index.max()) if len(arrays.tap_index) else 0
+        self.num_channels = 2
+        self._table = None
+        self._state = None                    # (torch uint8 tensor, bytes)
+        self._mirror()
+
+    def _mirror(self):
+        """The host's copy of what the device state says, for the dict form: all slots idle at position 0."""
+        self.positions = np.zeros(self.slots, np.int64)
+        self.live = np.zeros(self.slots, bool)
+        self.tables = np.zeros(self.slots, np.int32)
+        self._form = None
+
+    @property
+    def row_frames(self) -> int:
+        """Frames per row of the result: ``max_frames_per_call + latency_frames``."""
+        return self.max_frames_per_call + self.latency_frames
+
+    # ---- public ------------------------------------------------------------------------
+    def reset(self):
+        """End every voice, unflushed: every position back to 0 (enqueued on the current torch stream; the ring is not
+        cleared, it is never read before it is written), and either form may follow.  Allocates the state on first use."""
+        torch = _native.torch_module()
+        ctx = _native.default_context()
+        if self._state is None:
+            self._allocate(torch, ctx)
+        else:
+            self._reset_device(torch, ctx)
+        self._mirror()
+
+    def process(self, blocks=None, *, start=None, end=(), discard: bool = False):
+        """One call of the dict form.  ``blocks``: ``{slot: float32 (n, in_channels) array}`` (``(n,)`` as well for mono),
+        ``0 <= n <= max_frames_per_call``; ``start``: ``{slot: bank_index}``, the voices that begin with this call;
+        ``end``: the slots whose voice ends with it (its tail comes with this call).  Returns ``{slot: (n_out, 2)}`` for
+        every slot that got a block or ended.  Raises before any device call: ``ValueError`` for a slot outside the pool,
+        a block or an end for a slot that was never started, a start on a live slot (``discard=True`` allows it: what
+        the slot held is dropped, unflushed), a bank index outside the bank, a block above ``max_frames_per_call`` or of
+        another channel count; ``TypeError`` for a block that is not float32."""
+        if self._form == 'dev':
+            raise RuntimeError('this pool runs through process_dev(): the host does not know its positions; reset() first')
+        counts, flags, tables, live, x, answered = self._schedule(blocks, start, end, discard)
+        if not counts.any() and not flags.any():              # nothing pushed, started or ended: no device call
+            return {slot: np.zeros((0, 2), np.float32) for slot in answered}
+        want, positions = voice_spans(self.positions, counts, flags, self.latency_frames, self.max_frames_per_call)
+        y, got = self._call_host(x, counts, flags, tables)
+        if not np.array_equal(np.asarray(got, np.int64), want):
+            raise _native.NativeError(f'the voice pool returned the counts {list(got)}, the spans are {list(want)}')
+        self.positions, self.tables, self._form = positions, tables, 'dict'
+        live[(flags & VOICE_END) != 0] = False
+        self.live = live
+        return {slot: np.array(y[slot, :int(want[slot])]) for slot in answered}
+
+    def process_dev(self, x, counts, flags, tables, *, out=None):
+        """One call on device tensors, enqueued on the current stream: ``x`` float32 ``(slots, M, in_channels)``,
+        ``counts`` / ``flags`` / ``tables`` int32 ``(slots,)``.  Returns ``(y, out_counts)``: float32
+        ``(slots, M + H, 2)`` - the first ``out_counts[b]`` frames of row b are written, nothing at or past them - and
+        int32 ``(slots,)``; ``out=(y, out_counts)`` takes the caller's.  No check reads device memory; bad per-slot
+        values answer as ``include/vnd_voice_stream.h`` says (-1, NaN rows)."""
+        if self._form == 'dict':
+            raise RuntimeError('this pool runs through process(): mixing in process_dev() would leave the host mirror '
+                               'of the positions stale; reset() first')
+        S, M, cx = self.slots, self.max_frames_per_call, self.in_channels
+        y, out_counts = out if out is not None else (None, None)
+        for name, t, shape, dtype in (('x', x, (S, M, cx), 'float32'), ('counts', counts, (S,), 'int32'),
+                                      ('flags', flags, (S,), 'int32'), ('tables', tables, (S,), 'int32'),
+                                      ('y', y, (S, self.row_frames, 2), 'float32'),
+                                      ('out_counts', out_counts, (S,), 'int32')):
+            if t is None and name in ('y', 'out_counts'):
+                continue
+            if not _native.is_torch(t) or not t.is_cuda:
+                raise ValueError(f'{name} must be a device tensor')
+            if tuple(t.shape) != shape or str(t.dtype) != 'torch.' + dtype or not t.is_contiguous():
+                raise ValueError(f'{name} must be a contiguous {dtype} tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}')
+        return self._call_device(_native.torch_module(), x, counts, flags, tables, y, out_counts)
+
+    # ---- checks --------------------------------------------------------------------------
+    def _slot(self, slot, what: str) -> int:
+        if isinstance(slot, (bool, np.bool_)) or not isinstance(slot, (int, np.integer)) or not 0 <= slot < self.slots:
+            raise ValueError(f'{what}: slot {slot!r} is outside the pool of {self.slots} slots')
+        return int(slot)
+
+    def _schedule(self, blocks, start, end, discard: bool):
+        """The call's arrays from the dicts, every refusal included; nothing of the pool is changed."""
+        S, M, cx = self.slots, self.max_frames_per_call, self.in_channels
+        counts, flags = np.zeros(S, np.int32), np.zeros(S, np.int32)
+        tables, live = self.tables.copy(), self.live.copy()
+        for slot, index in dict(start or {}).items():
+            slot = self._slot(slot, 'start')
+            if isinstance(index, (bool, np.bool_)) or not isinstance(index, (int, np.integer)) \
+                    or not 0 <= index < len(self.bank_tables):
+                raise ValueError(f'start: bank index {index!r} of slot {slot} is outside the bank of {len(self.bank_tables)}')
+            if live[slot] and not discard:
+                raise ValueError(f'start: slot {slot} holds a live voice: end it first, or pass discard=True to drop it '
+                                 'unflushed')
+            flags[slot] |= VOICE_START
+            tables[slot] = self.bank_tables[int(index)]
+            live[slot] = True
+        x = np.zeros((S, M, cx), np.float32)
+        answered = set()
+        for slot, block in dict(blocks or {}).items():
+            slot = self._slot(slot, 'block')
+            if not live[slot]:
+                raise ValueError(f'block for slot {slot}, which was never started: name it in start=')
+            a = np.asarray(block)
+            if a.dtype != np.float32:
+                raise TypeError(f'block of slot {slot}: voices push float32 frames, got {a.dtype}')
+            if a.ndim == 1 and cx == 1:
+                a = a[:, None]
+            if a.ndim != 2 or a.shape[1] != cx:
+                raise ValueError(f'block of slot {slot} has shape {tuple(np.shape(block))}: expected (frames, {cx})')
+            if a.shape[0] > M:
+                raise ValueError(f'block of slot {slot}: {a.shape[0]} frames in one call, above max_frames_per_call={M}')
+            counts[slot] = a.shape[0]
+            x[slot, :a.shape[0]] = a
+            answered.add(slot)
+        for slot in list(end):
+            slot = self._slot(slot, 'end')
+            if not live[slot]:
+                raise ValueError(f'end of slot {slot}, which was never started')
+            if flags[slot] & VOICE_END:
+                raise ValueError(f'end: slot {slot} is named twice')
+            flags[slot] |= VOICE_END
+            answered.add(slot)
+        return counts, flags, tables, live, x, sorted(answered)
+
+    # ---- the device -------------------------------------------------------------------------
+    def _allocate(self, torch, ctx):
+        from . import decorrelation
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('the state of a voice pool is allocated and zeroed on first use: call reset() before the capture')
+        self._table = decorrelation._each_banks.get(ctx, self.arrays)
+        need = _native.voice_stream_state_bytes(self._table, self.slots, self.in_channels, self.max_frames_per_call)
+        buf = torch.empty((max(need, 16),), dtype=torch.uint8, device=torch.device('cuda', ctx.device))
+        self._state = (buf, need)
+        self._reset_device(torch, ctx)
+
+    def _reset_device(self, torch, ctx):
+        state, state_bytes = self._state
+        _native.voice_stream_reset_device(ctx, self._table, state.data_ptr(), state_bytes, self.slots, self.in_channels,
+                                          self.max_frames_per_call,
+                                          stream=torch.cuda.current_stream(state.device).cuda_stream)
+
+    def _ensure_state(self, torch, ctx):
+        if self._state is None:
+            self._allocate(torch, ctx)
+        return self._state
+
+    def _call_host(self, x, counts, flags, tables):
+        torch = _native.torch_module()
+        ctx = _native.default_context()
+        state, state_bytes = self._ensure_state(torch, ctx)
+        torch.cuda.current_stream(state.device).synchronize()          # (the reset, or a reset() on this stream)
+        y = np.empty((self.slots, self.row_frames, 2), np.float32)
+        got = _native.voice_stream_host(ctx, self._table, state.data_ptr(), state_bytes, self.max_frames_per_call, x, counts,
+                                        flags, tables, y, ms_encode=self.ms_encode, width=self.width)
+        return y, got
+
+    def _call_device(self, torch, x, counts, flags, tables, y, out_counts):
+        ctx = _native.default_context()
+        device = torch.device('cuda', ctx.device)
+        for t in (x, counts, flags, tables):
+            if t.device != device:
+                raise ValueError(f'tensor on {t.device}, the pool runs on {device}')
+        state, state_bytes = self._ensure_state(torch, ctx)
+        if y is None:
+            y = torch.empty((self.slots, self.row_frames, 2), dtype=torch.float32, device=device)
+        if out_counts is None:
+            out_counts = torch.empty((self.slots,), dtype=torch.int32, device=device)
+        self._form = 'dev'
+        _native.voice_stream_device(ctx, self._table, state.data_ptr(), state_bytes, self.max_frames_per_call, x.data_ptr(),
+                                    counts.data_ptr(), flags.data_ptr(), tables.data_ptr(), y.data_ptr(),
+                                    out_counts.data_ptr(), self.slots, self.in_channels, ms_encode=self.ms_encode,
+                                    width=self.width, stream=torch.cuda.current_stream(device).cuda_stream)
+        return y, out_counts
