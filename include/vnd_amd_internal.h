@@ -85,6 +85,12 @@ vnd_status vnd_describe_stream_launch(vnd_ctx *ctx, const vnd_taps *taps, int64_
 vnd_status vnd_describe_each_stream_launch(vnd_ctx *ctx, const vnd_taps *bank, int64_t max_frames_per_call, int64_t batch,
                                            int64_t position, int64_t n_in, int32_t in_channels, int32_t final,
                                            int32_t mode, int32_t epilogue, char *text, int32_t len);
+/* Diagnosis: the launch every vnd_voice_stream_f32_dev call (include/vnd_voice_stream.h) on a pool with these arguments
+ * takes - the pool's own scalar checks and planner, no pointers, no device work - as one line of key=value fields: r, W,
+ * lds_bytes, tiles (of the longest row, max_frames_per_call + H frames), nblocks (slots x tiles), fma, epilogue, threads,
+ * advance_groups (the workgroups of the kernel that advances the positions, one lane per slot).                          */
+vnd_status vnd_describe_voice_stream_launch(vnd_ctx *ctx, const vnd_taps *bank, int64_t max_frames_per_call, int64_t slots,
+                                            int32_t in_channels, int32_t mode, int32_t epilogue, char *text, int32_t len);
 /* Diagnosis (tests): vnd_decorrelate_fanout_f32_dev (in_channels == the table's channels: vnd_decorrelate_f32_dev), and which of the
  * stage's forms ran, in taken[4]: [0] 0 the table-order launch with the pointwise steps and the sums as passes of their own, 1 the
  * fast kernel with the pointwise steps (and, with VND_NORMALIZE_RMS, the sums) fused into its store phase, 2 the quad / octet kernel

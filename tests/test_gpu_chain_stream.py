@@ -251,7 +251,7 @@ def test_invalid_calls_write_nothing(vnd):
     before = state.cpu().clone()
     chunk = x[:, pos:pos + 40]
     for kw in (dict(n_in=M + 1), dict(bytes_=need.value - 1), dict(batch=65536), dict(channels=3), dict(dch=2),
-               dict(position=-1), dict(n_in=-1), dict(xp=False)):
+               dict(position=-1), dict(position=2 ** 60 + 1), dict(n_in=-1), dict(xp=False)):
         rc, y = call(chunk, False, **kw)
         assert rc == 1, kw
         assert np.all(y == 12345.0), kw

@@ -2,7 +2,8 @@
 many shapes and block schedules, for pools of 1 to 512 streams, in every input form, the concatenated rows equal
 cross_correlogram_batched on the whole signal bit for bit; the reference's fixtures fed block by block stay within the
 bound of DESIGN.md §3.8; reset() leaks nothing; a SignalChain stream can be metered as it runs; an output above 2^31
-floats; argument checks that write nothing."""
+floats; a stream planted at a position a long-lived one reaches (2^31 .. 2^60), by the ring layout the header documents;
+argument checks that write nothing."""
 import ctypes
 import json
 import pathlib
@@ -307,6 +308,53 @@ def test_output_above_2_to_31_floats(torch, an, dev):
     assert bits_equal(head.cpu().numpy(), one_shot(an, x[:, :n0], y[:, :n0], W, H, L))
 
 
+PLANTED = (2 ** 31 - 7, 2 ** 32 - 300, 2 ** 40 + 3, None)        # None: 2^60 less the frames pushed
+
+
+@pytest.mark.parametrize('position', PLANTED, ids=['2^31-7', '2^32-300', '2^40+3', 'ends-at-2^60'])
+def test_planted_position(torch, an, dev, position):
+    """A stream at position P has wc(P) windows behind it; window wc(P) starts at frame A = wc(P) x hop, in (P - W, P].
+    The signal starts at A: its frames below P go into the ring (slot = absolute frame mod (W - 1 + M)), the rest is
+    pushed, and the rows are the one-shot call's on the signal.  The ring frames [P - W + 1, A) are within reach of P but
+    belong to no window still to complete: they hold loud noise, everything else NaN, and no row may show either."""
+    from vndecorrelate_amd import _native
+    ctx = _native.default_context()
+    S, W, H, L, M, n = 3, 320, 160, 641, 333, 1500
+    P = 2 ** 60 - n if position is None else position
+    w0 = (P - W) // H + 1
+    A = w0 * H
+    held, cap = P - A, W - 1 + M
+    assert 0 < held < W - 1                                                    # there are frames of both kinds
+    x, y = signal(S, held + n, 17 + P % 107)
+    want = one_shot(an, x, y, W, H, L)
+    need = _native.correlogram_stream_state_bytes(S, W, M)
+    assert need == S * cap * 8
+    state = torch.full((need // 4,), float('nan'), dtype=torch.float32, device=dev)
+    history = np.random.default_rng(P % 109).uniform(-1e3, 1e3, (S, W - 1, 2)).astype(np.float32)
+    history[:, W - 1 - held:, 0], history[:, W - 1 - held:, 1] = x[:, :held], y[:, :held]
+    where = np.array([(P - (W - 1) + j) % cap for j in range(W - 1)], np.int64)  # Python integers: no wrap
+    state.view(S, cap, 2)[:, torch.from_numpy(where).to(dev)] = torch.from_numpy(history).to(dev)
+    xd, yd = torch.from_numpy(x).to(dev), torch.from_numpy(y).to(dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    outs, pos = [], P
+    for b in schedule('random', n, W, H, M, P % 113) + [0]:                    # the last call, of no frames, at P + n
+        rows = ((pos + b - W) // H + 1) - ((pos - W) // H + 1)
+        out = torch.full((S * rows * L + 64,), float('nan'), dtype=torch.float32, device=dev)
+        first = held + pos - P
+        xb, yb = xd[:, first:first + b].contiguous(), yd[:, first:first + b].contiguous()
+        got = _native.correlogram_stream_device(ctx, state.data_ptr(), need, M, xb.data_ptr(), yb.data_ptr(), max(b, 1), 1,
+                                                out.data_ptr(), S, pos, b, window=W, hop=H, num_lags=L, eps=EPS, stream=stream)
+        assert got == rows, (pos, b)
+        oh = out.cpu().numpy()
+        assert np.isnan(oh[S * rows * L:]).all() and not np.isnan(oh[:S * rows * L]).any(), (pos, b)
+        outs.append(oh[:S * rows * L].reshape(S, rows, L))
+        pos += b
+    assert pos == P + n and (position is not None or pos == 2 ** 60)
+    got = np.concatenate(outs, axis=1)
+    assert got.shape == want.shape and want.shape[1] == (held + n - W) // H + 1
+    assert bits_equal(got, want), np.argwhere(got.view(np.int32) != want.view(np.int32))[:3]
+
+
 def test_bad_arguments_write_nothing(torch, an, dev):
     from vndecorrelate_amd import _native
     ctx = _native.default_context()
@@ -328,7 +376,8 @@ def test_bad_arguments_write_nothing(torch, an, dev):
             a['W'], a['H'], a['L'], EPS, ctypes.byref(rows), ctypes.c_void_p(0))
         return rc, rows.value
 
-    invalid = [dict(state_bytes=need - 1), dict(n_in=M + 1), dict(n_in=-1), dict(pos=-1), dict(M=0), dict(batch=0),
+    invalid = [dict(state_bytes=need - 1), dict(n_in=M + 1), dict(n_in=-1), dict(pos=-1), dict(pos=2 ** 60 + 1), dict(M=0),
+               dict(batch=0),
                dict(ss=0), dict(fs=0), dict(W=0), dict(H=0), dict(L=0), dict(H=-3), dict(state=0), dict(x=0), dict(y=0),
                dict(out=0), dict(out=x.data_ptr()), dict(out=state.data_ptr()), dict(x=state.data_ptr()),
                dict(ss=2 ** 62)]

@@ -6,7 +6,11 @@ as NaN, every call's output starts as a NaN no arithmetic produces and ends in a
 each call *n_out is streaming.output_span's at the BANK's latency, every output frame was written and the tail was not.
 The concatenated outputs of stream b equal the C oracle on the whole signal with that stream's own table, then
 encode_side and apply_stereo_width (O.decorrelate's order).  Each case names the tile (r) the planner must report
-(vnd_describe_each_stream_launch); the pools that reach r = 2 and r = 4 are sized from the device's CU count."""
+(vnd_describe_each_stream_launch); the pools that reach r = 2 and r = 4 are sized from the device's CU count.
+
+The planted-position cases start a stream at a position a long-lived one reaches (2^31 .. 2^60) without pushing that
+many frames: the header documents the ring - slot = absolute frame mod capacity - so the frames below the position are
+written there by that rule and everything else stays NaN."""
 import contextlib
 import ctypes
 import io
@@ -28,6 +32,10 @@ THREADS = 16                 # C-oracle threads
 SIZES = (1, 200, 511, 512, 513, 2049, 5000)               # 200: shorter than H
 KAPPAS = (0.0, 0.3, 0.55, 0.3, 0.8, 1.0)                  # streams 1 and 3 share a kappa: 5 tables serve 6 streams
 INVALID, UNSUPPORTED = 1, 4
+MAX_POSITION = 1 << 60       # the largest position every block stream takes
+# 2^31 - 7: the first block crosses 2^31; 2^32 - 300: pos - reach and pos straddle 2^32; None: 2^60 less the frames pushed
+PLANTED = (2 ** 31 - 7, 2 ** 32 - 300, 2 ** 40 + 3, None)
+PLANTED_IDS = ['2^31-7', '2^32-300', '2^40+3', 'ends-at-2^60']
 
 
 @pytest.fixture(scope='module')
@@ -104,6 +112,21 @@ class Bank:
         return want
 
 
+def _function_bank(ctx):
+    """A bank whose weights are not +-1 (a function-path table: the gains folded into the weights), 3 candidates."""
+    from vndecorrelate_amd.taps import function_path_arrays
+    fir = O.generate_velvet_noise(duration_seconds=DURATION, num_impulses=IMPULSES, num_outs=6, sample_rate_hz=FS,
+                                  segment_envelope=(1.0, 0.5, 0.25), log_distribution_strength=0.6, seed=3)
+    bank = Bank(ctx, function_path_arrays(fir), [function_path_arrays(fir[:, 2 * c:2 * c + 2]) for c in range(3)])
+    bank.fir = fir
+    return bank
+
+
+def _ring_slots(position, reach, cap):
+    """The ring slots of the absolute frames [position - reach, position): Python integers, so nothing wraps."""
+    return np.array([(position - reach + j) % cap for j in range(reach)], np.int64)
+
+
 class Poisoned:
     """One pool's state (NaN-filled once, at construction) and the calls of vnd_each_stream_f32_dev on it."""
 
@@ -144,12 +167,20 @@ class Poisoned:
             ctypes.byref(got), ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
         return rc, got.value, y.cpu().numpy(), end - first
 
-    def signal(self, x, calls):
-        """x (S, n, cx); calls [(n_in, final)], the last one final: the concatenation of every call's outputs."""
+    def plant(self, position, history):
+        """The H frames below `position` of every stream, (S, H, cx), into the ring slots the header names."""
+        H, cap = self.bank.H, self.bank.H + self.M
+        assert history.shape == (self.S, H, self.cx) and history.dtype == np.float32
+        where = self.torch.from_numpy(_ring_slots(position, H, cap)).to(self.dev)
+        self.state.view(self.S, cap, self.cx)[:, where] = self.torch.from_numpy(history).to(self.dev)
+
+    def signal(self, x, calls, start=0):
+        """x (S, n, cx); calls [(n_in, final)], the last one final: the concatenation of every call's outputs.  The
+        first frame of x is absolute frame `start`."""
         xd = self.torch.from_numpy(np.ascontiguousarray(x)).to(self.dev)
-        outs, pos = [], 0
+        outs, pos = [], start
         for i, (n_in, final) in enumerate(calls):
-            chunk = xd[:, pos:pos + n_in].contiguous()
+            chunk = xd[:, pos - start:pos - start + n_in].contiguous()
             rc, got, yh, n_out = self.call(chunk, pos, n_in, final)
             assert rc == 0, self.ctx._lib.vnd_last_error()
             assert got == n_out, (i, got, n_out)
@@ -164,7 +195,7 @@ class Poisoned:
                 self.plans.append((n_out, plan))
             outs.append(yh[:body].view(np.float32).reshape(self.S, n_out, 2))
             pos += n_in
-        assert pos == x.shape[1] and calls[-1][1]
+        assert pos - start == x.shape[1] and calls[-1][1]
         return np.concatenate(outs, axis=1)
 
 
@@ -244,10 +275,8 @@ def test_frames_in_every_schedule(ctx, cx, envelope, filtered, epi):
 def test_function_path_bank_takes_the_exact_instantiation(ctx, cx):
     """A bank whose weights are not +-1 (a function-path table: the gains folded into the weights) runs the separate
     multiply and add; the plan says so."""
-    from vndecorrelate_amd.taps import function_path_arrays
-    fir = O.generate_velvet_noise(duration_seconds=DURATION, num_impulses=IMPULSES, num_outs=6, sample_rate_hz=FS,
-                                  segment_envelope=(1.0, 0.5, 0.25), log_distribution_strength=0.6, seed=3)
-    bank = Bank(ctx, function_path_arrays(fir), [function_path_arrays(fir[:, 2 * c:2 * c + 2]) for c in range(3)])
+    bank = _function_bank(ctx)
+    fir = bank.fir
     try:
         tables = np.array([2, 0, 1, 2], np.int32)
         for n, epi in ((513, (True, 0.35)), (2049, (False, None))):
@@ -265,28 +294,61 @@ def test_function_path_bank_takes_the_exact_instantiation(ctx, cx):
 
 
 # ---- 2. every tile ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('r', [1, 2, 4])
-def test_every_tile(ctx, r):
+def _tile_cases():
+    """each_stream_kernel<cx, MODE, r, EPI> in its 24 forms; the three cases that were here first keep their names."""
+    cases = []
+    for r, cx, path, epi in itertools.product((1, 2, 4), (2, 1), ('class', 'function'), ((True, 0.35), (False, None))):
+        first = (cx, path, epi) == (2, 'class', (True, 0.35))
+        cases.append(pytest.param(r, cx, path, epi, id=str(r) if first else f'{r}-cx{cx}-{path}-{"epi" if epi[0] else "plain"}'))
+    return cases
+
+
+@pytest.mark.parametrize('r, cx, path, epi', _tile_cases())
+def test_every_tile(ctx, r, cx, path, epi):
     """The planner's rule, the largest tile that still leaves every CU six workgroups: a call of 2100 output frames is
-    2 tiles at r = 4, 3 at r = 2 and 5 at r = 1, so pools of 3, 2 and (a few) x CU count streams reach each."""
+    2 tiles at r = 4, 3 at r = 2 and 5 at r = 1, so pools of 3, 2 and (a few) x CU count streams reach each.  The
+    class-path bank's +-1 weights take the fma instantiation, the function-path bank's the separate multiply and add."""
     cus = ctx.info()['compute_units']
     S = {4: 3 * cus, 2: 2 * cus, 1: 7}[r]
-    bank = Bank.of_members(ctx, _members(O.DEFAULT_ENVELOPE, (0,)))
+    bank = Bank.of_members(ctx, _members(O.DEFAULT_ENVELOPE, (0,))) if path == 'class' else _function_bank(ctx)
     try:
         H = bank.H
         first, last = H + 2100, 700                      # a call of 2100 outputs that fills the ring, then the final block
-        tables = (np.arange(S) % 5).astype(np.int32)
-        epi = (True, 0.35)
-        x = _noise((S, first + last, 2), 77 + r)
-        want = bank.reference(x, tables, 2, epi)
-        p = Poisoned(bank, tables, 2, first, epi)
+        tables = (np.arange(S) % len(bank.alone)).astype(np.int32)
+        x = _noise((S, first + last, cx), 77 + r)
+        want = bank.reference(x, tables, cx, epi)
+        p = Poisoned(bank, tables, cx, first, epi)
         got = p.signal(x, [(first, False), (last, True)])
         assert [n_out for n_out, _ in p.plans] == [2100, last + H]
         assert p.plans[0][1]['r'] == r, p.plans
         assert p.plans[0][1]['tiles'] == {4: 2, 2: 3, 1: 5}[r]
+        assert p.plans[0][1]['fma'] == int(path == 'class') and p.plans[0][1]['epilogue'] == int(epi[0])
         _same(got, want, ('tile', r))
         # a tile the call does not fill past half is never taken, however many streams there are
         assert p.describe(first, 480, False)['r'] == 1 and p.describe(first, 512, False)['r'] == 1
+    finally:
+        bank.close()
+
+
+# ---- 2b. a stream that has been running for a day --------------------------------------------------------------------
+@pytest.mark.parametrize('position', PLANTED, ids=PLANTED_IDS)
+def test_planted_position(ctx, position):
+    """The tap sum reads x[n .. n + H]: with the H frames below P in the ring, the outputs from frame P - H on are the
+    oracle's on the signal that starts there, whole."""
+    bank = Bank.of_members(ctx, _members(O.DEFAULT_ENVELOPE, (0,)))
+    try:
+        H, M, cx, epi = bank.H, 480, 2, (True, 0.35)
+        n = 1700
+        start = MAX_POSITION - n if position is None else position
+        sig = _noise((6, H + n, cx), 90 + start % 97)
+        rng = np.random.default_rng(start % 1009)
+        sizes = [int(b) for b in rng.permutation([0, 1, 17, H, H + 1, M, M])]
+        sizes.append(n - sum(sizes))
+        assert 0 < sizes[-1] <= M
+        p = Poisoned(bank, TABLES, cx, M, epi)
+        p.plant(start, sig[:, :H])
+        got = p.signal(sig[:, H:], _calls(sizes, 'flush' if position is None else 'final'), start=start)
+        _same(got, bank.reference(sig, TABLES, cx, epi), ('planted at', start))
     finally:
         bank.close()
 
@@ -488,7 +550,8 @@ def test_an_invalid_call_leaves_output_and_ring_untouched(ctx):
                                      (dict(n_in=M, state_bytes=p.state_bytes - 4), INVALID, b'the stream needs'),
                                      (dict(n_in=M, mode=1), UNSUPPORTED, b'VND_MODE_EXACT only'),
                                      (dict(n_in=M, mode=2), UNSUPPORTED, b'VND_MODE_EXACT only'),
-                                     (dict(n_in=M, pos=-1), INVALID, b'position')):
+                                     (dict(n_in=M, pos=-1), INVALID, b'position'),
+                                     (dict(n_in=M, pos=MAX_POSITION + 1), INVALID, b'position')):
             n_in = kwargs.pop('n_in')
             pos = kwargs.pop('pos', 0)
             rc, got, yh, n_out = p.call(chunk[:, :n_in].contiguous(), pos, n_in, True, **kwargs)
@@ -518,18 +581,25 @@ class PoisonedHaas:
         self.state = torch.full((max(self.state_bytes // 4, 1),), float('nan'), dtype=torch.float32, device=self.dev)
         self.frames = torch.from_numpy(self.delays).to(self.dev)
 
-    def signal(self, x, calls):
+    def plant(self, position, history):
+        """The max_delay frames below `position` of every stream, (S, max_delay, cx), into the ring slots the header names."""
+        D, cap = self.max_delay, self.max_delay + self.M
+        assert history.shape == (self.S, D, self.cx) and history.dtype == np.float32
+        where = self.torch.from_numpy(_ring_slots(position, D, cap)).to(self.dev)
+        self.state.view(self.S, cap, self.cx)[:, where] = self.torch.from_numpy(history).to(self.dev)
+
+    def signal(self, x, calls, start=0):
         torch = self.torch
         xd = torch.from_numpy(np.ascontiguousarray(x)).to(self.dev)
         poison = np.array([0x7FF4A5A5A5A5A5A5], np.int64)[0]
         sentinel = np.array([0x7FF5B0B0B0B0B0B0], np.int64)[0]
-        outs, pos = [], 0
+        outs, pos = [], start
         for i, (n_in, final) in enumerate(calls):
             n_out = n_in + (self.max_delay if final else 0)
             body = self.S * n_out * 2
             y = torch.full((body + 512,), int(sentinel), dtype=torch.int64, device=self.dev)
             y[:body] = int(poison)
-            chunk = xd[:, pos:pos + n_in].contiguous()
+            chunk = xd[:, pos - start:pos - start + n_in].contiguous()
             got = self.native.haas_each_stream_device(
                 self.ctx, self.state.data_ptr(), self.state_bytes, self.M, chunk.data_ptr(), y.data_ptr(), self.S, pos, n_in,
                 self.cx, self.frames.data_ptr(), final=final, max_delay=self.max_delay,
@@ -540,19 +610,20 @@ class PoisonedHaas:
             assert not (yh[:body] == poison).any(), f'call {i} left frames unwritten'
             outs.append(yh[:body].view(np.float64).reshape(self.S, n_out, 2))
             pos += n_in
-        assert pos == x.shape[1] and calls[-1][1]
+        assert pos - start == x.shape[1] and calls[-1][1]
         return np.concatenate(outs, axis=1)
 
 
-def _check_haas(dec, got, x, delays, cx, settings):
+def _check_haas(dec, got, x, delays, cx, settings, skip=0):
+    """`got` against HaasEffect.decorrelate of x, from x's frame `skip` on (a stream that started there)."""
     n = x.shape[1]
     for b, d in enumerate(delays):
         stage = dec.HaasEffect(sample_rate_hz=1, delay_time_seconds=float(d), delayed_channel=settings['delayed_channel'],
                                mode='MS' if settings['ms_mode'] else 'LR', width=settings['width'])
         want = stage.decorrelate(x[b, :, 0] if cx == 1 else x[b])
         assert want.shape == (n + d, 2) and want.dtype == np.float64
-        assert got[b, :n + d].tobytes() == want.tobytes(), (b, d)
-        assert not got[b, n + d:].view(np.int64).any(), (b, d)                   # +0.0, bit for bit
+        assert got[b, :n + d - skip].tobytes() == want[skip:].tobytes(), (b, d)
+        assert not got[b, n + d - skip:].view(np.int64).any(), (b, d)            # +0.0, bit for bit
 
 
 @pytest.mark.parametrize('cx', [1, 2])
@@ -575,6 +646,36 @@ def test_haas_rows_are_numpys(dec, ctx, cx, ms_mode, delayed_channel, width):
     # no delay anywhere: no state
     none = PoisonedHaas(ctx, [0, 0], 0, cx, 256, settings)
     _check_haas(dec, none.signal(x[:2], _calls(_blocks(n, 256), 'flush')), x[:2], [0, 0], cx, settings)
+
+
+@pytest.mark.parametrize('position', PLANTED, ids=PLANTED_IDS)
+def test_haas_planted_position(dec, ctx, position):
+    """A delay reads x[f - d]: with the max_delay frames below P in the ring, the outputs from P on are NumPy's on the
+    signal that starts at P - max_delay, from its frame max_delay on."""
+    M, D, cx = 256, 300, 2
+    delays = [0, 1, 255, 256, 257, D]
+    settings = dict(delayed_channel=1, ms_mode=True, width=0.3)
+    n = 700
+    start = MAX_POSITION - n if position is None else position
+    sig = _noise((len(delays), D + n, cx), 31 + start % 89)
+    rng = np.random.default_rng(start % 1013)
+    sizes = [int(b) for b in rng.permutation([0, 1, 17, M, M])]
+    sizes.append(n - sum(sizes))
+    assert 0 < sizes[-1] <= M
+    p = PoisonedHaas(ctx, delays, D, cx, M, settings)
+    p.plant(start, sig[:, :D])
+    got = p.signal(sig[:, D:], _calls(sizes, 'flush' if position is None else 'final'), start=start)
+    assert got.shape == (len(delays), n + D, 2)
+    _check_haas(dec, got, sig, delays, cx, settings, skip=D)
+    # one frame further the position is out of range: refused, and the ring keeps its bits
+    before = p.state.clone()
+    y = p.torch.full((len(delays) * M * 2,), 7.0, dtype=p.torch.float64, device=p.dev)
+    chunk = p.torch.zeros((len(delays), M, cx), dtype=p.torch.float32, device=p.dev)
+    with pytest.raises(ValueError, match='position'):
+        p.native.haas_each_stream_device(ctx, p.state.data_ptr(), p.state_bytes, M, chunk.data_ptr(), y.data_ptr(), len(delays),
+                                         MAX_POSITION + 1, M, cx, p.frames.data_ptr(), final=False, max_delay=D, **settings)
+    p.torch.cuda.synchronize(p.dev)
+    assert bool((y == 7.0).all()) and p.state.view(p.torch.int32).equal(before.view(p.torch.int32))
 
 
 def test_a_bad_delay_is_nan_for_that_stream_alone(dec, ctx):

@@ -228,6 +228,8 @@ def test_invalid_calls_write_nothing(vnd):
     assert call(481, need.value) == 1                 # n_in > max_frames_per_call
     assert call(480, need.value - 4) == 1             # state too short
     assert call(480, need.value, pos=-1) == 1         # negative position
+    assert call(480, need.value, pos=2 ** 60 + 1) == 1 and b'position' in lib.vnd_last_error()     # above the last one taken
+    assert n_out.value == 0
     torch.cuda.synchronize(dev)
     assert bool((y == 5.0).all()) and bool((state == 7.0).all())
     assert call(480, need.value) == 0 and n_out.value == 480    # the same call, valid: it runs

@@ -9,7 +9,8 @@ modes; the fast mode is within the one-shot fuzz's bar and bit-identical from ru
 whole signal in one final call; random ones with 0- and 1-frame calls, calls that only fill the ring, calls of H, H + 1
 and max_frames_per_call frames, ending with a flush or with a final block; then a second, shorter signal on the same
 state, whose ring still holds the first one's frames.  The Haas stream (include/vnd_haas_stream.h) goes through the same
-harness at the end."""
+harness at the end.  The planted-position cases start a stream at a position a long-lived one reaches (2^31 .. 2^60): the
+frames below it go into the ring by the header's rule, slot = absolute frame mod capacity, and the rest stays NaN."""
 import collections
 import ctypes
 
@@ -32,6 +33,10 @@ SENTINEL = 0x7FB0B0B0        # the tail behind n_out
 TAIL = 2048                  # frames of sentinel per call: one tile at r = 4
 THREADS = 16                 # C-oracle threads
 EPI = (True, 0.35)           # ms_encode plus width, for the stereo cases
+MAX_POSITION = 1 << 60       # the largest position a call takes
+# 2^31 - 7: the first block crosses 2^31; 2^32 - 300: pos - reach and pos straddle 2^32; None: 2^60 less the frames pushed
+PLANTED = (2 ** 31 - 7, 2 ** 32 - 300, 2 ** 40 + 3, None)
+PLANTED_IDS = ['2^31-7', '2^32-300', '2^40+3', 'ends-at-2^60']
 PLANS = collections.defaultdict(set)      # mode -> every distinct plan the file reached (printed at the end, -s)
 
 
@@ -131,19 +136,28 @@ class Poisoned:
         self.state = torch.full((max(need.value // 4, 1),), float('nan'), dtype=torch.float32, device=self.dev)
         self.plans = []
 
-    def signal(self, x, calls):
-        """x (S, n, cx); calls [(n_in, final)], the last one final: the concatenation of every call's outputs."""
+    def plant(self, position, history):
+        """The H frames below `position` of every stream, (S, H, cx), into the ring slots the header names."""
+        H, cap = self.H, self.H + self.M
+        assert history.shape == (self.S, H, self.cx) and history.dtype == np.float32 and H > 0
+        where = np.array([(position - H + j) % cap for j in range(H)], np.int64)         # Python integers: no wrap
+        ring = self.state.view(self.S, cap, self.cx)
+        ring[:, self.torch.from_numpy(where).to(self.dev)] = self.torch.from_numpy(history).to(self.dev)
+
+    def signal(self, x, calls, start=0):
+        """x (S, n, cx); calls [(n_in, final)], the last one final: the concatenation of every call's outputs.  The
+        first frame of x is absolute frame `start`."""
         from vndecorrelate_amd.streaming import output_span
         torch = self.torch
         S, C = self.S, self.C
         xd = torch.from_numpy(np.ascontiguousarray(x)).to(self.dev)
         stream = torch.cuda.current_stream(self.dev)
         epi = self.ms or self.width is not None
-        outs, pos = [], 0
+        outs, pos = [], start
         for i, (n_in, final) in enumerate(calls):
             first, end = output_span(pos, n_in, self.H, final)
             n_out = end - first
-            chunk = xd[:, pos:pos + n_in].contiguous()
+            chunk = xd[:, pos - start:pos - start + n_in].contiguous()
             body = S * n_out * C
             y = torch.full((body + TAIL * C,), SENTINEL, dtype=torch.int32, device=self.dev)
             y[:body] = POISON
@@ -165,7 +179,7 @@ class Poisoned:
             assert not len(hole), f'call {i} (pos {pos}, n_in {n_in}) left (stream, frame, channel) {tuple(hole[0])} unwritten'
             outs.append(yh[:body].view(np.float32).reshape(S, n_out, C))
             pos += n_in
-        assert pos == x.shape[1] and calls[-1][1]
+        assert pos - start == x.shape[1] and calls[-1][1]
         return np.concatenate(outs, axis=1)
 
 
@@ -383,6 +397,31 @@ def test_stream_plan_matrix(ctx, make, S, cx, n, M, mode, epi, want, reach_r):
         assert all(p['W'] == 2 * 256 * p['r'] + 16 for _, p in plans)
 
 
+# ---- a stream that has been running for a day -------------------------------------------------------------------------
+@pytest.mark.parametrize('position', PLANTED, ids=PLANTED_IDS)
+@pytest.mark.parametrize('mode', MODES)
+@pytest.mark.parametrize('kernel', ['conv_stream', 'conv_stream_direct'])
+def test_planted_position(ctx, kernel, mode, position):
+    """The tap sum reads x[n .. n + H]: with the H frames below P in the ring, the outputs from frame P - H on are the
+    oracle's on the signal that starts there, whole - bit for bit in the exact and fma modes; the fast mode's even / odd
+    chains follow E = P - H, so it is held to the file's bar for that mode."""
+    H, M, n = (T30, 700, 2900) if kernel == 'conv_stream' else (48000, 3000, 7000)
+    arr = _random_table(2, H, 30, 21)
+    S, cx = 2, 2
+    start = MAX_POSITION - n if position is None else position
+    table = _table(ctx, arr)
+    try:
+        sig = _signal(S, H + n, cx, 500 + mode + start % 101)
+        sizes = _sizes(n, H, M, np.random.default_rng(start % 1021))
+        p = Poisoned(ctx, table, arr, S, cx, M, mode, EPI)
+        p.plant(start, sig[:, :H])
+        got = p.signal(sig[:, H:], _calls(sizes, 'flush' if position is None else 'final'), start=start)
+        assert p.plans and all(plan['kernel'] == kernel for _, plan in p.plans), p.plans
+        _compare(got, arr, sig, cx, mode, EPI, ('planted at', start))
+    finally:
+        table.close()
+
+
 def test_band_is_where_the_issue_puts_it(ctx):
     """The fallback band starts where one stereo plane pair stops fitting: about 19.8 k frames with 160 KiB of LDS."""
     lo = _band_index(ctx, EXACT)
@@ -460,7 +499,7 @@ SENTINEL64 = 0x7FF5B0B0B0B0B0B0
 FS = 48000
 
 
-def _haas_signal(ctx, state, state_bytes, M, x, calls, d, dc, ms, width):
+def _haas_signal(ctx, state, state_bytes, M, x, calls, d, dc, ms, width, start=0):
     import torch
     from vndecorrelate_amd import _native
     from vndecorrelate_amd.streaming import haas_output_span
@@ -469,11 +508,11 @@ def _haas_signal(ctx, state, state_bytes, M, x, calls, d, dc, ms, width):
     S, n, cx = x.shape
     xd = torch.from_numpy(np.ascontiguousarray(x)).to(dev)
     stream = torch.cuda.current_stream(dev)
-    outs, pos = [], 0
+    outs, pos = [], start
     for i, (n_in, final) in enumerate(calls):
         first, end = haas_output_span(pos, n_in, d, final)
         n_out = end - first
-        chunk = xd[:, pos:pos + n_in].contiguous()
+        chunk = xd[:, pos - start:pos - start + n_in].contiguous()
         body = S * n_out * 2
         y = torch.full((body + TAIL * 2,), SENTINEL64, dtype=torch.int64, device=dev)
         y[:body] = POISON64
@@ -489,7 +528,7 @@ def _haas_signal(ctx, state, state_bytes, M, x, calls, d, dc, ms, width):
         assert not (yh[:body] == POISON64).any(), f'call {i} (pos {pos}) left frames unwritten'
         outs.append(yh[:body].view(np.float64).reshape(S, n_out, 2))
         pos += n_in
-    assert pos == n and calls[-1][1]
+    assert pos - start == n and calls[-1][1]
     return np.concatenate(outs, axis=1)
 
 
@@ -522,3 +561,40 @@ def test_haas_stream_poisoned(ctx, cx, d, dc, mode, width):
         got = _haas_signal(ctx, state, need.value, M, x, _calls(sizes, ending), d, dc, ms, width)
         assert got.shape == (S, n + d, 2)
         assert np.array_equal(got, want(x)), (n, ending, _first_diff(got, want(x)))
+
+
+@pytest.mark.parametrize('position', PLANTED, ids=PLANTED_IDS)
+def test_haas_stream_planted_position(ctx, position):
+    """A delay reads x[f - d]: with the d frames below P in the ring (slot = absolute frame mod (d + M)), the outputs
+    from P on are the reference's on the signal that starts at P - d, from its frame d on."""
+    import torch
+    from vndecorrelate_amd import _native
+    M, S, cx, d, dc, mode, width = 480, 3, 2, 481, 1, 'MS', 0.6
+    n = 1500
+    start = MAX_POSITION - n if position is None else position
+    lib = _native.load_library()
+    need = ctypes.c_int64()
+    assert lib.vnd_haas_stream_state_bytes(S, cx, d, M, ctypes.byref(need)) == 0 and need.value == S * (d + M) * cx * 4
+    dev = torch.device('cuda', ctx.device)
+    state = torch.full((need.value // 4,), float('nan'), dtype=torch.float32, device=dev)
+    sig = _signal(S, d + n, cx, 700 + start % 103)
+    where = np.array([(start - d + j) % (d + M) for j in range(d)], np.int64)
+    state.view(S, d + M, cx)[:, torch.from_numpy(where).to(dev)] = torch.from_numpy(sig[:, :d]).to(dev)
+    sizes = [int(b) for b in _sizes(n, d, M, np.random.default_rng(start % 1031))]
+    got = _haas_signal(ctx, state, need.value, M, sig[:, d:], _calls(sizes, 'flush' if position is None else 'final'),
+                       d, dc, True, width, start=start)
+    want = np.stack([O.haas_effect(sig[b], sample_rate_hz=FS, delay_time_seconds=d / FS, delayed_channel=dc, mode=mode,
+                                   width=width) for b in range(S)])
+    assert want.shape == (S, d + n + d, 2) and got.shape == (S, n + d, 2)
+    assert np.array_equal(got, want[:, d:]), _first_diff(got, want[:, d:])
+    # one frame further the position is out of range: refused, nothing written
+    before = state.clone()
+    y = torch.full((S, M, 2), 7.0, dtype=torch.float64, device=dev)
+    chunk = torch.zeros((S, M, cx), dtype=torch.float32, device=dev)
+    rows = ctypes.c_int64(-1)
+    rc = lib.vnd_haas_stream_f64_dev(ctx.handle, ctypes.c_void_p(state.data_ptr()), need.value, M, ctypes.c_void_p(chunk.data_ptr()),
+                                     ctypes.c_void_p(y.data_ptr()), S, MAX_POSITION + 1, M, cx, 0, d, dc, 1, 1, width,
+                                     ctypes.byref(rows), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    assert rc == 1 and b'position' in lib.vnd_last_error() and rows.value == 0
+    torch.cuda.synchronize(dev)
+    assert bool((y == 7.0).all()) and state.view(torch.int32).equal(before.view(torch.int32))

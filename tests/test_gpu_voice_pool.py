@@ -8,14 +8,20 @@ counts[b], y is prefilled with a NaN no arithmetic produces and ends in a sentin
 streaming.voice_spans', every frame below out_counts[b] was written, every frame at or past it was not, and the tail is
 intact.  The filter is that file's small one (16 kHz, 0.02 s, 15 taps, H <= 319, 5 tables); S = 6 and M = 600, so a row
 of M + H frames spans two 512-frame tiles.  A voice's concatenated outputs equal the C oracle on its whole signal with
-its own table alone, then encode_side and apply_stereo_width (O.decorrelate's order)."""
+its own table alone, then encode_side and apply_stereo_width (O.decorrelate's order).
+
+test_every_form runs all 24 voice_stream_kernel instantiations on pools of M = 2100 frames sized from the CU count, past
+one advance group, each naming its plan through vnd_describe_voice_stream_launch.  The planted-position tests put a slot
+at a position a long-lived voice reaches (2^31 .. 2^60) by the state layout the header documents - the int64 positions
+first, then the ring, slot = absolute frame mod capacity - without pushing that many frames."""
 import ctypes
 
 import numpy as np
 import pytest
 
 from oracle import vnd_oracle as O
-from test_gpu_each_stream import KAPPAS, POISON, SENTINEL, TABLES, Bank, Poisoned, _members, _noise, _same, _velvets
+from test_gpu_each_stream import (KAPPAS, POISON, SENTINEL, TABLES, Bank, Poisoned, _function_bank, _members, _noise, _same,
+                                  _velvets)
 
 pytestmark = pytest.mark.gpu
 
@@ -24,6 +30,8 @@ TAIL = 1024                  # int32 words of sentinel behind the last row
 START, END = 1, 2
 INVALID, UNSUPPORTED = 1, 4
 NAN_BITS = 0x7FC00000        # the ring's and the positions' first contents
+BIG_M = 2100                 # test_every_form: a steady-state call is 2 tiles at r = 4, 3 at r = 2 and 5 at r = 1
+MAX_POSITION = 1 << 60       # the largest position a call accepts (include/vnd_voice_stream.h)
 
 
 @pytest.fixture(scope='module')
@@ -51,15 +59,43 @@ def dec(ctx):
     decorrelation.set_device_epilogue(None)
 
 
+@pytest.fixture(scope='module')
+def function_bank(ctx):
+    """test_gpu_each_stream.py's function-path bank: 3 tables whose weights carry the gains, so not +-1."""
+    b = _function_bank(ctx)
+    assert 200 < b.H <= 319
+    yield b
+    b.close()
+
+
 _REFERENCES = {}
+
+
+def _reference_key(bank, x, table, cx, epi):
+    return (id(bank), x.tobytes(), int(table), cx, epi)
 
 
 def _reference(bank, x, table, cx, epi):
     """One voice alone through its table by the C oracle: computed once per signal and form."""
-    key = (x.tobytes(), int(table), cx, epi)
+    key = _reference_key(bank, x, table, cx, epi)
     if key not in _REFERENCES:
         _REFERENCES[key] = bank.reference(x[None], np.array([table], np.int32), cx, epi)[0]
     return _REFERENCES[key]
+
+
+def _batch_references(bank, plan, cx, epi):
+    """_reference for every voice of a large plan, one oracle call per (table, length); returns the keys it filled."""
+    groups = {}
+    for voices in plan.values():
+        for v in voices:
+            groups.setdefault((v.table, len(v.x)), []).append(v)
+    keys = []
+    for (table, _), voices in groups.items():
+        want = bank.reference(np.stack([v.x for v in voices]), np.full(len(voices), table, np.int32), cx, epi)
+        for v, w in zip(voices, want):
+            keys.append(_reference_key(bank, v.x, table, cx, epi))
+            _REFERENCES[keys[-1]] = w.copy()
+    return keys
 
 
 class Harness:
@@ -95,7 +131,24 @@ class Harness:
         return self.state.view(self.torch.int32).cpu().numpy()
 
     def positions(self):
-        return self.state_words()[:self.S * 2].view(np.int64).copy()
+        return self.state[:self.pos_bytes // 4].view(self.torch.int64).cpu().numpy()[:self.S].copy()
+
+    def ring(self):
+        """The ring as int32 words, (S, H + M, cx)."""
+        return self.state_words()[self.pos_bytes // 4:].reshape(self.S, self.H + self.M, self.cx)
+
+    def plant(self, slot, position, history):
+        """Put `slot` at `position` as the header lays the state out: the int64 position, and the H frames below it -
+        `history`, absolute frames [position - H, position) - each in ring slot (absolute frame mod capacity).  Every
+        other word of the slot's ring stays NaN."""
+        torch, H, cap = self.torch, self.H, self.H + self.M
+        assert history.shape == (H, self.cx) and history.dtype == np.float32
+        ring = self.state[self.pos_bytes // 4:].view(self.S, cap, self.cx)
+        where = np.array([(position - H + j) % cap for j in range(H)], np.int64)        # Python integers: no wrap
+        ring[slot, torch.from_numpy(where).to(self.dev)] = torch.from_numpy(history).to(self.dev)
+        self.state[:self.pos_bytes // 4].view(torch.int64)[slot] = position
+        self.mirror[slot] = position
+        assert int(self.positions()[slot]) == position
 
     def raw(self, blocks, counts, flags, tables, override=None):
         """One call on poisoned buffers: (status, out_counts, y as int32 (S, M + H, 2)); the tail is checked here."""
@@ -130,6 +183,7 @@ class Harness:
         assert rc == 0, self.lib.vnd_last_error()
         want, self.mirror = voice_spans(self.mirror, counts, flags, self.H, self.M)
         assert oc.tolist() == want.tolist(), (where, counts, flags)
+        assert self.positions().tolist() == self.mirror.tolist(), f'{where}: the positions on the device are not the mirror\'s'
         rows = []
         for b, n in enumerate(np.maximum(want, 0)):
             hole = np.argwhere(yh[b, :n] == POISON)
@@ -257,25 +311,200 @@ def test_edge_calls(bank):
 
 
 # ---- 2. lockstep -----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('cx', [1, 2])
-def test_lockstep_equals_each_stream_call_by_call(bank, cx):
+@pytest.mark.parametrize('cx, r', [pytest.param(1, None, id='1'), pytest.param(2, None, id='2'),
+                                   pytest.param(2, 2, id='2-r2'), pytest.param(2, 4, id='2-r4')])
+def test_lockstep_equals_each_stream_call_by_call(ctx, bank, cx, r):
+    """r None: the file's 6 slots.  r = 2, 4: test_every_form's pools, whose voice kernel takes that tile on every call
+    whatever tile the lockstep sibling takes for the call's own frames."""
     epi = (True, 0.35)
-    sizes = [600, 0, 37, 263, 600, 1]
-    x = _noise((S, sum(sizes), cx), 11 + cx)
-    lock = Poisoned(bank, TABLES, cx, M, epi)
-    h = Harness(bank, cx, epi)
+    if r is None:
+        slots, max_frames, sizes = S, M, [600, 0, 37, 263, 600, 1]
+        tables = TABLES
+    else:
+        slots, max_frames, sizes = _pool_slots(ctx, r), BIG_M, [BIG_M, 0, 700, BIG_M]
+        tables = (np.arange(slots) % 5).astype(np.int32)
+    x = _noise((slots, sum(sizes), cx), 11 + cx + (r or 0))
+    lock = Poisoned(bank, tables, cx, max_frames, epi)
+    h = Harness(bank, cx, epi, slots, max_frames)
+    if r is not None:
+        assert _voice_plan(bank, max_frames, slots, cx, epi)['r'] == r
     xd = h.torch.from_numpy(x).to(h.dev)
     pos = 0
     for i, n in enumerate(sizes):
         final = i == len(sizes) - 1
         rc, got, yh, n_out = lock.call(xd[:, pos:pos + n].contiguous(), pos, n, final)
         assert rc == 0 and got == n_out
-        want = yh[:S * n_out * 2].reshape(S, n_out, 2)
-        flags = np.full(S, (START if i == 0 else 0) | (END if final else 0), np.int32)
-        rows = h.call({b: x[b, pos:pos + n] for b in range(S)}, np.full(S, n, np.int32), flags, TABLES, f'call {i}')
-        for b in range(S):
+        want = yh[:slots * n_out * 2].reshape(slots, n_out, 2)
+        flags = np.full(slots, (START if i == 0 else 0) | (END if final else 0), np.int32)
+        rows = h.call({b: x[b, pos:pos + n] for b in range(slots)}, np.full(slots, n, np.int32), flags, tables, f'call {i}')
+        for b in range(slots):
             assert rows[b].view(np.int32).tobytes() == want[b].tobytes(), (i, b)
         pos += n
+    assert not h.positions().any()
+
+
+# ---- 2b. every instantiation, on pools past one advance group --------------------------------------------------------
+def _pool_slots(ctx, r):
+    """make_each_stream_plan takes the largest tile that leaves every CU six workgroups: a call of BIG_M frames is 2
+    tiles at r = 4 and 3 at r = 2.  The one slot more leaves a last advance group of 256 lanes with one live lane."""
+    cus = ctx.info()['compute_units']
+    return {4: 3 * cus + 1, 2: 2 * cus + 1, 1: 7}[r]
+
+
+def _voice_plan(bank, max_frames, slots, cx, epi):
+    head, *fields = bank.table.describe_voice_stream(max_frames, slots, cx, 0, epi[0] or epi[1] is not None).split()
+    assert head == 'voice_stream'
+    return {k: int(v) for k, v in (f.split('=') for f in fields)}
+
+
+def _pool_plan(slots, cx, H, T, seed):
+    """({slot: [Voice, ...]}, the slots never started).  The first seven slots hold every length the kernel can go wrong
+    at - 1, below H, 511, 513, M, M + H + 1, 3 M - a slot reused after END by a voice with another table, an END alone
+    with n = 0, a voice discarded by a START without END, and a slot that never starts; the slots after them draw from
+    the same cases: a tenth reused, a few END alone, a few discarded, some never started, the rest one voice."""
+    rng = np.random.default_rng(seed)
+    sig = lambda n, k: _noise((n, cx), 100003 * seed + k)
+    lengths = (1, 150, 511, 513, BIG_M, BIG_M + H + 1, 3 * BIG_M)
+    assert 150 < H
+    plan = {0: [Voice(sig(1, 0), 0, 0, whole=True), Voice(sig(BIG_M + H + 1, 1), 1, 2, end_with_last=False)],
+            1: [Voice(sig(150, 2), 1, 1, end_with_last=False)],
+            2: [Voice(sig(511, 3), 2, 0)],
+            3: [Voice(sig(513, 4), 0, 2)],
+            4: [Voice(sig(BIG_M, 5), 1, 1, discard_after=900), Voice(sig(3 * BIG_M, 6), 2, 0)],
+            5: [Voice(sig(BIG_M, 7), T - 1, 3)]}
+    never = [6]
+    for slot in range(7, slots):
+        u, k = rng.random(), 10 + 2 * slot
+        short = int(rng.choice(lengths[:6]))                           # two voices in a slot: neither is the longest
+        n = lengths[6] if rng.random() < 0.05 else short               # (the longest sets the number of calls: a few)
+        table, start = int(rng.integers(T)), int(rng.integers(0, 4))
+        if u < 0.08:
+            never.append(slot)
+        elif u < 0.18:                                                 # reused after END, by another table
+            plan[slot] = [Voice(sig(short, k), table, start % 2, end_with_last=bool(rng.random() < 0.5)),
+                          Voice(sig(int(rng.choice(lengths[:6])), k + 1), (table + 1) % T, 0)]
+        elif u < 0.22:                                                 # discarded by the START of the next voice
+            first = max(short, 511)
+            plan[slot] = [Voice(sig(first, k), table, start % 2, discard_after=int(rng.integers(1, first))),
+                          Voice(sig(int(rng.choice(lengths[:6])), k + 1), (table + 1) % T, 0)]
+        elif u < 0.27:                                                 # END alone, with n = 0
+            plan[slot] = [Voice(sig(n, k), table, start, end_with_last=False)]
+        else:
+            plan[slot] = [Voice(sig(n, k), table, 0 if n == lengths[-1] else start)]
+    return plan, never
+
+
+@pytest.mark.parametrize('epi', [(False, None), (True, 0.35)], ids=['plain', 'ms_encode-width'])
+@pytest.mark.parametrize('r', [1, 2, 4])
+@pytest.mark.parametrize('path', ['class', 'function'])
+@pytest.mark.parametrize('cx', [1, 2])
+def test_every_form(ctx, bank, function_bank, cx, path, r, epi):
+    """voice_stream_kernel<cx, MODE, r, EPI> for every cx, MODE (1: the class-path bank's +-1 weights, 0: the function-path
+    bank's), r and EPI, the plan named by the hook before anything runs; 3 x CUs + 1 slots reach r = 4, 2 x CUs + 1
+    reach r = 2 (four and three advance groups on 256 CUs, the last with one live lane), 7 slots plan r = 1.
+    (With H <= 319 a row of M + H frames has as many tiles as a call of M frames at every r: the workgroups past a
+    slot's n_out are those of the calls that push less than M.)"""
+    bk = bank if path == 'class' else function_bank
+    slots, T = _pool_slots(ctx, r), len(bk.alone)
+    plan_text = _voice_plan(bk, BIG_M, slots, cx, epi)
+    want = dict(r=r, fma=int(path == 'class'), epilogue=int(epi != (False, None)), tiles=-(-(BIG_M + bk.H) // (512 * r)),
+                nblocks=slots * -(-(BIG_M + bk.H) // (512 * r)), advance_groups=-(-slots // 256))
+    assert {k: plan_text[k] for k in want} == want, plan_text
+    assert r == 1 or want['advance_groups'] >= 3
+    plan, never = _pool_plan(slots, cx, bk.H, T, 1000 * cx + 10 * r + (path == 'class'))
+    keys = _batch_references(bk, plan, cx, epi)
+    try:
+        h = Harness(bk, cx, epi, slots, BIG_M)
+        calls = _drive(h, plan, np.random.default_rng(3 + cx + r))     # every call: out_counts, footprint, positions
+        assert calls >= 8, calls
+        print(f'{calls} calls, {slots} slots, {sum(len(v) for v in plan.values())} voices')
+        _check_voices(bk, plan, cx, epi)
+        assert not h.positions().any() and not h.mirror.any()         # every voice ended
+        assert (h.ring()[never] == NAN_BITS).all(), 'a slot that never started has frames in its ring'
+    finally:
+        for key in keys:
+            _REFERENCES.pop(key, None)
+
+
+# ---- 2c. positions a long-lived voice reaches ------------------------------------------------------------------------
+PLANTED = (2 ** 31 - 7,        # the first block crosses 2^31
+           2 ** 32 - 300,      # p - H and p straddle 2^32 inside one staged window
+           2 ** 32 + 12345, 2 ** 40 + 3,
+           2 ** 53 + 1,        # no float64 holds it: a detour through doubles shows
+           None)               # 2^60 less the frames the slot pushes: its last call, an END alone, is at 2^60 exactly
+
+
+@pytest.mark.parametrize('cx, epi', [(2, (True, 0.35)), (1, (True, 0.35))], ids=['ms_encode-width', 'mono-in'])
+def test_planted_positions(bank, cx, epi):
+    """No START anywhere: every slot goes on from the position and the H frames of history planted in its state.  The
+    tap sum reads x[n .. n + H], so the outputs from frame P - H on are the oracle's on the signal that starts there."""
+    h = Harness(bank, cx, epi)
+    H = bank.H
+    rng = np.random.default_rng(50 + cx)
+    pushed = [int(n) for n in rng.integers(900, 1900, S)]
+    sigs = [_noise((H + n, cx), 300 + 10 * cx + b) for b, n in enumerate(pushed)]
+    start = [MAX_POSITION - pushed[b] if P is None else P for b, P in enumerate(PLANTED)]
+    for b in range(S):
+        h.plant(b, start[b], sigs[b][:H])
+    assert h.mirror.tolist() == start
+    done, ended, outs = [0] * S, [False] * S, [[] for _ in range(S)]
+    call = 0
+    while not all(ended):
+        assert call < 40
+        blocks, counts, flags = {}, np.zeros(S, np.int32), np.zeros(S, np.int32)
+        for b in range(S):
+            if ended[b]:
+                continue
+            left = pushed[b] - done[b]
+            n = min(left, 0 if rng.random() < 0.3 else int(rng.integers(1, M + 1)))
+            if PLANTED[b] is None and left == 0:                       # the position is 2^60: the largest one taken
+                assert int(h.mirror[b]) == MAX_POSITION
+                flags[b], ended[b] = END, True
+            elif n == left and PLANTED[b] is not None and left:
+                flags[b], ended[b] = END, True                         # END on the last block
+            if n:
+                blocks[b] = sigs[b][H + done[b]:H + done[b] + n]
+            counts[b] = n
+            done[b] += n
+        rows = h.call(blocks, counts, flags, TABLES, f'call {call}')   # out_counts and positions against the mirror
+        for b in range(S):
+            outs[b].append(rows[b])
+        call += 1
+    assert call > 3 and not h.positions().any()
+    for b in range(S):
+        _same(np.concatenate(outs[b]), _reference(bank, sigs[b], TABLES[b], cx, epi), ('planted at', start[b]))
+
+
+def test_a_position_above_the_range_leaves_the_slot_alone(bank):
+    cx, epi = 2, (True, 0.35)
+    h = Harness(bank, cx, epi)
+    H = bank.H
+    x = _noise((S, 1000, cx), 8)
+    blocks = lambda first, n: {b: x[b, first:first + n] for b in range(S)}
+    h.call(blocks(0, 400), np.full(S, 400, np.int32), np.full(S, START, np.int32), TABLES, 'call 0')
+    # slot 3's position becomes 2^60 + 1 (its ring keeps the frames of call 0): without START the slot is refused
+    h.state[:h.pos_bytes // 4].view(h.torch.int64)[3] = MAX_POSITION + 1
+    before = h.state_words().copy()
+    rc, oc, yh = h.raw(blocks(400, 600), np.full(S, 600, np.int32), np.full(S, END, np.int32), TABLES)
+    assert rc == 0, h.lib.vnd_last_error()
+    assert oc[3] == -1 and (yh[3] == POISON).all()
+    assert int(h.positions()[3]) == MAX_POSITION + 1
+    assert h.ring()[3].tobytes() == before[h.pos_bytes // 4:].reshape(S, -1)[3].tobytes()
+    for b in (0, 1, 2, 4, 5):                                          # the neighbours end as if nothing had happened
+        assert oc[b] == 1000 - max(0, 400 - H) and (yh[b, oc[b]:] == POISON).all()
+        want = _reference(bank, x[b], TABLES[b], cx, epi)
+        _same(yh[b, :oc[b]].view(np.float32), want[max(0, 400 - H):], ('beside a bad position', b))
+    # the mirror answers the same -1, and the slot works again with START
+    from vndecorrelate_amd.streaming import voice_spans
+    h.mirror[:] = 0
+    h.mirror[3] = MAX_POSITION + 1
+    counts, flags = np.zeros(S, np.int32), np.zeros(S, np.int32)
+    counts[3] = 500
+    out, new = voice_spans(h.mirror, counts, flags, H, M)
+    assert out[3] == -1 and new[3] == MAX_POSITION + 1
+    flags[3] = START | END
+    rows = h.call({3: x[3, :500]}, counts, flags, TABLES, 'restarted')
+    _same(rows[3], _reference(bank, x[3, :500], TABLES[3], cx, epi), 'START over a bad position')
     assert not h.positions().any()
 
 

@@ -90,6 +90,31 @@ def test_output_counts_over_random_schedules(seed):
         assert output_span(0, n, latency, False) == (0, 0)
 
 
+@pytest.mark.parametrize('position', [2 ** 31 - 7, 2 ** 31, 2 ** 32 - 300, 2 ** 32, 2 ** 40 + 3, 2 ** 53 + 1, 2 ** 60 - 480, 2 ** 60])
+def test_output_span_at_the_positions_of_a_long_lived_stream(position):
+    """The span arithmetic around 2^31 and 2^32 and up to the last position a call takes, 2^60: exact integers, and one
+    call's end is the next call's start."""
+    from vndecorrelate_amd.streaming import haas_output_span, output_span
+    H = 1439
+    expect_first, pos, total = position - H, position, 0
+    blocks = [0, 1, H, H + 1, 480] if position < 2 ** 60 - 480 else ([480] if position < 2 ** 60 else [])
+    for b in blocks + [None]:
+        final = b is None
+        first, end = output_span(pos, 0 if final else b, H, final)
+        assert isinstance(first, int) and isinstance(end, int)
+        assert first == expect_first == pos - H and end == (pos if final else pos + b - H)
+        total += end - first
+        expect_first = end
+        pos += 0 if final else b
+    assert pos <= 2 ** 60 and total == sum(blocks) + H                # every frame pushed, and the H held before them
+    # a steady-state block returns as many frames as it was given, a Haas block too
+    assert output_span(position, 480, H, False) == (position - H, position + 480 - H)
+    first, end = haas_output_span(position, 480, 700, False)
+    assert end - first == 480
+    first, end = haas_output_span(position, 0, 700, True)
+    assert end - first == 700
+
+
 def test_errors_without_a_device():
     import vndecorrelate_amd.decorrelation as d
     from vndecorrelate_amd.streaming import convolve_velvet_noise_stream

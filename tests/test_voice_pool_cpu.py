@@ -125,6 +125,33 @@ def test_voice_spans_edge_rows():
         voice_spans([0, 0], [1], [0], H)
 
 
+def test_voice_spans_at_the_positions_of_a_long_lived_voice():
+    """Around 2^31, 2^32 and at the last position taken, 2^60, against Python's own integers; 2^60 + 1 is refused unless
+    the call STARTs over it."""
+    from vndecorrelate_amd.streaming import output_span, voice_spans
+    H, M = 300, 480
+    top = 1 << 60
+    positions = [2 ** 31 - 7, 2 ** 31, 2 ** 32 - 300, 2 ** 32 - 1, 2 ** 32, 2 ** 32 + 12345, 2 ** 40 + 3, 2 ** 53 + 1,
+                 top - M, top - 1, top]
+    for n, f in ((0, 0), (7, 0), (M, 0), (0, END), (M, END), (301, START), (M, START | END)):
+        out, new = voice_spans(positions, [n] * len(positions), [f] * len(positions), H, M)
+        assert out.dtype == new.dtype == np.int64
+        for p, got, after in zip(positions, out.tolist(), new.tolist()):
+            at = 0 if f & START else p
+            first, end = output_span(at, n, H, bool(f & END))
+            assert (got, after) == (end - first, 0 if f & END else at + n), (p, n, f)
+    # a steady-state call returns what it was given; an END returns the tail too - at any of these positions
+    out, new = voice_spans(positions, [M] * len(positions), [0] * len(positions), H, M)
+    assert out.tolist() == [M] * len(positions) and (new - np.array(positions) == M).all()
+    assert new[-1] == top + M                                          # the next call of that slot is the refused one
+    # outside [0, 2^60] without START: -1 and the position stays; START discards it like any other position
+    bad = [top + 1, top + M, 2 ** 62, -1, -2 ** 63]
+    out, new = voice_spans(bad, [7] * 5, [0, END, 0, 0, END], H, M)
+    assert out.tolist() == [-1] * 5 and new.tolist() == bad
+    out, new = voice_spans(bad, [7] * 5, [START, START | END, START, START, START], H, M)
+    assert out.tolist() == [0, 7, 0, 0, 0] and new.tolist() == [7, 0, 7, 7, 7]
+
+
 # ---- VoicePool over a fake native ------------------------------------------------------------------------------------
 class _FakeNative:
     """Stands for the device under a real pool: records what every call uploads and answers with the spans of a
@@ -306,6 +333,12 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
     assert (_native.VOICE_START, _native.VOICE_END) == (START, END)
     for wrapper in ('voice_stream_state_bytes', 'voice_stream_reset_device', 'voice_stream_device', 'voice_stream_host'):
         assert callable(getattr(_native, wrapper))
+    # the planner's description: declared beside the each-stream's, exported and bound
+    internal = _declared(REPO / 'include' / 'vnd_amd_internal.h')
+    assert 'vnd_describe_voice_stream_launch' in internal and 'vnd_describe_each_stream_launch' in internal
+    assert hasattr(lib, 'vnd_describe_voice_stream_launch')
+    assert 'vnd_describe_voice_stream_launch' in _native.INTERNAL_SIGNATURES
+    assert callable(_native.TapTable.describe_voice_stream)
 
 
 def test_checks_that_need_no_device(lib):
@@ -319,3 +352,8 @@ def test_checks_that_need_no_device(lib):
     got = ctypes.c_int64(-7)
     assert lib.vnd_voice_stream_state_bytes(null, 4, 2, 480, ctypes.byref(got)) == INVALID
     assert b'null tap table' in lib.vnd_last_error()
+    text = ctypes.create_string_buffer(64)
+    assert lib.vnd_describe_voice_stream_launch(null, null, 480, 4, 2, 0, 0, text, 64) == INVALID
+    assert b'null context' in lib.vnd_last_error() and not text.value
+    assert lib.vnd_describe_voice_stream_launch(null, null, 480, 4, 2, 0, 0, None, 64) == INVALID
+    assert b'null text' in lib.vnd_last_error()

@@ -144,6 +144,9 @@ INTERNAL_SIGNATURES = {
     'vnd_describe_each_stream_launch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                                        ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                                        ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32]),
+    'vnd_describe_voice_stream_launch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                        ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p,
+                                                        ctypes.c_int32]),
     'vnd_debug_decorrelate_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                      ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                                      ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
@@ -729,6 +732,16 @@ class TapTable:
         _check(self._lib.vnd_describe_each_stream_launch(self.ctx.handle, self.handle, max_frames_per_call, batch, position,
                                                          n_in, in_channels, int(bool(final)), int(mode),
                                                          int(bool(epilogue)), buf, 512), 'vnd_describe_each_stream_launch')
+        return buf.value.decode()
+
+    def describe_voice_stream(self, max_frames_per_call: int, slots: int, in_channels: int, mode: int = MODE_EXACT,
+                              epilogue: bool = False) -> str:
+        """The launch of every ``vnd_voice_stream_f32_dev`` call on a pool of ``slots`` voices over this bank
+        (``vnd_describe_voice_stream_launch``): ``r=``, ``tiles=``, ``nblocks=``, ``advance_groups=`` among its fields."""
+        buf = ctypes.create_string_buffer(512)
+        _check(self._lib.vnd_describe_voice_stream_launch(self.ctx.handle, self.handle, max_frames_per_call, slots, in_channels,
+                                                          int(mode), int(bool(epilogue)), buf, 512),
+               'vnd_describe_voice_stream_launch')
         return buf.value.decode()
 
     def read_stamps(self, batch: int, n: int, channels: int, mode: int = MODE_EXACT) -> np.ndarray:

@@ -261,4 +261,21 @@ vnd_status vnd_describe_each_stream_launch(vnd_ctx *ctx, const vnd_taps *t, int6
     return VND_OK;
 }
 
+// The plan of a vnd_voice_stream_f32_dev call on a pool with these arguments: the pool's scalar checks and
+// make_voice_stream_plan, the launch's own; advance_groups = the grid of voice_advance_kernel.  No pointers, no device work.
+vnd_status vnd_describe_voice_stream_launch(vnd_ctx *ctx, const vnd_taps *t, int64_t max_frames_per_call, int64_t slots,
+                                            int32_t in_channels, int32_t mode, int32_t epilogue, char *text, int32_t len)
+{
+    if (!text || len <= 0) return fail(VND_ERR_INVALID, "null text buffer");
+    int64_t need = 0;
+    vnd_status st = voice_stream_scalars(ctx, t, max_frames_per_call, slots, in_channels, mode, &need);
+    if (st != VND_OK) return st;
+    if ((st = voice_stream_rows(t, max_frames_per_call, slots)) != VND_OK) return st;
+    const EachStreamPlan p = make_voice_stream_plan(ctx, t, slots, max_frames_per_call, in_channels, epilogue != 0);
+    snprintf(text, (size_t)len, "voice_stream r=%d W=%d lds_bytes=%zu tiles=%d nblocks=%u fma=%d epilogue=%d threads=%d advance_groups=%lld",
+             p.r, p.W, p.lds_bytes, p.tiles, p.nblocks, p.fma ? 1 : 0, p.epi ? 1 : 0, kVpThreads,
+             (long long)((slots + kVoiceAdvanceThreads - 1) / kVoiceAdvanceThreads));
+    return VND_OK;
+}
+
 }  // extern "C"

@@ -174,9 +174,9 @@ vnd_status vnd_voice_stream_state_bytes(const vnd_taps *t, int64_t slots, int32_
     return VND_OK;
 }
 
-// What the three entries check of the pool: scalars, the bank, the state.  Nothing is written.
-static vnd_status voice_stream_pool(const vnd_ctx *ctx, const vnd_taps *t, const void *state, int64_t state_bytes,
-                                    int64_t max_frames_per_call, int64_t slots, int32_t Cx, int32_t mode)
+// The scalar side of the pool's checks, in the order the entries report them; *need = the bytes of its state.
+static vnd_status voice_stream_scalars(const vnd_ctx *ctx, const vnd_taps *t, int64_t max_frames_per_call, int64_t slots,
+                                       int32_t Cx, int32_t mode, int64_t *need)
 {
     if (!ctx || !t) return fail(VND_ERR_INVALID, "null context or tap table");
     if (slots < 0) return fail(VND_ERR_INVALID, "negative slots");
@@ -186,8 +186,22 @@ static vnd_status voice_stream_pool(const vnd_ctx *ctx, const vnd_taps *t, const
     if (max_frames_per_call < 0 || max_frames_per_call > ((int64_t)1 << 40))
         return fail(VND_ERR_INVALID, "max_frames_per_call %lld out of range", (long long)max_frames_per_call);
     if ((st = each_bank_limits(t, slots, mode, "voice", "slots", "stream it filter by filter")) != VND_OK) return st;
+    return vnd_voice_stream_state_bytes(t, slots, Cx, max_frames_per_call, need);
+}
+
+static vnd_status voice_stream_rows(const vnd_taps *t, int64_t max_frames_per_call, int64_t slots)
+{
+    if (slots * (max_frames_per_call + t->max_index) * 2 > ((int64_t)1 << 40)) return fail(VND_ERR_UNSUPPORTED, "problem too large");
+    return VND_OK;
+}
+
+// What the three entries check of the pool: scalars, the bank, the state.  Nothing is written.
+static vnd_status voice_stream_pool(const vnd_ctx *ctx, const vnd_taps *t, const void *state, int64_t state_bytes,
+                                    int64_t max_frames_per_call, int64_t slots, int32_t Cx, int32_t mode)
+{
     int64_t need = 0;
-    if ((st = vnd_voice_stream_state_bytes(t, slots, Cx, max_frames_per_call, &need)) != VND_OK) return st;
+    vnd_status st = voice_stream_scalars(ctx, t, max_frames_per_call, slots, Cx, mode, &need);
+    if (st != VND_OK) return st;
     if (state_bytes < need)
         return fail(VND_ERR_INVALID, "state of %lld bytes, the voice pool needs %lld", (long long)state_bytes, (long long)need);
     if (slots > 0 && !state) return fail(VND_ERR_INVALID, "null state pointer");
@@ -216,8 +230,7 @@ static vnd_status voice_stream_check(const vnd_ctx *ctx, const vnd_taps *t, cons
     if (st != VND_OK) return st;
     if (slots > 0 && (!counts || !flags || !tables || !out_counts || !y || (max_frames_per_call > 0 && !x)))
         return fail(VND_ERR_INVALID, "null chunk, counts, flags, table index, output or out_counts pointer");
-    if (slots * (max_frames_per_call + t->max_index) * 2 > ((int64_t)1 << 40)) return fail(VND_ERR_UNSUPPORTED, "problem too large");
-    return VND_OK;
+    return voice_stream_rows(t, max_frames_per_call, slots);
 }
 
 vnd_status vnd_voice_stream_f32_dev(vnd_ctx *ctx, const vnd_taps *t, void *state, int64_t state_bytes,

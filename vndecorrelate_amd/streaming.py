@@ -596,6 +596,7 @@ class ChainStream:
 # A voice pool   (include/vnd_voice_stream.h)
 # ----------------------------------------------------------------------------
 VOICE_START, VOICE_END = _native.VOICE_START, _native.VOICE_END
+VOICE_MAX_POSITION = 1 << 60            # the largest position a call goes on from
 
 
 def voice_spans(positions, counts, flags, latency: int, max_frames_per_call: Optional[int] = None):
@@ -606,7 +607,8 @@ def voice_spans(positions, counts, flags, latency: int, max_frames_per_call: Opt
         p  = START ? 0 : position            E  = max(0, p - H)
         E' = END ? p + n : max(0, p + n - H)  out_count = E' - E        new position = END ? 0 : p + n
 
-    A count below 0 (or above ``max_frames_per_call``, when given) answers -1 and leaves the position as it was."""
+    A count below 0 (or above ``max_frames_per_call``, when given), or without START a position outside ``[0, 2^60]``,
+    answers -1 and leaves the position as it was."""
     pos = np.asarray(positions, np.int64)
     n = np.asarray(counts, np.int64)
     f = np.asarray(flags, np.int64)
@@ -617,7 +619,7 @@ def voice_spans(positions, counts, flags, latency: int, max_frames_per_call: Opt
     p = np.where(start, 0, pos)
     first = np.maximum(0, p - H)
     last = np.where(end, p + n, np.maximum(0, p + n - H))
-    bad = n < 0
+    bad = (n < 0) | (p < 0) | (p > VOICE_MAX_POSITION)
     if max_frames_per_call is not None:
         bad |= n > int(max_frames_per_call)
     out = np.where(bad, -1, last - first).astype(np.int64)
