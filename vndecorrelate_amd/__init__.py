@@ -32,11 +32,14 @@ from .decorrelation import (  # noqa: F401
 from .analysis import cross_correlogram_batched, set_correlogram_device  # noqa: F401
 from .streaming import (  # noqa: F401
     ChainStream,
+    ChainVoicePool,
     EachStream,
     HaasEachStream,
     HaasStream,
+    HaasVoicePool,
     Stream,
     VoicePool,
     convolve_velvet_noise_stream,
+    haas_voice_spans,
     voice_spans,
 )

@@ -298,6 +298,20 @@ VOICE_STREAM_SIGNATURES = {
     'vnd_voice_stream_f32_host': (ctypes.c_int, _VOICE_STREAM_ARGS),
 }
 
+# include/vnd_haas_voice_stream.h: the voice pool of HaasEffect delays, a delay per slot
+_HAAS_VOICE_STREAM_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                           ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                           ctypes.c_double]
+HAAS_VOICE_STREAM_SIGNATURES = {
+    'vnd_haas_voice_stream_state_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                                         ctypes.POINTER(ctypes.c_int64)]),
+    'vnd_haas_voice_stream_reset_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                       ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p]),
+    'vnd_haas_voice_stream_f64_dev': (ctypes.c_int, _HAAS_VOICE_STREAM_ARGS + [ctypes.c_void_p]),
+    'vnd_haas_voice_stream_f64_host': (ctypes.c_int, _HAAS_VOICE_STREAM_ARGS),
+}
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -350,7 +364,8 @@ def load_library():
                                   + list(HAAS_SEARCH_SIGNATURES.items())
                                   + list(VELVET_SEARCH_SIGNATURES.items())
                                   + list(EACH_SIGNATURES.items()) + list(EACH_STREAM_SIGNATURES.items())
-                                  + list(VOICE_STREAM_SIGNATURES.items())):
+                                  + list(VOICE_STREAM_SIGNATURES.items())
+                                  + list(HAAS_VOICE_STREAM_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -1159,6 +1174,72 @@ def voice_stream_host(ctx: 'Context', bank: 'TapTable', state_ptr: int, state_by
     _voice_stream_call(ctx._lib.vnd_voice_stream_f32_host, 'vnd_voice_stream_f32_host', ctx, bank, state_ptr, state_bytes,
                        max_frames_per_call, x.ctypes.data, c.ctypes.data, f.ctypes.data, t.ctypes.data, y.ctypes.data,
                        out_counts.ctypes.data, slots, x.shape[2], ms_encode, width, mode)
+    return out_counts
+
+
+def haas_voice_stream_state_bytes(slots: int, channels: int, max_delay: int, max_frames_per_call: int) -> int:
+    """``vnd_haas_voice_stream_state_bytes``: one int64 position per slot (padded to 16 bytes), then the ring of a pool of
+    ``slots`` voices delayed by up to ``max_delay`` frames (none for ``max_delay`` 0)."""
+    need = ctypes.c_int64()
+    _check(load_library().vnd_haas_voice_stream_state_bytes(slots, channels, int(max_delay), max_frames_per_call,
+                                                            ctypes.byref(need)), 'vnd_haas_voice_stream_state_bytes')
+    return need.value
+
+
+def haas_voice_stream_reset_device(ctx: 'Context', state_ptr: int, state_bytes: int, slots: int, channels: int,
+                                   max_delay: int, max_frames_per_call: int, *, stream: int = 0):
+    """``vnd_haas_voice_stream_reset_dev``: every position of the pool to 0, enqueued on ``stream``; the ring is left alone."""
+    _check(ctx._lib.vnd_haas_voice_stream_reset_dev(ctx.handle, ctypes.c_void_p(state_ptr), state_bytes, slots, channels,
+                                                    int(max_delay), max_frames_per_call, ctypes.c_void_p(stream)),
+           'vnd_haas_voice_stream_reset_dev')
+
+
+def _haas_voice_stream_call(fn, name: str, ctx, state_ptr, state_bytes, max_frames_per_call, x_ptr, counts_ptr, flags_ptr,
+                            delays_ptr, y_ptr, out_counts_ptr, slots, channels, max_delay, delayed_channel, ms_mode, width,
+                            *stream):
+    _check(fn(ctx.handle, ctypes.c_void_p(state_ptr), state_bytes, max_frames_per_call, ctypes.c_void_p(x_ptr),
+              ctypes.c_void_p(counts_ptr), ctypes.c_void_p(flags_ptr), ctypes.c_void_p(delays_ptr), ctypes.c_void_p(y_ptr),
+              ctypes.c_void_p(out_counts_ptr), slots, channels, int(max_delay), int(delayed_channel), int(bool(ms_mode)),
+              int(width is not None), float(width or 0.0), *stream), name)
+
+
+def haas_voice_stream_device(ctx: 'Context', state_ptr: int, state_bytes: int, max_frames_per_call: int, x_ptr: int,
+                             counts_ptr: int, flags_ptr: int, delays_ptr: int, y_ptr: int, out_counts_ptr: int, slots: int,
+                             channels: int, *, max_delay: int, delayed_channel: int, ms_mode: bool, width, stream: int = 0):
+    """``vnd_haas_voice_stream_f64_dev``: one call of a Haas voice pool.  float32 ``(slots, M, channels)`` blocks, int32
+    ``(slots,)`` counts, flags (``VOICE_START``, ``VOICE_END``) and delays, the float64 ``(slots, M + max_delay, 2)``
+    result and the int32 ``(slots,)`` output counts are device buffers of fixed shape; two kernels enqueued on ``stream``,
+    nothing else."""
+    _haas_voice_stream_call(ctx._lib.vnd_haas_voice_stream_f64_dev, 'vnd_haas_voice_stream_f64_dev', ctx, state_ptr,
+                            state_bytes, max_frames_per_call, x_ptr, counts_ptr, flags_ptr, delays_ptr, y_ptr, out_counts_ptr,
+                            slots, channels, max_delay, delayed_channel, ms_mode, width, ctypes.c_void_p(stream))
+
+
+def haas_voice_stream_host(ctx: 'Context', state_ptr: int, state_bytes: int, max_frames_per_call: int, x: np.ndarray,
+                           counts, flags, delays, y: np.ndarray, *, max_delay: int, delayed_channel: int, ms_mode: bool,
+                           width) -> np.ndarray:
+    """``vnd_haas_voice_stream_f64_host``: the same from host arrays (the state stays on the device), synchronous.  ``x``
+    is a C-contiguous float32 ``(slots, M, 1|2)`` block, ``y`` a C-contiguous float64 ``(slots, M + max_delay, 2)`` array
+    written in place: the first ``out_counts[b]`` frames of row b.  Returns the int32 ``out_counts``."""
+    if x.dtype != np.float32 or not x.flags.c_contiguous or x.ndim != 3 or x.shape[1] != max_frames_per_call:
+        raise ValueError('haas_voice_stream_host wants a C-contiguous float32 (slots, max_frames_per_call, C) block')
+    slots = x.shape[0]
+    if y.dtype != np.float64 or not y.flags.c_contiguous or y.shape != (slots, max_frames_per_call + int(max_delay), 2):
+        raise ValueError('haas_voice_stream_host wants a C-contiguous float64 (slots, max_frames_per_call + max_delay, 2) '
+                         'result')
+    per_slot = []
+    for name, v in (('count', counts), ('flags value', flags), ('delay', delays)):
+        v = np.ascontiguousarray(v, np.int64)
+        i32 = np.iinfo(np.int32)
+        if v.ndim != 1 or v.size != slots or (v.size and (v.min() < i32.min or v.max() > i32.max)):
+            raise ValueError(f'haas_voice_stream_host wants one int32 {name} per slot: {slots} slots, shape {v.shape}')
+        per_slot.append(v.astype(np.int32))
+    c, f, d = per_slot
+    out_counts = np.zeros(slots, np.int32)
+    _haas_voice_stream_call(ctx._lib.vnd_haas_voice_stream_f64_host, 'vnd_haas_voice_stream_f64_host', ctx, state_ptr,
+                            state_bytes, max_frames_per_call, x.ctypes.data, c.ctypes.data, f.ctypes.data, d.ctypes.data,
+                            y.ctypes.data, out_counts.ctypes.data, slots, x.shape[2], max_delay, delayed_channel, ms_mode,
+                            width)
     return out_counts
 
 

@@ -1393,34 +1393,82 @@ def decorrelate_each_stream(decorrelators: Sequence[Decorrelator], *, in_channel
                                     delayed_channel=delayed_channel, ms_mode=ms_mode, width=width)
 
 
-def decorrelate_voice_pool(bank: Sequence[Decorrelator], *, slots: int, in_channels: int = 2, max_frames_per_call: int = 4800):
-    """A ``streaming.VoicePool``: ``slots`` slots over a ``bank`` of plain ``VelvetNoise`` (``normalizer=None``), each
-    slot a voice with a life of its own - it starts on any call with any filter of the bank, brings blocks of any size up
-    to ``max_frames_per_call`` or none, ends on any call, and the slot goes to the next voice.  Where
-    :func:`decorrelate_each_stream` advances a pool in lockstep from a position the host holds, the voice pool keeps one
-    position per slot in the device state (``vnd_voice_stream_f32_*``), so a call is a pure function of device memory and
-    ``process_dev`` can be replayed from a captured graph.
+def _haas_pool_settings(decorrelators, entry: str, one: str):
+    """What a streamed pool of ``HaasEffect`` checks of its list: ``(delayed_channel, ms_mode, width, delays)``, the
+    stage settings the same for every ``one`` (stream, bank entry) and a delay each; ``ValueError`` otherwise."""
+    from . import optimization
+    _same_across(decorrelators, ('delayed_channel', 'mode', 'width'), entry, one)
+    key = optimization._haas_key(decorrelators[0])
+    delays = [optimization._haas_delay(d) for d in decorrelators]
+    if key is None or None in delays:
+        raise ValueError(f'{entry} covers a plain HaasEffect in LR or MS layout with delayed channel 0 or 1, '
+                         'an integer delay in [0, 2**31) and a finite Python / float64 width or None')
+    return (*key, delays)
+
+
+def _chain_pool_stages(bank):
+    """The ``(VelvetNoise, HaasEffect)`` stages of a bank of chains, each exactly those two in that order; ``ValueError`` /
+    ``TypeError`` naming the bank entry otherwise."""
+    velvets, haases = [], []
+    for b, chain in enumerate(bank):
+        chain._init_decorrelators()
+        stages = list(chain._decorrelators)
+        if len(stages) != 2:
+            raise ValueError(f'bank entry {b}: a chain of {len(stages)} stages; a voice pool runs exactly one VelvetNoise '
+                             'stage and then one HaasEffect stage')
+        if type(stages[0]) is not VelvetNoise or type(stages[1]) is not HaasEffect:
+            raise TypeError(f'bank entry {b}: a chain of {type(stages[0]).__name__} then {type(stages[1]).__name__}; a voice '
+                            'pool runs exactly one VelvetNoise stage and then one HaasEffect stage')
+        velvets.append(stages[0])
+        haases.append(stages[1])
+    return velvets, haases
+
+
+def decorrelate_voice_pool(bank: Sequence, *, slots: int, in_channels: int = 2, max_frames_per_call: int = 4800):
+    """A voice pool: ``slots`` slots over a ``bank``, each slot a voice with a life of its own - it starts on any call
+    with any entry of the bank, brings blocks of any size up to ``max_frames_per_call`` or none, ends on any call, and the
+    slot goes to the next voice.  Where :func:`decorrelate_each_stream` advances a pool in lockstep from a position the
+    host holds, the voice pool keeps one position per slot in the device state, so a call is a pure function of device
+    memory and ``process_dev`` can be replayed from a captured graph.  Three kinds of bank:
+
+    * all plain ``VelvetNoise`` (``normalizer=None``): a ``streaming.VoicePool`` (``vnd_voice_stream_f32_*``), float32
+      out, ``latency_frames`` the bank's largest tap index.  The bank is deduplicated by content
+      (``pool.bank_tables[bank_index]`` is the candidate ``process_dev`` names).
+    * all ``HaasEffect``: a ``streaming.HaasVoicePool`` (``vnd_haas_voice_stream_f64_*``), float64 out, no latency, and a
+      voice's end returns its own delay's tail, ``pool.bank_delays[bank_index]`` frames.
+    * all ``SignalChain``, each exactly one ``VelvetNoise(normalizer=None)`` stage and then one ``HaasEffect`` stage (the
+      chains are instantiated now): a ``streaming.ChainVoicePool``, both stages on the device, float64 out.
 
     ``pool.process({slot: block}, start={slot: bank_index}, end=[slot])`` takes float32 NumPy blocks and returns
-    ``{slot: (n_out, 2)}``; ``pool.process_dev(x, counts, flags, tables)`` takes device tensors of fixed shape and only
-    enqueues.  For every voice the concatenation of its outputs equals ``bank[t].decorrelate(x_voice)`` bit for bit.
-    ``latency_frames`` is the bank's largest tap index.  The bank is deduplicated by content
-    (``pool.bank_tables[bank_index]`` is the candidate ``process_dev`` names) and checked as
-    :func:`decorrelate_each_stream` checks its list, with the same exceptions before any device call.  There is no host
-    fallback: a stream has no host loop to fall back to."""
+    ``{slot: (n_out, 2)}``; ``pool.process_dev(...)`` takes device tensors of fixed shape and only enqueues.  For every
+    voice the concatenation of its outputs equals ``bank[i].decorrelate(x_voice)`` - ``bank[i](x_voice)`` for a chain - bit
+    for bit.  The velvet stages are checked as :func:`decorrelate_each_stream` checks its ``VelvetNoise`` list and the Haas
+    stages as it checks its ``HaasEffect`` list, with the same exceptions before any device call; a mixed bank is a
+    ``TypeError`` listing the types.  There is no host fallback: a stream has no host loop to fall back to."""
     from . import streaming
     bank = list(bank)
     if not bank:
         raise ValueError('decorrelate_voice_pool needs at least one decorrelator: a voice starts with a filter of the bank')
     kinds = {type(d) for d in bank}
-    if kinds != {VelvetNoise}:
-        raise TypeError('decorrelate_voice_pool takes a bank of plain VelvetNoise decorrelators, got '
-                        + ', '.join(sorted(k.__name__ for k in kinds)))
+    if kinds not in ({VelvetNoise}, {HaasEffect}, {SignalChain}):
+        raise TypeError('decorrelate_voice_pool takes a bank of plain VelvetNoise decorrelators, of HaasEffect decorrelators '
+                        'or of VelvetNoise -> HaasEffect SignalChains, got ' + ', '.join(sorted(k.__name__ for k in kinds)))
     if isinstance(in_channels, (bool, np.bool_)) or in_channels not in (1, 2):
         raise ValueError(f'in_channels must be 1 (mono, fanned out) or 2 (stereo), got {in_channels!r}')
-    arrays, tables, ms_encode, width = _velvet_stream_bank(bank, 'decorrelate_voice_pool', 'bank entry')
-    return streaming.VoicePool(arrays, tables, slots=slots, in_channels=in_channels,
-                               max_frames_per_call=max_frames_per_call, ms_encode=ms_encode, width=width)
+    if kinds == {VelvetNoise}:
+        arrays, tables, ms_encode, width = _velvet_stream_bank(bank, 'decorrelate_voice_pool', 'bank entry')
+        return streaming.VoicePool(arrays, tables, slots=slots, in_channels=in_channels,
+                                   max_frames_per_call=max_frames_per_call, ms_encode=ms_encode, width=width)
+    if kinds == {HaasEffect}:
+        delayed_channel, ms_mode, width, delays = _haas_pool_settings(bank, 'decorrelate_voice_pool', 'bank entry')
+        return streaming.HaasVoicePool(delays, slots=slots, in_channels=in_channels, max_frames_per_call=max_frames_per_call,
+                                       delayed_channel=delayed_channel, ms_mode=ms_mode, width=width)
+    velvets, haases = _chain_pool_stages(bank)
+    arrays, tables, ms_encode, velvet_width = _velvet_stream_bank(velvets, 'decorrelate_voice_pool', 'bank entry')
+    delayed_channel, ms_mode, haas_width, delays = _haas_pool_settings(haases, 'decorrelate_voice_pool', 'bank entry')
+    return streaming.ChainVoicePool(arrays, tables, delays, slots=slots, in_channels=in_channels,
+                                    max_frames_per_call=max_frames_per_call, ms_encode=ms_encode, velvet_width=velvet_width,
+                                    delayed_channel=delayed_channel, ms_mode=ms_mode, haas_width=haas_width)
 
 
 # ----------------------------------------------------------------------------

@@ -627,7 +627,134 @@ def voice_spans(positions, counts, flags, latency: int, max_frames_per_call: Opt
     return out, new
 
 
-class VoicePool:
+class _SlotPool:
+    """What the voice pools share (:class:`VoicePool`, :class:`HaasVoicePool`, :class:`ChainVoicePool`): the host's mirror of
+    the slots, ``reset()``, and the dict form ``process`` with every refusal before the device.  A pool sets ``slots``,
+    ``in_channels``, ``max_frames_per_call`` and ``_state = None``, calls ``_mirror()``, and supplies the hooks below and
+    ``_allocate`` / ``_reset_device`` / ``_call_host``."""
+
+    def _mirror(self):
+        """The host's copy of what the device state says, for the dict form: all slots idle at position 0."""
+        self.positions = np.zeros(self.slots, np.int64)
+        self.live = np.zeros(self.slots, bool)
+        self.tables = np.zeros(self.slots, np.int32)
+        self._form = None
+
+
+    # ---- public ------------------------------------------------------------------------
+    def reset(self):
+        """End every voice, unflushed: every position back to 0 (enqueued on the current torch stream; the ring is not
+        cleared, it is never read before it is written), and either form may follow.  Allocates the state on first use."""
+        torch = _native.torch_module()
+        ctx = _native.default_context()
+        if self._state is None:
+            self._allocate(torch, ctx)
+        else:
+            self._reset_device(torch, ctx)
+        self._mirror()
+
+    def process(self, blocks=None, *, start=None, end=(), discard: bool = False):
+        """One call of the dict form.  ``blocks``: ``{slot: float32 (n, in_channels) array}`` (``(n,)`` as well for mono),
+        ``0 <= n <= max_frames_per_call``; ``start``: ``{slot: bank_index}``, the voices that begin with this call;
+        ``end``: the slots whose voice ends with it (its tail comes with this call).  Returns ``{slot: (n_out, 2)}`` for
+        every slot that got a block or ended.  Raises before any device call: ``ValueError`` for a slot outside the pool,
+        a block or an end for a slot that was never started, a start on a live slot (``discard=True`` allows it: what
+        the slot held is dropped, unflushed), a bank index outside the bank, a block above ``max_frames_per_call`` or of
+        another channel count; ``TypeError`` for a block that is not float32."""
+        if self._form == 'dev':
+            raise RuntimeError('this pool runs through process_dev(): the host does not know its positions; reset() first')
+        counts, flags, tables, live, x, answered = self._schedule(blocks, start, end, discard)
+        if not counts.any() and not flags.any():              # nothing pushed, started or ended: no device call
+            return {slot: np.zeros((0, 2), self._out_dtype) for slot in answered}
+        want, positions = self._spans(counts, flags, tables)
+        y, got = self._call_host(x, counts, flags, *self._per_slot(tables))
+        if not np.array_equal(np.asarray(got, np.int64), want):
+            raise _native.NativeError(f'the voice pool returned the counts {list(got)}, the spans are {list(want)}')
+        self._commit(positions)
+        self.tables, self._form = tables, 'dict'
+        live[(flags & VOICE_END) != 0] = False
+        self.live = live
+        return {slot: np.array(y[slot, :int(want[slot])]) for slot in answered}
+
+    # ---- what a pool supplies ------------------------------------------------------------------
+    _out_dtype = np.float32
+
+    def _spans(self, counts, flags, tables):
+        """``(out_counts, new positions)`` of the call, from the host mirror."""
+        raise NotImplementedError
+
+    def _per_slot(self, tables):
+        """The per-slot int32 arrays that go up beside counts and flags, from what ``_schedule`` keeps per slot."""
+        return (tables,)
+
+    def _bank_len(self) -> int:
+        """Entries in the bank a voice starts with."""
+        raise NotImplementedError
+
+    def _slot_value(self, index: int):
+        """What ``_schedule`` keeps in ``tables`` for a slot that starts with bank entry ``index``."""
+        raise NotImplementedError
+
+    def _commit(self, positions):
+        self.positions = positions
+
+    # ---- checks --------------------------------------------------------------------------
+    def _slot(self, slot, what: str) -> int:
+        if isinstance(slot, (bool, np.bool_)) or not isinstance(slot, (int, np.integer)) or not 0 <= slot < self.slots:
+            raise ValueError(f'{what}: slot {slot!r} is outside the pool of {self.slots} slots')
+        return int(slot)
+
+    def _schedule(self, blocks, start, end, discard: bool):
+        """The call's arrays from the dicts, every refusal included; nothing of the pool is changed."""
+        S, M, cx = self.slots, self.max_frames_per_call, self.in_channels
+        counts, flags = np.zeros(S, np.int32), np.zeros(S, np.int32)
+        tables, live = self.tables.copy(), self.live.copy()
+        for slot, index in dict(start or {}).items():
+            slot = self._slot(slot, 'start')
+            if isinstance(index, (bool, np.bool_)) or not isinstance(index, (int, np.integer)) \
+                    or not 0 <= index < self._bank_len():
+                raise ValueError(f'start: bank index {index!r} of slot {slot} is outside the bank of {self._bank_len()}')
+            if live[slot] and not discard:
+                raise ValueError(f'start: slot {slot} holds a live voice: end it first, or pass discard=True to drop it '
+                                 'unflushed')
+            flags[slot] |= VOICE_START
+            tables[slot] = self._slot_value(int(index))
+            live[slot] = True
+        x = np.zeros((S, M, cx), np.float32)
+        answered = set()
+        for slot, block in dict(blocks or {}).items():
+            slot = self._slot(slot, 'block')
+            if not live[slot]:
+                raise ValueError(f'block for slot {slot}, which was never started: name it in start=')
+            a = np.asarray(block)
+            if a.dtype != np.float32:
+                raise TypeError(f'block of slot {slot}: voices push float32 frames, got {a.dtype}')
+            if a.ndim == 1 and cx == 1:
+                a = a[:, None]
+            if a.ndim != 2 or a.shape[1] != cx:
+                raise ValueError(f'block of slot {slot} has shape {tuple(np.shape(block))}: expected (frames, {cx})')
+            if a.shape[0] > M:
+                raise ValueError(f'block of slot {slot}: {a.shape[0]} frames in one call, above max_frames_per_call={M}')
+            counts[slot] = a.shape[0]
+            x[slot, :a.shape[0]] = a
+            answered.add(slot)
+        for slot in list(end):
+            slot = self._slot(slot, 'end')
+            if not live[slot]:
+                raise ValueError(f'end of slot {slot}, which was never started')
+            if flags[slot] & VOICE_END:
+                raise ValueError(f'end: slot {slot} is named twice')
+            flags[slot] |= VOICE_END
+            answered.add(slot)
+        return counts, flags, tables, live, x, sorted(answered)
+
+    def _ensure_state(self, torch, ctx):
+        if self._state is None:
+            self._allocate(torch, ctx)
+        return self._state
+
+
+class VoicePool(_SlotPool):
     """``slots`` slots over a bank of velvet-noise filters, each slot a voice with a life of its own
     (``decorrelation.decorrelate_voice_pool``, ``vnd_voice_stream_f32_*``): voices start and end on any call, bring blocks
     of any size up to ``max_frames_per_call`` or none, and a slot is handed to a new voice with another filter of the bank
@@ -670,51 +797,10 @@ class VoicePool:
         self._state = None                    # (torch uint8 tensor, bytes)
         self._mirror()
 
-    def _mirror(self):
-        """The host's copy of what the device state says, for the dict form: all slots idle at position 0."""
-        self.positions = np.zeros(self.slots, np.int64)
-        self.live = np.zeros(self.slots, bool)
-        self.tables = np.zeros(self.slots, np.int32)
-        self._form = None
-
     @property
     def row_frames(self) -> int:
         """Frames per row of the result: ``max_frames_per_call + latency_frames``."""
         return self.max_frames_per_call + self.latency_frames
-
-    # ---- public ------------------------------------------------------------------------
-    def reset(self):
-        """End every voice, unflushed: every position back to 0 (enqueued on the current torch stream; the ring is not
-        cleared, it is never read before it is written), and either form may follow.  Allocates the state on first use."""
-        torch = _native.torch_module()
-        ctx = _native.default_context()
-        if self._state is None:
-            self._allocate(torch, ctx)
-        else:
-            self._reset_device(torch, ctx)
-        self._mirror()
-
-    def process(self, blocks=None, *, start=None, end=(), discard: bool = False):
-        """One call of the dict form.  ``blocks``: ``{slot: float32 (n, in_channels) array}`` (``(n,)`` as well for mono),
-        ``0 <= n <= max_frames_per_call``; ``start``: ``{slot: bank_index}``, the voices that begin with this call;
-        ``end``: the slots whose voice ends with it (its tail comes with this call).  Returns ``{slot: (n_out, 2)}`` for
-        every slot that got a block or ended.  Raises before any device call: ``ValueError`` for a slot outside the pool,
-        a block or an end for a slot that was never started, a start on a live slot (``discard=True`` allows it: what
-        the slot held is dropped, unflushed), a bank index outside the bank, a block above ``max_frames_per_call`` or of
-        another channel count; ``TypeError`` for a block that is not float32."""
-        if self._form == 'dev':
-            raise RuntimeError('this pool runs through process_dev(): the host does not know its positions; reset() first')
-        counts, flags, tables, live, x, answered = self._schedule(blocks, start, end, discard)
-        if not counts.any() and not flags.any():              # nothing pushed, started or ended: no device call
-            return {slot: np.zeros((0, 2), np.float32) for slot in answered}
-        want, positions = voice_spans(self.positions, counts, flags, self.latency_frames, self.max_frames_per_call)
-        y, got = self._call_host(x, counts, flags, tables)
-        if not np.array_equal(np.asarray(got, np.int64), want):
-            raise _native.NativeError(f'the voice pool returned the counts {list(got)}, the spans are {list(want)}')
-        self.positions, self.tables, self._form = positions, tables, 'dict'
-        live[(flags & VOICE_END) != 0] = False
-        self.live = live
-        return {slot: np.array(y[slot, :int(want[slot])]) for slot in answered}
 
     def process_dev(self, x, counts, flags, tables, *, out=None):
         """One call on device tensors, enqueued on the current stream: ``x`` float32 ``(slots, M, in_channels)``,
@@ -739,55 +825,14 @@ class VoicePool:
                 raise ValueError(f'{name} must be a contiguous {dtype} tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}')
         return self._call_device(_native.torch_module(), x, counts, flags, tables, y, out_counts)
 
-    # ---- checks --------------------------------------------------------------------------
-    def _slot(self, slot, what: str) -> int:
-        if isinstance(slot, (bool, np.bool_)) or not isinstance(slot, (int, np.integer)) or not 0 <= slot < self.slots:
-            raise ValueError(f'{what}: slot {slot!r} is outside the pool of {self.slots} slots')
-        return int(slot)
+    def _spans(self, counts, flags, tables):
+        return voice_spans(self.positions, counts, flags, self.latency_frames, self.max_frames_per_call)
 
-    def _schedule(self, blocks, start, end, discard: bool):
-        """The call's arrays from the dicts, every refusal included; nothing of the pool is changed."""
-        S, M, cx = self.slots, self.max_frames_per_call, self.in_channels
-        counts, flags = np.zeros(S, np.int32), np.zeros(S, np.int32)
-        tables, live = self.tables.copy(), self.live.copy()
-        for slot, index in dict(start or {}).items():
-            slot = self._slot(slot, 'start')
-            if isinstance(index, (bool, np.bool_)) or not isinstance(index, (int, np.integer)) \
-                    or not 0 <= index < len(self.bank_tables):
-                raise ValueError(f'start: bank index {index!r} of slot {slot} is outside the bank of {len(self.bank_tables)}')
-            if live[slot] and not discard:
-                raise ValueError(f'start: slot {slot} holds a live voice: end it first, or pass discard=True to drop it '
-                                 'unflushed')
-            flags[slot] |= VOICE_START
-            tables[slot] = self.bank_tables[int(index)]
-            live[slot] = True
-        x = np.zeros((S, M, cx), np.float32)
-        answered = set()
-        for slot, block in dict(blocks or {}).items():
-            slot = self._slot(slot, 'block')
-            if not live[slot]:
-                raise ValueError(f'block for slot {slot}, which was never started: name it in start=')
-            a = np.asarray(block)
-            if a.dtype != np.float32:
-                raise TypeError(f'block of slot {slot}: voices push float32 frames, got {a.dtype}')
-            if a.ndim == 1 and cx == 1:
-                a = a[:, None]
-            if a.ndim != 2 or a.shape[1] != cx:
-                raise ValueError(f'block of slot {slot} has shape {tuple(np.shape(block))}: expected (frames, {cx})')
-            if a.shape[0] > M:
-                raise ValueError(f'block of slot {slot}: {a.shape[0]} frames in one call, above max_frames_per_call={M}')
-            counts[slot] = a.shape[0]
-            x[slot, :a.shape[0]] = a
-            answered.add(slot)
-        for slot in list(end):
-            slot = self._slot(slot, 'end')
-            if not live[slot]:
-                raise ValueError(f'end of slot {slot}, which was never started')
-            if flags[slot] & VOICE_END:
-                raise ValueError(f'end: slot {slot} is named twice')
-            flags[slot] |= VOICE_END
-            answered.add(slot)
-        return counts, flags, tables, live, x, sorted(answered)
+    def _bank_len(self) -> int:
+        return len(self.bank_tables)
+
+    def _slot_value(self, index: int):
+        return self.bank_tables[index]
 
     # ---- the device -------------------------------------------------------------------------
     def _allocate(self, torch, ctx):
@@ -805,11 +850,6 @@ class VoicePool:
         _native.voice_stream_reset_device(ctx, self._table, state.data_ptr(), state_bytes, self.slots, self.in_channels,
                                           self.max_frames_per_call,
                                           stream=torch.cuda.current_stream(state.device).cuda_stream)
-
-    def _ensure_state(self, torch, ctx):
-        if self._state is None:
-            self._allocate(torch, ctx)
-        return self._state
 
     def _call_host(self, x, counts, flags, tables):
         torch = _native.torch_module()
@@ -838,3 +878,282 @@ class VoicePool:
                                     out_counts.data_ptr(), self.slots, self.in_channels, ms_encode=self.ms_encode,
                                     width=self.width, stream=torch.cuda.current_stream(device).cuda_stream)
         return y, out_counts
+
+
+# ----------------------------------------------------------------------------
+# A voice pool of Haas delays, and of velvet-then-Haas chains   (include/vnd_haas_voice_stream.h)
+# ----------------------------------------------------------------------------
+HAAS_VOICE_MAX_ROW_FRAMES = 65535 * 256       # VND_HAAS_VOICE_MAX_ROW_FRAMES: the workgroups of a row are one grid dimension
+
+
+def haas_voice_spans(positions, counts, flags, delays, max_delay: int, max_frames_per_call: Optional[int] = None):
+    """``(out_counts, new_positions)`` of one call of a Haas voice pool (``include/vnd_haas_voice_stream.h``), per slot,
+    from the positions before the call, the frames pushed, the ``VOICE_START`` / ``VOICE_END`` flags and the delays
+    alone - what the device computes from its own state::
+
+        p = START ? 0 : position      out_count = n + (END ? d : 0)      new position = END ? 0 : p + n
+
+    A count below 0 (or above ``max_frames_per_call``, when given), without START a position outside ``[0, 2^60]``, or -
+    on a slot with frames or a flag - a delay outside ``[0, max_delay]`` answers -1 and leaves the position as it was."""
+    d = np.asarray(delays, np.int64)
+    out, new = voice_spans(positions, counts, flags, 0, max_frames_per_call)
+    if d.shape != out.shape:
+        raise ValueError(f'delays of the shape of positions, counts and flags, got {d.shape} and {out.shape}')
+    pos, n, f = np.asarray(positions, np.int64), np.asarray(counts, np.int64), np.asarray(flags, np.int64)
+    work = (n != 0) | ((f & (VOICE_START | VOICE_END)) != 0)
+    bad = (out < 0) | (work & ((d < 0) | (d > int(max_delay))))
+    end = (f & VOICE_END) != 0
+    out = np.where(bad, -1, out + np.where(end & work, d, 0)).astype(np.int64)
+    return out, np.where(bad, pos, new).astype(np.int64)
+
+
+def _check_device_tensors(specs):
+    """``process_dev``'s look at its tensors: ``(name, tensor, shape, dtype, optional)`` each; no device memory is read."""
+    for name, t, shape, dtype, optional in specs:
+        if t is None and optional:
+            continue
+        if not _native.is_torch(t) or not t.is_cuda:
+            raise ValueError(f'{name} must be a device tensor')
+        if tuple(t.shape) != shape or str(t.dtype) != 'torch.' + dtype or not t.is_contiguous():
+            raise ValueError(f'{name} must be a contiguous {dtype} tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}')
+
+
+class HaasVoicePool(_SlotPool):
+    """``slots`` slots over a bank of ``HaasEffect`` delays, each slot a voice with a life of its own
+    (``decorrelation.decorrelate_voice_pool``, ``vnd_haas_voice_stream_f64_*``): :class:`VoicePool` for the Haas delay.
+    ``latency_frames`` is 0 - the delay is causal, a call returns the frames it was given - and a voice's end returns its
+    own delay's tail as well; ``tail_frames`` is the bank's largest delay, ``bank_delays[bank_index]`` the delay a voice
+    started with ``bank_index`` gets, ``row_frames = max_frames_per_call + tail_frames``.  For every voice the
+    concatenation of what its calls return equals ``bank[i].decorrelate(x_voice)`` bit for bit: float64, ``n + d`` frames.
+
+    The two forms of :class:`VoicePool`, with the same refusals and the same rule against mixing them:
+    ``process({slot: float32 block}, start={slot: bank_index}, end=[slot], discard=False)`` returns
+    ``{slot: float64 (n_out, 2)}``; ``process_dev(x, counts, flags, delays)`` takes device tensors of fixed shape, only
+    enqueues, and can be captured after ``reset()``."""
+
+    _out_dtype = np.float64
+
+    def __init__(self, bank_delays, *, slots: int, in_channels: int, max_frames_per_call: int, delayed_channel: int,
+                 ms_mode: bool, width: Optional[float] = None):
+        _check_counts(slots=slots, in_channels=in_channels, max_frames_per_call=max_frames_per_call)
+        if in_channels not in (1, 2):
+            raise ValueError(f'a pool of mono (1) or stereo (2) voices is taken, got in_channels={in_channels}')
+        if slots > _native.MAX_STREAMS_PER_CALL:
+            raise ValueError(f'slots {slots} above {_native.MAX_STREAMS_PER_CALL}: split the pool')
+        self.bank_delays = np.ascontiguousarray(bank_delays, np.int32)
+        if self.bank_delays.ndim != 1 or not self.bank_delays.size or self.bank_delays.min() < 0:
+            raise ValueError('bank_delays: one delay >= 0 per bank entry')
+        if delayed_channel not in (0, 1):
+            raise ValueError(f'delayed_channel must be 0 or 1, got {delayed_channel!r}')
+        self.max_delay = int(self.bank_delays.max())
+        if max_frames_per_call + self.max_delay > HAAS_VOICE_MAX_ROW_FRAMES:
+            raise ValueError(f'max_frames_per_call {max_frames_per_call} and the largest delay {self.max_delay} make a row '
+                             f'above {HAAS_VOICE_MAX_ROW_FRAMES} frames')
+        self.slots, self.in_channels, self.max_frames_per_call = int(slots), int(in_channels), int(max_frames_per_call)
+        self.delayed_channel, self.ms_mode, self.width = int(delayed_channel), bool(ms_mode), width
+        self.latency_frames, self.tail_frames = 0, self.max_delay
+        self.num_channels = 2
+        self._state = None
+        self._mirror()
+
+    @property
+    def row_frames(self) -> int:
+        """Frames per row of the result: ``max_frames_per_call + tail_frames``."""
+        return self.max_frames_per_call + self.max_delay
+
+    def process_dev(self, x, counts, flags, delays, *, out=None):
+        """One call on device tensors, enqueued on the current stream: ``x`` float32 ``(slots, M, in_channels)``,
+        ``counts`` / ``flags`` / ``delays`` int32 ``(slots,)``.  Returns ``(y, out_counts)``: float64
+        ``(slots, M + max delay, 2)`` - the first ``out_counts[b]`` frames of row b are written, nothing at or past
+        them - and int32 ``(slots,)``; ``out=(y, out_counts)`` takes the caller's.  No check reads device memory; bad
+        per-slot values answer -1 (``include/vnd_haas_voice_stream.h``)."""
+        if self._form == 'dict':
+            raise RuntimeError('this pool runs through process(): mixing in process_dev() would leave the host mirror '
+                               'of the positions stale; reset() first')
+        S, M, cx = self.slots, self.max_frames_per_call, self.in_channels
+        y, out_counts = out if out is not None else (None, None)
+        _check_device_tensors((('x', x, (S, M, cx), 'float32', False), ('counts', counts, (S,), 'int32', False),
+                               ('flags', flags, (S,), 'int32', False), ('delays', delays, (S,), 'int32', False),
+                               ('y', y, (S, self.row_frames, 2), 'float64', True),
+                               ('out_counts', out_counts, (S,), 'int32', True)))
+        return self._call_device(_native.torch_module(), x, counts, flags, delays, y, out_counts)
+
+    def _spans(self, counts, flags, delays):
+        return haas_voice_spans(self.positions, counts, flags, delays, self.max_delay, self.max_frames_per_call)
+
+    def _bank_len(self) -> int:
+        return len(self.bank_delays)
+
+    def _slot_value(self, index: int):
+        return self.bank_delays[index]                           # ``tables`` holds the slots' delays
+
+    # ---- the device -------------------------------------------------------------------------
+    def _allocate(self, torch, ctx):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('the state of a voice pool is allocated and zeroed on first use: call reset() before the capture')
+        need = _native.haas_voice_stream_state_bytes(self.slots, self.in_channels, self.max_delay, self.max_frames_per_call)
+        buf = torch.empty((max(need, 16),), dtype=torch.uint8, device=torch.device('cuda', ctx.device))
+        self._state = (buf, need)
+        self._reset_device(torch, ctx)
+
+    def _reset_device(self, torch, ctx):
+        state, state_bytes = self._state
+        _native.haas_voice_stream_reset_device(ctx, state.data_ptr(), state_bytes, self.slots, self.in_channels,
+                                               self.max_delay, self.max_frames_per_call,
+                                               stream=torch.cuda.current_stream(state.device).cuda_stream)
+
+    def _call_host(self, x, counts, flags, delays):
+        torch = _native.torch_module()
+        ctx = _native.default_context()
+        state, state_bytes = self._ensure_state(torch, ctx)
+        torch.cuda.current_stream(state.device).synchronize()          # (the reset, or a reset() on this stream)
+        y = np.empty((self.slots, self.row_frames, 2), np.float64)
+        got = _native.haas_voice_stream_host(ctx, state.data_ptr(), state_bytes, self.max_frames_per_call, x, counts, flags,
+                                             delays, y, max_delay=self.max_delay, delayed_channel=self.delayed_channel,
+                                             ms_mode=self.ms_mode, width=self.width)
+        return y, got
+
+    def _call_device(self, torch, x, counts, flags, delays, y, out_counts):
+        ctx = _native.default_context()
+        device = torch.device('cuda', ctx.device)
+        for t in (x, counts, flags, delays):
+            if t.device != device:
+                raise ValueError(f'tensor on {t.device}, the pool runs on {device}')
+        state, state_bytes = self._ensure_state(torch, ctx)
+        if y is None:
+            y = torch.empty((self.slots, self.row_frames, 2), dtype=torch.float64, device=device)
+        if out_counts is None:
+            out_counts = torch.empty((self.slots,), dtype=torch.int32, device=device)
+        self._form = 'dev'
+        _native.haas_voice_stream_device(ctx, state.data_ptr(), state_bytes, self.max_frames_per_call, x.data_ptr(),
+                                         counts.data_ptr(), flags.data_ptr(), delays.data_ptr(), y.data_ptr(),
+                                         out_counts.data_ptr(), self.slots, self.in_channels, max_delay=self.max_delay,
+                                         delayed_channel=self.delayed_channel, ms_mode=self.ms_mode, width=self.width,
+                                         stream=torch.cuda.current_stream(device).cuda_stream)
+        return y, out_counts
+
+
+class ChainVoicePool(VoicePool):
+    """``slots`` slots over a bank of chains ``VelvetNoise`` -> ``HaasEffect``, each slot a voice with a life of its own
+    (``decorrelation.decorrelate_voice_pool`` on a bank of ``SignalChain``): a voice goes through its velvet-noise filter
+    and then its Haas delay entirely on the device.  Two calls of the C ABI on one stream: ``vnd_voice_stream_f32_dev``
+    writes a float32 ``(slots, M + H, 2)`` buffer and an int32 ``out_counts`` that the pool owns (allocated in
+    ``reset()``, so nothing is allocated during a capture), and ``vnd_haas_voice_stream_f64_dev`` - with
+    ``max_frames_per_call = M + H``, stereo in - reads that ``out_counts`` as its ``counts`` from device memory and gets the
+    caller's own ``flags`` and ``delays``; a -1 of stage 1 is a bad count of stage 2 and answers -1.  A call stays a pure
+    function of device memory.
+
+    ``latency_frames`` is H, the velvet bank's largest tap index; ``tail_frames`` the bank's largest delay, a voice's own
+    tail is ``bank_delays[bank_index]``; ``bank_tables[bank_index]`` is its candidate of the deduplicated velvet bank;
+    ``row_frames = M + H + tail_frames``.  For every voice the concatenation of what its calls return equals
+    ``bank[i](x_voice)`` - ``chain(x)`` - bit for bit, float64.
+
+    ``process({slot: block}, start={slot: bank_index}, end=[slot], discard=False)`` makes one upload, runs both stages on
+    the device and makes one download (``transfers`` counts those of the last call);
+    ``process_dev(x, counts, flags, tables, delays)`` only enqueues and can be captured after ``reset()``.  Refusals and
+    the rule against mixing the forms are :class:`VoicePool`'s."""
+
+    _out_dtype = np.float64
+
+    def __init__(self, arrays: TapArrays, bank_tables, bank_delays, *, slots: int, in_channels: int, max_frames_per_call: int,
+                 ms_encode: bool, velvet_width: Optional[float], delayed_channel: int, ms_mode: bool,
+                 haas_width: Optional[float]):
+        VoicePool.__init__(self, arrays, bank_tables, slots=slots, in_channels=in_channels,
+                           max_frames_per_call=max_frames_per_call, ms_encode=ms_encode, width=velvet_width)
+        self.bank_delays = np.ascontiguousarray(bank_delays, np.int32)
+        if self.bank_delays.shape != self.bank_tables.shape or self.bank_delays.min() < 0:
+            raise ValueError('bank_delays: one delay >= 0 per bank entry')
+        self.haas = HaasVoicePool(self.bank_delays, slots=slots, in_channels=2,
+                                  max_frames_per_call=self.max_frames_per_call + self.latency_frames,
+                                  delayed_channel=delayed_channel, ms_mode=ms_mode, width=haas_width)
+        self.max_delay = self.tail_frames = self.haas.max_delay
+        self.transfers = {'to_device': 0, 'to_host': 0}
+        self._mid = None                      # (float32 (slots, M + H, 2), int32 (slots,)): stage 1's result, on the device
+
+    def _mirror(self):
+        VoicePool._mirror(self)
+        self.haas_positions = np.zeros(self.slots, np.int64)      # stage 2's: the frames stage 1 has returned
+
+    @property
+    def row_frames(self) -> int:
+        """Frames per row of the result: ``max_frames_per_call + latency_frames + tail_frames``."""
+        return self.haas.row_frames
+
+    def reset(self):
+        """End every voice in both stages, unflushed; allocates both states and the intermediate buffers on first use."""
+        VoicePool.reset(self)
+        self.haas.reset()
+
+    def process_dev(self, x, counts, flags, tables, delays, *, out=None):
+        """One call on device tensors, enqueued on the current stream: ``x`` float32 ``(slots, M, in_channels)``,
+        ``counts`` / ``flags`` / ``tables`` / ``delays`` int32 ``(slots,)``.  Returns ``(y, out_counts)``: float64
+        ``(slots, M + H + max delay, 2)`` and int32 ``(slots,)``; ``out=(y, out_counts)`` takes the caller's.  A bad
+        count answers -1 from both stages and leaves the slot alone.  A bad ``delays[b]`` on a slot with work is seen by
+        stage 2 only: it answers -1 and stands still, but stage 1 has taken the block and moved on, so the two stages of
+        that voice are out of step and its frames of this call are lost - restart the voice (START) before it goes on.
+        The dict form cannot send one: its delays come from the bank."""
+        if self._form == 'dict':
+            raise RuntimeError('this pool runs through process(): mixing in process_dev() would leave the host mirror '
+                               'of the positions stale; reset() first')
+        S, M, cx = self.slots, self.max_frames_per_call, self.in_channels
+        y, out_counts = out if out is not None else (None, None)
+        _check_device_tensors((('x', x, (S, M, cx), 'float32', False), ('counts', counts, (S,), 'int32', False),
+                               ('flags', flags, (S,), 'int32', False), ('tables', tables, (S,), 'int32', False),
+                               ('delays', delays, (S,), 'int32', False),
+                               ('y', y, (S, self.row_frames, 2), 'float64', True),
+                               ('out_counts', out_counts, (S,), 'int32', True)))
+        return self._call_device(_native.torch_module(), x, counts, flags, tables, delays, y, out_counts)
+
+    def _spans(self, counts, flags, entries):
+        mid, first = voice_spans(self.positions, counts, flags, self.latency_frames, self.max_frames_per_call)
+        out, second = haas_voice_spans(self.haas_positions, mid, flags, self.bank_delays[entries], self.max_delay,
+                                       self.haas.max_frames_per_call)
+        return out, (first, second)
+
+    def _per_slot(self, entries):
+        return self.bank_tables[entries], self.bank_delays[entries]
+
+    def _slot_value(self, index: int):
+        return index                          # the bank entry: its table and its delay go up together
+
+    def _commit(self, positions):
+        self.positions, self.haas_positions = positions
+
+    # ---- the device -------------------------------------------------------------------------
+    def _allocate(self, torch, ctx):
+        VoicePool._allocate(self, torch, ctx)
+        device = torch.device('cuda', ctx.device)
+        self._mid = (torch.empty((self.slots, self.haas.max_frames_per_call, 2), dtype=torch.float32, device=device),
+                     torch.empty((self.slots,), dtype=torch.int32, device=device))
+
+    def _call_host(self, x, counts, flags, tables, delays):
+        """One upload (the blocks and the four int32 arrays in one buffer), both stages, one download (y and out_counts)."""
+        torch = _native.torch_module()
+        ctx = _native.default_context()
+        device = torch.device('cuda', ctx.device)
+        S = self.slots
+        ints = np.stack([counts, flags, tables, delays]).astype(np.int32)
+        up = torch.from_numpy(np.concatenate([x.reshape(-1).view(np.uint8), ints.reshape(-1).view(np.uint8)])).to(device)
+        self.transfers = {'to_device': 1, 'to_host': 0}
+        x_dev = up[:x.nbytes].view(torch.float32).view(x.shape)
+        c, f, t, d = up[x.nbytes:].view(torch.int32).view(4, S)
+        y_bytes = S * self.row_frames * 2 * 8
+        down = torch.empty((y_bytes + 4 * S,), dtype=torch.uint8, device=device)
+        y = down[:y_bytes].view(torch.float64).view(S, self.row_frames, 2)
+        out_counts = down[y_bytes:].view(torch.int32)
+        form = self._form
+        try:
+            self._call_device(torch, x_dev, c, f, t, d, y, out_counts)
+        finally:
+            self._form = self.haas._form = form
+        host = down.cpu().numpy()
+        self.transfers['to_host'] = 1
+        return host[:y_bytes].view(np.float64).reshape(S, self.row_frames, 2), host[y_bytes:].view(np.int32)
+
+    def _call_device(self, torch, x, counts, flags, tables, delays, y, out_counts):
+        ctx = _native.default_context()
+        self._ensure_state(torch, ctx)
+        self.haas._ensure_state(torch, ctx)
+        mid, mid_counts = self._mid
+        VoicePool._call_device(self, torch, x, counts, flags, tables, mid, mid_counts)
+        return self.haas._call_device(torch, mid, mid_counts, flags, delays, y, out_counts)
