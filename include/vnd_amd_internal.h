@@ -91,6 +91,13 @@ vnd_status vnd_describe_each_stream_launch(vnd_ctx *ctx, const vnd_taps *bank, i
  * advance_groups (the workgroups of the kernel that advances the positions, one lane per slot).                          */
 vnd_status vnd_describe_voice_stream_launch(vnd_ctx *ctx, const vnd_taps *bank, int64_t max_frames_per_call, int64_t slots,
                                             int32_t in_channels, int32_t mode, int32_t epilogue, char *text, int32_t len);
+/* Diagnosis: the launch every vnd_correlogram_voice_stream_*_dev call (include/vnd_correlogram_voice_stream.h) on a pool with
+ * these sizes takes - the pool's own scalar checks and planner, no context, no pointers, no device work - as one line of
+ * key=value fields: rows_per_call (RC = ceil(max_frames_per_call / hop)), groups (window groups of 4 rows per slot), tiles
+ * (column tiles of 1024 lags), nblocks (slots x groups x tiles), threads, advance_groups (the workgroups of the kernel that
+ * advances the positions, one lane per slot).                                                                           */
+vnd_status vnd_describe_correlogram_voice_stream_launch(int64_t slots, int32_t window, int32_t hop, int32_t num_lags,
+                                                        int64_t max_frames_per_call, char *text, int32_t len);
 /* Diagnosis (tests): vnd_decorrelate_fanout_f32_dev (in_channels == the table's channels: vnd_decorrelate_f32_dev), and which of the
  * stage's forms ran, in taken[4]: [0] 0 the table-order launch with the pointwise steps and the sums as passes of their own, 1 the
  * fast kernel with the pointwise steps (and, with VND_NORMALIZE_RMS, the sums) fused into its store phase, 2 the quad / octet kernel

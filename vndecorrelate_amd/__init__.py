@@ -29,7 +29,13 @@ from .decorrelation import (  # noqa: F401
     set_each_device,
     set_white_noise_device,
 )
-from .analysis import cross_correlogram_batched, set_correlogram_device  # noqa: F401
+from .analysis import (  # noqa: F401
+    CorrelogramVoicePool,
+    correlogram_voice_spans,
+    cross_correlogram_batched,
+    cross_correlogram_voice_pool,
+    set_correlogram_device,
+)
 from .streaming import (  # noqa: F401
     ChainStream,
     ChainVoicePool,

@@ -147,6 +147,9 @@ INTERNAL_SIGNATURES = {
     'vnd_describe_voice_stream_launch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                                         ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p,
                                                         ctypes.c_int32]),
+    'vnd_describe_correlogram_voice_stream_launch': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                                    ctypes.c_int32, ctypes.c_int64, ctypes.c_char_p,
+                                                                    ctypes.c_int32]),
     'vnd_debug_decorrelate_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                      ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                                      ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
@@ -312,6 +315,22 @@ HAAS_VOICE_STREAM_SIGNATURES = {
     'vnd_haas_voice_stream_f64_host': (ctypes.c_int, _HAAS_VOICE_STREAM_ARGS),
 }
 
+# include/vnd_correlogram_voice_stream.h: the cross-correlogram of a voice pool - positions in the device state, counts and
+# flags per slot and call, float32 or float64 chunks
+_CORRELOGRAM_VOICE_STREAM_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                                  ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                  ctypes.c_int32, ctypes.c_float, ctypes.c_void_p]
+CORRELOGRAM_VOICE_STREAM_SIGNATURES = {
+    'vnd_correlogram_voice_stream_state_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
+                                                                ctypes.POINTER(ctypes.c_int64)]),
+    'vnd_correlogram_voice_stream_reset_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                              ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
+                                                              ctypes.c_void_p]),
+    'vnd_correlogram_voice_stream_f32_dev': (ctypes.c_int, _CORRELOGRAM_VOICE_STREAM_ARGS),
+    'vnd_correlogram_voice_stream_f64_dev': (ctypes.c_int, _CORRELOGRAM_VOICE_STREAM_ARGS),
+}
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -365,7 +384,8 @@ def load_library():
                                   + list(VELVET_SEARCH_SIGNATURES.items())
                                   + list(EACH_SIGNATURES.items()) + list(EACH_STREAM_SIGNATURES.items())
                                   + list(VOICE_STREAM_SIGNATURES.items())
-                                  + list(HAAS_VOICE_STREAM_SIGNATURES.items())):
+                                  + list(HAAS_VOICE_STREAM_SIGNATURES.items())
+                                  + list(CORRELOGRAM_VOICE_STREAM_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -860,6 +880,49 @@ def correlogram_stream_device(ctx: 'Context', state_ptr: int, state_bytes: int, 
         ctypes.c_void_p(y_ptr), stream_stride, frame_stride, ctypes.c_void_p(out_ptr), batch, position, n_in, window, hop,
         num_lags, float(eps), ctypes.byref(rows), ctypes.c_void_p(stream)), 'vnd_correlogram_stream_f32_dev')
     return rows.value
+
+
+def correlogram_voice_stream_state_bytes(slots: int, window: int, max_frames_per_call: int) -> int:
+    """``vnd_correlogram_voice_stream_state_bytes``: one int64 position per slot (padded to 16 bytes), then the ring of a
+    pool of ``slots`` voices."""
+    need = ctypes.c_int64()
+    _check(load_library().vnd_correlogram_voice_stream_state_bytes(slots, window, max_frames_per_call, ctypes.byref(need)),
+           'vnd_correlogram_voice_stream_state_bytes')
+    return need.value
+
+
+def correlogram_voice_stream_reset_device(ctx: 'Context', state_ptr: int, state_bytes: int, slots: int, window: int,
+                                          max_frames_per_call: int, *, stream: int = 0):
+    """``vnd_correlogram_voice_stream_reset_dev``: every position of the pool to 0, enqueued on ``stream``; the ring is
+    left alone."""
+    _check(ctx._lib.vnd_correlogram_voice_stream_reset_dev(ctx.handle, ctypes.c_void_p(state_ptr), state_bytes, slots, window,
+                                                           max_frames_per_call, ctypes.c_void_p(stream)),
+           'vnd_correlogram_voice_stream_reset_dev')
+
+
+def correlogram_voice_stream_device(ctx: 'Context', state_ptr: int, state_bytes: int, max_frames_per_call: int, x_ptr: int,
+                                    y_ptr: int, stream_stride: int, frame_stride: int, counts_ptr: int, flags_ptr: int,
+                                    out_ptr: int, out_counts_ptr: int, slots: int, *, window: int, hop: int, num_lags: int,
+                                    eps: float, float64: bool = False, stream: int = 0):
+    """``vnd_correlogram_voice_stream_f32_dev`` (``_f64_dev`` with ``float64``): one call of a correlogram voice pool.
+    Frame t of slot b at ``b * stream_stride + t * frame_stride`` elements of ``x_ptr`` / ``y_ptr``, int32 ``(slots,)``
+    counts and flags (``VOICE_START``, ``VOICE_END``), the float32 ``(slots, rows_per_call, num_lags)`` result and the
+    int32 ``out_counts``, all device memory, enqueued on ``stream``."""
+    name = 'vnd_correlogram_voice_stream_f64_dev' if float64 else 'vnd_correlogram_voice_stream_f32_dev'
+    _check(getattr(ctx._lib, name)(
+        ctx.handle, ctypes.c_void_p(state_ptr), state_bytes, max_frames_per_call, ctypes.c_void_p(x_ptr),
+        ctypes.c_void_p(y_ptr), stream_stride, frame_stride, ctypes.c_void_p(counts_ptr), ctypes.c_void_p(flags_ptr),
+        ctypes.c_void_p(out_ptr), ctypes.c_void_p(out_counts_ptr), slots, window, hop, num_lags, float(eps),
+        ctypes.c_void_p(stream)), name)
+
+
+def describe_correlogram_voice_stream(slots: int, window: int, hop: int, num_lags: int, max_frames_per_call: int) -> str:
+    """The fixed launch of a correlogram voice pool (``vnd_describe_correlogram_voice_stream_launch``):
+    ``rows_per_call=``, ``groups=``, ``tiles=``, ``nblocks=``, ``advance_groups=`` among its fields."""
+    buf = ctypes.create_string_buffer(512)
+    _check(load_library().vnd_describe_correlogram_voice_stream_launch(slots, window, hop, num_lags, max_frames_per_call, buf,
+                                                                      512), 'vnd_describe_correlogram_voice_stream_launch')
+    return buf.value.decode()
 
 
 def haas_scan_workspace_bytes(n: int, n_delays: int, max_delay: int) -> int:

@@ -9,7 +9,10 @@ The reference measures decorrelation with ``utils/dsp.py:313`` ``cross_correlogr
 * :func:`set_correlogram_device` and the pure routing rule :func:`correlogram_covers`; :func:`device_route`, the
   rule of every ``set_*_device`` switch of the package;
 * :func:`cross_correlogram_stream` - the same rows, block by block, for a pool of live streams
-  (``include/vnd_correlogram_stream.h``): a :class:`CorrelogramStream`.
+  (``include/vnd_correlogram_stream.h``): a :class:`CorrelogramStream`;
+* :func:`cross_correlogram_voice_pool` - the same rows for a pool of voices that start, end and push blocks of their own
+  sizes (``include/vnd_correlogram_voice_stream.h``): a :class:`CorrelogramVoicePool`, which meters a
+  ``decorrelate_voice_pool`` on the device; :func:`correlogram_voice_spans` is the device's mirror.
 
 Numerics: each correlation output is one float64 FMA chain over exact products, rounded once; the
 energies are float64 sums rounded once; the normaliser is NumPy 2's float32 arithmetic.  The result is within one
@@ -23,7 +26,8 @@ from typing import Optional
 import numpy as np
 
 from . import _native
-from .streaming import BlockStream
+from .streaming import (VOICE_END, VOICE_MAX_POSITION, VOICE_START, BlockStream, _check_counts, _check_device_tensors,
+                        _SlotPool)
 from .utils.dsp import EPSILON, correlogram_sizes, to_float32
 
 MAX_WINDOW = _native.CORRELOGRAM_MAX_WINDOW
@@ -337,5 +341,228 @@ def cross_correlogram_stream(num_streams: int = 1, *, sample_rate_hz: int = 4410
                              max_frames_per_call=max_frames_per_call)
 
 
+# ----------------------------------------------------------------------------
+# The correlogram of a voice pool   (include/vnd_correlogram_voice_stream.h)
+# ----------------------------------------------------------------------------
+def correlogram_voice_spans(positions, counts, flags, window: int, hop: int, max_frames_per_call: Optional[int] = None):
+    """``(out_counts, new_positions)`` of one call of a correlogram voice pool
+    (``include/vnd_correlogram_voice_stream.h``), per slot, from the positions before the call, the frames pushed and the
+    ``VOICE_START`` / ``VOICE_END`` flags alone - what the device computes from its own state::
+
+        p = START ? 0 : position        wc(q) = (q - W) // H + 1 if q >= W else 0
+        out_count = wc(p + n) - wc(p)   new position = END ? 0 : p + n
+
+    A count below 0 (or above ``max_frames_per_call``, when given), or without START a position outside ``[0, 2^60]``,
+    answers -1 and leaves the position as it was."""
+    pos = np.asarray(positions, np.int64)
+    n = np.asarray(counts, np.int64)
+    f = np.asarray(flags, np.int64)
+    if not (pos.shape == n.shape == f.shape):
+        raise ValueError(f'positions, counts and flags of one shape, got {pos.shape}, {n.shape}, {f.shape}')
+    W, H = int(window), int(hop)
+    if W < 1 or H < 1:
+        raise ValueError(f'window and hop must be >= 1, got {window} and {hop}')
+    start, end = (f & VOICE_START) != 0, (f & VOICE_END) != 0
+    p = np.where(start, 0, pos)
+    bad = (n < 0) | (p < 0) | (p > VOICE_MAX_POSITION)
+    if max_frames_per_call is not None:
+        bad |= n > int(max_frames_per_call)
+    p, n = np.where(bad, 0, p), np.where(bad, 0, n)          # (no arithmetic on a bad value)
+
+    def complete(q):
+        return np.where(q >= W, (q - W) // H + 1, 0)
+    out = np.where(bad, -1, complete(p + n) - complete(p)).astype(np.int64)
+    new = np.where(bad, pos, np.where(end, 0, p + n)).astype(np.int64)
+    return out, new
+
+
+class CorrelogramVoicePool(_SlotPool):
+    """``cross_correlogram`` of ``slots`` voices, each with a life of its own (:func:`cross_correlogram_voice_pool`,
+    ``vnd_correlogram_voice_stream_*_dev``): voices start and end on any call and push blocks of any size up to
+    ``max_frames_per_call`` or none.  The position lives in the device state, one per slot, so a call is a pure function
+    of device memory.  A call returns, per slot, the rows of the windows that became final - at most ``rows_per_call`` -
+    and for every voice the concatenation of its rows, from its start up to and including its end, equals
+    :func:`cross_correlogram_batched` of its whole signal bit for bit.  Windows that never complete are dropped, as in the
+    reference: an end has no tail.
+
+    Two forms; a pool is used through one of them (mixing them raises ``RuntimeError`` until ``reset()``):
+
+    * ``process({slot: block}, start=[slot, ...], end=[slot, ...], discard=False)`` - float32 or float64 NumPy blocks
+      ``(n, 2)`` in (channel 0 against channel 1; float64 is cast as ``cross_correlogram`` casts it),
+      ``{slot: float32 (rows, num_lags)}`` out for every slot that got a block or ended.  One upload and one download
+      (``transfers`` counts those of the last call); every refusal comes before any device call.
+    * ``process_dev(x, counts, flags, *, out=None)`` - ``x`` ``(slots, max_frames_per_call, 2)`` of the pool's ``dtype``
+      and int32 ``(slots,)`` ``counts`` and ``flags`` on the device; returns ``(rows, out_counts)``.  It only enqueues on
+      the current stream and can be captured with ``torch.cuda.graph`` after a ``reset()``.  To meter a decorrelating
+      pool, build the meter with ``max_frames_per_call=pool.row_frames`` (and ``dtype='float64'`` for a Haas or chain
+      pool) and hand it that pool's ``y`` and ``out_counts`` and the caller's ``flags``: a -1 of the pool is a bad count
+      here and answers -1.  A float64 sample is cast to float32 inside the kernel, round to nearest even."""
+
+    in_channels = 2
+    _out_dtype = np.float32
+
+    def __init__(self, slots: int, *, window: int, hop: int, num_lags: int, epsilon, max_frames_per_call: int,
+                 dtype='float32'):
+        _check_counts(slots=slots, max_frames_per_call=max_frames_per_call)
+        if slots > _native.MAX_STREAMS_PER_CALL:
+            raise ValueError(f'slots {slots} above {_native.MAX_STREAMS_PER_CALL}: split the pool')
+        if max_frames_per_call > _INT32_MAX:
+            raise ValueError(f'max_frames_per_call {max_frames_per_call} above 2**31 - 1: counts are int32')
+        if not correlogram_covers(0, window, hop, num_lags, epsilon):
+            raise ValueError(f'window {window}, hop {hop}, {num_lags} lags and epsilon {epsilon!r} have no device form '
+                             f'(correlogram_covers is False) and the pool has no NumPy one: use cross_correlogram')
+        try:
+            self.dtype = None if dtype is None else np.dtype(dtype)
+        except TypeError:
+            self.dtype = None
+        if self.dtype is None or self.dtype.name not in ('float32', 'float64'):      # (np.dtype(None) is float64)
+            raise ValueError(f"dtype must be 'float32' or 'float64', got {dtype!r}")
+        self.slots, self.max_frames_per_call = int(slots), int(max_frames_per_call)
+        self.window, self.hop, self.num_lags, self.epsilon = int(window), int(hop), int(num_lags), epsilon
+        # the fixed grid of the pool (include/vnd_correlogram_voice_stream.h): window groups of 4 rows x column tiles of
+        # 1024 lags per slot, one grid dimension; 2^23 workgroups a launch
+        groups, tiles = -(-self.rows_per_call // 4), -(-self.num_lags // 1024)
+        if groups * tiles > 65535 or self.slots * groups * tiles > 1 << 23 \
+                or self.slots * self.rows_per_call * self.num_lags > 1 << 40:
+            raise ValueError(f'{self.slots} slots of {self.rows_per_call} rows of {self.num_lags} lags per call are more than '
+                             f'one launch takes: raise the stride or lower max_frames_per_call')
+        self.transfers = {'to_device': 0, 'to_host': 0}
+        self._state = None                    # (torch uint8 tensor, bytes)
+        self._mirror()
+
+    @property
+    def rows_per_call(self) -> int:
+        """RC: the most rows a call returns per slot, ``ceil(max_frames_per_call / hop)``."""
+        return -(-self.max_frames_per_call // self.hop)
+
+    @property
+    def _out_width(self) -> int:
+        return self.num_lags
+
+    def process(self, blocks=None, *, start=(), end=(), discard: bool = False):
+        """One call of the dict form.  ``blocks``: ``{slot: (n, 2) float32 or float64 array}``,
+        ``0 <= n <= max_frames_per_call``; ``start``: the slots whose voice begins with this call; ``end``: the slots whose
+        voice ends with it.  Returns ``{slot: float32 (rows, num_lags)}`` for every slot that got a block or ended.  Raises
+        before any device call, as the other voice pools do: ``ValueError`` for a slot outside the pool or named twice, a
+        block or an end for a slot that was never started, a start on a live slot (``discard=True`` allows it: the voice
+        it held is dropped), a block above ``max_frames_per_call`` or not ``(n, 2)``; ``TypeError`` for a block that is
+        neither float32 nor float64."""
+        if self._form == 'dev':
+            raise RuntimeError('this pool runs through process_dev(): the host does not know its positions; reset() first')
+        starts = {}
+        for slot in list(start or ()):
+            slot = self._slot(slot, 'start')
+            if slot in starts:
+                raise ValueError(f'start: slot {slot} is named twice')
+            starts[slot] = 0
+        cast = {}
+        for slot, block in dict(blocks or {}).items():
+            a = np.asarray(block)
+            cast[slot] = to_float32(a) if a.dtype == np.float64 else a
+        return _SlotPool.process(self, cast, start=starts, end=end, discard=discard)
+
+    def process_dev(self, x, counts, flags, *, out=None):
+        """One call on device tensors, enqueued on the current stream: ``x`` ``(slots, M, 2)`` of the pool's dtype,
+        ``counts`` / ``flags`` int32 ``(slots,)``.  Returns ``(rows, out_counts)``: float32
+        ``(slots, rows_per_call, num_lags)`` - the first ``out_counts[b]`` rows of row-block b are written, nothing at or
+        past them - and int32 ``(slots,)``; ``out=(rows, out_counts)`` takes the caller's.  No check reads device memory;
+        bad per-slot values answer -1 (``include/vnd_correlogram_voice_stream.h``)."""
+        if self._form == 'dict':
+            raise RuntimeError('this pool runs through process(): mixing in process_dev() would leave the host mirror '
+                               'of the positions stale; reset() first')
+        S, M = self.slots, self.max_frames_per_call
+        rows, out_counts = out if out is not None else (None, None)
+        _check_device_tensors((('x', x, (S, M, 2), self.dtype.name, False), ('counts', counts, (S,), 'int32', False),
+                               ('flags', flags, (S,), 'int32', False),
+                               ('rows', rows, (S, self.rows_per_call, self.num_lags), 'float32', True),
+                               ('out_counts', out_counts, (S,), 'int32', True)))
+        return self._call_device(_torch(), x, counts, flags, rows, out_counts, self.dtype == np.float64)
+
+    # ---- what _SlotPool asks for ---------------------------------------------------------------
+    def _spans(self, counts, flags, tables):
+        return correlogram_voice_spans(self.positions, counts, flags, self.window, self.hop, self.max_frames_per_call)
+
+    def _per_slot(self, tables):
+        return ()
+
+    def _bank_len(self) -> int:
+        return 1                                  # a voice starts with nothing of its own: the pool has one setting
+
+    def _slot_value(self, index: int):
+        return 0
+
+    # ---- the device -------------------------------------------------------------------------
+    def _allocate(self, torch, ctx):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('the state of a voice pool is allocated and zeroed on first use: call reset() before the capture')
+        need = _native.correlogram_voice_stream_state_bytes(self.slots, self.window, self.max_frames_per_call)
+        buf = torch.empty((need,), dtype=torch.uint8, device=torch.device('cuda', ctx.device))
+        self._state = (buf, need)
+        self._reset_device(torch, ctx)
+
+    def _reset_device(self, torch, ctx):
+        state, state_bytes = self._state
+        _native.correlogram_voice_stream_reset_device(ctx, state.data_ptr(), state_bytes, self.slots, self.window,
+                                                      self.max_frames_per_call,
+                                                      stream=torch.cuda.current_stream(state.device).cuda_stream)
+
+    def _call_host(self, x, counts, flags):
+        """One upload (the blocks and the two int32 arrays in one buffer), the call, one download (rows and out_counts)."""
+        torch = _torch()
+        ctx = _native.default_context()
+        device = torch.device('cuda', ctx.device)
+        S = self.slots
+        ints = np.stack([counts, flags]).astype(np.int32)
+        up = torch.from_numpy(np.concatenate([x.reshape(-1).view(np.uint8), ints.reshape(-1).view(np.uint8)])).to(device)
+        self.transfers = {'to_device': 1, 'to_host': 0}
+        x_dev = up[:x.nbytes].view(torch.float32).view(x.shape)
+        c, f = up[x.nbytes:].view(torch.int32).view(2, S)
+        r_bytes = S * self.rows_per_call * self.num_lags * 4
+        down = torch.empty((r_bytes + 4 * S,), dtype=torch.uint8, device=device)
+        rows = down[:r_bytes].view(torch.float32).view(S, self.rows_per_call, self.num_lags)
+        out_counts = down[r_bytes:].view(torch.int32)
+        form = self._form
+        try:
+            self._call_device(torch, x_dev, c, f, rows, out_counts, False)
+        finally:
+            self._form = form
+        host = down.cpu().numpy()
+        self.transfers['to_host'] = 1
+        return host[:r_bytes].view(np.float32).reshape(S, self.rows_per_call, self.num_lags), host[r_bytes:].view(np.int32)
+
+    def _call_device(self, torch, x, counts, flags, rows, out_counts, float64: bool):
+        ctx = _native.default_context()
+        device = torch.device('cuda', ctx.device)
+        for t in (x, counts, flags):
+            if t.device != device:
+                raise ValueError(f'tensor on {t.device}, the pool runs on {device}')
+        state, state_bytes = self._ensure_state(torch, ctx)
+        if rows is None:
+            rows = torch.empty((self.slots, self.rows_per_call, self.num_lags), dtype=torch.float32, device=device)
+        if out_counts is None:
+            out_counts = torch.empty((self.slots,), dtype=torch.int32, device=device)
+        self._form = 'dev'
+        _native.correlogram_voice_stream_device(
+            ctx, state.data_ptr(), state_bytes, self.max_frames_per_call, x.data_ptr(), x.data_ptr() + x.element_size(),
+            2 * self.max_frames_per_call, 2, counts.data_ptr(), flags.data_ptr(), rows.data_ptr(), out_counts.data_ptr(),
+            self.slots, window=self.window, hop=self.hop, num_lags=self.num_lags, eps=float(self.epsilon), float64=float64,
+            stream=torch.cuda.current_stream(device).cuda_stream)
+        return rows, out_counts
+
+
+def cross_correlogram_voice_pool(slots: int, *, sample_rate_hz: int = 44100, max_lag_seconds: float = 0.02,
+                                 window_size_seconds: float = 0.02, stride_seconds: float = 0.01, epsilon: float = EPSILON,
+                                 max_frames_per_call: int = 4800, dtype='float32') -> CorrelogramVoicePool:
+    """A :class:`CorrelogramVoicePool`: ``cross_correlogram`` with these arguments for ``slots`` voices that start, end
+    and push blocks on their own, the positions in device memory.  The sizes come from ``correlogram_sizes`` as for the
+    one-shot call.  Sizes the device does not cover (:func:`correlogram_covers`), pools above ``MAX_STREAMS_PER_CALL`` and
+    a ``dtype`` other than ``'float32'`` / ``'float64'`` raise ``ValueError`` here: there is no NumPy pool.
+    ``set_correlogram_device`` is not consulted."""
+    window, hop, max_lag = correlogram_sizes(sample_rate_hz, max_lag_seconds, window_size_seconds, stride_seconds)
+    return CorrelogramVoicePool(slots, window=window, hop=hop, num_lags=2 * max_lag + 1, epsilon=epsilon,
+                                max_frames_per_call=max_frames_per_call, dtype=dtype)
+
+
 __all__ = ['cross_correlogram_batched', 'cross_correlogram_stream', 'CorrelogramStream', 'correlogram_covers',
-           'set_correlogram_device', 'MAX_WINDOW']
+           'set_correlogram_device', 'MAX_WINDOW', 'cross_correlogram_voice_pool', 'CorrelogramVoicePool',
+           'correlogram_voice_spans']

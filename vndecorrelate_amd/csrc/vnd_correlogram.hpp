@@ -46,6 +46,13 @@ struct CgArgs {
 // run.x(i) and run.y(i), i in [0, W).  slot0 is the ring slot of the window's first frame
 // (slot0_of(a, ww): one 64-bit modulo per window, not per sample); a source without a ring ignores it.  prologue(a, b)
 // runs first in every workgroup; false ends the workgroup.
+// What the body takes from the launch comes through the source too: view(args) is what every other hook is handed - the
+// kernel's arguments themselves for a source whose launch is uniform, a per-workgroup copy built from device memory for
+// one whose is not (vnd_correlogram_voice_stream.hpp) - cg(view) carries the row count (windows) and the base of the
+// rows (out) the workgroup writes, and stream / group / tile are its coordinates.
+__device__ __forceinline__ int64_t cg_grid_group(const CgArgs &a) { return a.group0 + blockIdx.x / (unsigned)a.tiles; }
+__device__ __forceinline__ int cg_grid_tile(const CgArgs &a) { return (int)(blockIdx.x % (unsigned)a.tiles); }
+
 struct CgSignal {                               // the one-shot call: x[b * stream_stride + f * frame_stride]
     using Args = CgArgs;
     static constexpr bool kRing = false;
@@ -56,7 +63,12 @@ struct CgSignal {                               // the one-shot call: x[b * stre
         __device__ __forceinline__ float x(int i) const { return px[bs + (f0 + i) * (int64_t)fs]; }
         __device__ __forceinline__ float y(int i) const { return py[bs + (f0 + i) * (int64_t)fs]; }
     };
+    using View = const Args &;
+    __device__ static __forceinline__ View view(const Args &a) { return a; }
     __device__ static __forceinline__ const CgArgs &cg(const Args &a) { return a; }
+    __device__ static __forceinline__ int64_t stream(const Args &) { return blockIdx.y; }
+    __device__ static __forceinline__ int64_t group(const Args &a) { return cg_grid_group(a); }
+    __device__ static __forceinline__ int tile(const Args &a) { return cg_grid_tile(a); }
     __device__ static __forceinline__ bool prologue(const Args &, int64_t) { return true; }
     __device__ static __forceinline__ int64_t slot0_of(const Args &, int64_t) { return 0; }
     __device__ static __forceinline__ Run run(const Args &a, int64_t b, int64_t ww, int64_t)
@@ -91,17 +103,18 @@ __device__ __forceinline__ void cg_block(double (&acc)[kCgR], const double (&lo)
 }
 
 template <class Src>
-__global__ __launch_bounds__(kCgThreads) void correlogram_kernel(const typename Src::Args sa)
+__global__ __launch_bounds__(kCgThreads) void correlogram_kernel(const typename Src::Args args)
 {
+    typename Src::View sa = Src::view(args);
     const CgArgs &a = Src::cg(sa);
     __shared__ __align__(16) float xs[kCgG][kCgTile + kCgTaps];
     __shared__ __align__(16) double hs[kCgG][kCgTaps];
     __shared__ float en[kCgG][2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g = lane >> 4;                                    // the lane's window in the group
-    const int64_t group = a.group0 + blockIdx.x / (unsigned)a.tiles;
-    const int T0 = (int)(blockIdx.x % (unsigned)a.tiles) * kCgTile;
-    const int64_t b = blockIdx.y;
+    const int64_t group = Src::group(sa);
+    const int T0 = Src::tile(sa) * kCgTile;
+    const int64_t b = Src::stream(sa);
     const int64_t w = group * kCgG + g;                         // the lane's window
     const int t0 = wave * kCgSpan + (lane & 15) * kCgR;         // the lane's first column, relative to T0
     const int W = a.W;

@@ -53,7 +53,12 @@ struct CgRing {
             return r >= 0 ? py[r * fs] : ring[slot(i)].y;
         }
     };
+    using View = const Args &;
+    __device__ static __forceinline__ View view(const Args &a) { return a; }
     __device__ static __forceinline__ const CgArgs &cg(const Args &a) { return a.cg; }
+    __device__ static __forceinline__ int64_t stream(const Args &) { return blockIdx.y; }
+    __device__ static __forceinline__ int64_t group(const Args &a) { return cg_grid_group(a.cg); }
+    __device__ static __forceinline__ int tile(const Args &a) { return cg_grid_tile(a.cg); }
     __device__ static __forceinline__ int64_t first_frame(const Args &a, int64_t ww) { return (a.w0 + ww) * a.cg.hop; }
     __device__ static __forceinline__ int64_t slot0_of(const Args &a, int64_t ww) { return first_frame(a, ww) % a.cap; }
     __device__ static __forceinline__ Run run(const Args &a, int64_t b, int64_t ww, int64_t slot0)

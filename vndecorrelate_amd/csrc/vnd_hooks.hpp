@@ -278,4 +278,19 @@ vnd_status vnd_describe_voice_stream_launch(vnd_ctx *ctx, const vnd_taps *t, int
     return VND_OK;
 }
 
+// The fixed launch of every vnd_correlogram_voice_stream_*_dev call on a pool with these sizes: the pool's own scalar checks
+// and cg_voice_plan, the launch's own.  No pointers, no device work.
+vnd_status vnd_describe_correlogram_voice_stream_launch(int64_t slots, int32_t window, int32_t hop, int32_t num_lags,
+                                                        int64_t max_frames_per_call, char *text, int32_t len)
+{
+    if (!text || len <= 0) return fail(VND_ERR_INVALID, "null text buffer");
+    CgVoicePlan p{};
+    vnd_status st = cg_voice_plan(slots, window, hop, num_lags, max_frames_per_call, &p);
+    if (st != VND_OK) return st;
+    snprintf(text, (size_t)len, "correlogram_voice_stream rows_per_call=%lld groups=%lld tiles=%lld nblocks=%lld threads=%d advance_groups=%lld",
+             (long long)p.rc, (long long)p.groups, (long long)p.tiles, (long long)p.workgroups, kCgThreads,
+             (long long)p.advance_groups);
+    return VND_OK;
+}
+
 }  // extern "C"

@@ -665,7 +665,7 @@ class _SlotPool:
             raise RuntimeError('this pool runs through process_dev(): the host does not know its positions; reset() first')
         counts, flags, tables, live, x, answered = self._schedule(blocks, start, end, discard)
         if not counts.any() and not flags.any():              # nothing pushed, started or ended: no device call
-            return {slot: np.zeros((0, 2), self._out_dtype) for slot in answered}
+            return {slot: np.zeros((0, self._out_width), self._out_dtype) for slot in answered}
         want, positions = self._spans(counts, flags, tables)
         y, got = self._call_host(x, counts, flags, *self._per_slot(tables))
         if not np.array_equal(np.asarray(got, np.int64), want):
@@ -678,6 +678,7 @@ class _SlotPool:
 
     # ---- what a pool supplies ------------------------------------------------------------------
     _out_dtype = np.float32
+    _out_width = 2                            # the last axis of what a slot returns
 
     def _spans(self, counts, flags, tables):
         """``(out_counts, new positions)`` of the call, from the host mirror."""
