@@ -31,10 +31,14 @@ from .decorrelation import (  # noqa: F401
 )
 from .analysis import (  # noqa: F401
     CorrelogramVoicePool,
+    PolarVoicePool,
     correlogram_voice_spans,
     cross_correlogram_batched,
     cross_correlogram_voice_pool,
+    polar_moments_ordered,
+    polar_voice_spans,
     set_correlogram_device,
+    stereo_image_voice_pool,
 )
 from .streaming import (  # noqa: F401
     ChainStream,

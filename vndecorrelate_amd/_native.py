@@ -150,6 +150,8 @@ INTERNAL_SIGNATURES = {
     'vnd_describe_correlogram_voice_stream_launch': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                                                     ctypes.c_int32, ctypes.c_int64, ctypes.c_char_p,
                                                                     ctypes.c_int32]),
+    'vnd_describe_polar_voice_stream_launch': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                                              ctypes.c_char_p, ctypes.c_int32]),
     'vnd_debug_decorrelate_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                      ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                                      ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
@@ -331,6 +333,20 @@ CORRELOGRAM_VOICE_STREAM_SIGNATURES = {
     'vnd_correlogram_voice_stream_f64_dev': (ctypes.c_int, _CORRELOGRAM_VOICE_STREAM_ARGS),
 }
 
+# include/vnd_polar_voice_stream.h: the eight polar moments of a voice pool - positions, reduce-lane sums and the incomplete
+# chunk's frames in the device state, counts and flags per slot and call, float32 or float64 chunks
+_POLAR_VOICE_STREAM_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+POLAR_VOICE_STREAM_SIGNATURES = {
+    'vnd_polar_voice_stream_state_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                                          ctypes.POINTER(ctypes.c_int64)]),
+    'vnd_polar_voice_stream_reset_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                        ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p]),
+    'vnd_polar_voice_stream_f32_dev': (ctypes.c_int, _POLAR_VOICE_STREAM_ARGS),
+    'vnd_polar_voice_stream_f64_dev': (ctypes.c_int, _POLAR_VOICE_STREAM_ARGS),
+}
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -385,7 +401,8 @@ def load_library():
                                   + list(EACH_SIGNATURES.items()) + list(EACH_STREAM_SIGNATURES.items())
                                   + list(VOICE_STREAM_SIGNATURES.items())
                                   + list(HAAS_VOICE_STREAM_SIGNATURES.items())
-                                  + list(CORRELOGRAM_VOICE_STREAM_SIGNATURES.items())):
+                                  + list(CORRELOGRAM_VOICE_STREAM_SIGNATURES.items())
+                                  + list(POLAR_VOICE_STREAM_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -922,6 +939,47 @@ def describe_correlogram_voice_stream(slots: int, window: int, hop: int, num_lag
     buf = ctypes.create_string_buffer(512)
     _check(load_library().vnd_describe_correlogram_voice_stream_launch(slots, window, hop, num_lags, max_frames_per_call, buf,
                                                                       512), 'vnd_describe_correlogram_voice_stream_launch')
+    return buf.value.decode()
+
+
+def polar_voice_stream_state_bytes(slots: int, max_frames_per_call: int, sample_bytes: int = 4) -> int:
+    """``vnd_polar_voice_stream_state_bytes``: the positions, the reduce-lane sums, the partials of one call and the ring of
+    a pool of ``slots`` voices; ``sample_bytes`` 4 for float32 frames, 8 for float64."""
+    need = ctypes.c_int64()
+    _check(load_library().vnd_polar_voice_stream_state_bytes(slots, max_frames_per_call, sample_bytes, ctypes.byref(need)),
+           'vnd_polar_voice_stream_state_bytes')
+    return need.value
+
+
+def polar_voice_stream_reset_device(ctx: 'Context', state_ptr: int, state_bytes: int, slots: int, max_frames_per_call: int,
+                                    sample_bytes: int = 4, *, stream: int = 0):
+    """``vnd_polar_voice_stream_reset_dev``: every position of the pool to 0, enqueued on ``stream``; sums and ring are left
+    alone."""
+    _check(ctx._lib.vnd_polar_voice_stream_reset_dev(ctx.handle, ctypes.c_void_p(state_ptr), state_bytes, slots,
+                                                     max_frames_per_call, sample_bytes, ctypes.c_void_p(stream)),
+           'vnd_polar_voice_stream_reset_dev')
+
+
+def polar_voice_stream_device(ctx: 'Context', state_ptr: int, state_bytes: int, max_frames_per_call: int, l_ptr: int,
+                              r_ptr: int, stream_stride: int, frame_stride: int, counts_ptr: int, flags_ptr: int,
+                              moments_ptr: int, valid_ptr: int, slots: int, *, float64: bool = False, stream: int = 0):
+    """``vnd_polar_voice_stream_f32_dev`` (``_f64_dev`` with ``float64``): one call of a polar-moments voice pool.  Frame t
+    of slot b at ``b * stream_stride + t * frame_stride`` elements of ``l_ptr`` / ``r_ptr``, int32 ``(slots,)`` counts and
+    flags (``VOICE_START``, ``VOICE_END``), the float64 ``(slots, 8)`` moments and the int32 ``valid``, all device memory,
+    enqueued on ``stream``."""
+    name = 'vnd_polar_voice_stream_f64_dev' if float64 else 'vnd_polar_voice_stream_f32_dev'
+    _check(getattr(ctx._lib, name)(
+        ctx.handle, ctypes.c_void_p(state_ptr), state_bytes, max_frames_per_call, ctypes.c_void_p(l_ptr),
+        ctypes.c_void_p(r_ptr), stream_stride, frame_stride, ctypes.c_void_p(counts_ptr), ctypes.c_void_p(flags_ptr),
+        ctypes.c_void_p(moments_ptr), ctypes.c_void_p(valid_ptr), slots, ctypes.c_void_p(stream)), name)
+
+
+def describe_polar_voice_stream(slots: int, max_frames_per_call: int, sample_bytes: int = 4) -> str:
+    """The fixed launch of a polar-moments voice pool (``vnd_describe_polar_voice_stream_launch``): ``groups=``,
+    ``nblocks=``, ``finish_groups=``, ``threads=`` and ``state_bytes=``."""
+    buf = ctypes.create_string_buffer(512)
+    _check(load_library().vnd_describe_polar_voice_stream_launch(slots, max_frames_per_call, sample_bytes, buf, 512),
+           'vnd_describe_polar_voice_stream_launch')
     return buf.value.decode()
 
 

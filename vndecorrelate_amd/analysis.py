@@ -12,7 +12,10 @@ The reference measures decorrelation with ``utils/dsp.py:313`` ``cross_correlogr
   (``include/vnd_correlogram_stream.h``): a :class:`CorrelogramStream`;
 * :func:`cross_correlogram_voice_pool` - the same rows for a pool of voices that start, end and push blocks of their own
   sizes (``include/vnd_correlogram_voice_stream.h``): a :class:`CorrelogramVoicePool`, which meters a
-  ``decorrelate_voice_pool`` on the device; :func:`correlogram_voice_spans` is the device's mirror.
+  ``decorrelate_voice_pool`` on the device; :func:`correlogram_voice_spans` is the device's mirror;
+* :func:`stereo_image_voice_pool` - the eight polar moments behind ``symmetry_aware_objective`` for such a pool of voices
+  (``include/vnd_polar_voice_stream.h``): a :class:`PolarVoicePool`; :func:`polar_voice_spans` is the device's mirror and
+  :func:`polar_moments_ordered` a NumPy restatement of its summation order.
 
 Numerics: each correlation output is one float64 FMA chain over exact products, rounded once; the
 energies are float64 sums rounded once; the normaliser is NumPy 2's float32 arithmetic.  The result is within one
@@ -563,6 +566,331 @@ def cross_correlogram_voice_pool(slots: int, *, sample_rate_hz: int = 44100, max
                                 max_frames_per_call=max_frames_per_call, dtype=dtype)
 
 
+# ----------------------------------------------------------------------------
+# The polar moments of a voice pool   (include/vnd_polar_voice_stream.h)
+# ----------------------------------------------------------------------------
+POLAR_CHUNK_FRAMES = 512              # frames per chunk of the moments reducer (kMomFrames)
+POLAR_REDUCE_LANES = 256              # its reduce lanes (kMomThreads)
+_TMAX = 4                             # the moment that is a maximum, not a sum
+
+
+def polar_voice_spans(positions, counts, flags, max_frames_per_call: Optional[int] = None):
+    """``(valid, new_positions)`` of one call of a polar-moments voice pool (``include/vnd_polar_voice_stream.h``), per
+    slot, from the positions before the call, the frames pushed and the ``VOICE_START`` / ``VOICE_END`` flags alone -
+    what the device computes from its own state::
+
+        p = START ? 0 : position      valid = 1, or 0 for n = 0 without a flag      new position = END ? 0 : p + n
+
+    A count below 0 (or above ``max_frames_per_call``, when given), or without START a position outside ``[0, 2^60]``,
+    answers -1 and leaves the position as it was."""
+    pos = np.asarray(positions, np.int64)
+    n = np.asarray(counts, np.int64)
+    f = np.asarray(flags, np.int64)
+    if not (pos.shape == n.shape == f.shape):
+        raise ValueError(f'positions, counts and flags of one shape, got {pos.shape}, {n.shape}, {f.shape}')
+    start, end = (f & VOICE_START) != 0, (f & VOICE_END) != 0
+    p = np.where(start, 0, pos)
+    bad = (n < 0) | (p < 0) | (p > VOICE_MAX_POSITION)
+    if max_frames_per_call is not None:
+        bad |= n > int(max_frames_per_call)
+    idle = ~bad & (n == 0) & ~start & ~end
+    p, n = np.where(bad, 0, p), np.where(bad, 0, n)          # (no arithmetic on a bad value)
+    valid = np.where(bad, -1, np.where(idle, 0, 1)).astype(np.int64)
+    new = np.where(bad | idle, pos, np.where(end, 0, p + n)).astype(np.int64)
+    return valid, new
+
+
+def _polar_fold(acc, more):
+    """``acc (+) more`` per moment: a float64 add, ``fmax`` for max |theta|."""
+    out = acc + more
+    out[..., _TMAX] = np.maximum(acc[..., _TMAX], more[..., _TMAX])
+    return out
+
+
+def _polar_tree(v):
+    """The workgroup tree of the moments kernels over ``(..., 256, 8)`` lane values: ``shfl_xor`` 32..1 in each wave of
+    64, then the four waves in order."""
+    w = v.reshape(v.shape[:-2] + (POLAR_REDUCE_LANES // 64, 64, 8))
+    lane = np.arange(64)
+    for sh in (32, 16, 8, 4, 2, 1):
+        w = _polar_fold(w, w[..., lane ^ sh, :])
+    out = w[..., 0, 0, :]
+    for k in range(1, POLAR_REDUCE_LANES // 64):
+        out = _polar_fold(out, w[..., k, 0, :])
+    return out
+
+
+def _polar_chunk_partials(terms):
+    """The partials of the chunks of ``(m, 8)`` per-frame terms that begin on a chunk boundary, ``(ceil(m / 512), 8)``:
+    lane t adds frames 512 c + t and 512 c + 256 + t from +0.0 (a frame that does not exist adds nothing; +0.0 is the
+    same), then the tree."""
+    m = len(terms)
+    chunks = -(-m // POLAR_CHUNK_FRAMES)
+    a = np.zeros((chunks * POLAR_CHUNK_FRAMES, 8), np.float64)
+    a[:m] = terms
+    a = a.reshape(chunks, 2, POLAR_REDUCE_LANES, 8)
+    return _polar_tree(_polar_fold(_polar_fold(np.zeros_like(a[:, 0]), a[:, 0]), a[:, 1]))
+
+
+class PolarMomentsState:
+    """What the streamed form of :func:`polar_moments_ordered` carries between blocks - the device state of one slot
+    (``include/vnd_polar_voice_stream.h``): ``position`` (a Python integer), ``lanes`` float64 ``(256, 8)``, reduce lane
+    t's sums over the completed chunks c = t (mod 256), and ``pending`` ``(position % 512, 8)``, the terms of the chunk
+    still incomplete."""
+
+    def __init__(self, position: int = 0, lanes=None, pending=None):
+        self.position = int(position)
+        self.lanes = np.zeros((POLAR_REDUCE_LANES, 8), np.float64) if lanes is None else np.array(lanes, np.float64)
+        self.pending = np.zeros((0, 8), np.float64) if pending is None else np.array(pending, np.float64)
+        if self.position < 0 or self.lanes.shape != (POLAR_REDUCE_LANES, 8) \
+                or self.pending.shape != (self.position % POLAR_CHUNK_FRAMES, 8):
+            raise ValueError(f'a state at position {position} holds (256, 8) lane sums and '
+                             f'({self.position % POLAR_CHUNK_FRAMES}, 8) pending terms, got {self.lanes.shape} and '
+                             f'{self.pending.shape}')
+
+    def push(self, terms) -> None:
+        """Append ``(n, 8)`` per-frame terms: chunks that become complete are folded into their lanes in ascending c."""
+        terms = np.asarray(terms, np.float64).reshape(-1, 8)
+        have = np.concatenate([self.pending, terms]) if len(self.pending) else terms
+        c0 = self.position // POLAR_CHUNK_FRAMES
+        self.position += len(terms)
+        done = self.position // POLAR_CHUNK_FRAMES - c0
+        if done:
+            partials = _polar_chunk_partials(have[:done * POLAR_CHUNK_FRAMES])
+            for first in range(0, done, POLAR_REDUCE_LANES):          # 256 consecutive chunks: 256 different lanes
+                part = partials[first:first + POLAR_REDUCE_LANES]
+                lanes = (c0 + first + np.arange(len(part))) % POLAR_REDUCE_LANES
+                self.lanes[lanes] = _polar_fold(self.lanes[lanes], part)
+        self.pending = np.array(have[done * POLAR_CHUNK_FRAMES:])
+
+    def moments(self):
+        """The eight moments of everything pushed so far."""
+        lanes = self.lanes.copy()
+        c0 = self.position // POLAR_CHUNK_FRAMES
+        lanes[min(c0, POLAR_REDUCE_LANES):] = 0.0                    # a lane without a completed chunk starts from +0.0
+        if len(self.pending) or self.position == 0:                  # (no frame at all: the one chunk of zeros)
+            t = c0 % POLAR_REDUCE_LANES
+            lanes[t] = _polar_fold(lanes[t], _polar_chunk_partials(self.pending if len(self.pending)
+                                                                   else np.zeros((1, 8)))[0])
+        return _polar_tree(lanes)
+
+
+def polar_moments_ordered(terms, state: Optional[PolarMomentsState] = None):
+    """The eight polar moments from ``(n, 8)`` float64 per-frame terms ``{r, r t, r t^2, r t^3, |t|, L R, L^2, R^2}`` in
+    the summation order of ``vnd_polar_moments_f32_dev`` with one pair (``csrc/vnd_moments.hpp``), restated in NumPy
+    float64: chunk c is frames ``[512 c, 512 c + 512)``; lane t of 256 adds frames ``512 c + t`` and ``512 c + 256 + t``;
+    a ``shfl_xor`` tree 32..1 per wave; the four waves in order; reduce lane t adds the chunk partials c = t (mod 256) in
+    ascending c from +0.0; the same tree; ``max |t|`` takes the same path through ``fmax``.
+
+    Without ``state``: the one-shot form, all frames at once.  With a :class:`PolarMomentsState`: the streamed form - the
+    terms are pushed onto the state, which carries the lane sums and the pending chunk as the device does, and the result
+    is the moments of everything the state has seen.  The two agree bit for bit for every split into blocks."""
+    terms = np.asarray(terms, np.float64).reshape(-1, 8)
+    if state is not None:
+        state.push(terms)
+        return state.moments()
+    partials = _polar_chunk_partials(terms) if len(terms) else np.zeros((1, 8), np.float64)
+    lanes = np.zeros((POLAR_REDUCE_LANES, 8), np.float64)
+    for first in range(0, len(partials), POLAR_REDUCE_LANES):
+        part = partials[first:first + POLAR_REDUCE_LANES]
+        lanes[:len(part)] = _polar_fold(lanes[:len(part)], part)
+    return _polar_tree(lanes)
+
+
+class PolarVoicePool(_SlotPool):
+    """The stereo image of ``slots`` voices, each with a life of its own (:func:`stereo_image_voice_pool`,
+    ``vnd_polar_voice_stream_*_dev``): voices start and end on any call and push blocks of any size up to
+    ``max_frames_per_call`` or none.  The position lives in the device state, one per slot, so a call is a pure function
+    of device memory.  After every call a slot's row holds the eight polar moments
+    ``{sum r, sum r t, sum r t^2, sum r t^3, max |t|, sum L R, sum L^2, sum R^2}`` of that voice's whole signal so far -
+    what ``symmetry_aware_objective`` is made of (:meth:`scores`).  With ``dtype='float32'`` they equal
+    ``vnd_polar_moments_f32_dev`` on the concatenation of the voice's frames bit for bit, whatever the schedule; with
+    ``dtype='float64'`` theta, r and the products are float64, as NumPy computes them on float64 arrays, and the moments
+    do not depend on the schedule either.
+
+    Two forms; a pool is used through one of them (mixing them raises ``RuntimeError`` until ``reset()``):
+
+    * ``process({slot: block}, start=[slot, ...], end=[slot, ...], discard=False)`` - ``(n, 2)`` NumPy blocks of the
+      pool's ``dtype`` in, ``{slot: float64 (8,)}`` out for every slot that got a block, started or ended.  One upload and
+      one download (``transfers`` counts those of the last call); every refusal comes before any device call.
+    * ``process_dev(y, counts, flags, *, out=None)`` - ``y`` ``(slots, max_frames_per_call, 2)`` of the pool's ``dtype``
+      and int32 ``(slots,)`` ``counts`` and ``flags`` on the device; returns ``(moments, valid)``.  It only enqueues on
+      the current stream and can be captured with ``torch.cuda.graph`` after a ``reset()``.  To meter a decorrelating
+      pool, build the meter with ``max_frames_per_call=pool.row_frames`` (and ``dtype='float64'`` for a Haas or chain
+      pool) and hand it that pool's ``y`` and ``out_counts`` and the caller's ``flags``: a -1 of the pool is a bad count
+      here and answers -1."""
+
+    in_channels = 2
+    _out_dtype = np.float64
+    _out_width = 8
+
+    def __init__(self, slots: int, *, max_frames_per_call: int, dtype='float32'):
+        _check_counts(slots=slots, max_frames_per_call=max_frames_per_call)
+        if slots > _native.MAX_STREAMS_PER_CALL:
+            raise ValueError(f'slots {slots} above {_native.MAX_STREAMS_PER_CALL}: split the pool')
+        if max_frames_per_call > _INT32_MAX:
+            raise ValueError(f'max_frames_per_call {max_frames_per_call} above 2**31 - 1: counts are int32')
+        try:
+            self.dtype = None if dtype is None else np.dtype(dtype)
+        except TypeError:
+            self.dtype = None
+        if self.dtype is None or self.dtype.name not in ('float32', 'float64'):      # (np.dtype(None) is float64)
+            raise ValueError(f"dtype must be 'float32' or 'float64', got {dtype!r}")
+        self.slots, self.max_frames_per_call = int(slots), int(max_frames_per_call)
+        self._block_dtype = self.dtype            # what _schedule holds every block to
+        # the fixed grid of the pool (include/vnd_polar_voice_stream.h): one workgroup per chunk of 512 frames a call can
+        # touch, one grid dimension per slot; 2^23 workgroups a launch
+        if self.chunks_per_call > 65535 or self.slots * self.chunks_per_call > 1 << 23:
+            raise ValueError(f'{self.slots} slots of {self.chunks_per_call} chunks per call are more than one launch takes: '
+                             f'lower max_frames_per_call or split the pool')
+        self.transfers = {'to_device': 0, 'to_host': 0}
+        self._state = None                    # (torch uint8 tensor, bytes)
+        self._mirror()
+
+    @property
+    def chunks_per_call(self) -> int:
+        """G: the chunks of 512 frames a call can touch per slot, ``ceil(max_frames_per_call / 512) + 1``."""
+        return -(-self.max_frames_per_call // POLAR_CHUNK_FRAMES) + 1
+
+    def process(self, blocks=None, *, start=(), end=(), discard: bool = False):
+        """One call of the dict form.  ``blocks``: ``{slot: (n, 2) array of the pool's dtype}``,
+        ``0 <= n <= max_frames_per_call``; ``start``: the slots whose voice begins with this call; ``end``: the slots whose
+        voice ends with it.  Returns ``{slot: float64 (8,)}``, the moments of the voice so far, for every slot that got a
+        block, started or ended.  Raises before any device call, as the other voice pools do: ``ValueError`` for a slot
+        outside the pool or named twice, a block or an end for a slot that was never started, a start on a live slot
+        (``discard=True`` allows it: the voice it held is dropped), a block above ``max_frames_per_call`` or not
+        ``(n, 2)``; ``TypeError`` for a block of another dtype than the pool's."""
+        if self._form == 'dev':
+            raise RuntimeError('this pool runs through process_dev(): the host does not know its positions; reset() first')
+        starts = {}
+        for slot in list(start or ()):
+            slot = self._slot(slot, 'start')
+            if slot in starts:
+                raise ValueError(f'start: slot {slot} is named twice')
+            starts[slot] = 0
+        counts, flags, tables, live, x, answered = self._schedule(blocks, starts, end, discard)
+        answered = sorted(set(answered) | set(starts))
+        if not counts.any() and not flags.any():              # nothing pushed, started or ended: no device call
+            return {}
+        want, positions = self._spans(counts, flags, tables)
+        moments, got = self._call_host(x, counts, flags)
+        if not np.array_equal(np.asarray(got, np.int64), want):
+            raise _native.NativeError(f'the voice pool answered {list(got)}, the spans are {list(want)}')
+        self._commit(positions)
+        self.tables, self._form = tables, 'dict'
+        live[(flags & VOICE_END) != 0] = False
+        self.live = live
+        return {slot: np.array(moments[slot]) for slot in answered if want[slot] == 1}        # (an empty block alone: idle)
+
+    def process_dev(self, y, counts, flags, *, out=None):
+        """One call on device tensors, enqueued on the current stream: ``y`` ``(slots, M, 2)`` of the pool's dtype,
+        ``counts`` / ``flags`` int32 ``(slots,)``.  Returns ``(moments, valid)``: float64 ``(slots, 8)`` - the row of a
+        slot that answered 1 is written, no other - and int32 ``(slots,)``; ``out=(moments, valid)`` takes the caller's.
+        No check reads device memory; bad per-slot values answer -1 (``include/vnd_polar_voice_stream.h``)."""
+        if self._form == 'dict':
+            raise RuntimeError('this pool runs through process(): mixing in process_dev() would leave the host mirror '
+                               'of the positions stale; reset() first')
+        S, M = self.slots, self.max_frames_per_call
+        moments, valid = out if out is not None else (None, None)
+        _check_device_tensors((('y', y, (S, M, 2), self.dtype.name, False), ('counts', counts, (S,), 'int32', False),
+                               ('flags', flags, (S,), 'int32', False), ('moments', moments, (S, 8), 'float64', True),
+                               ('valid', valid, (S,), 'int32', True)))
+        return self._call_device(_torch(), y, counts, flags, moments, valid)
+
+    def scores(self, moments, *, angle_limit: float, lambda_mean: float, lambda_skew: float, lambda_correlation: float,
+               lambda_penalty: float):
+        """``symmetry_aware_objective`` of each voice's output so far, from ``(k, 8)`` rows of moments (or one ``(8,)`` row,
+        or a device tensor): ``optimization.scores_from_moments``; lower is better."""
+        from . import optimization
+        if _native.is_torch(moments):
+            moments = moments.cpu().numpy()
+        m = np.asarray(moments, np.float64)
+        if m.shape[-1:] != (8,) or m.ndim not in (1, 2):
+            raise ValueError(f'moments of shape (8,) or (k, 8), got {m.shape}')
+        s = optimization.scores_from_moments(m.reshape(-1, 8), angle_limit=angle_limit, lambda_mean=lambda_mean,
+                                             lambda_skew=lambda_skew, lambda_correlation=lambda_correlation,
+                                             lambda_penalty=lambda_penalty)
+        return float(s[0]) if m.ndim == 1 else s
+
+    # ---- what _SlotPool asks for ---------------------------------------------------------------
+    def _spans(self, counts, flags, tables):
+        return polar_voice_spans(self.positions, counts, flags, self.max_frames_per_call)
+
+    def _per_slot(self, tables):
+        return ()
+
+    def _bank_len(self) -> int:
+        return 1                                  # a voice starts with nothing of its own: the pool has one setting
+
+    def _slot_value(self, index: int):
+        return 0
+
+    # ---- the device -------------------------------------------------------------------------
+    def _allocate(self, torch, ctx):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('the state of a voice pool is allocated and zeroed on first use: call reset() before the capture')
+        need = _native.polar_voice_stream_state_bytes(self.slots, self.max_frames_per_call, self.dtype.itemsize)
+        buf = torch.empty((need,), dtype=torch.uint8, device=torch.device('cuda', ctx.device))
+        self._state = (buf, need)
+        self._reset_device(torch, ctx)
+
+    def _reset_device(self, torch, ctx):
+        state, state_bytes = self._state
+        _native.polar_voice_stream_reset_device(ctx, state.data_ptr(), state_bytes, self.slots, self.max_frames_per_call,
+                                                self.dtype.itemsize, stream=torch.cuda.current_stream(state.device).cuda_stream)
+
+    def _call_host(self, x, counts, flags):
+        """One upload (the blocks and the two int32 arrays in one buffer), the call, one download (moments and valid)."""
+        torch = _torch()
+        ctx = _native.default_context()
+        device = torch.device('cuda', ctx.device)
+        S = self.slots
+        ints = np.stack([counts, flags]).astype(np.int32)
+        up = torch.from_numpy(np.concatenate([x.reshape(-1).view(np.uint8), ints.reshape(-1).view(np.uint8)])).to(device)
+        self.transfers = {'to_device': 1, 'to_host': 0}
+        x_dev = up[:x.nbytes].view(torch.float64 if self.dtype == np.float64 else torch.float32).view(x.shape)
+        c, f = up[x.nbytes:].view(torch.int32).view(2, S)
+        m_bytes = S * 8 * 8
+        down = torch.zeros((m_bytes + 4 * S,), dtype=torch.uint8, device=device)
+        moments = down[:m_bytes].view(torch.float64).view(S, 8)
+        valid = down[m_bytes:].view(torch.int32)
+        form = self._form
+        try:
+            self._call_device(torch, x_dev, c, f, moments, valid)
+        finally:
+            self._form = form
+        host = down.cpu().numpy()
+        self.transfers['to_host'] = 1
+        return host[:m_bytes].view(np.float64).reshape(S, 8), host[m_bytes:].view(np.int32)
+
+    def _call_device(self, torch, y, counts, flags, moments, valid):
+        ctx = _native.default_context()
+        device = torch.device('cuda', ctx.device)
+        for t in (y, counts, flags):
+            if t.device != device:
+                raise ValueError(f'tensor on {t.device}, the pool runs on {device}')
+        state, state_bytes = self._ensure_state(torch, ctx)
+        if moments is None:
+            moments = torch.zeros((self.slots, 8), dtype=torch.float64, device=device)
+        if valid is None:
+            valid = torch.empty((self.slots,), dtype=torch.int32, device=device)
+        self._form = 'dev'
+        _native.polar_voice_stream_device(
+            ctx, state.data_ptr(), state_bytes, self.max_frames_per_call, y.data_ptr(), y.data_ptr() + y.element_size(),
+            2 * self.max_frames_per_call, 2, counts.data_ptr(), flags.data_ptr(), moments.data_ptr(), valid.data_ptr(),
+            self.slots, float64=self.dtype == np.float64, stream=torch.cuda.current_stream(device).cuda_stream)
+        return moments, valid
+
+
+def stereo_image_voice_pool(slots: int, *, max_frames_per_call: int = 4800, dtype='float32') -> PolarVoicePool:
+    """A :class:`PolarVoicePool`: the eight polar moments of ``symmetry_aware_objective`` for ``slots`` voices that start,
+    end and push blocks on their own, the positions in device memory.  Pools above ``MAX_STREAMS_PER_CALL``, a
+    ``max_frames_per_call`` whose grid one launch does not take and a ``dtype`` other than ``'float32'`` / ``'float64'``
+    raise ``ValueError`` here: a stream has no host loop to fall back to."""
+    return PolarVoicePool(slots, max_frames_per_call=max_frames_per_call, dtype=dtype)
+
+
 __all__ = ['cross_correlogram_batched', 'cross_correlogram_stream', 'CorrelogramStream', 'correlogram_covers',
            'set_correlogram_device', 'MAX_WINDOW', 'cross_correlogram_voice_pool', 'CorrelogramVoicePool',
-           'correlogram_voice_spans']
+           'correlogram_voice_spans', 'stereo_image_voice_pool', 'PolarVoicePool', 'polar_voice_spans',
+           'polar_moments_ordered', 'PolarMomentsState']

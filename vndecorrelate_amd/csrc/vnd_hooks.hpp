@@ -293,4 +293,18 @@ vnd_status vnd_describe_correlogram_voice_stream_launch(int64_t slots, int32_t w
     return VND_OK;
 }
 
+// The fixed launch of every vnd_polar_voice_stream_*_dev call on a pool with these sizes: the pool's own scalar checks and
+// polar_voice_plan, the launch's own.  No pointers, no device work.
+vnd_status vnd_describe_polar_voice_stream_launch(int64_t slots, int64_t max_frames_per_call, int32_t sample_bytes, char *text,
+                                                  int32_t len)
+{
+    if (!text || len <= 0) return fail(VND_ERR_INVALID, "null text buffer");
+    PolarVoicePlan p{};
+    vnd_status st = polar_voice_plan(slots, max_frames_per_call, sample_bytes, &p);
+    if (st != VND_OK) return st;
+    snprintf(text, (size_t)len, "polar_voice_stream groups=%lld nblocks=%lld finish_groups=%lld threads=%d state_bytes=%lld",
+             (long long)p.G, (long long)p.workgroups, (long long)p.finish_groups, kPolarVoiceLanes, (long long)p.need);
+    return VND_OK;
+}
+
 }  // extern "C"

@@ -679,6 +679,7 @@ class _SlotPool:
     # ---- what a pool supplies ------------------------------------------------------------------
     _out_dtype = np.float32
     _out_width = 2                            # the last axis of what a slot returns
+    _block_dtype = np.float32                 # what a voice pushes
 
     def _spans(self, counts, flags, tables):
         """``(out_counts, new positions)`` of the call, from the host mirror."""
@@ -721,15 +722,15 @@ class _SlotPool:
             flags[slot] |= VOICE_START
             tables[slot] = self._slot_value(int(index))
             live[slot] = True
-        x = np.zeros((S, M, cx), np.float32)
+        x = np.zeros((S, M, cx), self._block_dtype)
         answered = set()
         for slot, block in dict(blocks or {}).items():
             slot = self._slot(slot, 'block')
             if not live[slot]:
                 raise ValueError(f'block for slot {slot}, which was never started: name it in start=')
             a = np.asarray(block)
-            if a.dtype != np.float32:
-                raise TypeError(f'block of slot {slot}: voices push float32 frames, got {a.dtype}')
+            if a.dtype != self._block_dtype:
+                raise TypeError(f'block of slot {slot}: voices push {np.dtype(self._block_dtype).name} frames, got {a.dtype}')
             if a.ndim == 1 and cx == 1:
                 a = a[:, None]
             if a.ndim != 2 or a.shape[1] != cx:
