@@ -89,17 +89,29 @@ vnd_status vnd_ctx_info(const vnd_ctx *ctx, char *name, int32_t len, int32_t *co
  * of tap_index / tap_weight, consumed IN TABLE ORDER.
  *
  * Function-path table (replaces the np.where scan of decorrelation.py:651-654):
- *   seg_offsets = seg_end = seg_gain = NULL; indices ascending.
+ *   seg_offsets = seg_end = seg_gain = NULL.  The scan yields ascending unique indices and no zero
+ *   weight, but none of that is required: the order of a channel's taps is free (it IS the summation
+ *   order of the exact modes), an index may repeat, a weight may be +-0 - every kernel form gives the
+ *   table-order sum (tests/test_gpu_taps_gate.py).
  * Class-path table (replaces _ParallelVelvetNoise, decorrelation.py:240-323,
  * consumed by VelvetNoise.convolve :402-414): per channel a CSR of segments,
  * seg_end[s] = exclusive end (absolute position in tap_index) of segment s,
  * seg_gain[s] = segment_envelope[s]; weights are -1 (negatives first) / +1;
  * apply_gain = 0 reproduces the skipped multiply of the identity envelope (:411).
- * chan_flags[c] & 1 marks an unfiltered channel that is copied through (:399-400);
- * may be NULL.  All indices must be >= 0 (and <= 2^30).  Arrays are HOST pointers, copied.
+ * chan_flags[c] & 1 marks an unfiltered channel that is copied through (:399-400), whatever taps
+ * and segments it carries; may be NULL.  Arrays are HOST pointers, copied.
+ * What is checked (VND_ERR_INVALID; *taps is NULL after any refusal): 1 <= num_channels <= 65535;
+ * tap_offsets[0] == 0 and non-decreasing; every index >= 0, and <= 2^30 (beyond: VND_ERR_UNSUPPORTED);
+ * with seg_offsets also seg_end and seg_gain, seg_offsets[0] == 0 and non-decreasing, a channel's
+ * segment ends non-decreasing inside [tap_offsets[c], tap_offsets[c+1]] (a segment may be empty) and,
+ * where the channel has taps, the last one == tap_offsets[c+1].  A channel may have no taps, with or
+ * without segments; tap_index / tap_weight may be NULL when there is no tap at all.
+ * What is NOT checked: the arrays' lengths - the entry reads tap_offsets[num_channels] taps,
+ * seg_offsets[num_channels] segments and num_channels flags through the pointers it is given.
  * A table with a non-finite weight keeps the reference's semantics (a term whose tap
  * reaches past the end of the stream drops, decorrelation.py:656-658, instead of
- * becoming 0 * inf) by running the index-testing gather kernel instead of the LDS ones. */
+ * becoming 0 * inf) by running the index-testing gather kernel instead of the LDS ones; so does a
+ * table whose applied segment gain is not finite (it multiplies the segment's sum, as in the reference). */
 vnd_status vnd_taps_create(vnd_ctx *ctx, int32_t num_channels,
                            const int32_t *tap_offsets, const int32_t *tap_index,
                            const float *tap_weight,
@@ -112,6 +124,10 @@ vnd_status vnd_taps_info(const vnd_taps *taps, int32_t *num_channels, int32_t *t
 /* Packed image of a table for transport between ranks (RCCL broadcast of the
  * shared impulse tables): serialise on rank 0, broadcast bytes, rebuild.      */
 vnd_status vnd_taps_serialize(const vnd_taps *taps, void *buf, int64_t capacity, int64_t *bytes);
+/* vnd_taps_deserialize takes bytes from anywhere (another rank, a file): buf must be 4-byte aligned (the
+ * image is read in place; VND_ERR_INVALID otherwise) and hold `bytes` bytes; bytes beyond the image are
+ * ignored.  The header's counts are held to the ranges above and to `bytes` before anything is read through
+ * them, then the rows go through vnd_taps_create's checks: a malformed image is refused, never followed. */
 vnd_status vnd_taps_deserialize(vnd_ctx *ctx, const void *buf, int64_t bytes, vnd_taps **taps);
 
 /* Sharding helpers for hosts that bring their own process group (the many-stream mode of

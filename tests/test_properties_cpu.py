@@ -35,7 +35,8 @@ def test_numpy_and_c_oracles_agree_function_path(fir, n, seed):
         assert np.array_equal(O.convolve_taps_scalar(x, arr.tap_offsets, arr.tap_index, arr.tap_weight), want)
     back = TapArrays.from_bytes(arr.to_bytes())
     assert np.array_equal(back.tap_index, arr.tap_index) and np.array_equal(back.tap_weight, arr.tap_weight)
-    # table invariants the kernels rely on: CSR, ascending unique indices per channel, no zero weights
+    # what function_path_arrays promises: CSR, ascending unique indices per channel, no zero weights (the kernels rely on the CSR
+    # rows alone - vnd_taps_create admits any order, duplicates and zero weights: tests/test_gpu_taps_gate.py)
     assert arr.tap_offsets[0] == 0 and arr.tap_offsets[-1] == len(arr.tap_index)
     for c in range(fir.shape[1]):
         sl = arr.tap_index[arr.tap_offsets[c]:arr.tap_offsets[c + 1]]

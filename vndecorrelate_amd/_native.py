@@ -576,16 +576,35 @@ class TapTable:
     @classmethod
     def create(cls, ctx: Context, tap_offsets, tap_index, tap_weight, *, seg_offsets=None,
                seg_end=None, seg_gain=None, chan_flags=None, apply_gain=False) -> 'TapTable':
-        tap_offsets = np.ascontiguousarray(tap_offsets, np.int32)
-        tap_index = np.ascontiguousarray(tap_index, np.int32)
-        tap_weight = np.ascontiguousarray(tap_weight, np.float32)
+        """The arrays of ``vnd_taps_create`` (include/vnd_amd.h).  The C side reads ``tap_offsets[-1]`` taps and
+        ``seg_offsets[-1]`` segments through bare pointers: arrays shorter than that are refused here, before the call
+        (``tap_index`` / ``tap_weight`` may be ``None`` for a table without taps)."""
+        tap_offsets = np.ascontiguousarray(tap_offsets, np.int32).ravel()
+        tap_index = None if tap_index is None else np.ascontiguousarray(tap_index, np.int32).ravel()
+        tap_weight = None if tap_weight is None else np.ascontiguousarray(tap_weight, np.float32).ravel()
         channels = len(tap_offsets) - 1
+        if channels < 1:
+            raise ValueError('tap_offsets needs one entry per channel and one more')
+        total = int(tap_offsets[-1])
+        for name, a in (('tap_index', tap_index), ('tap_weight', tap_weight)):
+            if (0 if a is None else len(a)) < total:
+                raise ValueError(f'{name} holds {0 if a is None else len(a)} entries, tap_offsets[-1] asks for {total}')
         if seg_offsets is not None:
-            seg_offsets = np.ascontiguousarray(seg_offsets, np.int32)
-            seg_end = np.ascontiguousarray(seg_end, np.int32)
-            seg_gain = np.ascontiguousarray(seg_gain, np.float32)
+            if seg_end is None or seg_gain is None:
+                raise ValueError('seg_offsets comes with seg_end and seg_gain')
+            seg_offsets = np.ascontiguousarray(seg_offsets, np.int32).ravel()
+            seg_end = np.ascontiguousarray(seg_end, np.int32).ravel()
+            seg_gain = np.ascontiguousarray(seg_gain, np.float32).ravel()
+            if len(seg_offsets) != len(tap_offsets):
+                raise ValueError(f'seg_offsets has {len(seg_offsets)} entries, tap_offsets {len(tap_offsets)}')
+            segs = int(seg_offsets[-1])
+            for name, a in (('seg_end', seg_end), ('seg_gain', seg_gain)):
+                if len(a) < segs:
+                    raise ValueError(f'{name} holds {len(a)} entries, seg_offsets[-1] asks for {segs}')
         if chan_flags is not None:
-            chan_flags = np.ascontiguousarray(chan_flags, np.uint8)
+            chan_flags = np.ascontiguousarray(chan_flags, np.uint8).ravel()
+            if len(chan_flags) < channels:
+                raise ValueError(f'chan_flags holds {len(chan_flags)} entries for {channels} channels')
         h = ctypes.c_void_p()
         _check(ctx._lib.vnd_taps_create(
             ctx.handle, channels, _ptr(tap_offsets, ctypes.c_int32), _ptr(tap_index, ctypes.c_int32),
@@ -597,7 +616,10 @@ class TapTable:
 
     @classmethod
     def from_bytes(cls, ctx: Context, image: bytes) -> 'TapTable':
-        buf = ctypes.create_string_buffer(image, len(image))
+        image = bytes(image)
+        if not image:
+            raise ValueError('empty tap image')
+        buf = ctypes.create_string_buffer(image, len(image))       # (its own copy, aligned for the words the C side reads in place)
         h = ctypes.c_void_p()
         _check(ctx._lib.vnd_taps_deserialize(ctx.handle, buf, len(image), ctypes.byref(h)),
                'vnd_taps_deserialize')

@@ -137,8 +137,11 @@ vnd_status vnd_taps_create(vnd_ctx *ctx, int32_t C, const int32_t *tap_offsets, 
     if (has_seg) {
         if (!seg_end || !seg_gain) return fail(VND_ERR_INVALID, "segment table incomplete");
         if (seg_offsets[0] != 0) return fail(VND_ERR_INVALID, "seg_offsets[0] must be 0");
-        for (int c = 0; c < C; ++c) {
+        // the whole row first: only then does every entry lie inside [0, seg_offsets[C]], the length the caller vouches for
+        // (an image's seg_offsets[C] is held to its header) - a walk begun before would follow a wild entry past seg_end
+        for (int c = 0; c < C; ++c)
             if (seg_offsets[c + 1] < seg_offsets[c]) return fail(VND_ERR_INVALID, "seg_offsets not monotone");
+        for (int c = 0; c < C; ++c) {
             int32_t prev = tap_offsets[c];
             for (int32_t s = seg_offsets[c]; s < seg_offsets[c + 1]; ++s) {
                 if (seg_end[s] < prev || seg_end[s] > tap_offsets[c + 1])
@@ -186,8 +189,12 @@ vnd_status vnd_taps_create(vnd_ctx *ctx, int32_t C, const int32_t *tap_offsets, 
         if (has_seg && t->apply_gain)
             for (int c = 0; c < C; ++c) {
                 int32_t k = tap_offsets[c];
-                for (int32_t sgi = seg_offsets[c]; sgi < seg_offsets[c + 1]; ++sgi)
-                    for (; k < seg_end[sgi]; ++k) eff[k] = tap_weight[k] * seg_gain[sgi];
+                for (int32_t sgi = seg_offsets[c]; sgi < seg_offsets[c + 1]; ++sgi) {
+                    // a gain that is not finite (or makes a weight so) is a non-finite weight to every kernel that folds it in:
+                    // the reference multiplies the segment's SUM by it, dropped terms left out - the index-testing kernel's sum
+                    t->nonfinite |= !std::isfinite(seg_gain[sgi]);
+                    for (; k < seg_end[sgi]; ++k) { eff[k] = tap_weight[k] * seg_gain[sgi]; t->nonfinite |= !std::isfinite(eff[k]); }
+                }
             }
         for (int c = 0; c < C; ++c) {
             for (int parity = 0; parity < 2; ++parity) {
@@ -303,12 +310,15 @@ vnd_status vnd_taps_deserialize(vnd_ctx *ctx, const void *buf, int64_t bytes, vn
     if (!out) return fail(VND_ERR_INVALID, "null out pointer");
     *out = nullptr;
     if (!buf || bytes < 32) return fail(VND_ERR_INVALID, "tap image too short");
+    // the image is read in place as int32 / float words
+    if ((uintptr_t)buf % 4 != 0) return fail(VND_ERR_INVALID, "tap image is not 4-byte aligned");
     const int32_t *p = (const int32_t *)buf;
     if (p[0] != kMagic || p[1] != VND_TAPS_IMAGE_VERSION) return fail(VND_ERR_INVALID, "not a tap image of this format version");
     const int32_t C = p[2], total = p[3], segs = p[4], has_seg = p[5], has_flags = p[6], gain = p[7];
-    if (C <= 0 || total < 0 || segs < 0) return fail(VND_ERR_INVALID, "corrupt tap image header");
-    const int64_t flag_words = has_flags ? (C + 3) / 4 : 0;
-    const int64_t words = 8 + (C + 1) + 2 * (int64_t)total + (has_seg ? (C + 1) + 2 * (int64_t)segs : 0) + flag_words;
+    // (the channel count is held to vnd_taps_create's range here, before any arithmetic on it)
+    if (C <= 0 || C > 65535 || total < 0 || segs < 0) return fail(VND_ERR_INVALID, "corrupt tap image header");
+    const int64_t flag_words = has_flags ? ((int64_t)C + 3) / 4 : 0;
+    const int64_t words = 8 + ((int64_t)C + 1) + 2 * (int64_t)total + (has_seg ? ((int64_t)C + 1) + 2 * (int64_t)segs : 0) + flag_words;
     if (bytes < words * 4) return fail(VND_ERR_INVALID, "tap image truncated");
     const int32_t *tap_off = p + 8;
     const int32_t *idx = tap_off + C + 1;

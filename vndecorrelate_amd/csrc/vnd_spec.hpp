@@ -260,7 +260,8 @@ inline std::string spec_prologue(const SpecTable &t, const SpecConfig &c)
                     for (int32_t sg = t.seg_off[ch]; sg < t.seg_off[ch + 1]; ++sg) {
                         const int32_t last = t.seg_end[sg] - 1 - t.tap_off[ch];      // spec scope: no empty segment
                         per[cc][last].end = t.apply_gain ? 3 : 2;
-                        per[cc][last].gain = t.seg_gain[sg];
+                        // (an ignored gain stays out of the source: the caller's number may be one no literal spells - inf - and the build failed)
+                        per[cc][last].gain = t.apply_gain ? t.seg_gain[sg] : 1.0f;
                     }
                 }
             }
