@@ -242,7 +242,17 @@ vnd_status vnd_decorrelate_fanout_f32_host(vnd_ctx *ctx, const vnd_taps *taps, c
  * vnd_scan_bank_f32_host runs the whole scan from a host signal (in_channels 1 or 2; the
  * bank table has 2*n_pairs channels) and returns moments[n_pairs][VND_MOMENTS].  The
  * candidates' convolution only (no side-channel encode / width / normaliser), which is
- * what optimize_velvet_noise builds (optimization.py:259-271: mode LR, normalizer None). */
+ * what optimize_velvet_noise builds (optimization.py:259-271: mode LR, normalizer None).
+ * Under one launch plan a row depends on its candidate and the signal only, bit for bit (not
+ * on its place in the bank, the other candidates or earlier calls).  Another plan - another
+ * tile, the moments as a pass of their own - may take the float64 sums in another order.  In
+ * VND_MODE_FAST the frames themselves are a function of the tile (a tile's last frame sums
+ * its odd-offset taps in another order than the other frames do): rows of different tiles
+ * agree within that mode's rounding, rows of one tile as above.
+ * Non-finite samples: a frame with a NaN or an infinity makes the summed slots (0-3, 5-7) NaN
+ * or infinite as NumPy's sums of the same float32 terms are.  Slot 4 is left unspecified for a
+ * signal with a NaN frame (the running maximum drops a NaN theta where np.max propagates it).
+ * n_frames == 0 gives eight zeros per pair.                                              */
 #define VND_MOMENTS 8
 vnd_status vnd_polar_moments_workspace_bytes(int64_t n_frames, int32_t n_pairs, int64_t *bytes);
 vnd_status vnd_polar_moments_f32_dev(vnd_ctx *ctx, const float *y_dev, int64_t n_frames, int32_t n_pairs,

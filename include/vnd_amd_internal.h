@@ -78,6 +78,15 @@ vnd_status vnd_debug_read_stamps(vnd_ctx *ctx, const vnd_taps *taps, int64_t bat
  * groups, nblocks.  epilogue = the call's ms_encode || use_width.                                                      */
 vnd_status vnd_describe_stream_launch(vnd_ctx *ctx, const vnd_taps *taps, int64_t batch, int64_t n_out,
                                       int32_t in_channels, int32_t mode, int32_t epilogue, char *text, int32_t len);
+/* Diagnosis (tests): the route a vnd_scan_bank_f32_host call of this shape takes - the call's own scalar checks and the one
+ * function that decides for it, no pointers, no device work - as one line.  It starts with `fused` (the convolution's store
+ * phase leaves the moments; y is never written) or `unfused` followed by `by_frame` / `by_candidate` (the stand-alone reducer's
+ * kernel: a lane per candidate from 64 pairs on), then the convolution's kernel (conv_ordered | conv_fast, with _fanout for a
+ * mono input staged once; conv_direct; conv_none for an empty signal) and the plan as key=value fields: cg (channels per
+ * workgroup), r (frame pairs per lane: the tile is 2 * nt * r frames), nt (threads), bc (1: the fan-out staging), tiles,
+ * direct, halo, lds, workgroups, mode, pairs.                                                                            */
+vnd_status vnd_describe_scan(vnd_ctx *ctx, const vnd_taps *bank, int64_t n_frames, int32_t in_channels, int32_t mode,
+                             char *text, int32_t len);
 /* Diagnosis: the launch a vnd_each_stream_f32_dev call (include/vnd_each_stream.h) with these arguments would take - the
  * call's own scalar checks and planner, no device work - as one line of key=value fields: r (frame pairs per lane: the
  * tile is 2 * 256 * r frames), W (window frames), lds_bytes, tiles (per stream), nblocks, n_out, fma (a bank of +-1

@@ -7,6 +7,7 @@ import io
 import numpy as np
 import pytest
 
+import scan_ref
 from conftest import make_input
 from oracle import vnd_oracle as O
 
@@ -49,17 +50,7 @@ def _candidates(vnd, meta):
             for k in meta['kappas']]
 
 
-def _moments64(y):
-    """float32 element maths as NumPy, float64 sums: what the device computes."""
-    left, right = y[:, 0], y[:, 1]
-    th = np.arctan2(left - right, left + right)
-    th = np.where(th < -np.pi / 2, th + np.pi, np.where(th > np.pi / 2, th - np.pi, th))
-    r = np.sqrt(left**2 + right**2)
-    assert th.dtype == np.float32 and r.dtype == np.float32
-    d = np.float64
-    return np.array([r.sum(dtype=d), (r * th).sum(dtype=d), (r * th**2).sum(dtype=d), (r * (th**2 * th)).sum(dtype=d),
-                     np.max(np.abs(th)) if len(th) else 0.0, (left * right).sum(dtype=d), (left * left).sum(dtype=d),
-                     (right * right).sum(dtype=d)])
+_moments64 = scan_ref.moments64      # float32 element maths as NumPy, float64 sums: what the device computes
 
 
 @pytest.mark.parametrize('mode', ['exact', 'fast'])
@@ -94,14 +85,17 @@ def test_optimize_velvet_noise_reproduces_reference(vnd, opt, golden):
     assert abs(kappa - meta['optimize_velvet_noise_grid9']) <= 1e-6
 
 
-@pytest.mark.parametrize('pairs,n', [(1, 1), (1, 777), (3, 5000), (63, 1025), (64, 1025), (100, 4099), (400, 513)])
+@pytest.mark.parametrize('pairs,n', [(1, 1), (1, 777), (3, 5000), (63, 1025), (64, 1025), (100, 4099), (400, 513),
+                                     (256, 513), (257, 511), (65, 512), (64, 0), (1, 0)])
 def test_moments_kernel_against_numpy(vnd, pairs, n):
-    """Both kernel shapes (lanes along time for narrow banks, lanes along candidates for wide ones)."""
+    """Both kernel shapes (lanes along time for narrow banks, lanes along candidates for wide ones); 257 pairs need a second
+    row of workgroups whose lanes past the last pair return; no frames give eight zeros per pair."""
     import torch
     from vndecorrelate_amd import _native
     ctx = _native.default_context()
     y = np.random.default_rng(pairs * 1000 + n).uniform(-1, 1, (n, 2 * pairs)).astype(np.float32)
-    y[n // 2] = 0.0                                      # a silent frame: r = 0, theta = 0
+    if n:
+        y[n // 2] = 0.0                                  # a silent frame: r = 0, theta = 0
     if n > 3:
         y[3, 0::2] = -y[3, 1::2]                         # L + R == 0: theta = +-pi/2 exactly
     yd = torch.from_numpy(y).cuda()
@@ -120,6 +114,28 @@ def test_moments_kernel_against_numpy(vnd, pairs, n):
         scale[1:4] = want[0] * np.array([np.pi / 2, (np.pi / 2) ** 2, (np.pi / 2) ** 3])
         assert np.all(np.abs(got[f] - want) <= 3e-8 * np.maximum(scale, 1.0)), (f, got[f], want)
         assert got[f][4] == want[4] or abs(got[f][4] - want[4]) <= 2.4e-7      # max |theta|: one float32 ulp
+
+
+@pytest.mark.parametrize('pairs,n', [(3, 1025), (63, 513), (64, 513), (257, 511)])
+def test_moments_kernel_integer_input_exactly(vnd, pairs, n):
+    """Integer-valued frames: L*R, L^2 and R^2 are exact in float32 and their float64 sums exact in any order, so slots 5-7
+    equal NumPy's bit for bit - a frame read twice, skipped or taken from a neighbouring candidate shows."""
+    import torch
+    from vndecorrelate_amd import _native
+    ctx = _native.default_context()
+    y = np.random.default_rng(pairs * 1000 + n).integers(-50, 51, (n, 2 * pairs)).astype(np.float32)
+    yd = torch.from_numpy(y).cuda()
+    ws = _native.polar_moments_workspace_bytes(n, pairs)
+    work = torch.empty(ws, dtype=torch.uint8, device='cuda')
+    out = torch.full((pairs, 8), -1.0, dtype=torch.float64, device='cuda')
+    _native.polar_moments_device(ctx, yd.data_ptr(), n, pairs, out.data_ptr(), work.data_ptr(), ws,
+                                 torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    got = out.cpu().numpy()
+    for f in range(pairs):
+        want = _moments64(y[:, 2 * f:2 * f + 2])
+        assert got[f][5:].tobytes() == want[5:].tobytes(), (f, got[f][5:], want[5:])
+        assert abs(got[f][4] - want[4]) <= 2.4e-7
 
 
 def test_scan_large_bank_equals_host_loop(vnd, opt):

@@ -10,6 +10,7 @@ import warnings
 import numpy as np
 import pytest
 
+import scan_ref
 from conftest import make_input
 from oracle import vnd_oracle as O
 
@@ -61,28 +62,8 @@ def _stereo(x):
     return np.repeat(x, 2, axis=1) if x.shape[1] == 1 else x
 
 
-def _moments64(y):
-    """tests/test_gpu_optimization.py's reference: float32 element maths as NumPy, float64 sums."""
-    left, right = y[:, 0], y[:, 1]
-    th = np.arctan2(left - right, left + right)
-    th = np.where(th < -np.pi / 2, th + np.pi, np.where(th > np.pi / 2, th - np.pi, th))
-    r = np.sqrt(left**2 + right**2)
-    assert th.dtype == np.float32 and r.dtype == np.float32
-    d = np.float64
-    return np.array([r.sum(dtype=d), (r * th).sum(dtype=d), (r * th**2).sum(dtype=d), (r * (th**2 * th)).sum(dtype=d),
-                     np.max(np.abs(th)) if len(th) else 0.0, (left * right).sum(dtype=d), (left * left).sum(dtype=d),
-                     (right * right).sum(dtype=d)])
-
-
-def _term_sums(y):
-    """Sum of |term| of every summed slot (slot 4, a maximum, gets 0)."""
-    left, right = y[:, 0], y[:, 1]
-    th = np.arctan2(left - right, left + right)
-    th = np.where(th < -np.pi / 2, th + np.pi, np.where(th > np.pi / 2, th - np.pi, th))
-    r = np.sqrt(left**2 + right**2)
-    d = np.float64
-    return np.array([np.abs(t).sum(dtype=d) for t in (r, r * th, r * th**2, r * (th**2 * th))] + [0.0]
-                    + [np.abs(t).sum(dtype=d) for t in (left * right, left * left, right * right)])
+_moments64 = scan_ref.moments64      # tests/test_gpu_optimization.py's reference: float32 element maths as NumPy, float64 sums
+_term_sums = scan_ref.term_sums      # sum of |term| of every summed slot (slot 4, a maximum, gets 0)
 
 
 # ---- 1. frames, exactly ----------------------------------------------------------------------------------------------

@@ -141,6 +141,8 @@ INTERNAL_SIGNATURES = {
     'vnd_describe_stream_launch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p,
                                                   ctypes.c_int32]),
+    'vnd_describe_scan': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                         ctypes.c_char_p, ctypes.c_int32]),
     'vnd_describe_each_stream_launch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                                        ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                                        ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32]),
@@ -796,6 +798,15 @@ class TapTable:
         buf = ctypes.create_string_buffer(512)
         _check(self._lib.vnd_describe_stream_launch(self.ctx.handle, self.handle, batch, n_out, in_channels, int(mode),
                                                     int(bool(epilogue)), buf, 512), 'vnd_describe_stream_launch')
+        return buf.value.decode()
+
+    def describe_scan(self, n: int, in_channels: int, mode: int = MODE_EXACT) -> str:
+        """The route ``scan_host`` takes for an ``(n, in_channels)`` signal (``vnd_describe_scan``; no device work): the
+        text starts with ``fused`` or ``unfused by_frame`` / ``unfused by_candidate``, then names the convolution's kernel
+        and carries ``cg=``, ``r=``, ``nt=``, ``bc=``, ``tiles=``, ``direct=`` among its fields."""
+        buf = ctypes.create_string_buffer(512)
+        _check(self._lib.vnd_describe_scan(self.ctx.handle, self.handle, n, in_channels, int(mode), buf, 512),
+               'vnd_describe_scan')
         return buf.value.decode()
 
     def describe_each_stream(self, max_frames_per_call: int, batch: int, position: int, n_in: int, in_channels: int,

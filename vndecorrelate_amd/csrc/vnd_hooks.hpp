@@ -246,6 +246,30 @@ vnd_status vnd_describe_stream_launch(vnd_ctx *ctx, const vnd_taps *t, int64_t b
     return VND_OK;
 }
 
+// The route a vnd_scan_bank_f32_host call of this shape takes: the call's own scalar checks and scan_route, the call's own
+// decision.  No pointers, no device work (make_spec_plan only plans: nothing is built or looked up).
+vnd_status vnd_describe_scan(vnd_ctx *ctx, const vnd_taps *t, int64_t n, int32_t in_channels, int32_t mode, char *text,
+                             int32_t len)
+{
+    vnd_status st = scan_check(ctx, t, n, in_channels, mode);
+    if (st != VND_OK) return st;
+    if (!text || len <= 0) return fail(VND_ERR_INVALID, "null text buffer");
+    const ScanRoute s = scan_route(ctx, t, n, in_channels, mode);
+    const Plan &p = s.p;
+    const int pairs = t->C / 2;
+    char conv[64];
+    if (n == 0) snprintf(conv, sizeof conv, "conv_none");
+    else if (p.direct) snprintf(conv, sizeof conv, "conv_direct");
+    else snprintf(conv, sizeof conv, "%s%s", mode == VND_MODE_FAST ? "conv_fast" : "conv_ordered", p.bc ? "_fanout" : "");
+    // the unfused launch carries no epilogue, so a large enough one may go to the per-table kernel where that builds
+    const bool spec = n > 0 && !s.fused && make_spec_plan(ctx, t, nullptr, nullptr, 1, n, t->C, in_channels, mode, nullptr).use;
+    snprintf(text, (size_t)len, "%s%s %s%s cg=%d r=%d nt=%d bc=%d tiles=%d direct=%d halo=%d lds=%zuB workgroups=%u mode=%d pairs=%d",
+             s.fused ? "fused" : "unfused", s.fused ? "" : (pairs >= kMomByCandidatePairs ? " by_candidate" : " by_frame"), conv,
+             spec ? " (or the per-table kernel)" : "", p.cg, p.r, p.direct ? kDirectThreads : p.nt, p.bc ? 1 : 0, p.tiles,
+             p.direct ? 1 : 0, p.direct || n == 0 ? 0 : p.W - 2 * p.nt * p.r, p.lds_bytes, p.nblocks, mode, pairs);
+    return VND_OK;
+}
+
 // The EachStreamPlan a vnd_each_stream_f32_dev call with these arguments takes: the same checks and planner, no pointers.
 vnd_status vnd_describe_each_stream_launch(vnd_ctx *ctx, const vnd_taps *t, int64_t max_frames_per_call, int64_t batch,
                                            int64_t pos, int64_t n_in, int32_t in_channels, int32_t final_, int32_t mode,

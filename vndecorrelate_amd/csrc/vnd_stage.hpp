@@ -411,6 +411,8 @@ vnd_status vnd_convolve_promote_host(vnd_ctx *ctx, int32_t C, const int32_t *tap
 // ------------------------------------------------------------------------------
 // candidate scan
 // ------------------------------------------------------------------------------
+// the unfused route's reducer takes a lane per candidate from this many pairs on (moments_by_candidate_kernel)
+constexpr int kMomByCandidatePairs = 64;
 static int64_t mom_chunks(int64_t n) { return std::max<int64_t>((n + kMomFrames - 1) / kMomFrames, 1); }
 
 vnd_status vnd_polar_moments_workspace_bytes(int64_t n, int32_t n_pairs, int64_t *bytes)
@@ -437,7 +439,7 @@ vnd_status vnd_polar_moments_f32_dev(vnd_ctx *ctx, const float *y, int64_t n, in
     hipStream_t stream = (hipStream_t)stream_;
     MArgs a{};
     a.y = y; a.partials = (double *)workspace; a.moments = moments; a.n = n; a.F = n_pairs; a.chunks = (int32_t)chunks;
-    if (n_pairs >= 64) {
+    if (n_pairs >= kMomByCandidatePairs) {
         const dim3 grid((unsigned)chunks, (unsigned)((n_pairs + kMomThreads - 1) / kMomThreads));
         hipLaunchKernelGGL(moments_by_candidate_kernel, grid, dim3(kMomThreads), 0, stream, a);
     } else {
@@ -449,29 +451,50 @@ vnd_status vnd_polar_moments_f32_dev(vnd_ctx *ctx, const float *y, int64_t n, in
     return VND_OK;
 }
 
-vnd_status vnd_scan_bank_f32_host(vnd_ctx *ctx, const vnd_taps *t, const float *x, int64_t n, int32_t in_channels,
-                                  int32_t mode, double *moments)
+// the scan's argument checks (all but its pointers): the entry point's and vnd_describe_scan's
+static vnd_status scan_check(const vnd_ctx *ctx, const vnd_taps *t, int64_t n, int32_t in_channels, int32_t mode)
 {
     if (!ctx || !t) return fail(VND_ERR_INVALID, "null context or tap table");
     if (t->C % 2 != 0) return fail(VND_ERR_INVALID, "a scan needs stereo pairs: the bank has %d channels", t->C);
     if (in_channels != 1 && in_channels != 2)
         return fail(VND_ERR_INVALID, "a scan takes a mono or stereo signal, got %d channels", in_channels);
-    vnd_status st = check_shape(ctx, t, 1, n, t->C, mode, in_channels);
+    return check_shape(ctx, t, 1, n, t->C, mode, in_channels);
+}
+
+// Which way a scan of n frames goes: the plan of its convolution launch (the generic kernels' - launch() makes the same one
+// from the same arguments; empty for n == 0, where nothing is convolved) and whether that launch's store phase leaves the
+// moments (fused).  The one place that decides: vnd_scan_bank_f32_host runs it, vnd_describe_scan (vnd_hooks.hpp) prints it.
+struct ScanRoute {
+    Plan p{};
+    bool fused = false;
+};
+
+static ScanRoute scan_route(const vnd_ctx *ctx, const vnd_taps *t, int64_t n, int32_t in_channels, int32_t mode)
+{
+    ScanRoute s;
+    if (n <= 0) return s;
+    s.p = make_plan(ctx, t, 1, n, t->C, mode, in_channels);
+    if (ctx->variant.nofuse) return s;
+    // Fused form: the convolution kernel's store phase reduces each tile to the eight moments per
+    // candidate (KArgs.sink_partials) - the [n][2F] output, 1.6 GB there and back for 400 candidates
+    // of a 5.7 s signal, is never written.  Needs the two-channels-per-workgroup epilogue instantiation.
+    kern_t k = s.p.direct ? nullptr
+                          : (mode == VND_MODE_FAST ? fast_epi_kernel(s.p) : ordered_epi_kernel(s.p, arithmetic_of(t, mode)));
+    s.fused = k != nullptr && s.p.cg == 2;
+    return s;
+}
+
+vnd_status vnd_scan_bank_f32_host(vnd_ctx *ctx, const vnd_taps *t, const float *x, int64_t n, int32_t in_channels,
+                                  int32_t mode, double *moments)
+{
+    vnd_status st = scan_check(ctx, t, n, in_channels, mode);
     if (st != VND_OK) return st;
     if (!moments || (n > 0 && !x)) return fail(VND_ERR_INVALID, "null pointer");
     const int32_t pairs = t->C / 2;
     HostCall call(ctx);
-    // Fused form: the convolution kernel's store phase reduces each tile to the eight moments per
-    // candidate (KArgs.sink_partials) - the [n][2F] output, 1.6 GB there and back for 400 candidates
-    // of a 5.7 s signal, is never written.  Needs the two-channels-per-workgroup epilogue instantiation.
-    Plan p{};
-    bool fused = false;
-    if (n > 0 && !ctx->variant.nofuse) {
-        p = make_plan(ctx, t, 1, n, t->C, mode, in_channels);
-        kern_t k = p.direct ? nullptr
-                            : (mode == VND_MODE_FAST ? fast_epi_kernel(p) : ordered_epi_kernel(p, arithmetic_of(t, mode)));
-        fused = k != nullptr && p.cg == 2;
-    }
+    const ScanRoute route = scan_route(ctx, t, n, in_channels, mode);
+    const Plan &p = route.p;
+    const bool fused = route.fused;
     int64_t ws = 0;                                        // unfused: the moments pass's own partial sums
     vnd_polar_moments_workspace_bytes(n, pairs, &ws);
     const size_t out_bytes = (size_t)pairs * kMoments * sizeof(double);
