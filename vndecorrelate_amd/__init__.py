@@ -35,9 +35,14 @@ from .analysis import (  # noqa: F401
     correlogram_voice_spans,
     cross_correlogram_batched,
     cross_correlogram_voice_pool,
+    lissajous_histogram_batched,
+    polar_coordinates_batched,
+    polar_histogram_batched,
     polar_moments_ordered,
     polar_voice_spans,
+    scope_covers,
     set_correlogram_device,
+    set_scope_device,
     stereo_image_voice_pool,
 )
 from .streaming import (  # noqa: F401

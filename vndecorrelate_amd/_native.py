@@ -349,6 +349,34 @@ POLAR_VOICE_STREAM_SIGNATURES = {
     'vnd_polar_voice_stream_f64_dev': (ctypes.c_int, _POLAR_VOICE_STREAM_ARGS),
 }
 
+# include/vnd_scope.h: the vectorscope's data - the polar sample of every frame of a pool, and the polar and Lissajous count
+# grids, float32 or float64 frames
+_POLAR_COORDS_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                      ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                      ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+_POLAR_HIST_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                    ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_void_p, ctypes.c_int32,
+                    ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                    ctypes.c_int64, ctypes.c_void_p]
+_LISSAJOUS_HIST_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                        ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+SCOPE_SIGNATURES = {
+    'vnd_scope_work_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+    'vnd_scope_route': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32)]),
+    'vnd_polar_coords_f32_dev': (ctypes.c_int, _POLAR_COORDS_ARGS),
+    'vnd_polar_coords_f64_dev': (ctypes.c_int, _POLAR_COORDS_ARGS),
+    'vnd_polar_hist_f32_dev': (ctypes.c_int, _POLAR_HIST_ARGS),
+    'vnd_polar_hist_f64_dev': (ctypes.c_int, _POLAR_HIST_ARGS),
+    'vnd_lissajous_hist_f32_dev': (ctypes.c_int, _LISSAJOUS_HIST_ARGS),
+    'vnd_lissajous_hist_f64_dev': (ctypes.c_int, _LISSAJOUS_HIST_ARGS),
+}
+SCOPE_MAX_BINS = 4096             # VND_SCOPE_MAX_BINS
+SCOPE_LDS_BYTES = 163840          # VND_SCOPE_LDS_BYTES
+SCOPE_SPAN_FRAMES = 32768         # VND_SCOPE_SPAN_FRAMES
+SCOPE_DIRECT_SPAN_FRAMES = 4096   # VND_SCOPE_DIRECT_SPAN_FRAMES
+SCOPE_ROUTE_LDS, SCOPE_ROUTE_DIRECT = 1, 2
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -404,7 +432,8 @@ def load_library():
                                   + list(VOICE_STREAM_SIGNATURES.items())
                                   + list(HAAS_VOICE_STREAM_SIGNATURES.items())
                                   + list(CORRELOGRAM_VOICE_STREAM_SIGNATURES.items())
-                                  + list(POLAR_VOICE_STREAM_SIGNATURES.items())):
+                                  + list(POLAR_VOICE_STREAM_SIGNATURES.items())
+                                  + list(SCOPE_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -1014,6 +1043,62 @@ def describe_polar_voice_stream(slots: int, max_frames_per_call: int, sample_byt
     _check(load_library().vnd_describe_polar_voice_stream_launch(slots, max_frames_per_call, sample_bytes, buf, 512),
            'vnd_describe_polar_voice_stream_launch')
     return buf.value.decode()
+
+
+def scope_work_bytes(batch: int) -> int:
+    """``vnd_scope_work_bytes``: the work memory of the per-signal maximum for a pool of ``batch`` signals."""
+    need = ctypes.c_int64()
+    _check(load_library().vnd_scope_work_bytes(batch, ctypes.byref(need)), 'vnd_scope_work_bytes')
+    return need.value
+
+
+def scope_route(bins0: int, bins1: int, used_frames: int) -> int:
+    """``vnd_scope_route``: the route (``SCOPE_ROUTE_LDS`` or ``SCOPE_ROUTE_DIRECT``) a histogram of this shape takes now."""
+    route = ctypes.c_int32()
+    _check(load_library().vnd_scope_route(bins0, bins1, used_frames, ctypes.byref(route)), 'vnd_scope_route')
+    return route.value
+
+
+def polar_coords_device(ctx: 'Context', l_ptr: int, r_ptr: int, batch: int, n: int, stream_stride: int, frame_stride: int,
+                        radii_ptr: int, thetas_ptr: int, *, ms_mode: bool = True, semicircular: bool = True,
+                        normalize: bool = True, work_ptr: int = 0, work_bytes: int = 0, float64: bool = False,
+                        stream: int = 0):
+    """``vnd_polar_coords_f32_dev`` (``_f64_dev`` with ``float64``): the polar sample of every frame of a pool (frame t of
+    signal b at ``b * stream_stride + t * frame_stride`` elements of ``l_ptr`` / ``r_ptr``) into ``(batch, n)`` radii and
+    thetas of the sample type, all device memory, enqueued on ``stream``."""
+    name = 'vnd_polar_coords_f64_dev' if float64 else 'vnd_polar_coords_f32_dev'
+    _check(getattr(ctx._lib, name)(
+        ctx.handle, ctypes.c_void_p(l_ptr), ctypes.c_void_p(r_ptr), batch, n, stream_stride, frame_stride,
+        int(bool(ms_mode)), int(bool(semicircular)), int(bool(normalize)), ctypes.c_void_p(radii_ptr),
+        ctypes.c_void_p(thetas_ptr), ctypes.c_void_p(work_ptr), work_bytes, ctypes.c_void_p(stream)), name)
+
+
+def polar_hist_device(ctx: 'Context', l_ptr: int, r_ptr: int, batch: int, n: int, stream_stride: int, frame_stride: int,
+                      angle_edges_ptr: int, num_angle_bins: int, radius_edges_ptr: int, num_radius_bins: int,
+                      counts_ptr: int, *, ms_mode: bool = True, semicircular: bool = True, radius_scale: float = 0.0,
+                      n_each_ptr: int = 0, accumulate: bool = False, work_ptr: int = 0, work_bytes: int = 0,
+                      float64: bool = False, stream: int = 0):
+    """``vnd_polar_hist_f32_dev`` (``_f64_dev`` with ``float64``): the polar count grid of a pool, uint32 ``(batch,
+    num_angle_bins, num_radius_bins)``, against float64 device edges; ``radius_scale`` 0 is the per-signal maximum."""
+    name = 'vnd_polar_hist_f64_dev' if float64 else 'vnd_polar_hist_f32_dev'
+    _check(getattr(ctx._lib, name)(
+        ctx.handle, ctypes.c_void_p(l_ptr), ctypes.c_void_p(r_ptr), batch, n, stream_stride, frame_stride,
+        int(bool(ms_mode)), int(bool(semicircular)), float(radius_scale), ctypes.c_void_p(angle_edges_ptr), num_angle_bins,
+        ctypes.c_void_p(radius_edges_ptr), num_radius_bins, ctypes.c_void_p(n_each_ptr), ctypes.c_void_p(counts_ptr),
+        int(bool(accumulate)), ctypes.c_void_p(work_ptr), work_bytes, ctypes.c_void_p(stream)), name)
+
+
+def lissajous_hist_device(ctx: 'Context', l_ptr: int, r_ptr: int, batch: int, n: int, stream_stride: int, frame_stride: int,
+                          x_edges_ptr: int, x_bins: int, y_edges_ptr: int, y_bins: int, counts_ptr: int, *,
+                          frame_step: int = 1, n_each_ptr: int = 0, accumulate: bool = False, float64: bool = False,
+                          stream: int = 0):
+    """``vnd_lissajous_hist_f32_dev`` (``_f64_dev`` with ``float64``): the L/R count grid of every ``frame_step``-th frame
+    of a pool, uint32 ``(batch, x_bins, y_bins)``, L on the first axis."""
+    name = 'vnd_lissajous_hist_f64_dev' if float64 else 'vnd_lissajous_hist_f32_dev'
+    _check(getattr(ctx._lib, name)(
+        ctx.handle, ctypes.c_void_p(l_ptr), ctypes.c_void_p(r_ptr), batch, n, stream_stride, frame_stride, frame_step,
+        ctypes.c_void_p(x_edges_ptr), x_bins, ctypes.c_void_p(y_edges_ptr), y_bins, ctypes.c_void_p(n_each_ptr),
+        ctypes.c_void_p(counts_ptr), int(bool(accumulate)), ctypes.c_void_p(stream)), name)
 
 
 def haas_scan_workspace_bytes(n: int, n_delays: int, max_delay: int) -> int:

@@ -32,6 +32,20 @@ __device__ __forceinline__ void polar_add(PolarAcc &a, float l, float r)
     a.rr += (double)(r * r);
 }
 
+// The sample alone, for the vectorscope (vnd_scope.hpp): polar_add's theta and radius with polar_coordinates' two options
+// open - `ms` false is LayoutMode.LR, atan2f(l, r); `fold` false keeps the whole circle.  The coordinates kernel and the
+// histogram kernels all take their sample from here, so a count grid is the grid of the thetas and radii written out.
+__device__ __forceinline__ void polar_sample(float l, float r, bool ms, bool fold, float &th, float &rad)
+{
+    const float kHalfPi = 1.57079632679489661923f, kPi = 3.14159265358979323846f;   // float32(np.pi / 2), float32(np.pi)
+    th = ms ? atan2f(l - r, l + r) : atan2f(l, r);
+    if (fold) {
+        if (th < -kHalfPi) th = th + kPi;
+        else if (th > kHalfPi) th = th - kPi;
+    }
+    rad = sqrtf(l * l + r * r);
+}
+
 __device__ __forceinline__ void polar_store(double *out, const PolarAcc &a)
 {
     out[0] = a.s0; out[1] = a.s1; out[2] = a.s2; out[3] = a.s3;
@@ -63,6 +77,18 @@ __device__ __forceinline__ void polar_add64(PolarAcc64 &a, double l, double r)
     a.lr += l * r;
     a.ll += l * l;
     a.rr += r * r;
+}
+
+// polar_sample for float64 frames
+__device__ __forceinline__ void polar_sample64(double l, double r, bool ms, bool fold, double &th, double &rad)
+{
+    const double kHalfPi = 1.5707963267948966, kPi = 3.141592653589793;          // np.pi / 2, np.pi
+    th = ms ? atan2(l - r, l + r) : atan2(l, r);
+    if (fold) {
+        if (th < -kHalfPi) th = th + kPi;
+        else if (th > kHalfPi) th = th - kPi;
+    }
+    rad = sqrt(l * l + r * r);
 }
 
 __device__ __forceinline__ void polar_values64(double v[kMoments], const PolarAcc64 &a)

@@ -109,6 +109,8 @@ struct SpecTable {
     X("VND_WIN_CHUNKS", win_chunks, 1) X("VND_WIN_BALANCE", win_balance, 1) X("VND_WIN_CHUNK_LEN0", win_chunk_len0, 0) \
     X("VND_WIN_STAGGER_TICKS", win_stagger_ticks, 300) X("VND_WIN_PACE", win_pace, 1) X("VND_WIN_PACE_MIN_TILES", win_pace_min_tiles, 16) \
     X("VND_NT_MIN_MB", nt_min_mb, 64) X("VND_NO_NT", no_nt, 0) X("VND_FORCE_NT", force_nt, 0) \
+    /* the vectorscope's histogram route (vnd_scope.hpp): 1 LDS-private, 2 direct, otherwise the entry's choice */ \
+    X("VND_SCOPE_ROUTE", scope_route, 0) \
     /* diagnosis builds */ \
     X("VND_WIN_STAMPS", win_stamps, 0) X("VND_WIN_STAMP_PHASES", win_stamp_phases, 1) X("VND_WIN_STAMP_WAVE", win_stamp_wave, 0)
 

@@ -1,0 +1,415 @@
+"""The vectorscope's data on the GPU (include/vnd_scope.h): what ``utils/plot.py`` reduces a signal to before it draws.
+
+The reference looks at a decorrelated signal through ``plot_polar_sample`` and ``plot_lissajous``; both are matplotlib
+around two steps that touch every frame - ``polar_coordinates(L, R, compute_weights=False)`` and ``np.histogram2d``.  Here
+those two steps run on the device for a whole pool, so a pool of voices that lives in device memory never comes down to be
+looked at:
+
+* :func:`polar_coordinates_batched` - ``(radii, thetas)`` of every frame of a pool (``vnd_polar_coords_*_dev``);
+* :func:`polar_histogram_batched` - the count grid of ``plot_polar_sample``'s heatmap, fused: no theta or radius is written
+  (``vnd_polar_hist_*_dev``);
+* :func:`lissajous_histogram_batched` - the count grid of ``plot_lissajous(color_mode='density')``
+  (``vnd_lissajous_hist_*_dev``);
+* :func:`set_scope_device` and the pure routing rule :func:`scope_covers`, through ``analysis.device_route``.
+
+Counts are integers: a grid equals ``np.histogram2d`` of the same coordinates cell for cell, whatever the route
+(``VND_SCOPE_ROUTE``) and the run.  The coordinates are NumPy 2's arithmetic on the sample type except for the
+last bits of ``atan2`` (two libm implementations).  Without a device, or for a call the device does not cover, every
+function is the NumPy loop: ``utils.dsp.polar_coordinates`` and ``np.histogram2d`` per signal.  Drawing, the heatmap's
+smoothing and ``log1p``, the pseudo hull and ``compute_weights=True`` are not here.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+
+from . import _native
+from .utils.dsp import LayoutMode, polar_coordinates
+
+MAX_BINS = _native.SCOPE_MAX_BINS
+SPAN_FRAMES = _native.SCOPE_SPAN_FRAMES               # frames of one signal per workgroup on the LDS-private route
+DIRECT_SPAN_FRAMES = _native.SCOPE_DIRECT_SPAN_FRAMES
+LDS_BYTES = _native.SCOPE_LDS_BYTES
+ROUTE_LDS, ROUTE_DIRECT = _native.SCOPE_ROUTE_LDS, _native.SCOPE_ROUTE_DIRECT
+_MAX_FRAMES = 2 ** 32 - 1                             # counts are uint32
+_MAX_BATCH = 65535                                    # VND_MAX_STREAMS
+_MAX_GROUPS = 2 ** 23
+_COORDS_SPAN = 2048                                   # the smallest span of any kernel: bounds every launch
+_torch = _native.torch_module
+
+_scope_device: Optional[bool] = None
+_edges_cache: dict = {}
+
+
+def set_scope_device(enabled: Optional[bool]) -> None:
+    """Where the three functions of this module run.
+
+    ``None`` (default): on the GPU when a gfx950 device is present and the call is covered (:func:`scope_covers`),
+    otherwise the NumPy code.  ``True``: the device for every covered call; such a call raises ``RuntimeError`` when
+    there is no device.  ``False``: always NumPy."""
+    global _scope_device
+    if enabled is not None and not isinstance(enabled, (bool, np.bool_)):
+        raise TypeError(f'set_scope_device takes True, False or None, not {enabled!r}')
+    _scope_device = None if enabled is None else bool(enabled)
+
+
+def scope_covers(dtype, batch: int, n_frames: int, bins0: int = 1, bins1: int = 1) -> bool:
+    """Whether a pool of ``batch`` signals of ``n_frames`` frames of ``dtype`` has a device form, for a grid of ``bins0`` x
+    ``bins1`` cells: float32 or float64 frames, 1 <= batch <= 65535, 1 <= n_frames < 2^32, bins of 1..MAX_BINS an axis and
+    at most 2^23 workgroups in a launch.  Everything else keeps the NumPy code and its exceptions (an empty signal:
+    ``ValueError`` from ``max``)."""
+    try:
+        if np.dtype(dtype) not in (np.dtype(np.float32), np.dtype(np.float64)):
+            return False
+    except TypeError:
+        return False
+    for v in (batch, n_frames, bins0, bins1):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, (bool, np.bool_)):
+            return False
+    if not 1 <= batch <= _MAX_BATCH or not 1 <= n_frames <= _MAX_FRAMES:
+        return False
+    if not 1 <= bins0 <= MAX_BINS or not 1 <= bins1 <= MAX_BINS:
+        return False
+    return batch * (-(-n_frames // _COORDS_SPAN)) <= _MAX_GROUPS
+
+
+def use_device(dtype, batch: int, n_frames: int, bins0: int = 1, bins1: int = 1) -> bool:
+    """The routing decision of one call: :func:`scope_covers` and :func:`set_scope_device`."""
+    from .analysis import device_route
+    return device_route(_scope_device, scope_covers(dtype, batch, n_frames, bins0, bins1),
+                        'set_scope_device(True): no gfx950 device (or no built extension) to run on')
+
+
+# ---- the binning rule ------------------------------------------------------------------------------------------------
+def histogram_bins(values, edges) -> np.ndarray:
+    """The device's binning rule in NumPy, which is ``np.histogramdd``'s: the bin of each value on ascending ``edges``
+    (``edges[k] <= v < edges[k + 1]``, ``v == edges[-1]`` in the last bin), -1 for a value that is dropped (outside the
+    range, NaN, +-inf)."""
+    edges = np.asarray(edges, np.float64)
+    v = np.asarray(values).astype(np.float64)
+    k = np.searchsorted(edges, v, side='right')
+    k[v == edges[-1]] -= 1
+    k -= 1
+    k[(k < 0) | (k >= len(edges) - 1)] = -1
+    return k
+
+
+def histogram_counts(v0, v1, edges0, edges1) -> np.ndarray:
+    """The count grid of coordinate pairs under :func:`histogram_bins`: int64 ``(len(edges0) - 1, len(edges1) - 1)``,
+    equal to ``np.histogram2d(v0, v1, [edges0, edges1])[0]`` cell for cell."""
+    k0, k1 = histogram_bins(v0, edges0), histogram_bins(v1, edges1)
+    keep = (k0 >= 0) & (k1 >= 0)
+    grid = np.zeros((len(edges0) - 1, len(edges1) - 1), np.int64)
+    np.add.at(grid, (k0[keep], k1[keep]), 1)
+    return grid
+
+
+def polar_edges(num_angle_bins: int = 240, num_radius_bins: int = 150):
+    """``plot_polar_sample``'s edges: degrees on [-90, 90] and normalised radii on [0, 1]."""
+    return np.linspace(-90.0, 90.0, num_angle_bins + 1), np.linspace(0.0, 1.0, num_radius_bins + 1)
+
+
+def lissajous_edges(bins=512, range=((-1.1, 1.1), (-1.1, 1.1))):      # noqa: A002 - np.histogram2d's name
+    """``np.histogram2d(..., bins=bins, range=range)``'s edges: ``np.linspace(lo, hi, bins + 1)`` an axis."""
+    bx, by = (bins, bins) if isinstance(bins, (int, np.integer)) else bins
+    (x0, x1), (y0, y1) = range
+    return np.linspace(float(x0), float(x1), int(bx) + 1), np.linspace(float(y0), float(y1), int(by) + 1)
+
+
+def lissajous_step(n_frames: int, max_points: Optional[int]) -> int:
+    """``plot_lissajous``'s decimation: every ``n // max_points``-th frame when ``n > max_points``."""
+    if max_points is None:
+        return 1
+    if isinstance(max_points, (bool, np.bool_)) or not isinstance(max_points, (int, np.integer)) or max_points < 1:
+        raise ValueError(f'max_points must be a positive integer or None, not {max_points!r}')
+    return n_frames // int(max_points) if n_frames > max_points else 1
+
+
+# ---- shapes ----------------------------------------------------------------------------------------------------------
+def _pool_shape(pool):
+    shape = tuple(pool.shape)
+    if len(shape) == 2 and shape[1] == 2:
+        return True, (1,) + shape
+    if len(shape) == 3 and shape[2] == 2:
+        return False, shape
+    raise ValueError(f'pool must be (batch, n, 2), or (n, 2) for one signal: got shape {shape}')
+
+
+def _mode(mode) -> bool:
+    if mode == LayoutMode.MS:
+        return True
+    if mode == LayoutMode.LR:
+        return False
+    raise ValueError(f"mode must be 'MS' or 'LR', not {mode!r}")
+
+
+def _bins(n, what: str) -> int:
+    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError(f'{what} must be a positive integer, not {n!r}')
+    return int(n)
+
+
+def _scale(radius_scale, accumulate: bool):
+    if radius_scale is None:
+        if accumulate:
+            raise ValueError('accumulate=True needs a fixed radius_scale: the per-signal maximum of a later block would '
+                             'rescale the earlier frames')
+        return None
+    scale = float(radius_scale)
+    if not (scale > 0.0 and np.isfinite(scale)):
+        raise ValueError(f'radius_scale must be a positive finite number or None, not {radius_scale!r}')
+    return scale
+
+
+def _host_n_each(counts, batch: int, n: int):
+    """Frames each signal contributes on the host route: ``counts`` outside ``[0, n]`` contributes none."""
+    if counts is None:
+        return [n] * batch
+    if _native.is_torch(counts):
+        counts = counts.detach().cpu().numpy()
+    c = np.asarray(counts).astype(np.int64).reshape(-1)
+    if len(c) != batch:
+        raise ValueError(f'counts must have one entry per signal: got {len(c)} for {batch}')
+    return [int(v) if 0 <= v <= n else 0 for v in c]
+
+
+def _device_of(pool):
+    """The context's torch device when ``pool`` is a tensor on it, else None."""
+    try:
+        torch = _torch()
+        device = torch.device('cuda', _native.default_context().device)
+    except RuntimeError:
+        return None
+    return device if pool.device == device else None
+
+
+def _tensor_channels(pool):
+    """Device pointers and strides of the channels of a (B, n, 2) tensor: ``(l_ptr, r_ptr, stream_stride, frame_stride,
+    keep)``."""
+    if pool.stride(2) != 1 or pool.stride(1) < 1 or (pool.shape[0] > 1 and pool.stride(0) < 1):
+        pool = pool.contiguous()
+    return (pool.data_ptr(), pool.data_ptr() + pool.element_size(), max(1, pool.stride(0)), pool.stride(1), pool)
+
+
+def _device_edges(torch, device, e0: np.ndarray, e1: np.ndarray):
+    """The two edge arrays on the device, uploaded once per distinct pair: a later call - or a graph capture - copies
+    nothing from the host."""
+    key = (str(device), e0.tobytes(), e1.tobytes())
+    got = _edges_cache.get(key)
+    if got is None:
+        if len(_edges_cache) >= 64:
+            _edges_cache.clear()
+        got = (torch.from_numpy(e0.copy()).to(device), torch.from_numpy(e1.copy()).to(device))
+        _edges_cache[key] = got
+    return got
+
+
+def _device_counts(torch, counts, batch: int, device):
+    if counts is None:
+        return None
+    if not _native.is_torch(counts):
+        counts = torch.from_numpy(np.ascontiguousarray(counts, np.int32))
+    if counts.dtype != torch.int32 or tuple(counts.shape) != (batch,):
+        raise ValueError(f'counts must be int32 of shape ({batch},): got {counts.dtype} {tuple(counts.shape)}')
+    return counts.to(device).contiguous()
+
+
+def _device_out(torch, out, shape, device, accumulate: bool):
+    if out is None:
+        if accumulate:
+            raise ValueError('accumulate=True needs the grid to add to: pass out=')
+        return torch.empty(shape, dtype=torch.int32, device=device)
+    if not _native.is_torch(out) or out.dtype != torch.int32 or tuple(out.shape) != tuple(shape) \
+            or out.device != device or not out.is_contiguous():
+        raise ValueError(f'out must be a contiguous int32 tensor of shape {tuple(shape)} on {device}')
+    return out
+
+
+def _host_out(out, grid: np.ndarray, accumulate: bool) -> np.ndarray:
+    if out is None:
+        if accumulate:
+            raise ValueError('accumulate=True needs the grid to add to: pass out=')
+        return grid
+    if not isinstance(out, np.ndarray) or out.shape != grid.shape:
+        raise ValueError(f'out must be a NumPy array of shape {grid.shape}')
+    if accumulate:
+        out += grid.astype(out.dtype)
+    else:
+        out[...] = grid
+    return out
+
+
+def _dtype_of(pool) -> np.dtype:
+    if not _native.is_torch(pool):
+        return np.asarray(pool).dtype
+    try:
+        return np.dtype(str(pool.dtype).replace('torch.', ''))
+    except TypeError:                                     # a torch dtype NumPy has no name for: not covered
+        return np.dtype(object)
+
+
+def _to_host(pool) -> np.ndarray:
+    return pool.detach().cpu().numpy() if _native.is_torch(pool) else np.asarray(pool)
+
+
+# ---- polar coordinates -----------------------------------------------------------------------------------------------
+def polar_coordinates_batched(pool, mode=LayoutMode.MS, semicircular: bool = True, normalize: bool = True):
+    """``polar_coordinates(pool[b, :, 0], pool[b, :, 1], mode, semicircular, normalize, compute_weights=False)`` for every
+    signal of a ``(B, n, 2)`` pool (``(n, 2)``: one signal): ``(radii, thetas)``, each ``(B, n)`` (``(n,)``) of the pool's
+    dtype.  ``normalize`` divides each signal's radii by its own maximum plus ``EPSILON``.  A float32 or float64 tensor on
+    the device in gives device tensors out, with nothing synchronised; NumPy in gives NumPy out.  On the device the radii
+    are NumPy's bit for bit, and the thetas within the last bits of ``atan2``."""
+    ms = _mode(mode)
+    single, (batch, n, _) = _pool_shape(pool)
+    is_tensor = _native.is_torch(pool)
+    dtype = _dtype_of(pool)
+    if use_device(dtype, batch, n) and (not is_tensor or _device_of(pool) is not None):
+        torch = _torch()
+        ctx = _native.default_context()
+        device = torch.device('cuda', ctx.device)
+        pd = (pool if is_tensor else torch.from_numpy(np.ascontiguousarray(pool)).to(device)).reshape(batch, n, 2)
+        lp, rp, ss, fs, keep = _tensor_channels(pd)
+        radii = torch.empty((batch, n), dtype=pd.dtype, device=device)
+        thetas = torch.empty((batch, n), dtype=pd.dtype, device=device)
+        work = torch.empty((batch,), dtype=torch.int64, device=device) if normalize else None
+        _native.polar_coords_device(ctx, lp, rp, batch, n, ss, fs, radii.data_ptr(), thetas.data_ptr(), ms_mode=ms,
+                                    semicircular=semicircular, normalize=normalize,
+                                    work_ptr=work.data_ptr() if normalize else 0, work_bytes=batch * 8 if normalize else 0,
+                                    float64=dtype == np.float64, stream=torch.cuda.current_stream(device).cuda_stream)
+        del keep
+        if single:
+            radii, thetas = radii[0], thetas[0]
+        return (radii, thetas) if is_tensor else (radii.cpu().numpy(), thetas.cpu().numpy())
+
+    host = _to_host(pool).reshape(batch, n, 2)
+    pairs = [polar_coordinates(host[b, :, 0], host[b, :, 1], LayoutMode.MS if ms else LayoutMode.LR, semicircular, normalize,
+                               compute_weights=False) for b in range(batch)]
+    radii = np.stack([p[0] for p in pairs]) if pairs else np.zeros((0, n), host.dtype)
+    thetas = np.stack([p[1] for p in pairs]) if pairs else np.zeros((0, n), host.dtype)
+    if single:
+        radii, thetas = radii[0], thetas[0]
+    if is_tensor:
+        torch = _torch()
+        return torch.from_numpy(radii).to(pool.device), torch.from_numpy(thetas).to(pool.device)
+    return radii, thetas
+
+
+# ---- histograms ------------------------------------------------------------------------------------------------------
+def _histogram(pool, e0: np.ndarray, e1: np.ndarray, counts, out, accumulate: bool, *, polar: bool, ms: bool = True,
+               semicircular: bool = True, scale: Optional[float] = None, step: int = 1):
+    """Both grids, on either route: ``(grid, edges0, edges1)``."""
+    single, (batch, n, _) = _pool_shape(pool)
+    bins0, bins1 = len(e0) - 1, len(e1) - 1
+    shape = (bins0, bins1) if single else (batch, bins0, bins1)
+    is_tensor = _native.is_torch(pool)
+    dtype = _dtype_of(pool)
+    if use_device(dtype, batch, n, bins0, bins1) and (not is_tensor or _device_of(pool) is not None):
+        torch = _torch()
+        ctx = _native.default_context()
+        device = torch.device('cuda', ctx.device)
+        pd = (pool if is_tensor else torch.from_numpy(np.ascontiguousarray(pool)).to(device)).reshape(batch, n, 2)
+        lp, rp, ss, fs, keep = _tensor_channels(pd)
+        d0, d1 = _device_edges(torch, device, e0, e1)
+        each = _device_counts(torch, counts, batch, device)
+        if is_tensor:
+            grid = _device_out(torch, out, shape, device, accumulate)
+        else:
+            if accumulate and out is None:
+                raise ValueError('accumulate=True needs the grid to add to: pass out=')
+            grid = torch.empty(shape, dtype=torch.int32, device=device)
+        stream = torch.cuda.current_stream(device).cuda_stream
+        on_device = is_tensor and accumulate
+        kw = dict(n_each_ptr=each.data_ptr() if each is not None else 0, accumulate=on_device, float64=dtype == np.float64,
+                  stream=stream)
+        if polar:
+            by_max = scale is None
+            work = torch.empty((batch,), dtype=torch.int64, device=device) if by_max else None
+            _native.polar_hist_device(ctx, lp, rp, batch, n, ss, fs, d0.data_ptr(), bins0, d1.data_ptr(), bins1, grid.data_ptr(),
+                                      ms_mode=ms, semicircular=semicircular, radius_scale=0.0 if by_max else scale,
+                                      work_ptr=work.data_ptr() if by_max else 0, work_bytes=batch * 8 if by_max else 0, **kw)
+        else:
+            _native.lissajous_hist_device(ctx, lp, rp, batch, n, ss, fs, d0.data_ptr(), bins0, d1.data_ptr(), bins1,
+                                          grid.data_ptr(), frame_step=step, **kw)
+        del keep
+        if is_tensor:
+            return grid, d0.clone(), d1.clone()
+        host_grid = grid.cpu().numpy().view(np.uint32).astype(np.float64)
+        return _host_out(out, host_grid, accumulate), e0, e1
+
+    host = _to_host(pool).reshape(batch, n, 2)
+    each_host = _host_n_each(counts, batch, n)
+    grids = np.zeros((batch, bins0, bins1), np.float64)
+    for b, m in enumerate(each_host):
+        left, right = host[b, :m, 0], host[b, :m, 1]
+        if m == 0:
+            continue
+        if polar:
+            radii, thetas = polar_coordinates(left, right, LayoutMode.MS if ms else LayoutMode.LR, semicircular,
+                                              scale is None, compute_weights=False)
+            if scale is not None:
+                radii = radii / radii.dtype.type(scale)
+            grids[b] = np.histogram2d(np.degrees(thetas), radii, bins=[e0, e1])[0]
+        else:
+            grids[b] = np.histogram2d(left[::step], right[::step], bins=[e0, e1])[0]
+    grids = grids.reshape(shape)
+    if is_tensor:
+        torch = _torch()
+        as_tensor = torch.from_numpy(grids.astype(np.int64).astype(np.uint32).view(np.int32)).to(pool.device)
+        if out is not None:
+            if not _native.is_torch(out) or out.dtype != torch.int32 or tuple(out.shape) != tuple(shape):
+                raise ValueError(f'out must be an int32 tensor of shape {tuple(shape)}')
+            if accumulate:
+                out += as_tensor.to(out.device)
+            else:
+                out.copy_(as_tensor)
+            as_tensor = out
+        elif accumulate:
+            raise ValueError('accumulate=True needs the grid to add to: pass out=')
+        return as_tensor, torch.from_numpy(e0.copy()).to(pool.device), torch.from_numpy(e1.copy()).to(pool.device)
+    return _host_out(out, grids, accumulate), e0, e1
+
+
+def polar_histogram_batched(pool, num_angle_bins: int = 240, num_radius_bins: int = 150, *, radius_scale=None, counts=None,
+                            out=None, accumulate: bool = False, mode=LayoutMode.MS, semicircular: bool = True):
+    """The count grid of ``plot_polar_sample``'s heatmap for every signal of a ``(B, n, 2)`` pool (``(n, 2)``: one signal):
+    ``(grid, angle_edges, radius_edges)`` with ``grid[b] == np.histogram2d(np.degrees(thetas), radii, bins=[angle_edges,
+    radius_edges])[0]`` of that signal's polar sample, edges ``np.linspace(-90, 90, num_angle_bins + 1)`` degrees and
+    ``np.linspace(0, 1, num_radius_bins + 1)``.
+
+    ``radius_scale`` None: the reference's radii, normalised by each signal's own maximum.  A positive number: ``radii /
+    radius_scale`` instead, which does not depend on the rest of the signal - so blocks of a signal can be added up:
+    ``accumulate=True`` adds to the grid passed as ``out`` (and needs a ``radius_scale``).  ``counts``: optional int32
+    ``(B,)``, signal b is its first ``counts[b]`` frames (a value outside ``[0, n]``: none) - the ``out_counts`` of a voice
+    pool or a block stream, read on the device.
+
+    A float32 or float64 tensor on the device in gives device tensors out with nothing synchronised - the grid an int32
+    tensor holding the uint32 counts (``out``, when given, is such a tensor); the device edges are uploaded on the first
+    call with a grid size, so warm a call up before capturing one in a graph.  NumPy in gives NumPy out, the grid float64 as
+    ``np.histogram2d`` returns it."""
+    bins0, bins1 = _bins(num_angle_bins, 'num_angle_bins'), _bins(num_radius_bins, 'num_radius_bins')
+    scale = _scale(radius_scale, accumulate)
+    e0, e1 = polar_edges(bins0, bins1)
+    return _histogram(pool, e0, e1, counts, out, accumulate, polar=True, ms=_mode(mode), semicircular=semicircular,
+                      scale=scale)
+
+
+def lissajous_histogram_batched(pool, bins=512, range=((-1.1, 1.1), (-1.1, 1.1)), *, max_points: Optional[int] = None,  # noqa: A002
+                                counts=None, out=None, accumulate: bool = False):
+    """The count grid of ``plot_lissajous(color_mode='density')`` for every signal of a ``(B, n, 2)`` pool (``(n, 2)``: one
+    signal): ``(grid, x_edges, y_edges)`` with ``grid[b] == np.histogram2d(left, right, bins=bins, range=range)[0]``, L on
+    the first axis.  ``max_points``: as the reference, every ``n // max_points``-th frame when ``n > max_points``
+    (``left[::step]``).  ``counts``, ``out``, ``accumulate`` and the tensor / NumPy forms as in
+    :func:`polar_histogram_batched`."""
+    e0, e1 = lissajous_edges(bins, range)
+    if len(e0) < 2 or len(e1) < 2 or not (np.all(np.diff(e0) > 0) and np.all(np.diff(e1) > 0)
+                                          and np.all(np.isfinite(e0)) and np.all(np.isfinite(e1))):
+        raise ValueError(f'bins {bins!r} and range {range!r} do not give ascending finite edges')
+    _, (_, n, _) = _pool_shape(pool)
+    step = lissajous_step(n, max_points)
+    return _histogram(pool, e0, e1, counts, out, accumulate, polar=False, step=step)
+
+
+__all__ = ['polar_coordinates_batched', 'polar_histogram_batched', 'lissajous_histogram_batched', 'set_scope_device',
+           'scope_covers', 'histogram_bins', 'histogram_counts', 'polar_edges', 'lissajous_edges', 'lissajous_step',
+           'SPAN_FRAMES', 'DIRECT_SPAN_FRAMES', 'MAX_BINS', 'ROUTE_LDS', 'ROUTE_DIRECT']
