@@ -38,6 +38,7 @@ from .analysis import (  # noqa: F401
     lissajous_histogram_batched,
     polar_coordinates_batched,
     polar_histogram_batched,
+    polar_level_batched,
     polar_moments_ordered,
     polar_voice_spans,
     scope_covers,

@@ -377,6 +377,21 @@ SCOPE_SPAN_FRAMES = 32768         # VND_SCOPE_SPAN_FRAMES
 SCOPE_DIRECT_SPAN_FRAMES = 4096   # VND_SCOPE_DIRECT_SPAN_FRAMES
 SCOPE_ROUTE_LDS, SCOPE_ROUTE_DIRECT = 1, 2
 
+# include/vnd_level.h: the polar level envelope - np.percentile of the radii of every angular slice of every signal
+_POLAR_LEVEL_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                     ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_void_p, ctypes.c_int32,
+                     ctypes.POINTER(ctypes.c_double), ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                     ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+LEVEL_SIGNATURES = {
+    'vnd_polar_level_work_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                  ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]),
+    'vnd_polar_level_f32_dev': (ctypes.c_int, _POLAR_LEVEL_ARGS),
+    'vnd_polar_level_f64_dev': (ctypes.c_int, _POLAR_LEVEL_ARGS),
+}
+LEVEL_MAX_PERCENTILES = 4         # VND_LEVEL_MAX_PERCENTILES
+LEVEL_MAX_BINS = 1024             # VND_LEVEL_MAX_BINS
+LEVEL_SPAN_FRAMES = 32768         # VND_LEVEL_SPAN_FRAMES
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -433,7 +448,7 @@ def load_library():
                                   + list(HAAS_VOICE_STREAM_SIGNATURES.items())
                                   + list(CORRELOGRAM_VOICE_STREAM_SIGNATURES.items())
                                   + list(POLAR_VOICE_STREAM_SIGNATURES.items())
-                                  + list(SCOPE_SIGNATURES.items())):
+                                  + list(SCOPE_SIGNATURES.items()) + list(LEVEL_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -1099,6 +1114,31 @@ def lissajous_hist_device(ctx: 'Context', l_ptr: int, r_ptr: int, batch: int, n:
         ctx.handle, ctypes.c_void_p(l_ptr), ctypes.c_void_p(r_ptr), batch, n, stream_stride, frame_stride, frame_step,
         ctypes.c_void_p(x_edges_ptr), x_bins, ctypes.c_void_p(y_edges_ptr), y_bins, ctypes.c_void_p(n_each_ptr),
         ctypes.c_void_p(counts_ptr), int(bool(accumulate)), ctypes.c_void_p(stream)), name)
+
+
+def polar_level_work_bytes(batch: int, n: int, num_bins: int, num_percentiles: int, float64: bool = False) -> int:
+    """``vnd_polar_level_work_bytes``: the work memory of one ``vnd_polar_level_*_dev`` call of this shape."""
+    need = ctypes.c_int64()
+    _check(load_library().vnd_polar_level_work_bytes(batch, n, num_bins, num_percentiles, int(bool(float64)),
+                                                     ctypes.byref(need)), 'vnd_polar_level_work_bytes')
+    return need.value
+
+
+def polar_level_device(ctx: 'Context', l_ptr: int, r_ptr: int, batch: int, n: int, stream_stride: int, frame_stride: int,
+                       angle_edges_ptr: int, num_bins: int, percentiles, levels_ptr: int, bin_counts_ptr: int, *,
+                       work_ptr: int, work_bytes: int, ms_mode: bool = True, semicircular: bool = True,
+                       radius_scale: float = 0.0, n_each_ptr: int = 0, float64: bool = False, stream: int = 0):
+    """``vnd_polar_level_f32_dev`` (``_f64_dev`` with ``float64``): ``np.percentile`` of the radii of every angular slice
+    of every signal of a pool - levels ``(batch, len(percentiles), num_bins)`` of the sample type and uint32 frames per bin
+    ``(batch, num_bins)``, against float64 device edges; ``percentiles`` is a host sequence, read at the call;
+    ``radius_scale`` 0 is the per-signal maximum."""
+    name = 'vnd_polar_level_f64_dev' if float64 else 'vnd_polar_level_f32_dev'
+    ps = (ctypes.c_double * max(1, len(percentiles)))(*[float(p) for p in percentiles])
+    _check(getattr(ctx._lib, name)(
+        ctx.handle, ctypes.c_void_p(l_ptr), ctypes.c_void_p(r_ptr), batch, n, stream_stride, frame_stride,
+        int(bool(ms_mode)), int(bool(semicircular)), float(radius_scale), ctypes.c_void_p(angle_edges_ptr), num_bins,
+        ps, len(percentiles), ctypes.c_void_p(n_each_ptr), ctypes.c_void_p(levels_ptr), ctypes.c_void_p(bin_counts_ptr),
+        ctypes.c_void_p(work_ptr), work_bytes, ctypes.c_void_p(stream)), name)
 
 
 def haas_scan_workspace_bytes(n: int, n_delays: int, max_delay: int) -> int:

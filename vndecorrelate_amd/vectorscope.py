@@ -1,22 +1,26 @@
-"""The vectorscope's data on the GPU (include/vnd_scope.h): what ``utils/plot.py`` reduces a signal to before it draws.
+"""The vectorscope's data on the GPU (include/vnd_scope.h, include/vnd_level.h): what ``utils/plot.py`` reduces a signal to
+before it draws.
 
-The reference looks at a decorrelated signal through ``plot_polar_sample`` and ``plot_lissajous``; both are matplotlib
-around two steps that touch every frame - ``polar_coordinates(L, R, compute_weights=False)`` and ``np.histogram2d``.  Here
-those two steps run on the device for a whole pool, so a pool of voices that lives in device memory never comes down to be
-looked at:
+The reference looks at a decorrelated signal through ``plot_polar_sample``, ``plot_lissajous`` and ``plot_polar_level``; all
+are matplotlib around steps that touch every frame - ``polar_coordinates(L, R, compute_weights=False)``, then
+``np.histogram2d`` or, for the level envelope, ``np.percentile`` per angular slice.  Here those steps run on the device for a
+whole pool, so a pool of voices that lives in device memory never comes down to be looked at:
 
 * :func:`polar_coordinates_batched` - ``(radii, thetas)`` of every frame of a pool (``vnd_polar_coords_*_dev``);
 * :func:`polar_histogram_batched` - the count grid of ``plot_polar_sample``'s heatmap, fused: no theta or radius is written
   (``vnd_polar_hist_*_dev``);
 * :func:`lissajous_histogram_batched` - the count grid of ``plot_lissajous(color_mode='density')``
   (``vnd_lissajous_hist_*_dev``);
+* :func:`polar_level_batched` - the raw envelope of ``plot_polar_level``: ``_build_pseudo_hull``'s per-slice percentiles of
+  the radii, an exact radix select (``vnd_polar_level_*_dev``), with :func:`percentile_rule`, NumPy's rule in one place;
 * :func:`set_scope_device` and the pure routing rule :func:`scope_covers`, through ``analysis.device_route``.
 
 Counts are integers: a grid equals ``np.histogram2d`` of the same coordinates cell for cell, whatever the route
 (``VND_SCOPE_ROUTE``) and the run.  The coordinates are NumPy 2's arithmetic on the sample type except for the
 last bits of ``atan2`` (two libm implementations).  Without a device, or for a call the device does not cover, every
-function is the NumPy loop: ``utils.dsp.polar_coordinates`` and ``np.histogram2d`` per signal.  Drawing, the heatmap's
-smoothing and ``log1p``, the pseudo hull and ``compute_weights=True`` are not here.
+function is the NumPy loop: ``utils.dsp.polar_coordinates`` and ``np.histogram2d`` (``np.percentile`` per slice) per signal.
+Drawing, the heatmap's smoothing and ``log1p``, the envelope's Gaussian smoothing and convex hull, and
+``compute_weights=True`` are not here.
 """
 from __future__ import annotations
 
@@ -32,6 +36,9 @@ SPAN_FRAMES = _native.SCOPE_SPAN_FRAMES               # frames of one signal per
 DIRECT_SPAN_FRAMES = _native.SCOPE_DIRECT_SPAN_FRAMES
 LDS_BYTES = _native.SCOPE_LDS_BYTES
 ROUTE_LDS, ROUTE_DIRECT = _native.SCOPE_ROUTE_LDS, _native.SCOPE_ROUTE_DIRECT
+LEVEL_MAX_BINS = _native.LEVEL_MAX_BINS               # slices of the level envelope on the device
+LEVEL_MAX_PERCENTILES = _native.LEVEL_MAX_PERCENTILES
+LEVEL_SPAN_FRAMES = _native.LEVEL_SPAN_FRAMES         # frames of one signal per workgroup of the level kernels
 _MAX_FRAMES = 2 ** 32 - 1                             # counts are uint32
 _MAX_BATCH = 65535                                    # VND_MAX_STREAMS
 _MAX_GROUPS = 2 ** 23
@@ -410,6 +417,154 @@ def lissajous_histogram_batched(pool, bins=512, range=((-1.1, 1.1), (-1.1, 1.1))
     return _histogram(pool, e0, e1, counts, out, accumulate, polar=False, step=step)
 
 
-__all__ = ['polar_coordinates_batched', 'polar_histogram_batched', 'lissajous_histogram_batched', 'set_scope_device',
-           'scope_covers', 'histogram_bins', 'histogram_counts', 'polar_edges', 'lissajous_edges', 'lissajous_step',
-           'SPAN_FRAMES', 'DIRECT_SPAN_FRAMES', 'MAX_BINS', 'ROUTE_LDS', 'ROUTE_DIRECT']
+# ---- the polar level envelope (include/vnd_level.h) ------------------------------------------------------------------
+def percentile_rule(m: int, p: float, dtype=np.float32):
+    """``np.percentile``'s rule (NumPy 2, ``method='linear'``) for ``m`` values of ``dtype`` and percentile ``p``:
+    ``(prev, next, gamma)`` - the two order statistics it reads, as indices into the sorted values, and the weight between
+    them, a ``dtype`` scalar.  Every step is one correctly rounded operation in ``dtype``; it is the arithmetic of the
+    device's init kernel (DESIGN.md §3.21).  ``p`` outside [0, 100], or NaN, raises NumPy's ``ValueError``."""
+    kind = np.dtype(dtype).type
+    if isinstance(m, (bool, np.bool_)) or not isinstance(m, (int, np.integer)) or m < 1:
+        raise ValueError(f'm must be a positive integer, not {m!r}')
+    p = float(p)
+    if not 0.0 <= p <= 100.0:
+        raise ValueError('Percentiles must be in the range [0, 100]')
+    q = kind(p) / kind(100)
+    top = kind(int(m) - 1)
+    v = top * q
+    if v >= top:
+        return int(m) - 1, int(m) - 1, kind(0)
+    prev = int(np.floor(v))
+    return prev, prev + 1, v - kind(prev)
+
+
+def percentile_of_sorted(values: np.ndarray, p: float):
+    """``np.percentile(values, p)`` of ascending ``values`` through :func:`percentile_rule`, bit for bit: NumPy's lerp, every
+    operation rounded on its own in the values' dtype."""
+    kind = values.dtype.type
+    prev, nxt, g = percentile_rule(len(values), p, values.dtype)
+    a, b = values[prev], values[nxt]
+    with np.errstate(invalid='ignore'):
+        d = b - a
+        return b - d * (kind(1) - g) if g >= kind(0.5) else a + d * g
+
+
+def level_edges(num_bins: int = 360):
+    """``_build_pseudo_hull``'s slices: ``(bin_edges, bin_centers)`` in degrees on [-90, 90]."""
+    edges = np.linspace(-90.0, 90.0, num_bins + 1)
+    return edges, 0.5 * (edges[:-1] + edges[1:])
+
+
+def _percentiles(percentiles):
+    ps = [float(p) for p in np.atleast_1d(np.asarray(percentiles, np.float64)).reshape(-1)]
+    if not ps:
+        raise ValueError('percentiles must hold at least one value')
+    for p in ps:
+        if not 0.0 <= p <= 100.0:
+            raise ValueError('Percentiles must be in the range [0, 100]')
+    return ps
+
+
+def level_covers(dtype, batch: int, n_frames: int, num_bins: int, num_percentiles: int) -> bool:
+    """Whether ``polar_level_batched`` of this shape has a device form: :func:`scope_covers` and the two limits of
+    include/vnd_level.h, at most ``LEVEL_MAX_BINS`` slices and ``LEVEL_MAX_PERCENTILES`` percentiles."""
+    return (scope_covers(dtype, batch, n_frames, num_bins, 1) and num_bins <= LEVEL_MAX_BINS
+            and 1 <= num_percentiles <= LEVEL_MAX_PERCENTILES)
+
+
+def _host_levels(left, right, edges, ps, ms: bool, semicircular: bool, scale):
+    """One signal on the host: the reference's mask and ``np.percentile`` per slice."""
+    radii, thetas = polar_coordinates(left, right, LayoutMode.MS if ms else LayoutMode.LR, semicircular, scale is None,
+                                      compute_weights=False)
+    if scale is not None:
+        radii = radii / radii.dtype.type(scale)
+    degrees = np.degrees(thetas)
+    bins = len(edges) - 1
+    levels, counts = np.zeros((len(ps), bins)), np.zeros(bins, np.int64)
+    for k in range(bins):
+        mask = (degrees >= edges[k]) & (degrees < edges[k + 1])
+        counts[k] = np.count_nonzero(mask)
+        if counts[k]:
+            inside = radii[mask]
+            for i, p in enumerate(ps):
+                levels[i, k] = np.percentile(inside, p)
+    return levels, counts
+
+
+def polar_level_batched(pool, num_bins: int = 360, percentiles=(95.0, 50.0), *, radius_scale=None, counts=None,
+                        mode=LayoutMode.MS, semicircular: bool = True):
+    """The raw envelope of ``plot_polar_level`` for every signal of a ``(B, n, 2)`` pool (``(n, 2)``: one signal):
+    ``(levels, bin_counts, bin_edges, bin_centers)`` with ``levels[b, i]`` the ``bin_percentile_radii`` of
+    ``_build_pseudo_hull(np.degrees(thetas), radii, num_bins, percentiles[i], smoothing_sigma=0, use_convex_hull=False)`` of
+    that signal's polar sample - per slice ``edges[k] <= degrees < edges[k + 1]`` of ``np.linspace(-90, 90, num_bins + 1)``,
+    ``np.percentile`` of the radii inside, 0 for an empty slice (a frame at exactly +90 degrees, R = -L with L > 0, is in no
+    slice) - and ``bin_counts[b]`` the frames per slice.  The envelope's smoothing and convex hull work on these ``num_bins``
+    numbers and stay with the caller.
+
+    ``radius_scale``, ``counts``, ``mode`` and ``semicircular`` as in :func:`polar_histogram_batched`.  There is no
+    ``accumulate``: percentiles of blocks do not add up.  ``percentiles`` outside [0, 100] raise NumPy's ``ValueError``.
+
+    A float32 or float64 tensor on the device in gives device tensors out with nothing synchronised: ``levels`` of the
+    pool's dtype, ``bin_counts`` int32 holding uint32; on the device a level is ``np.percentile`` of the device's own radii
+    bit for bit (an exact radix select).  The edges are uploaded on the first call with a ``num_bins``, so
+    warm a call up before capturing one in a graph.  NumPy in gives NumPy out: ``levels`` float64 holding the sample-type
+    values, as the reference's ``np.zeros(num_bins)`` array does, ``bin_counts`` int64.  More than ``LEVEL_MAX_BINS`` slices
+    or ``LEVEL_MAX_PERCENTILES`` percentiles, another dtype, or no device: the NumPy loop."""
+    bins = _bins(num_bins, 'num_bins')
+    ps = _percentiles(percentiles)
+    scale = _scale(radius_scale, False)
+    ms = _mode(mode)
+    edges, centers = level_edges(bins)
+    single, (batch, n, _) = _pool_shape(pool)
+    is_tensor = _native.is_torch(pool)
+    dtype = _dtype_of(pool)
+    from .analysis import device_route
+    on_device = device_route(_scope_device, level_covers(dtype, batch, n, bins, len(ps)),
+                             'set_scope_device(True): no gfx950 device (or no built extension) to run on')
+    if on_device and (not is_tensor or _device_of(pool) is not None):
+        torch = _torch()
+        ctx = _native.default_context()
+        device = torch.device('cuda', ctx.device)
+        pd = (pool if is_tensor else torch.from_numpy(np.ascontiguousarray(pool)).to(device)).reshape(batch, n, 2)
+        lp, rp, ss, fs, keep = _tensor_channels(pd)
+        d_edges, d_centers = _device_edges(torch, device, edges, centers)
+        each = _device_counts(torch, counts, batch, device)
+        is64 = dtype == np.float64
+        levels = torch.empty((batch, len(ps), bins), dtype=pd.dtype, device=device)
+        bin_counts = torch.empty((batch, bins), dtype=torch.int32, device=device)
+        work_bytes = _native.polar_level_work_bytes(batch, n, bins, len(ps), is64)
+        work = torch.empty(((work_bytes + 7) // 8,), dtype=torch.int64, device=device)
+        _native.polar_level_device(ctx, lp, rp, batch, n, ss, fs, d_edges.data_ptr(), bins, ps, levels.data_ptr(),
+                                   bin_counts.data_ptr(), work_ptr=work.data_ptr(), work_bytes=work_bytes, ms_mode=ms,
+                                   semicircular=semicircular, radius_scale=0.0 if scale is None else scale,
+                                   n_each_ptr=each.data_ptr() if each is not None else 0, float64=is64,
+                                   stream=torch.cuda.current_stream(device).cuda_stream)
+        del keep
+        if single:
+            levels, bin_counts = levels[0], bin_counts[0]
+        if is_tensor:
+            return levels, bin_counts, d_edges.clone(), d_centers.clone()
+        return (levels.cpu().numpy().astype(np.float64), bin_counts.cpu().numpy().view(np.uint32).astype(np.int64), edges,
+                centers)
+
+    host = _to_host(pool).reshape(batch, n, 2)
+    levels, bin_counts = np.zeros((batch, len(ps), bins)), np.zeros((batch, bins), np.int64)
+    for b, m in enumerate(_host_n_each(counts, batch, n)):
+        if m:
+            levels[b], bin_counts[b] = _host_levels(host[b, :m, 0], host[b, :m, 1], edges, ps, ms, semicircular, scale)
+    if single:
+        levels, bin_counts = levels[0], bin_counts[0]
+    if is_tensor:
+        torch = _torch()
+        out_dtype = host.dtype if host.dtype in (np.float32, np.float64) else np.float64
+        return (torch.from_numpy(levels.astype(out_dtype)).to(pool.device),
+                torch.from_numpy(bin_counts.astype(np.uint32).view(np.int32)).to(pool.device),
+                torch.from_numpy(edges.copy()).to(pool.device), torch.from_numpy(centers.copy()).to(pool.device))
+    return levels, bin_counts, edges, centers
+
+
+__all__ = ['polar_coordinates_batched', 'polar_histogram_batched', 'lissajous_histogram_batched', 'polar_level_batched',
+           'set_scope_device', 'scope_covers', 'level_covers', 'histogram_bins', 'histogram_counts', 'polar_edges',
+           'lissajous_edges', 'lissajous_step', 'level_edges', 'percentile_rule', 'percentile_of_sorted', 'SPAN_FRAMES',
+           'DIRECT_SPAN_FRAMES', 'MAX_BINS', 'ROUTE_LDS', 'ROUTE_DIRECT', 'LEVEL_MAX_BINS', 'LEVEL_MAX_PERCENTILES',
+           'LEVEL_SPAN_FRAMES']
