@@ -29,8 +29,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native
-from .streaming import (VOICE_END, VOICE_MAX_POSITION, VOICE_START, BlockStream, _check_counts, _check_device_tensors,
-                        _SlotPool)
+from .streaming import VOICE_END, BlockStream, _check_counts, _check_slots, _slot_ints, _SlotPool, _voice_head
 from .utils.dsp import EPSILON, correlogram_sizes, to_float32
 
 MAX_WINDOW = _native.CORRELOGRAM_MAX_WINDOW
@@ -357,19 +356,10 @@ def correlogram_voice_spans(positions, counts, flags, window: int, hop: int, max
 
     A count below 0 (or above ``max_frames_per_call``, when given), or without START a position outside ``[0, 2^60]``,
     answers -1 and leaves the position as it was."""
-    pos = np.asarray(positions, np.int64)
-    n = np.asarray(counts, np.int64)
-    f = np.asarray(flags, np.int64)
-    if not (pos.shape == n.shape == f.shape):
-        raise ValueError(f'positions, counts and flags of one shape, got {pos.shape}, {n.shape}, {f.shape}')
+    pos, n, start, end, p, bad = _voice_head(positions, counts, flags, max_frames_per_call)
     W, H = int(window), int(hop)
     if W < 1 or H < 1:
         raise ValueError(f'window and hop must be >= 1, got {window} and {hop}')
-    start, end = (f & VOICE_START) != 0, (f & VOICE_END) != 0
-    p = np.where(start, 0, pos)
-    bad = (n < 0) | (p < 0) | (p > VOICE_MAX_POSITION)
-    if max_frames_per_call is not None:
-        bad |= n > int(max_frames_per_call)
     p, n = np.where(bad, 0, p), np.where(bad, 0, n)          # (no arithmetic on a bad value)
 
     def complete(q):
@@ -377,6 +367,17 @@ def correlogram_voice_spans(positions, counts, flags, window: int, hop: int, max
     out = np.where(bad, -1, complete(p + n) - complete(p)).astype(np.int64)
     new = np.where(bad, pos, np.where(end, 0, p + n)).astype(np.int64)
     return out, new
+
+
+def _sample_dtype(dtype) -> np.dtype:
+    """A meter's ``dtype`` argument as a NumPy dtype: float32 or float64, else ``ValueError``."""
+    try:
+        parsed = None if dtype is None else np.dtype(dtype)                       # (np.dtype(None) is float64)
+    except TypeError:
+        parsed = None
+    if parsed is None or parsed.name not in ('float32', 'float64'):
+        raise ValueError(f"dtype must be 'float32' or 'float64', got {dtype!r}")
+    return parsed
 
 
 class CorrelogramVoicePool(_SlotPool):
@@ -407,19 +408,13 @@ class CorrelogramVoicePool(_SlotPool):
     def __init__(self, slots: int, *, window: int, hop: int, num_lags: int, epsilon, max_frames_per_call: int,
                  dtype='float32'):
         _check_counts(slots=slots, max_frames_per_call=max_frames_per_call)
-        if slots > _native.MAX_STREAMS_PER_CALL:
-            raise ValueError(f'slots {slots} above {_native.MAX_STREAMS_PER_CALL}: split the pool')
+        _check_slots(slots)
         if max_frames_per_call > _INT32_MAX:
             raise ValueError(f'max_frames_per_call {max_frames_per_call} above 2**31 - 1: counts are int32')
         if not correlogram_covers(0, window, hop, num_lags, epsilon):
             raise ValueError(f'window {window}, hop {hop}, {num_lags} lags and epsilon {epsilon!r} have no device form '
                              f'(correlogram_covers is False) and the pool has no NumPy one: use cross_correlogram')
-        try:
-            self.dtype = None if dtype is None else np.dtype(dtype)
-        except TypeError:
-            self.dtype = None
-        if self.dtype is None or self.dtype.name not in ('float32', 'float64'):      # (np.dtype(None) is float64)
-            raise ValueError(f"dtype must be 'float32' or 'float64', got {dtype!r}")
+        self.dtype = _sample_dtype(dtype)
         self.slots, self.max_frames_per_call = int(slots), int(max_frames_per_call)
         self.window, self.hop, self.num_lags, self.epsilon = int(window), int(hop), int(num_lags), epsilon
         # the fixed grid of the pool (include/vnd_correlogram_voice_stream.h): window groups of 4 rows x column tiles of
@@ -431,6 +426,10 @@ class CorrelogramVoicePool(_SlotPool):
                              f'one launch takes: raise the stride or lower max_frames_per_call')
         self.transfers = {'to_device': 0, 'to_host': 0}
         self._state = None                    # (torch uint8 tensor, bytes)
+        S = self.slots
+        self._inputs = (('x', (S, self.max_frames_per_call, 2), self.dtype.name, None),) + _slot_ints(S, 'counts', 'flags')
+        self._outputs = (('rows', (S, self.rows_per_call, self.num_lags), 'float32', 'empty'),
+                         ('out_counts', (S,), 'int32', 'empty'))
         self._mirror()
 
     @property
@@ -450,14 +449,8 @@ class CorrelogramVoicePool(_SlotPool):
         block or an end for a slot that was never started, a start on a live slot (``discard=True`` allows it: the voice
         it held is dropped), a block above ``max_frames_per_call`` or not ``(n, 2)``; ``TypeError`` for a block that is
         neither float32 nor float64."""
-        if self._form == 'dev':
-            raise RuntimeError('this pool runs through process_dev(): the host does not know its positions; reset() first')
-        starts = {}
-        for slot in list(start or ()):
-            slot = self._slot(slot, 'start')
-            if slot in starts:
-                raise ValueError(f'start: slot {slot} is named twice')
-            starts[slot] = 0
+        self._require_form('dict')
+        starts = self._start_slots(start)
         cast = {}
         for slot, block in dict(blocks or {}).items():
             a = np.asarray(block)
@@ -470,16 +463,7 @@ class CorrelogramVoicePool(_SlotPool):
         ``(slots, rows_per_call, num_lags)`` - the first ``out_counts[b]`` rows of row-block b are written, nothing at or
         past them - and int32 ``(slots,)``; ``out=(rows, out_counts)`` takes the caller's.  No check reads device memory;
         bad per-slot values answer -1 (``include/vnd_correlogram_voice_stream.h``)."""
-        if self._form == 'dict':
-            raise RuntimeError('this pool runs through process(): mixing in process_dev() would leave the host mirror '
-                               'of the positions stale; reset() first')
-        S, M = self.slots, self.max_frames_per_call
-        rows, out_counts = out if out is not None else (None, None)
-        _check_device_tensors((('x', x, (S, M, 2), self.dtype.name, False), ('counts', counts, (S,), 'int32', False),
-                               ('flags', flags, (S,), 'int32', False),
-                               ('rows', rows, (S, self.rows_per_call, self.num_lags), 'float32', True),
-                               ('out_counts', out_counts, (S,), 'int32', True)))
-        return self._call_device(_torch(), x, counts, flags, rows, out_counts, self.dtype == np.float64)
+        return self._process_dev((x, counts, flags), out)
 
     # ---- what _SlotPool asks for ---------------------------------------------------------------
     def _spans(self, counts, flags, tables):
@@ -495,62 +479,24 @@ class CorrelogramVoicePool(_SlotPool):
         return 0
 
     # ---- the device -------------------------------------------------------------------------
-    def _allocate(self, torch, ctx):
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError('the state of a voice pool is allocated and zeroed on first use: call reset() before the capture')
-        need = _native.correlogram_voice_stream_state_bytes(self.slots, self.window, self.max_frames_per_call)
-        buf = torch.empty((need,), dtype=torch.uint8, device=torch.device('cuda', ctx.device))
-        self._state = (buf, need)
-        self._reset_device(torch, ctx)
+    def _state_bytes(self, ctx) -> int:
+        return _native.correlogram_voice_stream_state_bytes(self.slots, self.window, self.max_frames_per_call)
 
-    def _reset_device(self, torch, ctx):
-        state, state_bytes = self._state
-        _native.correlogram_voice_stream_reset_device(ctx, state.data_ptr(), state_bytes, self.slots, self.window,
-                                                      self.max_frames_per_call,
-                                                      stream=torch.cuda.current_stream(state.device).cuda_stream)
+    def _reset_entry(self, ctx, state_ptr, state_bytes, stream):
+        _native.correlogram_voice_stream_reset_device(ctx, state_ptr, state_bytes, self.slots, self.window,
+                                                      self.max_frames_per_call, stream=stream)
 
     def _call_host(self, x, counts, flags):
         """One upload (the blocks and the two int32 arrays in one buffer), the call, one download (rows and out_counts)."""
-        torch = _torch()
-        ctx = _native.default_context()
-        device = torch.device('cuda', ctx.device)
-        S = self.slots
-        ints = np.stack([counts, flags]).astype(np.int32)
-        up = torch.from_numpy(np.concatenate([x.reshape(-1).view(np.uint8), ints.reshape(-1).view(np.uint8)])).to(device)
-        self.transfers = {'to_device': 1, 'to_host': 0}
-        x_dev = up[:x.nbytes].view(torch.float32).view(x.shape)
-        c, f = up[x.nbytes:].view(torch.int32).view(2, S)
-        r_bytes = S * self.rows_per_call * self.num_lags * 4
-        down = torch.empty((r_bytes + 4 * S,), dtype=torch.uint8, device=device)
-        rows = down[:r_bytes].view(torch.float32).view(S, self.rows_per_call, self.num_lags)
-        out_counts = down[r_bytes:].view(torch.int32)
-        form = self._form
-        try:
-            self._call_device(torch, x_dev, c, f, rows, out_counts, False)
-        finally:
-            self._form = form
-        host = down.cpu().numpy()
-        self.transfers['to_host'] = 1
-        return host[:r_bytes].view(np.float32).reshape(S, self.rows_per_call, self.num_lags), host[r_bytes:].view(np.int32)
+        return self._call_host_packed(x, (counts, flags))
 
-    def _call_device(self, torch, x, counts, flags, rows, out_counts, float64: bool):
-        ctx = _native.default_context()
-        device = torch.device('cuda', ctx.device)
-        for t in (x, counts, flags):
-            if t.device != device:
-                raise ValueError(f'tensor on {t.device}, the pool runs on {device}')
-        state, state_bytes = self._ensure_state(torch, ctx)
-        if rows is None:
-            rows = torch.empty((self.slots, self.rows_per_call, self.num_lags), dtype=torch.float32, device=device)
-        if out_counts is None:
-            out_counts = torch.empty((self.slots,), dtype=torch.int32, device=device)
-        self._form = 'dev'
+    def _launch(self, ctx, state_ptr, state_bytes, inputs, rows, out_counts, stream):
+        x, counts, flags = inputs                           # x is the host path's float32 cast or the pool's dtype
         _native.correlogram_voice_stream_device(
-            ctx, state.data_ptr(), state_bytes, self.max_frames_per_call, x.data_ptr(), x.data_ptr() + x.element_size(),
+            ctx, state_ptr, state_bytes, self.max_frames_per_call, x.data_ptr(), x.data_ptr() + x.element_size(),
             2 * self.max_frames_per_call, 2, counts.data_ptr(), flags.data_ptr(), rows.data_ptr(), out_counts.data_ptr(),
-            self.slots, window=self.window, hop=self.hop, num_lags=self.num_lags, eps=float(self.epsilon), float64=float64,
-            stream=torch.cuda.current_stream(device).cuda_stream)
-        return rows, out_counts
+            self.slots, window=self.window, hop=self.hop, num_lags=self.num_lags, eps=float(self.epsilon),
+            float64=x.element_size() == 8, stream=stream)
 
 
 def cross_correlogram_voice_pool(slots: int, *, sample_rate_hz: int = 44100, max_lag_seconds: float = 0.02,
@@ -583,16 +529,7 @@ def polar_voice_spans(positions, counts, flags, max_frames_per_call: Optional[in
 
     A count below 0 (or above ``max_frames_per_call``, when given), or without START a position outside ``[0, 2^60]``,
     answers -1 and leaves the position as it was."""
-    pos = np.asarray(positions, np.int64)
-    n = np.asarray(counts, np.int64)
-    f = np.asarray(flags, np.int64)
-    if not (pos.shape == n.shape == f.shape):
-        raise ValueError(f'positions, counts and flags of one shape, got {pos.shape}, {n.shape}, {f.shape}')
-    start, end = (f & VOICE_START) != 0, (f & VOICE_END) != 0
-    p = np.where(start, 0, pos)
-    bad = (n < 0) | (p < 0) | (p > VOICE_MAX_POSITION)
-    if max_frames_per_call is not None:
-        bad |= n > int(max_frames_per_call)
+    pos, n, start, end, p, bad = _voice_head(positions, counts, flags, max_frames_per_call)
     idle = ~bad & (n == 0) & ~start & ~end
     p, n = np.where(bad, 0, p), np.where(bad, 0, n)          # (no arithmetic on a bad value)
     valid = np.where(bad, -1, np.where(idle, 0, 1)).astype(np.int64)
@@ -726,16 +663,10 @@ class PolarVoicePool(_SlotPool):
 
     def __init__(self, slots: int, *, max_frames_per_call: int, dtype='float32'):
         _check_counts(slots=slots, max_frames_per_call=max_frames_per_call)
-        if slots > _native.MAX_STREAMS_PER_CALL:
-            raise ValueError(f'slots {slots} above {_native.MAX_STREAMS_PER_CALL}: split the pool')
+        _check_slots(slots)
         if max_frames_per_call > _INT32_MAX:
             raise ValueError(f'max_frames_per_call {max_frames_per_call} above 2**31 - 1: counts are int32')
-        try:
-            self.dtype = None if dtype is None else np.dtype(dtype)
-        except TypeError:
-            self.dtype = None
-        if self.dtype is None or self.dtype.name not in ('float32', 'float64'):      # (np.dtype(None) is float64)
-            raise ValueError(f"dtype must be 'float32' or 'float64', got {dtype!r}")
+        self.dtype = _sample_dtype(dtype)
         self.slots, self.max_frames_per_call = int(slots), int(max_frames_per_call)
         self._block_dtype = self.dtype            # what _schedule holds every block to
         # the fixed grid of the pool (include/vnd_polar_voice_stream.h): one workgroup per chunk of 512 frames a call can
@@ -745,6 +676,9 @@ class PolarVoicePool(_SlotPool):
                              f'lower max_frames_per_call or split the pool')
         self.transfers = {'to_device': 0, 'to_host': 0}
         self._state = None                    # (torch uint8 tensor, bytes)
+        S = self.slots
+        self._inputs = (('y', (S, self.max_frames_per_call, 2), self.dtype.name, None),) + _slot_ints(S, 'counts', 'flags')
+        self._outputs = (('moments', (S, 8), 'float64', 'zeros'), ('valid', (S,), 'int32', 'empty'))
         self._mirror()
 
     @property
@@ -760,14 +694,8 @@ class PolarVoicePool(_SlotPool):
         outside the pool or named twice, a block or an end for a slot that was never started, a start on a live slot
         (``discard=True`` allows it: the voice it held is dropped), a block above ``max_frames_per_call`` or not
         ``(n, 2)``; ``TypeError`` for a block of another dtype than the pool's."""
-        if self._form == 'dev':
-            raise RuntimeError('this pool runs through process_dev(): the host does not know its positions; reset() first')
-        starts = {}
-        for slot in list(start or ()):
-            slot = self._slot(slot, 'start')
-            if slot in starts:
-                raise ValueError(f'start: slot {slot} is named twice')
-            starts[slot] = 0
+        self._require_form('dict')
+        starts = self._start_slots(start)
         counts, flags, tables, live, x, answered = self._schedule(blocks, starts, end, discard)
         answered = sorted(set(answered) | set(starts))
         if not counts.any() and not flags.any():              # nothing pushed, started or ended: no device call
@@ -787,15 +715,7 @@ class PolarVoicePool(_SlotPool):
         ``counts`` / ``flags`` int32 ``(slots,)``.  Returns ``(moments, valid)``: float64 ``(slots, 8)`` - the row of a
         slot that answered 1 is written, no other - and int32 ``(slots,)``; ``out=(moments, valid)`` takes the caller's.
         No check reads device memory; bad per-slot values answer -1 (``include/vnd_polar_voice_stream.h``)."""
-        if self._form == 'dict':
-            raise RuntimeError('this pool runs through process(): mixing in process_dev() would leave the host mirror '
-                               'of the positions stale; reset() first')
-        S, M = self.slots, self.max_frames_per_call
-        moments, valid = out if out is not None else (None, None)
-        _check_device_tensors((('y', y, (S, M, 2), self.dtype.name, False), ('counts', counts, (S,), 'int32', False),
-                               ('flags', flags, (S,), 'int32', False), ('moments', moments, (S, 8), 'float64', True),
-                               ('valid', valid, (S,), 'int32', True)))
-        return self._call_device(_torch(), y, counts, flags, moments, valid)
+        return self._process_dev((y, counts, flags), out)
 
     def scores(self, moments, *, angle_limit: float, lambda_mean: float, lambda_skew: float, lambda_correlation: float,
                lambda_penalty: float):
@@ -826,60 +746,23 @@ class PolarVoicePool(_SlotPool):
         return 0
 
     # ---- the device -------------------------------------------------------------------------
-    def _allocate(self, torch, ctx):
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError('the state of a voice pool is allocated and zeroed on first use: call reset() before the capture')
-        need = _native.polar_voice_stream_state_bytes(self.slots, self.max_frames_per_call, self.dtype.itemsize)
-        buf = torch.empty((need,), dtype=torch.uint8, device=torch.device('cuda', ctx.device))
-        self._state = (buf, need)
-        self._reset_device(torch, ctx)
+    def _state_bytes(self, ctx) -> int:
+        return _native.polar_voice_stream_state_bytes(self.slots, self.max_frames_per_call, self.dtype.itemsize)
 
-    def _reset_device(self, torch, ctx):
-        state, state_bytes = self._state
-        _native.polar_voice_stream_reset_device(ctx, state.data_ptr(), state_bytes, self.slots, self.max_frames_per_call,
-                                                self.dtype.itemsize, stream=torch.cuda.current_stream(state.device).cuda_stream)
+    def _reset_entry(self, ctx, state_ptr, state_bytes, stream):
+        _native.polar_voice_stream_reset_device(ctx, state_ptr, state_bytes, self.slots, self.max_frames_per_call,
+                                                self.dtype.itemsize, stream=stream)
 
     def _call_host(self, x, counts, flags):
         """One upload (the blocks and the two int32 arrays in one buffer), the call, one download (moments and valid)."""
-        torch = _torch()
-        ctx = _native.default_context()
-        device = torch.device('cuda', ctx.device)
-        S = self.slots
-        ints = np.stack([counts, flags]).astype(np.int32)
-        up = torch.from_numpy(np.concatenate([x.reshape(-1).view(np.uint8), ints.reshape(-1).view(np.uint8)])).to(device)
-        self.transfers = {'to_device': 1, 'to_host': 0}
-        x_dev = up[:x.nbytes].view(torch.float64 if self.dtype == np.float64 else torch.float32).view(x.shape)
-        c, f = up[x.nbytes:].view(torch.int32).view(2, S)
-        m_bytes = S * 8 * 8
-        down = torch.zeros((m_bytes + 4 * S,), dtype=torch.uint8, device=device)
-        moments = down[:m_bytes].view(torch.float64).view(S, 8)
-        valid = down[m_bytes:].view(torch.int32)
-        form = self._form
-        try:
-            self._call_device(torch, x_dev, c, f, moments, valid)
-        finally:
-            self._form = form
-        host = down.cpu().numpy()
-        self.transfers['to_host'] = 1
-        return host[:m_bytes].view(np.float64).reshape(S, 8), host[m_bytes:].view(np.int32)
+        return self._call_host_packed(x, (counts, flags))
 
-    def _call_device(self, torch, y, counts, flags, moments, valid):
-        ctx = _native.default_context()
-        device = torch.device('cuda', ctx.device)
-        for t in (y, counts, flags):
-            if t.device != device:
-                raise ValueError(f'tensor on {t.device}, the pool runs on {device}')
-        state, state_bytes = self._ensure_state(torch, ctx)
-        if moments is None:
-            moments = torch.zeros((self.slots, 8), dtype=torch.float64, device=device)
-        if valid is None:
-            valid = torch.empty((self.slots,), dtype=torch.int32, device=device)
-        self._form = 'dev'
+    def _launch(self, ctx, state_ptr, state_bytes, inputs, moments, valid, stream):
+        y, counts, flags = inputs
         _native.polar_voice_stream_device(
-            ctx, state.data_ptr(), state_bytes, self.max_frames_per_call, y.data_ptr(), y.data_ptr() + y.element_size(),
+            ctx, state_ptr, state_bytes, self.max_frames_per_call, y.data_ptr(), y.data_ptr() + y.element_size(),
             2 * self.max_frames_per_call, 2, counts.data_ptr(), flags.data_ptr(), moments.data_ptr(), valid.data_ptr(),
-            self.slots, float64=self.dtype == np.float64, stream=torch.cuda.current_stream(device).cuda_stream)
-        return moments, valid
+            self.slots, float64=self.dtype == np.float64, stream=stream)
 
 
 def stereo_image_voice_pool(slots: int, *, max_frames_per_call: int = 4800, dtype='float32') -> PolarVoicePool:

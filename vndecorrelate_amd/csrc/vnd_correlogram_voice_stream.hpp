@@ -35,17 +35,14 @@
 //     with one wrap;
 //   - rows: r < rows <= RC, so row r of slot b lies inside out[b][RC][num_lags].
 //
-// cg_voice_advance_kernel, one lane per slot, follows on the same stream and writes pos[b] and out_counts[b].  The kernel
-// boundary is the ordering between every workgroup's read of pos[b] and its update (vnd_voice_stream.hpp).
+// voice_advance_kernel<CgVoiceArgs<T>>, one lane per slot, follows on the same stream and writes pos[b] and out_counts[b]
+// (vnd_voice_core.hpp).
 #pragma once
 #include "../../include/vnd_correlogram_voice_stream.h"
 
 // One slot's side of a call, from the stored position, counts[b] and flags[b] alone.
-struct CgVoiceSpan {
-    int64_t p, n;                  // position the call starts at, frames pushed
-    int64_t w0, rows;              // window of row 0, wc(p + n) - wc(p)
-    int64_t next;                  // the position after the call
-    bool end, ok;                  // !ok: a bad count or position - the slot is left alone, out_counts = -1
+struct CgVoiceSpan : vnd::VoiceHead {
+    int64_t w0, rows;              // window of row 0, wc(p + n) - wc(p); !ok: the slot is left alone, out_counts = rows = -1
 };
 
 __host__ __device__ inline int64_t cg_voice_complete(int64_t q, int64_t W, int64_t H) { return q >= W ? (q - W) / H + 1 : 0; }
@@ -53,15 +50,10 @@ __host__ __device__ inline int64_t cg_voice_complete(int64_t q, int64_t W, int64
 __host__ __device__ inline CgVoiceSpan cg_voice_span(int64_t stored, int32_t count, int32_t flags, int64_t M, int64_t W,
                                                      int64_t H)
 {
-    CgVoiceSpan v{};
-    v.end = (flags & VND_VOICE_END) != 0;
-    v.p = (flags & VND_VOICE_START) ? 0 : stored;
-    v.ok = count >= 0 && count <= M && v.p >= 0 && v.p <= vnd::kVoiceMaxPosition;
-    if (!v.ok) { v.p = 0; v.next = stored; v.rows = -1; return v; }
-    v.n = count;
+    CgVoiceSpan v{vnd::voice_head(stored, count, flags, M)};
+    if (!v.ok) { v.rows = -1; return v; }
     v.w0 = cg_voice_complete(v.p, W, H);
     v.rows = cg_voice_complete(v.p + v.n, W, H) - v.w0;
-    v.next = v.end ? 0 : v.p + v.n;
     return v;
 }
 
@@ -78,6 +70,11 @@ struct CgVoiceArgs {
     int32_t *__restrict__ out_counts;
     int64_t M, cap, rc;               // max_frames_per_call, W - 1 + M, ceil(M / H)
     int32_t slots;
+    __device__ vnd::VoiceAnswer advance(int64_t b) const
+    {
+        const CgVoiceSpan v = cg_voice_span(pos[b], counts[b], flags[b], M, cg.W, cg.hop);
+        return {(int32_t)v.rows, v.ok, v.next};
+    }
 };
 
 // grid = (slots, ceil(rc / kCgG) * tiles)
@@ -163,17 +160,6 @@ struct CgVoice {
     }
 };
 
-// grid = ceil(slots / kVoiceAdvanceThreads): behind correlogram_kernel<CgVoice<T>> on the same stream
-template <class T>
-__global__ __launch_bounds__(vnd::kVoiceAdvanceThreads) void cg_voice_advance_kernel(const CgVoiceArgs<T> a)
-{
-    const int64_t b = (int64_t)blockIdx.x * vnd::kVoiceAdvanceThreads + threadIdx.x;
-    if (b >= a.slots) return;
-    const CgVoiceSpan v = cg_voice_span(a.pos[b], a.counts[b], a.flags[b], a.M, a.cg.W, a.cg.hop);
-    a.out_counts[b] = (int32_t)v.rows;
-    if (v.ok) a.pos[b] = v.next;
-}
-
 // The fixed launch of a pool.
 struct CgVoicePlan {
     int64_t rc, groups, tiles, workgroups, advance_groups, cap, need;
@@ -195,7 +181,7 @@ static vnd_status cg_voice_plan(int64_t slots, int32_t window, int32_t hop, int3
     p.groups = (p.rc + kCgG - 1) / kCgG;
     p.tiles = ((int64_t)num_lags + kCgTile - 1) / kCgTile;
     p.workgroups = slots * p.groups * p.tiles;
-    p.advance_groups = (slots + vnd::kVoiceAdvanceThreads - 1) / vnd::kVoiceAdvanceThreads;
+    p.advance_groups = vnd::voice_advance_groups(slots);          // what launch_voice_advance launches
     if (slots * p.rc * (int64_t)num_lags > ((int64_t)1 << 40))
         return fail(VND_ERR_UNSUPPORTED, "an out of %lld x %lld x %d values, above 2^40", (long long)slots, (long long)p.rc, num_lags);
     if (p.groups * p.tiles > 65535)
@@ -204,15 +190,6 @@ static vnd_status cg_voice_plan(int64_t slots, int32_t window, int32_t hop, int3
     if (p.workgroups > ((int64_t)1 << 23))
         return fail(VND_ERR_UNSUPPORTED, "%lld workgroups in one launch, above 2^23", (long long)p.workgroups);
     *plan = p;
-    return VND_OK;
-}
-
-static vnd_status cg_voice_state(const void *state, int64_t state_bytes, int64_t need)
-{
-    if (state_bytes < need)
-        return fail(VND_ERR_INVALID, "state of %lld bytes, the voice pool needs %lld", (long long)state_bytes, (long long)need);
-    if (!state) return fail(VND_ERR_INVALID, "null state pointer");
-    if ((uintptr_t)state % 16 != 0) return fail(VND_ERR_INVALID, "the state is not 16-byte aligned");
     return VND_OK;
 }
 
@@ -227,24 +204,16 @@ static vnd_status cg_voice_stream_dev(vnd_ctx *ctx, void *state, int64_t state_b
     CgVoicePlan p{};
     vnd_status st = cg_voice_plan(slots, window, hop, num_lags, max_frames_per_call, &p);
     if (st != VND_OK) return st;
-    if ((st = cg_voice_state(state, state_bytes, p.need)) != VND_OK) return st;
+    if ((st = voice_state_check("voice pool", state, state_bytes, p.need, slots)) != VND_OK) return st;
     if (!x || !y || !counts || !flags || !out || !out_counts)
         return fail(VND_ERR_INVALID, "null chunk, counts, flags, output or out_counts pointer");
-    // extents in elements: the last sample of the last slot's longest chunk, and the output
-    int64_t span, xlast;
-    if (__builtin_mul_overflow(slots - 1, stream_stride, &span) ||
-        __builtin_mul_overflow(max_frames_per_call - 1, (int64_t)frame_stride, &xlast) ||
-        __builtin_add_overflow(span, xlast, &span) || span > INT64_MAX / 16)
-        return fail(VND_ERR_INVALID, "buffer extents overflow");
-    const int64_t xb = (span + 1) * (int64_t)sizeof(T), ob = slots * p.rc * (int64_t)num_lags * (int64_t)sizeof(float);
-    auto overlap = [](const void *u, int64_t ub, const void *v, int64_t vb) {
-        const char *u0 = (const char *)u, *v0 = (const char *)v;
-        return u0 < v0 + vb && v0 < u0 + ub;
-    };
+    int64_t xb = 0;
+    if ((st = voice_chunk_bytes(slots, stream_stride, max_frames_per_call, frame_stride, sizeof(T), &xb)) != VND_OK) return st;
+    const int64_t ob = slots * p.rc * (int64_t)num_lags * (int64_t)sizeof(float);
     for (const T *c : {x, y})
-        if (overlap(c, xb, out, ob) || overlap(c, xb, state, p.need))
+        if (voice_overlap(c, xb, out, ob) || voice_overlap(c, xb, state, p.need))
             return fail(VND_ERR_INVALID, "out and the state must not overlap the chunk");
-    if (overlap(out, ob, state, p.need)) return fail(VND_ERR_INVALID, "out must not overlap the state");
+    if (voice_overlap(out, ob, state, p.need)) return fail(VND_ERR_INVALID, "out must not overlap the state");
     DeviceScope on(ctx->device);
     if (!on.ok) return fail(VND_ERR_HIP, "cannot select device %d", ctx->device);
     hipStream_t stream = (hipStream_t)stream_;
@@ -262,7 +231,7 @@ static vnd_status cg_voice_stream_dev(vnd_ctx *ctx, void *state, int64_t state_b
     hipLaunchKernelGGL(correlogram_kernel<CgVoice<T>>, dim3((unsigned)slots, (unsigned)(p.groups * p.tiles)), dim3(kCgThreads),
                        0, stream, a);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(cg_voice_advance_kernel<T>, dim3((unsigned)p.advance_groups), dim3(vnd::kVoiceAdvanceThreads), 0, stream, a);
+    launch_voice_advance(a, slots, stream);
     HIP_TRY(hipGetLastError());
     return VND_OK;
 }
@@ -289,11 +258,8 @@ vnd_status vnd_correlogram_voice_stream_reset_dev(vnd_ctx *ctx, void *state, int
     int64_t need = 0;
     vnd_status st = vnd_correlogram_voice_stream_state_bytes(slots, window, max_frames_per_call, &need);
     if (st != VND_OK) return st;
-    if ((st = cg_voice_state(state, state_bytes, need)) != VND_OK) return st;
-    DeviceScope on(ctx->device);
-    if (!on.ok) return fail(VND_ERR_HIP, "cannot select device %d", ctx->device);
-    HIP_TRY(hipMemsetAsync(state, 0, (size_t)voice_position_bytes(slots), (hipStream_t)stream_));      // the positions only
-    return VND_OK;
+    if ((st = voice_state_check("voice pool", state, state_bytes, need, slots)) != VND_OK) return st;
+    return voice_reset_positions(ctx, state, slots, stream_);
 }
 
 vnd_status vnd_correlogram_voice_stream_f32_dev(vnd_ctx *ctx, void *state, int64_t state_bytes, int64_t max_frames_per_call,

@@ -34,8 +34,8 @@
 //     less than max_delay <= cap with one wrap;
 //   - y: frame k < n_out <= M + max_delay = the row.
 //
-// haas_voice_advance_kernel, one lane per slot, follows on the same stream and writes pos[b] and out_counts[b].  A kernel
-// boundary is the ordering between every workgroup's read of pos[b] and its update, as in vnd_voice_stream.hpp.
+// voice_advance_kernel<HaasVoiceArgs>, one lane per slot, follows on the same stream and writes pos[b] and out_counts[b]
+// (vnd_voice_core.hpp).
 #pragma once
 #include "vnd_haas_stream.hpp"
 #include "vnd_voice_stream.hpp"
@@ -84,6 +84,11 @@ struct HaasVoiceArgs {
     int32_t *__restrict__ out_counts;                   // [slots]
     int64_t M, cap;                                     // max_frames_per_call, max_delay + M
     int32_t max_delay, slots;
+    __device__ VoiceAnswer advance(int64_t b) const
+    {
+        const HaasVoiceSpan v = haas_voice_span(pos[b], counts[b], flags[b], delays[b], M, max_delay);
+        return {(int32_t)v.n_out, v.ok, v.next};
+    }
 };
 
 // grid = (slots, max(1, ceil((M + max_delay) / kHaasStreamThreads))): one lane per output frame of the longest row
@@ -118,16 +123,6 @@ __global__ __launch_bounds__(kHaasStreamThreads) void haas_voice_stream_kernel(c
     *(double2 *)(a.y + (b * (a.M + a.max_delay) + k) * 2) = make_double2(o[0], o[1]);
 }
 
-// grid = ceil(slots / kVoiceAdvanceThreads): behind haas_voice_stream_kernel on the same stream
-__global__ __launch_bounds__(kVoiceAdvanceThreads) void haas_voice_advance_kernel(const HaasVoiceArgs a)
-{
-    const int64_t b = (int64_t)blockIdx.x * kVoiceAdvanceThreads + threadIdx.x;
-    if (b >= a.slots) return;
-    const HaasVoiceSpan v = haas_voice_span(a.pos[b], a.counts[b], a.flags[b], a.delays[b], a.M, a.max_delay);
-    a.out_counts[b] = (int32_t)v.n_out;
-    if (v.ok) a.pos[b] = v.next;
-}
-
 }  // namespace vnd
 
 // ------------------------------------------------------------------------------
@@ -158,11 +153,7 @@ static vnd_status haas_voice_pool(const vnd_ctx *ctx, const void *state, int64_t
     int64_t need = 0;
     vnd_status st = vnd_haas_voice_stream_state_bytes(slots, Cx, max_delay, max_frames_per_call, &need);
     if (st != VND_OK) return st;
-    if (state_bytes < need)
-        return fail(VND_ERR_INVALID, "state of %lld bytes, the Haas voice pool needs %lld", (long long)state_bytes, (long long)need);
-    if (slots > 0 && !state) return fail(VND_ERR_INVALID, "null state pointer");
-    if ((uintptr_t)state % 16 != 0) return fail(VND_ERR_INVALID, "the state is not 16-byte aligned");
-    return VND_OK;
+    return voice_state_check("Haas voice pool", state, state_bytes, need, slots);
 }
 
 vnd_status vnd_haas_voice_stream_reset_dev(vnd_ctx *ctx, void *state, int64_t state_bytes, int64_t slots, int32_t Cx,
@@ -170,11 +161,7 @@ vnd_status vnd_haas_voice_stream_reset_dev(vnd_ctx *ctx, void *state, int64_t st
 {
     vnd_status st = haas_voice_pool(ctx, state, state_bytes, max_frames_per_call, slots, Cx, max_delay);
     if (st != VND_OK) return st;
-    if (slots == 0) return VND_OK;
-    DeviceScope on(ctx->device);
-    if (!on.ok) return fail(VND_ERR_HIP, "cannot select device %d", ctx->device);
-    HIP_TRY(hipMemsetAsync(state, 0, (size_t)voice_position_bytes(slots), (hipStream_t)stream_));     // the positions only
-    return VND_OK;
+    return slots == 0 ? VND_OK : voice_reset_positions(ctx, state, slots, stream_);
 }
 
 static vnd_status haas_voice_check(const vnd_ctx *ctx, const void *state, int64_t state_bytes, int64_t max_frames_per_call,
@@ -217,8 +204,7 @@ vnd_status vnd_haas_voice_stream_f64_dev(vnd_ctx *ctx, void *state, int64_t stat
     hipStream_t stream = (hipStream_t)stream_;
     hipLaunchKernelGGL(haas_voice_stream_kernel, dim3((unsigned)slots, tiles), dim3(kHaasStreamThreads), 0, stream, a);
     HIP_TRY(hipGetLastError());
-    const unsigned groups = (unsigned)((slots + kVoiceAdvanceThreads - 1) / kVoiceAdvanceThreads);
-    hipLaunchKernelGGL(haas_voice_advance_kernel, dim3(groups), dim3(kVoiceAdvanceThreads), 0, stream, a);
+    launch_voice_advance(a, slots, stream);
     HIP_TRY(hipGetLastError());
     return VND_OK;
 }

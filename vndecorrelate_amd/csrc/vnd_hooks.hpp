@@ -298,7 +298,7 @@ vnd_status vnd_describe_voice_stream_launch(vnd_ctx *ctx, const vnd_taps *t, int
     const EachStreamPlan p = make_voice_stream_plan(ctx, t, slots, max_frames_per_call, in_channels, epilogue != 0);
     snprintf(text, (size_t)len, "voice_stream r=%d W=%d lds_bytes=%zu tiles=%d nblocks=%u fma=%d epilogue=%d threads=%d advance_groups=%lld",
              p.r, p.W, p.lds_bytes, p.tiles, p.nblocks, p.fma ? 1 : 0, p.epi ? 1 : 0, kVpThreads,
-             (long long)((slots + kVoiceAdvanceThreads - 1) / kVoiceAdvanceThreads));
+             (long long)voice_advance_groups(slots));
     return VND_OK;
 }
 

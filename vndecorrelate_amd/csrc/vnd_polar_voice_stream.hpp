@@ -22,7 +22,7 @@
 // workgroup (p mod 512 = 511 with n = M touches G of them).
 //
 // polar_voice_finish_kernel, grid (slots), follows on the same stream; the kernel boundary is the ordering between every
-// workgroup's read of pos[b] and its update, and between the partials' writes and reads (vnd_voice_stream.hpp).  Lane t
+// workgroup's read of pos[b] and its update, and between the partials' writes and reads (vnd_voice_core.hpp).  Lane t
 // starts from sums[b][t] if t < floor(p / 512) - the lane has a completed chunk of THIS voice - and from +0.0 otherwise,
 // which is why the sums need no clearing at START; adds this call's completed chunks c = t (mod 256) in ascending c (with
 // M > 131072 a lane gets two in one call); stores the sums back unless END; adds the incomplete chunk's partial to its
@@ -48,25 +48,18 @@ constexpr int64_t kPolarVoiceChunk = 512;             // kMomFrames
 static_assert(kPolarVoiceLanes == vnd::kMomThreads && kPolarVoiceChunk == vnd::kMomFrames, "the one-shot order");
 
 // One slot's side of a call, from the stored position, counts[b] and flags[b] alone.
-struct PolarVoiceSpan {
-    int64_t p, n, q;               // position the call starts at, frames pushed, p + n
-    int64_t next;                  // the position after the call
-    int32_t valid;                 // 1 answered, 0 idle, -1 a bad count or position
-    bool end;
+struct PolarVoiceSpan : vnd::VoiceHead {
+    int64_t q;                     // p + n
+    int32_t valid;                 // 1 answered, 0 idle (p = q = 0, the position stays), -1 a bad count or position
 };
 
 __host__ __device__ inline PolarVoiceSpan polar_voice_span(int64_t stored, int32_t count, int32_t flags, int64_t M)
 {
-    PolarVoiceSpan v{};
-    v.end = (flags & VND_VOICE_END) != 0;
-    v.p = (flags & VND_VOICE_START) ? 0 : stored;
-    v.next = stored;
-    if (!(count >= 0 && count <= M && v.p >= 0 && v.p <= vnd::kVoiceMaxPosition)) { v.p = 0; v.valid = -1; return v; }
-    v.n = count;
+    PolarVoiceSpan v{vnd::voice_head(stored, count, flags, M)};
+    if (!v.ok) { v.valid = -1; return v; }
     v.q = v.p + v.n;
-    if (count == 0 && !(flags & (VND_VOICE_START | VND_VOICE_END))) { v.p = v.q = 0; return v; }      // idle
+    if (count == 0 && !(flags & (VND_VOICE_START | VND_VOICE_END))) { v.p = v.q = 0; return v; }      // idle: next is stored
     v.valid = 1;
-    v.next = v.end ? 0 : v.q;
     return v;
 }
 
@@ -246,15 +239,6 @@ static vnd_status polar_voice_plan(int64_t slots, int64_t max_frames_per_call, i
     return VND_OK;
 }
 
-static vnd_status polar_voice_state(const void *state, int64_t state_bytes, int64_t need)
-{
-    if (state_bytes < need)
-        return fail(VND_ERR_INVALID, "state of %lld bytes, the voice pool needs %lld", (long long)state_bytes, (long long)need);
-    if (!state) return fail(VND_ERR_INVALID, "null state pointer");
-    if ((uintptr_t)state % 16 != 0) return fail(VND_ERR_INVALID, "the state is not 16-byte aligned");
-    return VND_OK;
-}
-
 template <class T>
 static vnd_status polar_voice_stream_dev(vnd_ctx *ctx, void *state, int64_t state_bytes, int64_t max_frames_per_call, const T *l,
                                          const T *r, int64_t stream_stride, int32_t frame_stride, const int32_t *counts,
@@ -265,25 +249,17 @@ static vnd_status polar_voice_stream_dev(vnd_ctx *ctx, void *state, int64_t stat
     PolarVoicePlan p{};
     vnd_status st = polar_voice_plan(slots, max_frames_per_call, (int32_t)sizeof(T), &p);
     if (st != VND_OK) return st;
-    if ((st = polar_voice_state(state, state_bytes, p.need)) != VND_OK) return st;
+    if ((st = voice_state_check("voice pool", state, state_bytes, p.need, slots)) != VND_OK) return st;
     if (!l || !r || !counts || !flags || !moments || !valid)
         return fail(VND_ERR_INVALID, "null chunk, counts, flags, moments or valid pointer");
-    // extents in elements: the last sample of the last slot's longest chunk
-    int64_t span, last;
-    if (__builtin_mul_overflow(slots - 1, stream_stride, &span) ||
-        __builtin_mul_overflow(max_frames_per_call - 1, (int64_t)frame_stride, &last) ||
-        __builtin_add_overflow(span, last, &span) || span > INT64_MAX / 16)
-        return fail(VND_ERR_INVALID, "buffer extents overflow");
-    const int64_t xb = (span + 1) * (int64_t)sizeof(T), mb = slots * vnd::kMoments * (int64_t)sizeof(double),
-                  vb = slots * (int64_t)sizeof(int32_t);
-    auto overlap = [](const void *u, int64_t ub, const void *v, int64_t vb_) {
-        const char *u0 = (const char *)u, *v0 = (const char *)v;
-        return u0 < v0 + vb_ && v0 < u0 + ub;
-    };
+    int64_t xb = 0;
+    if ((st = voice_chunk_bytes(slots, stream_stride, max_frames_per_call, frame_stride, sizeof(T), &xb)) != VND_OK) return st;
+    const int64_t mb = slots * vnd::kMoments * (int64_t)sizeof(double), vb = slots * (int64_t)sizeof(int32_t);
     for (const T *c : {l, r})
-        if (overlap(c, xb, moments, mb) || overlap(c, xb, valid, vb) || overlap(c, xb, state, p.need))
+        if (voice_overlap(c, xb, moments, mb) || voice_overlap(c, xb, valid, vb) || voice_overlap(c, xb, state, p.need))
             return fail(VND_ERR_INVALID, "moments, valid and the state must not overlap the chunk");
-    if (overlap(moments, mb, state, p.need) || overlap(valid, vb, state, p.need) || overlap(moments, mb, valid, vb))
+    if (voice_overlap(moments, mb, state, p.need) || voice_overlap(valid, vb, state, p.need) ||
+        voice_overlap(moments, mb, valid, vb))
         return fail(VND_ERR_INVALID, "moments, valid and the state must not overlap one another");
     DeviceScope on(ctx->device);
     if (!on.ok) return fail(VND_ERR_HIP, "cannot select device %d", ctx->device);
@@ -324,11 +300,8 @@ vnd_status vnd_polar_voice_stream_reset_dev(vnd_ctx *ctx, void *state, int64_t s
     PolarVoicePlan p{};
     vnd_status st = polar_voice_plan(slots, max_frames_per_call, sample_bytes, &p);
     if (st != VND_OK) return st;
-    if ((st = polar_voice_state(state, state_bytes, p.need)) != VND_OK) return st;
-    DeviceScope on(ctx->device);
-    if (!on.ok) return fail(VND_ERR_HIP, "cannot select device %d", ctx->device);
-    HIP_TRY(hipMemsetAsync(state, 0, (size_t)voice_position_bytes(slots), (hipStream_t)stream_));      // the positions only
-    return VND_OK;
+    if ((st = voice_state_check("voice pool", state, state_bytes, p.need, slots)) != VND_OK) return st;
+    return voice_reset_positions(ctx, state, slots, stream_);
 }
 
 vnd_status vnd_polar_voice_stream_f32_dev(vnd_ctx *ctx, void *state, int64_t state_bytes, int64_t max_frames_per_call,

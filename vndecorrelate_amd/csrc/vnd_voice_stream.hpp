@@ -23,20 +23,22 @@
 //   - y: the descriptor covers (n_out - t0) frames of row b from t0 on, n_out <= M + H = the row; t0 < n_out;
 //   - tables[b]: each_tile's bounds check (NaN rows), nothing is indexed with a bad one.
 //
-// voice_advance_kernel, one lane per slot, follows on the same stream and writes pos[b] and out_counts[b].  A kernel
-// boundary is the ordering between every workgroup's read of pos[b] and its update: within one kernel the workgroups of a
-// slot are not ordered, and the last one out would have to be found with an atomic.
+// voice_advance_kernel<VoiceStreamArgs>, one lane per slot, follows on the same stream and writes pos[b] and out_counts[b]
+// (vnd_voice_core.hpp: the slot rule, and why a kernel boundary orders the reads of pos[b] before its update).
 #pragma once
 #include "vnd_each_stream.hpp"
-#include "../../include/vnd_voice_stream.h"
+#include "vnd_voice_core.hpp"
 
 namespace vnd {
 
-constexpr int64_t kVoiceMaxPosition = (int64_t)1 << 60;
-constexpr int kVoiceAdvanceThreads = 256;
 constexpr int64_t kVoiceMaxFrames = (int64_t)1 << 24;     // tiles of a row <= 65535 at the smallest tile; counts are int32
 
 // One slot's side of a call, from the stored position, counts[b] and flags[b] alone (include/vnd_voice_stream.h).
+// The slot rule is written out here, not taken from voice_head (vnd_voice_core.hpp, which the two meters use): with the
+// head in between the compiler orders the scalar preamble of voice_stream_kernel and haas_voice_stream_kernel differently,
+// and these two are the kernels a decorrelating server runs per block.  What holds this text and voice_head to one rule
+// is the pools' GPU tests, which compare every pool's out_counts and positions with the NumPy mirrors call by call, bad
+// and idle slots planted; tests/test_voice_spans_cpu.py holds those mirrors, not this text, to the headers' formulas.
 struct VoiceSpan {
     int64_t p, n;                  // position the call starts at, frames pushed
     int64_t first_out, n_out;      // E, E' - E
@@ -72,14 +74,12 @@ struct VoiceStreamArgs {
     int32_t *__restrict__ out_counts;                   // [slots]
     int64_t M, H, cap;                                  // max_frames_per_call, the bank's largest tap index, H + M
     int32_t T, slots;                                   // candidates in the bank
+    __device__ VoiceAnswer advance(int64_t b) const
+    {
+        const VoiceSpan v = voice_span(pos[b], counts[b], flags[b], M, H);
+        return {(int32_t)v.n_out, v.ok, v.next};
+    }
 };
-
-__device__ __forceinline__ int64_t uniform_i64(int64_t v)
-{
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
 
 // grid = (slots, max(1, ceil((M + H) / tile))); dynamic LDS = CX planes of k.W floats
 template <int CX, int MODE, int R, bool EPI>
@@ -106,16 +106,6 @@ __global__ __launch_bounds__(kVpThreads) void voice_stream_kernel(const VoiceStr
         [&](int q, const float (&o)[4]) { store_result<2>(rdst, shape, k.stream_out, q, 1, 2, o); });
 }
 
-// grid = ceil(slots / kVoiceAdvanceThreads): behind voice_stream_kernel on the same stream
-__global__ __launch_bounds__(kVoiceAdvanceThreads) void voice_advance_kernel(const VoiceStreamArgs a)
-{
-    const int64_t b = (int64_t)blockIdx.x * kVoiceAdvanceThreads + threadIdx.x;
-    if (b >= a.slots) return;
-    const VoiceSpan v = voice_span(a.pos[b], a.counts[b], a.flags[b], a.M, a.H);
-    a.out_counts[b] = (int32_t)v.n_out;
-    if (v.ok) a.pos[b] = v.next;
-}
-
 }  // namespace vnd
 
 // ------------------------------------------------------------------------------
@@ -140,9 +130,6 @@ static voice_stream_kern_t voice_stream_by_mode(const EachStreamPlan &p)
     if (p.epi) return p.fma ? voice_stream_by_r<CX, 1, true>(p.r) : voice_stream_by_r<CX, 0, true>(p.r);
     return p.fma ? voice_stream_by_r<CX, 1, false>(p.r) : voice_stream_by_r<CX, 0, false>(p.r);
 }
-
-// The positions come first in the state, padded to 16 bytes; the ring follows.
-static int64_t voice_position_bytes(int64_t slots) { return (slots * (int64_t)sizeof(int64_t) + 15) & ~(int64_t)15; }
 
 // The tile of the pool: make_each_stream_plan's rule for a call of M output frames - what a slot in steady state
 // returns - chosen once, and the tiles of the longest row a call can write, M + H.
@@ -202,11 +189,7 @@ static vnd_status voice_stream_pool(const vnd_ctx *ctx, const vnd_taps *t, const
     int64_t need = 0;
     vnd_status st = voice_stream_scalars(ctx, t, max_frames_per_call, slots, Cx, mode, &need);
     if (st != VND_OK) return st;
-    if (state_bytes < need)
-        return fail(VND_ERR_INVALID, "state of %lld bytes, the voice pool needs %lld", (long long)state_bytes, (long long)need);
-    if (slots > 0 && !state) return fail(VND_ERR_INVALID, "null state pointer");
-    if ((uintptr_t)state % 16 != 0) return fail(VND_ERR_INVALID, "the state is not 16-byte aligned");
-    return VND_OK;
+    return voice_state_check("voice pool", state, state_bytes, need, slots);
 }
 
 vnd_status vnd_voice_stream_reset_dev(vnd_ctx *ctx, void *state, int64_t state_bytes, int64_t slots, int32_t Cx,
@@ -214,11 +197,7 @@ vnd_status vnd_voice_stream_reset_dev(vnd_ctx *ctx, void *state, int64_t state_b
 {
     vnd_status st = voice_stream_pool(ctx, t, state, state_bytes, max_frames_per_call, slots, Cx, VND_MODE_EXACT);
     if (st != VND_OK) return st;
-    if (slots == 0) return VND_OK;
-    DeviceScope on(ctx->device);
-    if (!on.ok) return fail(VND_ERR_HIP, "cannot select device %d", ctx->device);
-    HIP_TRY(hipMemsetAsync(state, 0, (size_t)voice_position_bytes(slots), (hipStream_t)stream_));     // the positions only
-    return VND_OK;
+    return slots == 0 ? VND_OK : voice_reset_positions(ctx, state, slots, stream_);
 }
 
 static vnd_status voice_stream_check(const vnd_ctx *ctx, const vnd_taps *t, const void *state, int64_t state_bytes,
@@ -262,8 +241,7 @@ vnd_status vnd_voice_stream_f32_dev(vnd_ctx *ctx, const vnd_taps *t, void *state
     hipStream_t stream = (hipStream_t)stream_;
     hipLaunchKernelGGL(kern, dim3((unsigned)slots, (unsigned)p.tiles), dim3(kVpThreads), p.lds_bytes, stream, a);
     HIP_TRY(hipGetLastError());
-    const unsigned groups = (unsigned)((slots + kVoiceAdvanceThreads - 1) / kVoiceAdvanceThreads);
-    hipLaunchKernelGGL(voice_advance_kernel, dim3(groups), dim3(kVoiceAdvanceThreads), 0, stream, a);
+    launch_voice_advance(a, slots, stream);
     HIP_TRY(hipGetLastError());
     return VND_OK;
 }

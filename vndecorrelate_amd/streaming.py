@@ -599,6 +599,22 @@ VOICE_START, VOICE_END = _native.VOICE_START, _native.VOICE_END
 VOICE_MAX_POSITION = 1 << 60            # the largest position a call goes on from
 
 
+def _voice_head(positions, counts, flags, max_frames_per_call: Optional[int]):
+    """What every span function starts from: ``(pos, n, start, end, p, bad)`` as int64 / bool arrays of one shape, with
+    ``p = START ? 0 : pos`` and ``bad`` the slots whose count or ``p`` the device refuses."""
+    pos = np.asarray(positions, np.int64)
+    n = np.asarray(counts, np.int64)
+    f = np.asarray(flags, np.int64)
+    if not (pos.shape == n.shape == f.shape):
+        raise ValueError(f'positions, counts and flags of one shape, got {pos.shape}, {n.shape}, {f.shape}')
+    start, end = (f & VOICE_START) != 0, (f & VOICE_END) != 0
+    p = np.where(start, 0, pos)
+    bad = (n < 0) | (p < 0) | (p > VOICE_MAX_POSITION)
+    if max_frames_per_call is not None:
+        bad |= n > int(max_frames_per_call)
+    return pos, n, start, end, p, bad
+
+
 def voice_spans(positions, counts, flags, latency: int, max_frames_per_call: Optional[int] = None):
     """``(out_counts, new_positions)`` of one call of a voice pool (``include/vnd_voice_stream.h``), per slot, from the
     positions before the call, the frames pushed and the ``VOICE_START`` / ``VOICE_END`` flags alone - what the device
@@ -609,29 +625,44 @@ def voice_spans(positions, counts, flags, latency: int, max_frames_per_call: Opt
 
     A count below 0 (or above ``max_frames_per_call``, when given), or without START a position outside ``[0, 2^60]``,
     answers -1 and leaves the position as it was."""
-    pos = np.asarray(positions, np.int64)
-    n = np.asarray(counts, np.int64)
-    f = np.asarray(flags, np.int64)
-    if not (pos.shape == n.shape == f.shape):
-        raise ValueError(f'positions, counts and flags of one shape, got {pos.shape}, {n.shape}, {f.shape}')
+    pos, n, start, end, p, bad = _voice_head(positions, counts, flags, max_frames_per_call)
     H = int(latency)
-    start, end = (f & VOICE_START) != 0, (f & VOICE_END) != 0
-    p = np.where(start, 0, pos)
     first = np.maximum(0, p - H)
     last = np.where(end, p + n, np.maximum(0, p + n - H))
-    bad = (n < 0) | (p < 0) | (p > VOICE_MAX_POSITION)
-    if max_frames_per_call is not None:
-        bad |= n > int(max_frames_per_call)
     out = np.where(bad, -1, last - first).astype(np.int64)
     new = np.where(bad, pos, np.where(end, 0, p + n)).astype(np.int64)
     return out, new
 
 
+def _check_slots(slots: int):
+    if slots > _native.MAX_STREAMS_PER_CALL:
+        raise ValueError(f'slots {slots} above {_native.MAX_STREAMS_PER_CALL}: split the pool')
+
+
+def _slot_ints(slots: int, *names):
+    """The spec of a pool's int32 ``(slots,)`` input tensors."""
+    return tuple((name, (slots,), 'int32', None) for name in names)
+
+
+def _check_device_tensors(tensors, specs):
+    """``process_dev``'s look at its tensors, each against its ``(name, shape, dtype, fill)`` of the pool's spec: an
+    output (``fill`` set) may be None; no device memory is read."""
+    for t, (name, shape, dtype, fill) in zip(tensors, specs):
+        if t is None and fill:
+            continue
+        if not _native.is_torch(t) or not t.is_cuda:
+            raise ValueError(f'{name} must be a device tensor')
+        if tuple(t.shape) != shape or str(t.dtype) != 'torch.' + dtype or not t.is_contiguous():
+            raise ValueError(f'{name} must be a contiguous {dtype} tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}')
+
+
 class _SlotPool:
-    """What the voice pools share (:class:`VoicePool`, :class:`HaasVoicePool`, :class:`ChainVoicePool`): the host's mirror of
-    the slots, ``reset()``, and the dict form ``process`` with every refusal before the device.  A pool sets ``slots``,
-    ``in_channels``, ``max_frames_per_call`` and ``_state = None``, calls ``_mirror()``, and supplies the hooks below and
-    ``_allocate`` / ``_reset_device`` / ``_call_host``."""
+    """What the voice pools share (:class:`VoicePool`, :class:`HaasVoicePool`, :class:`ChainVoicePool` and the two meters
+    of ``analysis.py``): the host's mirror of the slots, ``reset()``, the dict form ``process`` with every refusal before
+    the device, the state and the device form.  A pool sets ``slots``, ``in_channels``, ``max_frames_per_call``,
+    ``_state = None`` and the spec of its device tensors - ``_inputs`` and its two ``_outputs``, ``(name, shape, dtype,
+    fill)`` each, ``fill`` None for an input and ``'empty'`` or ``'zeros'``, how an absent one is allocated, for an
+    output - calls ``_mirror()``, and supplies the hooks below and ``_call_host``."""
 
     def _mirror(self):
         """The host's copy of what the device state says, for the dict form: all slots idle at position 0."""
@@ -640,6 +671,13 @@ class _SlotPool:
         self.tables = np.zeros(self.slots, np.int32)
         self._form = None
 
+    def _require_form(self, form: str):
+        """A pool runs through one form until ``reset()``: refuse a call of ``form`` after one of the other."""
+        if form == 'dict' and self._form == 'dev':
+            raise RuntimeError('this pool runs through process_dev(): the host does not know its positions; reset() first')
+        if form == 'dev' and self._form == 'dict':
+            raise RuntimeError('this pool runs through process(): mixing in process_dev() would leave the host mirror '
+                               'of the positions stale; reset() first')
 
     # ---- public ------------------------------------------------------------------------
     def reset(self):
@@ -661,8 +699,7 @@ class _SlotPool:
         a block or an end for a slot that was never started, a start on a live slot (``discard=True`` allows it: what
         the slot held is dropped, unflushed), a bank index outside the bank, a block above ``max_frames_per_call`` or of
         another channel count; ``TypeError`` for a block that is not float32."""
-        if self._form == 'dev':
-            raise RuntimeError('this pool runs through process_dev(): the host does not know its positions; reset() first')
+        self._require_form('dict')
         counts, flags, tables, live, x, answered = self._schedule(blocks, start, end, discard)
         if not counts.any() and not flags.any():              # nothing pushed, started or ended: no device call
             return {slot: np.zeros((0, self._out_width), self._out_dtype) for slot in answered}
@@ -699,6 +736,18 @@ class _SlotPool:
 
     def _commit(self, positions):
         self.positions = positions
+
+    def _state_bytes(self, ctx) -> int:
+        """The bytes of the pool's device state."""
+        raise NotImplementedError
+
+    def _reset_entry(self, ctx, state_ptr: int, state_bytes: int, stream: int):
+        """The pool's native reset."""
+        raise NotImplementedError
+
+    def _launch(self, ctx, state_ptr: int, state_bytes: int, inputs, first, second, stream: int):
+        """The pool's native device call on its tuple of input tensors and its two output tensors."""
+        raise NotImplementedError
 
     # ---- checks --------------------------------------------------------------------------
     def _slot(self, slot, what: str) -> int:
@@ -750,10 +799,93 @@ class _SlotPool:
             answered.add(slot)
         return counts, flags, tables, live, x, sorted(answered)
 
+    def _start_slots(self, start) -> dict:
+        """``start`` as ``_schedule`` takes it, for a pool whose voices start with nothing of their own: a list of slots."""
+        starts = {}
+        for slot in list(start or ()):
+            slot = self._slot(slot, 'start')
+            if slot in starts:
+                raise ValueError(f'start: slot {slot} is named twice')
+            starts[slot] = 0
+        return starts
+
+    # ---- the device -------------------------------------------------------------------------
     def _ensure_state(self, torch, ctx):
         if self._state is None:
             self._allocate(torch, ctx)
         return self._state
+
+    def _allocate(self, torch, ctx):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('the state of a voice pool is allocated and zeroed on first use: call reset() before the capture')
+        need = self._state_bytes(ctx)
+        buf = torch.empty((max(need, 16),), dtype=torch.uint8, device=torch.device('cuda', ctx.device))
+        self._state = (buf, need)
+        self._reset_device(torch, ctx)
+
+    def _reset_device(self, torch, ctx):
+        state, state_bytes = self._state
+        self._reset_entry(ctx, state.data_ptr(), state_bytes, torch.cuda.current_stream(state.device).cuda_stream)
+
+    def _process_dev(self, inputs, out):
+        """``process_dev``: the form guard and the look at the tensors (no device memory is read), then the call."""
+        if self._form == 'dict':
+            self._require_form('dev')
+        _check_device_tensors(inputs, self._inputs)
+        if out is None:
+            return self._call_device(_native.torch_module(), inputs, None, None)
+        first, second = out
+        _check_device_tensors(out, self._outputs)
+        return self._call_device(_native.torch_module(), inputs, first, second)
+
+    def _call_device(self, torch, inputs, first, second):
+        """One device call on the current stream: the tuple of input tensors and the two outputs, each a tensor or None
+        (None: allocated here).  Returns the outputs."""
+        ctx = _native.default_context()
+        device = torch.device('cuda', ctx.device)
+        for t in inputs:
+            if t.device != device:
+                raise ValueError(f'tensor on {t.device}, the pool runs on {device}')
+        state, state_bytes = self._ensure_state(torch, ctx)
+        if first is None:
+            first = self._new_output(torch, device, *self._outputs[0])
+        if second is None:
+            second = self._new_output(torch, device, *self._outputs[1])
+        self._form = 'dev'
+        self._launch(ctx, state.data_ptr(), state_bytes, inputs, first, second, torch.cuda.current_stream(device).cuda_stream)
+        return first, second
+
+    @staticmethod
+    def _new_output(torch, device, name, shape, dtype, fill):
+        return getattr(torch, fill)(shape, dtype=getattr(torch, dtype), device=device)
+
+    def _call_host_packed(self, x, ints):
+        """A ``_call_host`` on the device form: one upload (the blocks and the int32 arrays ``ints`` in one buffer), the
+        call, one download (the pool's outputs in one buffer); ``transfers`` counts them.  ``_form`` stays as it was."""
+        torch = _native.torch_module()
+        device = torch.device('cuda', _native.default_context().device)
+        ints = np.stack(ints).astype(np.int32)
+        up = torch.from_numpy(np.concatenate([x.reshape(-1).view(np.uint8), ints.reshape(-1).view(np.uint8)])).to(device)
+        self.transfers = {'to_device': 1, 'to_host': 0}
+        x_dev = up[:x.nbytes].view(getattr(torch, x.dtype.name)).view(x.shape)
+        int_rows = up[x.nbytes:].view(torch.int32).view(len(ints), self.slots)
+        # the download buffer: the first output, then the second (int32 after a multiple of 8 bytes); zeroed as a whole
+        # if the pool wants either output zero-filled
+        (_, shape0, dtype0, fill0), (_, shape1, dtype1, fill1) = self._outputs
+        bytes0 = int(np.prod(shape0)) * np.dtype(dtype0).itemsize
+        bytes1 = int(np.prod(shape1)) * np.dtype(dtype1).itemsize
+        allocate = torch.zeros if 'zeros' in (fill0, fill1) else torch.empty
+        down = allocate((bytes0 + bytes1,), dtype=torch.uint8, device=device)
+        out0 = down[:bytes0].view(getattr(torch, dtype0)).view(shape0)
+        out1 = down[bytes0:].view(getattr(torch, dtype1)).view(shape1)
+        form = self._form
+        try:
+            self._call_device(torch, (x_dev, *int_rows), out0, out1)
+        finally:
+            self._form = form
+        host = down.cpu().numpy()
+        self.transfers['to_host'] = 1
+        return host[:bytes0].view(dtype0).reshape(shape0), host[bytes0:].view(dtype1).reshape(shape1)
 
 
 class VoicePool(_SlotPool):
@@ -780,8 +912,7 @@ class VoicePool(_SlotPool):
         _check_counts(slots=slots, in_channels=in_channels, max_frames_per_call=max_frames_per_call)
         if in_channels not in (1, 2):
             raise ValueError(f'a pool of mono (1) or stereo (2) voices is taken, got in_channels={in_channels}')
-        if slots > _native.MAX_STREAMS_PER_CALL:
-            raise ValueError(f'slots {slots} above {_native.MAX_STREAMS_PER_CALL}: split the pool')
+        _check_slots(slots)
         if max_frames_per_call > 1 << 24:
             raise ValueError(f'max_frames_per_call {max_frames_per_call} above 2**24')
         if arrays.num_channels < 2 or arrays.num_channels % 2:
@@ -797,6 +928,9 @@ class VoicePool(_SlotPool):
         self.num_channels = 2
         self._table = None
         self._state = None                    # (torch uint8 tensor, bytes)
+        S, M = self.slots, self.max_frames_per_call
+        self._inputs = (('x', (S, M, self.in_channels), 'float32', None),) + _slot_ints(S, 'counts', 'flags', 'tables')
+        self._outputs = (('y', (S, M + self.latency_frames, 2), 'float32', 'empty'), ('out_counts', (S,), 'int32', 'empty'))
         self._mirror()
 
     @property
@@ -810,22 +944,7 @@ class VoicePool(_SlotPool):
         ``(slots, M + H, 2)`` - the first ``out_counts[b]`` frames of row b are written, nothing at or past them - and
         int32 ``(slots,)``; ``out=(y, out_counts)`` takes the caller's.  No check reads device memory; bad per-slot
         values answer as ``include/vnd_voice_stream.h`` says (-1, NaN rows)."""
-        if self._form == 'dict':
-            raise RuntimeError('this pool runs through process(): mixing in process_dev() would leave the host mirror '
-                               'of the positions stale; reset() first')
-        S, M, cx = self.slots, self.max_frames_per_call, self.in_channels
-        y, out_counts = out if out is not None else (None, None)
-        for name, t, shape, dtype in (('x', x, (S, M, cx), 'float32'), ('counts', counts, (S,), 'int32'),
-                                      ('flags', flags, (S,), 'int32'), ('tables', tables, (S,), 'int32'),
-                                      ('y', y, (S, self.row_frames, 2), 'float32'),
-                                      ('out_counts', out_counts, (S,), 'int32')):
-            if t is None and name in ('y', 'out_counts'):
-                continue
-            if not _native.is_torch(t) or not t.is_cuda:
-                raise ValueError(f'{name} must be a device tensor')
-            if tuple(t.shape) != shape or str(t.dtype) != 'torch.' + dtype or not t.is_contiguous():
-                raise ValueError(f'{name} must be a contiguous {dtype} tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}')
-        return self._call_device(_native.torch_module(), x, counts, flags, tables, y, out_counts)
+        return self._process_dev((x, counts, flags, tables), out)
 
     def _spans(self, counts, flags, tables):
         return voice_spans(self.positions, counts, flags, self.latency_frames, self.max_frames_per_call)
@@ -837,21 +956,14 @@ class VoicePool(_SlotPool):
         return self.bank_tables[index]
 
     # ---- the device -------------------------------------------------------------------------
-    def _allocate(self, torch, ctx):
+    def _state_bytes(self, ctx) -> int:
         from . import decorrelation
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError('the state of a voice pool is allocated and zeroed on first use: call reset() before the capture')
         self._table = decorrelation._each_banks.get(ctx, self.arrays)
-        need = _native.voice_stream_state_bytes(self._table, self.slots, self.in_channels, self.max_frames_per_call)
-        buf = torch.empty((max(need, 16),), dtype=torch.uint8, device=torch.device('cuda', ctx.device))
-        self._state = (buf, need)
-        self._reset_device(torch, ctx)
+        return _native.voice_stream_state_bytes(self._table, self.slots, self.in_channels, self.max_frames_per_call)
 
-    def _reset_device(self, torch, ctx):
-        state, state_bytes = self._state
-        _native.voice_stream_reset_device(ctx, self._table, state.data_ptr(), state_bytes, self.slots, self.in_channels,
-                                          self.max_frames_per_call,
-                                          stream=torch.cuda.current_stream(state.device).cuda_stream)
+    def _reset_entry(self, ctx, state_ptr, state_bytes, stream):
+        _native.voice_stream_reset_device(ctx, self._table, state_ptr, state_bytes, self.slots, self.in_channels,
+                                          self.max_frames_per_call, stream=stream)
 
     def _call_host(self, x, counts, flags, tables):
         torch = _native.torch_module()
@@ -863,23 +975,12 @@ class VoicePool(_SlotPool):
                                         flags, tables, y, ms_encode=self.ms_encode, width=self.width)
         return y, got
 
-    def _call_device(self, torch, x, counts, flags, tables, y, out_counts):
-        ctx = _native.default_context()
-        device = torch.device('cuda', ctx.device)
-        for t in (x, counts, flags, tables):
-            if t.device != device:
-                raise ValueError(f'tensor on {t.device}, the pool runs on {device}')
-        state, state_bytes = self._ensure_state(torch, ctx)
-        if y is None:
-            y = torch.empty((self.slots, self.row_frames, 2), dtype=torch.float32, device=device)
-        if out_counts is None:
-            out_counts = torch.empty((self.slots,), dtype=torch.int32, device=device)
-        self._form = 'dev'
-        _native.voice_stream_device(ctx, self._table, state.data_ptr(), state_bytes, self.max_frames_per_call, x.data_ptr(),
+    def _launch(self, ctx, state_ptr, state_bytes, inputs, y, out_counts, stream):
+        x, counts, flags, tables = inputs
+        _native.voice_stream_device(ctx, self._table, state_ptr, state_bytes, self.max_frames_per_call, x.data_ptr(),
                                     counts.data_ptr(), flags.data_ptr(), tables.data_ptr(), y.data_ptr(),
                                     out_counts.data_ptr(), self.slots, self.in_channels, ms_encode=self.ms_encode,
-                                    width=self.width, stream=torch.cuda.current_stream(device).cuda_stream)
-        return y, out_counts
+                                    width=self.width, stream=stream)
 
 
 # ----------------------------------------------------------------------------
@@ -909,17 +1010,6 @@ def haas_voice_spans(positions, counts, flags, delays, max_delay: int, max_frame
     return out, np.where(bad, pos, new).astype(np.int64)
 
 
-def _check_device_tensors(specs):
-    """``process_dev``'s look at its tensors: ``(name, tensor, shape, dtype, optional)`` each; no device memory is read."""
-    for name, t, shape, dtype, optional in specs:
-        if t is None and optional:
-            continue
-        if not _native.is_torch(t) or not t.is_cuda:
-            raise ValueError(f'{name} must be a device tensor')
-        if tuple(t.shape) != shape or str(t.dtype) != 'torch.' + dtype or not t.is_contiguous():
-            raise ValueError(f'{name} must be a contiguous {dtype} tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}')
-
-
 class HaasVoicePool(_SlotPool):
     """``slots`` slots over a bank of ``HaasEffect`` delays, each slot a voice with a life of its own
     (``decorrelation.decorrelate_voice_pool``, ``vnd_haas_voice_stream_f64_*``): :class:`VoicePool` for the Haas delay.
@@ -940,8 +1030,7 @@ class HaasVoicePool(_SlotPool):
         _check_counts(slots=slots, in_channels=in_channels, max_frames_per_call=max_frames_per_call)
         if in_channels not in (1, 2):
             raise ValueError(f'a pool of mono (1) or stereo (2) voices is taken, got in_channels={in_channels}')
-        if slots > _native.MAX_STREAMS_PER_CALL:
-            raise ValueError(f'slots {slots} above {_native.MAX_STREAMS_PER_CALL}: split the pool')
+        _check_slots(slots)
         self.bank_delays = np.ascontiguousarray(bank_delays, np.int32)
         if self.bank_delays.ndim != 1 or not self.bank_delays.size or self.bank_delays.min() < 0:
             raise ValueError('bank_delays: one delay >= 0 per bank entry')
@@ -956,6 +1045,9 @@ class HaasVoicePool(_SlotPool):
         self.latency_frames, self.tail_frames = 0, self.max_delay
         self.num_channels = 2
         self._state = None
+        S, M = self.slots, self.max_frames_per_call
+        self._inputs = (('x', (S, M, self.in_channels), 'float32', None),) + _slot_ints(S, 'counts', 'flags', 'delays')
+        self._outputs = (('y', (S, self.row_frames, 2), 'float64', 'empty'), ('out_counts', (S,), 'int32', 'empty'))
         self._mirror()
 
     @property
@@ -969,16 +1061,7 @@ class HaasVoicePool(_SlotPool):
         ``(slots, M + max delay, 2)`` - the first ``out_counts[b]`` frames of row b are written, nothing at or past
         them - and int32 ``(slots,)``; ``out=(y, out_counts)`` takes the caller's.  No check reads device memory; bad
         per-slot values answer -1 (``include/vnd_haas_voice_stream.h``)."""
-        if self._form == 'dict':
-            raise RuntimeError('this pool runs through process(): mixing in process_dev() would leave the host mirror '
-                               'of the positions stale; reset() first')
-        S, M, cx = self.slots, self.max_frames_per_call, self.in_channels
-        y, out_counts = out if out is not None else (None, None)
-        _check_device_tensors((('x', x, (S, M, cx), 'float32', False), ('counts', counts, (S,), 'int32', False),
-                               ('flags', flags, (S,), 'int32', False), ('delays', delays, (S,), 'int32', False),
-                               ('y', y, (S, self.row_frames, 2), 'float64', True),
-                               ('out_counts', out_counts, (S,), 'int32', True)))
-        return self._call_device(_native.torch_module(), x, counts, flags, delays, y, out_counts)
+        return self._process_dev((x, counts, flags, delays), out)
 
     def _spans(self, counts, flags, delays):
         return haas_voice_spans(self.positions, counts, flags, delays, self.max_delay, self.max_frames_per_call)
@@ -990,19 +1073,12 @@ class HaasVoicePool(_SlotPool):
         return self.bank_delays[index]                           # ``tables`` holds the slots' delays
 
     # ---- the device -------------------------------------------------------------------------
-    def _allocate(self, torch, ctx):
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError('the state of a voice pool is allocated and zeroed on first use: call reset() before the capture')
-        need = _native.haas_voice_stream_state_bytes(self.slots, self.in_channels, self.max_delay, self.max_frames_per_call)
-        buf = torch.empty((max(need, 16),), dtype=torch.uint8, device=torch.device('cuda', ctx.device))
-        self._state = (buf, need)
-        self._reset_device(torch, ctx)
+    def _state_bytes(self, ctx) -> int:
+        return _native.haas_voice_stream_state_bytes(self.slots, self.in_channels, self.max_delay, self.max_frames_per_call)
 
-    def _reset_device(self, torch, ctx):
-        state, state_bytes = self._state
-        _native.haas_voice_stream_reset_device(ctx, state.data_ptr(), state_bytes, self.slots, self.in_channels,
-                                               self.max_delay, self.max_frames_per_call,
-                                               stream=torch.cuda.current_stream(state.device).cuda_stream)
+    def _reset_entry(self, ctx, state_ptr, state_bytes, stream):
+        _native.haas_voice_stream_reset_device(ctx, state_ptr, state_bytes, self.slots, self.in_channels, self.max_delay,
+                                               self.max_frames_per_call, stream=stream)
 
     def _call_host(self, x, counts, flags, delays):
         torch = _native.torch_module()
@@ -1015,24 +1091,13 @@ class HaasVoicePool(_SlotPool):
                                              ms_mode=self.ms_mode, width=self.width)
         return y, got
 
-    def _call_device(self, torch, x, counts, flags, delays, y, out_counts):
-        ctx = _native.default_context()
-        device = torch.device('cuda', ctx.device)
-        for t in (x, counts, flags, delays):
-            if t.device != device:
-                raise ValueError(f'tensor on {t.device}, the pool runs on {device}')
-        state, state_bytes = self._ensure_state(torch, ctx)
-        if y is None:
-            y = torch.empty((self.slots, self.row_frames, 2), dtype=torch.float64, device=device)
-        if out_counts is None:
-            out_counts = torch.empty((self.slots,), dtype=torch.int32, device=device)
-        self._form = 'dev'
-        _native.haas_voice_stream_device(ctx, state.data_ptr(), state_bytes, self.max_frames_per_call, x.data_ptr(),
+    def _launch(self, ctx, state_ptr, state_bytes, inputs, y, out_counts, stream):
+        x, counts, flags, delays = inputs
+        _native.haas_voice_stream_device(ctx, state_ptr, state_bytes, self.max_frames_per_call, x.data_ptr(),
                                          counts.data_ptr(), flags.data_ptr(), delays.data_ptr(), y.data_ptr(),
                                          out_counts.data_ptr(), self.slots, self.in_channels, max_delay=self.max_delay,
                                          delayed_channel=self.delayed_channel, ms_mode=self.ms_mode, width=self.width,
-                                         stream=torch.cuda.current_stream(device).cuda_stream)
-        return y, out_counts
+                                         stream=stream)
 
 
 class ChainVoicePool(VoicePool):
@@ -1071,6 +1136,10 @@ class ChainVoicePool(VoicePool):
         self.max_delay = self.tail_frames = self.haas.max_delay
         self.transfers = {'to_device': 0, 'to_host': 0}
         self._mid = None                      # (float32 (slots, M + H, 2), int32 (slots,)): stage 1's result, on the device
+        self._inputs += _slot_ints(self.slots, 'delays')
+        # stage 2's: what process_dev checks and the host call carves.  Stage 1 runs through the inherited _call_device
+        # with _mid always passed, so these shapes are never what its outputs are allocated from.
+        self._outputs = self.haas._outputs
 
     def _mirror(self):
         VoicePool._mirror(self)
@@ -1094,17 +1163,7 @@ class ChainVoicePool(VoicePool):
         stage 2 only: it answers -1 and stands still, but stage 1 has taken the block and moved on, so the two stages of
         that voice are out of step and its frames of this call are lost - restart the voice (START) before it goes on.
         The dict form cannot send one: its delays come from the bank."""
-        if self._form == 'dict':
-            raise RuntimeError('this pool runs through process(): mixing in process_dev() would leave the host mirror '
-                               'of the positions stale; reset() first')
-        S, M, cx = self.slots, self.max_frames_per_call, self.in_channels
-        y, out_counts = out if out is not None else (None, None)
-        _check_device_tensors((('x', x, (S, M, cx), 'float32', False), ('counts', counts, (S,), 'int32', False),
-                               ('flags', flags, (S,), 'int32', False), ('tables', tables, (S,), 'int32', False),
-                               ('delays', delays, (S,), 'int32', False),
-                               ('y', y, (S, self.row_frames, 2), 'float64', True),
-                               ('out_counts', out_counts, (S,), 'int32', True)))
-        return self._call_device(_native.torch_module(), x, counts, flags, tables, delays, y, out_counts)
+        return self._process_dev((x, counts, flags, tables, delays), out)
 
     def _spans(self, counts, flags, entries):
         mid, first = voice_spans(self.positions, counts, flags, self.latency_frames, self.max_frames_per_call)
@@ -1130,32 +1189,17 @@ class ChainVoicePool(VoicePool):
 
     def _call_host(self, x, counts, flags, tables, delays):
         """One upload (the blocks and the four int32 arrays in one buffer), both stages, one download (y and out_counts)."""
-        torch = _native.torch_module()
-        ctx = _native.default_context()
-        device = torch.device('cuda', ctx.device)
-        S = self.slots
-        ints = np.stack([counts, flags, tables, delays]).astype(np.int32)
-        up = torch.from_numpy(np.concatenate([x.reshape(-1).view(np.uint8), ints.reshape(-1).view(np.uint8)])).to(device)
-        self.transfers = {'to_device': 1, 'to_host': 0}
-        x_dev = up[:x.nbytes].view(torch.float32).view(x.shape)
-        c, f, t, d = up[x.nbytes:].view(torch.int32).view(4, S)
-        y_bytes = S * self.row_frames * 2 * 8
-        down = torch.empty((y_bytes + 4 * S,), dtype=torch.uint8, device=device)
-        y = down[:y_bytes].view(torch.float64).view(S, self.row_frames, 2)
-        out_counts = down[y_bytes:].view(torch.int32)
         form = self._form
         try:
-            self._call_device(torch, x_dev, c, f, t, d, y, out_counts)
+            return self._call_host_packed(x, (counts, flags, tables, delays))
         finally:
-            self._form = self.haas._form = form
-        host = down.cpu().numpy()
-        self.transfers['to_host'] = 1
-        return host[:y_bytes].view(np.float64).reshape(S, self.row_frames, 2), host[y_bytes:].view(np.int32)
+            self.haas._form = form
 
-    def _call_device(self, torch, x, counts, flags, tables, delays, y, out_counts):
+    def _call_device(self, torch, inputs, y, out_counts):
+        x, counts, flags, tables, delays = inputs
         ctx = _native.default_context()
         self._ensure_state(torch, ctx)
         self.haas._ensure_state(torch, ctx)
         mid, mid_counts = self._mid
-        VoicePool._call_device(self, torch, x, counts, flags, tables, mid, mid_counts)
-        return self.haas._call_device(torch, mid, mid_counts, flags, delays, y, out_counts)
+        VoicePool._call_device(self, torch, (x, counts, flags, tables), mid, mid_counts)
+        return self.haas._call_device(torch, (mid, mid_counts, flags, delays), y, out_counts)
