@@ -46,6 +46,14 @@ from .analysis import (  # noqa: F401
     set_scope_device,
     stereo_image_voice_pool,
 )
+from .spectral import (  # noqa: F401
+    coherence_batched,
+    csd_batched,
+    set_spectrum_device,
+    spectrogram_batched,
+    spectrum_covers,
+    welch_batched,
+)
 from .streaming import (  # noqa: F401
     ChainStream,
     ChainVoicePool,

@@ -392,6 +392,28 @@ LEVEL_MAX_PERCENTILES = 4         # VND_LEVEL_MAX_PERCENTILES
 LEVEL_MAX_BINS = 1024             # VND_LEVEL_MAX_BINS
 LEVEL_SPAN_FRAMES = 32768         # VND_LEVEL_SPAN_FRAMES
 
+# include/vnd_spectrum.h: short-time spectra of a pool - spectrogram columns and the Welch sums Pxx, Pyy, Pxy
+_SPECTRUM_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                  ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                  ctypes.c_int32, ctypes.c_double, ctypes.c_void_p]
+_SPECTROGRAM_ARGS = _SPECTRUM_ARGS + [ctypes.c_void_p, ctypes.c_void_p]
+_CROSS_SPECTRA_ARGS = _SPECTRUM_ARGS + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                        ctypes.c_void_p]
+SPECTRUM_SIGNATURES = {
+    'vnd_spectrum_run_length': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                               ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
+    'vnd_cross_spectra_work_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                    ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                    ctypes.POINTER(ctypes.c_int64)]),
+    'vnd_spectrogram_f32_dev': (ctypes.c_int, _SPECTROGRAM_ARGS),
+    'vnd_spectrogram_f64_dev': (ctypes.c_int, _SPECTROGRAM_ARGS),
+    'vnd_cross_spectra_f32_dev': (ctypes.c_int, _CROSS_SPECTRA_ARGS),
+    'vnd_cross_spectra_f64_dev': (ctypes.c_int, _CROSS_SPECTRA_ARGS),
+}
+SPECTRUM_MIN_NFFT = 64            # VND_SPECTRUM_MIN_NFFT
+SPECTRUM_MAX_NFFT = 4096          # VND_SPECTRUM_MAX_NFFT
+SPECTRUM_RUN = 32                 # VND_SPECTRUM_RUN
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -448,7 +470,8 @@ def load_library():
                                   + list(HAAS_VOICE_STREAM_SIGNATURES.items())
                                   + list(CORRELOGRAM_VOICE_STREAM_SIGNATURES.items())
                                   + list(POLAR_VOICE_STREAM_SIGNATURES.items())
-                                  + list(SCOPE_SIGNATURES.items()) + list(LEVEL_SIGNATURES.items())):
+                                  + list(SCOPE_SIGNATURES.items()) + list(LEVEL_SIGNATURES.items())
+                                  + list(SPECTRUM_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -1139,6 +1162,56 @@ def polar_level_device(ctx: 'Context', l_ptr: int, r_ptr: int, batch: int, n: in
         int(bool(ms_mode)), int(bool(semicircular)), float(radius_scale), ctypes.c_void_p(angle_edges_ptr), num_bins,
         ps, len(percentiles), ctypes.c_void_p(n_each_ptr), ctypes.c_void_p(levels_ptr), ctypes.c_void_p(bin_counts_ptr),
         ctypes.c_void_p(work_ptr), work_bytes, ctypes.c_void_p(stream)), name)
+
+
+def spectrum_run_length(nfft: int, nperseg: int, hop: int, float64: bool = False, cross_channels: int = 0) -> int:
+    """``vnd_spectrum_run_length``: the consecutive segments of one signal a workgroup owns - ``cross_channels`` 0 for the
+    spectrogram, 1 or 2 for the cross spectra."""
+    run = ctypes.c_int32()
+    _check(load_library().vnd_spectrum_run_length(nfft, nperseg, hop, int(bool(float64)), cross_channels, ctypes.byref(run)),
+           'vnd_spectrum_run_length')
+    return run.value
+
+
+def cross_spectra_work_bytes(batch: int, n: int, channels: int, nperseg: int, hop: int, nfft: int,
+                             float64: bool = False) -> int:
+    """``vnd_cross_spectra_work_bytes``: the work memory of one ``vnd_cross_spectra_*_dev`` call of this shape."""
+    need = ctypes.c_int64()
+    _check(load_library().vnd_cross_spectra_work_bytes(batch, n, channels, nperseg, hop, nfft, int(bool(float64)),
+                                                       ctypes.byref(need)), 'vnd_cross_spectra_work_bytes')
+    return need.value
+
+
+def _spectrum_args(ctx, frames_ptr, batch, n, stream_stride, frame_stride, channels, window_ptr, twiddles_ptr, nperseg, hop,
+                   nfft, detrend, scale, n_each_ptr):
+    return (ctx.handle, ctypes.c_void_p(frames_ptr), batch, n, stream_stride, frame_stride, channels,
+            ctypes.c_void_p(window_ptr), ctypes.c_void_p(twiddles_ptr), nperseg, hop, nfft, int(bool(detrend)), float(scale),
+            ctypes.c_void_p(n_each_ptr))
+
+
+def spectrogram_device(ctx: 'Context', frames_ptr: int, batch: int, n: int, stream_stride: int, frame_stride: int,
+                       channels: int, window_ptr: int, twiddles_ptr: int, nperseg: int, hop: int, nfft: int, sxx_ptr: int, *,
+                       detrend: bool = True, scale: float = 1.0, n_each_ptr: int = 0, float64: bool = False, stream: int = 0):
+    """``vnd_spectrogram_f32_dev`` (``_f64_dev`` with ``float64``): the power columns of every signal and channel of a pool,
+    ``(batch, channels, nfft // 2 + 1, (n - nperseg) // hop + 1)`` of the sample type, all device memory, enqueued on
+    ``stream``."""
+    name = 'vnd_spectrogram_f64_dev' if float64 else 'vnd_spectrogram_f32_dev'
+    _check(getattr(ctx._lib, name)(
+        *_spectrum_args(ctx, frames_ptr, batch, n, stream_stride, frame_stride, channels, window_ptr, twiddles_ptr, nperseg,
+                        hop, nfft, detrend, scale, n_each_ptr), ctypes.c_void_p(sxx_ptr), ctypes.c_void_p(stream)), name)
+
+
+def cross_spectra_device(ctx: 'Context', frames_ptr: int, batch: int, n: int, stream_stride: int, frame_stride: int,
+                         channels: int, window_ptr: int, twiddles_ptr: int, nperseg: int, hop: int, nfft: int, pxx_ptr: int,
+                         pyy_ptr: int, pxy_ptr: int, *, work_ptr: int, work_bytes: int, detrend: bool = True,
+                         scale: float = 1.0, n_each_ptr: int = 0, float64: bool = False, stream: int = 0):
+    """``vnd_cross_spectra_f32_dev`` (``_f64_dev`` with ``float64``): Welch's ``Pxx``, ``Pyy`` ``(batch, F)`` and ``Pxy``
+    ``(batch, F, 2)`` of a pool (one channel: ``Pxx`` alone), float64 sums in ascending segment order."""
+    name = 'vnd_cross_spectra_f64_dev' if float64 else 'vnd_cross_spectra_f32_dev'
+    _check(getattr(ctx._lib, name)(
+        *_spectrum_args(ctx, frames_ptr, batch, n, stream_stride, frame_stride, channels, window_ptr, twiddles_ptr, nperseg,
+                        hop, nfft, detrend, scale, n_each_ptr), ctypes.c_void_p(pxx_ptr), ctypes.c_void_p(pyy_ptr),
+        ctypes.c_void_p(pxy_ptr), ctypes.c_void_p(work_ptr), work_bytes, ctypes.c_void_p(stream)), name)
 
 
 def haas_scan_workspace_bytes(n: int, n_delays: int, max_delay: int) -> int:
