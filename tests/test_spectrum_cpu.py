@@ -9,18 +9,14 @@ import subprocess
 import numpy as np
 import pytest
 
+import spectrum_cases as C
+from spectrum_cases import GRID, hops as _hops        # (nfft, nperseg) of the device grid, and the hops of each
+
 REPO = pathlib.Path(__file__).resolve().parents[1]
 HEADER = REPO / 'include' / 'vnd_spectrum.h'
 NAMES = ['vnd_cross_spectra_f32_dev', 'vnd_cross_spectra_f64_dev', 'vnd_cross_spectra_work_bytes', 'vnd_spectrogram_f32_dev',
          'vnd_spectrogram_f64_dev', 'vnd_spectrum_run_length']
 INVALID, UNSUPPORTED = 1, 4
-# (nfft, nperseg) of the device grid, and the hops of each
-GRID = [(64, 64), (64, 2), (128, 128), (256, 256), (256, 200), (4096, 4096)]
-
-
-def _hops(nperseg):
-    return sorted({1, nperseg - nperseg // 8, nperseg})
-
 
 @pytest.fixture(scope='module')
 def lib():
@@ -76,6 +72,14 @@ def test_spectrum_covers_admits_and_refuses_the_list(sp):
     for nfft in (32, 96, 100, 255, 257, 4095, 8192, 256.0, None):
         assert covers(nfft=nfft, nperseg=20, noverlap=0) is (nfft is None and False), nfft
     assert covers(nfft=None)                                                                  # nfft defaults to nperseg
+    for nfft, nperseg in GRID:                                                                # every shape of the device grid
+        for hop in _hops(nperseg):
+            for dtype in (np.float32, np.float64):
+                for channels in (1, 2):
+                    assert covers(dtype=dtype, nfft=nfft, nperseg=nperseg, noverlap=nperseg - hop, channels=channels,
+                                  n_frames=nperseg + 3 * hop), (nfft, nperseg, hop)
+    assert len(GRID) == 15 and {n for n, _ in GRID} == {64, 128, 256, 512, 1024, 2048, 4096}
+    assert sum(p % 2 for _, p in GRID) == 6                                                   # the odd segments
     # 2 <= nperseg <= nfft, 0 <= noverlap < nperseg, n >= nperseg
     assert covers(nperseg=2, noverlap=1) and covers(nperseg=2, noverlap=0) and covers(nperseg=200)
     assert not covers(nperseg=1, noverlap=0) and not covers(nperseg=257) and not covers(nperseg=0)
@@ -206,6 +210,73 @@ def test_tables_and_scale(sp):
     assert sp.spectrum_scale(win, 48000.0, 'density') == 1.0 / (48000.0 * np.sum(win * win))
     assert sp.spectrum_scale(win, 48000.0, 'spectrum') == 1.0 / np.sum(win) ** 2
     assert sp.spectrum_scale(np.ones(64), 1.0, 'spectrum') == 2.0 ** -12
+
+
+# ---- the references the GPU tier rests on --------------------------------------------------------------------------------
+PARITY = [p for p in GRID if p != (64, 2)]     # two-sample segments: SciPy's own column error can be nearly zero
+
+
+@pytest.mark.parametrize('nfft,nperseg', PARITY, ids=['%d-%d' % p for p in PARITY])
+def test_scipys_float32_error_is_typical_in_every_column(nfft, nperseg):
+    """The GPU tier holds every device column to 4 x the error of SciPy's float32 call in the same column, so that error must
+    not be a lucky near-zero.  Noise: the smallest column error is at least a quarter of the shape's median (measured 0.68 to
+    0.95 of it).  0.9 + 1e-3 x noise: there the condition does NOT hold - a column's error is the rounding of its segment's
+    mean to float32, anywhere between nothing and half an ulp, and the smallest measured 0.015 to 0.063 of the median - and
+    what carries the rule instead is that the device's contract rounds the same mean: a model of the contract (float64 mean
+    rounded once, float32 subtract and multiply, exact transform) stays within 2 x SciPy's error in every column (measured
+    1.000 to 1.018), which leaves the other factor of two of the four to the transform's own rounding."""
+    from scipy.signal import get_window
+    hop = C.parity_case(nfft, nperseg)[0]
+    for name, x, ref, own in C.parity_reference(nfft, nperseg):
+        sci = C.column_errors(own, ref)
+        print(name, nfft, nperseg, 'smallest / median', sci.min() / np.median(sci))
+        assert sci.shape == (2, 2, 9) and (sci > 0).all()
+        if name == 'noise':
+            assert sci.min() >= 0.25 * np.median(sci), (sci.min(), np.median(sci))
+        else:
+            xs = np.ascontiguousarray(np.moveaxis(x, 2, 1))
+            model = C.column_errors(C.contract_model(xs, nfft, nperseg, hop, get_window(('tukey', 0.25), nperseg), 48000.0), ref)
+            print(name, nfft, nperseg, 'contract model / scipy float32', (model / sci).max())
+            assert (model <= 2 * sci).all(), float((model / sci).max())
+
+
+def test_the_half_ulp_budget_of_the_detrend():
+    """The detrend contract - float64 sum, divided and rounded once to the sample type - as a budget a column can be held
+    to without SciPy's float32 call: the change of the float64 column when its mean moves half a float32 ulp, plus the noise
+    cap.  The contract model stays under it at all nine new shapes (0.76 to 0.91 of it); a float32 running-sum mean does not
+    (6 to 75 times it), and SciPy's own pairwise float32 mean reaches 1.4 to 4 times it: the GPU test has teeth."""
+    from scipy.signal import get_window
+    over = 0
+    for nfft, nperseg in C.NEW_SHAPES:
+        hop = C.parity_case(nfft, nperseg)[0]
+        name, x, scipy_ref, own = C.parity_reference(nfft, nperseg)[1]
+        assert name == 'offset'
+        win = get_window(('tukey', 0.25), nperseg)
+        xs = np.ascontiguousarray(np.moveaxis(x, 2, 1))
+        ref, budget = C.detrend_budget(xs, nfft, nperseg, hop, win, 48000.0)
+        assert ref.shape == scipy_ref.shape and np.allclose(ref, scipy_ref, rtol=1e-9, atol=0)   # the reference is SciPy's
+        assert (budget > 8 * np.log2(nfft) * 2.0 ** -24).all()
+        model = C.column_errors(C.contract_model(xs, nfft, nperseg, hop, win, 48000.0), ref)
+        running = C.column_errors(C.contract_model(xs, nfft, nperseg, hop, win, 48000.0, mean='running'), ref)
+        print(nfft, nperseg, 'share of the budget: contract', (model / budget).max(), 'running sum', (running / budget).max(),
+              'scipy float32', (C.column_errors(own, ref) / budget).max())
+        assert (model <= budget).all(), (nfft, nperseg, float((model / budget).max()))
+        over += bool((running > budget).any())
+    assert over >= 1
+
+
+def test_replay_mean_is_the_documented_order():
+    cols = np.random.default_rng(9).uniform(0, 1, (3, 5, 11)).astype(np.float32)
+    one = C.replay_mean(cols, 32, np.float32)                      # one run: a plain ascending sum
+    want = np.zeros((3, 5))
+    for t in range(11):
+        want = want + cols[..., t].astype(np.float64)
+    assert _same_bits(one, (want / 11.0).astype(np.float32))
+    parts = [cols[..., t0:t0 + 4].astype(np.float64) for t0 in (0, 4, 8)]
+    want = ((parts[0][..., 0] + parts[0][..., 1] + parts[0][..., 2] + parts[0][..., 3])
+            + (parts[1][..., 0] + parts[1][..., 1] + parts[1][..., 2] + parts[1][..., 3])
+            + (parts[2][..., 0] + parts[2][..., 1] + parts[2][..., 2])) / 11.0
+    assert _same_bits(C.replay_mean(cols, 4, np.float64), want)
 
 
 def test_the_package_exports_it_and_the_module_stands_alone():
@@ -347,7 +418,7 @@ def test_work_bytes_and_run_length(lib):
                 for hop in _hops(nperseg):
                     assert lib.vnd_spectrum_run_length(nfft, nperseg, hop, f64, ch, ctypes.byref(run)) == 0
                     r = run.value
-                    assert 1 <= r <= 32
+                    assert 1 <= r <= 32 and r == C.spectrum_run(nfft, nperseg, hop, 8 if f64 else 4, ch), (nfft, nperseg, hop)
                     # the staged frames of a run fit 156 KiB beside the points (and, stereo, the left spectra of a pass)
                     points = 2 * 2368 * (2 if ch == 2 else 1)
                     assert (points + ch * ((r - 1) * hop + nperseg)) * (8 if f64 else 4) <= 156 * 1024
@@ -356,11 +427,21 @@ def test_work_bytes_and_run_length(lib):
                         assert lib.vnd_cross_spectra_work_bytes(3, n, ch, nperseg, hop, nfft, f64, ctypes.byref(got)) == 0
                         assert got.value == 3 * -(-segments // r) * (nfft // 2 + 1) * (4 if ch == 2 else 1) * 8
                     assert lib.vnd_spectrum_run_length(nfft, nperseg, hop, f64, 0, ctypes.byref(run)) == 0
+                    assert run.value == C.spectrum_run(nfft, nperseg, hop, 8 if f64 else 4, 0), (nfft, nperseg, hop)
                     tile = (nfft // 2 + 1) * (run.value | 1)
                     assert (2 * 2368 + (run.value - 1) * hop + nperseg + tile) * (8 if f64 else 4) <= 156 * 1024
     # the defaults own the longest run; the largest float64 segment still fits, alone
     assert spectral.run_length(256, 256, 224) == 32 and spectral.run_length(256, 256, 128, np.float32, 2) == 32
     assert spectral.run_length(4096, 4096, 4096, np.float64) == 2 and spectral.run_length(4096, 4096, 4096, np.float64, 2) == 1
+    # the shortest runs of a float64 stereo pool, which the GPU tier's Welch replay must meet: 8, 4, 2, 1 - whole passes
+    for (nfft, nperseg, hop), want in C.SHORTEST_RUNS.items():
+        assert spectral.run_length(nfft, nperseg, hop, np.float64, 2) == want == 2048 // (nfft // 2), (nfft, nperseg, hop)
+    assert all(shape in C.SHORTEST_RUNS for shape in C.WELCH_SHAPES[4:])
+    # the one float32 spectrogram run that is neither 32 nor a few: 30 segments, tile pitch 31
+    assert spectral.run_length(2048, 2048, 1) == 30
+    for nfft, nperseg, hop in C.ODD_ROOM:                          # the right channel's staged frames start at an odd offset
+        for dtype in (np.float32, np.float64):
+            assert ((spectral.run_length(nfft, nperseg, hop, dtype, 2) - 1) * hop + nperseg) % 2 == 1
     assert _native.cross_spectra_work_bytes(2, 1000, 2, 256, 128, 256) == 2 * 1 * 129 * 4 * 8
     for bad in ((0, 1000, 2, 256, 128, 256), (1, 0, 2, 256, 128, 256), (1, 1000, 3, 256, 128, 256), (1, 1000, 2, 1, 1, 256),
                 (1, 1000, 2, 256, 0, 256), (1, 255, 2, 256, 128, 256)):
