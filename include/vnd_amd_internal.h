@@ -113,6 +113,14 @@ vnd_status vnd_describe_correlogram_voice_stream_launch(int64_t slots, int32_t w
  * (the workgroups of the kernel that folds the partials and advances the positions, one per slot), threads, state_bytes. */
 vnd_status vnd_describe_polar_voice_stream_launch(int64_t slots, int64_t max_frames_per_call, int32_t sample_bytes,
                                                   char *text, int32_t len);
+/* Diagnosis: the launch every vnd_spectrum_voice_stream_*_dev call (include/vnd_spectrum_voice_stream.h) on a pool with these
+ * sizes takes - the pool's own scalar checks and planner, no context, no pointers, no device work - as one line of key=value
+ * fields: rows_per_call (RC = ceil(max_frames_per_call / hop)), run (R, the run length of the one-shot cross spectra), groups
+ * (G = ceil(RC / R) + 1 run workgroups per slot), nblocks (slots x groups), threads, advance_groups (the workgroups of the
+ * kernel that folds the runs, writes the means and advances the positions, one per slot), state_bytes.                   */
+vnd_status vnd_describe_spectrum_voice_stream_launch(int64_t slots, int32_t channels, int32_t nperseg, int32_t hop,
+                                                     int32_t nfft, int64_t max_frames_per_call, int32_t is_float64, char *text,
+                                                     int32_t len);
 /* Diagnosis (tests): vnd_decorrelate_fanout_f32_dev (in_channels == the table's channels: vnd_decorrelate_f32_dev), and which of the
  * stage's forms ran, in taken[4]: [0] 0 the table-order launch with the pointwise steps and the sums as passes of their own, 1 the
  * fast kernel with the pointwise steps (and, with VND_NORMALIZE_RMS, the sums) fused into its store phase, 2 the quad / octet kernel

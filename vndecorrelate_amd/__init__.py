@@ -47,11 +47,14 @@ from .analysis import (  # noqa: F401
     stereo_image_voice_pool,
 )
 from .spectral import (  # noqa: F401
+    SpectrumVoicePool,
     coherence_batched,
     csd_batched,
     set_spectrum_device,
     spectrogram_batched,
     spectrum_covers,
+    spectrum_voice_pool,
+    spectrum_voice_spans,
     welch_batched,
 )
 from .streaming import (  # noqa: F401

@@ -154,6 +154,9 @@ INTERNAL_SIGNATURES = {
                                                                     ctypes.c_int32]),
     'vnd_describe_polar_voice_stream_launch': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
                                                               ctypes.c_char_p, ctypes.c_int32]),
+    'vnd_describe_spectrum_voice_stream_launch': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                                 ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                                                 ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32]),
     'vnd_debug_decorrelate_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                      ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                                      ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
@@ -414,6 +417,24 @@ SPECTRUM_MIN_NFFT = 64            # VND_SPECTRUM_MIN_NFFT
 SPECTRUM_MAX_NFFT = 4096          # VND_SPECTRUM_MAX_NFFT
 SPECTRUM_RUN = 32                 # VND_SPECTRUM_RUN
 
+# include/vnd_spectrum_voice_stream.h: the short-time spectra of a voice pool - positions, Welch sums and the ring in the
+# device state, counts and flags per slot and call, float32 or float64 chunks
+_SPECTRUM_VOICE_STREAM_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                               ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                               ctypes.c_int32, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+SPECTRUM_VOICE_STREAM_SIGNATURES = {
+    'vnd_spectrum_voice_stream_state_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                             ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+                                                             ctypes.POINTER(ctypes.c_int64)]),
+    'vnd_spectrum_voice_stream_reset_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                           ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                           ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p]),
+    'vnd_spectrum_voice_stream_f32_dev': (ctypes.c_int, _SPECTRUM_VOICE_STREAM_ARGS),
+    'vnd_spectrum_voice_stream_f64_dev': (ctypes.c_int, _SPECTRUM_VOICE_STREAM_ARGS),
+}
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -471,7 +492,8 @@ def load_library():
                                   + list(CORRELOGRAM_VOICE_STREAM_SIGNATURES.items())
                                   + list(POLAR_VOICE_STREAM_SIGNATURES.items())
                                   + list(SCOPE_SIGNATURES.items()) + list(LEVEL_SIGNATURES.items())
-                                  + list(SPECTRUM_SIGNATURES.items())):
+                                  + list(SPECTRUM_SIGNATURES.items())
+                                  + list(SPECTRUM_VOICE_STREAM_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -1212,6 +1234,56 @@ def cross_spectra_device(ctx: 'Context', frames_ptr: int, batch: int, n: int, st
         *_spectrum_args(ctx, frames_ptr, batch, n, stream_stride, frame_stride, channels, window_ptr, twiddles_ptr, nperseg,
                         hop, nfft, detrend, scale, n_each_ptr), ctypes.c_void_p(pxx_ptr), ctypes.c_void_p(pyy_ptr),
         ctypes.c_void_p(pxy_ptr), ctypes.c_void_p(work_ptr), work_bytes, ctypes.c_void_p(stream)), name)
+
+
+def spectrum_voice_stream_state_bytes(slots: int, channels: int, nperseg: int, hop: int, nfft: int, max_frames_per_call: int,
+                                      float64: bool = False) -> int:
+    """``vnd_spectrum_voice_stream_state_bytes``: the positions, the Welch sums, the work of one call and the ring of a pool
+    of ``slots`` voices."""
+    need = ctypes.c_int64()
+    _check(load_library().vnd_spectrum_voice_stream_state_bytes(slots, channels, nperseg, hop, nfft, max_frames_per_call,
+                                                                int(bool(float64)), ctypes.byref(need)),
+           'vnd_spectrum_voice_stream_state_bytes')
+    return need.value
+
+
+def spectrum_voice_stream_reset_device(ctx: 'Context', state_ptr: int, state_bytes: int, slots: int, channels: int,
+                                       nperseg: int, hop: int, nfft: int, max_frames_per_call: int, float64: bool = False, *,
+                                       stream: int = 0):
+    """``vnd_spectrum_voice_stream_reset_dev``: every position of the pool to 0, enqueued on ``stream``; sums and ring are
+    left alone."""
+    _check(ctx._lib.vnd_spectrum_voice_stream_reset_dev(ctx.handle, ctypes.c_void_p(state_ptr), state_bytes, slots, channels,
+                                                        nperseg, hop, nfft, max_frames_per_call, int(bool(float64)),
+                                                        ctypes.c_void_p(stream)), 'vnd_spectrum_voice_stream_reset_dev')
+
+
+def spectrum_voice_stream_device(ctx: 'Context', state_ptr: int, state_bytes: int, max_frames_per_call: int, frames_ptr: int,
+                                 stream_stride: int, frame_stride: int, channels: int, counts_ptr: int, flags_ptr: int,
+                                 window_ptr: int, twiddles_ptr: int, nperseg: int, hop: int, nfft: int, cols_ptr: int,
+                                 out_counts_ptr: int, pxx_ptr: int, pyy_ptr: int, pxy_ptr: int, segments_ptr: int, slots: int,
+                                 *, detrend: bool = True, scale: float = 1.0, float64: bool = False, stream: int = 0):
+    """``vnd_spectrum_voice_stream_f32_dev`` (``_f64_dev`` with ``float64``): one call of a spectrum voice pool.  Sample t of
+    channel c of slot b at ``b * stream_stride + t * frame_stride + c`` elements of ``frames_ptr``, int32 ``(slots,)`` counts
+    and flags (``VOICE_START``, ``VOICE_END``), the ``(slots, rows_per_call, channels, F)`` columns (0: none), the int32
+    ``out_counts``, the means ``pxx``, ``pyy`` ``(slots, F)``, ``pxy`` ``(slots, F, 2)`` and the int64 ``segments`` (0 as a
+    group: none), all device memory, enqueued on ``stream``."""
+    name = 'vnd_spectrum_voice_stream_f64_dev' if float64 else 'vnd_spectrum_voice_stream_f32_dev'
+    p = ctypes.c_void_p
+    _check(getattr(ctx._lib, name)(
+        ctx.handle, p(state_ptr), state_bytes, max_frames_per_call, p(frames_ptr), stream_stride, frame_stride, channels,
+        p(counts_ptr), p(flags_ptr), p(window_ptr), p(twiddles_ptr), nperseg, hop, nfft, int(bool(detrend)), float(scale),
+        p(cols_ptr), p(out_counts_ptr), p(pxx_ptr), p(pyy_ptr), p(pxy_ptr), p(segments_ptr), slots, p(stream)), name)
+
+
+def describe_spectrum_voice_stream(slots: int, channels: int, nperseg: int, hop: int, nfft: int, max_frames_per_call: int,
+                                   float64: bool = False) -> str:
+    """The fixed launch of a spectrum voice pool (``vnd_describe_spectrum_voice_stream_launch``): ``rows_per_call=``,
+    ``run=``, ``groups=``, ``nblocks=``, ``threads=``, ``advance_groups=`` and ``state_bytes=``."""
+    buf = ctypes.create_string_buffer(512)
+    _check(load_library().vnd_describe_spectrum_voice_stream_launch(slots, channels, nperseg, hop, nfft, max_frames_per_call,
+                                                                    int(bool(float64)), buf, 512),
+           'vnd_describe_spectrum_voice_stream_launch')
+    return buf.value.decode()
 
 
 def haas_scan_workspace_bytes(n: int, n_delays: int, max_delay: int) -> int:

@@ -331,4 +331,19 @@ vnd_status vnd_describe_polar_voice_stream_launch(int64_t slots, int64_t max_fra
     return VND_OK;
 }
 
+// The fixed launch of every vnd_spectrum_voice_stream_*_dev call on a pool with these sizes: the pool's own scalar checks and
+// sv_plan, the launch's own.  No pointers, no device work.
+vnd_status vnd_describe_spectrum_voice_stream_launch(int64_t slots, int32_t channels, int32_t nperseg, int32_t hop, int32_t nfft,
+                                                     int64_t max_frames_per_call, int32_t is_float64, char *text, int32_t len)
+{
+    if (!text || len <= 0) return fail(VND_ERR_INVALID, "null text buffer");
+    SvPlan p{};
+    vnd_status st = sv_plan(slots, channels, nperseg, hop, nfft, max_frames_per_call, is_float64 ? 8 : 4, &p);
+    if (st != VND_OK) return st;
+    snprintf(text, (size_t)len, "spectrum_voice_stream rows_per_call=%lld run=%d groups=%lld nblocks=%lld threads=%d advance_groups=%lld state_bytes=%lld",
+             (long long)p.rc, p.run, (long long)p.groups, (long long)p.workgroups, kSpectrumThreads, (long long)p.finish_groups,
+             (long long)p.need);
+    return VND_OK;
+}
+
 }  // extern "C"

@@ -8,7 +8,10 @@ memory, by a batched real-input FFT in LDS, with SciPy's defaults and meanings:
 * :func:`spectrogram_batched` - ``scipy.signal.spectrogram`` (mode ``'psd'``, one-sided) of every signal and channel;
 * :func:`welch_batched`, :func:`csd_batched`, :func:`coherence_batched` - ``scipy.signal.welch``, ``csd`` and ``coherence``
   with ``average='mean'``; the sums over segments are float64, in ascending segment order, on every route of the device;
-* :func:`set_spectrum_device` and the pure routing rule :func:`spectrum_covers`.
+* :func:`set_spectrum_device` and the pure routing rule :func:`spectrum_covers`;
+* :func:`spectrum_voice_pool` - the same columns and means for a pool of voices that start, end and push blocks of their own
+  sizes (``include/vnd_spectrum_voice_stream.h``): a :class:`SpectrumVoicePool`, which meters the coherence of a
+  ``decorrelate_voice_pool`` on the device; :func:`spectrum_voice_spans` is the device's mirror.
 
 A column of a spectrogram is a function of its own segment of its own channel only: channels and segments are never
 packed into one transform, so a quiet side channel keeps its own rounding floor.  Without a device, or for
@@ -22,6 +25,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native
+from .streaming import _SlotPool, _check_counts, _check_slots, _slot_ints, _voice_head
 
 MIN_NFFT = _native.SPECTRUM_MIN_NFFT
 MAX_NFFT = _native.SPECTRUM_MAX_NFFT
@@ -508,6 +512,241 @@ def coherence_batched(pool, fs=1.0, window='hann', nperseg=256, noverlap=None, n
     return f, cxy
 
 
+# ----------------------------------------------------------------------------
+# The spectra of a voice pool   (include/vnd_spectrum_voice_stream.h)
+# ----------------------------------------------------------------------------
+def spectrum_voice_spans(positions, counts, flags, nperseg: int, hop: int, max_frames_per_call: Optional[int] = None):
+    """``(out_counts, segments, new_positions)`` of one call of a spectrum voice pool
+    (``include/vnd_spectrum_voice_stream.h``), per slot, from the positions before the call, the frames pushed and the
+    ``VOICE_START`` / ``VOICE_END`` flags alone - what the device computes from its own state::
+
+        p = START ? 0 : position        sc(q) = (q - W) // H + 1 if q >= W else 0
+        out_count = sc(p + n) - sc(p)   segments = sc(p + n)        new position = END ? 0 : p + n
+
+    ``segments`` is what the call leaves in ``segments[b]``, the count the means are taken over; it is -1 where the call
+    leaves the slot's means alone: a bad slot, and an idle one (no frame and no flag).  A count below 0 (or above
+    ``max_frames_per_call``, when given), or without START a position outside ``[0, 2^60]``, answers -1 and leaves the
+    position as it was."""
+    pos, n, start, end, p, bad = _voice_head(positions, counts, flags, max_frames_per_call)
+    W, H = int(nperseg), int(hop)
+    if W < 1 or H < 1:
+        raise ValueError(f'nperseg and hop must be >= 1, got {nperseg} and {hop}')
+    p, n = np.where(bad, 0, p), np.where(bad, 0, n)          # (no arithmetic on a bad value)
+
+    def complete(q):
+        return np.where(q >= W, (q - W) // H + 1, 0)
+    idle = ~bad & (n == 0) & ~start & ~end
+    out = np.where(bad, -1, complete(p + n) - complete(p)).astype(np.int64)
+    segments = np.where(bad | idle, -1, complete(p + n)).astype(np.int64)
+    new = np.where(bad, pos, np.where(end, 0, p + n)).astype(np.int64)
+    return out, segments, new
+
+
+class SpectrumVoicePool(_SlotPool):
+    """``scipy.signal.spectrogram`` columns and the Welch means ``Pxx``, ``Pyy``, ``Pxy`` of ``slots`` voices, each with a
+    life of its own (:func:`spectrum_voice_pool`, ``vnd_spectrum_voice_stream_*_dev``): voices start and end on any call and
+    push blocks of any size up to ``max_frames_per_call`` or none.  The position lives in the device state, one per slot,
+    so a call is a pure function of device memory.  A call returns, per slot, the ``'psd'`` columns of the segments that
+    became complete - at most ``rows_per_call``, time-major ``(rows, channels, F)`` - and leaves in ``pxx``, ``pyy``, ``pxy``
+    and ``segments``, tensors the pool owns at fixed addresses, the Welch means over every segment of the voice so far.
+    For every voice the concatenation of its columns equals :func:`spectrogram_batched` of its whole signal and the means
+    equal :func:`welch_batched` / :func:`csd_batched` of the frames pushed so far, bit for bit.  Segments that never
+    complete are dropped: an end has no tail.
+
+    Two forms; a pool is used through one of them (mixing them raises ``RuntimeError`` until ``reset()``):
+
+    * ``process({slot: block}, start=[slot, ...], end=[slot, ...], discard=False)`` - NumPy blocks ``(n, channels)`` of
+      the pool's dtype in, ``{slot: (T_new, channels, F)}`` out for every slot that got a block or ended; :meth:`welch`
+      reads a slot's means.  One upload and one download (``transfers`` counts those of the last call); every refusal
+      comes before any device call.
+    * ``process_dev(y, counts, flags, *, out=None)`` - ``y`` ``(slots, max_frames_per_call, channels)`` of the pool's
+      dtype and int32 ``(slots,)`` ``counts`` and ``flags`` on the device; returns ``(columns, out_counts)``.  It only
+      enqueues on the current stream and can be captured with ``torch.cuda.graph`` after a ``reset()``.  To meter a
+      decorrelating pool, build the meter with ``max_frames_per_call=pool.row_frames`` and the pool's dtype and hand it
+      that pool's ``y`` and ``out_counts`` and the caller's ``flags``: a -1 of the pool is a bad count here and answers -1.
+    """
+
+    def __init__(self, slots: int, max_frames_per_call: int, *, fs=1.0, window='hann', nperseg=256, noverlap=None, nfft=None,
+                 detrend='constant', scaling='density', channels: int = 2, dtype='float32', columns: bool = True):
+        _check_counts(slots=slots, max_frames_per_call=max_frames_per_call)
+        _check_slots(slots)
+        if max_frames_per_call > _MAX_FRAMES:
+            raise ValueError(f'max_frames_per_call {max_frames_per_call} above 2**31 - 1: counts are int32')
+        try:
+            parsed = None if dtype is None else np.dtype(dtype)
+        except TypeError:
+            parsed = None
+        if parsed is None or parsed.name not in ('float32', 'float64'):
+            raise ValueError(f"dtype must be 'float32' or 'float64', got {dtype!r}")
+        if isinstance(channels, (bool, np.bool_)) or channels not in (1, 2):
+            raise ValueError(f'channels must be 1 or 2, got {channels!r}')
+        if not isinstance(columns, (bool, np.bool_)):
+            raise ValueError(f'columns must be True or False, got {columns!r}')
+        nperseg = _segment_size(window, nperseg) if nperseg is None or _is_int(nperseg) else nperseg
+        if nfft is None:
+            nfft = nperseg
+        if noverlap is None and _is_int(nperseg):
+            noverlap = nperseg // 2
+        if not spectrum_covers(parsed, int(slots), nperseg, int(channels), nperseg, noverlap, nfft, detrend, scaling, window):
+            raise ValueError(f'nperseg {nperseg!r}, noverlap {noverlap!r}, nfft {nfft!r}, detrend {detrend!r}, scaling '
+                             f'{scaling!r} and this window have no device form (spectrum_covers is False) and the pool has '
+                             f'no SciPy one: use spectrogram_batched / coherence_batched')
+        self.dtype = parsed
+        self.slots, self.max_frames_per_call, self.in_channels = int(slots), int(max_frames_per_call), int(channels)
+        self.fs, self.window, self.detrend, self.scaling = fs, window, detrend, scaling
+        self.nperseg, self.noverlap, self.nfft = int(nperseg), int(noverlap), int(nfft)
+        self.hop = self.nperseg - self.noverlap
+        self.columns = bool(columns)
+        self._win64 = _window_values(window, self.nperseg)
+        self.scale = spectrum_scale(self._win64, fs, scaling)
+        if not (np.isfinite(self.scale) and self.scale > 0 and np.isfinite(parsed.type(self.scale)) and parsed.type(self.scale) > 0):
+            raise ValueError(f'the scale {self.scale!r} of this window, fs and scaling is not positive and finite in {parsed.name}')
+        # the fixed grid of the pool (include/vnd_spectrum_voice_stream.h): G = ceil(RC / R) + 1 run workgroups per slot, one
+        # grid dimension; 2^23 workgroups a launch; cols of at most 2^40 values
+        self.run = run_length(self.nfft, self.nperseg, self.hop, parsed, self.in_channels)
+        groups = -(-self.rows_per_call // self.run) + 1
+        if groups > 65535 or self.slots * groups > _MAX_GROUPS \
+                or self.slots * self.rows_per_call * self.in_channels * self.bins > 1 << 40:
+            raise ValueError(f'{self.slots} slots of {self.rows_per_call} segments of {self.bins} bins per call are more than '
+                             f'one launch takes: raise the hop or lower max_frames_per_call')
+        self.transfers = {'to_device': 0, 'to_host': 0}
+        self._state = None                    # (torch uint8 tensor, bytes)
+        self.pxx = self.pyy = self.pxy = self.segments = None
+        S, C = self.slots, self.in_channels
+        self._block_dtype = self._out_dtype = parsed.type
+        self._inputs = (('y', (S, self.max_frames_per_call, C), parsed.name, None),) + _slot_ints(S, 'counts', 'flags')
+        self._outputs = (('columns', (S, self.rows_per_call if self.columns else 0, C, self.bins), parsed.name, 'empty'),
+                         ('out_counts', (S,), 'int32', 'empty'))
+        self._mirror()
+
+    @property
+    def rows_per_call(self) -> int:
+        """RC: the most columns a call returns per slot, ``ceil(max_frames_per_call / hop)``."""
+        return -(-self.max_frames_per_call // self.hop)
+
+    @property
+    def bins(self) -> int:
+        return self.nfft // 2 + 1
+
+    @property
+    def f(self) -> np.ndarray:
+        """SciPy's one-sided bin frequencies."""
+        return bin_frequencies(self.nfft, self.fs)
+
+    @property
+    def _out_width(self) -> int:
+        return self.bins
+
+    def process(self, blocks=None, *, start=(), end=(), discard: bool = False):
+        """One call of the dict form.  ``blocks``: ``{slot: (n, channels) array of the pool's dtype}`` (``(n,)`` as well for
+        one channel), ``0 <= n <= max_frames_per_call``; ``start``: the slots whose voice begins with this call; ``end``:
+        the slots whose voice ends with it.  Returns ``{slot: (T_new, channels, F)}`` for every slot that got a block or
+        ended (without ``columns``: ``T_new`` is 0).  Raises before any device call, as the other voice pools do."""
+        self._require_form('dict')
+        out = _SlotPool.process(self, blocks, start=self._start_slots(start), end=end, discard=discard)
+        none = np.zeros((0, self.in_channels, self.bins), self.dtype)
+        return {slot: rows if rows.ndim == 3 else none.copy() for slot, rows in out.items()}
+
+    def process_dev(self, y, counts, flags, *, out=None):
+        """One call on device tensors, enqueued on the current stream: ``y`` ``(slots, M, channels)`` of the pool's dtype,
+        ``counts`` / ``flags`` int32 ``(slots,)``.  Returns ``(columns, out_counts)``: ``(slots, rows_per_call, channels,
+        F)`` of the pool's dtype - the first ``out_counts[b]`` rows of row-block b are written, nothing at or past them;
+        without ``columns`` it has no rows - and int32 ``(slots,)``; ``out=(columns, out_counts)`` takes the caller's.  The
+        means are in ``pxx``, ``pyy``, ``pxy`` and ``segments`` when the call has run.  No check reads device memory; bad
+        per-slot values answer -1 (``include/vnd_spectrum_voice_stream.h``)."""
+        return self._process_dev((y, counts, flags), out)
+
+    def coherence(self):
+        """SciPy's ``abs(Pxy)**2 / Pxx / Pyy`` of every slot, ``(slots, F)``, in torch operations on the means: enqueued on
+        the current stream, nothing synchronised.  A slot with no whole segment is 0 / 0: NaN."""
+        if self.in_channels != 2:
+            raise ValueError('coherence needs two channels')
+        if self.pxx is None:
+            raise RuntimeError('the pool has no means yet: call reset() or process first')
+        torch = _torch()
+        return torch.abs(torch.view_as_complex(self.pxy)) ** 2 / self.pxx / self.pyy
+
+    def welch(self, slot: int):
+        """``(segments, Pxx, Pyy, Pxy)`` of one slot as NumPy values, read from the device (it waits for the stream):
+        the segment count the means are taken over, ``(F,)`` arrays of the pool's dtype and the complex ``Pxy``; ``Pyy``
+        and ``Pxy`` are None with one channel."""
+        slot = self._slot(slot, 'welch')
+        if self.pxx is None:
+            raise RuntimeError('the pool has no means yet: call reset() or process first')
+        torch = _torch()
+        segments = int(self.segments[slot].cpu())
+        pxx = self.pxx[slot].cpu().numpy()
+        if self.in_channels == 1:
+            return segments, pxx, None, None
+        return segments, pxx, self.pyy[slot].cpu().numpy(), torch.view_as_complex(self.pxy[slot]).cpu().numpy()
+
+    # ---- what _SlotPool asks for ---------------------------------------------------------------
+    def _spans(self, counts, flags, tables):
+        out, _, new = spectrum_voice_spans(self.positions, counts, flags, self.nperseg, self.hop, self.max_frames_per_call)
+        return out, new
+
+    def _per_slot(self, tables):
+        return ()
+
+    def _bank_len(self) -> int:
+        return 1                                  # a voice starts with nothing of its own: the pool has one setting
+
+    def _slot_value(self, index: int):
+        return 0
+
+    # ---- the device -------------------------------------------------------------------------
+    def _allocate(self, torch, ctx):
+        """The means at their fixed addresses and the tables of the transform, then the state."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('the state of a voice pool is allocated and zeroed on first use: call reset() before the capture')
+        device = torch.device('cuda', ctx.device)
+        tdt = getattr(torch, self.dtype.name)
+        S, F = self.slots, self.bins
+        self._win, self._tw = _device_tables(torch, device, self._win64, self.nfft, self.dtype)
+        self.pxx = torch.zeros((S, F), dtype=tdt, device=device)
+        self.pyy = torch.zeros((S, F), dtype=tdt, device=device) if self.in_channels == 2 else None
+        self.pxy = torch.zeros((S, F, 2), dtype=tdt, device=device) if self.in_channels == 2 else None
+        self.segments = torch.zeros((S,), dtype=torch.int64, device=device)
+        _SlotPool._allocate(self, torch, ctx)
+
+    def _state_bytes(self, ctx) -> int:
+        return _native.spectrum_voice_stream_state_bytes(self.slots, self.in_channels, self.nperseg, self.hop, self.nfft,
+                                                         self.max_frames_per_call, self.dtype == np.float64)
+
+    def _reset_entry(self, ctx, state_ptr, state_bytes, stream):
+        _native.spectrum_voice_stream_reset_device(ctx, state_ptr, state_bytes, self.slots, self.in_channels, self.nperseg,
+                                                   self.hop, self.nfft, self.max_frames_per_call, self.dtype == np.float64,
+                                                   stream=stream)
+
+    def _call_host(self, x, counts, flags):
+        """One upload (the blocks and the two int32 arrays in one buffer), the call, one download (columns, out_counts)."""
+        return self._call_host_packed(x, (counts, flags))
+
+    def _launch(self, ctx, state_ptr, state_bytes, inputs, cols, out_counts, stream):
+        y, counts, flags = inputs
+        C, M = self.in_channels, self.max_frames_per_call
+        stereo = C == 2
+        _native.spectrum_voice_stream_device(
+            ctx, state_ptr, state_bytes, M, y.data_ptr(), C * M, C, C, counts.data_ptr(), flags.data_ptr(),
+            self._win.data_ptr(), self._tw.data_ptr(), self.nperseg, self.hop, self.nfft,
+            cols.data_ptr() if self.columns else 0, out_counts.data_ptr(), self.pxx.data_ptr(),
+            self.pyy.data_ptr() if stereo else 0, self.pxy.data_ptr() if stereo else 0, self.segments.data_ptr(), self.slots,
+            detrend=self.detrend is not False, scale=self.scale, float64=self.dtype == np.float64, stream=stream)
+
+
+def spectrum_voice_pool(slots: int, max_frames_per_call: int, fs=1.0, window='hann', nperseg=256, noverlap=None, nfft=None,
+                        detrend='constant', scaling='density', channels: int = 2, dtype='float32',
+                        columns: bool = True) -> SpectrumVoicePool:
+    """A :class:`SpectrumVoicePool`: ``scipy.signal.spectrogram`` columns and ``welch`` / ``csd`` / ``coherence`` means with
+    these arguments - ``welch``'s defaults, ``noverlap = nperseg // 2`` - for ``slots`` voices that start, end and push
+    blocks on their own, the positions in device memory.  What :func:`spectrum_covers` rejects, what one launch does not
+    take, pools above 65535 slots and a ``dtype`` other than ``'float32'`` / ``'float64'`` raise ``ValueError`` here: a
+    stream has no SciPy loop to fall back to.  ``columns=False`` keeps the means only.  ``set_spectrum_device`` is not
+    consulted."""
+    return SpectrumVoicePool(slots, max_frames_per_call, fs=fs, window=window, nperseg=nperseg, noverlap=noverlap, nfft=nfft,
+                             detrend=detrend, scaling=scaling, channels=channels, dtype=dtype, columns=columns)
+
+
 __all__ = ['spectrogram_batched', 'welch_batched', 'csd_batched', 'coherence_batched', 'set_spectrum_device',
            'spectrum_covers', 'twiddle_table', 'spectrum_scale', 'segment_times', 'bin_frequencies', 'run_length', 'MIN_NFFT',
-           'MAX_NFFT', 'RUN']
+           'MAX_NFFT', 'RUN', 'spectrum_voice_pool', 'SpectrumVoicePool', 'spectrum_voice_spans']
