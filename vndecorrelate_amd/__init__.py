@@ -32,16 +32,21 @@ from .decorrelation import (  # noqa: F401
 from .analysis import (  # noqa: F401
     CorrelogramVoicePool,
     PolarVoicePool,
+    ScopeVoicePool,
     correlogram_voice_spans,
     cross_correlogram_batched,
     cross_correlogram_voice_pool,
     lissajous_histogram_batched,
+    lissajous_histogram_voice_pool,
     polar_coordinates_batched,
     polar_histogram_batched,
+    polar_histogram_voice_pool,
     polar_level_batched,
     polar_moments_ordered,
     polar_voice_spans,
     scope_covers,
+    scope_voice_spans,
+    scope_voice_window,
     set_correlogram_device,
     set_scope_device,
     stereo_image_voice_pool,

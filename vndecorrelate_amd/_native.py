@@ -435,6 +435,26 @@ SPECTRUM_VOICE_STREAM_SIGNATURES = {
     'vnd_spectrum_voice_stream_f64_dev': (ctypes.c_int, _SPECTRUM_VOICE_STREAM_ARGS),
 }
 
+# include/vnd_scope_voice_stream.h: the vectorscope of a voice pool - positions and the ring of cells in the device state, the
+# count grids in caller-owned memory that belongs to the pool between calls, whole-voice or over a sliding window
+_SCOPE_VOICE_HEAD_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                          ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+_SCOPE_VOICE_TAIL_ARGS = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                          ctypes.c_int64, ctypes.c_void_p]
+_POLAR_HIST_VOICE_ARGS = _SCOPE_VOICE_HEAD_ARGS + [ctypes.c_int32, ctypes.c_int32, ctypes.c_double] + _SCOPE_VOICE_TAIL_ARGS
+_LISSAJOUS_HIST_VOICE_ARGS = _SCOPE_VOICE_HEAD_ARGS + _SCOPE_VOICE_TAIL_ARGS
+SCOPE_VOICE_STREAM_SIGNATURES = {
+    'vnd_scope_voice_stream_state_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                          ctypes.POINTER(ctypes.c_int64)]),
+    'vnd_scope_voice_stream_reset_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                        ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
+    'vnd_polar_hist_voice_stream_f32_dev': (ctypes.c_int, _POLAR_HIST_VOICE_ARGS),
+    'vnd_polar_hist_voice_stream_f64_dev': (ctypes.c_int, _POLAR_HIST_VOICE_ARGS),
+    'vnd_lissajous_hist_voice_stream_f32_dev': (ctypes.c_int, _LISSAJOUS_HIST_VOICE_ARGS),
+    'vnd_lissajous_hist_voice_stream_f64_dev': (ctypes.c_int, _LISSAJOUS_HIST_VOICE_ARGS),
+}
+SCOPE_VOICE_SPAN_FRAMES = 1024    # kScopeVoiceSpan: frames of one slot per workgroup of the bin kernel
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -493,7 +513,8 @@ def load_library():
                                   + list(POLAR_VOICE_STREAM_SIGNATURES.items())
                                   + list(SCOPE_SIGNATURES.items()) + list(LEVEL_SIGNATURES.items())
                                   + list(SPECTRUM_SIGNATURES.items())
-                                  + list(SPECTRUM_VOICE_STREAM_SIGNATURES.items())):
+                                  + list(SPECTRUM_VOICE_STREAM_SIGNATURES.items())
+                                  + list(SCOPE_VOICE_STREAM_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -1159,6 +1180,43 @@ def lissajous_hist_device(ctx: 'Context', l_ptr: int, r_ptr: int, batch: int, n:
         ctx.handle, ctypes.c_void_p(l_ptr), ctypes.c_void_p(r_ptr), batch, n, stream_stride, frame_stride, frame_step,
         ctypes.c_void_p(x_edges_ptr), x_bins, ctypes.c_void_p(y_edges_ptr), y_bins, ctypes.c_void_p(n_each_ptr),
         ctypes.c_void_p(counts_ptr), int(bool(accumulate)), ctypes.c_void_p(stream)), name)
+
+
+def scope_voice_stream_state_bytes(slots: int, max_frames_per_call: int, window_frames: int = 0) -> int:
+    """``vnd_scope_voice_stream_state_bytes``: the positions and, with ``window_frames`` > 0, the ring of cells of a pool of
+    ``slots`` voices."""
+    need = ctypes.c_int64()
+    _check(load_library().vnd_scope_voice_stream_state_bytes(slots, max_frames_per_call, window_frames, ctypes.byref(need)),
+           'vnd_scope_voice_stream_state_bytes')
+    return need.value
+
+
+def scope_voice_stream_reset_device(ctx: 'Context', state_ptr: int, state_bytes: int, slots: int, max_frames_per_call: int,
+                                    window_frames: int = 0, *, stream: int = 0):
+    """``vnd_scope_voice_stream_reset_dev``: every position of the pool to 0, enqueued on ``stream``; the ring and the
+    grid are left alone."""
+    _check(ctx._lib.vnd_scope_voice_stream_reset_dev(ctx.handle, ctypes.c_void_p(state_ptr), state_bytes, slots,
+                                                     max_frames_per_call, window_frames, ctypes.c_void_p(stream)),
+           'vnd_scope_voice_stream_reset_dev')
+
+
+def scope_voice_stream_device(ctx: 'Context', state_ptr: int, state_bytes: int, max_frames_per_call: int, window_frames: int,
+                              l_ptr: int, r_ptr: int, stream_stride: int, frame_stride: int, counts_ptr: int, flags_ptr: int,
+                              edges0_ptr: int, bins0: int, edges1_ptr: int, bins1: int, grid_ptr: int, valid_ptr: int,
+                              slots: int, *, polar: bool = True, ms_mode: bool = True, semicircular: bool = True,
+                              radius_scale: float = 0.0, float64: bool = False, stream: int = 0):
+    """``vnd_polar_hist_voice_stream_f32_dev`` (``polar=False``: ``vnd_lissajous_hist_voice_stream_f32_dev``; ``_f64_dev``
+    with ``float64``): one call of a count-grid voice pool.  Frame t of slot b at ``b * stream_stride + t * frame_stride``
+    elements of ``l_ptr`` / ``r_ptr``, int32 ``(slots,)`` counts and flags (``VOICE_START``, ``VOICE_END``), float64 device
+    edges, the pool's uint32 ``(slots, bins0, bins1)`` grid and the int32 ``valid``, all device memory, enqueued on
+    ``stream``."""
+    name = f"vnd_{'polar' if polar else 'lissajous'}_hist_voice_stream_{'f64' if float64 else 'f32'}_dev"
+    p = ctypes.c_void_p
+    head = (ctx.handle, p(state_ptr), state_bytes, max_frames_per_call, window_frames, p(l_ptr), p(r_ptr), stream_stride,
+            frame_stride, p(counts_ptr), p(flags_ptr))
+    mode = (int(bool(ms_mode)), int(bool(semicircular)), float(radius_scale)) if polar else ()
+    _check(getattr(ctx._lib, name)(*head, *mode, p(edges0_ptr), bins0, p(edges1_ptr), bins1, p(grid_ptr), p(valid_ptr), slots,
+                                   p(stream)), name)
 
 
 def polar_level_work_bytes(batch: int, n: int, num_bins: int, num_percentiles: int, float64: bool = False) -> int:

@@ -13,6 +13,9 @@ whole pool, so a pool of voices that lives in device memory never comes down to 
   (``vnd_lissajous_hist_*_dev``);
 * :func:`polar_level_batched` - the raw envelope of ``plot_polar_level``: ``_build_pseudo_hull``'s per-slice percentiles of
   the radii, an exact radix select (``vnd_polar_level_*_dev``), with :func:`percentile_rule`, NumPy's rule in one place;
+* :func:`polar_histogram_voice_pool` / :func:`lissajous_histogram_voice_pool` - the same grids for the voices of a voice
+  pool, block by block, of each voice's whole signal or of its last ``window_frames`` frames (:class:`ScopeVoicePool`,
+  ``include/vnd_scope_voice_stream.h``, DESIGN.md §3.25);
 * :func:`set_scope_device` and the pure routing rule :func:`scope_covers`, through ``analysis.device_route``.
 
 Counts are integers: a grid equals ``np.histogram2d`` of the same coordinates cell for cell, whatever the route
@@ -29,6 +32,8 @@ from typing import Optional
 import numpy as np
 
 from . import _native
+from .streaming import (VOICE_END, _check_counts, _check_device_tensors, _check_slots, _slot_ints, _SlotPool,
+                        _voice_head)
 from .utils.dsp import LayoutMode, polar_coordinates
 
 MAX_BINS = _native.SCOPE_MAX_BINS
@@ -563,7 +568,266 @@ def polar_level_batched(pool, num_bins: int = 360, percentiles=(95.0, 50.0), *, 
     return levels, bin_counts, edges, centers
 
 
+# ---- the vectorscope of a voice pool (include/vnd_scope_voice_stream.h) -----------------------------------------------
+_INT32_MAX = 2 ** 31 - 1
+VOICE_SPAN_FRAMES = _native.SCOPE_VOICE_SPAN_FRAMES   # frames of one slot per workgroup of the pool's bin kernel
+_VOICE_CLEAR_BYTES = 16384                            # bytes of one grid row per workgroup of its clear kernel
+
+
+def scope_voice_spans(positions, counts, flags, max_frames_per_call: Optional[int] = None):
+    """``(valid, new_positions)`` of one call of a count-grid voice pool (``include/vnd_scope_voice_stream.h``), per slot,
+    from the positions before the call, the frames pushed and the ``VOICE_START`` / ``VOICE_END`` flags alone - what the
+    device computes from its own state::
+
+        p = START ? 0 : position      valid = 1, or 0 for n = 0 without a flag      new position = END ? 0 : p + n
+
+    A slot that answers 1 from ``p = 0`` has its grid row cleared first.  A count below 0 (or above
+    ``max_frames_per_call``, when given), or without START a position outside ``[0, 2^60]``, answers -1 and leaves the
+    position as it was."""
+    pos, n, start, end, p, bad = _voice_head(positions, counts, flags, max_frames_per_call)
+    idle = ~bad & (n == 0) & ~start & ~end
+    p, n = np.where(bad, 0, p), np.where(bad, 0, n)          # (no arithmetic on a bad value)
+    valid = np.where(bad, -1, np.where(idle, 0, 1)).astype(np.int64)
+    new = np.where(bad | idle, pos, np.where(end, 0, p + n)).astype(np.int64)
+    return valid, new
+
+
+def scope_voice_window(position_after: int, window_frames: Optional[int] = None):
+    """``(lo, hi)``: the frames of a voice its grid row counts once the voice has pushed ``position_after`` frames (``p + n``
+    of the call, before an END sets the position back to 0) - the last ``window_frames`` of them, or all of them for the
+    whole-voice form (``None`` or 0)."""
+    q = int(position_after)
+    if q < 0:
+        raise ValueError(f'position_after must be >= 0, not {position_after!r}')
+    w = 0 if window_frames is None else int(window_frames)
+    if w < 0:
+        raise ValueError(f'window_frames must be >= 0 or None, not {window_frames!r}')
+    return (max(0, q - w) if w else 0), q
+
+
+class ScopeVoicePool(_SlotPool):
+    """The vectorscope of ``slots`` voices, each with a life of its own (:func:`polar_histogram_voice_pool`,
+    :func:`lissajous_histogram_voice_pool`; ``vnd_polar_hist_voice_stream_*_dev``, ``vnd_lissajous_hist_voice_stream_*_dev``):
+    voices start and end on any call and push blocks of any size up to ``max_frames_per_call`` or none.  The position lives
+    in the device state, one per slot, so a call is a pure function of device memory.  After every call row b of
+    :attr:`grid` is the count grid of voice b - of its whole signal so far, or with ``window_frames=W`` of its last ``W``
+    frames - equal to :func:`polar_histogram_batched` (``radius_scale=...``) / :func:`lissajous_histogram_batched` of those
+    frames cell for cell, whatever the schedule: counts are integers, and the frame that leaves the window takes its count
+    out of the cell it was put in.  A row is cleared when the slot's next voice begins; an END leaves it readable.
+
+    :attr:`grid` is one int32 ``(slots, bins0, bins1)`` device tensor holding the uint32 counts, at a fixed address,
+    allocated as zeros with the state: it belongs to the pool - read it, do not write it.
+
+    Two forms; a pool is used through one of them (mixing them raises ``RuntimeError`` until ``reset()``):
+
+    * ``process({slot: block}, start=[slot, ...], end=[slot, ...], discard=False, grids=True)`` - ``(n, 2)`` NumPy blocks of
+      the pool's ``dtype`` in, ``{slot: float64 (bins0, bins1)}`` out for every slot that got a block, started or ended -
+      the dtype :func:`polar_histogram_batched` gives NumPy callers.  One upload and one download (``transfers`` counts
+      those of the last call); ``grids=False`` downloads ``valid`` only and answers ``{slot: None}``.  Every refusal comes
+      before any device call.
+    * ``process_dev(y, counts, flags)`` - ``y`` ``(slots, max_frames_per_call, 2)`` of the pool's ``dtype`` and int32
+      ``(slots,)`` ``counts`` and ``flags`` on the device; returns ``(grid, valid)``.  It only enqueues on the current
+      stream and can be captured with ``torch.cuda.graph`` after a ``reset()``.  To meter a decorrelating pool, build the
+      meter with ``max_frames_per_call=pool.row_frames`` (and ``dtype='float64'`` for a Haas or chain pool) and hand it that
+      pool's ``y`` and ``out_counts`` and the caller's ``flags``: a -1 of the pool is a bad count here and answers -1."""
+
+    in_channels = 2
+    _out_dtype = np.float64
+
+    def __init__(self, slots: int, *, max_frames_per_call: int, edges, polar: bool, window_frames: Optional[int] = None,
+                 dtype='float32', radius_scale: Optional[float] = None, ms: bool = True, semicircular: bool = True):
+        from .analysis import _sample_dtype
+        _check_counts(slots=slots, max_frames_per_call=max_frames_per_call)
+        _check_slots(slots)
+        if max_frames_per_call > _INT32_MAX:
+            raise ValueError(f'max_frames_per_call {max_frames_per_call} above 2**31 - 1: counts are int32')
+        if window_frames is None:
+            window = 0
+        else:
+            _check_counts(window_frames=window_frames)
+            if window_frames < max_frames_per_call:
+                raise ValueError(f'window_frames {window_frames} below max_frames_per_call {max_frames_per_call}: two frames '
+                                 'of one call would share a ring entry')
+            if window_frames > _INT32_MAX:
+                raise ValueError(f'window_frames {window_frames} above 2**31 - 1')
+            window = int(window_frames)
+        self.dtype = _sample_dtype(dtype)
+        self.polar = bool(polar)
+        if self.polar:
+            if radius_scale is None:
+                raise ValueError('a voice pool needs a fixed radius_scale: the per-voice maximum of a later block would '
+                                 'rescale the earlier frames')
+            self.radius_scale = _scale(radius_scale, True)
+            if not 0.0 < float(self.dtype.type(self.radius_scale)) < np.inf:
+                raise ValueError(f'radius_scale {radius_scale!r} is zero or infinite in {self.dtype.name}')
+        else:
+            self.radius_scale = None
+        self.ms, self.semicircular = bool(ms), bool(semicircular)
+        e0, e1 = (np.ascontiguousarray(e, np.float64) for e in edges)
+        self.edges = (e0, e1)
+        self.bins = (len(e0) - 1, len(e1) - 1)
+        if not (1 <= self.bins[0] <= MAX_BINS and 1 <= self.bins[1] <= MAX_BINS):
+            raise ValueError(f'{self.bins[0]} x {self.bins[1]} bins: 1 to {MAX_BINS} an axis')
+        self.slots, self.max_frames_per_call, self.window_frames = int(slots), int(max_frames_per_call), window
+        self._block_dtype = self.dtype            # what _schedule holds every block to
+        # the fixed grids of the pool's launches (include/vnd_scope_voice_stream.h): 2^23 workgroups each
+        cells = self.bins[0] * self.bins[1]
+        groups = max(-(-self.max_frames_per_call // VOICE_SPAN_FRAMES), -(-cells * 4 // _VOICE_CLEAR_BYTES))
+        if self.slots * groups > _MAX_GROUPS:
+            raise ValueError(f'{self.slots} slots of {groups} workgroups are more than one launch takes: split the pool')
+        self.transfers = {'to_device': 0, 'to_host': 0}
+        self._state = None                    # (torch uint8 tensor, bytes)
+        self._grid = self._valid = self._own = self._edges_dev = None
+        S = self.slots
+        self._inputs = (('y', (S, self.max_frames_per_call, 2), self.dtype.name, None),) + _slot_ints(S, 'counts', 'flags')
+        self._outputs = (('grid', (S,) + self.bins, 'int32', 'zeros'), ('valid', (S,), 'int32', 'empty'))
+        self._mirror()
+
+    @property
+    def grid(self):
+        """The pool's count grids: int32 ``(slots, bins0, bins1)`` on the device, holding uint32; allocated, as zeros, with
+        the state on first use."""
+        if self._grid is None:
+            self._ensure_state(_torch(), _native.default_context())
+        return self._grid
+
+    def process(self, blocks=None, *, start=(), end=(), discard: bool = False, grids: bool = True):
+        """One call of the dict form.  ``blocks``: ``{slot: (n, 2) array of the pool's dtype}``,
+        ``0 <= n <= max_frames_per_call``; ``start``: the slots whose voice begins with this call; ``end``: the slots whose
+        voice ends with it.  Returns ``{slot: float64 (bins0, bins1)}``, the grid of the voice (``grids=False``: ``None``,
+        and only ``valid`` comes down), for every slot that got a block, started or ended.  Raises before any device call,
+        as the other voice pools do: ``ValueError`` for a slot outside the pool or named twice, a block or an end for a
+        slot that was never started, a start on a live slot (``discard=True`` allows it: the voice it held is dropped), a
+        block above ``max_frames_per_call`` or not ``(n, 2)``; ``TypeError`` for a block of another dtype than the
+        pool's."""
+        self._require_form('dict')
+        starts = self._start_slots(start)
+        counts, flags, tables, live, x, answered = self._schedule(blocks, starts, end, discard)
+        answered = sorted(set(answered) | set(starts))
+        if not counts.any() and not flags.any():              # nothing pushed, started or ended: no device call
+            return {}
+        want, positions = self._spans(counts, flags, tables)
+        host_grid, got = self._call_host(x, counts, flags, bool(grids))
+        if not np.array_equal(np.asarray(got, np.int64), want):
+            raise _native.NativeError(f'the voice pool answered {list(got)}, the spans are {list(want)}')
+        self._commit(positions)
+        self.tables, self._form = tables, 'dict'
+        live[(flags & VOICE_END) != 0] = False
+        self.live = live
+        return {slot: (host_grid[slot].astype(np.float64) if grids else None)
+                for slot in answered if want[slot] == 1}      # (an empty block alone: idle)
+
+    def process_dev(self, y, counts, flags, *, valid=None):
+        """One call on device tensors, enqueued on the current stream: ``y`` ``(slots, M, 2)`` of the pool's dtype,
+        ``counts`` / ``flags`` int32 ``(slots,)``.  Returns ``(grid, valid)``: the pool's own :attr:`grid` - the row of a
+        slot that answered 1 is updated, no other - and int32 ``(slots,)``, the pool's own tensor at a fixed address
+        unless ``valid=`` gives the caller's.  No check reads device memory; bad per-slot values answer -1
+        (``include/vnd_scope_voice_stream.h``)."""
+        if self._form == 'dict':
+            self._require_form('dev')
+        _check_device_tensors((y, counts, flags), self._inputs)
+        if valid is not None:
+            _check_device_tensors((valid,), self._outputs[1:])
+        torch = _torch()
+        self._ensure_state(torch, _native.default_context())
+        return self._call_device(torch, (y, counts, flags), self._grid, self._valid if valid is None else valid)
+
+    # ---- what _SlotPool asks for ---------------------------------------------------------------
+    def _spans(self, counts, flags, tables):
+        return scope_voice_spans(self.positions, counts, flags, self.max_frames_per_call)
+
+    def _per_slot(self, tables):
+        return ()
+
+    def _bank_len(self) -> int:
+        return 1                                  # a voice starts with nothing of its own: the pool has one setting
+
+    def _slot_value(self, index: int):
+        return 0
+
+    # ---- the device -------------------------------------------------------------------------
+    def _state_bytes(self, ctx) -> int:
+        return _native.scope_voice_stream_state_bytes(self.slots, self.max_frames_per_call, self.window_frames)
+
+    def _allocate(self, torch, ctx):
+        _SlotPool._allocate(self, torch, ctx)
+        device = torch.device('cuda', ctx.device)
+        # the grid and valid in one buffer: the dict form brings both down in one copy
+        grid_bytes = self.slots * self.bins[0] * self.bins[1] * 4
+        self._own = torch.zeros((grid_bytes + 4 * self.slots,), dtype=torch.uint8, device=device)
+        self._grid = self._own[:grid_bytes].view(torch.int32).view((self.slots,) + self.bins)
+        self._valid = self._own[grid_bytes:].view(torch.int32)
+        self._edges_dev = _device_edges(torch, device, *self.edges)
+
+    def _reset_entry(self, ctx, state_ptr, state_bytes, stream):
+        _native.scope_voice_stream_reset_device(ctx, state_ptr, state_bytes, self.slots, self.max_frames_per_call,
+                                                self.window_frames, stream=stream)
+
+    def _call_host(self, x, counts, flags, grids: bool = True):
+        """One upload (the blocks and the two int32 arrays in one buffer), the call, one download (the grids and valid, or
+        valid alone)."""
+        torch = _torch()
+        ctx = _native.default_context()
+        device = torch.device('cuda', ctx.device)
+        self._ensure_state(torch, ctx)
+        ints = np.stack([counts, flags]).astype(np.int32)
+        up = torch.from_numpy(np.concatenate([x.reshape(-1).view(np.uint8), ints.reshape(-1).view(np.uint8)])).to(device)
+        self.transfers = {'to_device': 1, 'to_host': 0}
+        x_dev = up[:x.nbytes].view(getattr(torch, x.dtype.name)).view(x.shape)
+        int_rows = up[x.nbytes:].view(torch.int32).view(2, self.slots)
+        form = self._form
+        try:
+            self._call_device(torch, (x_dev, *int_rows), self._grid, self._valid)
+        finally:
+            self._form = form
+        host = (self._own if grids else self._valid).cpu().numpy()
+        self.transfers['to_host'] = 1
+        if not grids:
+            return None, host
+        cut = host.nbytes - 4 * self.slots
+        return host[:cut].view(np.uint32).reshape((self.slots,) + self.bins), host[cut:].view(np.int32)
+
+    def _launch(self, ctx, state_ptr, state_bytes, inputs, grid, valid, stream):
+        y, counts, flags = inputs
+        e0, e1 = self._edges_dev
+        _native.scope_voice_stream_device(
+            ctx, state_ptr, state_bytes, self.max_frames_per_call, self.window_frames, y.data_ptr(),
+            y.data_ptr() + y.element_size(), 2 * self.max_frames_per_call, 2, counts.data_ptr(), flags.data_ptr(),
+            e0.data_ptr(), self.bins[0], e1.data_ptr(), self.bins[1], grid.data_ptr(), valid.data_ptr(), self.slots,
+            polar=self.polar, ms_mode=self.ms, semicircular=self.semicircular,
+            radius_scale=self.radius_scale if self.polar else 0.0, float64=self.dtype == np.float64, stream=stream)
+
+
+def polar_histogram_voice_pool(slots: int, *, max_frames_per_call: int, radius_scale, num_angle_bins: int = 240,
+                               num_radius_bins: int = 150, window_frames: Optional[int] = None, dtype='float32',
+                               mode=LayoutMode.MS, semicircular: bool = True) -> ScopeVoicePool:
+    """A :class:`ScopeVoicePool` of polar grids: ``plot_polar_sample``'s heatmap counts for ``slots`` voices that start, end
+    and push blocks on their own - of each voice's whole signal, or with ``window_frames`` of its last ``window_frames``
+    frames (at least ``max_frames_per_call``).  ``radius_scale``, a positive number, is required: the per-voice maximum
+    cannot stream.  Edges, ``mode`` and ``semicircular`` as in :func:`polar_histogram_batched`.  There is no ``frame_step``:
+    the reference decimates only above 100 000 points, and a window of a second is below that."""
+    bins0, bins1 = _bins(num_angle_bins, 'num_angle_bins'), _bins(num_radius_bins, 'num_radius_bins')
+    return ScopeVoicePool(slots, max_frames_per_call=max_frames_per_call, edges=polar_edges(bins0, bins1), polar=True,
+                          window_frames=window_frames, dtype=dtype, radius_scale=radius_scale, ms=_mode(mode),
+                          semicircular=semicircular)
+
+
+def lissajous_histogram_voice_pool(slots: int, *, max_frames_per_call: int, bins=512, range=((-1.1, 1.1), (-1.1, 1.1)),  # noqa: A002
+                                   window_frames: Optional[int] = None, dtype='float32') -> ScopeVoicePool:
+    """A :class:`ScopeVoicePool` of Lissajous grids: ``plot_lissajous(color_mode='density')``'s counts, L on the first
+    axis, for ``slots`` voices - whole-voice, or over the last ``window_frames`` frames.  ``bins`` and ``range`` as in
+    :func:`lissajous_histogram_batched`; there is no ``max_points``."""
+    e0, e1 = lissajous_edges(bins, range)
+    if len(e0) < 2 or len(e1) < 2 or not (np.all(np.diff(e0) > 0) and np.all(np.diff(e1) > 0)
+                                          and np.all(np.isfinite(e0)) and np.all(np.isfinite(e1))):
+        raise ValueError(f'bins {bins!r} and range {range!r} do not give ascending finite edges')
+    return ScopeVoicePool(slots, max_frames_per_call=max_frames_per_call, edges=(e0, e1), polar=False,
+                          window_frames=window_frames, dtype=dtype)
+
+
 __all__ = ['polar_coordinates_batched', 'polar_histogram_batched', 'lissajous_histogram_batched', 'polar_level_batched',
+           'ScopeVoicePool', 'polar_histogram_voice_pool', 'lissajous_histogram_voice_pool', 'scope_voice_spans',
+           'scope_voice_window', 'VOICE_SPAN_FRAMES',
            'set_scope_device', 'scope_covers', 'level_covers', 'histogram_bins', 'histogram_counts', 'polar_edges',
            'lissajous_edges', 'lissajous_step', 'level_edges', 'percentile_rule', 'percentile_of_sorted', 'SPAN_FRAMES',
            'DIRECT_SPAN_FRAMES', 'MAX_BINS', 'ROUTE_LDS', 'ROUTE_DIRECT', 'LEVEL_MAX_BINS', 'LEVEL_MAX_PERCENTILES',
