@@ -31,6 +31,7 @@ from .decorrelation import (  # noqa: F401
 )
 from .analysis import (  # noqa: F401
     CorrelogramVoicePool,
+    LevelVoicePool,
     PolarVoicePool,
     ScopeVoicePool,
     correlogram_voice_spans,
@@ -42,6 +43,7 @@ from .analysis import (  # noqa: F401
     polar_histogram_batched,
     polar_histogram_voice_pool,
     polar_level_batched,
+    polar_level_voice_pool,
     polar_moments_ordered,
     polar_voice_spans,
     scope_covers,

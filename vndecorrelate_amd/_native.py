@@ -455,6 +455,29 @@ SCOPE_VOICE_STREAM_SIGNATURES = {
 }
 SCOPE_VOICE_SPAN_FRAMES = 1024    # kScopeVoiceSpan: frames of one slot per workgroup of the bin kernel
 
+# include/vnd_polar_level_voice_stream.h: the level envelope of a voice pool - positions, fills and the rings of keys and
+# slices in the device state; a push per block, the levels from the state alone
+_LEVEL_VOICE_PUSH_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                          ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                          ctypes.c_int32, ctypes.c_double, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
+                          ctypes.c_void_p]
+_LEVEL_VOICE_LEVELS_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                            ctypes.POINTER(ctypes.c_double), ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]
+LEVEL_VOICE_STREAM_SIGNATURES = {
+    'vnd_polar_level_voice_stream_state_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                                ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]),
+    'vnd_polar_level_voice_stream_reset_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                              ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                                              ctypes.c_void_p]),
+    'vnd_polar_level_voice_stream_push_f32_dev': (ctypes.c_int, _LEVEL_VOICE_PUSH_ARGS),
+    'vnd_polar_level_voice_stream_push_f64_dev': (ctypes.c_int, _LEVEL_VOICE_PUSH_ARGS),
+    'vnd_polar_level_voice_stream_work_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                               ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]),
+    'vnd_polar_level_voice_stream_levels_f32_dev': (ctypes.c_int, _LEVEL_VOICE_LEVELS_ARGS),
+    'vnd_polar_level_voice_stream_levels_f64_dev': (ctypes.c_int, _LEVEL_VOICE_LEVELS_ARGS),
+}
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -514,7 +537,8 @@ def load_library():
                                   + list(SCOPE_SIGNATURES.items()) + list(LEVEL_SIGNATURES.items())
                                   + list(SPECTRUM_SIGNATURES.items())
                                   + list(SPECTRUM_VOICE_STREAM_SIGNATURES.items())
-                                  + list(SCOPE_VOICE_STREAM_SIGNATURES.items())):
+                                  + list(SCOPE_VOICE_STREAM_SIGNATURES.items())
+                                  + list(LEVEL_VOICE_STREAM_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -1242,6 +1266,67 @@ def polar_level_device(ctx: 'Context', l_ptr: int, r_ptr: int, batch: int, n: in
         int(bool(ms_mode)), int(bool(semicircular)), float(radius_scale), ctypes.c_void_p(angle_edges_ptr), num_bins,
         ps, len(percentiles), ctypes.c_void_p(n_each_ptr), ctypes.c_void_p(levels_ptr), ctypes.c_void_p(bin_counts_ptr),
         ctypes.c_void_p(work_ptr), work_bytes, ctypes.c_void_p(stream)), name)
+
+
+def level_voice_stream_state_bytes(slots: int, max_frames_per_call: int, window_frames: int, float64: bool = False) -> int:
+    """``vnd_polar_level_voice_stream_state_bytes``: the positions, the fills and the rings of keys and slices of a pool of
+    ``slots`` voices over ``window_frames`` frames each."""
+    need = ctypes.c_int64()
+    _check(load_library().vnd_polar_level_voice_stream_state_bytes(slots, max_frames_per_call, window_frames,
+                                                                   int(bool(float64)), ctypes.byref(need)),
+           'vnd_polar_level_voice_stream_state_bytes')
+    return need.value
+
+
+def level_voice_stream_reset_device(ctx: 'Context', state_ptr: int, state_bytes: int, slots: int, max_frames_per_call: int,
+                                    window_frames: int, *, float64: bool = False, stream: int = 0):
+    """``vnd_polar_level_voice_stream_reset_dev``: every position and fill of the pool to 0, enqueued on ``stream``; the
+    rings are left alone."""
+    _check(ctx._lib.vnd_polar_level_voice_stream_reset_dev(ctx.handle, ctypes.c_void_p(state_ptr), state_bytes, slots,
+                                                           max_frames_per_call, window_frames, int(bool(float64)),
+                                                           ctypes.c_void_p(stream)),
+           'vnd_polar_level_voice_stream_reset_dev')
+
+
+def level_voice_stream_push_device(ctx: 'Context', state_ptr: int, state_bytes: int, max_frames_per_call: int,
+                                   window_frames: int, l_ptr: int, r_ptr: int, stream_stride: int, frame_stride: int,
+                                   counts_ptr: int, flags_ptr: int, angle_edges_ptr: int, num_bins: int, valid_ptr: int,
+                                   slots: int, *, radius_scale: float, ms_mode: bool = True, semicircular: bool = True,
+                                   float64: bool = False, stream: int = 0):
+    """``vnd_polar_level_voice_stream_push_f32_dev`` (``_f64_dev`` with ``float64``): one call's frames into the rings of
+    a level voice pool.  Frame t of slot b at ``b * stream_stride + t * frame_stride`` elements of ``l_ptr`` / ``r_ptr``,
+    int32 ``(slots,)`` counts and flags (``VOICE_START``, ``VOICE_END``), float64 device edges and the int32 ``valid``, all
+    device memory, enqueued on ``stream``."""
+    name = f"vnd_polar_level_voice_stream_push_{'f64' if float64 else 'f32'}_dev"
+    p = ctypes.c_void_p
+    _check(getattr(ctx._lib, name)(ctx.handle, p(state_ptr), state_bytes, max_frames_per_call, window_frames, p(l_ptr), p(r_ptr),
+                                   stream_stride, frame_stride, p(counts_ptr), p(flags_ptr), int(bool(ms_mode)),
+                                   int(bool(semicircular)), float(radius_scale), p(angle_edges_ptr), num_bins, p(valid_ptr),
+                                   slots, p(stream)), name)
+
+
+def level_voice_stream_work_bytes(slots: int, window_frames: int, num_bins: int, num_percentiles: int,
+                                  float64: bool = False) -> int:
+    """``vnd_polar_level_voice_stream_work_bytes``: the work memory of one levels call of a level voice pool."""
+    need = ctypes.c_int64()
+    _check(load_library().vnd_polar_level_voice_stream_work_bytes(slots, window_frames, num_bins, num_percentiles,
+                                                                  int(bool(float64)), ctypes.byref(need)),
+           'vnd_polar_level_voice_stream_work_bytes')
+    return need.value
+
+
+def level_voice_stream_levels_device(ctx: 'Context', state_ptr: int, state_bytes: int, max_frames_per_call: int,
+                                     window_frames: int, num_bins: int, percentiles, levels_ptr: int, bin_counts_ptr: int,
+                                     slots: int, *, work_ptr: int, work_bytes: int, float64: bool = False, stream: int = 0):
+    """``vnd_polar_level_voice_stream_levels_f32_dev`` (``_f64_dev`` with ``float64``): the envelope of every slot from the
+    pool's state alone - levels ``(slots, len(percentiles), num_bins)`` of the sample type and uint32 frames per slice
+    ``(slots, num_bins)``; ``percentiles`` is a host sequence, read at the call."""
+    name = f"vnd_polar_level_voice_stream_levels_{'f64' if float64 else 'f32'}_dev"
+    ps = (ctypes.c_double * max(1, len(percentiles)))(*[float(p) for p in percentiles])
+    p = ctypes.c_void_p
+    _check(getattr(ctx._lib, name)(ctx.handle, p(state_ptr), state_bytes, max_frames_per_call, window_frames, num_bins, ps,
+                                   len(percentiles), p(levels_ptr), p(bin_counts_ptr), p(work_ptr), work_bytes, slots,
+                                   p(stream)), name)
 
 
 def spectrum_run_length(nfft: int, nperseg: int, hop: int, float64: bool = False, cross_channels: int = 0) -> int:

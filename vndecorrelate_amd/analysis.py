@@ -774,13 +774,15 @@ def stereo_image_voice_pool(slots: int, *, max_frames_per_call: int = 4800, dtyp
 
 
 # the vectorscope's data (include/vnd_scope.h): the third way the reference looks at a decorrelated signal
-from .vectorscope import (ScopeVoicePool, lissajous_histogram_batched, lissajous_histogram_voice_pool,  # noqa: E402
-                          polar_coordinates_batched, polar_histogram_batched, polar_histogram_voice_pool,
-                          polar_level_batched, scope_covers, scope_voice_spans, scope_voice_window, set_scope_device)
+from .vectorscope import (LevelVoicePool, ScopeVoicePool, lissajous_histogram_batched,  # noqa: E402
+                          lissajous_histogram_voice_pool, polar_coordinates_batched, polar_histogram_batched,
+                          polar_histogram_voice_pool, polar_level_batched, polar_level_voice_pool, scope_covers,
+                          scope_voice_spans, scope_voice_window, set_scope_device)
 
 __all__ = ['cross_correlogram_batched', 'cross_correlogram_stream', 'CorrelogramStream', 'correlogram_covers',
            'set_correlogram_device', 'MAX_WINDOW', 'cross_correlogram_voice_pool', 'CorrelogramVoicePool',
            'correlogram_voice_spans', 'stereo_image_voice_pool', 'PolarVoicePool', 'polar_voice_spans',
            'polar_moments_ordered', 'PolarMomentsState', 'polar_coordinates_batched', 'polar_histogram_batched',
            'lissajous_histogram_batched', 'polar_level_batched', 'set_scope_device', 'scope_covers', 'ScopeVoicePool',
-           'polar_histogram_voice_pool', 'lissajous_histogram_voice_pool', 'scope_voice_spans', 'scope_voice_window']
+           'polar_histogram_voice_pool', 'lissajous_histogram_voice_pool', 'scope_voice_spans', 'scope_voice_window',
+           'LevelVoicePool', 'polar_level_voice_pool']

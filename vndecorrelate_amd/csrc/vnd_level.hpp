@@ -18,6 +18,8 @@
 //   level_min_kernel      grid as stage: the smallest key above the prefix of every asking cell - atomicMin on the bit
 //                         patterns, in LDS, then in global memory
 //   level_finish_kernel   a thread per output: NumPy's lerp on the two order statistics
+// Everything from level_init_kernel on is "the select over staged keys", level_run_select: the voice pool of
+// vnd_level_voice_stream.hpp runs it over its rings, which hold what level_stage_kernel stages (level_frame).
 // Digits are d bits, the widest for which a signal's counters and prefixes fit VND_SCOPE_LDS_BYTES (360 bins x 2
 // percentiles: d = 5, 7 passes over float32 keys, 13 over float64) - narrower for short signals, level_digit_bits below.
 //
@@ -69,6 +71,23 @@ __device__ __forceinline__ void level_count(unsigned int *cnt, int idx)
     }
 }
 
+// What is staged for one frame: its slice on the edges e (staged in LDS; inv = bins / (e[bins] - e[0])), -1 for none, and
+// its key, the bit pattern of radius / den.  level_stage_kernel and the voice pool's push (vnd_level_voice_stream.hpp) both
+// stage through this function, so a ring entry of the pool is what the one-shot entry writes for the frame.
+template <class T>
+__device__ __forceinline__ int level_frame(T l, T r, bool ms, bool fold, T den, const double *e, int bins, double inv,
+                                           typename ScopeKind<T>::Bits &key)
+{
+    using K = ScopeKind<T>;
+    T th, rad;
+    K::sample(l, r, ms, fold, th, rad);
+    const double deg = (double)K::degrees(th);
+    int k = scope_bin(e, bins, inv, deg);
+    if (deg == e[bins]) k = -1;                                   // the reference's mask: `<` on the last edge too
+    key = K::bits(scope_radius(rad, den));
+    return k;
+}
+
 // grid = (ceil(n_frames / span), batch); dynamic LDS: the edges, then the bins' counters
 template <class T>
 __global__ __launch_bounds__(kLevelThreads) void level_stage_kernel(const LevelArgs<T> a)
@@ -91,13 +110,11 @@ __global__ __launch_bounds__(kLevelThreads) void level_stage_kernel(const LevelA
     typename K::Bits *__restrict__ keys = a.keys + b * a.s.n_frames;
     unsigned short *__restrict__ kb = a.bins + b * a.s.n_frames;
     for (int64_t j = j0 + threadIdx.x; j < j1; j += kLevelThreads) {
-        T l, r, th, rad;
+        T l, r;
         scope_load(a.s, pl, pr, j, l, r);
-        K::sample(l, r, a.s.ms != 0, a.s.fold != 0, th, rad);
-        const double deg = (double)K::degrees(th);
-        int k = scope_bin(e, bins, inv, deg);
-        if (deg == e[bins]) k = -1;                               // the reference's mask: `<` on the last edge too
-        keys[j] = K::bits(scope_radius(rad, den));
+        typename K::Bits key;
+        const int k = level_frame(l, r, a.s.ms != 0, a.s.fold != 0, den, e, bins, inv, key);
+        keys[j] = key;
         kb[j] = k < 0 ? kLevelNoBin : (unsigned short)k;
         level_count(cnt, k);
     }
@@ -296,20 +313,29 @@ struct LevelLayout {
 
 static int64_t level_align8(int64_t v) { return (v + 7) & ~(int64_t)7; }
 
+// The select's part of the work memory from byte `at` on - the cell state and the digit histograms; `keys` is where it ends.
 // (the shape is inside the header's limits: nothing overflows)
-static LevelLayout level_layout(int64_t batch, int64_t n_frames, int32_t bins, int32_t num_p, int64_t key_bytes)
+static LevelLayout level_select_layout(int64_t at, int64_t batch, int64_t n_frames, int32_t bins, int32_t num_p, int64_t key_bytes)
 {
     LevelLayout w{};
     const int64_t cells = batch * bins * num_p;
     w.digit_bits = level_digit_bits(n_frames, bins, num_p, key_bytes);
-    int64_t at = batch * 8;
     w.prefix = at; at += cells * 8;
     w.next = at; at += cells * 8;
     w.gamma = at; at += cells * 8;
     w.rank = at; at += level_align8(cells * 4);
     w.flags = at; at += level_align8(cells * 4);
     w.hist = at; w.hist_bytes = level_align8((cells << w.digit_bits) * 4); at += w.hist_bytes;
-    w.keys = at; at += level_align8(batch * n_frames * key_bytes);
+    w.keys = w.bins = w.total = at;
+    return w;
+}
+
+// The one-shot entry's work memory: the per-signal maximum, the select's part, then the staged keys and bins.
+static LevelLayout level_layout(int64_t batch, int64_t n_frames, int32_t bins, int32_t num_p, int64_t key_bytes)
+{
+    LevelLayout w = level_select_layout(batch * 8, batch, n_frames, bins, num_p, key_bytes);
+    int64_t at = w.keys;
+    at += level_align8(batch * n_frames * key_bytes);
     w.bins = at; at += level_align8(batch * n_frames * 2);
     w.total = at;
     return w;
@@ -323,6 +349,56 @@ static vnd_status level_check_shape(int64_t batch, int64_t n_frames, int32_t bin
     if (num_p > VND_LEVEL_MAX_PERCENTILES)
         return fail(VND_ERR_UNSUPPORTED, "%d percentiles, above %d", num_p, VND_LEVEL_MAX_PERCENTILES);
     return scope_check_groups(batch, n_frames, VND_LEVEL_SPAN_FRAMES);
+}
+
+// The select over staged keys, for both callers (level_dev below; the voice pool's levels entry over its rings,
+// vnd_level_voice_stream.hpp).  `a` has keys, bins, bin_counts (counted), s.n_frames, s.step, s.n_each, s.bins0 and s.span, the
+// cell state and hist at `w`'s offsets of `base`, levels, num_p and q.  level_select_allow comes before anything is enqueued.
+struct LevelSelectLds { size_t select, min; };
+
+template <class T>
+static vnd_status level_select_allow(vnd_ctx *ctx, int32_t bins, int32_t num_p, int digit_bits, LevelSelectLds *lds)
+{
+    using Bits = typename ScopeKind<T>::Bits;
+    const int cells = bins * num_p;
+    lds->select = (size_t)cells * sizeof(Bits) + ((size_t)cells << digit_bits) * 4;
+    lds->min = (size_t)cells * (2 * sizeof(Bits) + 4);
+    vnd_status st = allow_lds(ctx, (const void *)level_select_kernel<T>, lds->select);
+    if (st != VND_OK) return st;
+    return allow_lds(ctx, (const void *)level_min_kernel<T>, lds->min);
+}
+
+template <class T>
+static void level_fill_select(LevelArgs<T> &a, char *base, const LevelLayout &w, int64_t batch, int32_t bins, const double *percentiles,
+                              int32_t num_p)
+{
+    using Bits = typename ScopeKind<T>::Bits;
+    a.prefix = (Bits *)(base + w.prefix); a.next = (Bits *)(base + w.next); a.gamma = (T *)(base + w.gamma);
+    a.rank = (unsigned int *)(base + w.rank); a.flags = (unsigned int *)(base + w.flags); a.hist = (unsigned int *)(base + w.hist);
+    a.num_p = num_p; a.digit_bits = w.digit_bits; a.cells_all = batch * bins * num_p;
+    for (int32_t p = 0; p < num_p; ++p) a.q[p] = (T)percentiles[p] / (T)100;
+}
+
+template <class T>
+static vnd_status level_run_select(LevelArgs<T> a, const LevelLayout &w, const LevelSelectLds &lds, int64_t batch, hipStream_t stream)
+{
+    using Bits = typename ScopeKind<T>::Bits;
+    HIP_TRY(hipMemsetAsync(a.hist, 0, (size_t)w.hist_bytes, stream));
+    const dim3 frames_grid((unsigned)((a.s.n_frames + a.s.span - 1) / a.s.span), (unsigned)batch);
+    const dim3 cells_grid((unsigned)((a.cells_all + kLevelCellThreads - 1) / kLevelCellThreads));
+    hipLaunchKernelGGL(level_init_kernel<T>, cells_grid, dim3(kLevelCellThreads), 0, stream, a);
+    constexpr int kKeyBits = 8 * (int)sizeof(Bits);
+    for (int hi = kKeyBits; hi > 0; hi -= w.digit_bits) {
+        a.shift = hi > w.digit_bits ? hi - w.digit_bits : 0;
+        a.width = hi - a.shift;
+        a.last = a.shift == 0;
+        hipLaunchKernelGGL(level_select_kernel<T>, frames_grid, dim3(kLevelThreads), lds.select, stream, a);
+        hipLaunchKernelGGL(level_advance_kernel<T>, cells_grid, dim3(kLevelCellThreads), 0, stream, a);
+    }
+    hipLaunchKernelGGL(level_min_kernel<T>, frames_grid, dim3(kLevelThreads), lds.min, stream, a);
+    hipLaunchKernelGGL(level_finish_kernel<T>, cells_grid, dim3(kLevelCellThreads), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return VND_OK;
 }
 
 template <class T>
@@ -376,37 +452,18 @@ static vnd_status level_dev(vnd_ctx *ctx, const T *l, const T *r, int64_t batch,
     a.s.work = (unsigned long long *)work; a.s.scale = by_max ? (T)0 : (T)radius_scale; a.s.normalize = by_max;
     a.s.ms = ms_mode != 0; a.s.fold = semicircular != 0; a.s.span = VND_LEVEL_SPAN_FRAMES;
     a.keys = (Bits *)(base + w.keys); a.bins = (unsigned short *)(base + w.bins); a.bin_counts = bin_counts;
-    a.prefix = (Bits *)(base + w.prefix); a.next = (Bits *)(base + w.next); a.gamma = (T *)(base + w.gamma);
-    a.rank = (unsigned int *)(base + w.rank); a.flags = (unsigned int *)(base + w.flags); a.hist = (unsigned int *)(base + w.hist);
-    a.levels = levels; a.num_p = num_p; a.digit_bits = w.digit_bits; a.cells_all = cells_all;
-    for (int32_t p = 0; p < num_p; ++p) a.q[p] = (T)percentiles[p] / (T)100;
+    a.levels = levels;
+    level_fill_select(a, base, w, batch, bins, percentiles, num_p);
 
-    const int cells = bins * num_p;
     const size_t stage_lds = (size_t)(bins + 1) * 8 + (size_t)bins * 4;
-    const size_t select_lds = (size_t)cells * sizeof(Bits) + ((size_t)cells << w.digit_bits) * 4;
-    const size_t min_lds = (size_t)cells * (2 * sizeof(Bits) + 4);
-    if ((st = allow_lds(ctx, (const void *)level_select_kernel<T>, select_lds)) != VND_OK) return st;
-    if ((st = allow_lds(ctx, (const void *)level_min_kernel<T>, min_lds)) != VND_OK) return st;
+    LevelSelectLds lds{};
+    if ((st = level_select_allow<T>(ctx, bins, num_p, w.digit_bits, &lds)) != VND_OK) return st;
 
     if (by_max && (st = scope_launch_max(a.s, batch, stream)) != VND_OK) return st;
     HIP_TRY(hipMemsetAsync(bin_counts, 0, (size_t)batch * bins * 4, stream));
-    HIP_TRY(hipMemsetAsync(base + w.hist, 0, (size_t)w.hist_bytes, stream));
     const dim3 frames_grid((unsigned)((n_frames + VND_LEVEL_SPAN_FRAMES - 1) / VND_LEVEL_SPAN_FRAMES), (unsigned)batch);
-    const dim3 cells_grid((unsigned)((cells_all + kLevelCellThreads - 1) / kLevelCellThreads));
     hipLaunchKernelGGL(level_stage_kernel<T>, frames_grid, dim3(kLevelThreads), stage_lds, stream, a);
-    hipLaunchKernelGGL(level_init_kernel<T>, cells_grid, dim3(kLevelCellThreads), 0, stream, a);
-    constexpr int kKeyBits = 8 * (int)sizeof(Bits);
-    for (int hi = kKeyBits; hi > 0; hi -= w.digit_bits) {
-        a.shift = hi > w.digit_bits ? hi - w.digit_bits : 0;
-        a.width = hi - a.shift;
-        a.last = a.shift == 0;
-        hipLaunchKernelGGL(level_select_kernel<T>, frames_grid, dim3(kLevelThreads), select_lds, stream, a);
-        hipLaunchKernelGGL(level_advance_kernel<T>, cells_grid, dim3(kLevelCellThreads), 0, stream, a);
-    }
-    hipLaunchKernelGGL(level_min_kernel<T>, frames_grid, dim3(kLevelThreads), min_lds, stream, a);
-    hipLaunchKernelGGL(level_finish_kernel<T>, cells_grid, dim3(kLevelCellThreads), 0, stream, a);
-    HIP_TRY(hipGetLastError());
-    return VND_OK;
+    return level_run_select(a, w, lds, batch, stream);
 }
 
 extern "C" {

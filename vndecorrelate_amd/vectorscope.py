@@ -16,6 +16,8 @@ whole pool, so a pool of voices that lives in device memory never comes down to 
 * :func:`polar_histogram_voice_pool` / :func:`lissajous_histogram_voice_pool` - the same grids for the voices of a voice
   pool, block by block, of each voice's whole signal or of its last ``window_frames`` frames (:class:`ScopeVoicePool`,
   ``include/vnd_scope_voice_stream.h``, DESIGN.md §3.25);
+* :func:`polar_level_voice_pool` - the level envelope of each voice's last ``window_frames`` frames, the same select over
+  a ring of staged keys (:class:`LevelVoicePool`, ``include/vnd_polar_level_voice_stream.h``, DESIGN.md §3.26);
 * :func:`set_scope_device` and the pure routing rule :func:`scope_covers`, through ``analysis.device_route``.
 
 Counts are integers: a grid equals ``np.histogram2d`` of the same coordinates cell for cell, whatever the route
@@ -825,9 +827,252 @@ def lissajous_histogram_voice_pool(slots: int, *, max_frames_per_call: int, bins
                           window_frames=window_frames, dtype=dtype)
 
 
+# ---- the level envelope of a voice pool (include/vnd_polar_level_voice_stream.h) -------------------------------------
+class LevelVoicePool(_SlotPool):
+    """The level envelope of ``slots`` voices, each with a life of its own (:func:`polar_level_voice_pool`;
+    ``vnd_polar_level_voice_stream_*``): voices start and end on any call and push blocks of any size up to
+    ``max_frames_per_call`` or none, by the slot rule of :class:`ScopeVoicePool` (:func:`scope_voice_spans`).  Percentiles of
+    blocks do not add up, so the device state keeps the window: a ring per slot with the key (the radius's bit pattern) and
+    the slice of each of the voice's last ``window_frames`` frames, and the radix select of :func:`polar_level_batched` runs
+    over the ring as it lies - an order statistic does not depend on the order of its multiset.  Row b of :attr:`levels` is
+    :func:`polar_level_batched` (``radius_scale=...``) of the frames :func:`scope_voice_window` names, bit for bit,
+    whatever the schedule.  An END leaves the envelope readable; the slot's next voice drops it.
+
+    :attr:`levels`, ``(slots, len(percentiles), num_bins)`` of the pool's dtype, and :attr:`bin_counts`, int32 ``(slots,
+    num_bins)`` holding uint32, are device tensors at fixed addresses, allocated as zeros with the state: they belong to
+    the pool - read them, do not write them.  :attr:`bin_edges` and :attr:`bin_centers` are :func:`level_edges`' arrays.
+
+    Pushing and reading are two device entries: blocks arrive a hundred times a second, a display redraws thirty times.
+    Two forms; a pool is used through one of them (mixing them raises ``RuntimeError`` until ``reset()``):
+
+    * ``process({slot: block}, start=[slot, ...], end=[slot, ...], discard=False, levels=True)`` - ``(n, 2)`` NumPy blocks
+      of the pool's ``dtype`` in, ``{slot: float64 (len(percentiles), num_bins)}`` out for every slot that got a block,
+      started or ended - the dtype :func:`polar_level_batched` gives NumPy callers.  One upload and one download;
+      ``levels=False`` pushes only, downloads ``valid`` alone and answers ``{slot: None}``.  Every refusal comes before any
+      device call.
+    * ``process_dev(y, counts, flags, levels=True)`` - ``y`` ``(slots, max_frames_per_call, 2)`` of the pool's ``dtype`` and
+      int32 ``(slots,)`` ``counts`` and ``flags`` on the device; returns ``(levels, valid)``.  It only enqueues on the
+      current stream and can be captured with ``torch.cuda.graph`` after a ``reset()``; ``levels=False`` pushes only, and
+      ``read_dev()`` enqueues the levels entry alone.  To meter a decorrelating pool, build the meter with
+      ``max_frames_per_call=pool.row_frames`` (and ``dtype='float64'`` for a Haas or chain pool) and hand it that pool's
+      ``y`` and ``out_counts`` and the caller's ``flags``: a -1 of the pool is a bad count here and answers -1."""
+
+    in_channels = 2
+    _out_dtype = np.float64
+
+    def __init__(self, slots: int, *, max_frames_per_call: int, window_frames: int, radius_scale, num_bins: int = 360,
+                 percentiles=(95.0, 50.0), dtype='float32', ms: bool = True, semicircular: bool = True):
+        from .analysis import _sample_dtype
+        _check_counts(slots=slots, max_frames_per_call=max_frames_per_call, window_frames=window_frames)
+        _check_slots(slots)
+        if max_frames_per_call > _INT32_MAX:
+            raise ValueError(f'max_frames_per_call {max_frames_per_call} above 2**31 - 1: counts are int32')
+        if window_frames < max_frames_per_call:
+            raise ValueError(f'window_frames {window_frames} below max_frames_per_call {max_frames_per_call}: two frames of '
+                             'one call would share a ring entry')
+        if window_frames > _INT32_MAX:
+            raise ValueError(f'window_frames {window_frames} above 2**31 - 1')
+        self.dtype = _sample_dtype(dtype)
+        if radius_scale is None:
+            raise ValueError('a voice pool needs a fixed radius_scale: the per-voice maximum of a later block would rescale '
+                             'the earlier frames')
+        self.radius_scale = _scale(radius_scale, True)
+        if not 0.0 < float(self.dtype.type(self.radius_scale)) < np.inf:
+            raise ValueError(f'radius_scale {radius_scale!r} is zero or infinite in {self.dtype.name}')
+        self.num_bins = _bins(num_bins, 'num_bins')
+        if self.num_bins > LEVEL_MAX_BINS:
+            raise ValueError(f'num_bins {num_bins}: a level voice pool takes 1 to {LEVEL_MAX_BINS} slices')
+        self.percentiles = tuple(_percentiles(percentiles))
+        if len(self.percentiles) > LEVEL_MAX_PERCENTILES:
+            raise ValueError(f'{len(self.percentiles)} percentiles: a level voice pool takes 1 to {LEVEL_MAX_PERCENTILES}')
+        self.ms, self.semicircular = bool(ms), bool(semicircular)
+        self.bin_edges, self.bin_centers = level_edges(self.num_bins)
+        self.slots, self.max_frames_per_call, self.window_frames = int(slots), int(max_frames_per_call), int(window_frames)
+        self._block_dtype = self.dtype            # what _schedule holds every block to
+        # the fixed grids of the pool's launches (include/vnd_polar_level_voice_stream.h): 2^23 workgroups each
+        groups = max(-(-self.max_frames_per_call // VOICE_SPAN_FRAMES), -(-self.window_frames // LEVEL_SPAN_FRAMES))
+        if self.slots * groups > _MAX_GROUPS:
+            raise ValueError(f'{self.slots} slots of {groups} workgroups are more than one launch takes: split the pool')
+        self.transfers = {'to_device': 0, 'to_host': 0}
+        self._state = None                    # (torch uint8 tensor, bytes)
+        self._levels = self._valid = self._own = self._bin_counts = self._work = self._edges_dev = None
+        self._with_levels = True
+        S = self.slots
+        self._inputs = (('y', (S, self.max_frames_per_call, 2), self.dtype.name, None),) + _slot_ints(S, 'counts', 'flags')
+        self._outputs = (('levels', (S, len(self.percentiles), self.num_bins), self.dtype.name, 'zeros'),
+                         ('valid', (S,), 'int32', 'empty'))
+        self._mirror()
+
+    @property
+    def levels(self):
+        """The pool's envelopes: ``(slots, len(percentiles), num_bins)`` of the pool's dtype on the device; allocated, as
+        zeros, with the state on first use."""
+        if self._levels is None:
+            self._ensure_state(_torch(), _native.default_context())
+        return self._levels
+
+    @property
+    def bin_counts(self):
+        """The frames per slice of every slot's window, as of the last levels call: int32 ``(slots, num_bins)`` on the
+        device, holding uint32."""
+        if self._bin_counts is None:
+            self._ensure_state(_torch(), _native.default_context())
+        return self._bin_counts
+
+    def process(self, blocks=None, *, start=(), end=(), discard: bool = False, levels: bool = True):
+        """One call of the dict form.  ``blocks``: ``{slot: (n, 2) array of the pool's dtype}``,
+        ``0 <= n <= max_frames_per_call``; ``start``: the slots whose voice begins with this call; ``end``: the slots whose
+        voice ends with it.  Returns ``{slot: float64 (len(percentiles), num_bins)}``, the envelope of the voice's window
+        (``levels=False``: ``None``; the frames are pushed, nothing is selected and only ``valid`` comes down), for every
+        slot that got a block, started or ended.  Raises before any device call, as :meth:`ScopeVoicePool.process`
+        does."""
+        self._require_form('dict')
+        starts = self._start_slots(start)
+        counts, flags, tables, live, x, answered = self._schedule(blocks, starts, end, discard)
+        answered = sorted(set(answered) | set(starts))
+        if not counts.any() and not flags.any():              # nothing pushed, started or ended: no device call
+            return {}
+        want, positions = self._spans(counts, flags, tables)
+        host_levels, got = self._call_host(x, counts, flags, bool(levels))
+        if not np.array_equal(np.asarray(got, np.int64), want):
+            raise _native.NativeError(f'the voice pool answered {list(got)}, the spans are {list(want)}')
+        self._commit(positions)
+        self.tables, self._form = tables, 'dict'
+        live[(flags & VOICE_END) != 0] = False
+        self.live = live
+        return {slot: (host_levels[slot].astype(np.float64) if levels else None)
+                for slot in answered if want[slot] == 1}      # (an empty block alone: idle)
+
+    def process_dev(self, y, counts, flags, *, levels: bool = True, valid=None):
+        """One call on device tensors, enqueued on the current stream: ``y`` ``(slots, M, 2)`` of the pool's dtype,
+        ``counts`` / ``flags`` int32 ``(slots,)``.  The frames are pushed into the rings; with ``levels`` the envelopes of
+        all slots are computed from the state behind the push.  Returns ``(levels, valid)``: the pool's own
+        :attr:`levels` and int32 ``(slots,)``, the pool's own tensor at a fixed address unless ``valid=`` gives the
+        caller's.  No check reads device memory; bad per-slot values answer -1
+        (``include/vnd_polar_level_voice_stream.h``)."""
+        if self._form == 'dict':
+            self._require_form('dev')
+        _check_device_tensors((y, counts, flags), self._inputs)
+        if valid is not None:
+            _check_device_tensors((valid,), self._outputs[1:])
+        torch = _torch()
+        self._ensure_state(torch, _native.default_context())
+        self._with_levels = bool(levels)
+        try:
+            return self._call_device(torch, (y, counts, flags), self._levels, self._valid if valid is None else valid)
+        finally:
+            self._with_levels = True
+
+    def read_dev(self):
+        """The levels entry alone, enqueued on the current stream: :attr:`levels` and :attr:`bin_counts` of every slot from
+        the state as the pushes so far left it.  Returns :attr:`levels`."""
+        torch = _torch()
+        ctx = _native.default_context()
+        state, state_bytes = self._ensure_state(torch, ctx)
+        self._read(ctx, state.data_ptr(), state_bytes, self._levels, torch.cuda.current_stream(state.device).cuda_stream)
+        return self._levels
+
+    # ---- what _SlotPool asks for ---------------------------------------------------------------
+    def _spans(self, counts, flags, tables):
+        return scope_voice_spans(self.positions, counts, flags, self.max_frames_per_call)
+
+    def _per_slot(self, tables):
+        return ()
+
+    def _bank_len(self) -> int:
+        return 1                                  # a voice starts with nothing of its own: the pool has one setting
+
+    def _slot_value(self, index: int):
+        return 0
+
+    # ---- the device -------------------------------------------------------------------------
+    def _is64(self) -> bool:
+        return self.dtype == np.float64
+
+    def _state_bytes(self, ctx) -> int:
+        return _native.level_voice_stream_state_bytes(self.slots, self.max_frames_per_call, self.window_frames, self._is64())
+
+    def _allocate(self, torch, ctx):
+        _SlotPool._allocate(self, torch, ctx)
+        device = torch.device('cuda', ctx.device)
+        # the levels and valid in one buffer: the dict form brings both down in one copy
+        shape = self._outputs[0][1]
+        level_bytes = int(np.prod(shape)) * self.dtype.itemsize
+        self._own = torch.zeros((level_bytes + 4 * self.slots,), dtype=torch.uint8, device=device)
+        self._levels = self._own[:level_bytes].view(getattr(torch, self.dtype.name)).view(shape)
+        self._valid = self._own[level_bytes:].view(torch.int32)
+        self._bin_counts = torch.zeros((self.slots, self.num_bins), dtype=torch.int32, device=device)
+        self._work_bytes = _native.level_voice_stream_work_bytes(self.slots, self.window_frames, self.num_bins,
+                                                                 len(self.percentiles), self._is64())
+        self._work = torch.empty(((self._work_bytes + 7) // 8,), dtype=torch.int64, device=device)
+        self._edges_dev = _device_edges(torch, device, self.bin_edges, self.bin_centers)
+        # one read of the fresh state: whatever the select sets up on its first launch happens here, not inside a capture
+        state, state_bytes = self._state
+        self._read(ctx, state.data_ptr(), state_bytes, self._levels, torch.cuda.current_stream(device).cuda_stream)
+
+    def _reset_entry(self, ctx, state_ptr, state_bytes, stream):
+        _native.level_voice_stream_reset_device(ctx, state_ptr, state_bytes, self.slots, self.max_frames_per_call,
+                                                self.window_frames, float64=self._is64(), stream=stream)
+
+    def _call_host(self, x, counts, flags, levels: bool = True):
+        """One upload (the blocks and the two int32 arrays in one buffer), the call, one download (the levels and valid,
+        or valid alone)."""
+        torch = _torch()
+        ctx = _native.default_context()
+        device = torch.device('cuda', ctx.device)
+        self._ensure_state(torch, ctx)
+        ints = np.stack([counts, flags]).astype(np.int32)
+        up = torch.from_numpy(np.concatenate([x.reshape(-1).view(np.uint8), ints.reshape(-1).view(np.uint8)])).to(device)
+        self.transfers = {'to_device': 1, 'to_host': 0}
+        x_dev = up[:x.nbytes].view(getattr(torch, x.dtype.name)).view(x.shape)
+        int_rows = up[x.nbytes:].view(torch.int32).view(2, self.slots)
+        form = self._form
+        self._with_levels = levels
+        try:
+            self._call_device(torch, (x_dev, *int_rows), self._levels, self._valid)
+        finally:
+            self._form, self._with_levels = form, True
+        host = (self._own if levels else self._valid).cpu().numpy()
+        self.transfers['to_host'] = 1
+        if not levels:
+            return None, host
+        cut = host.nbytes - 4 * self.slots
+        return host[:cut].view(self.dtype).reshape(self._outputs[0][1]), host[cut:].view(np.int32)
+
+    def _launch(self, ctx, state_ptr, state_bytes, inputs, levels, valid, stream):
+        y, counts, flags = inputs
+        _native.level_voice_stream_push_device(
+            ctx, state_ptr, state_bytes, self.max_frames_per_call, self.window_frames, y.data_ptr(),
+            y.data_ptr() + y.element_size(), 2 * self.max_frames_per_call, 2, counts.data_ptr(), flags.data_ptr(),
+            self._edges_dev[0].data_ptr(), self.num_bins, valid.data_ptr(), self.slots, radius_scale=self.radius_scale,
+            ms_mode=self.ms, semicircular=self.semicircular, float64=self._is64(), stream=stream)
+        if self._with_levels:
+            self._read(ctx, state_ptr, state_bytes, levels, stream)
+
+    def _read(self, ctx, state_ptr, state_bytes, levels, stream):
+        _native.level_voice_stream_levels_device(
+            ctx, state_ptr, state_bytes, self.max_frames_per_call, self.window_frames, self.num_bins, self.percentiles,
+            levels.data_ptr(), self._bin_counts.data_ptr(), self.slots, work_ptr=self._work.data_ptr(),
+            work_bytes=self._work_bytes, float64=self._is64(), stream=stream)
+
+
+def polar_level_voice_pool(slots: int, *, max_frames_per_call: int, window_frames: int, radius_scale, num_bins: int = 360,
+                           percentiles=(95.0, 50.0), dtype='float32', mode=LayoutMode.MS,
+                           semicircular: bool = True) -> LevelVoicePool:
+    """A :class:`LevelVoicePool`: ``plot_polar_level``'s raw envelope - the ``percentiles`` of the radius in each of
+    ``num_bins`` angular slices - over the last ``window_frames`` frames (at least ``max_frames_per_call``) of ``slots``
+    voices that start, end and push blocks on their own.  ``radius_scale``, a positive number, is required: the per-voice
+    maximum cannot stream.  Slices, ``percentiles``, ``mode`` and ``semicircular`` as in :func:`polar_level_batched`.
+    There is no whole-voice form (its ring would be unbounded) and no host loop: another dtype, more than
+    ``LEVEL_MAX_BINS`` slices or ``LEVEL_MAX_PERCENTILES`` percentiles raise ``ValueError`` here."""
+    return LevelVoicePool(slots, max_frames_per_call=max_frames_per_call, window_frames=window_frames,
+                          radius_scale=radius_scale, num_bins=num_bins, percentiles=percentiles, dtype=dtype, ms=_mode(mode),
+                          semicircular=semicircular)
+
+
 __all__ = ['polar_coordinates_batched', 'polar_histogram_batched', 'lissajous_histogram_batched', 'polar_level_batched',
            'ScopeVoicePool', 'polar_histogram_voice_pool', 'lissajous_histogram_voice_pool', 'scope_voice_spans',
-           'scope_voice_window', 'VOICE_SPAN_FRAMES',
+           'scope_voice_window', 'VOICE_SPAN_FRAMES', 'LevelVoicePool', 'polar_level_voice_pool',
            'set_scope_device', 'scope_covers', 'level_covers', 'histogram_bins', 'histogram_counts', 'polar_edges',
            'lissajous_edges', 'lissajous_step', 'level_edges', 'percentile_rule', 'percentile_of_sorted', 'SPAN_FRAMES',
            'DIRECT_SPAN_FRAMES', 'MAX_BINS', 'ROUTE_LDS', 'ROUTE_DIRECT', 'LEVEL_MAX_BINS', 'LEVEL_MAX_PERCENTILES',
