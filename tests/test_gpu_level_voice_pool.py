@@ -753,3 +753,41 @@ def test_dict_form_equals_the_batched_levels_of_the_window(torch, ctx, vs):
     assert np.array_equal(meter.bin_counts[1].cpu().numpy().astype(np.int64), want_cnt)
     with pytest.raises(RuntimeError, match='runs through process\\(\\)'):
         meter.process_dev(None, None, None)
+
+
+# ---- 6. three workgroups a slot -------------------------------------------------------------------------------------------
+def span_schedule(M, seed, dtype):
+    """Eight calls of three slots with M = 2 spans + 3.  Slot 0 pushes M, M, span, span + 1, span - 1, M, 1, M; slot 1 a
+    permutation of these, ENDs on call 3 and STARTs again on call 4; slot 2 a random count in [0, M].  START on call 0, END on
+    the last call: whole workgroups leave past n, and the wrap of a ring falls into the first, second and third workgroup."""
+    span = (M - 3) // 2
+    rng = np.random.default_rng(seed)
+    first = [M, M, span, span + 1, span - 1, M, 1, M]
+    second = [span + 1, M, 1, M, span - 1, M, span, M]
+    assert sorted(first) == sorted(second)
+    out = []
+    for i in range(8):
+        counts = np.array([first[i], second[i], int(rng.integers(0, M + 1))], np.int64)
+        flags = np.array([START if i == 0 else 0, START if i in (0, 4) else (END if i == 3 else 0), START if i == 0 else 0],
+                         np.int32)
+        if i == 7:
+            flags |= END
+        out.append(([frames(rng, int(c), dtype) for c in counts], counts, flags))
+    return out
+
+
+@pytest.mark.parametrize('dtype', [np.float32, np.float64], ids=['f32', 'f64'])
+@pytest.mark.parametrize('window', ['M', 'M+span+1'])
+def test_three_workgroups_a_slot_wrap_an_odd_ring(torch, ctx, vs, window, dtype):
+    from vndecorrelate_amd import _native
+    span = _native.SCOPE_VOICE_SPAN_FRAMES
+    S, M = 3, 2 * span + 3
+    assert span == 1024 and -(-M // span) == 3 and M % span == 3
+    W = {'M': M, 'M+span+1': M + span + 1}[window]
+    h = Harness(torch, ctx, vs, S, M, W, 8, (95.0, 50.0), dtype=dtype)
+    for blocks, counts, flags in span_schedule(M, 41 + W, dtype):
+        _, _, valid = h.call(blocks, counts, flags)
+        assert valid[:2].tolist() == [1, 1] and valid[2] >= 0
+    assert h.checked == 8 * S and not h.mirror.any()
+    assert h.slid >= 8                                                # the window slid: ring entries were written over
+    assert 4 * M + 3 * span + 1 > 2 * W                               # slot 0 went over its ring more than twice

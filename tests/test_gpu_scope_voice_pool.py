@@ -617,3 +617,41 @@ def test_bad_arguments_write_nothing(torch, ctx, vs, dtype, polar):
     h.reset()
     rows, valid = h.call([np.full((M, 2), 0.25, dtype)] * S, [M] * S, [START] * S)       # the good call writes
     assert valid.tolist() == [1, 1] and rows.sum(axis=1).tolist() == [M, M] and (rows.max(axis=1) == M).all()
+
+
+# ---- 9. three workgroups a slot -------------------------------------------------------------------------------------------
+def span_schedule(M, seed, dtype):
+    """Eight calls of three slots with M = 2 spans + 3.  Slot 0 pushes M, M, span, span + 1, span - 1, M, 1, M; slot 1 a
+    permutation of these, ENDs on call 3 and STARTs again on call 4; slot 2 a random count in [0, M].  START on call 0, END on
+    the last call: whole workgroups leave past n, and the wrap of a ring falls into the first, second and third workgroup."""
+    span = (M - 3) // 2
+    rng = np.random.default_rng(seed)
+    first = [M, M, span, span + 1, span - 1, M, 1, M]
+    second = [span + 1, M, 1, M, span - 1, M, span, M]
+    assert sorted(first) == sorted(second)
+    out = []
+    for i in range(8):
+        counts = np.array([first[i], second[i], int(rng.integers(0, M + 1))], np.int64)
+        flags = np.array([START if i == 0 else 0, START if i in (0, 4) else (END if i == 3 else 0), START if i == 0 else 0],
+                         np.int32)
+        if i == 7:
+            flags |= END
+        out.append(([frames(rng, int(c), dtype) for c in counts], counts, flags))
+    return out
+
+
+@pytest.mark.parametrize('dtype', [np.float32, np.float64], ids=['f32', 'f64'])
+@pytest.mark.parametrize('window', ['M', 'M+span+1', 'whole'])
+def test_three_workgroups_a_slot_wrap_an_odd_ring(torch, ctx, vs, window, dtype):
+    from vndecorrelate_amd import _native
+    span = _native.SCOPE_VOICE_SPAN_FRAMES
+    S, M = 3, 2 * span + 3
+    assert span == 1024 and -(-M // span) == 3 and M % span == 3
+    W = {'M': M, 'M+span+1': M + span + 1, 'whole': 0}[window]
+    h = Harness(torch, ctx, S, M, W, *polar_12x7(vs), dtype=dtype)
+    seen = run_schedule(h, span_schedule(M, 31 + W, dtype))
+    assert all(v[:2] == [1, 1] and v[2] >= 0 for _, v in seen) and h.checked >= 16
+    assert not h.positions().any()
+    if W:
+        assert h.slid >= 8                                            # the window slid: frames left through the ring
+        assert 4 * M + 3 * span + 1 > 2 * W                           # slot 0 went over its ring more than twice

@@ -68,10 +68,11 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
         assert callable(getattr(_native, wrapper))
     comment = HEADER.read_text()
     assert 'fill is a prefix length' in comment and 'distinct residues mod W' in comment and 'BYTE FOR BYTE' in comment
-    # one translation unit: the new part comes after the three it builds on
+    # one translation unit: the new part comes after what it builds on, the window core between the one-shots and the pools
     unit = (REPO / 'vndecorrelate_amd' / 'csrc' / 'vnd_amd.hip').read_text()
-    order = [unit.index(f'#include "{n}"') for n in ('vnd_level.hpp', 'vnd_scope_voice_stream.hpp', 'vnd_level_voice_stream.hpp')]
-    assert order == sorted(order)
+    order = [unit.index(f'#include "{n}"') for n in ('vnd_voice_stream.hpp', 'vnd_scope.hpp', 'vnd_level.hpp', 'vnd_voice_window.hpp',
+                                                     'vnd_scope_voice_stream.hpp', 'vnd_level_voice_stream.hpp')]
+    assert order == sorted(order) and unit.count('#include "vnd_voice_window.hpp"') == 1
 
 
 def test_the_frame_body_is_stated_once():
@@ -84,6 +85,30 @@ def test_the_frame_body_is_stated_once():
     # the select over staged keys: one host helper, both callers
     assert level.count('level_run_select(') == 2 and voice.count('level_run_select(a,') == 1
     assert 'level_select_kernel' not in voice and 'voice_head' not in voice and 'scope_voice_span(' in voice
+
+
+def test_the_ring_walk_is_stated_once():
+    """The slot rule, the walk of a workgroup and its ring entry with the one wrap: vnd_voice_window.hpp, called by both
+    pools' kernels; the level pool loads the chunk's frame with the one-shot's scope_load."""
+    csrc = REPO / 'vndecorrelate_amd' / 'csrc'
+    core = (csrc / 'vnd_voice_window.hpp').read_text()
+    pools = [(csrc / name).read_text() for name in ('vnd_scope_voice_stream.hpp', 'vnd_level_voice_stream.hpp')]
+    assert core.count('slot -= W') == 1 and core.count('-= W') == 1 and core.count('% W') == 1
+    assert core.count('ScopeVoiceSpan scope_voice_span(') == 1 and core.count('struct VoiceWindowWalk') == 1
+    assert core.count('kScopeVoiceSpan = 1024') == 1 and core.count('kScopeVoiceThreads = 256') == 1
+    assert core.count('distinct residues mod W') == 1 and core.count('vnd_status voice_window_plan(') == 1
+    assert core.count('vnd_status voice_window_scale(') == 1
+    assert pools[1].count('scope_load(a.s, pl, pr, j, l, r)') == 1 and 'a.s.packed' not in pools[1] and 'if (a.packed)' not in pools[1]
+    assert pools[0].count('if (a.packed) {') == 1          # (the scope pool keeps its own packed load: its file says why)
+    for text in pools:
+        assert '-= a.W' not in text and '-= W' not in text and '% a.W' not in text and '% W' not in text
+        assert text.count('VoiceWindowWalk w;') == 1 and text.count('w.open(a.pos, a.counts, a.flags, a.M, b, blockIdx.x)') == 1
+        assert text.count('w.entry(j)') == 1
+        assert 'distinct residues' not in text and 'vnd_voice_window.hpp' in text
+        assert text.count('voice_window_plan(') == 1 and 'radius_scale is NaN' not in text and 'scope_overlap(' not in text
+        assert text.count('voice_window_scale<T>(radius_scale)') == 1 and 'scope_clash(outs,' in text
+    scope = (csrc / 'vnd_scope.hpp').read_text()
+    assert scope.count('static int scope_clash(') == 1 and scope.count('scope_clash(outs,') == 2
 
 
 # ---- the sizes -------------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""The four public span functions of the voice pools against a scalar restatement of their headers' formulas, slot by
+"""The six public span functions of the voice pools against a scalar restatement of their headers' formulas, slot by
 slot, on the full grid of positions, counts and flags - bad and idle corners included.  The restatements are plain ``if``s
 and share nothing with the functions under test.  No GPU."""
 import itertools
@@ -62,15 +62,45 @@ def _polar(pos, n, f):
     return 1, (0 if f & END else p + n)
 
 
+def _scope(pos, n, f):
+    """include/vnd_scope_voice_stream.h: valid and the position; a row is cleared when a slot answers 1 from p = 0."""
+    p = pos
+    if f & START:
+        p = 0
+    if n < 0 or n > M:
+        return -1, pos
+    if p < 0 or p > TOP:
+        return -1, pos
+    if n == 0 and f & START == 0 and f & END == 0:
+        return 0, pos
+    if f & END:
+        return 1, 0
+    return 1, p + n
+
+
+def _spectrum(pos, n, f):
+    """include/vnd_spectrum_voice_stream.h, nperseg W and hop HOP: (out_count, segments, new position)."""
+    p, bad = _head(pos, n, f)
+    if bad:
+        return -1, -1, pos
+
+    def complete(q):
+        if q < W:
+            return 0
+        return (q - W) // HOP + 1
+    if n == 0 and not f & (START | END):                  # idle: the means stay as they are
+        return 0, -1, pos
+    return complete(p + n) - complete(p), complete(p + n), (0 if f & END else p + n)
+
+
 def _columns(grid):
     return [np.array(c, np.int64) for c in zip(*grid)]
 
 
 def _check(got, want, grid):
-    out, new = got
-    assert out.dtype == np.int64 and new.dtype == np.int64
-    for cell, o, q, (wo, wq) in zip(grid, out.tolist(), new.tolist(), want):
-        assert (o, q) == (wo, wq), cell
+    assert all(a.dtype == np.int64 for a in got)
+    for cell, *values, expected in zip(grid, *(a.tolist() for a in got), want):
+        assert tuple(values) == expected, cell
 
 
 def test_grid_size():
@@ -100,3 +130,17 @@ def test_polar_voice_spans_grid():
     from vndecorrelate_amd.analysis import polar_voice_spans
     pos, n, f = _columns(GRID)
     _check(polar_voice_spans(pos, n, f, M), [_polar(*cell) for cell in GRID], GRID)
+
+
+def test_scope_voice_spans_grid():
+    from vndecorrelate_amd.vectorscope import scope_voice_spans
+    pos, n, f = _columns(GRID)
+    _check(scope_voice_spans(pos, n, f, M), [_scope(*cell) for cell in GRID], GRID)
+
+
+def test_spectrum_voice_spans_grid():
+    from vndecorrelate_amd.spectral import spectrum_voice_spans
+    pos, n, f = _columns(GRID)
+    got = spectrum_voice_spans(pos, n, f, W, HOP, M)
+    assert len(got) == 3
+    _check(got, [_spectrum(*cell) for cell in GRID], GRID)

@@ -29,11 +29,11 @@ from typing import Optional
 import numpy as np
 
 from . import _native
-from .streaming import VOICE_END, BlockStream, _check_counts, _check_slots, _slot_ints, _SlotPool, _voice_head
+from .streaming import (_INT32_MAX, BlockStream, _MeterPool, _sample_dtype, _slot_ints, _SlotPool,  # noqa: F401
+                        _valid_voice_spans, _voice_head)
 from .utils.dsp import EPSILON, correlogram_sizes, to_float32
 
 MAX_WINDOW = _native.CORRELOGRAM_MAX_WINDOW
-_INT32_MAX = 2 ** 31 - 1
 _torch = _native.torch_module          # the name this module's device paths look torch up by
 
 _correlogram_device: Optional[bool] = None
@@ -369,18 +369,7 @@ def correlogram_voice_spans(positions, counts, flags, window: int, hop: int, max
     return out, new
 
 
-def _sample_dtype(dtype) -> np.dtype:
-    """A meter's ``dtype`` argument as a NumPy dtype: float32 or float64, else ``ValueError``."""
-    try:
-        parsed = None if dtype is None else np.dtype(dtype)                       # (np.dtype(None) is float64)
-    except TypeError:
-        parsed = None
-    if parsed is None or parsed.name not in ('float32', 'float64'):
-        raise ValueError(f"dtype must be 'float32' or 'float64', got {dtype!r}")
-    return parsed
-
-
-class CorrelogramVoicePool(_SlotPool):
+class CorrelogramVoicePool(_MeterPool):
     """``cross_correlogram`` of ``slots`` voices, each with a life of its own (:func:`cross_correlogram_voice_pool`,
     ``vnd_correlogram_voice_stream_*_dev``): voices start and end on any call and push blocks of any size up to
     ``max_frames_per_call`` or none.  The position lives in the device state, one per slot, so a call is a pure function
@@ -402,20 +391,15 @@ class CorrelogramVoicePool(_SlotPool):
       pool) and hand it that pool's ``y`` and ``out_counts`` and the caller's ``flags``: a -1 of the pool is a bad count
       here and answers -1.  A float64 sample is cast to float32 inside the kernel, round to nearest even."""
 
-    in_channels = 2
     _out_dtype = np.float32
 
     def __init__(self, slots: int, *, window: int, hop: int, num_lags: int, epsilon, max_frames_per_call: int,
                  dtype='float32'):
-        _check_counts(slots=slots, max_frames_per_call=max_frames_per_call)
-        _check_slots(slots)
-        if max_frames_per_call > _INT32_MAX:
-            raise ValueError(f'max_frames_per_call {max_frames_per_call} above 2**31 - 1: counts are int32')
+        _MeterPool.__init__(self, slots, max_frames_per_call, dtype)
+        self._block_dtype = np.float32            # the dict form casts float64 blocks, as cross_correlogram does
         if not correlogram_covers(0, window, hop, num_lags, epsilon):
             raise ValueError(f'window {window}, hop {hop}, {num_lags} lags and epsilon {epsilon!r} have no device form '
                              f'(correlogram_covers is False) and the pool has no NumPy one: use cross_correlogram')
-        self.dtype = _sample_dtype(dtype)
-        self.slots, self.max_frames_per_call = int(slots), int(max_frames_per_call)
         self.window, self.hop, self.num_lags, self.epsilon = int(window), int(hop), int(num_lags), epsilon
         # the fixed grid of the pool (include/vnd_correlogram_voice_stream.h): window groups of 4 rows x column tiles of
         # 1024 lags per slot, one grid dimension; 2^23 workgroups a launch
@@ -424,8 +408,6 @@ class CorrelogramVoicePool(_SlotPool):
                 or self.slots * self.rows_per_call * self.num_lags > 1 << 40:
             raise ValueError(f'{self.slots} slots of {self.rows_per_call} rows of {self.num_lags} lags per call are more than '
                              f'one launch takes: raise the stride or lower max_frames_per_call')
-        self.transfers = {'to_device': 0, 'to_host': 0}
-        self._state = None                    # (torch uint8 tensor, bytes)
         S = self.slots
         self._inputs = (('x', (S, self.max_frames_per_call, 2), self.dtype.name, None),) + _slot_ints(S, 'counts', 'flags')
         self._outputs = (('rows', (S, self.rows_per_call, self.num_lags), 'float32', 'empty'),
@@ -469,15 +451,6 @@ class CorrelogramVoicePool(_SlotPool):
     def _spans(self, counts, flags, tables):
         return correlogram_voice_spans(self.positions, counts, flags, self.window, self.hop, self.max_frames_per_call)
 
-    def _per_slot(self, tables):
-        return ()
-
-    def _bank_len(self) -> int:
-        return 1                                  # a voice starts with nothing of its own: the pool has one setting
-
-    def _slot_value(self, index: int):
-        return 0
-
     # ---- the device -------------------------------------------------------------------------
     def _state_bytes(self, ctx) -> int:
         return _native.correlogram_voice_stream_state_bytes(self.slots, self.window, self.max_frames_per_call)
@@ -485,10 +458,6 @@ class CorrelogramVoicePool(_SlotPool):
     def _reset_entry(self, ctx, state_ptr, state_bytes, stream):
         _native.correlogram_voice_stream_reset_device(ctx, state_ptr, state_bytes, self.slots, self.window,
                                                       self.max_frames_per_call, stream=stream)
-
-    def _call_host(self, x, counts, flags):
-        """One upload (the blocks and the two int32 arrays in one buffer), the call, one download (rows and out_counts)."""
-        return self._call_host_packed(x, (counts, flags))
 
     def _launch(self, ctx, state_ptr, state_bytes, inputs, rows, out_counts, stream):
         x, counts, flags = inputs                           # x is the host path's float32 cast or the pool's dtype
@@ -529,12 +498,7 @@ def polar_voice_spans(positions, counts, flags, max_frames_per_call: Optional[in
 
     A count below 0 (or above ``max_frames_per_call``, when given), or without START a position outside ``[0, 2^60]``,
     answers -1 and leaves the position as it was."""
-    pos, n, start, end, p, bad = _voice_head(positions, counts, flags, max_frames_per_call)
-    idle = ~bad & (n == 0) & ~start & ~end
-    p, n = np.where(bad, 0, p), np.where(bad, 0, n)          # (no arithmetic on a bad value)
-    valid = np.where(bad, -1, np.where(idle, 0, 1)).astype(np.int64)
-    new = np.where(bad | idle, pos, np.where(end, 0, p + n)).astype(np.int64)
-    return valid, new
+    return _valid_voice_spans(positions, counts, flags, max_frames_per_call)
 
 
 def _polar_fold(acc, more):
@@ -634,7 +598,7 @@ def polar_moments_ordered(terms, state: Optional[PolarMomentsState] = None):
     return _polar_tree(lanes)
 
 
-class PolarVoicePool(_SlotPool):
+class PolarVoicePool(_MeterPool):
     """The stereo image of ``slots`` voices, each with a life of its own (:func:`stereo_image_voice_pool`,
     ``vnd_polar_voice_stream_*_dev``): voices start and end on any call and push blocks of any size up to
     ``max_frames_per_call`` or none.  The position lives in the device state, one per slot, so a call is a pure function
@@ -657,25 +621,16 @@ class PolarVoicePool(_SlotPool):
       pool) and hand it that pool's ``y`` and ``out_counts`` and the caller's ``flags``: a -1 of the pool is a bad count
       here and answers -1."""
 
-    in_channels = 2
     _out_dtype = np.float64
     _out_width = 8
 
     def __init__(self, slots: int, *, max_frames_per_call: int, dtype='float32'):
-        _check_counts(slots=slots, max_frames_per_call=max_frames_per_call)
-        _check_slots(slots)
-        if max_frames_per_call > _INT32_MAX:
-            raise ValueError(f'max_frames_per_call {max_frames_per_call} above 2**31 - 1: counts are int32')
-        self.dtype = _sample_dtype(dtype)
-        self.slots, self.max_frames_per_call = int(slots), int(max_frames_per_call)
-        self._block_dtype = self.dtype            # what _schedule holds every block to
+        _MeterPool.__init__(self, slots, max_frames_per_call, dtype)
         # the fixed grid of the pool (include/vnd_polar_voice_stream.h): one workgroup per chunk of 512 frames a call can
         # touch, one grid dimension per slot; 2^23 workgroups a launch
         if self.chunks_per_call > 65535 or self.slots * self.chunks_per_call > 1 << 23:
             raise ValueError(f'{self.slots} slots of {self.chunks_per_call} chunks per call are more than one launch takes: '
                              f'lower max_frames_per_call or split the pool')
-        self.transfers = {'to_device': 0, 'to_host': 0}
-        self._state = None                    # (torch uint8 tensor, bytes)
         S = self.slots
         self._inputs = (('y', (S, self.max_frames_per_call, 2), self.dtype.name, None),) + _slot_ints(S, 'counts', 'flags')
         self._outputs = (('moments', (S, 8), 'float64', 'zeros'), ('valid', (S,), 'int32', 'empty'))
@@ -694,21 +649,7 @@ class PolarVoicePool(_SlotPool):
         outside the pool or named twice, a block or an end for a slot that was never started, a start on a live slot
         (``discard=True`` allows it: the voice it held is dropped), a block above ``max_frames_per_call`` or not
         ``(n, 2)``; ``TypeError`` for a block of another dtype than the pool's."""
-        self._require_form('dict')
-        starts = self._start_slots(start)
-        counts, flags, tables, live, x, answered = self._schedule(blocks, starts, end, discard)
-        answered = sorted(set(answered) | set(starts))
-        if not counts.any() and not flags.any():              # nothing pushed, started or ended: no device call
-            return {}
-        want, positions = self._spans(counts, flags, tables)
-        moments, got = self._call_host(x, counts, flags)
-        if not np.array_equal(np.asarray(got, np.int64), want):
-            raise _native.NativeError(f'the voice pool answered {list(got)}, the spans are {list(want)}')
-        self._commit(positions)
-        self.tables, self._form = tables, 'dict'
-        live[(flags & VOICE_END) != 0] = False
-        self.live = live
-        return {slot: np.array(moments[slot]) for slot in answered if want[slot] == 1}        # (an empty block alone: idle)
+        return self._process_valid(blocks, start, end, discard, np.array)
 
     def process_dev(self, y, counts, flags, *, out=None):
         """One call on device tensors, enqueued on the current stream: ``y`` ``(slots, M, 2)`` of the pool's dtype,
@@ -732,19 +673,6 @@ class PolarVoicePool(_SlotPool):
                                              lambda_penalty=lambda_penalty)
         return float(s[0]) if m.ndim == 1 else s
 
-    # ---- what _SlotPool asks for ---------------------------------------------------------------
-    def _spans(self, counts, flags, tables):
-        return polar_voice_spans(self.positions, counts, flags, self.max_frames_per_call)
-
-    def _per_slot(self, tables):
-        return ()
-
-    def _bank_len(self) -> int:
-        return 1                                  # a voice starts with nothing of its own: the pool has one setting
-
-    def _slot_value(self, index: int):
-        return 0
-
     # ---- the device -------------------------------------------------------------------------
     def _state_bytes(self, ctx) -> int:
         return _native.polar_voice_stream_state_bytes(self.slots, self.max_frames_per_call, self.dtype.itemsize)
@@ -752,10 +680,6 @@ class PolarVoicePool(_SlotPool):
     def _reset_entry(self, ctx, state_ptr, state_bytes, stream):
         _native.polar_voice_stream_reset_device(ctx, state_ptr, state_bytes, self.slots, self.max_frames_per_call,
                                                 self.dtype.itemsize, stream=stream)
-
-    def _call_host(self, x, counts, flags):
-        """One upload (the blocks and the two int32 arrays in one buffer), the call, one download (moments and valid)."""
-        return self._call_host_packed(x, (counts, flags))
 
     def _launch(self, ctx, state_ptr, state_bytes, inputs, moments, valid, stream):
         y, counts, flags = inputs

@@ -427,6 +427,7 @@ vnd_status vnd_prepare_launch(vnd_ctx *ctx, const vnd_taps *t, int64_t batch, in
 #include "vnd_level.hpp"
 #include "vnd_spectrum.hpp"
 #include "vnd_spectrum_voice_stream.hpp"
+#include "vnd_voice_window.hpp"
 #include "vnd_scope_voice_stream.hpp"
 #include "vnd_level_voice_stream.hpp"
 #include "vnd_hooks.hpp"

@@ -1,35 +1,29 @@
 // vnd_level_voice_stream.hpp - the polar level envelope of a voice pool (include/vnd_polar_level_voice_stream.h): the per-slice
 // percentiles of vnd_level.hpp over the last W frames of every voice, the signal arriving block by block, the position per
 // slot in the device state and a count and start / end flags per slot and call.
-// (one translation unit: included by vnd_amd.hip after vnd_level.hpp, vnd_voice_core.hpp and vnd_scope_voice_stream.hpp)
+// (one translation unit: included by vnd_amd.hip after vnd_level.hpp, vnd_voice_core.hpp and vnd_voice_window.hpp)
 //
 // Percentiles of blocks do not add up, so the state keeps the window itself: per slot a ring of keys and a ring of slices,
 // entry g mod W what level_stage_kernel would stage for the voice's frame g - through level_frame, the one function both
 // kernels call.  An order statistic does not depend on the order of its multiset: the select runs over the ring as it lies.
 //
 // PUSH, two launches on the caller's stream, grids fixed by (slots, M):
-//   level_voice_stage_kernel, grid (ceil(M / kScopeVoiceSpan), slots), 256 threads: idle slots, bad slots and workgroups past
-//     n leave before the edges are staged.  Frame j of the chunk is the voice's frame g = p + j; the lane writes its key and
-//     slice to entry g mod W.  It reads nothing of the rings.
+//   level_voice_stage_kernel, the walk of vnd_voice_window.hpp: idle slots, bad slots and workgroups past n leave before the
+//     edges are staged.  Frame j of the chunk is the voice's frame g = p + j; the lane writes its key and slice to entry
+//     g mod W.  It reads nothing of the rings.
 //   voice_advance_kernel<LevelVoiceArgs<T>> (vnd_voice_core.hpp) writes valid[b] and pos[b]; the slot's advance() also writes
 //     fill[b] = min(p + n, W), by the same lane, for a slot that answers 1.
-// The slot rule is scope_voice_span's (vnd_scope_voice_stream.hpp) as it stands; its `clear` is not used: nothing is cleared.
+// The slot rule is scope_voice_span's (vnd_voice_window.hpp) as it stands; its `clear` is not used: nothing is cleared.
 //
 // LEVELS, a pure function of the state: a memset of bin_counts, level_voice_count_kernel (grid (ceil(W / span), slots): the
 // slices of ring entries [0, fill) counted in LDS through level_count and added to bin_counts), then level_run_select of
 // vnd_level.hpp with LevelArgs pointing keys / bins at the rings, n_frames = W and n_each = fill - scope_span's rule for
 // n_each makes a fill outside [0, W] no frames at all.
 //
-// Ring.  M <= W, so the frames [p, p + n) of one call have n <= W distinct residues mod W: every ring entry a call touches is
-// written by the one lane that owns its frame.  fill is a prefix length: a voice that has pushed q < W frames owns [0, q),
-// one that has pushed more owns the whole ring; what lies beyond fill is a previous voice's and is never read.
-//
-// Every index that is built from device data:
-//   - counts[b] outside [0, M], or pos[b] outside [0, 2^60] without START: the span is not ok and both kernels leave before
-//     anything is addressed with it (the advance kernel writes valid[b] = -1 only) - so 0 <= p <= 2^60, 0 <= n <= M;
-//   - chunk frames: j < n, so [0, n) of row b;
-//   - ring entries: (p + j0) mod W in [0, W) plus a lane offset j - j0 < n <= W, one wrap;
-//   - fill[b] and the staged slices, in the levels kernels: scope_span and the `k < bins` compare of vnd_level.hpp.
+// Ring: the argument of vnd_voice_window.hpp, with the slot rule and the indices built from device data.  What is this pool's:
+// fill is a prefix length - a voice that has pushed q < W frames owns [0, q), one that has pushed more owns the whole ring;
+// what lies beyond fill is a previous voice's and is never read - and fill[b] and the staged slices meet, in the levels
+// kernels, scope_span and the `k < bins` compare of vnd_level.hpp.
 #pragma once
 #include "../../include/vnd_polar_level_voice_stream.h"
 
@@ -59,12 +53,8 @@ __global__ __launch_bounds__(kScopeVoiceThreads) void level_voice_stage_kernel(c
 {
     extern __shared__ __attribute__((aligned(16))) double level_voice_lds[];
     const int64_t b = blockIdx.y;
-    const ScopeVoiceSpan s = scope_voice_span(vnd::uniform_i64(a.pos[b]), __builtin_amdgcn_readfirstlane(a.counts[b]),
-                                              __builtin_amdgcn_readfirstlane(a.flags[b]), a.M);
-    if (s.valid != 1) return;                                     // idle or bad: nothing is addressed with the values
-    const int64_t j0 = (int64_t)blockIdx.x * kScopeVoiceSpan;
-    if (j0 >= s.n) return;                                        // (workgroup-uniform, before any barrier)
-    const int64_t j1 = j0 + kScopeVoiceSpan < s.n ? j0 + kScopeVoiceSpan : s.n;
+    VoiceWindowWalk w;
+    if (!w.open(a.pos, a.counts, a.flags, a.M, b, blockIdx.x)) return;
     const int bins = a.s.bins0;
     double *e = level_voice_lds;
     for (int i = threadIdx.x; i <= bins; i += kScopeVoiceThreads) e[i] = a.s.e0[i];
@@ -74,14 +64,13 @@ __global__ __launch_bounds__(kScopeVoiceThreads) void level_voice_stage_kernel(c
     const T *__restrict__ pr = a.s.r + b * a.s.stream_stride;
     typename ScopeKind<T>::Bits *__restrict__ keys = a.keys + b * a.W;
     unsigned short *__restrict__ kb = a.bins + b * a.W;
-    const int64_t slot0 = (s.p + j0) % a.W;                       // uniform
-    for (int64_t j = j0 + threadIdx.x; j < j1; j += kScopeVoiceThreads) {
+    w.enter(a.W);
+    for (int64_t j = w.j0 + threadIdx.x; j < w.j1; j += kScopeVoiceThreads) {
         T l, r;
         scope_load(a.s, pl, pr, j, l, r);
         typename ScopeKind<T>::Bits key;
         const int k = level_frame(l, r, a.s.ms != 0, a.s.fold != 0, a.s.scale, e, bins, inv, key);
-        int64_t slot = slot0 + (j - j0);                          // j - j0 < n <= M <= W: one wrap
-        if (slot >= a.W) slot -= a.W;
+        const int64_t slot = w.entry(j);
         keys[slot] = key;
         kb[slot] = k < 0 ? kLevelNoBin : (unsigned short)k;
     }
@@ -120,24 +109,13 @@ struct LevelVoicePlan {
     int64_t stage_groups, fill_at, keys_at, bins_at, need;
 };
 
-// The scalar side of the pool's checks, in the order the entries report them.
+// voice_window_plan's checks (there is no whole-voice form), then the state: the positions, the fills, the two rings.
 static vnd_status level_voice_plan(int64_t slots, int64_t max_frames_per_call, int64_t window_frames, int64_t key_bytes,
                                    LevelVoicePlan *plan)
 {
-    if (slots < 1 || max_frames_per_call < 1) return fail(VND_ERR_INVALID, "slots and max_frames_per_call must be >= 1");
-    if (max_frames_per_call > INT32_MAX)
-        return fail(VND_ERR_INVALID, "max_frames_per_call %lld above INT32_MAX: counts are int32", (long long)max_frames_per_call);
-    if (window_frames < max_frames_per_call)
-        return fail(VND_ERR_INVALID, "window_frames %lld below max_frames_per_call %lld: two frames of one call would share a ring entry",
-                    (long long)window_frames, (long long)max_frames_per_call);
-    if (slots > VND_MAX_STREAMS) return fail(VND_ERR_UNSUPPORTED, "slots %lld above %d: split the pool", (long long)slots, VND_MAX_STREAMS);
-    if (window_frames > INT32_MAX)
-        return fail(VND_ERR_UNSUPPORTED, "window_frames %lld above INT32_MAX", (long long)window_frames);
     LevelVoicePlan p{};
-    p.stage_groups = (max_frames_per_call + kScopeVoiceSpan - 1) / kScopeVoiceSpan;
-    if (p.stage_groups * slots > kScopeMaxGroups)
-        return fail(VND_ERR_UNSUPPORTED, "%lld workgroups in one launch, above 2^23: split the pool", (long long)(p.stage_groups * slots));
-    // slots < 2^16, W < 2^31, 8-byte keys: every product fits int64
+    const vnd_status st = voice_window_plan(slots, max_frames_per_call, window_frames, false, &p.stage_groups);
+    if (st != VND_OK) return st;
     p.fill_at = voice_position_bytes(slots);
     p.keys_at = p.fill_at + level_voice_pad16(slots * (int64_t)sizeof(int32_t));
     p.bins_at = p.keys_at + level_voice_pad16(slots * window_frames * key_bytes);
@@ -158,27 +136,19 @@ static vnd_status level_voice_push_dev(vnd_ctx *ctx, void *state, int64_t state_
         return fail(VND_ERR_INVALID, "null state, chunk, counts, flags, edges or valid pointer");
     if (stream_stride < 1 || frame_stride < 1) return fail(VND_ERR_INVALID, "strides must be >= 1");
     if (bins < 1) return fail(VND_ERR_INVALID, "num_bins must be >= 1");
-    if (radius_scale != radius_scale) return fail(VND_ERR_INVALID, "radius_scale is NaN");
-    if (!(radius_scale > 0.0))
-        return fail(VND_ERR_INVALID, "radius_scale %g: a voice pool needs a fixed positive scale, the per-voice maximum of a "
-                                     "later block would rescale the earlier frames", radius_scale);
-    if (!(radius_scale <= (double)std::numeric_limits<T>::max() && (T)radius_scale > (T)0))
-        return fail(VND_ERR_INVALID, "radius_scale %g is zero or infinite in the sample type", radius_scale);
-    LevelVoicePlan p{};
-    vnd_status st = level_voice_plan(slots, max_frames_per_call, window_frames, (int64_t)sizeof(Bits), &p);
+    vnd_status st = voice_window_scale<T>(radius_scale);
     if (st != VND_OK) return st;
+    LevelVoicePlan p{};
+    if ((st = level_voice_plan(slots, max_frames_per_call, window_frames, (int64_t)sizeof(Bits), &p)) != VND_OK) return st;
     if ((st = voice_state_check("level voice pool", state, state_bytes, p.need, slots)) != VND_OK) return st;
     int64_t xb = 0;
     if ((st = voice_chunk_bytes(slots, stream_stride, max_frames_per_call, frame_stride, sizeof(T), &xb)) != VND_OK) return st;
     // (a bin count above the limit is refused below; here it only must not overflow)
     const ScopeRegion outs[] = {{valid, slots * 4}, {state, p.need}};
     const ScopeRegion ins[] = {{l, xb}, {r, xb}, {edges, ((int64_t)bins + 1) * 8}, {counts, slots * 4}, {flags, slots * 4}};
-    for (const ScopeRegion &out : outs)
-        for (const ScopeRegion &in : ins)
-            if (scope_overlap(out.p, out.bytes, in.p, in.bytes))
-                return fail(VND_ERR_INVALID, "valid and the state must not overlap the chunk, the edges, counts or flags");
-    if (scope_overlap(outs[0].p, outs[0].bytes, outs[1].p, outs[1].bytes))
-        return fail(VND_ERR_INVALID, "valid and the state must not overlap one another");
+    if (const int hit = scope_clash(outs, 2, ins, 5, false))
+        return fail(VND_ERR_INVALID, "valid and the state must not overlap %s",
+                    hit == 1 ? "the chunk, the edges, counts or flags" : "one another");
     if (bins > VND_LEVEL_MAX_BINS) return fail(VND_ERR_UNSUPPORTED, "%d bins, above %d", bins, VND_LEVEL_MAX_BINS);
     if (!ctx) return fail(VND_ERR_INVALID, "null context");
     DeviceScope on(ctx->device);
@@ -229,10 +199,8 @@ static vnd_status level_voice_levels_dev(vnd_ctx *ctx, const void *state, int64_
     const int64_t cells_all = slots * bins * num_p;
     const ScopeRegion regions[] = {{levels, cells_all * (int64_t)sizeof(T)}, {bin_counts, slots * bins * 4}, {work, w.total},
                                    {state, p.need}};
-    for (int i = 0; i < 4; ++i)
-        for (int k = i + 1; k < 4; ++k)
-            if (scope_overlap(regions[i].p, regions[i].bytes, regions[k].p, regions[k].bytes))
-                return fail(VND_ERR_INVALID, "levels, bin_counts, work and the state must not overlap one another");
+    if (scope_clash(regions, 4, nullptr, 0, true))
+        return fail(VND_ERR_INVALID, "levels, bin_counts, work and the state must not overlap one another");
     if (!ctx) return fail(VND_ERR_INVALID, "null context");
     DeviceScope on(ctx->device);
     if (!on.ok) return fail(VND_ERR_HIP, "cannot select device %d", ctx->device);

@@ -270,6 +270,21 @@ static bool scope_overlap(const void *u, int64_t ub, const void *v, int64_t vb)
 
 struct ScopeRegion { const void *p; int64_t bytes; };
 
+// "These outputs overlap none of these inputs, nor one another": 0, or 1 for an output on an input and 2 for two outputs - the
+// caller has a message for each.  by_output: output i is held against the inputs and against the outputs after it before
+// output i + 1 is looked at; else every output against the inputs first.  (The order decides which message a call gets.)
+static int scope_clash(const ScopeRegion *outs, int n_out, const ScopeRegion *ins, int n_in, bool by_output)
+{
+    for (int pass = 0; pass < 2; ++pass)
+        for (int i = 0; i < n_out; ++i) {
+            for (int k = 0; pass == 0 && k < n_in; ++k)
+                if (scope_overlap(outs[i].p, outs[i].bytes, ins[k].p, ins[k].bytes)) return 1;
+            for (int k = i + 1; pass == (by_output ? 0 : 1) && k < n_out; ++k)
+                if (scope_overlap(outs[i].p, outs[i].bytes, outs[k].p, outs[k].bytes)) return 2;
+        }
+    return 0;
+}
+
 // The checks every entry shares: the pool's shape and extent (frame_bytes: what l and r each span), then the limits.
 static vnd_status scope_check_pool(const void *l, const void *r, int64_t batch, int64_t n_frames, int64_t stream_stride,
                                    int32_t frame_stride, int64_t sample_bytes, int64_t *frame_bytes)
@@ -342,14 +357,9 @@ static vnd_status scope_coords_dev(vnd_ctx *ctx, const T *l, const T *r, int64_t
     if (normalize && (st = scope_check_work(work, work_bytes, batch)) != VND_OK) return st;
     if (batch > INT64_MAX / 16 / n_frames) return fail(VND_ERR_INVALID, "buffer extents overflow");
     const int64_t ob = batch * n_frames * (int64_t)sizeof(T), wb = normalize ? batch * 8 : 0;
-    const ScopeRegion outs[] = {{radii, ob}, {thetas, ob}, {normalize ? work : nullptr, wb}};
-    for (int i = 0; i < 3; ++i) {
-        if (scope_overlap(outs[i].p, outs[i].bytes, l, fb) || scope_overlap(outs[i].p, outs[i].bytes, r, fb))
-            return fail(VND_ERR_INVALID, "radii, thetas and work must not overlap the frames");
-        for (int k = i + 1; k < 3; ++k)
-            if (scope_overlap(outs[i].p, outs[i].bytes, outs[k].p, outs[k].bytes))
-                return fail(VND_ERR_INVALID, "radii, thetas and work must not overlap one another");
-    }
+    const ScopeRegion outs[] = {{radii, ob}, {thetas, ob}, {normalize ? work : nullptr, wb}}, ins[] = {{l, fb}, {r, fb}};
+    if (const int hit = scope_clash(outs, 3, ins, 2, true))
+        return fail(VND_ERR_INVALID, "radii, thetas and work must not overlap %s", hit == 1 ? "the frames" : "one another");
     if ((st = scope_check_limits(batch, n_frames)) != VND_OK) return st;
     if ((st = scope_check_groups(batch, n_frames, kScopeCoordsSpan)) != VND_OK) return st;
     if (!ctx) return fail(VND_ERR_INVALID, "null context");
@@ -400,12 +410,8 @@ static vnd_status scope_hist_dev(vnd_ctx *ctx, const T *l, const T *r, int64_t b
     const ScopeRegion outs[] = {{counts, cb}, {by_max ? work : nullptr, wb}};
     const ScopeRegion ins[] = {{l, fb}, {r, fb}, {e0, ((int64_t)bins0 + 1) * 8}, {e1, ((int64_t)bins1 + 1) * 8},
                                {n_each, batch * 4}};
-    for (const ScopeRegion &o : outs)
-        for (const ScopeRegion &i : ins)
-            if (scope_overlap(o.p, o.bytes, i.p, i.bytes))
-                return fail(VND_ERR_INVALID, "counts and work must not overlap the frames, the edges or n_each");
-    if (scope_overlap(outs[0].p, outs[0].bytes, outs[1].p, outs[1].bytes))
-        return fail(VND_ERR_INVALID, "counts and work must not overlap one another");
+    if (const int hit = scope_clash(outs, 2, ins, 5, false))
+        return fail(VND_ERR_INVALID, "counts and work must not overlap %s", hit == 1 ? "the frames, the edges or n_each" : "one another");
     if ((st = scope_check_limits(batch, n_frames)) != VND_OK) return st;
     if (!bins_ok) return fail(VND_ERR_UNSUPPORTED, "%d x %d bins, above %d an axis", bins0, bins1, VND_SCOPE_MAX_BINS);
     if (frame_step > n_frames) frame_step = n_frames;             // frame 0 alone either way, and no product can overflow

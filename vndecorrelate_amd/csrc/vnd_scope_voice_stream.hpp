@@ -1,7 +1,7 @@
 // vnd_scope_voice_stream.hpp - the vectorscope of a voice pool (include/vnd_scope_voice_stream.h): the polar and Lissajous
 // count grids of vnd_scope.hpp with the signal arriving block by block, the position per slot in the device state and a count
 // and start / end flags per slot and call - whole-voice, or over the last W frames of each voice (a sliding window).
-// (one translation unit: included by vnd_amd.hip after vnd_scope.hpp and vnd_voice_stream.hpp)
+// (one translation unit: included by vnd_amd.hip after vnd_scope.hpp and vnd_voice_window.hpp)
 //
 // The cell of a frame is formed by scope_hist_kernel's own functions - ScopeKind<T>::sample / degrees, scope_radius, scope_bin
 // on edges staged in LDS - so a grid row is the one-shot entry's, cell for cell.  What is new is the life cycle of a row and
@@ -12,51 +12,29 @@
 //   scope_voice_clear_kernel, grid (ceil(4 cells / 16 KiB), slots): a workgroup leaves at once unless its slot answers 1 from
 //     position 0 - a START, or a voice that begins at 0 after an END or a reset; otherwise it zeroes its 16 KiB of the row with
 //     16-byte stores (4-byte stores for a head and a tail that are not 16-byte aligned).
-//   scope_voice_bin_kernel, grid (ceil(M / kScopeVoiceSpan), slots), 256 threads: idle slots, bad slots and workgroups past n
-//     leave before the edges are staged.  Frame j of the chunk is the voice's frame g = p + j.  With W > 0 the lane reads
-//     ring[g mod W] when g >= W - the cell of frame g - W - and takes one count out of it when it lies in [0, cells); then it
-//     adds one count to the new cell, if the frame has one, and stores the new cell or -1 in ring[g mod W].  Global integer
-//     atomics: the direct route of vnd_scope.hpp (DESIGN.md 3.25 says why not the LDS-private one).
+//   scope_voice_bin_kernel, the walk of vnd_voice_window.hpp: idle slots, bad slots and workgroups past n leave before the
+//     edges are staged.  Frame j of the chunk is the voice's frame g = p + j.  With W > 0 the lane reads ring[g mod W] when
+//     g >= W - the cell of frame g - W - and takes one count out of it when it lies in [0, cells); then it adds one count
+//     to the new cell, if the frame has one, and stores the new cell or -1 in ring[g mod W].  Global integer atomics: the
+//     direct route of vnd_scope.hpp (DESIGN.md 3.25 says why not the LDS-private one).
 //   voice_advance_kernel<ScopeVoiceArgs<T>> (vnd_voice_core.hpp) writes valid[b] and pos[b].
 // The kernel boundaries are the ordering clear -> bin -> advance: every read of pos[b] comes before its update, and every
 // count of a call lands on a cleared row (vnd_voice_core.hpp, ORDERING).
 //
-// Ring.  M <= W, so the frames [p, p + n) of one call have n <= W distinct residues mod W: every ring entry a call touches is
-// read and written by the one lane that owns its frame, and no lane races another although the workgroups of a slot are
-// unordered.  An entry is read only for g >= W, when frame g - W of THIS voice wrote it: the ring is never cleared.
-//
-// Every index that is built from device data:
-//   - counts[b] outside [0, M], or pos[b] outside [0, 2^60] without START: the span is not ok and all three kernels leave
-//     before anything is addressed with it (the advance kernel writes valid[b] = -1 only) - so 0 <= p <= 2^60, 0 <= n <= M;
-//   - chunk frames: j < n, so [0, n) of row b;
-//   - ring entries: (p + j0) mod W in [0, W) plus a lane offset j - j0 < n <= W, one wrap;
-//   - a new cell is k0 * bins1 + k1 with both bins from scope_bin, in [0, cells); a cell READ from the ring is used only when
-//     it lies in [0, cells), whatever the state holds.
+// Ring: the argument of vnd_voice_window.hpp, with the slot rule and the indices built from device data.  What is this pool's:
+// an entry is read only for g >= W, when frame g - W of THIS voice wrote it, so the ring is never cleared; a new cell is
+// k0 * bins1 + k1 with both bins from scope_bin, in [0, cells); a cell READ from the ring is used only when it lies in
+// [0, cells), whatever the state holds.
 #pragma once
 #include "../../include/vnd_scope_voice_stream.h"
 
-constexpr int kScopeVoiceThreads = 256;
-constexpr int64_t kScopeVoiceSpan = 1024;             // frames of one slot per workgroup of the bin kernel
 constexpr int64_t kScopeVoiceClearBytes = 16384;      // bytes of one row per workgroup of the clear kernel
-
-// One slot's side of a call, from the stored position, counts[b] and flags[b] alone.
-struct ScopeVoiceSpan : vnd::VoiceHead {
-    int32_t valid;                 // 1 answered, 0 idle (nothing is touched), -1 a bad count or position
-    bool clear;                    // answered from position 0: the row is cleared first
-};
-
-__host__ __device__ inline ScopeVoiceSpan scope_voice_span(int64_t stored, int32_t count, int32_t flags, int64_t M)
-{
-    ScopeVoiceSpan v{vnd::voice_head(stored, count, flags, M)};
-    if (!v.ok) { v.valid = -1; return v; }
-    if (count == 0 && !v.start && !v.end) return v;               // idle: next is the stored position
-    v.valid = 1;
-    v.clear = v.p == 0;
-    return v;
-}
 
 template <class T>
 struct ScopeVoiceArgs {
+    // The chunk fields of ScopeArgs<T> in this struct's own text, and the packed load below in the kernel's: with ScopeArgs<T>
+    // embedded, as LevelVoiceArgs<T> has it, the whole-voice form measured 0.2 - 1.6 % slower at 256 slots x 4800 frames
+    // (profiles/voice_window_core_rates.json); registers, LDS and occupancy were the same either way.
     const T *__restrict__ l;            // the chunk: frame t of slot b at b * stream_stride + t * frame_stride
     const T *__restrict__ r;
     int64_t stream_stride, frame_stride;
@@ -72,27 +50,19 @@ struct ScopeVoiceArgs {
     int64_t slots, M, W;
     T scale;                            // polar: radius / scale
     int32_t ms, fold, packed;           // packed: r == l + 1 on even strides, 2-element aligned - one load a frame
-    __device__ ScopeVoiceSpan span(int64_t b) const { return scope_voice_span(pos[b], counts[b], flags[b], M); }
     __device__ vnd::VoiceAnswer advance(int64_t b) const
     {
-        const ScopeVoiceSpan v = span(b);
+        const ScopeVoiceSpan v = scope_voice_span(pos[b], counts[b], flags[b], M);
         return {v.valid, v.valid == 1, v.next};
     }
 };
-
-template <class T>
-__device__ __forceinline__ ScopeVoiceSpan scope_voice_view(const ScopeVoiceArgs<T> &a, int64_t b)
-{
-    return scope_voice_span(vnd::uniform_i64(a.pos[b]), __builtin_amdgcn_readfirstlane(a.counts[b]),
-                            __builtin_amdgcn_readfirstlane(a.flags[b]), a.M);
-}
 
 // grid = (ceil(4 cells / kScopeVoiceClearBytes), slots)
 template <class T>
 __global__ __launch_bounds__(kScopeVoiceThreads) void scope_voice_clear_kernel(const ScopeVoiceArgs<T> a)
 {
     const int64_t b = blockIdx.y;
-    const ScopeVoiceSpan s = scope_voice_view(a, b);
+    const ScopeVoiceSpan s = scope_voice_view(a.pos, a.counts, a.flags, a.M, b);
     if (s.valid != 1 || !s.clear) return;                         // (workgroup-uniform)
     constexpr int64_t kPer = kScopeVoiceClearBytes / 4;
     const int64_t cells = (int64_t)a.bins0 * a.bins1;
@@ -115,23 +85,21 @@ __global__ __launch_bounds__(kScopeVoiceThreads) void scope_voice_bin_kernel(con
     using K = ScopeKind<T>;
     extern __shared__ __attribute__((aligned(16))) double scope_voice_lds[];
     const int64_t b = blockIdx.y;
-    const ScopeVoiceSpan s = scope_voice_view(a, b);
-    if (s.valid != 1) return;                                     // idle or bad: nothing is addressed with the values
-    const int64_t j0 = (int64_t)blockIdx.x * kScopeVoiceSpan;
-    if (j0 >= s.n) return;                                        // (workgroup-uniform, before any barrier)
-    const int64_t j1 = j0 + kScopeVoiceSpan < s.n ? j0 + kScopeVoiceSpan : s.n;
-    double *e0 = scope_voice_lds, *e1 = scope_voice_lds + (a.bins0 + 1);
-    for (int i = threadIdx.x; i <= a.bins0; i += kScopeVoiceThreads) e0[i] = a.e0[i];
-    for (int i = threadIdx.x; i <= a.bins1; i += kScopeVoiceThreads) e1[i] = a.e1[i];
+    VoiceWindowWalk w;
+    if (!w.open(a.pos, a.counts, a.flags, a.M, b, blockIdx.x)) return;
+    const int bins0 = a.bins0, bins1 = a.bins1;
+    double *e0 = scope_voice_lds, *e1 = scope_voice_lds + (bins0 + 1);
+    for (int i = threadIdx.x; i <= bins0; i += kScopeVoiceThreads) e0[i] = a.e0[i];
+    for (int i = threadIdx.x; i <= bins1; i += kScopeVoiceThreads) e1[i] = a.e1[i];
     __syncthreads();
-    const double inv0 = (double)a.bins0 / (e0[a.bins0] - e0[0]), inv1 = (double)a.bins1 / (e1[a.bins1] - e1[0]);
-    const int cells = a.bins0 * a.bins1;
+    const double inv0 = (double)bins0 / (e0[bins0] - e0[0]), inv1 = (double)bins1 / (e1[bins1] - e1[0]);
+    const int cells = bins0 * bins1;
     const T *__restrict__ pl = a.l + b * a.stream_stride;
     const T *__restrict__ pr = a.r + b * a.stream_stride;
     unsigned int *__restrict__ out = a.grid + b * (int64_t)cells;
     int32_t *__restrict__ ring = a.W > 0 ? a.ring + b * a.W : nullptr;
-    const int64_t slot0 = a.W > 0 ? (s.p + j0) % a.W : 0;         // uniform
-    for (int64_t j = j0 + threadIdx.x; j < j1; j += kScopeVoiceThreads) {
+    if (ring) w.enter(a.W);
+    for (int64_t j = w.j0 + threadIdx.x; j < w.j1; j += kScopeVoiceThreads) {
         const int64_t i = j * a.frame_stride;
         T l, r;
         if (a.packed) {
@@ -151,15 +119,14 @@ __global__ __launch_bounds__(kScopeVoiceThreads) void scope_voice_bin_kernel(con
             v1 = (double)r;
         }
         int c = -1;
-        const int k0 = scope_bin(e0, a.bins0, inv0, v0);
+        const int k0 = scope_bin(e0, bins0, inv0, v0);
         if (k0 >= 0) {
-            const int k1 = scope_bin(e1, a.bins1, inv1, v1);
-            if (k1 >= 0) c = k0 * a.bins1 + k1;
+            const int k1 = scope_bin(e1, bins1, inv1, v1);
+            if (k1 >= 0) c = k0 * bins1 + k1;
         }
         if (ring) {
-            int64_t slot = slot0 + (j - j0);                      // j - j0 < n <= M <= W: one wrap
-            if (slot >= a.W) slot -= a.W;
-            if (s.p + j >= a.W) {                                 // frame g - W of this voice leaves the window
+            const int64_t slot = w.entry(j);
+            if (w.s.p + j >= a.W) {                               // frame g - W of this voice leaves the window
                 const int32_t old = ring[slot];
                 if (old >= 0 && old < cells) atomicSub(out + old, 1u);
             }
@@ -175,24 +142,12 @@ struct ScopeVoicePlan {
     int64_t bin_groups, ring_at, need;
 };
 
-// The scalar side of the pool's checks, in the order the entries report them.
+// voice_window_plan's checks (window_frames = 0: whole-voice), then the state: the positions, the ring.
 static vnd_status scope_voice_plan(int64_t slots, int64_t max_frames_per_call, int64_t window_frames, ScopeVoicePlan *plan)
 {
-    if (slots < 1 || max_frames_per_call < 1) return fail(VND_ERR_INVALID, "slots and max_frames_per_call must be >= 1");
-    if (max_frames_per_call > INT32_MAX)
-        return fail(VND_ERR_INVALID, "max_frames_per_call %lld above INT32_MAX: counts are int32", (long long)max_frames_per_call);
-    if (window_frames < 0) return fail(VND_ERR_INVALID, "window_frames %lld below 0", (long long)window_frames);
-    if (window_frames > 0 && window_frames < max_frames_per_call)
-        return fail(VND_ERR_INVALID, "window_frames %lld below max_frames_per_call %lld: two frames of one call would share a ring entry",
-                    (long long)window_frames, (long long)max_frames_per_call);
-    if (slots > VND_MAX_STREAMS) return fail(VND_ERR_UNSUPPORTED, "slots %lld above %d: split the pool", (long long)slots, VND_MAX_STREAMS);
-    if (window_frames > INT32_MAX)
-        return fail(VND_ERR_UNSUPPORTED, "window_frames %lld above INT32_MAX", (long long)window_frames);
     ScopeVoicePlan p{};
-    p.bin_groups = (max_frames_per_call + kScopeVoiceSpan - 1) / kScopeVoiceSpan;
-    if (p.bin_groups * slots > kScopeMaxGroups)
-        return fail(VND_ERR_UNSUPPORTED, "%lld workgroups in one launch, above 2^23: split the pool", (long long)(p.bin_groups * slots));
-    // slots < 2^16, W < 2^31: the product fits int64
+    const vnd_status st = voice_window_plan(slots, max_frames_per_call, window_frames, true, &p.bin_groups);
+    if (st != VND_OK) return st;
     p.ring_at = voice_position_bytes(slots);
     p.need = p.ring_at + ((slots * window_frames * (int64_t)sizeof(int32_t) + 15) & ~(int64_t)15);
     *plan = p;
@@ -210,17 +165,10 @@ static vnd_status scope_voice_stream_dev(vnd_ctx *ctx, void *state, int64_t stat
         return fail(VND_ERR_INVALID, "null state, chunk, counts, flags, edges, grid or valid pointer");
     if (stream_stride < 1 || frame_stride < 1) return fail(VND_ERR_INVALID, "strides must be >= 1");
     if (bins0 < 1 || bins1 < 1) return fail(VND_ERR_INVALID, "bin counts must be >= 1");
-    if (POLAR) {
-        if (radius_scale != radius_scale) return fail(VND_ERR_INVALID, "radius_scale is NaN");
-        if (!(radius_scale > 0.0))
-            return fail(VND_ERR_INVALID, "radius_scale %g: a voice pool needs a fixed positive scale, the per-voice maximum of a "
-                                         "later block would rescale the earlier frames", radius_scale);
-        if (!(radius_scale <= (double)std::numeric_limits<T>::max() && (T)radius_scale > (T)0))
-            return fail(VND_ERR_INVALID, "radius_scale %g is zero or infinite in the sample type", radius_scale);
-    }
+    vnd_status st = VND_OK;
+    if (POLAR && (st = voice_window_scale<T>(radius_scale)) != VND_OK) return st;
     ScopeVoicePlan p{};
-    vnd_status st = scope_voice_plan(slots, max_frames_per_call, window_frames, &p);
-    if (st != VND_OK) return st;
+    if ((st = scope_voice_plan(slots, max_frames_per_call, window_frames, &p)) != VND_OK) return st;
     if ((st = voice_state_check("scope voice pool", state, state_bytes, p.need, slots)) != VND_OK) return st;
     if ((uintptr_t)grid % 4 != 0) return fail(VND_ERR_INVALID, "the grid is not 4-byte aligned");
     int64_t xb = 0;
@@ -232,14 +180,9 @@ static vnd_status scope_voice_stream_dev(vnd_ctx *ctx, void *state, int64_t stat
     const ScopeRegion outs[] = {{grid, slots * cells * 4}, {valid, slots * 4}, {state, p.need}};
     const ScopeRegion ins[] = {{l, xb}, {r, xb}, {e0, ((int64_t)bins0 + 1) * 8}, {e1, ((int64_t)bins1 + 1) * 8}, {counts, slots * 4},
                                {flags, slots * 4}};
-    for (int i = 0; i < 3; ++i) {
-        for (const ScopeRegion &in : ins)
-            if (scope_overlap(outs[i].p, outs[i].bytes, in.p, in.bytes))
-                return fail(VND_ERR_INVALID, "grid, valid and the state must not overlap the chunk, the edges, counts or flags");
-        for (int k = i + 1; k < 3; ++k)
-            if (scope_overlap(outs[i].p, outs[i].bytes, outs[k].p, outs[k].bytes))
-                return fail(VND_ERR_INVALID, "grid, valid and the state must not overlap one another");
-    }
+    if (const int hit = scope_clash(outs, 3, ins, 6, true))
+        return fail(VND_ERR_INVALID, "grid, valid and the state must not overlap %s",
+                    hit == 1 ? "the chunk, the edges, counts or flags" : "one another");
     if (!bins_ok) return fail(VND_ERR_UNSUPPORTED, "%d x %d bins, above %d an axis", bins0, bins1, VND_SCOPE_MAX_BINS);
     const int64_t clear_groups = (cells * 4 + kScopeVoiceClearBytes - 1) / kScopeVoiceClearBytes;
     if (clear_groups * slots > kScopeMaxGroups)

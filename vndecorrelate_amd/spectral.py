@@ -25,13 +25,12 @@ from typing import Optional
 import numpy as np
 
 from . import _native
-from .streaming import _SlotPool, _check_counts, _check_slots, _slot_ints, _voice_head
+from .streaming import _INT32_MAX, _MeterPool, _slot_ints, _SlotPool, _voice_head
 
 MIN_NFFT = _native.SPECTRUM_MIN_NFFT
 MAX_NFFT = _native.SPECTRUM_MAX_NFFT
 RUN = _native.SPECTRUM_RUN                              # the most consecutive segments a workgroup owns
 _MAX_BATCH = 65535                                      # VND_MAX_STREAMS
-_MAX_FRAMES = 2 ** 31 - 1
 _MAX_GROUPS = 2 ** 23
 _MAX_ELEMENTS = 2 ** 59
 _torch = _native.torch_module
@@ -99,7 +98,7 @@ def spectrum_covers(dtype, batch: int, n_frames: int, channels: int = 1, nperseg
         return False
     if not MIN_NFFT <= nfft <= MAX_NFFT or nfft & (nfft - 1):
         return False
-    if not 2 <= nperseg <= nfft or not 0 <= noverlap < nperseg or not nperseg <= n_frames <= _MAX_FRAMES:
+    if not 2 <= nperseg <= nfft or not 0 <= noverlap < nperseg or not nperseg <= n_frames <= _INT32_MAX:
         return False
     if not (detrend is False or (isinstance(detrend, str) and detrend == 'constant')):
         return False
@@ -542,7 +541,7 @@ def spectrum_voice_spans(positions, counts, flags, nperseg: int, hop: int, max_f
     return out, segments, new
 
 
-class SpectrumVoicePool(_SlotPool):
+class SpectrumVoicePool(_MeterPool):
     """``scipy.signal.spectrogram`` columns and the Welch means ``Pxx``, ``Pyy``, ``Pxy`` of ``slots`` voices, each with a
     life of its own (:func:`spectrum_voice_pool`, ``vnd_spectrum_voice_stream_*_dev``): voices start and end on any call and
     push blocks of any size up to ``max_frames_per_call`` or none.  The position lives in the device state, one per slot,
@@ -568,16 +567,8 @@ class SpectrumVoicePool(_SlotPool):
 
     def __init__(self, slots: int, max_frames_per_call: int, *, fs=1.0, window='hann', nperseg=256, noverlap=None, nfft=None,
                  detrend='constant', scaling='density', channels: int = 2, dtype='float32', columns: bool = True):
-        _check_counts(slots=slots, max_frames_per_call=max_frames_per_call)
-        _check_slots(slots)
-        if max_frames_per_call > _MAX_FRAMES:
-            raise ValueError(f'max_frames_per_call {max_frames_per_call} above 2**31 - 1: counts are int32')
-        try:
-            parsed = None if dtype is None else np.dtype(dtype)
-        except TypeError:
-            parsed = None
-        if parsed is None or parsed.name not in ('float32', 'float64'):
-            raise ValueError(f"dtype must be 'float32' or 'float64', got {dtype!r}")
+        _MeterPool.__init__(self, slots, max_frames_per_call, dtype)
+        parsed = self.dtype
         if isinstance(channels, (bool, np.bool_)) or channels not in (1, 2):
             raise ValueError(f'channels must be 1 or 2, got {channels!r}')
         if not isinstance(columns, (bool, np.bool_)):
@@ -591,8 +582,7 @@ class SpectrumVoicePool(_SlotPool):
             raise ValueError(f'nperseg {nperseg!r}, noverlap {noverlap!r}, nfft {nfft!r}, detrend {detrend!r}, scaling '
                              f'{scaling!r} and this window have no device form (spectrum_covers is False) and the pool has '
                              f'no SciPy one: use spectrogram_batched / coherence_batched')
-        self.dtype = parsed
-        self.slots, self.max_frames_per_call, self.in_channels = int(slots), int(max_frames_per_call), int(channels)
+        self.in_channels = int(channels)
         self.fs, self.window, self.detrend, self.scaling = fs, window, detrend, scaling
         self.nperseg, self.noverlap, self.nfft = int(nperseg), int(noverlap), int(nfft)
         self.hop = self.nperseg - self.noverlap
@@ -609,11 +599,9 @@ class SpectrumVoicePool(_SlotPool):
                 or self.slots * self.rows_per_call * self.in_channels * self.bins > 1 << 40:
             raise ValueError(f'{self.slots} slots of {self.rows_per_call} segments of {self.bins} bins per call are more than '
                              f'one launch takes: raise the hop or lower max_frames_per_call')
-        self.transfers = {'to_device': 0, 'to_host': 0}
-        self._state = None                    # (torch uint8 tensor, bytes)
         self.pxx = self.pyy = self.pxy = self.segments = None
         S, C = self.slots, self.in_channels
-        self._block_dtype = self._out_dtype = parsed.type
+        self._out_dtype = parsed.type
         self._inputs = (('y', (S, self.max_frames_per_call, C), parsed.name, None),) + _slot_ints(S, 'counts', 'flags')
         self._outputs = (('columns', (S, self.rows_per_call if self.columns else 0, C, self.bins), parsed.name, 'empty'),
                          ('out_counts', (S,), 'int32', 'empty'))
@@ -685,15 +673,6 @@ class SpectrumVoicePool(_SlotPool):
         out, _, new = spectrum_voice_spans(self.positions, counts, flags, self.nperseg, self.hop, self.max_frames_per_call)
         return out, new
 
-    def _per_slot(self, tables):
-        return ()
-
-    def _bank_len(self) -> int:
-        return 1                                  # a voice starts with nothing of its own: the pool has one setting
-
-    def _slot_value(self, index: int):
-        return 0
-
     # ---- the device -------------------------------------------------------------------------
     def _allocate(self, torch, ctx):
         """The means at their fixed addresses and the tables of the transform, then the state."""
@@ -717,10 +696,6 @@ class SpectrumVoicePool(_SlotPool):
         _native.spectrum_voice_stream_reset_device(ctx, state_ptr, state_bytes, self.slots, self.in_channels, self.nperseg,
                                                    self.hop, self.nfft, self.max_frames_per_call, self.dtype == np.float64,
                                                    stream=stream)
-
-    def _call_host(self, x, counts, flags):
-        """One upload (the blocks and the two int32 arrays in one buffer), the call, one download (columns, out_counts)."""
-        return self._call_host_packed(x, (counts, flags))
 
     def _launch(self, ctx, state_ptr, state_bytes, inputs, cols, out_counts, stream):
         y, counts, flags = inputs

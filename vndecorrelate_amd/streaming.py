@@ -634,6 +634,23 @@ def voice_spans(positions, counts, flags, latency: int, max_frames_per_call: Opt
     return out, new
 
 
+def _valid_voice_spans(positions, counts, flags, max_frames_per_call: Optional[int] = None):
+    """``(valid, new_positions)`` of one call of a pool that answers ``valid`` (``analysis.polar_voice_spans``,
+    ``vectorscope.scope_voice_spans``), per slot, from the positions before the call, the frames pushed and the
+    ``VOICE_START`` / ``VOICE_END`` flags alone - what the device computes from its own state::
+
+        p = START ? 0 : position      valid = 1, or 0 for n = 0 without a flag      new position = END ? 0 : p + n
+
+    A count below 0 (or above ``max_frames_per_call``, when given), or without START a position outside ``[0, 2^60]``,
+    answers -1 and leaves the position as it was."""
+    pos, n, start, end, p, bad = _voice_head(positions, counts, flags, max_frames_per_call)
+    idle = ~bad & (n == 0) & ~start & ~end
+    p, n = np.where(bad, 0, p), np.where(bad, 0, n)          # (no arithmetic on a bad value)
+    valid = np.where(bad, -1, np.where(idle, 0, 1)).astype(np.int64)
+    new = np.where(bad | idle, pos, np.where(end, 0, p + n)).astype(np.int64)
+    return valid, new
+
+
 def _check_slots(slots: int):
     if slots > _native.MAX_STREAMS_PER_CALL:
         raise ValueError(f'slots {slots} above {_native.MAX_STREAMS_PER_CALL}: split the pool')
@@ -657,12 +674,12 @@ def _check_device_tensors(tensors, specs):
 
 
 class _SlotPool:
-    """What the voice pools share (:class:`VoicePool`, :class:`HaasVoicePool`, :class:`ChainVoicePool` and the two meters
-    of ``analysis.py``): the host's mirror of the slots, ``reset()``, the dict form ``process`` with every refusal before
-    the device, the state and the device form.  A pool sets ``slots``, ``in_channels``, ``max_frames_per_call``,
-    ``_state = None`` and the spec of its device tensors - ``_inputs`` and its two ``_outputs``, ``(name, shape, dtype,
-    fill)`` each, ``fill`` None for an input and ``'empty'`` or ``'zeros'``, how an absent one is allocated, for an
-    output - calls ``_mirror()``, and supplies the hooks below and ``_call_host``."""
+    """What the voice pools share (:class:`VoicePool`, :class:`HaasVoicePool`, :class:`ChainVoicePool` and, through
+    :class:`_MeterPool`, the five meters of ``analysis.py``, ``spectral.py`` and ``vectorscope.py``): the host's mirror of
+    the slots, ``reset()``, the dict form ``process`` with every refusal before the device, the state and the device form.
+    A pool sets ``slots``, ``in_channels``, ``max_frames_per_call``, ``_state = None`` and the spec of its device tensors
+    - ``_inputs`` and its two ``_outputs``, ``(name, shape, dtype, fill)`` each, ``fill`` None for an input and
+    ``'empty'`` or ``'zeros'``, how an absent one is allocated, for an output - calls ``_mirror()``, and supplies the hooks below and ``_call_host``."""
 
     def _mirror(self):
         """The host's copy of what the device state says, for the dict form: all slots idle at position 0."""
@@ -717,6 +734,7 @@ class _SlotPool:
     _out_dtype = np.float32
     _out_width = 2                            # the last axis of what a slot returns
     _block_dtype = np.float32                 # what a voice pushes
+    _own = None                               # (buffer, first, second): the outputs of a pool that keeps them, once allocated
 
     def _spans(self, counts, flags, tables):
         """``(out_counts, new positions)`` of the call, from the host mirror."""
@@ -827,26 +845,27 @@ class _SlotPool:
         state, state_bytes = self._state
         self._reset_entry(ctx, state.data_ptr(), state_bytes, torch.cuda.current_stream(state.device).cuda_stream)
 
-    def _process_dev(self, inputs, out):
-        """``process_dev``: the form guard and the look at the tensors (no device memory is read), then the call."""
+    def _process_dev(self, inputs, out=None, *, valid=None):
+        """``process_dev``: the form guard and the look at the tensors (no device memory is read), then the call.  ``out``:
+        the caller's two outputs; ``valid``: the caller's second output alone, for a pool that keeps the first."""
         if self._form == 'dict':
             self._require_form('dev')
         _check_device_tensors(inputs, self._inputs)
-        if out is None:
-            return self._call_device(_native.torch_module(), inputs, None, None)
-        first, second = out
-        _check_device_tensors(out, self._outputs)
+        first, second = (None, valid) if out is None else out
+        _check_device_tensors((first, second), self._outputs)
         return self._call_device(_native.torch_module(), inputs, first, second)
 
     def _call_device(self, torch, inputs, first, second):
         """One device call on the current stream: the tuple of input tensors and the two outputs, each a tensor or None
-        (None: allocated here).  Returns the outputs."""
+        (None: the pool's own if it keeps its outputs, else allocated here).  Returns the outputs."""
         ctx = _native.default_context()
         device = torch.device('cuda', ctx.device)
         for t in inputs:
             if t.device != device:
                 raise ValueError(f'tensor on {t.device}, the pool runs on {device}')
         state, state_bytes = self._ensure_state(torch, ctx)
+        if self._own is not None:
+            first, second = self._own[1], self._own[2] if second is None else second
         if first is None:
             first = self._new_output(torch, device, *self._outputs[0])
         if second is None:
@@ -859,33 +878,115 @@ class _SlotPool:
     def _new_output(torch, device, name, shape, dtype, fill):
         return getattr(torch, fill)(shape, dtype=getattr(torch, dtype), device=device)
 
-    def _call_host_packed(self, x, ints):
+    def _packed_outputs(self, torch, device, allocate):
+        """``(buffer, first, second)``: both outputs in one uint8 buffer from ``allocate``, the first, then the second
+        (int32 after a multiple of 4 bytes) - one copy brings both down."""
+        (_, shape0, dtype0, _), (_, shape1, dtype1, _) = self._outputs
+        bytes0 = int(np.prod(shape0)) * np.dtype(dtype0).itemsize
+        bytes1 = int(np.prod(shape1)) * np.dtype(dtype1).itemsize
+        down = allocate((bytes0 + bytes1,), dtype=torch.uint8, device=device)
+        return (down, down[:bytes0].view(getattr(torch, dtype0)).view(shape0),
+                down[bytes0:].view(getattr(torch, dtype1)).view(shape1))
+
+    def _call_host_packed(self, x, ints, first: bool = True):
         """A ``_call_host`` on the device form: one upload (the blocks and the int32 arrays ``ints`` in one buffer), the
-        call, one download (the pool's outputs in one buffer); ``transfers`` counts them.  ``_form`` stays as it was."""
+        call, one download (the pool's outputs in one buffer - its own at its fixed address if it keeps them, else a fresh
+        one; without ``first`` the second output alone, and None for the first); ``transfers`` counts them.  ``_form``
+        stays as it was."""
         torch = _native.torch_module()
-        device = torch.device('cuda', _native.default_context().device)
+        ctx = _native.default_context()
+        device = torch.device('cuda', ctx.device)
+        self._ensure_state(torch, ctx)
         ints = np.stack(ints).astype(np.int32)
         up = torch.from_numpy(np.concatenate([x.reshape(-1).view(np.uint8), ints.reshape(-1).view(np.uint8)])).to(device)
         self.transfers = {'to_device': 1, 'to_host': 0}
         x_dev = up[:x.nbytes].view(getattr(torch, x.dtype.name)).view(x.shape)
         int_rows = up[x.nbytes:].view(torch.int32).view(len(ints), self.slots)
-        # the download buffer: the first output, then the second (int32 after a multiple of 8 bytes); zeroed as a whole
-        # if the pool wants either output zero-filled
+        # the download buffer: zeroed as a whole if the pool wants either output zero-filled
         (_, shape0, dtype0, fill0), (_, shape1, dtype1, fill1) = self._outputs
-        bytes0 = int(np.prod(shape0)) * np.dtype(dtype0).itemsize
-        bytes1 = int(np.prod(shape1)) * np.dtype(dtype1).itemsize
-        allocate = torch.zeros if 'zeros' in (fill0, fill1) else torch.empty
-        down = allocate((bytes0 + bytes1,), dtype=torch.uint8, device=device)
-        out0 = down[:bytes0].view(getattr(torch, dtype0)).view(shape0)
-        out1 = down[bytes0:].view(getattr(torch, dtype1)).view(shape1)
+        down, out0, out1 = self._own or self._packed_outputs(torch, device,
+                                                             torch.zeros if 'zeros' in (fill0, fill1) else torch.empty)
         form = self._form
         try:
             self._call_device(torch, (x_dev, *int_rows), out0, out1)
         finally:
             self._form = form
-        host = down.cpu().numpy()
+        host = (down if first else out1).cpu().numpy()
         self.transfers['to_host'] = 1
-        return host[:bytes0].view(dtype0).reshape(shape0), host[bytes0:].view(dtype1).reshape(shape1)
+        if not first:
+            return None, host
+        cut = host.nbytes - out1.numel() * out1.element_size()
+        return host[:cut].view(dtype0).reshape(shape0), host[cut:].view(dtype1).reshape(shape1)
+
+
+_INT32_MAX = 2 ** 31 - 1
+
+
+def _sample_dtype(dtype) -> np.dtype:
+    """A meter's ``dtype`` argument as a NumPy dtype: float32 or float64, else ``ValueError``."""
+    try:
+        parsed = None if dtype is None else np.dtype(dtype)                       # (np.dtype(None) is float64)
+    except TypeError:
+        parsed = None
+    if parsed is None or parsed.name not in ('float32', 'float64'):
+        raise ValueError(f"dtype must be 'float32' or 'float64', got {dtype!r}")
+    return parsed
+
+
+class _MeterPool(_SlotPool):
+    """What the meters share (``analysis.CorrelogramVoicePool`` and ``PolarVoicePool``, ``spectral.SpectrumVoicePool``,
+    ``vectorscope.ScopeVoicePool`` and ``LevelVoicePool``): a meter is a pool whose voices start with nothing of their own.
+    It takes ``start`` as a list of slots, pushes stereo frames of its ``dtype`` (float32 or float64) with int32 counts,
+    and unless it says otherwise answers ``valid`` in {-1, 0, 1} by :func:`_valid_voice_spans`."""
+
+    in_channels = 2
+
+    def __init__(self, slots: int, max_frames_per_call: int, dtype):
+        _check_counts(slots=slots, max_frames_per_call=max_frames_per_call)
+        _check_slots(slots)
+        if max_frames_per_call > _INT32_MAX:
+            raise ValueError(f'max_frames_per_call {max_frames_per_call} above 2**31 - 1: counts are int32')
+        self.dtype = _sample_dtype(dtype)
+        self.slots, self.max_frames_per_call = int(slots), int(max_frames_per_call)
+        self._block_dtype = self.dtype            # what _schedule holds every block to
+        self.transfers = {'to_device': 0, 'to_host': 0}
+        self._state = None                    # (torch uint8 tensor, bytes)
+
+    def _process_valid(self, blocks, start, end, discard: bool, row, *host_args):
+        """The dict form of a meter that answers ``valid``: every slot that got a block, started or ended and answered 1
+        (an empty block alone is idle) with ``row(its row of the first output)``, or None without ``row``.
+        ``host_args`` go to ``_call_host`` behind x, counts and flags."""
+        self._require_form('dict')
+        starts = self._start_slots(start)
+        counts, flags, tables, live, x, answered = self._schedule(blocks, starts, end, discard)
+        answered = sorted(set(answered) | set(starts))
+        if not counts.any() and not flags.any():              # nothing pushed, started or ended: no device call
+            return {}
+        want, positions = self._spans(counts, flags, tables)
+        rows, got = self._call_host(x, counts, flags, *host_args)
+        if not np.array_equal(np.asarray(got, np.int64), want):
+            raise _native.NativeError(f'the voice pool answered {list(got)}, the spans are {list(want)}')
+        self._commit(positions)
+        self.tables, self._form = tables, 'dict'
+        live[(flags & VOICE_END) != 0] = False
+        self.live = live
+        return {slot: row(rows[slot]) if row else None for slot in answered if want[slot] == 1}
+
+    def _spans(self, counts, flags, tables):
+        return _valid_voice_spans(self.positions, counts, flags, self.max_frames_per_call)
+
+    def _per_slot(self, tables):
+        return ()
+
+    def _bank_len(self) -> int:
+        return 1                                  # a voice starts with nothing of its own: the pool has one setting
+
+    def _slot_value(self, index: int):
+        return 0
+
+    def _call_host(self, x, counts, flags):
+        """One upload (the blocks and the two int32 arrays in one buffer), the call, one download (both outputs)."""
+        return self._call_host_packed(x, (counts, flags))
 
 
 class VoicePool(_SlotPool):

@@ -34,8 +34,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native
-from .streaming import (VOICE_END, _check_counts, _check_device_tensors, _check_slots, _slot_ints, _SlotPool,
-                        _voice_head)
+from .streaming import _INT32_MAX, _check_counts, _MeterPool, _slot_ints, _SlotPool, _valid_voice_spans
 from .utils.dsp import LayoutMode, polar_coordinates
 
 MAX_BINS = _native.SCOPE_MAX_BINS
@@ -571,7 +570,6 @@ def polar_level_batched(pool, num_bins: int = 360, percentiles=(95.0, 50.0), *, 
 
 
 # ---- the vectorscope of a voice pool (include/vnd_scope_voice_stream.h) -----------------------------------------------
-_INT32_MAX = 2 ** 31 - 1
 VOICE_SPAN_FRAMES = _native.SCOPE_VOICE_SPAN_FRAMES   # frames of one slot per workgroup of the pool's bin kernel
 _VOICE_CLEAR_BYTES = 16384                            # bytes of one grid row per workgroup of its clear kernel
 
@@ -586,12 +584,7 @@ def scope_voice_spans(positions, counts, flags, max_frames_per_call: Optional[in
     A slot that answers 1 from ``p = 0`` has its grid row cleared first.  A count below 0 (or above
     ``max_frames_per_call``, when given), or without START a position outside ``[0, 2^60]``, answers -1 and leaves the
     position as it was."""
-    pos, n, start, end, p, bad = _voice_head(positions, counts, flags, max_frames_per_call)
-    idle = ~bad & (n == 0) & ~start & ~end
-    p, n = np.where(bad, 0, p), np.where(bad, 0, n)          # (no arithmetic on a bad value)
-    valid = np.where(bad, -1, np.where(idle, 0, 1)).astype(np.int64)
-    new = np.where(bad | idle, pos, np.where(end, 0, p + n)).astype(np.int64)
-    return valid, new
+    return _valid_voice_spans(positions, counts, flags, max_frames_per_call)
 
 
 def scope_voice_window(position_after: int, window_frames: Optional[int] = None):
@@ -607,7 +600,29 @@ def scope_voice_window(position_after: int, window_frames: Optional[int] = None)
     return (max(0, q - w) if w else 0), q
 
 
-class ScopeVoicePool(_SlotPool):
+def _window(window_frames, max_frames_per_call: int) -> int:
+    """A pool's ``window_frames`` against its (checked) ``max_frames_per_call``, as an int."""
+    _check_counts(window_frames=window_frames)
+    if window_frames < max_frames_per_call:
+        raise ValueError(f'window_frames {window_frames} below max_frames_per_call {max_frames_per_call}: two frames '
+                         'of one call would share a ring entry')
+    if window_frames > _INT32_MAX:
+        raise ValueError(f'window_frames {window_frames} above 2**31 - 1')
+    return int(window_frames)
+
+
+def _fixed_scale(radius_scale, dtype: np.dtype) -> float:
+    """A voice pool's ``radius_scale``: given, positive, and neither zero nor infinite in the pool's ``dtype``."""
+    if radius_scale is None:
+        raise ValueError('a voice pool needs a fixed radius_scale: the per-voice maximum of a later block would '
+                         'rescale the earlier frames')
+    scale = _scale(radius_scale, True)
+    if not 0.0 < float(dtype.type(scale)) < np.inf:
+        raise ValueError(f'radius_scale {radius_scale!r} is zero or infinite in {dtype.name}')
+    return scale
+
+
+class ScopeVoicePool(_MeterPool):
     """The vectorscope of ``slots`` voices, each with a life of its own (:func:`polar_histogram_voice_pool`,
     :func:`lissajous_histogram_voice_pool`; ``vnd_polar_hist_voice_stream_*_dev``, ``vnd_lissajous_hist_voice_stream_*_dev``):
     voices start and end on any call and push blocks of any size up to ``max_frames_per_call`` or none.  The position lives
@@ -633,53 +648,26 @@ class ScopeVoicePool(_SlotPool):
       meter with ``max_frames_per_call=pool.row_frames`` (and ``dtype='float64'`` for a Haas or chain pool) and hand it that
       pool's ``y`` and ``out_counts`` and the caller's ``flags``: a -1 of the pool is a bad count here and answers -1."""
 
-    in_channels = 2
     _out_dtype = np.float64
 
     def __init__(self, slots: int, *, max_frames_per_call: int, edges, polar: bool, window_frames: Optional[int] = None,
                  dtype='float32', radius_scale: Optional[float] = None, ms: bool = True, semicircular: bool = True):
-        from .analysis import _sample_dtype
-        _check_counts(slots=slots, max_frames_per_call=max_frames_per_call)
-        _check_slots(slots)
-        if max_frames_per_call > _INT32_MAX:
-            raise ValueError(f'max_frames_per_call {max_frames_per_call} above 2**31 - 1: counts are int32')
-        if window_frames is None:
-            window = 0
-        else:
-            _check_counts(window_frames=window_frames)
-            if window_frames < max_frames_per_call:
-                raise ValueError(f'window_frames {window_frames} below max_frames_per_call {max_frames_per_call}: two frames '
-                                 'of one call would share a ring entry')
-            if window_frames > _INT32_MAX:
-                raise ValueError(f'window_frames {window_frames} above 2**31 - 1')
-            window = int(window_frames)
-        self.dtype = _sample_dtype(dtype)
+        _MeterPool.__init__(self, slots, max_frames_per_call, dtype)
+        self.window_frames = 0 if window_frames is None else _window(window_frames, max_frames_per_call)
         self.polar = bool(polar)
-        if self.polar:
-            if radius_scale is None:
-                raise ValueError('a voice pool needs a fixed radius_scale: the per-voice maximum of a later block would '
-                                 'rescale the earlier frames')
-            self.radius_scale = _scale(radius_scale, True)
-            if not 0.0 < float(self.dtype.type(self.radius_scale)) < np.inf:
-                raise ValueError(f'radius_scale {radius_scale!r} is zero or infinite in {self.dtype.name}')
-        else:
-            self.radius_scale = None
+        self.radius_scale = _fixed_scale(radius_scale, self.dtype) if self.polar else None
         self.ms, self.semicircular = bool(ms), bool(semicircular)
         e0, e1 = (np.ascontiguousarray(e, np.float64) for e in edges)
         self.edges = (e0, e1)
         self.bins = (len(e0) - 1, len(e1) - 1)
         if not (1 <= self.bins[0] <= MAX_BINS and 1 <= self.bins[1] <= MAX_BINS):
             raise ValueError(f'{self.bins[0]} x {self.bins[1]} bins: 1 to {MAX_BINS} an axis')
-        self.slots, self.max_frames_per_call, self.window_frames = int(slots), int(max_frames_per_call), window
-        self._block_dtype = self.dtype            # what _schedule holds every block to
         # the fixed grids of the pool's launches (include/vnd_scope_voice_stream.h): 2^23 workgroups each
         cells = self.bins[0] * self.bins[1]
         groups = max(-(-self.max_frames_per_call // VOICE_SPAN_FRAMES), -(-cells * 4 // _VOICE_CLEAR_BYTES))
         if self.slots * groups > _MAX_GROUPS:
             raise ValueError(f'{self.slots} slots of {groups} workgroups are more than one launch takes: split the pool')
-        self.transfers = {'to_device': 0, 'to_host': 0}
-        self._state = None                    # (torch uint8 tensor, bytes)
-        self._grid = self._valid = self._own = self._edges_dev = None
+        self._edges_dev = None
         S = self.slots
         self._inputs = (('y', (S, self.max_frames_per_call, 2), self.dtype.name, None),) + _slot_ints(S, 'counts', 'flags')
         self._outputs = (('grid', (S,) + self.bins, 'int32', 'zeros'), ('valid', (S,), 'int32', 'empty'))
@@ -689,9 +677,9 @@ class ScopeVoicePool(_SlotPool):
     def grid(self):
         """The pool's count grids: int32 ``(slots, bins0, bins1)`` on the device, holding uint32; allocated, as zeros, with
         the state on first use."""
-        if self._grid is None:
+        if self._own is None:
             self._ensure_state(_torch(), _native.default_context())
-        return self._grid
+        return self._own[1]
 
     def process(self, blocks=None, *, start=(), end=(), discard: bool = False, grids: bool = True):
         """One call of the dict form.  ``blocks``: ``{slot: (n, 2) array of the pool's dtype}``,
@@ -702,22 +690,8 @@ class ScopeVoicePool(_SlotPool):
         slot that was never started, a start on a live slot (``discard=True`` allows it: the voice it held is dropped), a
         block above ``max_frames_per_call`` or not ``(n, 2)``; ``TypeError`` for a block of another dtype than the
         pool's."""
-        self._require_form('dict')
-        starts = self._start_slots(start)
-        counts, flags, tables, live, x, answered = self._schedule(blocks, starts, end, discard)
-        answered = sorted(set(answered) | set(starts))
-        if not counts.any() and not flags.any():              # nothing pushed, started or ended: no device call
-            return {}
-        want, positions = self._spans(counts, flags, tables)
-        host_grid, got = self._call_host(x, counts, flags, bool(grids))
-        if not np.array_equal(np.asarray(got, np.int64), want):
-            raise _native.NativeError(f'the voice pool answered {list(got)}, the spans are {list(want)}')
-        self._commit(positions)
-        self.tables, self._form = tables, 'dict'
-        live[(flags & VOICE_END) != 0] = False
-        self.live = live
-        return {slot: (host_grid[slot].astype(np.float64) if grids else None)
-                for slot in answered if want[slot] == 1}      # (an empty block alone: idle)
+        row = (lambda counts: counts.view(np.uint32).astype(np.float64)) if grids else None
+        return self._process_valid(blocks, start, end, discard, row, bool(grids))
 
     def process_dev(self, y, counts, flags, *, valid=None):
         """One call on device tensors, enqueued on the current stream: ``y`` ``(slots, M, 2)`` of the pool's dtype,
@@ -725,27 +699,7 @@ class ScopeVoicePool(_SlotPool):
         slot that answered 1 is updated, no other - and int32 ``(slots,)``, the pool's own tensor at a fixed address
         unless ``valid=`` gives the caller's.  No check reads device memory; bad per-slot values answer -1
         (``include/vnd_scope_voice_stream.h``)."""
-        if self._form == 'dict':
-            self._require_form('dev')
-        _check_device_tensors((y, counts, flags), self._inputs)
-        if valid is not None:
-            _check_device_tensors((valid,), self._outputs[1:])
-        torch = _torch()
-        self._ensure_state(torch, _native.default_context())
-        return self._call_device(torch, (y, counts, flags), self._grid, self._valid if valid is None else valid)
-
-    # ---- what _SlotPool asks for ---------------------------------------------------------------
-    def _spans(self, counts, flags, tables):
-        return scope_voice_spans(self.positions, counts, flags, self.max_frames_per_call)
-
-    def _per_slot(self, tables):
-        return ()
-
-    def _bank_len(self) -> int:
-        return 1                                  # a voice starts with nothing of its own: the pool has one setting
-
-    def _slot_value(self, index: int):
-        return 0
+        return self._process_dev((y, counts, flags), valid=valid)
 
     # ---- the device -------------------------------------------------------------------------
     def _state_bytes(self, ctx) -> int:
@@ -754,11 +708,7 @@ class ScopeVoicePool(_SlotPool):
     def _allocate(self, torch, ctx):
         _SlotPool._allocate(self, torch, ctx)
         device = torch.device('cuda', ctx.device)
-        # the grid and valid in one buffer: the dict form brings both down in one copy
-        grid_bytes = self.slots * self.bins[0] * self.bins[1] * 4
-        self._own = torch.zeros((grid_bytes + 4 * self.slots,), dtype=torch.uint8, device=device)
-        self._grid = self._own[:grid_bytes].view(torch.int32).view((self.slots,) + self.bins)
-        self._valid = self._own[grid_bytes:].view(torch.int32)
+        self._own = self._packed_outputs(torch, device, torch.zeros)      # the grid and valid, kept
         self._edges_dev = _device_edges(torch, device, *self.edges)
 
     def _reset_entry(self, ctx, state_ptr, state_bytes, stream):
@@ -768,26 +718,7 @@ class ScopeVoicePool(_SlotPool):
     def _call_host(self, x, counts, flags, grids: bool = True):
         """One upload (the blocks and the two int32 arrays in one buffer), the call, one download (the grids and valid, or
         valid alone)."""
-        torch = _torch()
-        ctx = _native.default_context()
-        device = torch.device('cuda', ctx.device)
-        self._ensure_state(torch, ctx)
-        ints = np.stack([counts, flags]).astype(np.int32)
-        up = torch.from_numpy(np.concatenate([x.reshape(-1).view(np.uint8), ints.reshape(-1).view(np.uint8)])).to(device)
-        self.transfers = {'to_device': 1, 'to_host': 0}
-        x_dev = up[:x.nbytes].view(getattr(torch, x.dtype.name)).view(x.shape)
-        int_rows = up[x.nbytes:].view(torch.int32).view(2, self.slots)
-        form = self._form
-        try:
-            self._call_device(torch, (x_dev, *int_rows), self._grid, self._valid)
-        finally:
-            self._form = form
-        host = (self._own if grids else self._valid).cpu().numpy()
-        self.transfers['to_host'] = 1
-        if not grids:
-            return None, host
-        cut = host.nbytes - 4 * self.slots
-        return host[:cut].view(np.uint32).reshape((self.slots,) + self.bins), host[cut:].view(np.int32)
+        return self._call_host_packed(x, (counts, flags), first=grids)
 
     def _launch(self, ctx, state_ptr, state_bytes, inputs, grid, valid, stream):
         y, counts, flags = inputs
@@ -828,7 +759,7 @@ def lissajous_histogram_voice_pool(slots: int, *, max_frames_per_call: int, bins
 
 
 # ---- the level envelope of a voice pool (include/vnd_polar_level_voice_stream.h) -------------------------------------
-class LevelVoicePool(_SlotPool):
+class LevelVoicePool(_MeterPool):
     """The level envelope of ``slots`` voices, each with a life of its own (:func:`polar_level_voice_pool`;
     ``vnd_polar_level_voice_stream_*``): voices start and end on any call and push blocks of any size up to
     ``max_frames_per_call`` or none, by the slot rule of :class:`ScopeVoicePool` (:func:`scope_voice_spans`).  Percentiles of
@@ -857,28 +788,13 @@ class LevelVoicePool(_SlotPool):
       ``max_frames_per_call=pool.row_frames`` (and ``dtype='float64'`` for a Haas or chain pool) and hand it that pool's
       ``y`` and ``out_counts`` and the caller's ``flags``: a -1 of the pool is a bad count here and answers -1."""
 
-    in_channels = 2
     _out_dtype = np.float64
 
     def __init__(self, slots: int, *, max_frames_per_call: int, window_frames: int, radius_scale, num_bins: int = 360,
                  percentiles=(95.0, 50.0), dtype='float32', ms: bool = True, semicircular: bool = True):
-        from .analysis import _sample_dtype
-        _check_counts(slots=slots, max_frames_per_call=max_frames_per_call, window_frames=window_frames)
-        _check_slots(slots)
-        if max_frames_per_call > _INT32_MAX:
-            raise ValueError(f'max_frames_per_call {max_frames_per_call} above 2**31 - 1: counts are int32')
-        if window_frames < max_frames_per_call:
-            raise ValueError(f'window_frames {window_frames} below max_frames_per_call {max_frames_per_call}: two frames of '
-                             'one call would share a ring entry')
-        if window_frames > _INT32_MAX:
-            raise ValueError(f'window_frames {window_frames} above 2**31 - 1')
-        self.dtype = _sample_dtype(dtype)
-        if radius_scale is None:
-            raise ValueError('a voice pool needs a fixed radius_scale: the per-voice maximum of a later block would rescale '
-                             'the earlier frames')
-        self.radius_scale = _scale(radius_scale, True)
-        if not 0.0 < float(self.dtype.type(self.radius_scale)) < np.inf:
-            raise ValueError(f'radius_scale {radius_scale!r} is zero or infinite in {self.dtype.name}')
+        _MeterPool.__init__(self, slots, max_frames_per_call, dtype)
+        self.window_frames = _window(window_frames, max_frames_per_call)
+        self.radius_scale = _fixed_scale(radius_scale, self.dtype)
         self.num_bins = _bins(num_bins, 'num_bins')
         if self.num_bins > LEVEL_MAX_BINS:
             raise ValueError(f'num_bins {num_bins}: a level voice pool takes 1 to {LEVEL_MAX_BINS} slices')
@@ -887,15 +803,11 @@ class LevelVoicePool(_SlotPool):
             raise ValueError(f'{len(self.percentiles)} percentiles: a level voice pool takes 1 to {LEVEL_MAX_PERCENTILES}')
         self.ms, self.semicircular = bool(ms), bool(semicircular)
         self.bin_edges, self.bin_centers = level_edges(self.num_bins)
-        self.slots, self.max_frames_per_call, self.window_frames = int(slots), int(max_frames_per_call), int(window_frames)
-        self._block_dtype = self.dtype            # what _schedule holds every block to
         # the fixed grids of the pool's launches (include/vnd_polar_level_voice_stream.h): 2^23 workgroups each
         groups = max(-(-self.max_frames_per_call // VOICE_SPAN_FRAMES), -(-self.window_frames // LEVEL_SPAN_FRAMES))
         if self.slots * groups > _MAX_GROUPS:
             raise ValueError(f'{self.slots} slots of {groups} workgroups are more than one launch takes: split the pool')
-        self.transfers = {'to_device': 0, 'to_host': 0}
-        self._state = None                    # (torch uint8 tensor, bytes)
-        self._levels = self._valid = self._own = self._bin_counts = self._work = self._edges_dev = None
+        self._bin_counts = self._work = self._edges_dev = None
         self._with_levels = True
         S = self.slots
         self._inputs = (('y', (S, self.max_frames_per_call, 2), self.dtype.name, None),) + _slot_ints(S, 'counts', 'flags')
@@ -907,9 +819,9 @@ class LevelVoicePool(_SlotPool):
     def levels(self):
         """The pool's envelopes: ``(slots, len(percentiles), num_bins)`` of the pool's dtype on the device; allocated, as
         zeros, with the state on first use."""
-        if self._levels is None:
+        if self._own is None:
             self._ensure_state(_torch(), _native.default_context())
-        return self._levels
+        return self._own[1]
 
     @property
     def bin_counts(self):
@@ -926,22 +838,8 @@ class LevelVoicePool(_SlotPool):
         (``levels=False``: ``None``; the frames are pushed, nothing is selected and only ``valid`` comes down), for every
         slot that got a block, started or ended.  Raises before any device call, as :meth:`ScopeVoicePool.process`
         does."""
-        self._require_form('dict')
-        starts = self._start_slots(start)
-        counts, flags, tables, live, x, answered = self._schedule(blocks, starts, end, discard)
-        answered = sorted(set(answered) | set(starts))
-        if not counts.any() and not flags.any():              # nothing pushed, started or ended: no device call
-            return {}
-        want, positions = self._spans(counts, flags, tables)
-        host_levels, got = self._call_host(x, counts, flags, bool(levels))
-        if not np.array_equal(np.asarray(got, np.int64), want):
-            raise _native.NativeError(f'the voice pool answered {list(got)}, the spans are {list(want)}')
-        self._commit(positions)
-        self.tables, self._form = tables, 'dict'
-        live[(flags & VOICE_END) != 0] = False
-        self.live = live
-        return {slot: (host_levels[slot].astype(np.float64) if levels else None)
-                for slot in answered if want[slot] == 1}      # (an empty block alone: idle)
+        row = (lambda values: values.astype(np.float64)) if levels else None
+        return self._process_valid(blocks, start, end, discard, row, bool(levels))
 
     def process_dev(self, y, counts, flags, *, levels: bool = True, valid=None):
         """One call on device tensors, enqueued on the current stream: ``y`` ``(slots, M, 2)`` of the pool's dtype,
@@ -950,16 +848,9 @@ class LevelVoicePool(_SlotPool):
         :attr:`levels` and int32 ``(slots,)``, the pool's own tensor at a fixed address unless ``valid=`` gives the
         caller's.  No check reads device memory; bad per-slot values answer -1
         (``include/vnd_polar_level_voice_stream.h``)."""
-        if self._form == 'dict':
-            self._require_form('dev')
-        _check_device_tensors((y, counts, flags), self._inputs)
-        if valid is not None:
-            _check_device_tensors((valid,), self._outputs[1:])
-        torch = _torch()
-        self._ensure_state(torch, _native.default_context())
         self._with_levels = bool(levels)
         try:
-            return self._call_device(torch, (y, counts, flags), self._levels, self._valid if valid is None else valid)
+            return self._process_dev((y, counts, flags), valid=valid)
         finally:
             self._with_levels = True
 
@@ -969,21 +860,8 @@ class LevelVoicePool(_SlotPool):
         torch = _torch()
         ctx = _native.default_context()
         state, state_bytes = self._ensure_state(torch, ctx)
-        self._read(ctx, state.data_ptr(), state_bytes, self._levels, torch.cuda.current_stream(state.device).cuda_stream)
-        return self._levels
-
-    # ---- what _SlotPool asks for ---------------------------------------------------------------
-    def _spans(self, counts, flags, tables):
-        return scope_voice_spans(self.positions, counts, flags, self.max_frames_per_call)
-
-    def _per_slot(self, tables):
-        return ()
-
-    def _bank_len(self) -> int:
-        return 1                                  # a voice starts with nothing of its own: the pool has one setting
-
-    def _slot_value(self, index: int):
-        return 0
+        self._read(ctx, state.data_ptr(), state_bytes, self._own[1], torch.cuda.current_stream(state.device).cuda_stream)
+        return self._own[1]
 
     # ---- the device -------------------------------------------------------------------------
     def _is64(self) -> bool:
@@ -995,12 +873,7 @@ class LevelVoicePool(_SlotPool):
     def _allocate(self, torch, ctx):
         _SlotPool._allocate(self, torch, ctx)
         device = torch.device('cuda', ctx.device)
-        # the levels and valid in one buffer: the dict form brings both down in one copy
-        shape = self._outputs[0][1]
-        level_bytes = int(np.prod(shape)) * self.dtype.itemsize
-        self._own = torch.zeros((level_bytes + 4 * self.slots,), dtype=torch.uint8, device=device)
-        self._levels = self._own[:level_bytes].view(getattr(torch, self.dtype.name)).view(shape)
-        self._valid = self._own[level_bytes:].view(torch.int32)
+        self._own = self._packed_outputs(torch, device, torch.zeros)      # the levels and valid, kept
         self._bin_counts = torch.zeros((self.slots, self.num_bins), dtype=torch.int32, device=device)
         self._work_bytes = _native.level_voice_stream_work_bytes(self.slots, self.window_frames, self.num_bins,
                                                                  len(self.percentiles), self._is64())
@@ -1008,7 +881,7 @@ class LevelVoicePool(_SlotPool):
         self._edges_dev = _device_edges(torch, device, self.bin_edges, self.bin_centers)
         # one read of the fresh state: whatever the select sets up on its first launch happens here, not inside a capture
         state, state_bytes = self._state
-        self._read(ctx, state.data_ptr(), state_bytes, self._levels, torch.cuda.current_stream(device).cuda_stream)
+        self._read(ctx, state.data_ptr(), state_bytes, self._own[1], torch.cuda.current_stream(device).cuda_stream)
 
     def _reset_entry(self, ctx, state_ptr, state_bytes, stream):
         _native.level_voice_stream_reset_device(ctx, state_ptr, state_bytes, self.slots, self.max_frames_per_call,
@@ -1017,27 +890,11 @@ class LevelVoicePool(_SlotPool):
     def _call_host(self, x, counts, flags, levels: bool = True):
         """One upload (the blocks and the two int32 arrays in one buffer), the call, one download (the levels and valid,
         or valid alone)."""
-        torch = _torch()
-        ctx = _native.default_context()
-        device = torch.device('cuda', ctx.device)
-        self._ensure_state(torch, ctx)
-        ints = np.stack([counts, flags]).astype(np.int32)
-        up = torch.from_numpy(np.concatenate([x.reshape(-1).view(np.uint8), ints.reshape(-1).view(np.uint8)])).to(device)
-        self.transfers = {'to_device': 1, 'to_host': 0}
-        x_dev = up[:x.nbytes].view(getattr(torch, x.dtype.name)).view(x.shape)
-        int_rows = up[x.nbytes:].view(torch.int32).view(2, self.slots)
-        form = self._form
         self._with_levels = levels
         try:
-            self._call_device(torch, (x_dev, *int_rows), self._levels, self._valid)
+            return self._call_host_packed(x, (counts, flags), first=levels)
         finally:
-            self._form, self._with_levels = form, True
-        host = (self._own if levels else self._valid).cpu().numpy()
-        self.transfers['to_host'] = 1
-        if not levels:
-            return None, host
-        cut = host.nbytes - 4 * self.slots
-        return host[:cut].view(self.dtype).reshape(self._outputs[0][1]), host[cut:].view(np.int32)
+            self._with_levels = True
 
     def _launch(self, ctx, state_ptr, state_bytes, inputs, levels, valid, stream):
         y, counts, flags = inputs
