@@ -41,12 +41,10 @@ def test_haas_stream_header_is_plain_c():
 
 
 def test_haas_stream_symbols_exported_and_bound(lib):
-    from vndecorrelate_amd import _native
     names = _declared(HEADER)
     assert names == ['vnd_haas_stream_f64_dev', 'vnd_haas_stream_f64_host', 'vnd_haas_stream_state_bytes']
     for name in names:
         assert hasattr(lib, name), f'{name} declared in vnd_haas_stream.h but not exported'
-    assert sorted(_native.HAAS_STREAM_SIGNATURES) == names
     assert not set(names) & set(_declared(REPO / 'include' / 'vnd_amd.h'))
     assert not set(names) & set(_declared(REPO / 'include' / 'vnd_stream.h'))
 

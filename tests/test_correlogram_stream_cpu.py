@@ -43,7 +43,6 @@ def test_symbols_exported_and_bound(lib):
     assert names == ['vnd_correlogram_stream_f32_dev', 'vnd_correlogram_stream_state_bytes']
     for name in names:
         assert hasattr(lib, name), f'{name} declared in vnd_correlogram_stream.h but not exported'
-    assert sorted(_native.CORRELOGRAM_STREAM_SIGNATURES) == names
     assert not set(names) & set(_declared(REPO / 'include' / 'vnd_amd.h'))
     assert not set(names) & set(_declared(REPO / 'include' / 'vnd_analysis.h'))
     assert not set(names) & set(_native.ANALYSIS_SIGNATURES)

