@@ -100,6 +100,12 @@ vnd_status vnd_describe_each_stream_launch(vnd_ctx *ctx, const vnd_taps *bank, i
  * advance_groups (the workgroups of the kernel that advances the positions, one lane per slot).                          */
 vnd_status vnd_describe_voice_stream_launch(vnd_ctx *ctx, const vnd_taps *bank, int64_t max_frames_per_call, int64_t slots,
                                             int32_t in_channels, int32_t mode, int32_t epilogue, char *text, int32_t len);
+/* Diagnosis: the launch every vnd_voice_fade_stream_f32_dev call (include/vnd_voice_fade_stream.h) on a pool with these
+ * arguments takes - that pool's scalar checks, vnd_describe_voice_stream_launch's planner - as one line that starts with
+ * voice_fade_stream and carries that hook's fields, then fade_frames.                                                   */
+vnd_status vnd_describe_voice_fade_stream_launch(vnd_ctx *ctx, const vnd_taps *bank, int64_t max_frames_per_call,
+                                                 int64_t fade_frames, int64_t slots, int32_t in_channels, int32_t mode,
+                                                 int32_t epilogue, char *text, int32_t len);
 /* Diagnosis: the launch every vnd_correlogram_voice_stream_*_dev call (include/vnd_correlogram_voice_stream.h) on a pool with
  * these sizes takes - the pool's own scalar checks and planner, no context, no pointers, no device work - as one line of
  * key=value fields: rows_per_call (RC = ceil(max_frames_per_call / hop)), groups (window groups of 4 rows per slot), tiles

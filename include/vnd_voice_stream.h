@@ -37,7 +37,8 @@
  *     (a state that was never reset) unless the call carries START.
  *   - tables[b] outside [0, T) on a slot that has work: that slot's out_counts[b] rows are NaN (the convention of
  *     vnd_each_stream.h); the position still advances.
- * The table of a slot is expected to change only with START; the C ABI does not police this.
+ * The table of a slot is expected to change only with START; the C ABI does not police this.  (A live voice changes its
+ * table, crossfaded, in the pool of vnd_voice_fade_stream.h.)
  *
  * ---- state ------------------------------------------------------------------------------------------------------------
  * `state_bytes` at least what vnd_voice_stream_state_bytes returns, state_dev 16-byte aligned: first one int64 position

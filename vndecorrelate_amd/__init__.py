@@ -68,12 +68,15 @@ from .streaming import (  # noqa: F401
     ChainStream,
     ChainVoicePool,
     EachStream,
+    FadeVoicePool,
     HaasEachStream,
     HaasStream,
     HaasVoicePool,
     Stream,
     VoicePool,
     convolve_velvet_noise_stream,
+    fade_gains,
     haas_voice_spans,
+    voice_fade_spans,
     voice_spans,
 )

@@ -96,6 +96,7 @@ INTERNAL_SIGNATURES = {
     'vnd_describe_scan': (_int, [_p, _p, _i64, _i32, _i32, _str, _i32]),
     'vnd_describe_each_stream_launch': (_int, [_p, _p, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _str, _i32]),
     'vnd_describe_voice_stream_launch': (_int, [_p, _p, _i64, _i64, _i32, _i32, _i32, _str, _i32]),
+    'vnd_describe_voice_fade_stream_launch': (_int, [_p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _str, _i32]),
     'vnd_describe_correlogram_voice_stream_launch': (_int, [_i64, _i32, _i32, _i32, _i64, _str, _i32]),
     'vnd_describe_polar_voice_stream_launch': (_int, [_i64, _i64, _i32, _str, _i32]),
     'vnd_describe_spectrum_voice_stream_launch': (_int, [_i64, _i32, _i32, _i32, _i32, _i64, _i32, _str, _i32]),
@@ -190,6 +191,17 @@ VOICE_STREAM_SIGNATURES = {
     'vnd_voice_stream_reset_dev': (_int, [_p, _p, _i64, _i64, _i32, _p, _i64, _p]),
     'vnd_voice_stream_f32_dev': (_int, _VOICE_STREAM_ARGS + [_p]),
     'vnd_voice_stream_f32_host': (_int, _VOICE_STREAM_ARGS),
+}
+
+# include/vnd_voice_fade_stream.h: the voice pool whose live voices change their filter, crossfaded (the wrappers:
+# _native_fade.py)
+VOICE_SWITCH = 4                      # VND_VOICE_SWITCH
+VOICE_FADE_MAX_FRAMES = 1 << 20       # VND_VOICE_FADE_MAX_FRAMES
+VOICE_FADE_STREAM_SIGNATURES = {
+    'vnd_voice_fade_stream_state_bytes': (_int, [_p, _i64, _i32, _i64, _i64, _i64p]),
+    'vnd_voice_fade_stream_reset_dev': (_int, [_p, _p, _i64, _i64, _i32, _p, _i64, _i64, _p]),
+    'vnd_voice_fade_stream_f32_dev': (_int, [_p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32,
+                                             _i32, _i32, _f64, _p]),
 }
 
 # include/vnd_haas_voice_stream.h: the voice pool of HaasEffect delays, a delay per slot
@@ -324,6 +336,7 @@ HEADERS = {
     'vnd_correlogram_stream.h': CORRELOGRAM_STREAM_SIGNATURES,
     'vnd_each_stream.h': EACH_STREAM_SIGNATURES,
     'vnd_voice_stream.h': VOICE_STREAM_SIGNATURES,
+    'vnd_voice_fade_stream.h': VOICE_FADE_STREAM_SIGNATURES,
     'vnd_haas_voice_stream.h': HAAS_VOICE_STREAM_SIGNATURES,
     'vnd_correlogram_voice_stream.h': CORRELOGRAM_VOICE_STREAM_SIGNATURES,
     'vnd_polar_voice_stream.h': POLAR_VOICE_STREAM_SIGNATURES,

@@ -302,6 +302,24 @@ vnd_status vnd_describe_voice_stream_launch(vnd_ctx *ctx, const vnd_taps *t, int
     return VND_OK;
 }
 
+// The plan of a vnd_voice_fade_stream_f32_dev call on a pool with these arguments: vnd_describe_voice_stream_launch's
+// sibling - the crossfading pool's scalar checks, the same planner - with fade_frames behind its fields.
+vnd_status vnd_describe_voice_fade_stream_launch(vnd_ctx *ctx, const vnd_taps *t, int64_t max_frames_per_call,
+                                                 int64_t fade_frames, int64_t slots, int32_t in_channels, int32_t mode,
+                                                 int32_t epilogue, char *text, int32_t len)
+{
+    if (!text || len <= 0) return fail(VND_ERR_INVALID, "null text buffer");
+    int64_t need = 0;
+    vnd_status st = voice_fade_scalars(ctx, t, max_frames_per_call, fade_frames, slots, in_channels, mode, &need);
+    if (st != VND_OK) return st;
+    if ((st = voice_stream_rows(t, max_frames_per_call, slots)) != VND_OK) return st;
+    const EachStreamPlan p = make_voice_stream_plan(ctx, t, slots, max_frames_per_call, in_channels, epilogue != 0);
+    snprintf(text, (size_t)len, "voice_fade_stream r=%d W=%d lds_bytes=%zu tiles=%d nblocks=%u fma=%d epilogue=%d threads=%d advance_groups=%lld fade_frames=%lld",
+             p.r, p.W, p.lds_bytes, p.tiles, p.nblocks, p.fma ? 1 : 0, p.epi ? 1 : 0, kVpThreads,
+             (long long)voice_advance_groups(slots), (long long)fade_frames);
+    return VND_OK;
+}
+
 // The fixed launch of every vnd_correlogram_voice_stream_*_dev call on a pool with these sizes: the pool's own scalar checks
 // and cg_voice_plan, the launch's own.  No pointers, no device work.
 vnd_status vnd_describe_correlogram_voice_stream_launch(int64_t slots, int32_t window, int32_t hop, int32_t num_lags,

@@ -1,4 +1,4 @@
-// vnd_voice_core.hpp - what the seven voice pools share (vnd_voice_stream.hpp, vnd_haas_voice_stream.hpp,
+// vnd_voice_core.hpp - what the eight voice pools share (vnd_voice_stream.hpp, vnd_voice_fade_stream.hpp, vnd_haas_voice_stream.hpp,
 // vnd_correlogram_voice_stream.hpp, vnd_polar_voice_stream.hpp, vnd_spectrum_voice_stream.hpp, vnd_scope_voice_stream.hpp,
 // vnd_level_voice_stream.hpp): the slot rule, the head of the state, the checks of the state and of strided chunks, the
 // reset, and the kernel that moves the positions on.  (vnd_voice_window.hpp: what the last two share beyond it.)

@@ -1424,7 +1424,8 @@ def _chain_pool_stages(bank):
     return velvets, haases
 
 
-def decorrelate_voice_pool(bank: Sequence, *, slots: int, in_channels: int = 2, max_frames_per_call: int = 4800):
+def decorrelate_voice_pool(bank: Sequence, *, slots: int, in_channels: int = 2, max_frames_per_call: int = 4800,
+                           fade_frames: Optional[int] = None, fade='linear'):
     """A voice pool: ``slots`` slots over a ``bank``, each slot a voice with a life of its own - it starts on any call
     with any entry of the bank, brings blocks of any size up to ``max_frames_per_call`` or none, ends on any call, and the
     slot goes to the next voice.  Where :func:`decorrelate_each_stream` advances a pool in lockstep from a position the
@@ -1444,7 +1445,13 @@ def decorrelate_voice_pool(bank: Sequence, *, slots: int, in_channels: int = 2, 
     voice the concatenation of its outputs equals ``bank[i].decorrelate(x_voice)`` - ``bank[i](x_voice)`` for a chain - bit
     for bit.  The velvet stages are checked as :func:`decorrelate_each_stream` checks its ``VelvetNoise`` list and the Haas
     stages as it checks its ``HaasEffect`` list, with the same exceptions before any device call; a mixed bank is a
-    ``TypeError`` listing the types.  There is no host fallback: a stream has no host loop to fall back to."""
+    ``TypeError`` listing the types.  There is no host fallback: a stream has no host loop to fall back to.
+
+    ``fade_frames`` (an int, with a bank of plain ``VelvetNoise`` only; ``ValueError`` for a Haas or chain bank) returns a
+    ``streaming.FadeVoicePool`` (``vnd_voice_fade_stream_f32_dev``): ``pool.process(..., switch={slot: bank_index})`` moves a
+    live voice to another bank entry, crossfaded over ``fade_frames`` frames from the first frame the slot has not yet
+    returned.  ``fade`` names the gains (``streaming.fade_gains``): ``'linear'``, ``'equal_power'``, or a pair
+    ``(fade_out, fade_in)`` of finite float32 arrays of length ``fade_frames``.  ``None`` returns the pools above."""
     from . import streaming
     bank = list(bank)
     if not bank:
@@ -1455,8 +1462,16 @@ def decorrelate_voice_pool(bank: Sequence, *, slots: int, in_channels: int = 2, 
                         'or of VelvetNoise -> HaasEffect SignalChains, got ' + ', '.join(sorted(k.__name__ for k in kinds)))
     if isinstance(in_channels, (bool, np.bool_)) or in_channels not in (1, 2):
         raise ValueError(f'in_channels must be 1 (mono, fanned out) or 2 (stereo), got {in_channels!r}')
+    if fade_frames is not None and kinds != {VelvetNoise}:
+        raise ValueError('decorrelate_voice_pool: fade_frames is taken with a bank of plain VelvetNoise decorrelators; Haas '
+                         'and chain voices do not switch')
     if kinds == {VelvetNoise}:
         arrays, tables, ms_encode, width = _velvet_stream_bank(bank, 'decorrelate_voice_pool', 'bank entry')
+        if fade_frames is not None:
+            gains = streaming.fade_gains(fade_frames, fade)
+            return streaming.FadeVoicePool(arrays, tables, slots=slots, in_channels=in_channels,
+                                           max_frames_per_call=max_frames_per_call, fade_frames=fade_frames, fade_gains=gains,
+                                           ms_encode=ms_encode, width=width)
         return streaming.VoicePool(arrays, tables, slots=slots, in_channels=in_channels,
                                    max_frames_per_call=max_frames_per_call, ms_encode=ms_encode, width=width)
     if kinds == {HaasEffect}:

@@ -717,7 +717,10 @@ class _SlotPool:
         the slot held is dropped, unflushed), a bank index outside the bank, a block above ``max_frames_per_call`` or of
         another channel count; ``TypeError`` for a block that is not float32."""
         self._require_form('dict')
-        counts, flags, tables, live, x, answered = self._schedule(blocks, start, end, discard)
+        return self._run_schedule(*self._schedule(blocks, start, end, discard))
+
+    def _run_schedule(self, counts, flags, tables, live, x, answered):
+        """The call that ``_schedule`` drew up: the device call, its counts against the spans, the mirror moved on."""
         if not counts.any() and not flags.any():              # nothing pushed, started or ended: no device call
             return {slot: np.zeros((0, self._out_width), self._out_dtype) for slot in answered}
         want, positions = self._spans(counts, flags, tables)
@@ -1082,6 +1085,183 @@ class VoicePool(_SlotPool):
                                     counts.data_ptr(), flags.data_ptr(), tables.data_ptr(), y.data_ptr(),
                                     out_counts.data_ptr(), self.slots, self.in_channels, ms_encode=self.ms_encode,
                                     width=self.width, stream=stream)
+
+
+# ----------------------------------------------------------------------------
+# A voice pool whose live voices change their filter, crossfaded   (include/vnd_voice_fade_stream.h)
+# ----------------------------------------------------------------------------
+VOICE_SWITCH = _native.VOICE_SWITCH
+VOICE_FADE_MAX_FRAMES = _native.VOICE_FADE_MAX_FRAMES
+
+
+def voice_fade_spans(positions, records, counts, flags, tables, latency: int, fade_frames: int,
+                     max_frames_per_call: Optional[int] = None):
+    """``(out_counts, new_positions, new_records, fade_left)`` of one call of a crossfading voice pool
+    (``include/vnd_voice_fade_stream.h``), per slot, from the positions and records before the call - ``records`` is int64
+    ``(slots, 3)``: ``s``, ``old``, ``cur`` - the frames pushed, the ``VOICE_START`` / ``VOICE_END`` / ``VOICE_SWITCH``
+    flags and the tables of the call alone - what the device computes from its own state::
+
+        fresh = START or position == 0          p, E, E', out_count, new position: voice_spans'
+        (old, cur, s) = (table, table, -F) if fresh else the record
+        accept = SWITCH and not fresh and E >= s + F:    (old, cur, s) = (cur, table, E)
+        fade_left = 0 if END else min(F, max(0, s + F - E'))
+
+    A bad slot (``voice_spans``' rule) answers -1 twice and keeps its position and its record."""
+    pos, n, start, end, p, bad = _voice_head(positions, counts, flags, max_frames_per_call)
+    rec = np.asarray(records, np.int64)
+    t = np.asarray(tables, np.int64)
+    if rec.shape != pos.shape + (3,) or t.shape != pos.shape:
+        raise ValueError(f'records of shape {pos.shape + (3,)} and tables of shape {pos.shape}, got {rec.shape}, {t.shape}')
+    H, F = int(latency), int(fade_frames)
+    p, n = np.where(bad, 0, p), np.where(bad, 0, n)          # (no arithmetic on a bad value)
+    first = np.maximum(0, p - H)
+    last = np.where(end, p + n, np.maximum(0, p + n - H))
+    s, old, cur = rec[..., 0], rec[..., 1], rec[..., 2]
+    fresh = ~bad & (start | (pos == 0))
+    switch = (np.asarray(flags, np.int64) & VOICE_SWITCH) != 0
+    accept = ~bad & ~fresh & switch & (first - F >= s)         # E >= s + F, without a sum a planted s could wrap
+    new_s = np.where(fresh, -F, np.where(accept, first, s))
+    new_old = np.where(fresh, t, np.where(accept, cur, old))
+    new_cur = np.where(fresh | accept, t, cur)
+    left = np.where(new_s >= last, F, np.where(new_s < last - F, 0, new_s + F - last))
+    out = np.where(bad, -1, last - first).astype(np.int64)
+    new = np.where(bad, pos, np.where(end, 0, p + n)).astype(np.int64)
+    fade_left = np.where(bad, -1, np.where(end, 0, left)).astype(np.int64)
+    return out, new, np.stack([new_s, new_old, new_cur], axis=-1).astype(np.int64), fade_left
+
+
+def fade_gains(fade_frames: int, fade='linear') -> np.ndarray:
+    """The float32 ``(2, fade_frames)`` gains of a crossfade, row 0 fade-out and row 1 fade-in, frame ``j`` of the fade
+    scaled by column ``j``.  ``fade``: ``'linear'`` - ``in[j] = float32((j + 1) / (F + 1))``, ``out = float32(1) - in``;
+    ``'equal_power'`` - ``in, out = sin, cos`` of ``pi/2 * (j + 1) / (F + 1)`` in float64, then rounded to float32; or a
+    pair ``(fade_out, fade_in)`` of finite float32 arrays of length ``fade_frames``.  ``ValueError`` otherwise."""
+    if isinstance(fade_frames, (bool, np.bool_)) or not isinstance(fade_frames, (int, np.integer)) \
+            or not 0 <= fade_frames <= VOICE_FADE_MAX_FRAMES:
+        raise ValueError(f'fade_frames must be an integer in [0, {VOICE_FADE_MAX_FRAMES}], got {fade_frames!r}')
+    F = int(fade_frames)
+    if isinstance(fade, str):
+        ramp = (np.arange(F, dtype=np.float64) + 1.0) / (F + 1.0)
+        if fade == 'linear':
+            rise = ramp.astype(np.float32)
+            return np.stack([np.float32(1) - rise, rise])
+        if fade == 'equal_power':
+            return np.stack([np.cos(np.pi / 2 * ramp), np.sin(np.pi / 2 * ramp)]).astype(np.float32)
+        raise ValueError(f"fade must be 'linear', 'equal_power' or a pair of float32 arrays, got {fade!r}")
+    try:
+        fall, rise = fade
+    except (TypeError, ValueError):
+        raise ValueError("fade must be 'linear', 'equal_power' or a pair (fade_out, fade_in) of float32 arrays") from None
+    for name, g in (('fade_out', fall), ('fade_in', rise)):
+        if not isinstance(g, np.ndarray) or g.dtype != np.float32 or g.shape != (F,):
+            raise ValueError(f'{name} must be a float32 array of shape ({F},), got {getattr(g, "dtype", type(g).__name__)} '
+                             f'{getattr(g, "shape", "")}')
+        if not np.isfinite(g).all():
+            raise ValueError(f'{name} holds a gain that is not finite')
+    return np.ascontiguousarray(np.stack([fall, rise]))
+
+
+class FadeVoicePool(VoicePool):
+    """A :class:`VoicePool` whose live voices change their filter (``decorrelation.decorrelate_voice_pool`` with
+    ``fade_frames``, ``vnd_voice_fade_stream_f32_dev``): a voice that switches keeps its position, its history and its
+    latency, and from the first frame it has not yet returned its output fades over ``fade_frames`` frames from the bank
+    entry it had to the new one - ``old * fade_gains[0][j] + new * fade_gains[1][j]`` on the convolved frames, float32, before
+    the stage's pointwise steps.  One fade per voice is in flight: ``fade_left[slot]`` is the number of frames of it the
+    slot has yet to return, and a switch is taken only at 0.  A voice that never switches returns :class:`VoicePool`'s
+    bytes.
+
+    * ``process({slot: block}, start=..., end=..., switch={slot: bank_index})`` - the dict form.  Besides
+      :class:`VoicePool`'s refusals, ``ValueError`` before any device call for a switch on a slot with no live voice,
+      together with a start of that slot, to an index outside the bank, or while ``fade_left[slot] > 0``.
+    * ``process_dev(x, counts, flags, tables)`` - flags may carry ``VOICE_SWITCH``, and ``tables[b]`` is read when a
+      voice begins and when its switch is accepted; a switch that comes while ``fade_left_dev[b] > 0`` is ignored.
+      ``(y, out_counts)`` are :class:`VoicePool`'s, so every meter attaches unchanged; ``fade_left_dev`` is the pool's
+      own int32 ``(slots,)`` tensor at a fixed address, written by every call."""
+
+    def __init__(self, arrays: TapArrays, bank_tables, *, slots: int, in_channels: int, max_frames_per_call: int,
+                 fade_frames: int, fade_gains: np.ndarray, ms_encode: bool = False, width: Optional[float] = None):
+        gains = np.ascontiguousarray(fade_gains)
+        if isinstance(fade_frames, (bool, np.bool_)) or not isinstance(fade_frames, (int, np.integer)) \
+                or not 0 <= fade_frames <= VOICE_FADE_MAX_FRAMES:
+            raise ValueError(f'fade_frames must be an integer in [0, {VOICE_FADE_MAX_FRAMES}], got {fade_frames!r}')
+        if gains.dtype != np.float32 or gains.shape != (2, fade_frames) or not np.isfinite(gains).all():
+            raise ValueError(f'fade_gains must be a finite float32 array of shape (2, {fade_frames})')
+        self.fade_frames, self.fade_gains = int(fade_frames), gains
+        self.transfers = {'to_device': 0, 'to_host': 0}
+        self._fade = None                     # (gains on the device or None, fade_left_dev)
+        VoicePool.__init__(self, arrays, bank_tables, slots=slots, in_channels=in_channels,
+                           max_frames_per_call=max_frames_per_call, ms_encode=ms_encode, width=width)
+
+    def _mirror(self):
+        VoicePool._mirror(self)
+        self.records = np.zeros((self.slots, 3), np.int64)        # (s, old, cur); a slot at position 0 takes its own from the call
+        self.fade_left = np.zeros(self.slots, np.int64)
+
+    @property
+    def fade_left_dev(self):
+        """The int32 ``(slots,)`` device tensor every call writes ``fade_left`` to; allocated by ``reset()``."""
+        if self._fade is None:
+            raise RuntimeError('fade_left_dev is allocated with the state: call reset() first')
+        return self._fade[1]
+
+    def process(self, blocks=None, *, start=None, end=(), switch=None, discard: bool = False):
+        """:meth:`VoicePool.process` with ``switch``: ``{slot: bank_index}``, the live voices that change to another bank
+        entry with this call.  The fade begins at the first frame the slot returns in this call."""
+        self._require_form('dict')
+        counts, flags, tables, live, x, answered = self._schedule(blocks, start, end, discard)
+        for slot, index in dict(switch or {}).items():
+            slot = self._slot(slot, 'switch')
+            if isinstance(index, (bool, np.bool_)) or not isinstance(index, (int, np.integer)) \
+                    or not 0 <= index < self._bank_len():
+                raise ValueError(f'switch: bank index {index!r} of slot {slot} is outside the bank of {self._bank_len()}')
+            if flags[slot] & VOICE_START:
+                raise ValueError(f'switch: slot {slot} starts with this call: a voice begins with the entry in start=')
+            if not live[slot]:
+                raise ValueError(f'switch: slot {slot} holds no live voice')
+            if self.fade_left[slot] > 0:
+                raise ValueError(f'switch: slot {slot} has {int(self.fade_left[slot])} frames of its fade left to return')
+            flags[slot] |= VOICE_SWITCH
+            tables[slot] = self._slot_value(int(index))
+        return self._run_schedule(counts, flags, tables, live, x, answered)
+
+    def _spans(self, counts, flags, tables):
+        out, positions, records, fade_left = voice_fade_spans(self.positions, self.records, counts, flags, tables,
+                                                              self.latency_frames, self.fade_frames, self.max_frames_per_call)
+        return out, (positions, records, fade_left)
+
+    def _commit(self, state):
+        self.positions, self.records, self.fade_left = state
+
+    # ---- the device -------------------------------------------------------------------------
+    def _state_bytes(self, ctx) -> int:
+        from . import _native_fade, decorrelation
+        self._table = decorrelation._each_banks.get(ctx, self.arrays)
+        return _native_fade.voice_fade_stream_state_bytes(self._table, self.slots, self.in_channels, self.max_frames_per_call,
+                                                          self.fade_frames)
+
+    def _allocate(self, torch, ctx):
+        VoicePool._allocate(self, torch, ctx)
+        device = torch.device('cuda', ctx.device)
+        gains = torch.from_numpy(self.fade_gains).to(device) if self.fade_frames else None     # uploaded once
+        self._fade = (gains, torch.zeros((self.slots,), dtype=torch.int32, device=device))
+
+    def _reset_entry(self, ctx, state_ptr, state_bytes, stream):
+        from . import _native_fade
+        _native_fade.voice_fade_stream_reset_device(ctx, self._table, state_ptr, state_bytes, self.slots, self.in_channels,
+                                                    self.max_frames_per_call, self.fade_frames, stream=stream)
+
+    def _call_host(self, x, counts, flags, tables):
+        """One upload (the blocks and the three int32 arrays in one buffer), the call, one download (y and out_counts)."""
+        return self._call_host_packed(x, (counts, flags, tables))
+
+    def _launch(self, ctx, state_ptr, state_bytes, inputs, y, out_counts, stream):
+        from . import _native_fade
+        x, counts, flags, tables = inputs
+        gains, fade_left = self._fade
+        _native_fade.voice_fade_stream_device(ctx, self._table, state_ptr, state_bytes, self.max_frames_per_call,
+                                              self.fade_frames, None if gains is None else gains.data_ptr(), x.data_ptr(),
+                                              counts.data_ptr(), flags.data_ptr(), tables.data_ptr(), y.data_ptr(),
+                                              out_counts.data_ptr(), fade_left.data_ptr(), self.slots, self.in_channels,
+                                              ms_encode=self.ms_encode, width=self.width, stream=stream)
 
 
 # ----------------------------------------------------------------------------
