@@ -21,6 +21,7 @@ from .decorrelation import (  # noqa: F401
     decorrelate_bank,
     decorrelate_each,
     decorrelate_each_stream,
+    decorrelate_fade_voice_pool,
     decorrelate_voice_pool,
     each_covers,
     generate_velvet_noise,
@@ -65,17 +66,20 @@ from .spectral import (  # noqa: F401
     welch_batched,
 )
 from .streaming import (  # noqa: F401
+    ChainFadeVoicePool,
     ChainStream,
     ChainVoicePool,
     EachStream,
     FadeVoicePool,
     HaasEachStream,
+    HaasFadeVoicePool,
     HaasStream,
     HaasVoicePool,
     Stream,
     VoicePool,
     convolve_velvet_noise_stream,
     fade_gains,
+    haas_voice_fade_spans,
     haas_voice_spans,
     voice_fade_spans,
     voice_spans,

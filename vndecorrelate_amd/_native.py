@@ -213,6 +213,15 @@ HAAS_VOICE_STREAM_SIGNATURES = {
     'vnd_haas_voice_stream_f64_host': (_int, _HAAS_VOICE_STREAM_ARGS),
 }
 
+# include/vnd_haas_voice_fade_stream.h: the Haas voice pool whose live voices change their delay, crossfaded (the
+# wrappers: _native_haas_fade.py)
+HAAS_VOICE_FADE_STREAM_SIGNATURES = {
+    'vnd_haas_voice_fade_stream_state_bytes': (_int, [_i64, _i32, _i32, _i64, _i64, _i64p]),
+    'vnd_haas_voice_fade_stream_reset_dev': (_int, [_p, _p, _i64, _i64, _i32, _i32, _i64, _i64, _p]),
+    'vnd_haas_voice_fade_stream_f64_dev': (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32,
+                                                  _i32, _i32, _i32, _f64, _p]),
+}
+
 # include/vnd_correlogram_voice_stream.h: the cross-correlogram of a voice pool - positions in the device state, counts and
 # flags per slot and call, float32 or float64 chunks
 _CORRELOGRAM_VOICE_STREAM_ARGS = [_p, _p, _i64, _i64, _p, _p, _i64, _i32, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _f32, _p]
@@ -338,6 +347,7 @@ HEADERS = {
     'vnd_voice_stream.h': VOICE_STREAM_SIGNATURES,
     'vnd_voice_fade_stream.h': VOICE_FADE_STREAM_SIGNATURES,
     'vnd_haas_voice_stream.h': HAAS_VOICE_STREAM_SIGNATURES,
+    'vnd_haas_voice_fade_stream.h': HAAS_VOICE_FADE_STREAM_SIGNATURES,
     'vnd_correlogram_voice_stream.h': CORRELOGRAM_VOICE_STREAM_SIGNATURES,
     'vnd_polar_voice_stream.h': POLAR_VOICE_STREAM_SIGNATURES,
     'vnd_scope.h': SCOPE_SIGNATURES,

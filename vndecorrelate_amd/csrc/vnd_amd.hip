@@ -422,6 +422,7 @@ vnd_status vnd_prepare_launch(vnd_ctx *ctx, const vnd_taps *t, int64_t batch, in
 #include "vnd_voice_stream.hpp"
 #include "vnd_voice_fade_stream.hpp"
 #include "vnd_haas_voice_stream.hpp"
+#include "vnd_haas_voice_fade_stream.hpp"
 #include "vnd_correlogram_voice_stream.hpp"
 #include "vnd_polar_voice_stream.hpp"
 #include "vnd_scope.hpp"

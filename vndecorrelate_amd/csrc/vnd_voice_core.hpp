@@ -1,5 +1,5 @@
-// vnd_voice_core.hpp - what the eight voice pools share (vnd_voice_stream.hpp, vnd_voice_fade_stream.hpp, vnd_haas_voice_stream.hpp,
-// vnd_correlogram_voice_stream.hpp, vnd_polar_voice_stream.hpp, vnd_spectrum_voice_stream.hpp, vnd_scope_voice_stream.hpp,
+// vnd_voice_core.hpp - what the nine voice pools share (vnd_voice_stream.hpp, vnd_voice_fade_stream.hpp, vnd_haas_voice_stream.hpp,
+// vnd_haas_voice_fade_stream.hpp, vnd_correlogram_voice_stream.hpp, vnd_polar_voice_stream.hpp, vnd_spectrum_voice_stream.hpp, vnd_scope_voice_stream.hpp,
 // vnd_level_voice_stream.hpp): the slot rule, the head of the state, the checks of the state and of strided chunks, the
 // reset, and the kernel that moves the positions on.  (vnd_voice_window.hpp: what the last two share beyond it.)
 // (one translation unit: included by vnd_voice_stream.hpp, after vnd_objects.hpp's fail / DeviceScope / HIP_TRY)
@@ -10,8 +10,8 @@
 // stays as stored and it answers -1.  Otherwise the call pushes n = count frames at p and the position becomes END ? 0 :
 // p + n.  2^60 leaves every sum of a position, a count and a pool size far inside int64.  Each pool adds its own part -
 // what comes out, its own bad and idle cases - in its span function, which host and device both call.  cg_voice_span and
-// polar_voice_span start from voice_head; voice_span, and haas_voice_span on top of it, write the same rule out in their
-// own text (vnd_voice_stream.hpp says why).
+// polar_voice_span start from voice_head; voice_span, and haas_voice_span and haas_voice_fade_span on top of it, write the
+// same rule out in their own text (vnd_voice_stream.hpp says why).
 //
 // ORDERING.  Every workgroup of the compute kernel reads pos[b]; within one kernel the workgroups of a slot are not ordered,
 // and the last one out would have to be found with an atomic.  So a second, small kernel follows on the same stream and

@@ -1451,7 +1451,8 @@ def decorrelate_voice_pool(bank: Sequence, *, slots: int, in_channels: int = 2, 
     ``streaming.FadeVoicePool`` (``vnd_voice_fade_stream_f32_dev``): ``pool.process(..., switch={slot: bank_index})`` moves a
     live voice to another bank entry, crossfaded over ``fade_frames`` frames from the first frame the slot has not yet
     returned.  ``fade`` names the gains (``streaming.fade_gains``): ``'linear'``, ``'equal_power'``, or a pair
-    ``(fade_out, fade_in)`` of finite float32 arrays of length ``fade_frames``.  ``None`` returns the pools above."""
+    ``(fade_out, fade_in)`` of finite float32 arrays of length ``fade_frames``.  ``None`` returns the pools above.
+    :func:`decorrelate_fade_voice_pool` is the entry for switchable pools of all three bank kinds."""
     from . import streaming
     bank = list(bank)
     if not bank:
@@ -1484,6 +1485,49 @@ def decorrelate_voice_pool(bank: Sequence, *, slots: int, in_channels: int = 2, 
     return streaming.ChainVoicePool(arrays, tables, delays, slots=slots, in_channels=in_channels,
                                     max_frames_per_call=max_frames_per_call, ms_encode=ms_encode, velvet_width=velvet_width,
                                     delayed_channel=delayed_channel, ms_mode=ms_mode, haas_width=haas_width)
+
+
+def decorrelate_fade_voice_pool(bank: Sequence, *, slots: int, in_channels: int = 2, max_frames_per_call: int = 4800,
+                                fade_frames: int, fade='linear'):
+    """A voice pool whose live voices can move to another entry of the ``bank`` without a click:
+    ``pool.process(..., switch={slot: bank_index})`` crossfades a live voice over ``fade_frames`` frames from the first frame
+    the slot has not yet returned, and ``process_dev`` takes ``streaming.VOICE_SWITCH`` in its flags.  The banks, their
+    checks and their exceptions are :func:`decorrelate_voice_pool`'s; ``fade`` names the gains as there
+    (``streaming.fade_gains``).
+
+    * all plain ``VelvetNoise``: what ``decorrelate_voice_pool(..., fade_frames=fade_frames, fade=fade)`` returns, a
+      ``streaming.FadeVoicePool``.
+    * all ``HaasEffect``: a ``streaming.HaasFadeVoicePool`` (``vnd_haas_voice_fade_stream_f64_dev``): the delayed column
+      fades from the old delay to the new one in float64 - what applies the result of
+      ``optimization.optimize_haas_delay_batched`` to a voice that is running.
+    * all ``VelvetNoise`` -> ``HaasEffect`` ``SignalChain``: a ``streaming.ChainFadeVoicePool``, both stages fading on the
+      same gains from the same output frame.
+
+    A voice that never switches returns the bytes of the pool :func:`decorrelate_voice_pool` builds on the same bank."""
+    from . import streaming
+    bank = list(bank)
+    kinds = {type(d) for d in bank}
+    if fade_frames is None:
+        raise ValueError('decorrelate_fade_voice_pool: fade_frames must be an integer; decorrelate_voice_pool builds the '
+                         'pools whose voices do not switch')
+    if kinds not in ({HaasEffect}, {SignalChain}):            # a velvet bank, and every refusal of an empty or mixed one
+        return decorrelate_voice_pool(bank, slots=slots, in_channels=in_channels, max_frames_per_call=max_frames_per_call,
+                                      fade_frames=fade_frames, fade=fade)
+    if isinstance(in_channels, (bool, np.bool_)) or in_channels not in (1, 2):
+        raise ValueError(f'in_channels must be 1 (mono, fanned out) or 2 (stereo), got {in_channels!r}')
+    gains = streaming.fade_gains(fade_frames, fade)
+    if kinds == {HaasEffect}:
+        delayed_channel, ms_mode, width, delays = _haas_pool_settings(bank, 'decorrelate_fade_voice_pool', 'bank entry')
+        return streaming.HaasFadeVoicePool(delays, slots=slots, in_channels=in_channels,
+                                           max_frames_per_call=max_frames_per_call, delayed_channel=delayed_channel,
+                                           ms_mode=ms_mode, fade_frames=fade_frames, fade_gains=gains, width=width)
+    velvets, haases = _chain_pool_stages(bank)
+    arrays, tables, ms_encode, velvet_width = _velvet_stream_bank(velvets, 'decorrelate_fade_voice_pool', 'bank entry')
+    delayed_channel, ms_mode, haas_width, delays = _haas_pool_settings(haases, 'decorrelate_fade_voice_pool', 'bank entry')
+    return streaming.ChainFadeVoicePool(arrays, tables, delays, slots=slots, in_channels=in_channels,
+                                        max_frames_per_call=max_frames_per_call, fade_frames=fade_frames, fade_gains=gains,
+                                        ms_encode=ms_encode, velvet_width=velvet_width, delayed_channel=delayed_channel,
+                                        ms_mode=ms_mode, haas_width=haas_width)
 
 
 # ----------------------------------------------------------------------------

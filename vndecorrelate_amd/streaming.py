@@ -1160,6 +1160,18 @@ def fade_gains(fade_frames: int, fade='linear') -> np.ndarray:
     return np.ascontiguousarray(np.stack([fall, rise]))
 
 
+def _fade_settings(fade_frames, fade_gains):
+    """``(fade_frames, fade_gains)`` as a crossfading pool keeps them: an int in ``[0, VOICE_FADE_MAX_FRAMES]`` and a finite
+    contiguous float32 ``(2, fade_frames)`` array; ``ValueError`` otherwise."""
+    gains = np.ascontiguousarray(fade_gains)
+    if isinstance(fade_frames, (bool, np.bool_)) or not isinstance(fade_frames, (int, np.integer)) \
+            or not 0 <= fade_frames <= VOICE_FADE_MAX_FRAMES:
+        raise ValueError(f'fade_frames must be an integer in [0, {VOICE_FADE_MAX_FRAMES}], got {fade_frames!r}')
+    if gains.dtype != np.float32 or gains.shape != (2, fade_frames) or not np.isfinite(gains).all():
+        raise ValueError(f'fade_gains must be a finite float32 array of shape (2, {fade_frames})')
+    return int(fade_frames), gains
+
+
 class FadeVoicePool(VoicePool):
     """A :class:`VoicePool` whose live voices change their filter (``decorrelation.decorrelate_voice_pool`` with
     ``fade_frames``, ``vnd_voice_fade_stream_f32_dev``): a voice that switches keeps its position, its history and its
@@ -1179,13 +1191,7 @@ class FadeVoicePool(VoicePool):
 
     def __init__(self, arrays: TapArrays, bank_tables, *, slots: int, in_channels: int, max_frames_per_call: int,
                  fade_frames: int, fade_gains: np.ndarray, ms_encode: bool = False, width: Optional[float] = None):
-        gains = np.ascontiguousarray(fade_gains)
-        if isinstance(fade_frames, (bool, np.bool_)) or not isinstance(fade_frames, (int, np.integer)) \
-                or not 0 <= fade_frames <= VOICE_FADE_MAX_FRAMES:
-            raise ValueError(f'fade_frames must be an integer in [0, {VOICE_FADE_MAX_FRAMES}], got {fade_frames!r}')
-        if gains.dtype != np.float32 or gains.shape != (2, fade_frames) or not np.isfinite(gains).all():
-            raise ValueError(f'fade_gains must be a finite float32 array of shape (2, {fade_frames})')
-        self.fade_frames, self.fade_gains = int(fade_frames), gains
+        self.fade_frames, self.fade_gains = _fade_settings(fade_frames, fade_gains)
         self.transfers = {'to_device': 0, 'to_host': 0}
         self._fade = None                     # (gains on the device or None, fade_left_dev)
         VoicePool.__init__(self, arrays, bank_tables, slots=slots, in_channels=in_channels,
@@ -1484,3 +1490,230 @@ class ChainVoicePool(VoicePool):
         mid, mid_counts = self._mid
         VoicePool._call_device(self, torch, (x, counts, flags, tables), mid, mid_counts)
         return self.haas._call_device(torch, (mid, mid_counts, flags, delays), y, out_counts)
+
+
+# ----------------------------------------------------------------------------
+# Haas and chain voice pools whose live voices change their delay, crossfaded   (include/vnd_haas_voice_fade_stream.h)
+# ----------------------------------------------------------------------------
+def haas_voice_fade_spans(positions, records, counts, flags, delays, max_delay: int, fade_frames: int,
+                          max_frames_per_call: Optional[int] = None):
+    """``(out_counts, new_positions, new_records, fade_left)`` of one call of a crossfading Haas voice pool
+    (``include/vnd_haas_voice_fade_stream.h``), per slot, from the positions and records before the call - ``records`` is
+    int64 ``(slots, 3)``: ``s``, ``old``, ``cur``, the delays in frames - the frames pushed, the ``VOICE_START`` /
+    ``VOICE_END`` / ``VOICE_SWITCH`` flags and the delays of the call alone - what the device computes from its own state::
+
+        work  = n > 0 or START or END or SWITCH       fresh = START or position == 0
+        p = 0 if fresh else position                  e = p + n
+        (old, cur, s) = (delay, delay, -F) if fresh else the record
+        accept = SWITCH and not fresh and p >= s + F:    (old, cur, s) = (cur, delay, p)
+        out_count = n + (max(cur, min(old, max(0, s + F - e))) if END else 0)
+        new position = 0 if END else e                fade_left = 0 if END else min(F, max(0, s + F - e))
+
+    An idle slot (no work) answers 0 and keeps its position and its record.  A bad slot answers -1 twice and keeps both:
+    ``haas_voice_spans``' bad count or position; a delay outside ``[0, max_delay]`` on a call that takes it (fresh with
+    work, or an accepted switch); a stored ``old`` or ``cur`` outside ``[0, max_delay]`` on a slot that goes on with work."""
+    pos, n, start, end, p, bad = _voice_head(positions, counts, flags, max_frames_per_call)
+    rec = np.asarray(records, np.int64)
+    d = np.asarray(delays, np.int64)
+    if rec.shape != pos.shape + (3,) or d.shape != pos.shape:
+        raise ValueError(f'records of shape {pos.shape + (3,)} and delays of shape {pos.shape}, got {rec.shape}, {d.shape}')
+    D, F = int(max_delay), int(fade_frames)
+    p, n = np.where(bad, 0, p), np.where(bad, 0, n)          # (no arithmetic on a bad value)
+    switch = (np.asarray(flags, np.int64) & VOICE_SWITCH) != 0
+    work = (n > 0) | start | end | switch
+    fresh = start | (pos == 0)
+    s, old, cur = rec[..., 0], rec[..., 1], rec[..., 2]
+    kept = (old >= 0) & (old <= D) & (cur >= 0) & (cur <= D)
+    accept = ~bad & ~fresh & kept & switch & (p - F >= s)     # p >= s + F, without a sum a planted s could wrap
+    bad = bad | (((fresh & work) | accept) & ((d < 0) | (d > D))) | (~fresh & work & ~kept)
+    new_s = np.where(fresh, -F, np.where(accept, p, s))
+    new_old = np.where(fresh, d, np.where(accept, cur, old))
+    new_cur = np.where(fresh | accept, d, cur)
+    e = p + n
+    left = np.where(new_s >= e, F, np.where(new_s < e - F, 0, new_s + F - e))
+    ahead = new_s - e                                         # (read only where s >= e: a fade that begins past e)
+    reach = np.where(new_s >= e, np.where(ahead >= new_old, new_old, np.minimum(new_old, ahead + F)),
+                     np.minimum(new_old, left))
+    still = bad | ~work
+    out = np.where(bad, -1, n + np.where(end, np.maximum(new_cur, reach), 0)).astype(np.int64)
+    new = np.where(still, pos, np.where(end, 0, e)).astype(np.int64)
+    records = np.where(still[..., None], rec, np.stack([new_s, new_old, new_cur], axis=-1)).astype(np.int64)
+    fade_left = np.where(bad, -1, np.where(end, 0, left)).astype(np.int64)
+    return out, new, records, fade_left
+
+
+class HaasFadeVoicePool(HaasVoicePool):
+    """A :class:`HaasVoicePool` whose live voices change their delay (``decorrelation.decorrelate_fade_voice_pool`` on a
+    bank of ``HaasEffect``, ``vnd_haas_voice_fade_stream_f64_dev``): a voice that switches keeps its position and its
+    history, and from the first frame it has not yet returned - the delay is causal: its position - its delayed column
+    fades over ``fade_frames`` frames from the delay it had to the new one, ``old * fade_gains[0][j] + new * fade_gains[1][j]``
+    in float64, before the MS decode and the width.  The fade goes on through the tail of an END, which is as long as
+    either delay still contributes.  One fade per voice is in flight: ``fade_left[slot]`` is the number of frames of it the
+    slot has yet to return, and a switch is taken only at 0.  ``records[slot]`` is ``(s, old, cur)``: the first frame of the
+    slot's latest fade and the delays before and after it.  A voice that never switches returns :class:`HaasVoicePool`'s
+    bytes.
+
+    * ``process({slot: block}, start=..., end=..., switch={slot: bank_index})`` - the dict form, with
+      :class:`FadeVoicePool`'s refusals before any device call: a switch on a slot with no live voice, together with a
+      start of that slot, to an index outside the bank, or while ``fade_left[slot] > 0``.  One upload and one download.
+    * ``process_dev(x, counts, flags, delays)`` - flags may carry ``VOICE_SWITCH``, and ``delays[b]`` is read when a voice
+      begins and when its switch is accepted; a switch that comes while ``fade_left_dev[b] > 0`` is ignored.
+      ``(y, out_counts)`` are :class:`HaasVoicePool`'s, so every meter attaches unchanged; ``fade_left_dev`` is the pool's
+      own int32 ``(slots,)`` tensor at a fixed address, written by every call."""
+
+    def __init__(self, bank_delays, *, slots: int, in_channels: int, max_frames_per_call: int, delayed_channel: int,
+                 ms_mode: bool, fade_frames: int, fade_gains: np.ndarray, width: Optional[float] = None):
+        self.fade_frames, self.fade_gains = _fade_settings(fade_frames, fade_gains)
+        self.transfers = {'to_device': 0, 'to_host': 0}
+        self._fade = None                     # (gains on the device or None, fade_left_dev)
+        HaasVoicePool.__init__(self, bank_delays, slots=slots, in_channels=in_channels,
+                               max_frames_per_call=max_frames_per_call, delayed_channel=delayed_channel, ms_mode=ms_mode,
+                               width=width)
+
+    def _mirror(self):
+        HaasVoicePool._mirror(self)
+        self.records = np.zeros((self.slots, 3), np.int64)        # (s, old, cur); a slot at position 0 takes its own from the call
+        self.fade_left = np.zeros(self.slots, np.int64)
+
+    fade_left_dev = FadeVoicePool.fade_left_dev
+
+    def process(self, blocks=None, *, start=None, end=(), switch=None, discard: bool = False):
+        """:meth:`HaasVoicePool.process` with ``switch``: ``{slot: bank_index}``, the live voices that change to another
+        bank entry's delay with this call.  The fade begins at the first frame the slot returns in this call."""
+        return FadeVoicePool.process(self, blocks, start=start, end=end, switch=switch, discard=discard)
+
+    def _spans(self, counts, flags, delays):
+        out, positions, records, fade_left = haas_voice_fade_spans(self.positions, self.records, counts, flags, delays,
+                                                                   self.max_delay, self.fade_frames, self.max_frames_per_call)
+        return out, (positions, records, fade_left)
+
+    _commit = FadeVoicePool._commit
+
+    # ---- the device -------------------------------------------------------------------------
+    def _state_bytes(self, ctx) -> int:
+        from . import _native_haas_fade
+        return _native_haas_fade.haas_voice_fade_stream_state_bytes(self.slots, self.in_channels, self.max_delay,
+                                                                    self.max_frames_per_call, self.fade_frames)
+
+    def _allocate(self, torch, ctx):
+        HaasVoicePool._allocate(self, torch, ctx)
+        device = torch.device('cuda', ctx.device)
+        gains = torch.from_numpy(self.fade_gains).to(device) if self.fade_frames else None     # uploaded once
+        self._fade = (gains, torch.zeros((self.slots,), dtype=torch.int32, device=device))
+
+    def _reset_entry(self, ctx, state_ptr, state_bytes, stream):
+        from . import _native_haas_fade
+        _native_haas_fade.haas_voice_fade_stream_reset_device(ctx, state_ptr, state_bytes, self.slots, self.in_channels,
+                                                              self.max_delay, self.max_frames_per_call, self.fade_frames,
+                                                              stream=stream)
+
+    def _call_host(self, x, counts, flags, delays):
+        """One upload (the blocks and the three int32 arrays in one buffer), the call, one download (y and out_counts)."""
+        return self._call_host_packed(x, (counts, flags, delays))
+
+    def _launch(self, ctx, state_ptr, state_bytes, inputs, y, out_counts, stream):
+        from . import _native_haas_fade
+        x, counts, flags, delays = inputs
+        gains, fade_left = self._fade
+        _native_haas_fade.haas_voice_fade_stream_device(
+            ctx, state_ptr, state_bytes, self.max_frames_per_call, self.fade_frames,
+            None if gains is None else gains.data_ptr(), x.data_ptr(), counts.data_ptr(), flags.data_ptr(), delays.data_ptr(),
+            y.data_ptr(), out_counts.data_ptr(), fade_left.data_ptr(), self.slots, self.in_channels, max_delay=self.max_delay,
+            delayed_channel=self.delayed_channel, ms_mode=self.ms_mode, width=self.width, stream=stream)
+
+
+class ChainFadeVoicePool(FadeVoicePool):
+    """A :class:`ChainVoicePool` whose live voices change their bank entry - filter and delay together
+    (``decorrelation.decorrelate_fade_voice_pool`` on a bank of ``SignalChain``): :class:`FadeVoicePool`
+    (``vnd_voice_fade_stream_f32_dev``) and then :class:`HaasFadeVoicePool` (``vnd_haas_voice_fade_stream_f64_dev``),
+    composed as :class:`ChainVoicePool` composes its stages: stage 2 has ``max_frames_per_call = M + H``, reads stage 1's
+    ``out_counts`` from device memory as its counts, and gets the caller's ``flags`` - ``VOICE_SWITCH`` included - and
+    ``delays``, with the same ``fade_frames`` and gains.  The contract is composition: for every schedule the result is
+    :class:`HaasFadeVoicePool`'s rule applied to what :class:`FadeVoicePool` returned.  Stage 2's position is the number of
+    frames stage 1 has returned, so a switch both stages accept starts both fades at the same output frame.
+
+    One corner: while a voice is inside its first H frames stage 1 has returned nothing, so stage 2 stands at position 0
+    and is *fresh*: a switch there gives stage 2 the new delay without a fade, where stage 1 fades its filter.
+
+    ``fade_left`` and ``fade_left_dev`` are the elementwise maximum of the two stages'; on the device the maximum is
+    written into the pool's own tensor by every call.  ``records`` are stage 1's and ``haas_records`` stage 2's.
+    ``process(..., switch={slot: bank_index})`` refuses a switch while ``fade_left[slot] > 0``, so in the dict form both
+    stages take a switch or - at the corner above - stage 2 takes it fresh; ``process_dev(x, counts, flags, tables,
+    delays)`` lets each stage apply its own rule.  ``(y, out_counts)`` are :class:`ChainVoicePool`'s."""
+
+    _out_dtype = np.float64
+
+    def __init__(self, arrays: TapArrays, bank_tables, bank_delays, *, slots: int, in_channels: int, max_frames_per_call: int,
+                 fade_frames: int, fade_gains: np.ndarray, ms_encode: bool, velvet_width: Optional[float],
+                 delayed_channel: int, ms_mode: bool, haas_width: Optional[float]):
+        FadeVoicePool.__init__(self, arrays, bank_tables, slots=slots, in_channels=in_channels,
+                               max_frames_per_call=max_frames_per_call, fade_frames=fade_frames, fade_gains=fade_gains,
+                               ms_encode=ms_encode, width=velvet_width)
+        self.bank_delays = np.ascontiguousarray(bank_delays, np.int32)
+        if self.bank_delays.shape != self.bank_tables.shape or self.bank_delays.min() < 0:
+            raise ValueError('bank_delays: one delay >= 0 per bank entry')
+        self.haas = HaasFadeVoicePool(self.bank_delays, slots=slots, in_channels=2,
+                                      max_frames_per_call=self.max_frames_per_call + self.latency_frames,
+                                      delayed_channel=delayed_channel, ms_mode=ms_mode, fade_frames=self.fade_frames,
+                                      fade_gains=self.fade_gains, width=haas_width)
+        self.max_delay = self.tail_frames = self.haas.max_delay
+        self._mid = None                      # (float32 (slots, M + H, 2), int32 (slots,)): stage 1's result, on the device
+        self._left = None                     # int32 (slots,): the maximum of the stages' fade_left, on the device
+        self._inputs += _slot_ints(self.slots, 'delays')
+        self._outputs = self.haas._outputs    # stage 2's, as ChainVoicePool: stage 1 always gets _mid
+
+    def _mirror(self):
+        FadeVoicePool._mirror(self)
+        self.haas_positions = np.zeros(self.slots, np.int64)      # stage 2's: the frames stage 1 has returned
+        self.haas_records = np.zeros((self.slots, 3), np.int64)
+
+    row_frames = ChainVoicePool.row_frames
+    reset = ChainVoicePool.reset
+
+    @property
+    def fade_left_dev(self):
+        """The int32 ``(slots,)`` device tensor every call writes the maximum of the two stages' ``fade_left`` to;
+        allocated by ``reset()``."""
+        if self._left is None:
+            raise RuntimeError('fade_left_dev is allocated with the state: call reset() first')
+        return self._left
+
+    def process_dev(self, x, counts, flags, tables, delays, *, out=None):
+        """:meth:`ChainVoicePool.process_dev`, where flags may carry ``VOICE_SWITCH``: stage 1 reads ``tables[b]`` and stage
+        2 ``delays[b]`` when a voice begins and when that stage accepts the switch."""
+        return self._process_dev((x, counts, flags, tables, delays), out)
+
+    def _spans(self, counts, flags, entries):
+        mid, first, records, left = voice_fade_spans(self.positions, self.records, counts, flags, self.bank_tables[entries],
+                                                     self.latency_frames, self.fade_frames, self.max_frames_per_call)
+        out, second, haas_records, haas_left = haas_voice_fade_spans(
+            self.haas_positions, self.haas_records, mid, flags, self.bank_delays[entries], self.max_delay, self.fade_frames,
+            self.haas.max_frames_per_call)
+        return out, (first, records, second, haas_records, np.maximum(left, haas_left))
+
+    _per_slot = ChainVoicePool._per_slot
+    _slot_value = ChainVoicePool._slot_value
+
+    def _commit(self, state):
+        self.positions, self.records, self.haas_positions, self.haas_records, self.fade_left = state
+
+    # ---- the device -------------------------------------------------------------------------
+    def _allocate(self, torch, ctx):
+        FadeVoicePool._allocate(self, torch, ctx)
+        device = torch.device('cuda', ctx.device)
+        self._mid = (torch.empty((self.slots, self.haas.max_frames_per_call, 2), dtype=torch.float32, device=device),
+                     torch.empty((self.slots,), dtype=torch.int32, device=device))
+        self._left = torch.zeros((self.slots,), dtype=torch.int32, device=device)
+
+    _call_host = ChainVoicePool._call_host
+
+    def _call_device(self, torch, inputs, y, out_counts):
+        x, counts, flags, tables, delays = inputs
+        ctx = _native.default_context()
+        self._ensure_state(torch, ctx)
+        self.haas._ensure_state(torch, ctx)
+        mid, mid_counts = self._mid
+        VoicePool._call_device(self, torch, (x, counts, flags, tables), mid, mid_counts)
+        out = self.haas._call_device(torch, (mid, mid_counts, flags, delays), y, out_counts)
+        torch.maximum(self._fade[1], self.haas._fade[1], out=self._left)       # (no allocation: capturable)
+        return out
