@@ -331,6 +331,17 @@ LEVEL_VOICE_STREAM_SIGNATURES = {
     'vnd_polar_level_voice_stream_levels_f64_dev': (_int, _LEVEL_VOICE_LEVELS_ARGS),
 }
 
+# include/vnd_haas_scan_voice_stream.h: the Haas-delay scan of a voice pool - positions, fills, heads and the ring of input
+# frames in the device state; a push per block, (slot, delay) pairs scored from the state alone (wrappers: _native_haas_scan_voice.py)
+HAAS_SCAN_VOICE_STREAM_SIGNATURES = {
+    'vnd_haas_scan_voice_stream_state_bytes': (_int, [_i64, _i64, _i64, _i32, _i64p]),
+    'vnd_haas_scan_voice_stream_reset_dev': (_int, [_p, _p, _i64, _i64, _i64, _i64, _i32, _p]),
+    'vnd_haas_scan_voice_stream_push_f32_dev': (_int, [_p, _p, _i64, _i64, _i64, _p, _i32, _p, _p, _p, _i64, _p]),
+    'vnd_haas_scan_voice_stream_workspace_bytes': (_int, [_i64, _i32, _i32, _i64p]),
+    'vnd_haas_scan_voice_stream_pairs_f64_dev': (_int, [_p, _p, _i64, _i64, _i64, _i32, _i64, _p, _p, _i32, _i32, _i32, _i32, _i32,
+                                                        _f64, _p, _p, _i64, _p]),
+}
+
 # header under include/ -> its table: load_library declares all of them, and a new header is one line here
 HEADERS = {
     'vnd_amd.h': SIGNATURES,
@@ -356,6 +367,7 @@ HEADERS = {
     'vnd_spectrum_voice_stream.h': SPECTRUM_VOICE_STREAM_SIGNATURES,
     'vnd_scope_voice_stream.h': SCOPE_VOICE_STREAM_SIGNATURES,
     'vnd_polar_level_voice_stream.h': LEVEL_VOICE_STREAM_SIGNATURES,
+    'vnd_haas_scan_voice_stream.h': HAAS_SCAN_VOICE_STREAM_SIGNATURES,
 }
 
 _lib = None

@@ -14,6 +14,7 @@
 //   vnd_stream.hpp       chunked streaming of the tap sum (include/vnd_stream.h); the ring of every float32 block stream
 //   vnd_haas_stream.hpp  chunked streaming of the HaasEffect delay, one for the pool or one per stream (include/vnd_haas_stream.h, vnd_each_stream.h)
 //   vnd_each_stream.hpp  a pool streamed through one filter per stream (include/vnd_each_stream.h)
+//   vnd_haas_scan_voice_stream.hpp  the Haas-delay scan over the windows a voice pool keeps (include/vnd_haas_scan_voice_stream.h)
 #include "vnd_objects.hpp"
 #include "vnd_plan.hpp"
 
@@ -432,4 +433,5 @@ vnd_status vnd_prepare_launch(vnd_ctx *ctx, const vnd_taps *t, int64_t batch, in
 #include "vnd_voice_window.hpp"
 #include "vnd_scope_voice_stream.hpp"
 #include "vnd_level_voice_stream.hpp"
+#include "vnd_haas_scan_voice_stream.hpp"
 #include "vnd_hooks.hpp"

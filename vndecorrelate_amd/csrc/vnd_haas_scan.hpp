@@ -19,6 +19,9 @@
 // partial, then a fixed-order reduction of pair p's ceil((n + d_p) / kHsTile) partials.  Neither the other pairs of a
 // launch, nor their order, nor the launch's extent enter pair p's order, so results are bit-identical across runs
 // and across how the pairs are ordered and split into launches.
+//
+// The two kernels' bodies are templates over where a signal's frames come from (HsFrames below: a contiguous pool), so
+// that vnd_haas_scan_voice_stream.hpp can run the same text over the rings of a voice pool and the two cannot drift.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -36,6 +39,22 @@ constexpr int kHsTile = kHsThreads * kHsPer;            // 2048 frames per workg
 constexpr int kHsBlock = 16;                            // pairs per workgroup
 constexpr int kHsWin = 4096;                            // staged delayed-column doubles (32 KB of LDS)
 
+__host__ __device__ __forceinline__ int64_t hs_chunks(int64_t frames) { return (frames + kHsTile - 1) / kHsTile; }
+
+// Where a run's frames come from.  The scan's body (hs_scan_body, hs_reduce_body) is written once over an Args type with
+//   signal(f)    the signal of pair f, as stored (any int32)
+//   valid(s, d)  whether pair (s, d) is inside the contract - nothing is addressed with an s or a d that is not
+//   open(s)      the frames of a valid signal s (workgroup-uniform): n, and column(h, c, k), column c of the padded buffer
+//                before the roll at frame k - zero outside [0, n)
+// and the fields h, delays, partials, moments, F and cap.  Two instantiations: HsArgs below, a contiguous pool
+// x[batch][n][Cx] where every signal has h.n frames, and HsRingArgs of vnd_haas_scan_voice_stream.hpp, the windows a voice
+// pool keeps in rings, each with a length of its own.
+struct HsFrames {
+    const float *__restrict__ xs;                       // [n][Cx]
+    int64_t n;
+    __device__ __forceinline__ double column(const HArgs &h, int c, int64_t k) const { return haas_column(h, xs, c, k); }
+};
+
 struct HsArgs {
     HArgs h;                                            // pool (h.x, h.n, h.Cx) and the shared configuration
     const int32_t *__restrict__ signals;                // [F] signal of each pair; nullptr: every pair is signal 0
@@ -45,16 +64,13 @@ struct HsArgs {
     int32_t F;                                          // pairs
     int32_t batch;                                      // signals in the pool
     int64_t cap;                                        // partials per pair the workspace holds
+    __device__ __forceinline__ int32_t signal(int f) const { return signals ? signals[f] : 0; }
+    __device__ __forceinline__ bool valid(int32_t s, int32_t d) const
+    {
+        return s >= 0 && s < batch && d >= 0 && hs_chunks(h.n + d) <= cap;
+    }
+    __device__ __forceinline__ HsFrames open(int32_t s) const { return {h.x + (int64_t)s * h.n * h.Cx, h.n}; }
 };
-
-__device__ __forceinline__ int64_t hs_chunks(int64_t frames) { return (frames + kHsTile - 1) / kHsTile; }
-
-__device__ __forceinline__ bool hs_valid(const HsArgs &a, int32_t s, int32_t d)
-{
-    return s >= 0 && s < a.batch && d >= 0 && hs_chunks(a.h.n + d) <= a.cap;
-}
-
-__device__ __forceinline__ int32_t hs_signal(const HsArgs &a, int f) { return a.signals ? a.signals[f] : 0; }
 
 // fixed-order sum (max for slot 4) of v over the workgroup; the result is valid in thread 0
 __device__ __forceinline__ void hs_block_reduce(double v[kMoments], double (*red)[kMoments])
@@ -83,8 +99,9 @@ __device__ __forceinline__ void hs_block_reduce(double v[kMoments], double (*red
     __syncthreads();                                    // red[] is free for the next candidate
 }
 
-// grid = (tiles, ceil(F / kHsBlock))
-__global__ __launch_bounds__(kHsThreads) void haas_scan_kernel(const HsArgs a)
+// The scan of one workgroup: tile blockIdx.x of the block of pairs blockIdx.y.  grid = (tiles, ceil(F / kHsBlock))
+template <class Args>
+__device__ __forceinline__ void hs_scan_body(const Args &a)
 {
     __shared__ double hist[kHsWin];
     __shared__ double red[kHsThreads / 64][kMoments];
@@ -93,9 +110,9 @@ __global__ __launch_bounds__(kHsThreads) void haas_scan_kernel(const HsArgs a)
     const int f0 = blockIdx.y * kHsBlock;
     const int nb = min(kHsBlock, a.F - f0);
     if ((int)threadIdx.x < nb) {
-        const int32_t s = hs_signal(a, f0 + threadIdx.x), d = a.delays[f0 + threadIdx.x];
+        const int32_t s = a.signal(f0 + threadIdx.x), d = a.delays[f0 + threadIdx.x];
         sl[threadIdx.x] = s;
-        dl[threadIdx.x] = hs_valid(a, s, d) ? d : -1;
+        dl[threadIdx.x] = a.valid(s, d) ? d : -1;
     }
     __syncthreads();
     if ((int)threadIdx.x < nb && (threadIdx.x == 0 || sl[threadIdx.x - 1] != sl[threadIdx.x])) {
@@ -115,32 +132,33 @@ __global__ __launch_bounds__(kHsThreads) void haas_scan_kernel(const HsArgs a)
         r1 = run[r0][0];
         const int32_t s = __builtin_amdgcn_readfirstlane(sl[r0]);
         const int32_t dmin = run[r0][1], dmax = run[r0][2];
-        if (dmax < 0 || t0 >= h.n + dmax) continue;     // no pair of the run reaches this tile
-        const float *__restrict__ xs = h.x + (int64_t)s * h.n * h.Cx;
+        if (dmax < 0) continue;                         // no pair of the run is inside the contract
+        const auto x = a.open(s);                       // (s is valid: a pair of the run is)
+        if (t0 >= x.n + dmax) continue;                 // no pair of the run reaches this tile
         // the delayed column over [t0 - dmax, t0 + kHsTile - dmin)
         const int64_t span = (int64_t)kHsTile + dmax - dmin;
         const bool staged = span <= kHsWin;
         if (staged) {
             __syncthreads();                            // the previous run's readers are done with hist
             const int64_t k0 = t0 - dmax;
-            for (int i = threadIdx.x; i < span; i += kHsThreads) hist[i] = haas_column(h, xs, cd, k0 + i);
+            for (int i = threadIdx.x; i < span; i += kHsThreads) hist[i] = x.column(h, cd, k0 + i);
             __syncthreads();
         }
         double und[kHsPer];                             // the undelayed column at this lane's frames
 #pragma unroll
-        for (int j = 0; j < kHsPer; ++j) und[j] = haas_column(h, xs, cu, t0 + threadIdx.x + j * kHsThreads);
+        for (int j = 0; j < kHsPer; ++j) und[j] = x.column(h, cu, t0 + threadIdx.x + j * kHsThreads);
 
         for (int c = r0; c < r1; ++c) {
             const int32_t d = __builtin_amdgcn_readfirstlane(dl[c]);
             if (d < 0) continue;
-            const int64_t len = h.n + d;
+            const int64_t len = x.n + d;
             if (t0 >= len) continue;                    // (uniform) pair c has no frame here
             PolarAcc64 acc;
 #pragma unroll
             for (int j = 0; j < kHsPer; ++j) {
                 const int64_t k = t0 + threadIdx.x + j * kHsThreads;
                 if (k < len) {
-                    const double del = staged ? hist[(k - t0) + (dmax - d)] : haas_column(h, xs, cd, k - d);
+                    const double del = staged ? hist[(k - t0) + (dmax - d)] : x.column(h, cd, k - d);
                     double v[2];
                     haas_frame(h, cu == 0 ? und[j] : del, cu == 0 ? del : und[j], v);
                     polar_add64(acc, v[0], v[1]);
@@ -158,16 +176,20 @@ __global__ __launch_bounds__(kHsThreads) void haas_scan_kernel(const HsArgs a)
     }
 }
 
+__global__ __launch_bounds__(kHsThreads) void haas_scan_kernel(const HsArgs a) { hs_scan_body(a); }
+
 // One workgroup per pair: lanes stride over its ceil((n + d) / kHsTile) partials, then the fixed tree.  A pair
-// outside the contract (signal outside [0, batch), negative delay, or more partials than the workspace holds) gets
-// NaN moments.
-__global__ __launch_bounds__(kHsThreads) void haas_scan_reduce_kernel(const HsArgs a)
+// outside the contract (for HsArgs: signal outside [0, batch), negative delay, or more partials than the workspace
+// holds) gets NaN moments.
+template <class Args>
+__device__ __forceinline__ void hs_reduce_body(const Args &a)
 {
     __shared__ double red[kHsThreads / 64][kMoments];
     const int f = blockIdx.x;
     const int32_t d = a.delays[f];
-    const bool ok = hs_valid(a, hs_signal(a, f), d);
-    const int64_t chunks = ok ? hs_chunks(a.h.n + d) : 0;
+    const int32_t s = a.signal(f);
+    const bool ok = a.valid(s, d);
+    const int64_t chunks = ok ? hs_chunks(a.open(s).n + d) : 0;
     double v[kMoments];
 #pragma unroll
     for (int k = 0; k < kMoments; ++k) v[k] = 0.0;
@@ -182,6 +204,8 @@ __global__ __launch_bounds__(kHsThreads) void haas_scan_reduce_kernel(const HsAr
         for (int k = 0; k < kMoments; ++k) a.moments[(int64_t)f * kMoments + k] = ok ? v[k] : __builtin_nan("");
     }
 }
+
+__global__ __launch_bounds__(kHsThreads) void haas_scan_reduce_kernel(const HsArgs a) { hs_reduce_body(a); }
 
 }  // namespace vnd
 

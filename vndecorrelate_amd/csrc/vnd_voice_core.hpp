@@ -1,7 +1,7 @@
-// vnd_voice_core.hpp - what the nine voice pools share (vnd_voice_stream.hpp, vnd_voice_fade_stream.hpp, vnd_haas_voice_stream.hpp,
+// vnd_voice_core.hpp - what the ten voice pools share (vnd_voice_stream.hpp, vnd_voice_fade_stream.hpp, vnd_haas_voice_stream.hpp,
 // vnd_haas_voice_fade_stream.hpp, vnd_correlogram_voice_stream.hpp, vnd_polar_voice_stream.hpp, vnd_spectrum_voice_stream.hpp, vnd_scope_voice_stream.hpp,
-// vnd_level_voice_stream.hpp): the slot rule, the head of the state, the checks of the state and of strided chunks, the
-// reset, and the kernel that moves the positions on.  (vnd_voice_window.hpp: what the last two share beyond it.)
+// vnd_level_voice_stream.hpp, vnd_haas_scan_voice_stream.hpp): the slot rule, the head of the state, the checks of the state and
+// of strided chunks, the reset, and the kernel that moves the positions on.  (vnd_voice_window.hpp: what the last three share beyond it.)
 // (one translation unit: included by vnd_voice_stream.hpp, after vnd_objects.hpp's fail / DeviceScope / HIP_TRY)
 //
 // THE SLOT RULE.  A pool's state begins with one int64 position per slot; a call brings a count and START / END flags per

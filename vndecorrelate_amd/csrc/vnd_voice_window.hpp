@@ -1,6 +1,7 @@
-// vnd_voice_window.hpp - what the two window pools share (vnd_scope_voice_stream.hpp, vnd_level_voice_stream.hpp): the slot
-// rule, the walk of a workgroup over its frames and their ring entries, the scalar side of the plan and the radius_scale check.
-// (one translation unit: included by vnd_amd.hip after vnd_scope.hpp and vnd_voice_core.hpp, before the two pools' files)
+// vnd_voice_window.hpp - what the window pools share (vnd_scope_voice_stream.hpp, vnd_level_voice_stream.hpp,
+// vnd_haas_scan_voice_stream.hpp): the slot rule, the walk of a workgroup over its frames and their ring entries, the scalar
+// side of the plan and the radius_scale check.
+// (one translation unit: included by vnd_amd.hip after vnd_scope.hpp and vnd_voice_core.hpp, before the pools' files)
 //
 // A window pool keeps, per slot, a ring of W entries behind the positions: entry g mod W belongs to the voice's frame g.  A
 // call brings the frames [p, p + n) of each slot, n <= M, and a launch of grid (ceil(M / kScopeVoiceSpan), slots) with
@@ -10,7 +11,8 @@
 // Ring.  M <= W, so the frames [p, p + n) of one call have n <= W distinct residues mod W: every ring entry a call touches is
 // read and written by the one lane that owns its frame, and no lane races another although the workgroups of a slot are
 // unordered.  The ring is never cleared: each pool says in its own file which entries it may read (the scope pool entry
-// g mod W only for g >= W, when frame g - W of THIS voice wrote it; the level pool the prefix its fill names).
+// g mod W only for g >= W, when frame g - W of THIS voice wrote it; the level pool the prefix its fill names; the Haas scan
+// pool the fill entries that end before its head).
 //
 // Every index that is built from device data:
 //   - counts[b] outside [0, M], or pos[b] outside [0, 2^60] without START: the span is not ok and every kernel leaves before

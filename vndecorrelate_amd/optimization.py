@@ -39,9 +39,11 @@ import numpy as np
 from numpy.typing import NDArray
 
 from . import _native, analysis
+from . import _native_haas_scan_voice as _scan_native
 from . import decorrelation as _dec
 from .bounded import minimize_bounded_lockstep, round_half_even
 from .decorrelation import Decorrelator, HaasEffect, VelvetNoise
+from .streaming import VOICE_START, _check_device_tensors, _MeterPool, _slot_ints, _SlotPool, _valid_voice_spans
 from .taps import TapArrays, class_path_bank_arrays
 from .utils.dsp import EPSILON, LayoutMode, polar_coordinates, to_float32
 
@@ -589,6 +591,336 @@ def optimize_haas_delay_batched(*, input_signals, sample_rate_hz: int, max_delay
         out.append(haas_search(_DevicePairScorer(ctx, pool, weights), part.shape[0], taus, sample_rate_hz, grid_size,
                                stats))
     return np.concatenate(out)
+
+
+# ---- the Haas-delay scan of a voice pool (include/vnd_haas_scan_voice_stream.h) ---------------------------------------
+def haas_scan_voice_spans(positions, fills, heads, counts, flags, window_frames: int,
+                          max_frames_per_call: Optional[int] = None):
+    """``(valid, new_positions, new_fills, new_heads)`` of one push of a :class:`HaasScanVoicePool`
+    (``include/vnd_haas_scan_voice_stream.h``), per slot, from the state before the call, the frames pushed and the
+    ``VOICE_START`` / ``VOICE_END`` flags alone - what the device computes from its own state::
+
+        p = START ? 0 : position      valid = 1, or 0 for n = 0 without a flag      new position = END ? 0 : p + n
+        fill = min(p + n, W)          head = (p + n) mod W                          (of a slot that answers 1)
+
+    The slot's window in time order is then the ring entries ``(head - fill + k) mod W``, ``k in [0, fill)``.  A count
+    below 0 (or above ``max_frames_per_call``, when given), or without START a position outside ``[0, 2^60]``, answers -1;
+    such a slot and an idle one keep position, fill and head."""
+    W = int(window_frames)
+    if W < 1:
+        raise ValueError(f'window_frames must be >= 1, got {window_frames}')
+    valid, new = _valid_voice_spans(positions, counts, flags, max_frames_per_call)
+    fills, heads = np.asarray(fills, np.int64), np.asarray(heads, np.int64)
+    if not (fills.shape == heads.shape == valid.shape):
+        raise ValueError(f'fills and heads of the shape of positions, got {fills.shape} and {heads.shape}')
+    answered = valid == 1
+    start = (np.asarray(flags, np.int64) & VOICE_START) != 0
+    p = np.where(start | ~answered, 0, np.asarray(positions, np.int64))       # (no arithmetic on a bad value)
+    q = p + np.where(answered, np.asarray(counts, np.int64), 0)
+    return (valid, new, np.where(answered, np.minimum(q, W), fills).astype(np.int64),
+            np.where(answered, q % W, heads).astype(np.int64))
+
+
+class HaasScanVoicePool(_MeterPool):
+    """The last ``window_frames`` input frames of ``slots`` voices, each with a life of its own, kept on the device to
+    score candidate Haas delays against (:func:`haas_scan_voice_pool`; ``vnd_haas_scan_voice_stream_*``): voices start and
+    end on any call and push blocks of any size up to ``max_frames_per_call`` or none, by the slot rule of the other
+    meters (:func:`haas_scan_voice_spans`).  The device state keeps a ring of input frames per slot, and beside the
+    position how many entries are the voice's (``fill``) and where its next frame goes (``head``): a delay depends on the
+    order of the frames.  A (slot, delay) pair's row of moments is ``vnd_haas_pairs_f64_dev``'s for the slot's window as
+    a contiguous signal, bit for bit, whatever the schedule.  An END leaves the window readable; the slot's next voice
+    drops it.  One ``HaasEffect`` configuration per pool: ``delayed_channel``, ``mode``, ``width``.
+
+    Pushing and scanning are two device entries: blocks arrive a hundred times a second, a voice is re-optimised now and
+    then.  Two forms of the push; a pool is used through one of them (mixing them raises ``RuntimeError`` until
+    ``reset()``):
+
+    * ``process({slot: block}, start=[slot, ...], end=[slot, ...], discard=False)`` - float32 ``(n, in_channels)`` NumPy
+      blocks in, ``{slot: None}`` out for every slot that got a block, started or ended.  One upload, and ``valid`` alone
+      comes down.  Every refusal comes before any device call.
+    * ``process_dev(x, counts, flags)`` - ``x`` float32 ``(slots, max_frames_per_call, in_channels)`` and int32
+      ``(slots,)`` ``counts`` and ``flags`` on the device, a fading pool's own if it has one (``VOICE_SWITCH`` is
+      ignored); returns ``valid``.  It only enqueues on the current stream and can be captured with
+      ``torch.cuda.graph`` after a ``reset()``.
+
+    The scan reads the state alone and goes with either form: :meth:`scan_dev` and :meth:`pairs_dev` on device tensors,
+    :meth:`scan` from NumPy, :meth:`scores` for the objective, :meth:`optimize` for the reference's whole search."""
+
+    _out_dtype = np.float64
+
+    def __init__(self, slots: int, *, in_channels: int, max_frames_per_call: int, window_frames: int, max_delay: int,
+                 sample_rate_hz=None, max_delay_seconds=None, delayed_channel: int = 0, ms_mode: bool = False,
+                 width: Optional[float] = None):
+        _MeterPool.__init__(self, slots, max_frames_per_call, 'float32')
+        if isinstance(in_channels, (bool, np.bool_)) or in_channels not in (1, 2):
+            raise ValueError(f'a pool of mono (1) or stereo (2) voices is taken, got in_channels={in_channels!r}')
+        for name, value in (('window_frames', window_frames), ('max_delay', max_delay)):
+            if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or value < 0:
+                raise ValueError(f'{name} must be a non-negative integer, not {value!r}')
+        if window_frames < self.max_frames_per_call:
+            raise ValueError(f'window_frames {window_frames} below max_frames_per_call {self.max_frames_per_call}: two '
+                             'frames of one call would share a ring entry')
+        if window_frames > _INT32_MAX or max_delay > _INT32_MAX:
+            raise ValueError(f'window_frames {window_frames} and max_delay {max_delay} must stay below 2**31')
+        if delayed_channel not in (0, 1) or isinstance(delayed_channel, (bool, np.bool_)):
+            raise ValueError(f'delayed_channel must be 0 or 1, got {delayed_channel!r}')
+        if width is not None and not np.isfinite(float(width)):
+            raise ValueError(f'width must be a finite number or None, got {width!r}')
+        self.in_channels = int(in_channels)
+        self.window_frames, self.max_delay = int(window_frames), int(max_delay)
+        self.sample_rate_hz, self.max_delay_seconds = sample_rate_hz, max_delay_seconds
+        self.delayed_channel, self.ms_mode, self.width = int(delayed_channel), bool(ms_mode), width
+        if self.slots * -(-self.max_frames_per_call // 1024) > 1 << 23:       # the copy's grid: 1024 frames a workgroup
+            raise ValueError(f'{self.slots} slots of {self.max_frames_per_call} frames per call are more than one launch '
+                             'takes: split the pool')
+        S = self.slots
+        self._inputs = (('x', (S, self.max_frames_per_call, self.in_channels), 'float32', None),) \
+            + _slot_ints(S, 'counts', 'flags')
+        self._valid_spec = (('valid', (S,), 'int32', 'empty'),)
+        self._valid = None                    # the pool's own valid, at a fixed address
+        self._grids = {}                      # D -> (slot index, delays, moments) of the full grid, on the device
+        self._workspace = None
+        self._mirror()
+
+    @property
+    def chunks_per_pair(self) -> int:
+        """The partials a pair can have: ``ceil((window_frames + max_delay) / 2048)``, the scan's grid along the frames."""
+        return -(-(self.window_frames + self.max_delay) // 2048)
+
+    # ---- the push ---------------------------------------------------------------------------
+    def process(self, blocks=None, *, start=(), end=(), discard: bool = False):
+        """One push of the dict form.  ``blocks``: ``{slot: float32 (n, in_channels) array}`` (``(n,)`` as well for
+        mono), ``0 <= n <= max_frames_per_call``; ``start``: the slots whose voice begins with this call; ``end``: the
+        slots whose voice ends with it.  Returns ``{slot: None}`` for every slot that got a block, started or ended: a
+        push computes nothing, :meth:`scan` does.  Raises before any device call, as the other voice pools do:
+        ``ValueError`` for a slot outside the pool or named twice, a block or an end for a slot that was never started,
+        a start on a live slot (``discard=True`` allows it: the voice it held is dropped), a block above
+        ``max_frames_per_call`` or of another channel count; ``TypeError`` for a block that is not float32."""
+        return self._process_valid(blocks, start, end, discard, None, False)
+
+    def process_dev(self, x, counts, flags, *, valid=None):
+        """One push on device tensors, enqueued on the current stream: ``x`` float32 ``(slots, M, in_channels)``,
+        ``counts`` / ``flags`` int32 ``(slots,)``.  Returns ``valid``, int32 ``(slots,)``: the pool's own tensor at a
+        fixed address unless ``valid=`` gives the caller's.  No check reads device memory; bad per-slot values answer -1
+        (``include/vnd_haas_scan_voice_stream.h``)."""
+        if self._form == 'dict':
+            self._require_form('dev')
+        _check_device_tensors((x, counts, flags), self._inputs)
+        _check_device_tensors((valid,), self._valid_spec)
+        valid = self._push(_native.torch_module(), (x, counts, flags), valid)
+        self._form = 'dev'
+        return valid
+
+    def _push(self, torch, inputs, valid):
+        ctx, device, state, state_bytes = self._device(torch, inputs)
+        x, counts, flags = inputs
+        valid = self._valid if valid is None else valid
+        _scan_native.haas_scan_voice_stream_push_device(
+            ctx, state.data_ptr(), state_bytes, self.max_frames_per_call, self.window_frames, x.data_ptr(),
+            self.in_channels, counts.data_ptr(), flags.data_ptr(), valid.data_ptr(), self.slots,
+            stream=torch.cuda.current_stream(device).cuda_stream)
+        return valid
+
+    def _call_host(self, x, counts, flags, rows: bool = False):
+        """One upload (the blocks and the two int32 arrays in one buffer), the push, one download (``valid``)."""
+        torch = _native.torch_module()
+        ctx = _native.default_context()
+        device = torch.device('cuda', ctx.device)
+        ints = np.stack([counts, flags]).astype(np.int32)
+        up = torch.from_numpy(np.concatenate([x.reshape(-1).view(np.uint8), ints.reshape(-1).view(np.uint8)])).to(device)
+        self.transfers = {'to_device': 1, 'to_host': 0}
+        x_dev = up[:x.nbytes].view(torch.float32).view(x.shape)
+        int_rows = up[x.nbytes:].view(torch.int32).view(2, self.slots)
+        valid = self._push(torch, (x_dev, int_rows[0], int_rows[1]), None).cpu().numpy()
+        self.transfers['to_host'] = 1
+        return None, valid
+
+    # ---- the scan ---------------------------------------------------------------------------
+    def pairs_dev(self, slot_idx, delays, *, out=None):
+        """The raw scan, enqueued on the current stream: ``slot_idx`` and ``delays``, int32 ``(P,)`` device tensors, name
+        P (slot, delay) pairs; returns their moments, float64 ``(P, 8)`` (``out=`` takes the caller's).  A pair whose slot
+        is outside the pool or whose delay is outside ``[0, max_delay]`` gets a row of NaN; no check reads device memory.
+        Pairs sorted by (slot, delay) run fastest; any order, duplicates and any split into calls give the same rows."""
+        torch = _native.torch_module()
+        for name, t in (('slot_idx', slot_idx), ('delays', delays)):
+            if not _native.is_torch(t) or not t.is_cuda or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+                raise ValueError(f'{name} must be a contiguous int32 device tensor of shape (P,)')
+        count = int(slot_idx.shape[0])
+        if count < 1 or int(delays.shape[0]) != count:
+            raise ValueError(f'slot_idx and delays name the same P >= 1 pairs, got {tuple(slot_idx.shape)} and '
+                             f'{tuple(delays.shape)}')
+        if count > _native.HAAS_PAIRS_MAX:
+            raise ValueError(f'{count} pairs, a call takes {_native.HAAS_PAIRS_MAX}: split them')
+        if out is not None:
+            _check_device_tensors((out,), (('out', (count, _native.MOMENTS), 'float64', None),))
+        ctx, device, state, state_bytes = self._device(torch, (slot_idx, delays) + (() if out is None else (out,)))
+        if out is None:
+            out = torch.empty((count, _native.MOMENTS), dtype=torch.float64, device=device)
+        need = count * self.chunks_per_pair * 64
+        if self._workspace is None or self._workspace.numel() * 8 < need:
+            self._workspace = torch.empty((need // 8,), dtype=torch.float64, device=device)
+        _scan_native.haas_scan_voice_stream_pairs_device(
+            ctx, state.data_ptr(), state_bytes, self.max_frames_per_call, self.window_frames, self.in_channels, self.slots,
+            slot_idx.data_ptr(), delays.data_ptr(), count, out.data_ptr(), max_delay=self.max_delay,
+            delayed_channel=self.delayed_channel, ms_mode=self.ms_mode, width=self.width,
+            workspace_ptr=self._workspace.data_ptr(), workspace_bytes=self._workspace.numel() * 8,
+            stream=torch.cuda.current_stream(device).cuda_stream)
+        return out
+
+    def scan_dev(self, delays):
+        """Every slot against one grid of delays, enqueued on the current stream: ``delays``, an int32 ``(D,)`` device
+        tensor shared by all slots (ascending runs fastest), gives ``moments``, float64 ``(slots, D, 8)`` on the device -
+        the pool's own tensor for this ``D`` at a fixed address: read it, do not write it.  The pair arrays of the full
+        grid are built once per ``D`` and kept on the device, sorted by (slot, delay); the first call for a ``D``
+        allocates them, so make it before a capture."""
+        torch = _native.torch_module()
+        if not _native.is_torch(delays) or not delays.is_cuda or delays.dtype != torch.int32 or delays.dim() != 1 \
+                or not delays.is_contiguous() or delays.shape[0] < 1:
+            raise ValueError('delays must be a contiguous int32 device tensor of shape (D,), D >= 1')
+        D = int(delays.shape[0])
+        if self.slots * D > _native.HAAS_PAIRS_MAX:
+            raise ValueError(f'{self.slots} slots x {D} delays are more than the {_native.HAAS_PAIRS_MAX} pairs of a call: '
+                             'use pairs_dev on parts of the grid')
+        if D not in self._grids:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f'the pair arrays of a grid of {D} delays are allocated on first use: call scan_dev '
+                                   'once before the capture')
+            device = delays.device
+            self._grids[D] = (torch.arange(self.slots, dtype=torch.int32, device=device).repeat_interleave(D),
+                              torch.empty((self.slots, D), dtype=torch.int32, device=device),
+                              torch.empty((self.slots, D, _native.MOMENTS), dtype=torch.float64, device=device))
+            need = self.slots * D * self.chunks_per_pair * 64
+            if self._workspace is None or self._workspace.numel() * 8 < need:
+                self._workspace = torch.empty((need // 8,), dtype=torch.float64, device=device)
+        slot_idx, tiled, moments = self._grids[D]
+        tiled.copy_(delays.unsqueeze(0).expand(self.slots, D))
+        self.pairs_dev(slot_idx, tiled.view(-1), out=moments.view(-1, _native.MOMENTS))
+        return moments
+
+    def scan(self, delays) -> NDArray[np.float64]:
+        """The NumPy form of :meth:`scan_dev`: ``delays``, ``(D,)`` integers in ``[0, max_delay]``, up; float64
+        ``(slots, D, 8)`` moments down.  It reads the state only, so it goes with either form of the push."""
+        d = np.asarray(delays)
+        if d.ndim != 1 or not d.size or d.dtype.kind not in 'iu' or d.min() < 0 or d.max() > self.max_delay:
+            raise ValueError(f'delays: (D,) integers in [0, {self.max_delay}], D >= 1')
+        torch = _native.torch_module()
+        device = torch.device('cuda', _native.default_context().device)
+        return self.scan_dev(torch.from_numpy(d.astype(np.int32)).to(device)).cpu().numpy()
+
+    def scores(self, moments, *, angle_limit: float = np.pi / 4, lambda_mean: float = 5.0, lambda_skew: float = 2.0,
+               lambda_correlation: float = 15.0, lambda_penalty: float = 1e3):
+        """``symmetry_aware_objective`` of every row of ``(..., 8)`` moments; lower is better.  NumPy in, NumPy out:
+        :func:`scores_from_moments`.  A device tensor in, a device float64 tensor out - the same float64 operations in
+        torch, enqueued on the current stream - so ``delays[pool.scores(moments).argmin(-1)]`` is the device int32
+        ``(slots,)`` tensor a :class:`~vndecorrelate_amd.streaming.HaasFadeVoicePool` takes as its ``delays``."""
+        if not _native.is_torch(moments):
+            m = np.asarray(moments, np.float64)
+            if m.shape[-1:] != (_native.MOMENTS,):
+                raise ValueError(f'moments of shape (..., 8), got {m.shape}')
+            return scores_from_moments(m.reshape(-1, _native.MOMENTS), angle_limit=angle_limit, lambda_mean=lambda_mean,
+                                       lambda_skew=lambda_skew, lambda_correlation=lambda_correlation,
+                                       lambda_penalty=lambda_penalty).reshape(m.shape[:-1])
+        torch = _native.torch_module()
+        if moments.dtype != torch.float64 or tuple(moments.shape[-1:]) != (_native.MOMENTS,):
+            raise ValueError(f'moments: a float64 tensor of shape (..., 8), got {moments.dtype} {tuple(moments.shape)}')
+        s0, s1, s2, s3, tmax, lr, ll = (moments[..., k] for k in range(7))
+        total = s0 + EPSILON
+        spread = s2 / total
+        skew = (s3 / total) / (torch.clamp(spread, min=EPSILON) ** 1.5)
+        correlation = lr / (torch.sqrt(ll) + EPSILON) ** 2
+        exceedance = torch.clamp(tmax - angle_limit, min=0.0)
+        objective = (spread - lambda_mean * (s1 / total) ** 2 - lambda_skew * skew ** 2
+                     - lambda_correlation * correlation ** 2 - lambda_penalty * exceedance ** 2)
+        return -objective
+
+    def optimize(self, slots=None, *, grid_size: int = 400, angle_limit: float = np.pi / 4, lambda_mean: float = 5.0,
+                 lambda_skew: float = 2.0, lambda_correlation: float = 15.0,
+                 lambda_penalty: float = 1e3) -> NDArray[np.float64]:
+        """:func:`optimize_haas_delay_batched` for the windows of ``slots`` (default: every slot): ``(len(slots),)``
+        float64 delays in seconds.  It is :func:`haas_search` - the grid of ``grid_size`` taus up to the pool's
+        ``max_delay_seconds``, the local minima, their lockstep refinement - with a scorer over the rings: pairs go up,
+        moments come down, one pairs launch per round (more only past the workspace budget).  A pair's moments are the
+        one-shot's for the slot's window bit for bit, so the result is what :func:`optimize_haas_delay_batched` returns
+        on the device route for the same windows.  The optimiser's own configuration only: LR, ``delayed_channel=0``, no
+        width, on a pool built with ``sample_rate_hz`` and ``max_delay_seconds``; anything else raises ``ValueError``
+        before any device call."""
+        if self.ms_mode or self.delayed_channel != 0 or self.width is not None:
+            raise ValueError("optimize searches HaasEffect(mode='LR', delayed_channel=0, width=None) as optimize_haas_delay "
+                             f'does: this pool scans ms_mode={self.ms_mode}, delayed_channel={self.delayed_channel}, '
+                             f'width={self.width!r}')
+        if self.sample_rate_hz is None or self.max_delay_seconds is None:
+            raise ValueError('optimize needs the pool built with sample_rate_hz and max_delay_seconds')
+        chosen = list(range(self.slots)) if slots is None else [self._slot(s, 'optimize') for s in slots]
+        if isinstance(grid_size, (bool, np.bool_)) or not isinstance(grid_size, (int, np.integer)) or grid_size < 1:
+            raise ValueError(f'grid_size must be a positive integer, not {grid_size!r}')
+        if not chosen:
+            return np.zeros(0, np.float64)
+        weights = dict(angle_limit=angle_limit, lambda_mean=lambda_mean, lambda_skew=lambda_skew,
+                       lambda_correlation=lambda_correlation, lambda_penalty=lambda_penalty)
+        torch = _native.torch_module()
+        device = torch.device('cuda', _native.default_context().device)
+        slot_of = np.asarray(chosen, np.int64)
+        per_launch = max(1, min(_HAAS_SCAN_BYTES // (self.chunks_per_pair * 64), _native.HAAS_PAIRS_MAX))
+
+        def score(signals, delays):
+            rows = []
+            for first in range(0, delays.size, per_launch):               # launches bounded by their workspace
+                pairs = np.stack([slot_of[signals[first:first + per_launch]], delays[first:first + per_launch]])
+                up = torch.from_numpy(pairs.astype(np.int32)).to(device)
+                rows.append(self.pairs_dev(up[0], up[1]).cpu().numpy())
+            moments = np.concatenate(rows) if rows else np.zeros((0, _native.MOMENTS))
+            return scores_from_moments(moments, **weights)
+
+        self.last_search = HaasSearchStats(route='voice pool', signals=len(chosen))
+        taus = np.linspace(0.0, self.max_delay_seconds, grid_size)
+        return haas_search(score, len(chosen), taus, self.sample_rate_hz, grid_size, self.last_search)
+
+    # ---- the device -------------------------------------------------------------------------
+    def _device(self, torch, tensors):
+        """``(ctx, device, state, state_bytes)`` after the look at where the tensors live."""
+        ctx = _native.default_context()
+        device = torch.device('cuda', ctx.device)
+        for t in tensors:
+            if t.device != device:
+                raise ValueError(f'tensor on {t.device}, the pool runs on {device}')
+        state, state_bytes = self._ensure_state(torch, ctx)
+        return ctx, device, state, state_bytes
+
+    def _state_bytes(self, ctx) -> int:
+        return _scan_native.haas_scan_voice_stream_state_bytes(self.slots, self.max_frames_per_call, self.window_frames,
+                                                               self.in_channels)
+
+    def _allocate(self, torch, ctx):
+        _SlotPool._allocate(self, torch, ctx)
+        self._valid = torch.zeros((self.slots,), dtype=torch.int32, device=torch.device('cuda', ctx.device))
+
+    def _reset_entry(self, ctx, state_ptr, state_bytes, stream):
+        _scan_native.haas_scan_voice_stream_reset_device(ctx, state_ptr, state_bytes, self.slots, self.max_frames_per_call,
+                                                         self.window_frames, self.in_channels, stream=stream)
+
+
+def haas_scan_voice_pool(slots: int, *, in_channels: int, max_frames_per_call: int, window_frames: int,
+                         max_delay_seconds, sample_rate_hz, delayed_channel: int = 0, mode=LayoutMode.LR,
+                         width: Optional[float] = None) -> HaasScanVoicePool:
+    """A :class:`HaasScanVoicePool`: the last ``window_frames`` input frames (at least ``max_frames_per_call``) of
+    ``slots`` mono or stereo voices that start, end and push blocks on their own, kept on the device, and the Haas-delay
+    scan over them for delays up to ``round(max_delay_seconds * sample_rate_hz)`` frames (ties to even, as
+    ``HaasEffect`` rounds) under the one configuration ``delayed_channel``, ``mode``, ``width``.  There is no host loop:
+    whatever the pool does not cover raises ``ValueError`` here."""
+    if mode == LayoutMode.MS:
+        ms = True
+    elif mode == LayoutMode.LR:
+        ms = False
+    else:
+        raise ValueError(f"mode must be 'MS' or 'LR', not {mode!r}")
+    if not (np.isfinite(float(sample_rate_hz)) and float(sample_rate_hz) > 0 and np.isfinite(float(max_delay_seconds))
+            and float(max_delay_seconds) >= 0):
+        raise ValueError(f'sample_rate_hz must be positive and max_delay_seconds non-negative, got {sample_rate_hz!r} '
+                         f'and {max_delay_seconds!r}')
+    max_delay = int(haas_delays(max_delay_seconds, sample_rate_hz))
+    return HaasScanVoicePool(slots, in_channels=in_channels, max_frames_per_call=max_frames_per_call,
+                             window_frames=window_frames, max_delay=max_delay, sample_rate_hz=sample_rate_hz,
+                             max_delay_seconds=max_delay_seconds, delayed_channel=delayed_channel, ms_mode=ms, width=width)
 
 
 def optimize_velvet_noise(*, input_signal: NDArray, sample_rate_hz: int, duration_seconds: float,
